@@ -9,10 +9,17 @@ positives + negatives, every one of which goes through forward+backward+update (
 
     python bench.py --gpus N --steps K --warmup W            (N>1: launched by torch.distributed.run)
     python bench.py --layout c5 --dim 256 --ks 2,3,4,5,6,7,8 --rows 16384 --edges 100000000     (BASELINE configs[4])
+    python bench.py --full                                   (adds the figures listed under --full below)
+    python bench.py --dump-outputs DIR                       (the last timed step's outputs as DIR/<name>.npy)
 
+A plain run sets up, warms up, times exactly --steps steps and prints the line; everything else it can measure is behind --full.
 Prints ONE JSON line on rank 0:
   value / ms_per_step   the headline workload (configs[2]: hg38 1 Mb, mixed k in {2..5}, d = 64, table front end)
-  roofline              the dominant kernel class, timed live with HIP events on the launch stream inside the timed region
+--full adds:
+  roofline              the dominant kernel class, timed live with HIP events on the launch stream inside the timed region (every class
+                        over two untimed steps first: kernel_class_ms_per_step, roofline_by_kernel_class)
+  model_step_only       the model step alone on the last batch, timed after the timed region
+  collectives           (N > 1 or a torchrun launch) HIP events around every collective of the timed steps
   roofline_gather       (N = 1) the embedding-row gather alone on 1 M x 64, 16 M x 64 and 1 M x 256 tables with uniform ids, timed
                         live the same way: achieved = rows * (4 d + 8) / t against the 8 TB/s HBM-read roof (north_star target 40 %)
   extra_points          (N = 1, default run only) the other workloads the survey names, each a short run of the same step: adj front
@@ -66,10 +73,13 @@ METRIC = "training hyperedges/sec at k∈{2..5}, embed_dim=64; 1/2/4/8 MI355X"
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (per window)")
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--windows", type=int, default=7, help="timed windows of --steps steps each; ms_per_step / value are the MEDIAN window "
+    ap.add_argument("--windows", type=int, default=1, help="timed windows of --steps steps each; ms_per_step / value are the MEDIAN window "
                                                              "(min and max are reported beside it)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: kernel-class profile and roofline, "
+                                                        "model step alone, per-collective times, gather rooflines, extra workloads, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--rows", type=int, default=65536, help="rows (positives+negatives) per GPU per step")
     ap.add_argument("--front-end", choices=["table", "adj"], default="table")
     ap.add_argument("--layout", default="hg38_1mb", help="hg38_1mb | hg38_100kb | c1 | c5 (matcha_amd/synth.py LAYOUTS)")
@@ -77,9 +87,10 @@ def parse():
     ap.add_argument("--ks", default="2,3,4,5")
     ap.add_argument("--edges-per-k", type=int, default=100000)
     ap.add_argument("--edges", type=int, default=0, help="layout c5: total number of known hyperedges (default 100 M), built on the device")
-    ap.add_argument("--prof", default="auto", help="kernel class for the live roofline (see matcha_amd/_lib.py PROF) or 'none'")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip roofline_gather and extra_points (profiling runs)")
+    ap.add_argument("--prof", help="kernel class for the live roofline (see matcha_amd/_lib.py PROF), 'auto' or 'none' "
+                                   "(default: auto with --full, none without)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full without roofline_gather and extra_points (profiling runs)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--graph", action="store_true", help="replay the step from a hipGraph (single GPU)")
     ap.add_argument("--table-exchange", choices=["auto", "dense", "sparse"], default="auto")
@@ -209,8 +220,9 @@ class Dist:
 
 
 def run_workload(dist, *, layout, dim, ks, rows, front_end, steps, warmup, prof="auto", graph=False, edges_per_k=100000, edges=0,
-                 table_exchange="auto", model_only=True, deterministic=False, zipf=False, windows=1):
-    """Build the workload on the device, run `warmup` untimed + `steps` timed steps, return the measurements."""
+                 table_exchange="auto", model_only=True, deterministic=False, zipf=False, windows=1, time_collectives=False, dump=False):
+    """Build the workload on the device, run `warmup` untimed + `steps` timed steps, return the measurements (and with `dump`, the
+    last timed step's outputs on the host)."""
     from matcha_amd.engine import Trainer
     from matcha_amd.sampler import HyperedgeSet, NegativeSampler
     device, world, rank = dist.device, dist.world, dist.rank
@@ -256,7 +268,7 @@ def run_workload(dist, *, layout, dim, ks, rows, front_end, steps, warmup, prof=
     clf.train()                                                           # dropout ON, as in the reference's training step
     trainer = Trainer(clf, lr=1e-3, base_seed=99, table_exchange=table_exchange, deterministic=deterministic)
     trainer.force_collectives = dist.launched and world == 1       # 1-rank torchrun: still go through RCCL
-    trainer.time_collectives = world > 1 or dist.launched           # HIP events around every collective: the first multi-GPU run diagnoses itself
+    trainer.time_collectives = time_collectives and (world > 1 or dist.launched)     # HIP events around every collective: the first multi-GPU run diagnoses itself
 
     x = torch.zeros((B, L), dtype=torch.long, device=device)
     y = torch.cat([torch.ones(P, device=device), torch.zeros(B - P, device=device)])      # main.py:444-445
@@ -268,6 +280,7 @@ def run_workload(dist, *, layout, dim, ks, rows, front_end, steps, warmup, prof=
 
     step_no = torch.zeros(1, dtype=torch.long, device=device)
     lib_ = _lib.load()
+    last = {}         # the step's outputs (bce, recon, logits): views of the trainer's buffers, rewritten by every step or graph replay
 
     def one_step():
         rc = int(chrom_rng.integers(n_chrom)) if front_end == "adj" else 0
@@ -277,7 +290,8 @@ def run_workload(dist, *, layout, dim, ks, rows, front_end, steps, warmup, prof=
             x[:P] = synth.csr_to_padded(csr_off, csr_ids, L, idx)
             torch.index_select(shard_w, 0, idx, out=w[:P])
             sampler.sample_into(x[:P], x[P:])
-            return trainer.step(x, y, w, alpha=1.0, beta=0.001, random_chrom=rc)     # phase-2 weighting (main.py:672-673)
+            last["out"] = trainer.step(x, y, w, alpha=1.0, beta=0.001, random_chrom=rc)     # phase-2 weighting (main.py:672-673)
+            return last["out"]
         # the next P positives (wrapping around the shard), their weights and both RNG seeds + 1 in one launch: what matcha_amd.train's
         # captured step does (matcha_step_select, main.py:160-161)
         st_ = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
@@ -287,7 +301,8 @@ def run_workload(dist, *, layout, dim, ks, rows, front_end, steps, warmup, prof=
         sampler.sample_into(x[:P], x[P:], advance_seed=False)
         trainer.seed_advanced_by_caller = True
         try:
-            return trainer.step(x, y, w, alpha=1.0, beta=0.001, random_chrom=rc)     # phase-2 weighting (main.py:672-673)
+            last["out"] = trainer.step(x, y, w, alpha=1.0, beta=0.001, random_chrom=rc)     # phase-2 weighting (main.py:672-673)
+            return last["out"]
         finally:
             trainer.seed_advanced_by_caller = False
 
@@ -348,6 +363,7 @@ def run_workload(dist, *, layout, dim, ks, rows, front_end, steps, warmup, prof=
         win.append(dt)
     elapsed = float(np.median(win))
     steps_timed = steps * len(win)
+    outputs = step_outputs(last["out"], x, w, trainer.rt.flat) if dump else None
     roof = None
     if prof_cls != "none":
         ms, n, wk = C.c_double(), C.c_int64(), C.c_double()
@@ -423,7 +439,7 @@ def run_workload(dist, *, layout, dim, ks, rows, front_end, steps, warmup, prof=
     losses = trainer.losses.cpu().tolist()
     # every MFMA- / HBM-bound kernel class against its roofline, from the same two-step measurement that picked the dominant one
     # (work scaled from the launch bound to the real tokens like `roofline`; the sampler's and AdamW's work is exact)
-    fill_all = (float((x != 0).sum().item()) + 1.0) / (B * L + 1.0)
+    fill_all = (float((x != 0).sum().item()) + 1.0) / (B * L + 1.0) if class_ms else 1.0
     roof_all = {}
     for name, ms_step in class_ms.items():
         wpl, lps = class_work[name]
@@ -454,11 +470,40 @@ def run_workload(dist, *, layout, dim, ks, rows, front_end, steps, warmup, prof=
     out = dict(B=B, P=P, L=L, N=N, elapsed=elapsed, windows=win, roof=roof, roof_all=roof_all, class_ms=class_ms, model_only_ms=model_only_ms, losses=losses,
                pool=pool, wts=None if pool is None else wts, num=num, known_edges=workload_edges, sparse_exchange=bool(trainer._sparse),
                exhausted_negatives=exhausted, comm_bytes=dict(trainer.comm_bytes), overlap=bool(trainer._side is not None and trainer._overlap()),
-               collectives=coll)
+               collectives=coll, outputs=outputs)
     del trainer, clf, sampler, hset, pool_all
     gc.collect()
     torch.cuda.empty_cache()
     return out
+
+
+DUMP_BYTES_PER_ARRAY = 12 << 20     # --dump-outputs: at most 12 MiB per array (four arrays can reach it: < 64 MiB in all)
+
+
+def fixed_sample(t, dtype):
+    """`t` as a host array of `dtype`; above DUMP_BYTES_PER_ARRAY, its rows at a fixed seeded, sorted index sample (the same for every
+    run and build with the same arguments)."""
+    row_bytes = np.dtype(dtype).itemsize * max(1, t[0].numel() if t.dim() > 1 else 1)
+    cap = DUMP_BYTES_PER_ARRAY // row_bytes
+    if t.shape[0] > cap:
+        idx = np.sort(np.random.default_rng(0).choice(t.shape[0], size=cap, replace=False))
+        t = t[torch.from_numpy(idx).to(t.device)]
+    return t.detach().cpu().numpy().astype(dtype)
+
+
+def step_outputs(out, x, w, params):
+    """What a caller of the timed step receives, copied to the host after the timed region: the step's (bce, recon, logits), the batch it
+    built (the selected positives and the sampled negatives as node ids, their weights) and the parameters after its AdamW update."""
+    bce, recon, logits = out
+    return {"bce": fixed_sample(bce.reshape(1), np.float32), "recon": fixed_sample(recon.reshape(-1), np.float32),
+            "logits": fixed_sample(logits, np.float32), "batch_ids": fixed_sample(x, np.float64),
+            "batch_weights": fixed_sample(w, np.float32), "params": fixed_sample(params, np.float32)}
+
+
+def write_outputs(outputs, out_dir):
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def gather_roofline(device):
@@ -612,6 +657,8 @@ def front_gather_roofline(device):
 
 def main():
     args = parse()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(self_launch(args))
     dist = Dist()
@@ -631,8 +678,11 @@ def main():
     ks = [int(v) for v in args.ks.split(",")]
 
     m = run_workload(dist, layout=args.layout, dim=args.dim, ks=ks, rows=args.rows, front_end=args.front_end, steps=args.steps,
-                     warmup=args.warmup, prof=args.prof, graph=args.graph, edges_per_k=args.edges_per_k, edges=args.edges,
-                     table_exchange=args.table_exchange, deterministic=args.deterministic, zipf=args.zipf, windows=args.windows)
+                     warmup=args.warmup, prof=args.prof or ("auto" if args.full else "none"), graph=args.graph, edges_per_k=args.edges_per_k,
+                     edges=args.edges, table_exchange=args.table_exchange, deterministic=args.deterministic, zipf=args.zipf, windows=args.windows,
+                     model_only=args.full, time_collectives=args.full, dump=bool(args.dump_outputs) and rank == 0)
+    if m["outputs"] is not None:
+        write_outputs(m["outputs"], args.dump_outputs)
     B, P, L, N = m["B"], m["P"], m["L"], m["N"]
     elapsed = m["elapsed"]
     result = {
@@ -666,7 +716,7 @@ def main():
         "csrc_sha16": csrc_sha16(),
     }
     default_run = (args.layout, args.dim, args.front_end, args.rows, args.ks) == ("hg38_1mb", 64, "table", 65536, "2,3,4,5")
-    if rank == 0 and world == 1 and not args.no_extras and not args.graph:
+    if args.full and rank == 0 and world == 1 and not args.no_extras and not args.graph:
         result["roofline_gather"] = gather_roofline(dist.device)
         result["roofline_gather_in_step"] = front_gather_roofline(dist.device)
         if default_run:
@@ -725,7 +775,7 @@ def main():
             except Exception as exc:      # the driver flow is an extra: never lose the headline line over it
                 extras["train_driver_epoch"] = {"error": repr(exc)[:200]}
             result["extra_points"] = extras
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and m["pool"] is not None:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and m["pool"] is not None:
         result["cpu_baseline"] = cpu_baseline(args, m["num"], ks, L, m["pool"], m["wts"], 3)
     if rank == 0:
         print(json.dumps(result, ensure_ascii=False))

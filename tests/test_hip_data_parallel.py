@@ -352,7 +352,7 @@ def test_bench_multi_rank_path_two_ranks_on_one_gpu(tmp_path):
     env = dict(os.environ, MATCHA_DIST_BACKEND="gloo", MATCHA_LOCAL_DEVICE="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--rows", "8192", "--edges-per-k", "20000"]
+           "--rows", "8192", "--edges-per-k", "20000", "--full"]
     run = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600, cwd=str(tmp_path))
     assert run.returncode == 0, run.stderr[-2000:]
     line = [l for l in run.stdout.splitlines() if l.startswith("{")][-1]

@@ -11,7 +11,7 @@ for lib in matcha_amd/lib/abl/*.so; do
 import json,sys
 d=json.loads(sys.stdin.read()); print('$name', d['kernel'], 'avg_launch_ms', d['avg_launch_ms'], 'frac', d['frac'])" | tee -a $LOG
   fi
-  MATCHA_HIP_LIB=$(pwd)/$lib python bench.py --no-extras --no-cpu-baseline ${BENCH_ARGS:-} 2>/dev/null | tail -1 | python -c "
+  MATCHA_HIP_LIB=$(pwd)/$lib python bench.py --full --windows 7 --no-extras --no-cpu-baseline ${BENCH_ARGS:-} 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('$name', 'step', d['ms_per_step'], d['kernel_class_ms_per_step'])" | tee -a $LOG
 done

@@ -31,7 +31,7 @@ run)
   mkdir -p gpurun_out; LOG=gpurun_out/abl_fwd32.log; : > $LOG
   for lib in $LIBOUT/*.so; do
     name=$(basename $lib .so); name=${name#libmatcha_hip_}
-    MATCHA_HIP_LIB=$(pwd)/$lib python bench.py --no-extras --no-cpu-baseline --steps ${ABL_STEPS:-20} --warmup 5 ${ABL_BENCH_ARGS:-} 2>/dev/null | tail -1 | python -c "
+    MATCHA_HIP_LIB=$(pwd)/$lib python bench.py --full --windows 7 --no-extras --no-cpu-baseline --steps ${ABL_STEPS:-20} --warmup 5 ${ABL_BENCH_ARGS:-} 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); c=d['roofline_by_kernel_class']
 print('$name', 'fused_fwd', round(c['fused_fwd']['ms_per_step'],4), 'fused_bwd', round(c['fused_bwd']['ms_per_step'],4), 'step', round(d['ms_per_step'],4))" | tee -a $LOG

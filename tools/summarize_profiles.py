@@ -23,7 +23,7 @@ rows = list(csv.DictReader(open(src)))
 with open(f"profiles/{rnd}_kernel_stats.md", "w") as f:
     f.write(f"# rocprofv3 --kernel-trace --stats ({rnd})\n\n")
     f.write("Command (on the MI355X box): `rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --steps 20 --warmup 5 "
-            "--prof none --no-cpu-baseline --no-extras`\n(65536 rows per step; calls = 5 warm-up + 7 windows x 20 timed steps; hg38-1Mb, table front end, d=64, L=5; raw CSV next to this file)\n\n")
+            "--prof none --no-cpu-baseline --no-extras`\n(65536 rows per step; calls = 5 warm-up + 20 timed steps; hg38-1Mb, table front end, d=64, L=5; raw CSV next to this file)\n\n")
     f.write("| kernel | calls | total ms | avg us | % |\n|---|---:|---:|---:|---:|\n")
     for r in rows[:26]:
         f.write(f"| `{r['Name'][:90]}` | {r['Calls']} | {float(r['TotalDurationNs'])/1e6:.3f} | {float(r['AverageNs'])/1e3:.1f} | {float(r['Percentage']):.1f} |\n")

@@ -3,7 +3,7 @@ import json
 import subprocess
 import sys
 
-out = subprocess.run([sys.executable, "bench.py", "--steps", "8", "--warmup", "3", "--no-cpu-baseline"] + sys.argv[1:],
+out = subprocess.run([sys.executable, "bench.py", "--full", "--windows", "7", "--steps", "8", "--warmup", "3", "--no-cpu-baseline"] + sys.argv[1:],
                      capture_output=True, text=True).stdout.strip().splitlines()
 if not out:
     raise SystemExit("bench.py produced no output")
