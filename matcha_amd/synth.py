@@ -27,6 +27,9 @@ LAYOUTS = {
     "hg38_1mb": HG38_1MB,              # configs[1], configs[2]: N = 3067
     "hg38_100kb": HG38_100KB,          # configs[3]: N ~ 30.4 k
     "c5": [50000] * 20,                # configs[4]: 1 M nodes (20 synthetic chromosomes of 50 000 bins; table front end only)
+    # adj blocks around and over 256 bins (the fused kernels' column groups of 256 / chunks of 64; 2 491 = hg38 100 kb chr1) + one block of
+    # exactly 64; seven chromosomes, because the fused embed_dim-64 adj path needs n_attr = C + 1 to be a multiple of 4: N = 4 156
+    "wide_adj": [255, 256, 320, 257, 513, 2491, 64],
 }
 
 

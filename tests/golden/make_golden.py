@@ -644,19 +644,28 @@ def round4(M):
     g3_long(M, "c23_adj_d64", synth.LAYOUTS["c23"], 64, "adj", 49)
 
 
-def g3_big(M, name, num, d, mode, seed, ks, rows_per_k, n_eval=64):
+def g3_big(M, name, num, d, mode, seed, ks, rows_per_k, n_eval=64, adj_stride=0, expect_chroms=None, cap=32768):
     """Round 6 fixture g3big_*: ONE dropout-free training step of the real reference on a batch large enough for the kernels the
     library picks at bench sizes (d = 64: more than 512 half tiles -> fused_fwd32_kernel + tail_bwd64_kernel + fused_bwdh_kernel on a
     full grid; d = 128: enc128 at thousands of rows; d = 256 / k up to 8: the wide layer-wise kernels and the ML = 8 instances).
     Stored: the batch (node ids in the narrowest integer type), logits, losses, every gradient tensor -- in full up to 32 768
     elements, every s-th element above (key grad0s<s>/name) --, which tensors have grad None, and eval-mode logits of the first
-    `n_eval` rows evaluated as their own batch at the same width L (the forward-only kernels; Modules.py:278-318)."""
+    `n_eval` rows evaluated as their own batch at the same width L (the forward-only kernels; Modules.py:278-318).
+    adj_stride (round 7): the adj tensors whose columns are the bins of a chromosome -- every `tied weight_0` [d, n_c] and the drawn
+    chromosome's recon head `FF_Linear0.weight` [n_r, d] -- are stored as every adj_stride-th element of the flattened tensor with a
+    stride coprime to the row length (asserted): the stored elements then walk every column of tied weight_0 (every row of the head)
+    about d / adj_stride times, so that every bin of a wide block is checked in a file of a few hundred KB; the head's bias is stored
+    in full.  `cap` (elements stored in full) may be lowered for the other tensors to keep the file small.
+    expect_chroms: (training step's chromosome, eval forward's chromosome) the fixture was designed around, asserted."""
     clf, attr, feats, inter_z, sd = build_ref(M, num, d, mode, seed)
     C, N = len(num), int(np.sum(num))
     set_dropout(clf, 0.0)
     clf.train()
     out = {}
     chrom = predraw_chroms(C, 1, 4321)
+    if expect_chroms is not None:
+        assert chrom[0] == expect_chroms[0] and predraw_chroms(C, 1, 7)[0] == expect_chroms[1], (chrom, predraw_chroms(C, 1, 7))
+        np.random.seed(4321)           # predraw_chroms leaves the seed where the forward expects it; the eval draw above moved it
     out["chroms"] = np.asarray(chrom, dtype=np.int64)
     x, y, w = synth.make_batch(np.random.default_rng(seed + 5), N, list(ks), rows_per_k)
     out["x0"] = x.astype(np.int16 if N < 32767 else np.int32)
@@ -671,7 +680,13 @@ def g3_big(M, name, num, d, mode, seed, ks, rows_per_k, n_eval=64):
             none.append(n_)
             continue
         gnp = p.grad.numpy().reshape(-1)
-        stride = -(-gnp.size // 32768)
+        stride = -(-gnp.size // cap)
+        if adj_stride and ("tied weight_0" in n_ or ".FF_Linear0.weight" in n_):
+            rows, row_len = p.grad.shape
+            assert math.gcd(adj_stride, row_len) == 1 and adj_stride <= rows, (n_, adj_stride, p.grad.shape)
+            stride = adj_stride
+        elif adj_stride and ".FF_Linear0.bias" in n_:
+            stride = 1
         if stride == 1:
             out["grad0/" + n_] = p.grad.numpy().copy()
         else:
@@ -818,6 +833,19 @@ def round6(M, U):
     sampler_stats_c3(M, U)
 
 
+def round7(M):
+    """Wide adj blocks: chromosomes of 255 / 256 / 320 / 257 / 513 / 2 491 / 64 bins (synth.LAYOUTS["wide_adj"]) -- one column under, at
+    and over the fused kernels' 256-column groups, whole 64-column chunks with a partial second group, two groups and a 1-column tail,
+    hg38 100 kb chr1, and one whole chunk (the seventh chromosome makes n_attr = 8: the fused adj path needs a multiple of 4).  The
+    training step reconstructs chromosome 5 (2 491 bins), the eval forward chromosome 4 (513)."""
+    K5 = (2, 3, 4, 5)
+    num = synth.LAYOUTS["wide_adj"]
+    # 9 216 rows: fused_fwd32 + the fused adj kernels;  4 096 rows: enc128 + the layer-wise adj kernels.  Strides 7 and 13: coprime to every
+    # width of the layout and to d (about nine samples per column / head row)
+    g3_big(M, "wide_adj_d64_k5", num, 64, "adj", 71, K5, 2304, adj_stride=7, expect_chroms=(5, 4), cap=4096)
+    g3_big(M, "wide_adj_d128_k5", num, 128, "adj", 72, K5, 1024, adj_stride=13, expect_chroms=(5, 4), cap=4096)
+
+
 def main():
     torch.set_num_threads(4)
     M, U = import_reference()
@@ -826,6 +854,9 @@ def main():
         return
     if "--round6" in sys.argv:       # only the fixtures round 6 added
         round6(M, U)
+        return
+    if "--round7" in sys.argv:       # only the fixtures round 7 added
+        round7(M)
         return
     g1_g5(M)
     g2_eval(M, "tiny_adj", synth.LAYOUTS["tiny"], 16, "adj", 21)
@@ -850,6 +881,7 @@ def main():
     g9_process(M, U)
     round4(M)
     round6(M, U)
+    round7(M)
 
 
 if __name__ == "__main__":

@@ -493,6 +493,8 @@ G3BIG_KERNELS = {
     "c1_adj_d128_k5": ({"enc128_fwd_kernel", "enc128_bwd_kernel"}, {"attn_fwd_wide_kernel", "attn_bwd_wide_kernel"}),
     "c1_table_d128_k8": ({"enc128_fwd_kernel", "enc128_bwd_kernel"}, {"attn_fwd_wide_kernel", "attn_bwd_wide_kernel"}),
     "c1_table_d256_k8": ({"gemm_wide_kernel", "gemm_tn_wide_kernel", "attn_fwd_wide_kernel", "attn_bwd_wide_kernel"}, {"enc128_fwd_kernel", "fused_fwd32_kernel"}),
+    "wide_adj_d64_k5": (_BIG64[0] | {"adj_fused_fwd_kernel", "adj_recon_kernel", "adj_fused_bwd_kernel"}, _BIG64[1] | {"adj_encode_fwd_kernel"}),
+    "wide_adj_d128_k5": ({"enc128_fwd_kernel", "enc128_bwd_kernel", "adj_encode_fwd_kernel", "adj_tn_kernel<1>"}, {"adj_fused_fwd_kernel", "adj_fused_bwd_kernel"}),
 }
 
 
