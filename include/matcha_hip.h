@@ -255,6 +255,24 @@ int matcha_backward(const matcha_shape* shp, const matcha_tensors* params, const
                     matcha_tensors* grads, int32_t* touched,
                     void* ws, size_t ws_bytes, matcha_stream_t stream);
 
+/* The two training objectives of the reference (task_mode, main.py:532).  matcha_forward / matcha_backward are the BCE case. */
+#define MATCHA_OBJECTIVE_BCE 0          /* weighted BCE on the logits (main.py:56) */
+#define MATCHA_OBJECTIVE_SOFTPLUS_MSE 1 /* mse_loss(softplus(logits), y), an unweighted mean over the B rows (main.py:60-117) */
+
+/* matcha_forward / matcha_backward with the objective chosen per call; every other argument is theirs.  Under
+ * MATCHA_OBJECTIVE_SOFTPLUS_MSE `y` holds the regression targets, `w` is ignored (may be NULL), losses[0] is the MSE and
+ * the logit gradient is alpha * 2 (softplus(z) - y) softplus'(z) / B (torch's softplus: z > 20 ? z : log1p(exp(z))).
+ * An unknown objective returns MATCHA_EINVAL before any device call. */
+int matcha_forward_objective(int32_t objective, const matcha_shape* shp, const matcha_tensors* params, const matcha_frozen* frozen,
+                             const matcha_step_opts* opts, const int64_t* x, int64_t B, int32_t L,
+                             const float* y, const float* w, float* logits, float* losses,
+                             void* ws, size_t ws_bytes, matcha_stream_t stream);
+int matcha_backward_objective(int32_t objective, const matcha_shape* shp, const matcha_tensors* params, const matcha_frozen* frozen,
+                              const matcha_step_opts* opts, const int64_t* x, int64_t B, int32_t L,
+                              const float* y, const float* w, const float* dlogits, const float* drecon,
+                              matcha_tensors* grads, int32_t* touched,
+                              void* ws, size_t ws_bytes, matcha_stream_t stream);
+
 /* model.get_node_embeddings(x) (Modules.py:252-259), eval mode: rows float [T,d] for ids int64 [T].
  * `status`: optional device status word (ids outside [0, n_nodes] are flagged and read as id 0). */
 int matcha_node_embeddings(const matcha_shape* shp, const matcha_tensors* params, const matcha_frozen* frozen,
@@ -343,6 +361,17 @@ int matcha_step_select(const int64_t* pos, const float* w, int64_t n_rows, int32
                        matcha_stream_t stream);
 int matcha_step_record(const float* logits, const float* losses, const int64_t* x, int64_t B, int32_t L, int64_t* it, int64_t n_steps,
                        float* sums, float* preds, int64_t* sizes, matcha_stream_t stream);
+/* matcha_step_record_pairs: the regression counterpart of matcha_step_record (main.py:60-117): same counter, same loss sums, same
+ * past-the-end guard.  The B rows are paired by a bijection pi of [0, B) drawn from (seed[0], it) -- a 6-round Feistel network
+ * over the next even power of two with cycle walking (tests/test_cpu_regress.py restates it) -- and for every pair
+ * j < B/2 of rows r0 = pi(2j), r1 = pi(2j+1), with y the targets float [B]:
+ *   preds[it][j]  = sigmoid(softplus(logits[r0]) - softplus(logits[r1]))
+ *   labels[it][j] = y[r0] == y[r1] ? -1 (masked pair) : (y[r1] < y[r0] ? 1 : 0)      (torch.argmin of the pair)
+ *   sizes[it][j]  = non-zero entries of x[r0]
+ * preds / labels / sizes are [n_steps, B/2]. */
+int matcha_step_record_pairs(const float* logits, const float* losses, const float* y, const int64_t* x, int64_t B, int32_t L,
+                             int64_t* it, int64_t n_steps, const uint64_t* seed, float* sums, float* preds, int32_t* labels,
+                             int64_t* sizes, matcha_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Op-level entry points (the kernels behind matcha_forward/backward, exposed so that each one is

@@ -79,6 +79,10 @@ SIGNATURES = {
                                  _I32, _fp, _fp, _fp, _fp, _fp, _SZ, _fp]),
     "matcha_backward": (C.c_int, [C.POINTER(Shape), C.POINTER(Tensors), C.POINTER(Frozen), C.POINTER(StepOpts), _fp, _I64,
                                   _I32, _fp, _fp, _fp, _fp, C.POINTER(Tensors), _fp, _fp, _SZ, _fp]),
+    "matcha_forward_objective": (C.c_int, [_I32, C.POINTER(Shape), C.POINTER(Tensors), C.POINTER(Frozen), C.POINTER(StepOpts), _fp, _I64,
+                                           _I32, _fp, _fp, _fp, _fp, _fp, _SZ, _fp]),
+    "matcha_backward_objective": (C.c_int, [_I32, C.POINTER(Shape), C.POINTER(Tensors), C.POINTER(Frozen), C.POINTER(StepOpts), _fp, _I64,
+                                            _I32, _fp, _fp, _fp, _fp, C.POINTER(Tensors), _fp, _fp, _SZ, _fp]),
     "matcha_node_embeddings": (C.c_int, [C.POINTER(Shape), C.POINTER(Tensors), C.POINTER(Frozen), _fp, _I64, _fp, _fp, _SZ, _fp, _fp]),
     "matcha_get_embedding": (C.c_int, [C.POINTER(Shape), C.POINTER(Tensors), C.POINTER(Frozen), C.POINTER(StepOpts), _fp, _I64, _I32,
                                        _fp, _fp, _fp, _fp, _fp, _SZ, _fp]),
@@ -97,6 +101,7 @@ SIGNATURES = {
     "matcha_hashset_contains": (C.c_int, [_fp, _fp, _I32, _fp, _I64, _I32, _fp, _fp]),
     "matcha_step_select": (C.c_int, [_fp, _fp, _I64, _I32, _fp, _I32, _fp, _fp, _fp, _I64, _fp, _fp, _fp, _fp]),
     "matcha_step_record": (C.c_int, [_fp, _fp, _fp, _I64, _I32, _fp, _I64, _fp, _fp, _fp, _fp]),
+    "matcha_step_record_pairs": (C.c_int, [_fp, _fp, _fp, _fp, _I64, _I32, _fp, _I64, _fp, _fp, _fp, _fp, _fp, _fp]),
     "matcha_neg_sample": (C.c_int, [_fp, _fp, _I64, _I32, _fp, _I64, _I32, _I32, _I32, _fp, _I32, _fp, _I32, _fp, _fp, _fp, _fp]),
     "matcha_gemm_tn_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
     "matcha_gemm": (C.c_int, [_I32, _fp, _fp, _fp, _I64, _I64, _I64, C.POINTER(GemmEpilogue), _fp, _fp, _fp, _SZ, _fp]),
@@ -115,6 +120,9 @@ SIGNATURES = {
     "matcha_corrcoef_block": (C.c_int, [_fp, _I64, _I32, _fp, _fp, _SZ, _fp]),
     "matcha_zscore_rows": (C.c_int, [_fp, _I64, _I64, _fp]),
 }
+
+OBJECTIVE_BCE, OBJECTIVE_SOFTPLUS_MSE = 0, 1      # MATCHA_OBJECTIVE_* of include/matcha_hip.h
+OBJECTIVES = {"class": OBJECTIVE_BCE, "regress": OBJECTIVE_SOFTPLUS_MSE}      # the reference's task_mode (main.py:532)
 
 FEAT_ROW_PAD = 64           # adj front end: feature rows padded to this many floats (matcha_frozen.feat_row_pad)
 ABI_VERSION = 7             # MATCHA_ABI_VERSION of include/matcha_hip.h

@@ -288,6 +288,7 @@ struct Fwd32Args {
   const uint64_t* seed;
   float p_fc1, p_pff;
   float* ddyn0; float* dXs; float* tslab; float alpha_over_B;
+  int objective;      // MATCHA_OBJECTIVE_*: the per-hyperedge loss and its logit gradient (fused_fwd32_tail.hpp)
   float* qkv;         // training: the record per (half tile, head) -- this wavefront's own r rows + probabilities, kImgRecH floats (fused_bwdh_kernel)
   float* tail_dh2;    // single-wave kernel, training: [T][64] dH2 rows -- the tail's backward stops behind its LayerNorms, tail_bwd64_kernel does the convolutions
 };
@@ -675,7 +676,7 @@ int launch_prep_heads(const matcha_tensors& p, float* folded, float* merged, flo
 
 int launch_fused_fwd32(const matcha_tensors& p, const float* folded, const float* frag, const float* X, const Ragged& rg, int64_t B, int L, const float* y,
                        const float* w, float* Y, float* H1, float* H2, float* logits, float* row_loss, const uint64_t* seed, float p_fc1, float p_pff,
-                       hipStream_t st, float* ddyn0, float* dXs, float* tslab, float alpha, float* rimg, float* tail_dh2) {
+                       hipStream_t st, float* ddyn0, float* dXs, float* tslab, float alpha, float* rimg, float* tail_dh2, int objective) {
   Fwd32Args g;
   g.tail_dh2 = nullptr;
   g.X = X; g.row_off = rg.row_off; g.tok_slot = rg.tok_slot; g.count = rg.count; g.half_meta = rg.half_meta; g.tok_pos = rg.tok_pos;
@@ -683,9 +684,11 @@ int launch_fused_fwd32(const matcha_tensors& p, const float* folded, const float
   g.wfrag = reinterpret_cast<const u32x4*>(frag);
   (void)folded;
   g.hp = HeadParams{p.pff_ln_g, p.pff_ln_b, p.ln1_g, p.ln1_b, p.ln2_g, p.ln2_b, p.cls_w, p.cls_b};
-  g.y = y; g.w = w; g.Y = Y; g.H1 = H1; g.H2 = H2; g.logits = logits; g.row_loss = (y && w) ? row_loss : nullptr;
+  const bool target = objective == MATCHA_OBJECTIVE_SOFTPLUS_MSE ? y != nullptr : (y && w);
+  g.objective = objective;
+  g.y = y; g.w = w; g.Y = Y; g.H1 = H1; g.H2 = H2; g.logits = logits; g.row_loss = target ? row_loss : nullptr;
   g.seed = seed; g.p_fc1 = p_fc1; g.p_pff = p_pff;
-  g.ddyn0 = (y && w) ? ddyn0 : nullptr; g.dXs = dXs; g.tslab = tslab; g.alpha_over_B = alpha / (float)B; g.qkv = rimg;
+  g.ddyn0 = target ? ddyn0 : nullptr; g.dXs = dXs; g.tslab = tslab; g.alpha_over_B = alpha / (float)B; g.qkv = rimg;
   size_t lds = ((size_t)2 * kHT + 64) * sizeof(float);
   auto launch = [&](auto kfn) { hipLaunchKernelGGL(kfn, dim3(rg.nhalves), dim3(64), lds, st, g); };
   // algorithmic flops per token (the reference formulation's): 8 heads x 4 GEMMs (Q, K, V, fc1 block) + the two pff GEMMs, 2*64*64 each

@@ -121,14 +121,23 @@
     const int lo_g = g.row_off[b];
     const int lo = lo_g - t0, kk = g.row_off[b + 1] - lo_g;
     float yb = 0.f, wb = 0.f;
-    if (g.row_loss) { yb = g.y[b]; wb = g.w[b]; }
+    const bool mse = g.objective == MATCHA_OBJECTIVE_SOFTPLUS_MSE;      // wave-uniform (a launch parameter)
+    if (g.row_loss) { yb = g.y[b]; wb = mse ? 0.f : g.w[b]; }
     float tot = 0.f;
     for (int i = 0; i < kk; ++i) tot += outs[lo + i];
     const float z = tot / ((float)kk + 1e-15f);
     g.logits[b] = z;
-    if (g.row_loss) g.row_loss[b] = wb * (fmaxf(z, 0.f) - z * yb + log1pf(expf(-fabsf(z))));
-    if (g.ddyn0) {                                    // main.py:56 backward: d bce / d z = w (sigmoid(z) - y) / B  (x alpha, main.py:166)
-      const float dz = g.alpha_over_B * wb * (1.f / (1.f + expf(-z)) - yb);
+    float dz = 0.f;
+    if (mse) {                                        // main.py:87-90: (softplus(z) - y)^2; d / d z = 2 (softplus(z) - y) softplus'(z) / B  (x alpha)
+      const float big = z > 20.f ? 1.f : 0.f;         // torch's softplus threshold
+      const float err = (big != 0.f ? z : log1pf(expf(z))) - yb;
+      if (g.row_loss) g.row_loss[b] = err * err;
+      dz = g.alpha_over_B * 2.f * err * (big != 0.f ? 1.f : 1.f / (1.f + expf(-z)));
+    } else {
+      if (g.row_loss) g.row_loss[b] = wb * (fmaxf(z, 0.f) - z * yb + log1pf(expf(-fabsf(z))));
+      if (g.ddyn0) dz = g.alpha_over_B * wb * (1.f / (1.f + expf(-z)) - yb);     // main.py:56 backward: d bce / d z = w (sigmoid(z) - y) / B  (x alpha, main.py:166)
+    }
+    if (g.ddyn0) {
       const float dout = dz / ((float)kk + 1e-15f);
       for (int i = 0; i < kk; ++i) douts[lo + i] = dout;
     }

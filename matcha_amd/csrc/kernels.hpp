@@ -125,10 +125,11 @@ int launch_ln3_bwd(const float* X, const float* dqin, const float* dkin, const f
                    const float* gq, const float* gk, const float* gv, float* dZ0, float* slab, float* dgq, float* dbq,
                    float* dgk, float* dbk, float* dgv, float* dbv, hipStream_t st, const int32_t* t_dev = nullptr);
 int launch_head_fwd(const int32_t* row_off, const float* H2, const float* X, int64_t B, int L, int d, const HeadParams& hp,
-                    const float* y, const float* w, float* logits, float* row_loss, float* bce_out, hipStream_t st);
+                    const float* y, const float* w, float* logits, float* row_loss, float* bce_out, hipStream_t st,
+                    int objective = MATCHA_OBJECTIVE_BCE);
 int launch_head_bwd(const int32_t* row_off, const float* H2, const float* X, int64_t B, int L, int d, const HeadParams& hp,
                     const float* y, const float* w, const float* logits, const float* dlogits, float alpha, float* dH2,
-                    float* dXs, float* slab, const HeadParams& ghp, hipStream_t st);
+                    float* dXs, float* slab, const HeadParams& ghp, hipStream_t st, int objective = MATCHA_OBJECTIVE_BCE);
 size_t colsum_slab_bytes(int64_t n, int nv, int d);
 int launch_loss_reduce(const float* row_loss, int64_t B, float* bce_out, hipStream_t st, bool zero_recon = false,     // zero_recon: losses[1..2] = 0 too
                        float* zero_buf = nullptr, size_t zero_bytes = 0);                                               // a buffer zeroed by extra blocks of the launch
@@ -155,7 +156,7 @@ int launch_prep_heads(const matcha_tensors& p, float* folded, float* merged, flo
 int launch_fused_fwd32(const matcha_tensors& p, const float* folded, const float* frag, const float* X, const Ragged& rg, int64_t B, int L, const float* y,
                        const float* w, float* Y, float* H1, float* H2, float* logits, float* row_loss, const uint64_t* seed, float p_fc1, float p_pff,
                        hipStream_t st, float* ddyn0 = nullptr, float* dXs = nullptr, float* tslab = nullptr, float alpha = 0.f, float* rimg = nullptr,
-                       float* tail_dh2 = nullptr);       // tail_dh2 (large batches only): the convolutions' backward is left to launch_tail_bwd64
+                       float* tail_dh2 = nullptr, int objective = MATCHA_OBJECTIVE_BCE);       // tail_dh2 (large batches only): the convolutions' backward is left to launch_tail_bwd64
 // tail_bwd.hip: the backward of pff_n1's two convolutions as its own kernel behind fused_fwd32_kernel (large batches)
 int tail_bwd_grid();
 size_t tail_bwd_slab_floats();

@@ -155,8 +155,15 @@ static bool enc128_enabled(const matcha_shape& s, const matcha_step_opts& o) {
 }
 static bool fused_enabled(const matcha_shape& s) { return s.d == 64 && options().disable_fused != 1 && !options().disable_merged; }
 static bool fused_front_enabled() { return (options().disable_fused & 2) == 0; }
-static bool loss_in_forward(const matcha_shape& s, const matcha_step_opts& o, const float* y, const float* w) {
-  return o.loss_in_forward && !o.forward_only && y && w && fused_enabled(s);
+// the loss can be computed: BCE needs labels and weights, the softplus MSE only its targets
+static bool has_target(int objective, const float* y, const float* w) { return objective == MATCHA_OBJECTIVE_SOFTPLUS_MSE ? y != nullptr : (y && w); }
+static bool loss_in_forward(const matcha_shape& s, const matcha_step_opts& o, const float* y, const float* w, int objective) {
+  return o.loss_in_forward && !o.forward_only && has_target(objective, y, w) && fused_enabled(s);
+}
+static int check_objective(int32_t objective, const char* fn) {
+  if (objective == MATCHA_OBJECTIVE_BCE || objective == MATCHA_OBJECTIVE_SOFTPLUS_MSE) return MATCHA_OK;
+  set_error("%s: unknown objective %d (MATCHA_OBJECTIVE_BCE or MATCHA_OBJECTIVE_SOFTPLUS_MSE)", fn, (int)objective);
+  return MATCHA_EINVAL;
 }
 // Which formulation the forward that last ran on a workspace used.  matcha_backward keys off THIS record, not off the option: flipping
 // disable_merged between a forward and its backward (two separate calls on the autograd path) would otherwise make the merged backward
@@ -420,7 +427,7 @@ extern "C" size_t matcha_workspace_bytes_forward(const matcha_shape* shp, int64_
 static int forward_impl(const matcha_shape* shp, const matcha_tensors* params, const matcha_frozen* frozen,
                         const matcha_step_opts* opts, const int64_t* x, int64_t B, int32_t L, const float* y,
                         const float* w_bce, float* logits, float* losses, void* ws, size_t ws_bytes,
-                        matcha_stream_t stream, bool force_layerwise, bool stop_before_head) {
+                        matcha_stream_t stream, bool force_layerwise, bool stop_before_head, int objective) {
   MATCHA_TRY(check_shape(shp, B, L));
   MATCHA_CHECK_ARG(params && frozen && opts && x && ws, "matcha_forward: null pointer");
   MATCHA_CHECK_ARG(((uintptr_t)ws) % 256 == 0, "matcha_forward: workspace must be 256-byte aligned");
@@ -445,7 +452,8 @@ static int forward_impl(const matcha_shape* shp, const matcha_tensors* params, c
 
   // which fused kernels will run on this workspace (decided here: the plan, the front end and the saved records depend on it)
   const bool fused_path = !force_layerwise && fused_enabled(s);
-  const bool lif = fused_path && loss_in_forward(s, *opts, y, w_bce);      // the tail's backward runs in the forward kernel: nothing saved
+  const bool tgt = has_target(objective, y, w_bce);
+  const bool lif = fused_path && loss_in_forward(s, *opts, y, w_bce, objective);      // the tail's backward runs in the forward kernel: nothing saved
   // a training forward leaves r rows + probabilities per (half tile, head) for fused_bwdh_kernel (merged heads: fused_fwd32.hip)
   const bool keep_rimg = !opts->forward_only;
   // CSR plan: real tokens + one shared padding token; the fused kernels walk the HALF tiles (level 1: no 64-row tile list, no token -> tile
@@ -460,7 +468,7 @@ static int forward_impl(const matcha_shape* shp, const matcha_tensors* params, c
   float* recon_out = losses ? losses + 1 : nullptr;
   const bool front = !force_layerwise && fused_enabled(s) && front_bwd_supported(s.d, s.n_attr) && fused_front_enabled();
   // table front end: the two reconstruction-loss slots are zero; loss_reduce_kernel writes them when it runs anyway
-  const bool recon_zero_in_loss = s.mode == 0 && recon_out && fused_path && y && w_bce && losses;
+  const bool recon_zero_in_loss = s.mode == 0 && recon_out && fused_path && tgt && losses;
   // adj front end at embed_dim 64: gather-GEMM, W1, attribute path and next_w in ONE kernel over the chromosome-sorted rows (adj_fused.hip)
   const bool adj_fused = front && fused_path && s.mode == 1 && adj_fused_eligible(s, *frozen);
   if (s.mode == 0) {
@@ -503,18 +511,18 @@ static int forward_impl(const matcha_shape* shp, const matcha_tensors* params, c
     const bool split_tail = lif && !fused_small_batch(w.rg) && (options().fused_dbg & 1) == 0;
     // the backward kernel's heads ADD their d x_hat rows (float atomics) unless the sum has to be reproducible: the rows are zeroed by a launch
     // that runs anyway -- tail_bwd64_kernel, or for small batches the loss reduction's -- and the record says so
-    const bool zero_dx = lif && !opts->deterministic && !opts->sparse_table_grad && (split_tail || fused_small_batch(w.rg)) && y && w_bce && losses;
+    const bool zero_dx = lif && !opts->deterministic && !opts->sparse_table_grad && (split_tail || fused_small_batch(w.rg)) && tgt && losses;
     note_forward(ws, true, true, false, split_tail, zero_dx);
     // (with the tail's backward in the forward kernel, Y and H1 are still handed over: the single-wave kernel PARKS the two rows there
     // (and the normalised H2 row in H2's place) between the tail's forward and backward halves instead of holding 96 registers per lane -- fused_fwd32_tail.hpp)
     MATCHA_TRY(launch_fused_fwd32(p, w.folded, w.frag, w.X, w.rg, B, L, y, w_bce, (save || lif) ? w.Y : nullptr, (save || lif) ? w.H1 : nullptr, (save || lif) ? w.H2 : nullptr,
                                   lg_out, w.row_loss, opts->seed, train ? opts->p_drop_fc1 : 0.f, train ? opts->p_drop_pff : 0.f, st,
-                                  lif ? w.ddyn0 : nullptr, w.dXs, w.tslab, opts->alpha, keep_rimg ? w.qkv : nullptr, split_tail ? w.dH2 : nullptr));
+                                  lif ? w.ddyn0 : nullptr, w.dXs, w.tslab, opts->alpha, keep_rimg ? w.qkv : nullptr, split_tail ? w.dH2 : nullptr, objective));
     if (split_tail)
       MATCHA_TRY(launch_tail_bwd64(p, w.dH2, w.Y, w.H1, w.rg, opts->seed, train ? opts->p_drop_fc1 : 0.f, train ? opts->p_drop_pff : 0.f, w.ddyn0, w.tslab2, w.tslab,
-                                   zero_dx ? w.dO : nullptr, st, w.row_loss, B, (y && w_bce) ? losses : nullptr, recon_zero_in_loss));      // ... zeroes the backward's d x_hat rows, reduces the loss
+                                   zero_dx ? w.dO : nullptr, st, w.row_loss, B, tgt ? losses : nullptr, recon_zero_in_loss));      // ... zeroes the backward's d x_hat rows, reduces the loss
     const bool zero_in_loss = zero_dx && !split_tail;
-    if (y && w_bce && losses && !split_tail)
+    if (tgt && losses && !split_tail)
       MATCHA_TRY(launch_loss_reduce(w.row_loss, B, losses, st, recon_zero_in_loss, zero_in_loss ? w.dO : nullptr, zero_in_loss ? (size_t)Tn * 64 * sizeof(float) : 0));
     if (logits && lg_out != logits && hipMemcpyAsync(logits, w.logits, B * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) {
       set_error("logits copy failed"); return MATCHA_EHIP;
@@ -579,7 +587,7 @@ static int forward_impl(const matcha_shape* shp, const matcha_tensors* params, c
   if (stop_before_head) return MATCHA_OK;
   // LayerNorms, (dynamic-static)^2, Conv1d(d->1), masked mean, weighted BCE   (Modules.py:373-374, :290-311; main.py:56)
   HeadParams hp = {p.pff_ln_g, p.pff_ln_b, p.ln1_g, p.ln1_b, p.ln2_g, p.ln2_b, p.cls_w, p.cls_b};
-  MATCHA_TRY(launch_head_fwd(w.rg.row_off, w.H2, w.X, B, L, d, hp, y, w_bce, w.logits, w.row_loss, losses, st));
+  MATCHA_TRY(launch_head_fwd(w.rg.row_off, w.H2, w.X, B, L, d, hp, y, w_bce, w.logits, w.row_loss, losses, st, objective));
   if (logits && hipMemcpyAsync(logits, w.logits, B * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) {
     set_error("logits copy failed"); return MATCHA_EHIP;
   }
@@ -590,7 +598,14 @@ extern "C" int matcha_forward(const matcha_shape* shp, const matcha_tensors* par
                               const matcha_step_opts* opts, const int64_t* x, int64_t B, int32_t L, const float* y,
                               const float* w_bce, float* logits, float* losses, void* ws, size_t ws_bytes,
                               matcha_stream_t stream) {
-  return forward_impl(shp, params, frozen, opts, x, B, L, y, w_bce, logits, losses, ws, ws_bytes, stream, false, false);
+  return forward_impl(shp, params, frozen, opts, x, B, L, y, w_bce, logits, losses, ws, ws_bytes, stream, false, false, MATCHA_OBJECTIVE_BCE);
+}
+
+extern "C" int matcha_forward_objective(int32_t objective, const matcha_shape* shp, const matcha_tensors* params, const matcha_frozen* frozen,
+                                        const matcha_step_opts* opts, const int64_t* x, int64_t B, int32_t L, const float* y,
+                                        const float* w, float* logits, float* losses, void* ws, size_t ws_bytes, matcha_stream_t stream) {
+  MATCHA_TRY(check_objective(objective, "matcha_forward_objective"));
+  return forward_impl(shp, params, frozen, opts, x, B, L, y, w, logits, losses, ws, ws_bytes, stream, false, false, objective);
 }
 
 extern "C" int matcha_get_embedding(const matcha_shape* shp, const matcha_tensors* params, const matcha_frozen* frozen,
@@ -600,7 +615,7 @@ extern "C" int matcha_get_embedding(const matcha_shape* shp, const matcha_tensor
   matcha_step_opts o = *opts;
   o.forward_only = 0;                  // full workspace layout: the layer-by-layer path keeps H2 and X in HBM
   o.loss_in_forward = 0;
-  MATCHA_TRY(forward_impl(shp, params, frozen, &o, x, B, L, nullptr, nullptr, nullptr, losses, ws, ws_bytes, stream, true, true));
+  MATCHA_TRY(forward_impl(shp, params, frozen, &o, x, B, L, nullptr, nullptr, nullptr, losses, ws, ws_bytes, stream, true, true, MATCHA_OBJECTIVE_BCE));
   Workspace w;
   carve(*shp, B, L, (char*)ws, w);
   if (attn && hipMemcpyAsync(attn, w.P, (size_t)B * MATCHA_N_HEAD * L * L * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
@@ -671,13 +686,14 @@ extern "C" int matcha_table_grad_rows(const matcha_shape* shp, int64_t B, int32_
   return MATCHA_OK;
 }
 
-extern "C" int matcha_backward(const matcha_shape* shp, const matcha_tensors* params, const matcha_frozen* frozen,
-                               const matcha_step_opts* opts, const int64_t* x, int64_t B, int32_t L, const float* y,
-                               const float* w_bce, const float* dlogits, const float* drecon, matcha_tensors* grads,
-                               int32_t* touched, void* ws, size_t ws_bytes, matcha_stream_t stream) {
+static int backward_impl(const matcha_shape* shp, const matcha_tensors* params, const matcha_frozen* frozen,
+                         const matcha_step_opts* opts, const int64_t* x, int64_t B, int32_t L, const float* y,
+                         const float* w_bce, const float* dlogits, const float* drecon, matcha_tensors* grads,
+                         int32_t* touched, void* ws, size_t ws_bytes, matcha_stream_t stream, int objective) {
   MATCHA_TRY(check_shape(shp, B, L));
   MATCHA_CHECK_ARG(params && frozen && opts && x && ws && grads, "matcha_backward: null pointer");
-  MATCHA_CHECK_ARG(dlogits || (y && w_bce), "matcha_backward: need dlogits or (y, w)");
+  MATCHA_CHECK_ARG(dlogits || has_target(objective, y, w_bce),
+                   objective == MATCHA_OBJECTIVE_BCE ? "matcha_backward: need dlogits or (y, w)" : "matcha_backward: need dlogits or y");
   const matcha_shape& s = *shp;
   const matcha_tensors& p = *params;
   matcha_tensors& g_ = *grads;
@@ -696,7 +712,7 @@ extern "C" int matcha_backward(const matcha_shape* shp, const matcha_tensors* pa
   const int fwd_state = ws_state(ws);
   MATCHA_CHECK_ARG(fwd_state >= 0, "matcha_backward: no matcha_forward on record for this workspace (one backward per forward, same ws pointer)");
   const bool fused_fwd = (fwd_state & 2) != 0;          // which kernels the forward ran is what decides, not the option table now
-  const bool lif = fused_fwd && loss_in_forward(s, *opts, y, w_bce);
+  const bool lif = fused_fwd && loss_in_forward(s, *opts, y, w_bce, objective);
   MATCHA_CHECK_ARG(!(lif && dlogits), "matcha_backward: opts->loss_in_forward excludes an explicit dlogits");
   bool dx_zeroed = false, tail_in_bwd = false;
   TailReduceArgs tail_args;
@@ -719,7 +735,7 @@ extern "C" int matcha_backward(const matcha_shape* shp, const matcha_tensors* pa
   // tail: dH2, dXs and the gradients of pff_n1.layer_norm, layer_norm1/2, pff_classifier
   HeadParams hp = {p.pff_ln_g, p.pff_ln_b, p.ln1_g, p.ln1_b, p.ln2_g, p.ln2_b, p.cls_w, p.cls_b};
   HeadParams ghp = {g_.pff_ln_g, g_.pff_ln_b, g_.ln1_g, g_.ln1_b, g_.ln2_g, g_.ln2_b, g_.cls_w, g_.cls_b};
-  MATCHA_TRY(launch_head_bwd(w.rg.row_off, w.H2, w.X, B, L, d, hp, y, w_bce, w.logits, dlogits, opts->alpha, w.dH2, w.dXs, w.slab, ghp, st));
+  MATCHA_TRY(launch_head_bwd(w.rg.row_off, w.H2, w.X, B, L, d, hp, y, w_bce, w.logits, dlogits, opts->alpha, w.dH2, w.dXs, w.slab, ghp, st, objective));
   // pff_n1 conv1: dW1 += dH2^T H1 ; db1 += colsum(dH2) ; dZ1 = (dH2 W1) * dropmask * (1 - tanh^2)
   MATCHA_TRY(launch_gemm_tn(w.dH2, w.H1, g_.pff1_w, g_.pff1_b, d, d, Tn, d, d, nullptr, true, w.gemm_ws, w.gemm_ws_bytes, st, cnt));
   {
@@ -837,6 +853,21 @@ extern "C" int matcha_backward(const matcha_shape* shp, const matcha_tensors* pa
                             w.rg.tok_slot));
   }
   return MATCHA_OK;
+}
+
+extern "C" int matcha_backward(const matcha_shape* shp, const matcha_tensors* params, const matcha_frozen* frozen,
+                               const matcha_step_opts* opts, const int64_t* x, int64_t B, int32_t L, const float* y,
+                               const float* w_bce, const float* dlogits, const float* drecon, matcha_tensors* grads,
+                               int32_t* touched, void* ws, size_t ws_bytes, matcha_stream_t stream) {
+  return backward_impl(shp, params, frozen, opts, x, B, L, y, w_bce, dlogits, drecon, grads, touched, ws, ws_bytes, stream, MATCHA_OBJECTIVE_BCE);
+}
+
+extern "C" int matcha_backward_objective(int32_t objective, const matcha_shape* shp, const matcha_tensors* params, const matcha_frozen* frozen,
+                                         const matcha_step_opts* opts, const int64_t* x, int64_t B, int32_t L, const float* y,
+                                         const float* w, const float* dlogits, const float* drecon, matcha_tensors* grads,
+                                         int32_t* touched, void* ws, size_t ws_bytes, matcha_stream_t stream) {
+  MATCHA_TRY(check_objective(objective, "matcha_backward_objective"));
+  return backward_impl(shp, params, frozen, opts, x, B, L, y, w, dlogits, drecon, grads, touched, ws, ws_bytes, stream, objective);
 }
 
 extern "C" int matcha_node_embeddings(const matcha_shape* shp, const matcha_tensors* params, const matcha_frozen* frozen,

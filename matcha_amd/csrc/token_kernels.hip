@@ -481,7 +481,7 @@ template <int NCH>
 __global__ __launch_bounds__(256) void head_fwd_kernel(const int32_t* __restrict__ row_off, const float* __restrict__ H2,
                                                        const float* __restrict__ X, int64_t B, int L, int d, HeadParams hp,
                                                        const float* __restrict__ y, const float* __restrict__ w,
-                                                       float* __restrict__ logits, float* __restrict__ row_loss) {
+                                                       float* __restrict__ logits, float* __restrict__ row_loss, int objective) {
   const int s = threadIdx.x & 15;
   const int64_t b = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
   if (b >= B) return;
@@ -514,7 +514,11 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const int32_t* __restrict
   const float z = total / (cnt + 1e-15f);
   if (s == 0) {
     logits[b] = z;
-    if (row_loss) {
+    if (row_loss && objective == MATCHA_OBJECTIVE_SOFTPLUS_MSE) {
+      // mse_loss(softplus(z), y) per row (main.py:87-90): (softplus(z) - y)^2, torch's softplus threshold 20
+      const float e = (z > 20.f ? z : log1pf(expf(z))) - y[b];
+      row_loss[b] = e * e;
+    } else if (row_loss) {
       // binary_cross_entropy_with_logits: w * (max(z,0) - z*y + log1p(exp(-|z|)))
       const float yy = y[b];
       row_loss[b] = w[b] * (fmaxf(z, 0.f) - z * yy + log1pf(expf(-fabsf(z))));
@@ -523,7 +527,8 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const int32_t* __restrict
 }
 
 // Backward of the tail.  dlogit[b] is either given (autograd glue) or derived from the BCE:
-//   dlogit = alpha * w * (sigmoid(z) - y) / B.
+//   dlogit = alpha * w * (sigmoid(z) - y) / B,
+// or under MATCHA_OBJECTIVE_SOFTPLUS_MSE (w unused) from the softplus MSE:  dlogit = alpha * 2 (softplus(z) - y) softplus'(z) / B.
 // Writes dH2 [T,d] (gradient w.r.t. pff_n1's pre-LayerNorm sum) and dXs [T,d] (gradient into X through
 // the static branch); parameter gradients as per-block column sums slab[blk][7][d] + slab_bc[blk]:
 //   {dgp, dbp, dg1, db1, dg2, db2, dwc}, dbc.
@@ -533,7 +538,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const int32_t* __restrict
                                                        const float* __restrict__ y, const float* __restrict__ w,
                                                        const float* __restrict__ logits, const float* __restrict__ dlogits,
                                                        float alpha, float* __restrict__ dH2, float* __restrict__ dXs,
-                                                       float* __restrict__ slab, int rows_per_blk) {
+                                                       float* __restrict__ slab, int rows_per_blk, int objective) {
   __shared__ float lds[16 * 256];
   __shared__ float lds_bc[16];
   const int s = threadIdx.x & 15, slot = threadIdx.x >> 4;
@@ -554,7 +559,11 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const int32_t* __restrict
     const float cnt = (float)(t_hi - t_lo);
     float dz;
     if (dlogits) dz = dlogits[b];
-    else {
+    else if (objective == MATCHA_OBJECTIVE_SOFTPLUS_MSE) {
+      const float z = logits[b];
+      const float e = (z > 20.f ? z : log1pf(expf(z))) - y[b];
+      dz = alpha * 2.f * e * (z > 20.f ? 1.f : 1.f / (1.f + expf(-z))) / (float)B;
+    } else {
       const float z = logits[b];
       const float sg = 1.f / (1.f + expf(-z));
       dz = alpha * w[b] * (sg - y[b]) / (float)B;
@@ -783,11 +792,11 @@ int launch_loss_reduce(const float* row_loss, int64_t B, float* bce_out, hipStre
 }
 
 int launch_head_fwd(const int32_t* row_off, const float* H2, const float* X, int64_t B, int L, int d, const HeadParams& hp,
-                    const float* y, const float* w, float* logits, float* row_loss, float* bce_out, hipStream_t st) {
+                    const float* y, const float* w, float* logits, float* row_loss, float* bce_out, hipStream_t st, int objective) {
   if (B <= 0) return MATCHA_OK;
-  float* rl = (y && w) ? row_loss : nullptr;
+  float* rl = (objective == MATCHA_OBJECTIVE_SOFTPLUS_MSE ? y != nullptr : (y && w)) ? row_loss : nullptr;
   ProfScope ps(MATCHA_PROF_HEAD_FWD, (double)B * L * (8.0 * d + 8.0), st);   // read H2, X rows + ids
-  DISPATCH_NCH(d, hipLaunchKernelGGL((head_fwd_kernel<NCH>), dim3((unsigned)cdiv(B, 16)), dim3(256), 0, st, row_off, H2, X, B, L, d, hp, y, w, logits, rl));
+  DISPATCH_NCH(d, hipLaunchKernelGGL((head_fwd_kernel<NCH>), dim3((unsigned)cdiv(B, 16)), dim3(256), 0, st, row_off, H2, X, B, L, d, hp, y, w, logits, rl, objective));
   MATCHA_CHECK_LAUNCH("head_fwd_kernel");
   if (rl && bce_out) {
     hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(1024), 0, st, rl, B, bce_out, 0, (float4*)nullptr, (int64_t)0);
@@ -798,13 +807,13 @@ int launch_head_fwd(const int32_t* row_off, const float* H2, const float* X, int
 
 int launch_head_bwd(const int32_t* row_off, const float* H2, const float* X, int64_t B, int L, int d, const HeadParams& hp,
                     const float* y, const float* w, const float* logits, const float* dlogits, float alpha, float* dH2,
-                    float* dXs, float* slab, const HeadParams& ghp, hipStream_t st) {
+                    float* dXs, float* slab, const HeadParams& ghp, hipStream_t st, int objective) {
   if (B <= 0) return MATCHA_OK;
   int per;
   const int nblk = colsum_blocks(B, &per);
   {
     ProfScope ps(MATCHA_PROF_HEAD_BWD, (double)B * L * (16.0 * d + 8.0), st);  // read H2, X; write dH2, dXs
-    DISPATCH_NCH(d, hipLaunchKernelGGL((head_bwd_kernel<NCH>), dim3(nblk), dim3(256), 0, st, row_off, H2, X, B, L, d, hp, y, w, logits, dlogits, alpha, dH2, dXs, slab, per));
+    DISPATCH_NCH(d, hipLaunchKernelGGL((head_bwd_kernel<NCH>), dim3(nblk), dim3(256), 0, st, row_off, H2, X, B, L, d, hp, y, w, logits, dlogits, alpha, dH2, dXs, slab, per, objective));
   }
   MATCHA_CHECK_LAUNCH("head_bwd_kernel");
   ColsumDst dst = {{(float*)ghp.gp, (float*)ghp.bp, (float*)ghp.g1, (float*)ghp.b1, (float*)ghp.g2, (float*)ghp.b2, (float*)ghp.wc, (float*)ghp.bc}};

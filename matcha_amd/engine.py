@@ -28,13 +28,21 @@ from .parallel import allreduce_bucket, broadcast_parameters, exchange_table_row
 class Trainer:
     def __init__(self, model: Classifier, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 1e-2, process_group=None, base_seed: int = 0, table_exchange: str = "auto",
-                 deterministic: bool = False):
+                 deterministic: bool = False, objective: str = "class"):
         """``table_exchange`` (data parallel, table front end): "dense" = the table gradient rides in the flat all-reduce bucket,
         "sparse" = all-gather of per-token (id, row) lists + a deterministic local sum, "auto" = whichever
         moves fewer bytes for the batch shape (parallel.sparse_exchange_pays).
         ``deterministic`` (table front end): the embedding backward sorts the tokens by node id and sums each node's rows in
         token order (one writer per table row) instead of float atomics -- every parameter is then bitwise reproducible from
-        run to run; costs ~60 us per 65 536-row step (2 %).  The row-sparse exchange always reduces this way."""
+        run to run; costs ~60 us per 65 536-row step (2 %).  The row-sparse exchange always reduces this way.
+        ``objective``: the reference's task_mode (main.py:532).  "class" = the weighted BCE on labels y and weights w (main.py:56);
+        "regress" = mse_loss(softplus(logits), y) on regression targets y, an unweighted mean over the rows (main.py:60-117; w is
+        ignored and may be None).  ``self.losses[0]`` is that objective's loss.  Data parallel scales both alike: each is a mean
+        over rows."""
+        if objective not in _lib.OBJECTIVES:
+            raise ValueError("objective must be 'class' or 'regress'")
+        self.objective = objective
+        self._obj = _lib.OBJECTIVES[objective]
         self.deterministic = bool(deterministic)
         if table_exchange not in ("auto", "dense", "sparse"):
             raise ValueError("table_exchange must be 'auto', 'dense' or 'sparse'")
@@ -155,16 +163,17 @@ class Trainer:
             opts.encoder_done_event = self._enc_event.cuda_event
         if not self.seed_advanced_by_caller:
             self.seed.add_(1)                               # new dropout masks every step (graph-replay safe)
-        _lib.check(self.lib.matcha_forward(C.byref(rt.shape), C.byref(rt.params), C.byref(rt.frozen), C.byref(opts), _lib.ptr(x), B, L,
-                                           _lib.ptr(y), _lib.ptr(w), _lib.ptr(logits), _lib.ptr(self.losses), _lib.ptr(ws), ws.numel(),
-                                           st), "matcha_forward")
+        _lib.check(self.lib.matcha_forward_objective(self._obj, C.byref(rt.shape), C.byref(rt.params), C.byref(rt.frozen), C.byref(opts),
+                                                     _lib.ptr(x), B, L, _lib.ptr(y), _lib.ptr(w), _lib.ptr(logits), _lib.ptr(self.losses),
+                                                     _lib.ptr(ws), ws.numel(), st), "matcha_forward_objective")
         drecon = None
         if (self.world > 1 or self.force_collectives) and rt.shape.mode == 1 and beta != 0.0:
             # adj front end under data parallel: the recon loss is a mean over a rank-dependent number of rows
             drecon = recon_grad_weight(self.losses[2:3], beta, self.pg)
-        _lib.check(self.lib.matcha_backward(C.byref(rt.shape), C.byref(rt.params), C.byref(rt.frozen), C.byref(opts), _lib.ptr(x), B, L,
-                                            _lib.ptr(y), _lib.ptr(w), None, _lib.ptr(drecon) if drecon is not None else None,
-                                            C.byref(self.grads), _lib.ptr(self.touched), _lib.ptr(ws), ws.numel(), st), "matcha_backward")
+        _lib.check(self.lib.matcha_backward_objective(self._obj, C.byref(rt.shape), C.byref(rt.params), C.byref(rt.frozen), C.byref(opts),
+                                                      _lib.ptr(x), B, L, _lib.ptr(y), _lib.ptr(w), None,
+                                                      _lib.ptr(drecon) if drecon is not None else None, C.byref(self.grads),
+                                                      _lib.ptr(self.touched), _lib.ptr(ws), ws.numel(), st), "matcha_backward_objective")
         if overlap:
             self._start_encoder_allreduce()
         return logits
@@ -298,7 +307,7 @@ class Trainer:
                                                 xws.numel(), rt.stream()), "matcha_scatter_rows")
 
     def eval_forward(self, x, y, w, random_chrom=0):
-        """Forward + weighted BCE + reconstruction loss only (eval_epoch, main.py:200-258): no dropout, nothing kept for a backward, the
+        """Forward + the objective's loss (weighted BCE, or the softplus MSE under objective="regress") + reconstruction loss only (eval_epoch, main.py:200-258): no dropout, nothing kept for a backward, the
         compact forward workspace.  Returns the logits [B]; ``self.losses`` holds (bce, recon, rows of the recon mean).  Nothing
         synchronises and nothing allocates after the first call of a shape, so the call can be captured in a hipGraph (train.py)."""
         rt = self.rt
@@ -313,9 +322,9 @@ class Trainer:
         opts = self._opts(1.0, 1.0, random_chrom)
         opts.training, opts.forward_only, opts.loss_in_forward = 0, 1, 0
         opts.sparse_table_grad, opts.deterministic = 0, 0
-        _lib.check(self.lib.matcha_forward(C.byref(rt.shape), C.byref(rt.params), C.byref(rt.frozen), C.byref(opts), _lib.ptr(x), B, L,
-                                           _lib.ptr(y), _lib.ptr(w), _lib.ptr(logits), _lib.ptr(self.losses), _lib.ptr(ws), ws.numel(),
-                                           rt.stream()), "matcha_forward")
+        _lib.check(self.lib.matcha_forward_objective(self._obj, C.byref(rt.shape), C.byref(rt.params), C.byref(rt.frozen), C.byref(opts),
+                                                     _lib.ptr(x), B, L, _lib.ptr(y), _lib.ptr(w), _lib.ptr(logits), _lib.ptr(self.losses),
+                                                     _lib.ptr(ws), ws.numel(), rt.stream()), "matcha_forward_objective")
         return logits
 
     def optimizer_step(self):
@@ -331,7 +340,7 @@ class Trainer:
         tensor the kernels read when they run (what a captured step needs, ``capture``)."""
         x = x.contiguous()
         y = y.reshape(-1).contiguous()
-        w = w.reshape(-1).contiguous()
+        w = None if w is None else w.reshape(-1).contiguous()
         logits = self.forward_backward(x, y, w, alpha, beta, random_chrom, max_tokens=max_tokens)
         self.all_reduce()
         self.optimizer_step()
@@ -356,7 +365,7 @@ class Trainer:
                                "alpha and beta are baked into a captured graph as well.")
         x = x.contiguous()
         y = y.reshape(-1).contiguous()
-        w = w.reshape(-1).contiguous()
+        w = None if w is None else w.reshape(-1).contiguous()
         side = torch.cuda.Stream(self.rt.device)
         side.wait_stream(torch.cuda.current_stream(self.rt.device))
         with torch.cuda.stream(side):

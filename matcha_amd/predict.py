@@ -89,9 +89,13 @@ def generate_pair_wise(chrom_range, chrom_id: int, min_dis: int, device=None) ->
     return torch.stack([first, j], dim=1)
 
 
-def pairwise_probabilities(model, chrom_range, chrom_id: int, min_dis: int, batch_rows: int = 1 << 20) -> Tuple[torch.Tensor, torch.Tensor]:
+def pairwise_probabilities(model, chrom_range, chrom_id: int, min_dis: int, batch_rows: int = 1 << 20,
+                           task_mode: str = "class") -> Tuple[torch.Tensor, torch.Tensor]:
     """(pairs int64 [n, 2], probabilities float32 [n]) on the model's device: sigmoid(model(pairs)) at width L = 2
-    (denoise_contact.py:147-153)."""
+    (denoise_contact.py:147-153); softplus(model(pairs)) for a model trained with task_mode 'regress' (:154-157)."""
+    if task_mode not in ("class", "regress"):
+        raise ValueError("task_mode must be 'class' or 'regress'")
+    act = torch.nn.functional.softplus if task_mode == "regress" else torch.sigmoid
     model.eval()
     dev = model.layer_norm1.weight.device
     pairs = generate_pair_wise(chrom_range, chrom_id, min_dis, dev)
@@ -104,7 +108,7 @@ def pairwise_probabilities(model, chrom_range, chrom_id: int, min_dis: int, batc
     try:
         with torch.no_grad():
             for s in range(0, len(pairs), batch_rows):
-                out[s:s + batch_rows] = torch.sigmoid(model(pairs[s:s + batch_rows].contiguous()).reshape(-1))
+                out[s:s + batch_rows] = act(model(pairs[s:s + batch_rows].contiguous()).reshape(-1))
         if check_each is not None:
             model.check_status()            # IndexError if chrom_range does not belong to this model (ids beyond its tables)
     finally:
@@ -157,6 +161,7 @@ def main(argv=None):
     b = sub.add_parser("pairwise", help="denoise_contact.py's sweep: probability matrix of all intra-chromosome pairs")
     b.add_argument("--chrom", type=int, required=True, help="index into config chrom_list")
     b.add_argument("-o", "--output", type=str, default="./pairwise.npy")
+    b.add_argument("--task-mode", choices=["class", "regress"], default="class", help="the model's training objective: sigmoid or softplus outputs")
     for q in (a, b):
         q.add_argument("--config", type=str, default="./config.JSON")
     args = ap.parse_args(argv)
@@ -167,7 +172,7 @@ def main(argv=None):
         print("%d interactions -> %s" % (len(samples), args.output))
     else:
         chrom_range = np.load(os.path.join(temp_dir, "chrom_range.npy"))
-        pairs, proba = pairwise_probabilities(model, chrom_range, args.chrom, config["min_distance"])
+        pairs, proba = pairwise_probabilities(model, chrom_range, args.chrom, config["min_distance"], task_mode=args.task_mode)
         np.save(args.output, proba2matrix(pairs, None, proba).cpu().numpy())
         print("%d pairs -> %s" % (len(pairs), args.output))
 

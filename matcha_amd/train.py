@@ -113,11 +113,48 @@ def predict(model: Classifier, rows, batch_size: int = 100000) -> np.ndarray:
     return np.concatenate([o.cpu().numpy() for o in outs], axis=0) if outs else np.zeros((0, 1), dtype=np.float32)
 
 
+class PairRecord:
+    """The epoch records of the regression objective (main.py:94-117) on the device: every step's rows paired by a fresh random
+    bijection (matcha_step_record_pairs), the pair predictions sigmoid(softplus(z0) - softplus(z1)), the pair labels (-1 = masked:
+    equal targets) and the size of each pair's first row, [n_batch, B/2] each, plus the running loss sums.  Nothing synchronises;
+    the masked pairs are filtered once at the end of the epoch (_epoch_metrics)."""
+
+    def __init__(self, n_batch: int, B: int, dev, it: Optional[torch.Tensor] = None):
+        """``it``: the device step counter to advance (a captured epoch's, which matcha_step_select reads); a counter of its own if None."""
+        H = B // 2
+        self.n_batch, self.B = n_batch, B
+        self.it = torch.zeros(1, dtype=torch.long, device=dev) if it is None else it
+        self.seed = torch.zeros(1, dtype=torch.long, device=dev)
+        self.sums = torch.zeros(2, dtype=torch.float32, device=dev)
+        self.preds = torch.empty((n_batch, H), dtype=torch.float32, device=dev)
+        self.labels = torch.empty((n_batch, H), dtype=torch.int32, device=dev)
+        self.sizes = torch.empty((n_batch, H), dtype=torch.long, device=dev)
+
+    def reset(self, seed: int):
+        """Start of an epoch: step counter and sums to zero, a new pairing seed (the pairs of step i are a function of (seed, i))."""
+        self.it.zero_(); self.sums.zero_(); self.seed.fill_(int(seed))
+
+    def record(self, logits, losses, y, x):
+        L = int(x.shape[1])
+        stream = C.c_void_p(torch.cuda.current_stream(logits.device).cuda_stream)
+        _lib.check(_lib.load().matcha_step_record_pairs(_lib.ptr(logits), _lib.ptr(losses), _lib.ptr(y), _lib.ptr(x), self.B, L, _lib.ptr(self.it),
+                                                        self.n_batch, _lib.ptr(self.seed), _lib.ptr(self.sums), _lib.ptr(self.preds),
+                                                        _lib.ptr(self.labels), _lib.ptr(self.sizes), stream), "matcha_step_record_pairs")
+
+
 class Session:
-    """Everything one training run needs on the device: model, fused trainer, positive set, negative sampler."""
+    """Everything one training run needs on the device: model, fused trainer, positive set, negative sampler.
+    ``task_mode`` (main.py:532): 'class' = weighted BCE on positives and NEG_NUM negatives per positive; 'regress' = the model learns
+    each k-mer's weight -- one negative per positive, targets y = weight / 0, mse_loss(softplus(logits), y), metrics on random pairs
+    of rows (main.py:60-117)."""
 
     def __init__(self, model: Classifier, node2chrom: np.ndarray, chrom_range: np.ndarray, min_size: int, max_size: int, min_dis: int,
-                 seed: int = 0, deterministic: bool = False):
+                 seed: int = 0, deterministic: bool = False, task_mode: str = "class"):
+        if task_mode not in ("class", "regress"):
+            raise ValueError("task_mode must be 'class' or 'regress'")
+        self.task_mode = task_mode
+        self.regress = task_mode == "regress"
+        self.neg_num = 1 if self.regress else NEG_NUM          # generate_negative(..., neg_num=1) in forward_op_batch_regress (main.py:71)
         self.deterministic = deterministic
         self.model = model
         self.dev = model.layer_norm1.weight.device
@@ -125,14 +162,15 @@ class Session:
         self.node2chrom, self.chrom_range = node2chrom, chrom_range
         self.n_chrom = len(chrom_range)
         self.rank, self.world = _dist()
-        self.trainer = Trainer(model, lr=1e-3, base_seed=seed, deterministic=deterministic)      # AdamW(lr=1e-3), main.py:630
+        self.trainer = Trainer(model, lr=1e-3, base_seed=seed, deterministic=deterministic, objective=task_mode)      # AdamW(lr=1e-3), main.py:630
         self._generation = 0          # bumped whenever the trainer or the sampler is replaced: a captured step belongs to ONE pair of them
         self.set_known(None)
         self.rng = np.random.default_rng(seed)
 
     def new_optimizer(self):
         """main.py:671 builds a fresh AdamW (moments and step counts reset) for phase 2."""
-        self.trainer = Trainer(self.model, lr=1e-3, base_seed=int(self.rng.integers(1 << 30)), deterministic=self.deterministic)
+        self.trainer = Trainer(self.model, lr=1e-3, base_seed=int(self.rng.integers(1 << 30)), deterministic=self.deterministic,
+                               objective=self.task_mode)
         self._generation += 1
         self.__dict__.pop("_graph_state", None)
         self.__dict__.pop("_eval_state", None)
@@ -144,17 +182,21 @@ class Session:
         else:
             hs = HyperedgeSet(torch.from_numpy(np.ascontiguousarray(edges)).to(self.dev))
         # the draw is rank-shared (numpy's global stream is); the rank offset gives every rank its own negative stream
-        self.sampler = NegativeSampler(hs, self.node2chrom, self.chrom_range, neg_num=NEG_NUM, min_dis=self.min_dis,
+        self.sampler = NegativeSampler(hs, self.node2chrom, self.chrom_range, neg_num=self.neg_num, min_dis=self.min_dis,
                                        seed=int(np.random.randint(1 << 30)) + 7919 * self.rank)
         self._generation = getattr(self, "_generation", 0) + 1
         self.__dict__.pop("_graph_state", None)         # a captured step has the old sampler's tables and seed baked in
         self.__dict__.pop("_eval_state", None)
 
     def make_batch(self, pos: torch.Tensor, pos_w: torch.Tensor):
-        """generate_negative's output (main.py:443-448): x = [pos; neg], y = [1..; 0..], w = [pos_w..; 1..]."""
+        """generate_negative's output (main.py:443-448): x = [pos; neg], y = [1..; 0..], w = [pos_w..; 1..].
+        task_mode 'regress' (main.py:449-454): one negative per positive, y = [pos_w..; 0..], w = [1..]."""
         P = pos.shape[0]
         neg = self.sampler.sample(pos)
         x = torch.cat([pos, neg], dim=0)
+        if self.regress:
+            y = torch.cat([pos_w.to(torch.float32), torch.zeros(neg.shape[0], device=self.dev)])
+            return x, y, torch.ones(x.shape[0], device=self.dev), (x != 0).sum(dim=1)
         y = torch.cat([torch.ones(P, device=self.dev), torch.zeros(neg.shape[0], device=self.dev)])
         w = torch.cat([pos_w.to(torch.float32), torch.ones(neg.shape[0], device=self.dev)])
         sizes = (x != 0).sum(dim=1)
@@ -183,17 +225,24 @@ class Session:
             return False
         return GRAPH_EPOCHS and (tr.rt.mode == 0 or beta == 0.0 or tr.supports_device_chrom())
 
+    def pair_seed(self) -> int:
+        """The seed of one epoch's pairings (task_mode 'regress'): drawn from the session's own generator, so numpy's global stream -- the
+        split, the shuffles and random_chrom -- stays where the class-mode loop leaves it."""
+        return int(self.rng.integers(1 << 62))
+
     def graph_epoch(self, e: torch.Tensor, w: torch.Tensor, n_batch: int, P: int, alpha: float, beta: float, tok_max=None):
         """e int64 [>= n_batch * P, L], w float32: the epoch's shuffled positives (data parallel: THIS RANK's rows of every global batch, in
         step order).  Returns (bce_sum, recon_sum, preds [n_batch, B], labels [B], sizes [n_batch, B]) as device tensors; nothing has
         synchronised.  ``tok_max`` (data parallel): per step the largest real-token count of any rank (host arithmetic of the driver), for
-        the compacted row-sparse exchange."""
-        dev, L, B = self.dev, int(e.shape[1]), P * (1 + NEG_NUM)
+        the compacted row-sparse exchange.
+        task_mode 'regress': the step's targets land in y[0:P] (matcha_step_select writes them there) and the records are the pairs'
+        (PairRecord): returns (mse_sum, recon_sum, preds [n_batch, B/2], labels [n_batch, B/2], sizes [n_batch, B/2])."""
+        dev, L, B = self.dev, int(e.shape[1]), P * (1 + self.neg_num)
         dp = self.world > 1
         # the chromosome of every step's reconstruction branch, drawn exactly as the step-by-step loop draws them (Modules.py:192)
         chroms = np.asarray([self.random_chrom() for _ in range(n_batch)], dtype=np.int32)
         # (a monotonically increasing generation, not id(): CPython reuses the id of a freed Trainer / sampler)
-        key = (n_batch, P, L, float(alpha), float(beta), self._generation)
+        key = (n_batch, P, L, float(alpha), float(beta), self._generation, self.task_mode)
         st = self.__dict__.get("_graph_state")
         if st is not None and not self.trainer.rt.still_packed():
             # parameters moved since the capture (model.to(), a rebuilt runtime): the graph would train the old buffers -- as
@@ -209,9 +258,16 @@ class Session:
                       ww=torch.ones(B, dtype=torch.float32, device=dev),                                  # main.py:446-447
                       preds=torch.empty((n_batch, B), dtype=torch.float32, device=dev), sizes=torch.empty((n_batch, B), dtype=torch.long, device=dev),
                       sums=torch.zeros(2, dtype=torch.float32, device=dev))
+            if self.regress:
+                st["y"].zero_()                                                                           # main.py:452: negatives' target 0
+                st["pairs"] = PairRecord(n_batch, B, dev, it=st["it"])      # advances the counter matcha_step_select reads
             self._graph_state = st
         st["pos"].copy_(e[:n_batch * P]); st["w"].copy_(w[:n_batch * P]); st["chroms"].copy_(torch.from_numpy(chroms))
         st["it"].zero_(); st["sums"].zero_()
+        if self.regress:
+            st["pairs"].reset(self.pair_seed())
+        # the positives' weights are the BCE weights (ww) in class mode and the regression targets (y) in regress mode
+        sel_w = st["y"] if self.regress else st["ww"]
 
         lib = _lib.load()
         n_rows = n_batch * P
@@ -223,7 +279,7 @@ class Session:
             # and reconstruction chromosome (matcha_step_select) and the row of the epoch's prediction / size buffers (matcha_step_record)
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             _lib.check(lib.matcha_step_select(_lib.ptr(st["pos"]), _lib.ptr(st["w"]), n_rows, L, _lib.ptr(st["it"]), P, _lib.ptr(st["x"]),
-                                              _lib.ptr(st["ww"]), _lib.ptr(st["chroms"]), n_batch, _lib.ptr(st["cell"]),
+                                              _lib.ptr(sel_w), _lib.ptr(st["chroms"]), n_batch, _lib.ptr(st["cell"]),
                                               _lib.ptr(self.sampler.seed), _lib.ptr(tr.seed), stream),
                        "matcha_step_select")
             self.sampler.sample_into(st["x"][:P], st["x"][P:], advance_seed=False)
@@ -244,6 +300,9 @@ class Session:
         def part_b():
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             tr.optimizer_step()
+            if self.regress:
+                st["pairs"].record(st["logits"], tr.losses, st["y"], st["x"])
+                return
             _lib.check(lib.matcha_step_record(_lib.ptr(st["logits"]), _lib.ptr(tr.losses), _lib.ptr(st["x"]), B, L, _lib.ptr(st["it"]),
                                               n_batch, _lib.ptr(st["sums"]), _lib.ptr(st["preds"]), _lib.ptr(st["sizes"]), stream),
                        "matcha_step_record")
@@ -257,7 +316,7 @@ class Session:
         if os.environ.get("MATCHA_TRAIN_GRAPH") == "steps":      # development: the same device-side step function, enqueued call by call
             for i in range(n_batch):
                 one_step(i)
-            return st["sums"][0], st["sums"][1], st["preds"], st["y"], st["sizes"]
+            return _epoch_records(st)
         if st["graph"] is None:
             # the first steps of the epoch run call by call on a side stream (they ARE steps of the epoch: buffers get allocated,
             # kernels loaded), then the same functions are captured; capturing enqueues nothing
@@ -294,21 +353,30 @@ class Session:
                 st["graph"].replay()
                 tm["graph_replays"] += 1
                 STATS["train_graph_replays"] += 1
-        return st["sums"][0], st["sums"][1], st["preds"], st["y"], st["sizes"]
+        return _epoch_records(st)
+
+
+def _epoch_records(st: dict):
+    """(loss_sum, recon_sum, preds, labels, sizes) of a captured epoch's state: class mode -- preds / sizes [n_batch, B], labels = the
+    step's y [B]; regress mode -- the pair records [n_batch, B/2] each."""
+    pr = st.get("pairs")
+    if pr is not None:
+        return pr.sums[0], pr.sums[1], pr.preds, pr.labels, pr.sizes
+    return st["sums"][0], st["sums"][1], st["preds"], st["y"], st["sizes"]
 
 
 def _graph_eval(sess: Session, e: torch.Tensor, w: torch.Tensor, n_batch: int, P: int):
     """eval_epoch's loop as replays of ONE captured forward-only step (round 5): device-side batch selection
     (matcha_step_select), negative sampling, matcha_forward(forward_only) with the loss inside, matcha_step_record.  Same device-side
     state machine as Session.graph_epoch; returns (bce_sum, recon_sum, preds [n_batch, B], labels [B], sizes [n_batch, B])."""
-    dev, L, B = sess.dev, int(e.shape[1]), P * (1 + NEG_NUM)
+    dev, L, B = sess.dev, int(e.shape[1]), P * (1 + sess.neg_num)
     # the reconstruction chromosome of every forward, drawn exactly as Classifier.forward draws it (Modules.py:192: np.random.choice on numpy's
     # global stream, adj front end only) so that the call-by-call loop and this one leave the stream in the same state
     if sess.trainer.rt.mode == 1:
         chroms = np.asarray([int(np.random.choice(np.arange(sess.n_chrom), 1)[0]) for _ in range(n_batch)], dtype=np.int32)
     else:
         chroms = np.zeros(n_batch, dtype=np.int32)
-    key = (n_batch, P, L, sess._generation)
+    key = (n_batch, P, L, sess._generation, sess.task_mode)
     st = sess.__dict__.get("_eval_state")
     if st is not None and not sess.trainer.rt.still_packed():
         # parameters moved since the capture (model.to(), a rebuilt runtime): a replay would evaluate the old buffers (as graph_epoch refuses to)
@@ -321,20 +389,29 @@ def _graph_eval(sess: Session, e: torch.Tensor, w: torch.Tensor, n_batch: int, P
                   y=torch.cat([torch.ones(P, device=dev), torch.zeros(B - P, device=dev)]), ww=torch.ones(B, dtype=torch.float32, device=dev),
                   preds=torch.empty((n_batch, B), dtype=torch.float32, device=dev), sizes=torch.empty((n_batch, B), dtype=torch.long, device=dev),
                   sums=torch.zeros(2, dtype=torch.float32, device=dev))
+        if sess.regress:
+            st["y"].zero_()
+            st["pairs"] = PairRecord(n_batch, B, dev, it=st["it"])
         sess._eval_state = st
     st["pos"].copy_(e[:n_batch * P]); st["w"].copy_(w[:n_batch * P]); st["chroms"].copy_(torch.from_numpy(chroms))
     st["it"].zero_(); st["sums"].zero_()
+    if sess.regress:
+        st["pairs"].reset(sess.pair_seed())
+    sel_w = st["y"] if sess.regress else st["ww"]
     lib = _lib.load()
     n_rows = n_batch * P
     tr = sess.trainer
 
     def one_step():
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.matcha_step_select(_lib.ptr(st["pos"]), _lib.ptr(st["w"]), n_rows, L, _lib.ptr(st["it"]), P, _lib.ptr(st["x"]), _lib.ptr(st["ww"]),
+        _lib.check(lib.matcha_step_select(_lib.ptr(st["pos"]), _lib.ptr(st["w"]), n_rows, L, _lib.ptr(st["it"]), P, _lib.ptr(st["x"]), _lib.ptr(sel_w),
                                           _lib.ptr(st["chroms"]), n_batch, _lib.ptr(st["cell"]), _lib.ptr(sess.sampler.seed), None, stream),
                    "matcha_step_select")          # (no dropout in a forward-only step: the trainer's dropout seed stays where the call-by-call loop leaves it)
         sess.sampler.sample_into(st["x"][:P], st["x"][P:], advance_seed=False)
         logits = tr.eval_forward(st["x"], st["y"], st["ww"], random_chrom=st["cell"])
+        if sess.regress:
+            st["pairs"].record(logits, tr.losses, st["y"], st["x"])
+            return
         _lib.check(lib.matcha_step_record(_lib.ptr(logits), _lib.ptr(tr.losses), _lib.ptr(st["x"]), B, L, _lib.ptr(st["it"]), n_batch, _lib.ptr(st["sums"]),
                                           _lib.ptr(st["preds"]), _lib.ptr(st["sizes"]), stream), "matcha_step_record")
 
@@ -353,7 +430,7 @@ def _graph_eval(sess: Session, e: torch.Tensor, w: torch.Tensor, n_batch: int, P
         st["graph"] = g
     for _ in range(n_batch - done):
         st["graph"].replay()
-    return st["sums"][0], st["sums"][1], st["preds"], st["y"], st["sizes"]
+    return _epoch_records(st)
 
 
 def train_epoch(sess: Session, edges: np.ndarray, weights: np.ndarray, alpha: float, beta: float, batch_size: int = BATCH_SIZE):
@@ -374,7 +451,7 @@ def train_epoch(sess: Session, edges: np.ndarray, weights: np.ndarray, alpha: fl
     tok_max = None
     if sess.world > 1:
         k_host = (edges != 0).sum(1)[perm_host][:n_batch * gb].reshape(n_batch, batch_size, sess.world)        # [step, row, rank]: strided shards
-        tok_max = ((1 + NEG_NUM) * k_host.sum(1).max(1)).tolist()
+        tok_max = ((1 + sess.neg_num) * k_host.sum(1).max(1)).tolist()
     tm = sess.__dict__.setdefault("timing", {})          # wall clock of the epoch's phases (tools/epoch_bench.py reads it)
     t_loop = time.perf_counter()
     if n_batch > 0 and sess.graph_ok(beta):
@@ -389,23 +466,33 @@ def train_epoch(sess: Session, edges: np.ndarray, weights: np.ndarray, alpha: fl
             both = torch.stack([bce_sum, rec_sum])
             torch.distributed.all_reduce(both)
             bce_sum, rec_sum = both[0] / sess.world, both[1] / sess.world
-        pred, label, size = p2.reshape(-1), y1.repeat(n_batch), s2.reshape(-1)
+        pred, label, size = p2.reshape(-1), (y1.reshape(-1) if sess.regress else y1.repeat(n_batch)), s2.reshape(-1)
         torch.cuda.synchronize(dev)                                              # the epoch's one synchronisation
         tm["loop_s"] = time.perf_counter() - t_loop
         return _epoch_metrics(sess, bce_sum, rec_sum, pred, label, size, n_batch)
     bce_sum = torch.zeros((), device=dev)
     rec_sum = torch.zeros((), device=dev)
     preds, labels, sizes = [], [], []
+    pairs = None
+    if sess.regress and n_batch > 0:
+        pairs = PairRecord(n_batch, batch_size * (1 + sess.neg_num), dev)
+        pairs.reset(sess.pair_seed())
     for i in range(n_batch):
         pos, pw = e[i * gb:(i + 1) * gb][mine], w[i * gb:(i + 1) * gb][mine]
         x, y, ww, s = sess.make_batch(pos, pw)
         bce, recon, logits = sess.trainer.step(x, y, ww, alpha=alpha, beta=beta, random_chrom=sess.random_chrom(),
                                                max_tokens=None if tok_max is None else tok_max[i])
+        if pairs is not None:
+            pairs.record(logits, sess.trainer.losses, y, x)                     # main.py:94-117: the step's pairs, loss sums
+            continue
         bce_sum += bce
         rec_sum += recon[0]
         preds.append(torch.sigmoid(logits).clone())                             # main.py:58
         labels.append(y)
         sizes.append(s)
+    if pairs is not None:
+        bce_sum, rec_sum = pairs.sums[0], pairs.sums[1]
+        preds, labels, sizes = [pairs.preds.reshape(-1)], [pairs.labels.reshape(-1)], [pairs.sizes.reshape(-1)]
     if sess.world > 1:                                                           # epoch means over all ranks; metrics below: this rank's rows
         both = torch.stack([bce_sum, rec_sum])
         torch.distributed.all_reduce(both)
@@ -429,9 +516,19 @@ def _epoch_metrics_impl(sess: Session, bce_sum, rec_sum, pred, label, size, n_ba
     exhausted = sess.sampler.check_status()                                      # KeyError for nodes without a chromosome
     if exhausted:
         print(f"warning: {exhausted} negatives could not be redrawn within 65536 trials and were returned equal to their positive")
+    auc, aupr, acc = _metrics(sess, pred, label, size)
+    return float(bce_sum) / max(n_batch, 1), float(rec_sum) / max(n_batch, 1), acc, auc, aupr
+
+
+def _metrics(sess: Session, pred, label, size):
+    """roc_auc_cuda + accuracy per size (main.py:186-195).  Regress mode: the pair records, masked pairs (label -1: equal targets,
+    main.py:99-102) dropped here, once per epoch."""
+    if sess.regress and pred.numel():
+        keep = label >= 0
+        pred, label, size = pred[keep], label[keep].to(torch.float32), size[keep]
     auc, aupr = U.roc_auc_cuda(label, pred, size, sess.max_size)
     acc = U.accuracy(pred, label, size, sess.max_size)
-    return float(bce_sum) / max(n_batch, 1), float(rec_sum) / max(n_batch, 1), acc, auc, aupr
+    return auc, aupr, acc
 
 
 @torch.no_grad()
@@ -452,29 +549,38 @@ def eval_epoch(sess: Session, edges: np.ndarray, weights: np.ndarray, batch_size
     if n_batch > 0 and sess.graph_ok(1.0, training=False):
         # the forward-only step captured once and replayed per batch (the training epoch's mechanism); metrics as in _epoch_metrics
         bce_t, rec_t, p2, y1, s2 = _graph_eval(sess, e, w, n_batch, batch_size)
-        pred, label, size = p2.reshape(-1), y1.repeat(n_batch), s2.reshape(-1)
+        pred, label, size = p2.reshape(-1), (y1.reshape(-1) if sess.regress else y1.repeat(n_batch)), s2.reshape(-1)
         torch.cuda.synchronize(dev)
         tm["eval_loop_s"] = time.perf_counter() - t_loop
         sess.trainer.check_status()
-        auc, aupr = U.roc_auc_cuda(label, pred, size, sess.max_size)
-        acc = U.accuracy(pred, label, size, sess.max_size)
+        auc, aupr, acc = _metrics(sess, pred, label, size)
         return float(bce_t) / n_batch, float(rec_t) / n_batch, acc, auc, aupr
     bce_sum, rec_sum = torch.zeros((), device=dev), torch.zeros((), device=dev)
     preds, labels, sizes = [], [], []
+    pairs = None
+    if sess.regress and n_batch > 0:
+        pairs = PairRecord(n_batch, batch_size * (1 + sess.neg_num), dev)
+        pairs.reset(sess.pair_seed())
     with model.deferred_id_check():                     # nothing synchronises inside the loop; ids are checked once behind it
         for i in range(n_batch):
             pos, pw = e[i * batch_size:(i + 1) * batch_size], w[i * batch_size:(i + 1) * batch_size]
             x, y, ww, s = sess.make_batch(pos, pw)
             logits, recon = model(x, return_recon=True)
+            if pairs is not None:                       # main.py:207-210: the softplus MSE and the step's pairs
+                mse = torch.nn.functional.mse_loss(torch.nn.functional.softplus(logits.view(-1)), y)
+                pairs.record(logits.view(-1).contiguous(), torch.stack([mse, recon[0]]), y, x)
+                continue
             bce_sum += torch.nn.functional.binary_cross_entropy_with_logits(logits.view(-1), y, weight=ww)
             rec_sum += recon[0]
             preds.append(torch.sigmoid(logits.view(-1)))
             labels.append(y)
             sizes.append(s)
+    if pairs is not None:
+        bce_sum, rec_sum = pairs.sums[0], pairs.sums[1]
+        preds, labels, sizes = [pairs.preds.reshape(-1)], [pairs.labels.reshape(-1)], [pairs.sizes.reshape(-1)]
     bce_sum, rec_sum = float(bce_sum), float(rec_sum)
     pred, label, size = torch.cat(preds), torch.cat(labels), torch.cat(sizes)
-    auc, aupr = U.roc_auc_cuda(label, pred, size, sess.max_size)
-    acc = U.accuracy(pred, label, size, sess.max_size)
+    auc, aupr, acc = _metrics(sess, pred, label, size)
     return bce_sum / max(n_batch, 1), rec_sum / max(n_batch, 1), acc, auc, aupr
 
 
@@ -527,7 +633,7 @@ def init_distributed(backend: Optional[str] = None) -> Tuple[int, int, str]:
 
 
 def run(config: dict, front_end: str = "adj", epochs1: int = 3, epochs2: int = 30, batches_per_epoch: int = 1000, device: str = "cuda",
-        emb_path: Optional[str] = "../embeddings.npy", log=print, deterministic: bool = False) -> Classifier:
+        emb_path: Optional[str] = "../embeddings.npy", log=print, deterministic: bool = False, task_mode: str = "class") -> Classifier:
     """The script body of main.py:516-685 (on every rank of a data-parallel launch, see the module docstring)."""
     rank, world = _dist()
     if world > 1:
@@ -567,7 +673,7 @@ def run(config: dict, front_end: str = "adj", epochs1: int = 3, epochs2: int = 3
     model = Classifier(n_head=8, d_model=d, d_k=d, d_v=d, node_embedding=ne, diag_mask=True, bottle_neck=d, attribute_dict=attr).to(device)
     save_embeddings(model, N, emb_path if rank == 0 else None)                     # main.py:625 (every rank: keeps the numpy stream shared)
 
-    sess = Session(model, node2chrom, chrom_range.astype(np.int32), min_size, max_size, min_dis, deterministic=deterministic)
+    sess = Session(model, node2chrom, chrom_range.astype(np.int32), min_size, max_size, min_dis, deterministic=deterministic, task_mode=task_mode)
     # phase 1: alpha 0, beta 1, empty dict (negatives == positives)             main.py:637-643
     train(sess, (train_data, train_w), (test_data, test_w), epochs1, 0.0, 1.0, temp_dir, N, batches_per_epoch=batches_per_epoch,
           emb_path=emb_path, log=log)
@@ -592,9 +698,12 @@ def main(argv=None):
     ap.add_argument("--epochs2", type=int, default=30)
     ap.add_argument("--batches-per-epoch", type=int, default=1000)
     ap.add_argument("--deterministic", action="store_true", help="table front end: sorted embedding backward (bitwise reproducible table)")
+    ap.add_argument("--task-mode", choices=["class", "regress"], default="class",
+                    help="main.py:532: 'class' = weighted BCE on pos / neg labels; 'regress' = learn each k-mer's weight (softplus MSE)")
     a = ap.parse_args(argv)
     rank, world, device = init_distributed()
-    run(U.get_config(a.config), a.front_end, a.epochs1, a.epochs2, a.batches_per_epoch, device=device, deterministic=a.deterministic)
+    run(U.get_config(a.config), a.front_end, a.epochs1, a.epochs2, a.batches_per_epoch, device=device, deterministic=a.deterministic,
+        task_mode=a.task_mode)
     if world > 1:
         torch.distributed.destroy_process_group()
 
