@@ -13,12 +13,17 @@ tests/test_oracle_golden.py).
 
 Randomness is *injected*: dropout masks are multiplier tensors (0 or 1/(1-p)),
 ``random_chrom`` (Modules.py:192) is an argument.
+
+Any dtype: every intermediate follows the parameters' dtype, so ``{k: v.double()}`` parameters with
+``FrontEnd.to(torch.float64)`` give the fp64 oracle (tests/fp64_grade.py).  The matrix products, the batched
+products and tanh go through ``ops`` (an ``Ops``; torch's own by default), so that a test can swap in an
+emulation of reduced-precision arithmetic and check that its criterion notices.
 """
 from __future__ import annotations
 
 import math
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional
+from typing import Callable, Dict, List, Optional
 
 import numpy as np
 import torch
@@ -93,6 +98,11 @@ class FrontEnd:
     def n_chrom(self) -> int:
         return len(self.bounds) - 1
 
+    def to(self, dtype: torch.dtype) -> "FrontEnd":
+        """The same front end with feats and inter in ``dtype`` (the oracle's intermediates follow the parameters' dtype)."""
+        return FrontEnd(mode=self.mode, bounds=list(self.bounds), feats=[f.to(dtype) for f in self.feats],
+                        inter=None if self.inter is None else self.inter.to(dtype))
+
     @property
     def n_nodes(self) -> int:
         return int(self.bounds[-1])
@@ -101,13 +111,25 @@ class FrontEnd:
 # --------------------------------------------------------------------------------------
 # forward
 # --------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class Ops:
+    """The operations a test may replace: ``mm`` (every ``@`` of the forward: activations times a transposed weight),
+    ``bmm`` (the two attention products) and ``tanh``.  The defaults are torch's own, so the plain oracle is unchanged."""
+    mm: Callable = torch.matmul
+    bmm: Callable = torch.bmm
+    tanh: Callable = torch.tanh
+
+
+TORCH_OPS = Ops()
+
+
 def _ln(x, P, prefix):
     return F.layer_norm(x, (x.shape[-1],), P[prefix + ".weight"], P[prefix + ".bias"], LN_EPS)
 
 
 def node_embeddings(P: Dict[str, torch.Tensor], fe: FrontEnd, xf: torch.Tensor,
                     random_chrom: Optional[int] = None,
-                    adj_mask: Optional[torch.Tensor] = None):
+                    adj_mask: Optional[torch.Tensor] = None, ops: Ops = TORCH_OPS):
     """``node_embedding(x.view(-1))`` -> (rows [T,d], recon_loss [1]).
 
     adj  : MultipleEmbedding.forward Modules.py:176-201 (+ SparseEmbedding :67, TiedAutoEncoder :104-113)
@@ -118,9 +140,10 @@ def node_embeddings(P: Dict[str, torch.Tensor], fe: FrontEnd, xf: torch.Tensor,
         W = P["node_embedding.weight"]
         return F.embedding(xf, W, padding_idx=0), torch.zeros(1, dtype=W.dtype)
 
+    dt = P["node_embedding.Embedding_Linear0.tied weight_1"].dtype
     d = P["node_embedding.Embedding_Linear0.tied weight_1"].shape[0]
     T = xf.shape[0]
-    final = torch.zeros((T, d), dtype=torch.float32)
+    final = torch.zeros((T, d), dtype=dt)
     for i in range(fe.n_chrom):
         lo, hi = fe.bounds[i] + 1, fe.bounds[i + 1] + 1
         sel = (xf >= lo) & (xf < hi)                                  # :181
@@ -131,9 +154,9 @@ def node_embeddings(P: Dict[str, torch.Tensor], fe: FrontEnd, xf: torch.Tensor,
             rows = rows * adj_mask[sel][:, : rows.shape[1]]           # :186
         w0 = P[f"node_embedding.Embedding_Linear{i}.tied weight_0"]
         w1 = P[f"node_embedding.Embedding_Linear{i}.tied weight_1"]
-        h = torch.tanh(rows @ w0.t()) @ w1.t()                        # :109-113 (use_bias=False :163)
+        h = ops.mm(ops.tanh(ops.mm(rows, w0.t())), w1.t())             # :109-113 (use_bias=False :163)
         final = final.index_put((sel.nonzero(as_tuple=True)[0],), h)  # :188
-    recon_loss = torch.zeros(1, dtype=torch.float32)
+    recon_loss = torch.zeros(1, dtype=dt)
     if random_chrom is None:
         raise ValueError("adj mode needs the drawn random_chrom (Modules.py:192)")
     r = int(random_chrom)
@@ -142,7 +165,7 @@ def node_embeddings(P: Dict[str, torch.Tensor], fe: FrontEnd, xf: torch.Tensor,
         target = fe.inter[xf[other] - 1][:, fe.bounds[r]:fe.bounds[r + 1]]         # :196-197
         wr = P[f"node_embedding.Embedding_recon{r}.FF_Linear0.weight"]
         br = P[f"node_embedding.Embedding_recon{r}.FF_Linear0.bias"]
-        rec = torch.tanh(final[other]) @ wr.t() + br                  # :198
+        rec = ops.mm(ops.tanh(final[other]), wr.t()) + br             # :198
         recon_loss = recon_loss + (target - rec).pow(2).mean(dim=-1).mean() * 100  # :199
     return final, recon_loss
 
@@ -150,7 +173,7 @@ def node_embeddings(P: Dict[str, torch.Tensor], fe: FrontEnd, xf: torch.Tensor,
 def classifier_forward(P: Dict[str, torch.Tensor], fe: FrontEnd, x: torch.Tensor, *,
                        random_chrom: Optional[int] = None,
                        masks: Optional[Dict[str, torch.Tensor]] = None,
-                       return_intermediates: bool = False):
+                       return_intermediates: bool = False, ops: Ops = TORCH_OPS):
     """Classifier.forward(x, return_recon=True) (Modules.py:278-318) -> (logits [B,1], recon_loss [1]).
 
     x: LongTensor [B,L], 0 = padding.  ``masks`` (training only) may hold multiplier tensors
@@ -163,42 +186,43 @@ def classifier_forward(P: Dict[str, torch.Tensor], fe: FrontEnd, x: torch.Tensor
     x = x.long()
     B, L = x.shape
     xf = x.reshape(-1)
-    non_pad = x.ne(0).to(torch.float32).unsqueeze(-1)                     # :12-14  [B,L,1]
+    non_pad = x.ne(0).to(P["next_w.FF_Linear0.weight"].dtype).unsqueeze(-1)   # :12-14  [B,L,1]
+    mm = ops.mm
 
     # get_embedding :261-276
-    attr = P["attribute_dict_embedding.weight"][xf] @ P["attribute_nn.weight"].t() + P["attribute_nn.bias"]   # :263-264
-    node, recon_loss = node_embeddings(P, fe, xf, random_chrom, masks.get("adj"))
+    attr = mm(P["attribute_dict_embedding.weight"][xf], P["attribute_nn.weight"].t()) + P["attribute_nn.bias"]   # :263-264
+    node, recon_loss = node_embeddings(P, fe, xf, random_chrom, masks.get("adj"), ops)
     d = node.shape[-1]
     x0 = node + attr                                                       # :269
-    X = torch.tanh(x0 @ P["next_w.FF_Linear0.weight"].t() + P["next_w.FF_Linear0.bias"])   # :270
+    X = ops.tanh(mm(x0, P["next_w.FF_Linear0.weight"].t()) + P["next_w.FF_Linear0.bias"])   # :270
     X = X.view(B, L, d)
 
     # encode1.mul_head_attn  :513-575 (called as (dynamic, dynamic, static, key_pad) :612-613)
     pre = "encode1.mul_head_attn."
     H = N_HEAD
-    q = (_ln(X, P, pre + "layer_norm1") @ P[pre + "w_qs.weight"].t()).view(B, L, H, d)   # :519, :527
-    k = (_ln(X, P, pre + "layer_norm2") @ P[pre + "w_ks.weight"].t()).view(B, L, H, d)   # :520, :528
-    v = (_ln(X, P, pre + "layer_norm3") @ P[pre + "w_vs.weight"].t()).view(B, L, H, d)   # :521, :529
+    q = mm(_ln(X, P, pre + "layer_norm1"), P[pre + "w_qs.weight"].t()).view(B, L, H, d)   # :519, :527
+    k = mm(_ln(X, P, pre + "layer_norm2"), P[pre + "w_ks.weight"].t()).view(B, L, H, d)   # :520, :528
+    v = mm(_ln(X, P, pre + "layer_norm3"), P[pre + "w_vs.weight"].t()).view(B, L, H, d)   # :521, :529
     q = q.permute(2, 0, 1, 3).reshape(H * B, L, d)                        # :531-536
     k = k.permute(2, 0, 1, 3).reshape(H * B, L, d)
     v = v.permute(2, 0, 1, 3).reshape(H * B, L, d)
-    attn = torch.bmm(q, k.transpose(1, 2)) / math.sqrt(d)                 # :449-450 (temperature = d_k**0.5 :493)
+    attn = ops.bmm(q, k.transpose(1, 2)) / math.sqrt(d)                   # :449-450 (temperature = d_k**0.5 :493)
     eye = torch.eye(L, dtype=torch.bool).unsqueeze(0)
     attn = attn.masked_fill(eye, -1e32)                                   # :443-445 with diag_mask = 1 - eye :543-546
     attn = torch.softmax(attn, dim=-1)
-    o = torch.bmm(attn, v)                                                # :458
+    o = ops.bmm(attn, v)                                                  # :458
     o = o.view(H, B, L, d).permute(1, 2, 0, 3).reshape(B, L, H * d)       # :563-566
-    dyn = o @ P[pre + "fc1.weight"].t() + P[pre + "fc1.bias"]             # :572
+    dyn = mm(o, P[pre + "fc1.weight"].t()) + P[pre + "fc1.bias"]          # :572
     if "fc1" in masks:
         dyn = dyn * masks["fc1"].view(B, L, d)
 
     # encode1.pff_n1 ([d,d,d], residual, layer_norm)  :614, :353-376 ; Conv1d(k=1) == per-token Linear
     pp = "encode1.pff_n1."
     y = dyn * non_pad
-    h = torch.tanh(y @ P[pp + "PWF_Conv0.weight"][:, :, 0].t() + P[pp + "PWF_Conv0.bias"])   # :357-358
+    h = ops.tanh(mm(y, P[pp + "PWF_Conv0.weight"][:, :, 0].t()) + P[pp + "PWF_Conv0.bias"])   # :357-358
     if "pff" in masks:
         h = h * masks["pff"].view(B, L, d)                                 # :359-360
-    h = h @ P[pp + "PWF_Conv1.weight"][:, :, 0].t() + P[pp + "PWF_Conv1.bias"]               # :362
+    h = mm(h, P[pp + "PWF_Conv1.weight"][:, :, 0].t()) + P[pp + "PWF_Conv1.bias"]             # :362
     h = h + y                                                              # :370-371
     dynamic = _ln(h, P, pp + "layer_norm") * non_pad                      # :373-374, :614
 
@@ -206,7 +230,7 @@ def classifier_forward(P: Dict[str, torch.Tensor], fe: FrontEnd, x: torch.Tensor
     dynamic_n = _ln(dynamic, P, "layer_norm1")
     static_n = _ln(X, P, "layer_norm2")
     diff2 = (dynamic_n - static_n) ** 2                                    # :295
-    out = diff2 @ P["pff_classifier.PWF_Conv0.weight"][:, :, 0].t() + P["pff_classifier.PWF_Conv0.bias"]  # :299
+    out = mm(diff2, P["pff_classifier.PWF_Conv0.weight"][:, :, 0].t()) + P["pff_classifier.PWF_Conv0.bias"]  # :299
     logits = (out * non_pad).sum(dim=-2) / (non_pad.sum(dim=-2) + 1e-15)  # :309-311
     if return_intermediates:
         return logits, recon_loss, dict(x0=x0, X=X, q=q, k=k, v=v, attn=attn, o=o, dyn=dyn, y=y,

@@ -40,17 +40,18 @@ def g3big_grad_ref(g, name):
     raise KeyError(name)
 
 
-def oracle_state(num, d, mode, seed, requires_grad=False):
-    """(P, fe, sd_numpy): the same deterministic weights/features make_golden.py loaded into the reference."""
+def oracle_state(num, d, mode, seed, requires_grad=False, dtype=torch.float32):
+    """(P, fe, sd_numpy): the same deterministic weights/features make_golden.py loaded into the reference; P and fe in ``dtype``
+    (torch.float64: the fp64 oracle of tests/fp64_grade.py), sd as generated (float32)."""
     attr = O.attribute_table(num)
     sd = synth.make_state_dict(np.random.default_rng(seed), num, d, mode, attr)
     P = {}
     for k, v in sd.items():
-        t = torch.from_numpy(np.array(v))
+        t = torch.from_numpy(np.array(v)).to(dtype)
         if requires_grad and not k.startswith("attribute_dict"):
             t.requires_grad_(True)
         P[k] = t
-    fe = front_end(num, mode, seed)
+    fe = front_end(num, mode, seed).to(dtype)
     return P, fe, sd
 
 

@@ -128,7 +128,7 @@ def _sparse_worker(rank, world, port, out_dir):
         mode, bounds, n_chrom, n_nodes = "table", fe.bounds, fe.n_chrom, fe.n_nodes
     import oracle.hypersagnn as OH
     orig = OH.node_embeddings
-    OH.node_embeddings = lambda P_, fe_, xf, rc=None, am=None: (rows_in * (xf != 0).unsqueeze(-1), torch.zeros(1))
+    OH.node_embeddings = lambda P_, fe_, xf, rc=None, am=None, ops=None: (rows_in * (xf != 0).unsqueeze(-1), torch.zeros(1))
     try:
         loss, *_ = O.total_loss(P2, fe, xs, ys, ws, 1.0, 0.0)
         g_rows, = torch.autograd.grad(loss, [rows_in])

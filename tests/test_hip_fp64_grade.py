@@ -1,0 +1,201 @@
+"""Every kernel route of the training step held to fp32 grade against the fp64 oracle (tests/fp64_grade.py): one dropout-free
+Trainer.forward_backward step and the eval-mode model(x) of each case, every output within K = 8 times the fp32 oracle's own noise.
+The parity tests elsewhere allow 1e-4 (the north star); a kernel that silently loses a factor of 20 -- a dropped bf16 plane product,
+a tanh that is only accurate in absolute terms -- passes them and fails here.  Each case also asserts its kernel set (a size rule that
+moves a case onto other kernels fails it) and that its bound is tight enough to reject the three-product witness.  GPU only (-m gpu).
+"""
+import contextlib
+from dataclasses import dataclass, field, replace
+from typing import Dict, FrozenSet, Tuple
+
+import numpy as np
+import pytest
+import torch
+
+from matcha_amd import synth, _lib
+from tests import fp64_grade as G
+from tests.helpers import oracle_state
+from tests.test_hip_model import hip_model, _trainer_grads
+
+pytestmark = pytest.mark.gpu
+
+# kernel sets (matcha_launch_log): what each case must run and must not run, so that a size rule or a switch that moves a case onto other
+# kernels fails it instead of quietly testing something else.  The sets of t16 / a32 and the sorted-gradient kernels were read off the
+# first MI355X run and frozen.
+_BIG64 = frozenset({"fused_fwd32_kernel", "tail_bwd64_kernel", "fused_bwdh_kernel", "fbm_reduce_kernel", "fbm_chain_kernel"})
+_FRONT64 = frozenset({"front_fwd3_kernel", "front_bwd_kernel"})
+_ADJ64 = frozenset({"adj_fused_fwd_kernel", "adj_recon_kernel", "adj_fused_bwd_kernel"})
+_ENC128 = frozenset({"enc128_fwd_kernel", "enc128_bwd_kernel", "enc128_unfold_kernel", "head_fwd_kernel", "head_bwd_kernel"})
+_WIDE = frozenset({"gemm_wide_kernel", "gemm_tn_wide_kernel", "attn_fwd_wide_kernel", "attn_bwd_wide_kernel"})
+_LAYERWISE = frozenset({"attn_fwd_kernel", "attn_bwd_kernel", "ln3_fwd_kernel", "ln3_bwd_kernel", "head_fwd_kernel", "head_bwd_kernel",
+                        "gemm_lds_kernel", "gemm_tn_kernel", "embed_fwd_kernel", "embed_scatter_kernel"})
+_SORTED_TABLE = frozenset({"tg_hist_kernel", "tg_idscan_kernel", "tg_place_kernel", "tg_runsum_kernel", "tg_colscan_kernel"})
+_SMALL = frozenset({"fused_fwd32h_kernel", "plan_small_kernel"})
+_NOT_FUSED = frozenset({"fused_fwd32_kernel", "fused_fwd32h_kernel", "fused_bwdh_kernel", "enc128_fwd_kernel", "attn_fwd_wide_kernel"})
+
+
+@dataclass(frozen=True)
+class Case:
+    layout: str
+    d: int
+    mode: str
+    seed: int                              # weights (and the adj features)
+    ks: Tuple[int, ...] = (2, 3, 4, 5)
+    rows_per_k: int = 1024
+    L: int = 0
+    rows: object = None                    # None = the whole batch; an int, or "edge-" / "edge+" (size rule, resolved on the device)
+    batch_seed: int = 0                    # 0: seed + 500
+    route: str = ""                        # "det" | "nolif" | "fourprod" | "layerwise"
+    objective: str = "class"
+    stress: str = ""                       # "small" | "sharp" | "saturated" | "hot"
+    must: FrozenSet[str] = frozenset()
+    must_not: FrozenSet[str] = frozenset()
+    k_of: Dict[str, float] = field(default_factory=dict, hash=False, compare=False)
+
+
+T64 = Case("hg38_1mb", 64, "table", 81, must=_BIG64 | _FRONT64,
+           must_not=_SMALL | _SORTED_TABLE | {"embed_fwd_kernel", "front_fwd_kernel", "head_bwd_kernel", "attn_fwd_kernel"})
+A64 = Case("hg38_1mb", 64, "adj", 82, must=_BIG64 | _ADJ64, must_not=_SMALL | {"adj_encode_fwd_kernel", "front_fwd3_kernel", "attn_fwd_kernel"})
+T128 = Case("c1", 128, "table", 83, ks=(2, 3, 4, 5, 6, 7, 8), rows_per_k=585, must=_ENC128,
+            must_not={"attn_fwd_wide_kernel", "attn_bwd_wide_kernel", "attn_fwd_kernel", "attn_bwd_kernel"})
+_TINY = dict(batch_seed=1009, must=_SMALL | _FRONT64 | {"fused_bwdh_kernel"}, must_not={"fused_fwd32_kernel", "tail_bwd64_kernel"})
+
+CASES = {
+    "t64_big": T64,
+    "t64_det": replace(T64, route="det", must=T64.must | _SORTED_TABLE, must_not=T64.must_not - _SORTED_TABLE),
+    "t64_nolif": replace(T64, route="nolif", must=(T64.must - {"tail_bwd64_kernel"}) | {"head_bwd_kernel"},
+                         must_not=(T64.must_not - {"head_bwd_kernel"}) | {"tail_bwd64_kernel"}),
+    # at embed_dim 64 both switches land on the layer-by-layer kernels with the reference's four products per head
+    "t64_fourprod": replace(T64, route="fourprod", must=_LAYERWISE, must_not=_BIG64 | _FRONT64 | _SMALL),
+    "t64_layerwise": replace(T64, route="layerwise", must=_LAYERWISE, must_not=_BIG64 | _FRONT64 | _SMALL),
+    # the last batch size whose half tiles fit two per CU (the one-workgroup-per-half forward; the plan there is already the multi-launch
+    # one) and the first that does not
+    "t64_edge-": replace(T64, rows="edge-", must={"fused_fwd32h_kernel", "fused_bwdh_kernel"} | _FRONT64, must_not={"fused_fwd32_kernel", "tail_bwd64_kernel"}),
+    "t64_edge+": replace(T64, rows="edge+"),
+    # (a batch whose first rows let the witness show: at one to three rows its logit error is a matter of the rows drawn)
+    "t64_tiny1": replace(T64, rows=1, **_TINY),
+    "t64_tiny2": replace(T64, rows=2, **_TINY),
+    "t64_tiny3": replace(T64, rows=3, **_TINY),
+    "t64_k8": Case("c23", 64, "table", 84, ks=(2, 3, 4, 5, 6, 7, 8), rows_per_k=585, L=8, must=T64.must, must_not=T64.must_not),
+    "t64_nattr5": Case("c1", 64, "table", 85, rows_per_k=512, must={"embed_fwd_kernel", "embed_scatter_kernel", "fused_fwd32h_kernel",
+                                                                     "fused_bwdh_kernel", "lnhat_bwd_kernel"}, must_not=_FRONT64),
+    "a64_hg38": A64,
+    "a64_wide": replace(A64, layout="wide_adj", seed=86),
+    "t128": T128,
+    "a128_wide": Case("wide_adj", 128, "adj", 87, ks=(2, 3, 4, 5, 6, 7, 8), rows_per_k=585,
+                      must=_ENC128 | {"adj_encode_fwd_kernel", "adj_tn_kernel<1>"}, must_not=T128.must_not | _ADJ64),
+    "t256": Case("c1", 256, "table", 88, ks=(2, 3, 4, 5, 6, 7, 8), rows_per_k=286, must=_WIDE, must_not={"enc128_fwd_kernel", "enc128_bwd_kernel", "fused_fwd32_kernel"}),
+    "t16": Case("tiny", 16, "table", 89, rows_per_k=64, must=_LAYERWISE | {"plan_small_kernel"}, must_not=_NOT_FUSED),
+    "a32": Case("tiny", 32, "adj", 90, rows_per_k=64, must=(_LAYERWISE - {"embed_scatter_kernel"}) | {"plan_small_kernel", "adj_encode_fwd_kernel",
+                "adj_sort_small_kernel", "adj_tn_kernel<0>", "adj_tn_kernel<1>"}, must_not=_NOT_FUSED | _ADJ64),
+    # pff_classifier's bias gradient is ONE number, the sum of 4 096 dlogits 2 (softplus(z) - y) softplus'(z) / B that cancel 40 : 1, so its
+    # e is a single draw of the logits' propagated rounding noise and so is the fp32 noise it is divided by (measured ratio 7.6): K 16
+    "r64": replace(T64, objective="regress", k_of={"pff_classifier.PWF_Conv0.bias": 16.0}),
+}
+for _base in ("t64_big", "a64_hg38", "t128"):
+    for _s in ("small", "sharp", "saturated", "hot"):
+        _c = CASES[_base]
+        CASES[f"{_base}_{_s}"] = replace(_c, stress=_s, rows_per_k=3 * _c.rows_per_k if _s == "hot" else _c.rows_per_k)
+CASES["t128_hot"] = replace(CASES["t128_hot"], batch_seed=1101)          # (the default batch leaves the witness only 2.0x out)
+CASES["t64_big_hot_det"] = replace(CASES["t64_big_hot"], route="det", must=CASES["t64_det"].must, must_not=CASES["t64_det"].must_not)
+
+RESULTS = {}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _ratio_table():
+    yield
+    if RESULTS:
+        print("\nfp32 grade: worst e(HIP) / noise per case (step: logits, losses, every gradient; eval: model(x) logits)")
+        for name, (step, ev, wit) in RESULTS.items():
+            print(f"  {name:22s} step {step:5.2f}   eval {ev:5.2f}   witness {wit:6.1f} x bound")
+
+
+def _halves_cap(T, L):
+    """ragged.hip halves_cap: the half tiles the ragged plan provisions for T tokens of rows of L slots."""
+    cdiv = lambda a, b: -(-a // b)
+    return cdiv(T + 1, 32 - L) + cdiv(T + 1, 63 * 32)
+
+
+def _edge_rows(which, L):
+    """The batch size at which halves_cap(B L, L) last stays at 2 CU (edge-: the small-batch forward) and the next one (edge+)."""
+    cap = 2 * torch.cuda.get_device_properties(0).multi_processor_count
+    B = 1
+    while _halves_cap((B + 1) * L, L) <= cap:
+        B += 1
+    assert _halves_cap(B * L, L) <= cap < _halves_cap((B + 1) * L, L)
+    return B if which == "edge-" else B + 1
+
+
+_DATA = {}
+
+
+def _data(c: Case):
+    """(sd, fe, x, y, w, chrom, references, three-product witness) of a case; cached, several routes share one batch."""
+    key = replace(c, route="", must=frozenset(), must_not=frozenset())
+    if key in _DATA:
+        return _DATA[key]
+    num = synth.LAYOUTS[c.layout]
+    _, fe, sd = oracle_state(num, c.d, c.mode, c.seed)
+    x, y, w = G.make_case_batch(c.layout, list(c.ks), c.rows_per_k, c.batch_seed or c.seed + 500, c.L)
+    if c.rows is not None:
+        n = _edge_rows(c.rows, x.shape[1]) if isinstance(c.rows, str) else c.rows
+        assert n <= len(x)
+        x, y, w = x[:n], y[:n], w[:n]
+    chrom = int(np.random.default_rng(c.seed).integers(fe.n_chrom))
+    if c.stress == "small":
+        sd = G.small_amplitude(sd)
+    elif c.stress == "sharp":
+        sd = G.sharp_attention(sd)
+    elif c.stress == "saturated":
+        sd = G.saturated_logits(sd, fe, x, chrom)
+        w = w.copy()
+        w[::5] = 0.0
+    elif c.stress == "hot":
+        x = G.hot_node(x, 0.85)                             # 85 % of 12 285 - 12 288 rows: > 10^4 addends into one table row
+    if c.objective == "regress":
+        y = np.where(y > 0, w, 0.0).astype(np.float32)       # positive rows carry a target in [0.5, 4), negatives 0
+        w = None
+    ref = G.references(sd, fe, x, y, w, chrom=chrom, objective=c.objective)
+    wit = G.oracle_step(sd, fe, x, y, w, chrom=chrom, objective=c.objective, ops=G.THREE_PRODUCT, backward=False)
+    _DATA[key] = (sd, fe, x, y, w, chrom, ref, wit)
+    return _DATA[key]
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_step_and_eval_at_fp32_grade(name):
+    from matcha_amd.engine import Trainer
+    c = CASES[name]
+    sd, fe, x, y, w, chrom, ref, wit = _data(c)
+    clf, _ = hip_model(synth.LAYOUTS[c.layout], c.d, c.mode, c.seed, sd=sd)
+    for m in clf.modules():
+        if isinstance(m, torch.nn.Dropout):
+            m.p = 0.0
+    clf.train()
+    switch = {"fourprod": "disable_merged", "layerwise": "disable_fused"}.get(c.route)
+    with (_lib.option(switch) if switch else contextlib.nullcontext()):
+        tr = Trainer(clf, lr=1e-3, deterministic=(c.route == "det"), objective=c.objective)
+        if c.route == "nolif":
+            tr.loss_in_forward = False
+        xd = torch.from_numpy(x).cuda().contiguous()
+        yd = torch.from_numpy(y).cuda().contiguous()
+        wd = None if w is None else torch.from_numpy(w).cuda().contiguous()
+        with _lib.launch_log() as log:
+            logits = tr.forward_backward(xd, yd, wd, 1.0, 0.001, chrom)
+            torch.cuda.synchronize()
+        grads = {n: (None if v is None else v.cpu().double().numpy()) for n, v in _trainer_grads(tr, clf).items()}
+        got = G.StepOut(logits.cpu().double().numpy(),
+                        {G.main_loss_name(c.objective): float(tr.losses[0]), "recon": float(tr.losses[1])}, grads)
+        clf.eval()
+        with torch.no_grad():
+            lg_eval = clf(xd).cpu().double().numpy()
+    ran = {k for k, n in log.counts.items() if n > 0}
+    print(f"{name}: B = {len(x)}, L = {x.shape[1]}, kernels {sorted(ran)}")
+    ratio = G.assert_grade(f"{name} step", G.grade(got, ref, c.k_of))
+    ratio_eval = G.assert_grade(f"{name} eval", G.logit_rows(lg_eval, ref, c.k_of.get("logits", G.K)))
+    # the bound must be tight enough to reject the three-product witness (its forward is enough)
+    wit_over = max(r.err / (r.k * r.noise) for r in G.logit_rows(wit.logits, ref, c.k_of.get("logits", G.K)))
+    RESULTS[name] = (ratio, ratio_eval, wit_over)
+    assert wit_over >= 2.0, (name, wit_over)
+    assert set(c.must) <= ran, (name, sorted(set(c.must) - ran), sorted(ran))
+    assert not (set(c.must_not) & ran), (name, sorted(set(c.must_not) & ran))

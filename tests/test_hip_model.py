@@ -19,11 +19,13 @@ TOL = 1e-4     # north_star: <= 1e-4 rel fp32
 GAUGE = "encode1.mul_head_attn.layer_norm2.bias"    # see tests/test_oracle_golden.py
 
 
-def hip_model(num, d, mode, seed):
-    """Our Modules.Classifier on cuda:0 with the deterministic synthetic weights."""
+def hip_model(num, d, mode, seed, sd=None):
+    """Our Modules.Classifier on cuda:0 with the deterministic synthetic weights (or the state dict ``sd``, e.g. a transformed copy of
+    them; the adj front end's features still come from ``seed``)."""
     import Modules as M
     attr = O.attribute_table(num)
-    sd = synth.make_state_dict(np.random.default_rng(seed), num, d, mode, attr)
+    if sd is None:
+        sd = synth.make_state_dict(np.random.default_rng(seed), num, d, mode, attr)
     N = int(np.sum(num))
     if mode == "table":
         ne = M.Wrap_Embedding(N + 1, d, padding_idx=0)
