@@ -504,6 +504,29 @@ int matcha_corrcoef_block(const float* adj, int64_t ld, int32_t n, float* out, v
                           matcha_stream_t stream);
 int matcha_zscore_rows(float* matrix, int64_t rows, int64_t cols, matcha_stream_t stream);
 
+/* ---- denoised contact maps (Code/denoise_contact.py:147-207) ----------------------------------------------------------
+ * One chromosome [lo, hi) of chrom_range, n = hi - lo bins, pairs (i, j) with i + min_dis <= j in generate_pair_wise order: row
+ * r = i - lo holds max(0, n - min_dis - r) pairs, stored contiguously.  Bit for bit with the reference's numpy for the same inputs.
+ * matcha_denoise_intra   the post-processing up to the quantile transforms (:160-188):
+ *     proba        device float32 [n_pairs]: the sweep's probabilities (n_pairs = K (K + 1) / 2, K = n - min_dis)
+ *     origin       device float32, element (lo - 1, lo - 1) of intra_adj, row stride origin_ld >= n (elements)
+ *     my, origin_part, my_proba   device float32 [n, n]: the three matrices the reference hands to its QuantileTransformer,
+ *                  my and my_proba with the gap rows / columns zeroed; none may alias another or an input
+ *     gap          device uint8 [2 n]: gap1 (row sums of the observed matrix == 0) then gap2 (column sums == 0)
+ *     ws           matcha_denoise_workspace_bytes(n) bytes: six coverage vectors, 24 n bytes rounded up to 256 (597 760 bytes at
+ *                  n = 24 900; the matrices themselves live in the caller's outputs)
+ *   Refuses, before any device call: a null pointer, n < 1 or n * n >= 2^31 (the quantile transform's limit), min_dis outside
+ *   [0, n) (no pairs), an n_pairs that does not match n and min_dis, origin_ld < n, a workspace that is too small.
+ * matcha_denoise_pixels  balanced = m[i - lo, j - lo] for every pair, in pair order (:205-207): out device float32 [n_pairs].
+ * Deliberate differences from the reference: (a) the quantile transforms between the two calls fit on all n^2 values
+ * (subsample=None; identical to scikit-learn's default up to n = 100); (b) a chromosome without pairs is refused here and skipped by
+ * matcha_amd/denoise.py, where the reference crashes; (c) the .mcool container is written only when h5py imports (always an .npz). */
+size_t matcha_denoise_workspace_bytes(int32_t n);
+int matcha_denoise_intra(const float* proba, int64_t n_pairs, int32_t n, int32_t min_dis, const float* origin, int64_t origin_ld,
+                         float* my, float* origin_part, float* my_proba, uint8_t* gap, void* ws, size_t ws_bytes,
+                         matcha_stream_t stream);
+int matcha_denoise_pixels(const float* m, int32_t n, int32_t min_dis, float* out, matcha_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -119,6 +119,9 @@ SIGNATURES = {
     "matcha_corrcoef_workspace_bytes": (_SZ, [_I32]),
     "matcha_corrcoef_block": (C.c_int, [_fp, _I64, _I32, _fp, _fp, _SZ, _fp]),
     "matcha_zscore_rows": (C.c_int, [_fp, _I64, _I64, _fp]),
+    "matcha_denoise_workspace_bytes": (_SZ, [_I32]),
+    "matcha_denoise_intra": (C.c_int, [_fp, _I64, _I32, _I32, _fp, _I64, _fp, _fp, _fp, _fp, _fp, _SZ, _fp]),
+    "matcha_denoise_pixels": (C.c_int, [_fp, _I32, _I32, _fp, _fp]),
 }
 
 OBJECTIVE_BCE, OBJECTIVE_SOFTPLUS_MSE = 0, 1      # MATCHA_OBJECTIVE_* of include/matcha_hip.h
