@@ -171,9 +171,16 @@ typedef struct matcha_frozen {
                                 multiple of 4 -- aligned 16-byte loads of feature rows; the fused embed_dim-64 kernels
                                 (csrc/adj_fused.hip) require P = 64, other values run the layer-by-layer kernels               */
   int32_t attr_mode;         /* 0 = attribute rows are read from attr_table; 1 = the table has the structure main.py:497-512 builds
-                                (one-hot chromosome || bin index inside the chromosome / attr_scale, row 0 zeros) and is NOT read:
-                                a token's row is rebuilt from its node id, attr_bounds and attr_scale (one random row per token
-                                instead of two; the caller has verified the structure bit for bit, attr_table may be NULL)     */
+                                (one-hot chromosome || bin index inside the chromosome / attr_scale, row 0 zeros; the caller has
+                                verified it bit for bit) and kernels MAY rebuild a token's row from its node id, attr_bounds and
+                                attr_scale instead of reading it (one random row per token instead of two).  Not every kernel
+                                rebuilds: at embed_dim 64 the fused forward does, while the fused front end's backward and the
+                                layer-by-layer attribute_nn backward gather attr_table.  So attr_table is to be given under
+                                attr_mode 1 as well: the fused embed_dim-64 front end (forward and backward) and every
+                                layer-by-layer backward return MATCHA_EINVAL without it; only forward calls that run
+                                embed_fwd_kernel or the fused adj forward do without.  Its CONTENTS must equal the rows computed
+                                from attr_bounds and attr_scale -- all three derived from one snapshot of the table -- or the
+                                forward and the backward of one step read different attribute rows                            */
   int32_t attr_ld;           /* attr_mode 0: row stride of attr_table in floats (0 = n_attr); 32 = rows padded to one 128-byte
                                 fetch unit                                                                                       */
   float attr_scale;          /* attr_mode 1: num[0] of main.py:503                                                               */
@@ -248,7 +255,12 @@ int matcha_forward(const matcha_shape* shp, const matcha_tensors* params, const 
  * gradient this step: [0] always 1, [1] table, [2+i] adj encoder of chromosome i, [2+C+i] recon head i --
  * these are the tensors whose grad is not None in the reference (SURVEY.md §7 "AdamW semantics").
  * The call CONSUMES the activations its forward left in `ws` (gradients overwrite them): one backward per forward,
- * as loss.backward() without retain_graph. */
+ * as loss.backward() without retain_graph.  The library keeps a host-side record per workspace pointer of the last
+ * differentiable forward: it is written by a forward without opts->forward_only, dropped by a forward WITH it (which
+ * keeps nothing for a backward and overwrites what was there) and dropped by the backward that consumed it.
+ * matcha_backward on a workspace without a record -- never used, last used by a forward_only forward, already
+ * consumed by a backward, or evicted (the 4096 most recent workspaces are remembered) -- returns MATCHA_EINVAL
+ * before any launch. */
 int matcha_backward(const matcha_shape* shp, const matcha_tensors* params, const matcha_frozen* frozen,
                     const matcha_step_opts* opts, const int64_t* x, int64_t B, int32_t L,
                     const float* y, const float* w, const float* dlogits, const float* drecon,

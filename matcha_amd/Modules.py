@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import weakref
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -317,8 +318,30 @@ def _attr_structure(table: torch.Tensor):
 
 class _Runtime:
     """Flat storage for the LIVE parameters (one buffer -> one AdamW launch, one all-reduce bucket) plus the
-    ctypes descriptors handed to the C ABI.  Rebuilt whenever a parameter's storage moved (``.to()``,
-    ``load_state_dict`` into fresh tensors, unpickling)."""
+    ctypes descriptors handed to the C ABI, and derived copies of the FROZEN inputs: the attribute table
+    (padded to 32 floats, with the attr_mode / attr_bounds / attr_scale decision taken from it) and, on the adj front
+    end, the re-packed feature blocks; inter_initial is a copy or, when it already is float32 on the device, an alias.
+
+    What keeps it valid (``still_packed``; tests/test_hip_state.py part A):
+    * live parameters are views into ``flat``: in-place writes (``load_state_dict``, optimizers, ``copy_``) need no
+      rebuild -- the kernels read the new values; a parameter whose storage MOVED (``p.data = ...``, a device change,
+      unpickling, ``deepcopy``) makes the runtime stale;
+    * frozen inputs are tracked by (data_ptr, _version) of the tensor the module tree holds at the time of the call, looked up from
+      the model itself (``model.attribute_dict_embedding.weight``, ``model.node_embedding.embeddings[i].embedding``,
+      ``.inter_initial.embedding``): ``load_state_dict``, an in-place ``copy_``, the assignment of a new tensor / Parameter and the
+      replacement of one of these sub-modules as a whole are all seen.  A rewrite
+      of the attribute table with the SAME bytes (train() reloads its checkpoint at the end of every phase) is accepted
+      after one device compare per version bump; any other change makes the runtime stale.
+    A stale runtime is rebuilt by ``Classifier._runtime()`` on the model's next call, with every derived quantity taken
+    again from the new tensors; a Trainer holds on to the runtime it was built with and raises instead.
+    NOT detectable: an in-place edit through ``.data`` (``w.data.add_(1)``) bumps no version counter.  For a live parameter
+    that is harmless (the kernels read the storage itself); for a frozen input the derived copies go stale silently, so
+    change frozen inputs through one of the tracked paths only.  There is deliberately no per-call device compare.  Live parameters
+    are tracked by OBJECT: assigning a new ``nn.Parameter`` (or a new sub-module) in place of a live one is not seen either; write
+    into the existing parameter instead.
+    Cost: the table front end compares one pair of integers per call.  The adj front end builds a tuple of n_chrom + 1 such pairs per
+    model call / eager Trainer step (host Python, no device work); its effect on eager adj steps has not been measured -- bench.py times
+    the table front end, and captured replays do not pass through here."""
 
     def __init__(self, model: "Classifier"):
         self.lib = _lib.load()
@@ -393,12 +416,16 @@ class _Runtime:
         self.seg_off = torch.tensor(seg_off, dtype=torch.int64, device=dev)
         self.seg_group = torch.tensor(seg_group, dtype=torch.int32, device=dev)
         self.n_touched = 2 + 2 * self.n_chrom
-        # frozen inputs
+        # frozen inputs.  The kernels work on PRIVATE copies of them (the table padded to 32 floats, the feature blocks re-packed) and on
+        # structure decided from the table once, so the runtime remembers which tensor state -- (data_ptr, _version) of what the module
+        # tree holds NOW, read from the MODEL at call time (a weak reference: the model owns the runtime), not through a tensor or a
+        # sub-module captured here -- those copies were taken from (still_packed)
+        self._model = weakref.ref(model)
         self.attr_table = attr_mod.weight.detach().to(device=dev, dtype=torch.float32).contiguous()
-        # the kernels work on a (padded) COPY of this frozen table and on structure decided from it once: remember which tensor state that was
-        self._attr_src = attr_mod.weight
-        self._attr_ref = self.attr_table                      # the unpadded device copy the structure decision was taken from
-        self._attr_src_state = (attr_mod.weight.data_ptr(), attr_mod.weight._version)
+        if self.attr_table.data_ptr() == attr_mod.weight.data_ptr():
+            self.attr_table = self.attr_table.clone()         # a float32 table already on the device: .to() / .contiguous() return the weight itself
+        self._attr_ref = self.attr_table                      # the unpadded private copy the structure decision is taken from: a snapshot, never the live weight
+        self._attr_src_state = self._tensor_state(attr_mod.weight)
         self._keep = [self.attr_table]
         self.frozen = _lib.Frozen()
         self.frozen.attr_table = self.attr_table.data_ptr()
@@ -414,8 +441,9 @@ class _Runtime:
             self.frozen.attr_bounds = self.attr_bounds.data_ptr()
             self.attr_mode = 1
             self._keep.append(self.attr_bounds)
-        # (the table stays available under attr_mode 1: the fused embed_dim-64 front end keeps gathering its rows -- attr_src.hpp --
-        # and the layer-by-layer attribute_nn backward reads them as the B operand of its weight-gradient product)
+        # (the table stays available under attr_mode 1: the fused embed_dim-64 forward rebuilds a row from its node id and never reads
+        # it, while front_bwd_kernel and the layer-by-layer path -- embed_fwd_kernel, the attribute_nn weight-gradient product -- still
+        # gather its rows.  Bounds, scale and table are therefore always derived from ONE snapshot, here)
         if self.n_attr < 32 and ATTR_PAD:
             self.attr_table = torch.nn.functional.pad(self.attr_table, (0, 32 - self.n_attr)).contiguous()
             self._keep[0] = self.attr_table
@@ -445,6 +473,9 @@ class _Runtime:
             self.frozen.inter = self.inter.data_ptr()
             self.frozen.bounds_host = self.bounds_host.ctypes.data
             self._keep += [self.feat_pack, self.inter, self.bounds_dev, self.feat_off_dev]
+            # the reference reads embeddings[i].embedding and inter_initial.embedding on every forward; feat_pack is a re-packed copy
+            # and `inter` a copy or an alias: remember the state they were taken from
+            self._adj_src_state = self._adj_state(ne)
         self.shape = _lib.Shape(d, self.n_attr, self.n_nodes, self.n_chrom, self.mode, self.max_bins)
         self.params = self.tensors_for(self.flat)
         self.seed = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -472,18 +503,36 @@ class _Runtime:
             setattr(t, field, base + 4 * off)
         return t
 
+    @staticmethod
+    def _tensor_state(t: torch.Tensor):
+        return (t.data_ptr(), t._version)
+
+    def _adj_state(self, ne):
+        if not hasattr(ne, "embeddings"):
+            return None             # the front end was replaced by another kind: stale
+        return tuple(self._tensor_state(e.embedding) for e in ne.embeddings) + (self._tensor_state(ne.inter_initial.embedding),)
+
     def still_packed(self) -> bool:
-        """The live parameters still sit where the kernels were told, and the frozen attribute table has not been rewritten in place
-        (load_state_dict after the first forward: the runtime holds a padded copy and a cached structure decision) -- otherwise the
-        owner rebuilds the runtime."""
-        state = (self._attr_src.data_ptr(), self._attr_src._version)
+        """True while the runtime's view of the model is valid: the live parameters still sit where the kernels were told, and the
+        frozen inputs the runtime keeps derived copies of -- the attribute table (padded copy, attr_mode / bounds / scale), on the adj
+        front end the feature blocks (feat_pack) and inter_initial -- are the tensors, in the state, the copies were taken from.
+        Otherwise the owner rebuilds the runtime (Classifier._runtime) or refuses to go on (Trainer).  Two tuples of integers are
+        compared per call: no device work and no synchronisation on a call where nothing changed."""
+        model = self._model()
+        if model is None:
+            return False
+        w = model.attribute_dict_embedding.weight
+        state = self._tensor_state(w)
         if state != self._attr_src_state:
             # a version bump alone is not a change: train() ends every phase with load_state_dict(model_link), which copy_()s the same bytes
-            # into the frozen table (ADVICE r05).  Compare ONCE per bump (one synchronising device compare) and accept an identical table.
-            src = self._attr_src.detach()
+            # into the frozen table (ADVICE r05).  Compare ONCE per bump (one synchronising device compare, against the private snapshot)
+            # and accept an identical table.
+            src = w.detach()
             if tuple(src.shape) != tuple(self._attr_ref.shape) or not torch.equal(src.to(device=self.device, dtype=torch.float32), self._attr_ref):
                 return False
             self._attr_src_state = state
+        if self.mode == 1 and self._adj_state(model.node_embedding) != self._adj_src_state:
+            return False            # (nothing rewrites these with the same bytes -- they are not in the state dict --, so any change rebuilds)
         return all(p.data_ptr() == e for p, e in zip(self.live, self.expected_ptrs))
 
     def workspace(self, B: int, L: int, forward_only: bool = False) -> torch.Tensor:
@@ -546,7 +595,12 @@ class _ClassifierFn(torch.autograd.Function):
 class Classifier(nn.Module):
     """Hyper-SAGNN hyperedge classifier (reference Modules.py:204-318): same constructor, parameters and call
     surface; forward = fused gfx950 kernels.  ``model(x)`` returns LOGITS [B,1] (callers apply sigmoid, as in
-    main.py:58 / predict_multiway.py:113)."""
+    main.py:58 / predict_multiway.py:113).
+
+    A call's result depends on the module tree as it is AT the call: train() / eval(), every ``Dropout.p``, the live
+    parameters and the frozen inputs (attribute table, adj feature blocks, inter_initial) are read per call, and a
+    model changed after its first forward through ``load_state_dict``, ``copy_``, tensor assignment, ``.to()``,
+    ``deepcopy`` or pickling behaves like a freshly built one (``_Runtime`` says how, and what is not detectable)."""
 
     def __init__(self, n_head, d_model, d_k, d_v, node_embedding, diag_mask, bottle_neck, attribute_dict=None, **args):
         super().__init__()

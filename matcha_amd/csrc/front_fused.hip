@@ -570,9 +570,10 @@ int front_grid() {
 
 int launch_front_fwd(const matcha_tensors& p, const int64_t* ids, const float* table, const float* dense, const matcha_frozen& f, int n_attr,
                      const Ragged& rg, int64_t tcap, float* x0, float* X, hipStream_t st, const PrepSpec* prep) {
-  // the fused front end GATHERS attribute rows (rows padded to one 128-byte unit when the caller padded them, attr_ld): its row pieces are
-  // loaded by eight threads per row inside a register prefetch pipeline; rebuilding them from the node id there (attr_mode 1) put a branch
-  // around the loads and cost 20 % of front_bwd_kernel -- embed_fwd_kernel and the fused adj forward, one thread / one lane pair per row, do rebuild
+  // attr_mode 1: this forward (front_fwd3_kernel) rebuilds a token's attribute row from its node id and reads no table; front_bwd_kernel
+  // keeps GATHERING the rows (padded to one 128-byte unit when the caller padded them, attr_ld): its row pieces are loaded by eight threads
+  // per row inside a register prefetch pipeline, and rebuilding them there put a branch around the loads and cost 20 % of the kernel.  So the
+  // table's contents must equal the computed rows (include/matcha_hip.h, matcha_frozen.attr_mode).  Any other table: front_fwd_kernel gathers
   MATCHA_CHECK_ARG(f.attr_table, "front end: attr_table is required (also under attr_mode 1)");
   FrontFwdArgs g;
   // attr_mode 1 (the table has get_attributes' structure): front_fwd3_kernel -- no attribute rows gathered, no attribute product; any other

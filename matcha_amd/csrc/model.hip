@@ -187,7 +187,13 @@ static int ws_state(const void* ws) {       // -1: no forward on record for this
   auto it = g_fwd_state.find(ws);
   return it != g_fwd_state.end() ? it->second.first : -1;
 }
-static bool fwd_ran_merged(const void* ws) { return ws_state(ws) > 0 && (ws_state(ws) & 1) != 0; }
+// The record of a workspace is dropped by a forward_only forward on it (which keeps nothing a backward could read and overwrites what an
+// earlier training forward left there) and by the backward that consumed it (matcha_backward overwrites the saved activations with their
+// gradients): a backward then finds no record and is refused before any launch.
+static void forget_forward(const void* ws) {
+  std::lock_guard<std::mutex> lk(g_fwd_mu);
+  g_fwd_state.erase(ws);
+}
 
 // B_all[h d + a][b] = sum_m W_k[h d + m][a] W_q[h d + m][b];   M_all[n][h d + b] = sum_m Wfc1[n][h d + m] W_v[h d + m][b]   (16 small GEMMs)
 static int merged_weights(const matcha_shape& s, const matcha_tensors& p, Workspace& w, hipStream_t st) {
@@ -512,7 +518,7 @@ static int forward_impl(const matcha_shape* shp, const matcha_tensors* params, c
     // the backward kernel's heads ADD their d x_hat rows (float atomics) unless the sum has to be reproducible: the rows are zeroed by a launch
     // that runs anyway -- tail_bwd64_kernel, or for small batches the loss reduction's -- and the record says so
     const bool zero_dx = lif && !opts->deterministic && !opts->sparse_table_grad && (split_tail || fused_small_batch(w.rg)) && tgt && losses;
-    note_forward(ws, true, true, false, split_tail, zero_dx);
+    if (opts->forward_only) forget_forward(ws); else note_forward(ws, true, true, false, split_tail, zero_dx);
     // (with the tail's backward in the forward kernel, Y and H1 are still handed over: the single-wave kernel PARKS the two rows there
     // (and the normalised H2 row in H2's place) between the tail's forward and backward halves instead of holding 96 registers per lane -- fused_fwd32_tail.hpp)
     MATCHA_TRY(launch_fused_fwd32(p, w.folded, w.frag, w.X, w.rg, B, L, y, w_bce, (save || lif) ? w.Y : nullptr, (save || lif) ? w.H1 : nullptr, (save || lif) ? w.H2 : nullptr,
@@ -532,7 +538,7 @@ static int forward_impl(const matcha_shape* shp, const matcha_tensors* params, c
   nan_check("x0", w.x0, cnt, 0, d, st);
   nan_check("X", w.X, cnt, 0, d, st);
   const bool mlw = merged_layerwise(s);
-  note_forward(ws, mlw, false, enc);                 // the backward pass on this workspace must use the same formulation
+  if (opts->forward_only) forget_forward(ws); else note_forward(ws, mlw, false, enc);      // the backward pass on this workspace must use the same formulation
   if (enc) {
     // LayerNorms, merged heads, attention, fc1 + dropout + mask: X -> Y in one kernel; a training forward leaves r rows + probabilities
     MATCHA_TRY(merged_weights(s, p, w, st));
@@ -714,6 +720,7 @@ static int backward_impl(const matcha_shape* shp, const matcha_tensors* params, 
   const bool fused_fwd = (fwd_state & 2) != 0;          // which kernels the forward ran is what decides, not the option table now
   const bool lif = fused_fwd && loss_in_forward(s, *opts, y, w_bce, objective);
   MATCHA_CHECK_ARG(!(lif && dlogits), "matcha_backward: opts->loss_in_forward excludes an explicit dlogits");
+  forget_forward(ws);                                   // one backward per forward: from here on the saved activations are being overwritten
   bool dx_zeroed = false, tail_in_bwd = false;
   TailReduceArgs tail_args;
   if (lif) {
@@ -786,7 +793,7 @@ static int backward_impl(const matcha_shape* shp, const matcha_tensors* params, 
     MATCHA_TRY(merged_chain(s, p, g_, w, st));
     MATCHA_TRY(encoder_done(*opts, st));
   } else {
-  if (fwd_ran_merged(ws)) {
+  if ((fwd_state & 1) != 0) {
     // merged heads: dM_all = ddyn0^T Z ; d fc1_b += colsum ; dZ = ddyn0 M_all   (the scratch gradients start from zero: the TN GEMM
     // accumulates C and the column sums alike, and fc1_b's gradient must accumulate)
     MATCHA_TRY(zero_async(w.lwdM, (size_t)hd * d * sizeof(float), st));

@@ -148,7 +148,7 @@ class Trainer:
         exchange and its host wait (all_reduce).  The driver knows it: every rank holds the whole global batch on the host."""
         rt = self.rt
         if not rt.still_packed():
-            raise _lib.MatchaHipError("model parameters moved after the Trainer was built; create a new Trainer")
+            raise _lib.MatchaHipError("model parameters moved or a frozen input (attribute table, adj features) changed after the Trainer was built; create a new Trainer")
         B, L = x.shape
         ws, logits = self._buffers(B, L)
         self._sparse = self._use_sparse(B, L)
@@ -312,7 +312,7 @@ class Trainer:
         synchronises and nothing allocates after the first call of a shape, so the call can be captured in a hipGraph (train.py)."""
         rt = self.rt
         if not rt.still_packed():
-            raise _lib.MatchaHipError("model parameters moved after the Trainer was built; create a new Trainer")
+            raise _lib.MatchaHipError("model parameters moved or a frozen input (attribute table, adj features) changed after the Trainer was built; create a new Trainer")
         B, L = x.shape
         key = (B, L, "eval")
         if key not in self._ws:

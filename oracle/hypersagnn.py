@@ -267,8 +267,9 @@ class AdamWRef:
 
     Defaults (torch): betas (0.9, 0.999), eps 1e-8, weight_decay 1e-2, amsgrad False.
     Per tensor: ``step`` counts only the steps in which the tensor had a gradient; tensors
-    whose grad is None are skipped entirely (no decay).  Checked against torch.optim.AdamW in
-    tests/test_oracle_unit.py.
+    whose grad is None are skipped entirely (no decay).  Checked against the reference's own torch.optim.AdamW trajectories
+    (parameters after the first and the last recorded step, adj fixtures with grad-None tensors included) in
+    tests/test_oracle_golden.py; tests/test_cpu_twins.py holds the plain-C restatements to the same oracle.
     """
 
     def __init__(self, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-2):

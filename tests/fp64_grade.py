@@ -270,3 +270,19 @@ def make_case_batch(layout, ks, rows_per_k, seed, L=0):
     """(x int64 [B, L], y float32 [B], w float32 [B]) of synth.make_batch."""
     x, y, w = synth.make_batch(np.random.default_rng(seed), int(np.sum(synth.LAYOUTS[layout])), ks, rows_per_k, L)
     return x, y.reshape(-1), w.reshape(-1)
+
+
+def halves_cap(T, L):
+    """ragged.hip halves_cap: the half tiles the ragged plan provisions for T tokens of rows of L slots."""
+    cdiv = lambda a, b: -(-a // b)
+    return cdiv(T + 1, 32 - L) + cdiv(T + 1, 63 * 32)
+
+
+def edge_rows(which, L):
+    """The batch size at which halves_cap(B L, L) last stays at 2 CU (edge-: the small-batch forward) and the next one (edge+)."""
+    cap = 2 * torch.cuda.get_device_properties(0).multi_processor_count
+    B = 1
+    while halves_cap((B + 1) * L, L) <= cap:
+        B += 1
+    assert halves_cap(B * L, L) <= cap < halves_cap((B + 1) * L, L)
+    return B if which == "edge-" else B + 1

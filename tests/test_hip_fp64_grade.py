@@ -111,22 +111,6 @@ def _ratio_table():
             print(f"  {name:22s} step {step:5.2f}   eval {ev:5.2f}   witness {wit:6.1f} x bound")
 
 
-def _halves_cap(T, L):
-    """ragged.hip halves_cap: the half tiles the ragged plan provisions for T tokens of rows of L slots."""
-    cdiv = lambda a, b: -(-a // b)
-    return cdiv(T + 1, 32 - L) + cdiv(T + 1, 63 * 32)
-
-
-def _edge_rows(which, L):
-    """The batch size at which halves_cap(B L, L) last stays at 2 CU (edge-: the small-batch forward) and the next one (edge+)."""
-    cap = 2 * torch.cuda.get_device_properties(0).multi_processor_count
-    B = 1
-    while _halves_cap((B + 1) * L, L) <= cap:
-        B += 1
-    assert _halves_cap(B * L, L) <= cap < _halves_cap((B + 1) * L, L)
-    return B if which == "edge-" else B + 1
-
-
 _DATA = {}
 
 
@@ -139,7 +123,7 @@ def _data(c: Case):
     _, fe, sd = oracle_state(num, c.d, c.mode, c.seed)
     x, y, w = G.make_case_batch(c.layout, list(c.ks), c.rows_per_k, c.batch_seed or c.seed + 500, c.L)
     if c.rows is not None:
-        n = _edge_rows(c.rows, x.shape[1]) if isinstance(c.rows, str) else c.rows
+        n = G.edge_rows(c.rows, x.shape[1]) if isinstance(c.rows, str) else c.rows
         assert n <= len(x)
         x, y, w = x[:n], y[:n], w[:n]
     chrom = int(np.random.default_rng(c.seed).integers(fe.n_chrom))
