@@ -539,6 +539,39 @@ int matcha_denoise_intra(const float* proba, int64_t n_pairs, int32_t n, int32_t
                          matcha_stream_t stream);
 int matcha_denoise_pixels(const float* m, int32_t n, int32_t min_dis, float* out, matcha_stream_t stream);
 
+/* ---- de novo k-way sweep -------------------------------------------------------------------------------
+ * Candidates of size k in the region [lo, lo + n) of node ids: strictly ascending k-tuples whose adjacent differences are all
+ * >= min_gap (min_gap = min_distance + 1 is the rule of Code/generate_kmers.py:18, :33 and of the negative sampler), in
+ * lexicographic order; the rank of a candidate is its position in that order, from 0.  With m = n - (k - 1)(min_gap - 1) there are
+ * C(m, k) of them (0 when m < k).  Supported: 2 <= k <= 8, n >= 1, min_gap >= 1, C(m, k) < 2^63 -- a larger count is refused.
+ * matcha_kway_count   host only: C(m, k), or -1 for invalid arguments or a count >= 2^63.
+ * matcha_kway_rows    writes x, device int64 [count, L] with k <= L <= 8, columns k .. L-1 zero: row i is the candidate of rank
+ *     rank0 + i (ranks == NULL; the range must lie inside [0, C(m, k)), else refused) or of rank ranks[i] (device int64 [count];
+ *     a rank outside [0, C(m, k)) gives an all-zero row).  64-bit integer unranking, k steps per row; count = 0 launches nothing.
+ *
+ * Streaming selection of the best K (score, rank) pairs.  Total order: higher score first (IEEE comparison, so -0.0 == +0.0 and
+ * the rank decides; +inf is the highest score, -inf the lowest), then lower rank.  A NaN score or a row with skip[i] != 0 is never
+ * kept.  After any sequence of updates the state holds the best min(K, valid rows seen) pairs, and the same pairs bit for bit
+ * however the rows were cut into updates (no atomics: nothing depends on arrival order).
+ * matcha_topk_bytes   bytes of one state for K pairs and updates of at most max_chunk rows (1 <= K, max_chunk < 2^31); 0 when out
+ *     of range.  Sized without asking the device.  K and max_chunk are passed again to the other three calls: the library keeps
+ *     nothing on the host between calls and never reads the state back.
+ * matcha_topk_init    empties the state (a kernel, no memset).
+ * matcha_topk_update  scores device float32 [n], row i has rank rank0 + i; skip optional device int32 [n] (the layout
+ *     matcha_hashset_contains writes); 0 <= n <= max_chunk, n = 0 is a no-op that launches nothing.
+ * matcha_topk_read    scores_out device float32 [K], ranks_out device int64 [K], sorted in the order above; n_out device int64:
+ *     the number of valid pairs (entries beyond it are score 0, rank -1).
+ * All refuse, before any device call: a null pointer, K or max_chunk out of range, a state smaller than matcha_topk_bytes. */
+int64_t matcha_kway_count(int32_t n, int32_t k, int32_t min_gap);
+int matcha_kway_rows(int64_t lo, int32_t n, int32_t k, int32_t min_gap, int64_t rank0, const int64_t* ranks, int64_t count,
+                     int32_t L, int64_t* x, matcha_stream_t stream);
+size_t matcha_topk_bytes(int32_t K, int64_t max_chunk);
+int matcha_topk_init(void* state, size_t bytes, int32_t K, int64_t max_chunk, matcha_stream_t stream);
+int matcha_topk_update(void* state, size_t bytes, int32_t K, int64_t max_chunk, const float* scores, const int32_t* skip,
+                       int64_t n, int64_t rank0, matcha_stream_t stream);
+int matcha_topk_read(const void* state, size_t bytes, int32_t K, int64_t max_chunk, float* scores_out, int64_t* ranks_out,
+                     int64_t* n_out, matcha_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

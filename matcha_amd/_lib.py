@@ -122,6 +122,12 @@ SIGNATURES = {
     "matcha_denoise_workspace_bytes": (_SZ, [_I32]),
     "matcha_denoise_intra": (C.c_int, [_fp, _I64, _I32, _I32, _fp, _I64, _fp, _fp, _fp, _fp, _fp, _SZ, _fp]),
     "matcha_denoise_pixels": (C.c_int, [_fp, _I32, _I32, _fp, _fp]),
+    "matcha_kway_count": (_I64, [_I32, _I32, _I32]),
+    "matcha_kway_rows": (C.c_int, [_I64, _I32, _I32, _I32, _I64, _fp, _I64, _I32, _fp, _fp]),
+    "matcha_topk_bytes": (_SZ, [_I32, _I64]),
+    "matcha_topk_init": (C.c_int, [_fp, _SZ, _I32, _I64, _fp]),
+    "matcha_topk_update": (C.c_int, [_fp, _SZ, _I32, _I64, _fp, _fp, _I64, _I64, _fp]),
+    "matcha_topk_read": (C.c_int, [_fp, _SZ, _I32, _I64, _fp, _fp, _fp, _fp]),
 }
 
 OBJECTIVE_BCE, OBJECTIVE_SOFTPLUS_MSE = 0, 1      # MATCHA_OBJECTIVE_* of include/matcha_hip.h

@@ -1,0 +1,385 @@
+// De novo k-way sweep: the candidates of a region made on the device from their rank, and a streaming selection that
+// keeps the best K (score, rank) pairs across chunks without the scores ever leaving the device.
+//
+// Candidates.  A candidate of size k in the region [lo, lo + n) is a strictly ascending k-tuple of node ids whose adjacent differences
+// are all >= min_gap (generate_kmers.py:18, :33 and the sampler's rule with min_gap = min_distance + 1).  With s = min_gap - 1 and
+// m = n - (k - 1) s, y_j = x_j - lo - j s maps them, order preserved, onto the plain k-subsets of [0, m): C(m, k) of them, ranked
+// lexicographically from 0.
+//
+//   kway_rows_kernel   one thread per row.  The lexicographic rank r of y equals total - 1 - (colexicographic rank of the mirrored set
+//                      z_j = m - 1 - y_j), so the row is read off the combinatorial number system of q = total - 1 - r: for j = k .. 1
+//                      the largest c with C(c, j) <= q (z_{k-j} = c, q -= C(c, j)).  c is estimated as (q j!)^(1/j) + (j - 1) / 2 in
+//                      float64 and corrected with exact integer binomials, so the result does not depend on the estimate.  64-bit
+//                      integers throughout: C(a, j) is built as C(a-j+i, i) = C(a-j+i-1, i-1) (a-j+i) / i with gcd(a-j+i, i) divided out
+//                      of both factors first, which keeps every intermediate <= the result (n = 120 000, k = 4 has C > 2^61, where
+//                      the plain product passes 2^64).  Rows go through LDS and leave as one contiguous, coalesced run per block.
+//                      The same kernel serves a range of ranks (rank0 + i) and a device list of ranks (the winners at the end).
+//
+// Selection.  The total order is: higher score first (IEEE comparison: -0.0 == +0.0, +inf highest, -inf lowest), then lower rank; NaN
+// scores and rows with skip[i] != 0 are never kept.  The state is the K best pairs so far, sorted, padded with sentinels.
+//
+//   topk_init_kernel   fills the state with sentinels (no memset).
+//   topk_keys_kernel   score -> 32-bit key that sorts ascending in the order above (-0.0 folded onto +0.0 in the key only; the stored
+//                      score keeps its bits), invalid rows -> the sentinel key; value = the row's index in the chunk.
+//   rocPRIM radix sort of (key, index): stable, and the chunk's ranks ascend with the index, so the chunk comes out in the total order.
+//   topk_merge_kernel  merge path over the sorted state and the chunk's best min(K, n) rows: output position p finds its split by a
+//                      binary search on the composite (key, rank) and takes one element.
+//   topk_commit_kernel copies the merged K back into the state.
+//   topk_read_kernel   scores, ranks and the number of valid pairs (the first sentinel's position).
+//
+// No atomics of any kind: every output element has one owner, so the state after a sequence of updates depends only on the multiset of
+// (score, rank) pairs seen -- not on how the stream was cut, and not on timing.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include "kernels.hpp"
+
+namespace matcha {
+namespace {
+
+constexpr int kMaxK = MATCHA_MAX_L;            // candidate sizes 2 .. 8
+constexpr int kRowsPerBlock = 256;
+constexpr uint32_t kSentinel = 0xFFFFFFFFu;    // sorts behind every real key (the worst real key is -inf: 0xFF800000)
+
+__host__ __device__ __forceinline__ uint32_t gcd_small(uint32_t a, uint32_t b) {
+  while (b) { const uint32_t t = a % b; a = b; b = t; }
+  return a;
+}
+
+// r / d for d in 1 .. 8 with constant divisors (a 64-bit division by a variable is a long software routine on the device)
+__host__ __device__ __forceinline__ uint64_t div_small(uint64_t r, uint32_t d) {
+  switch (d) {
+    case 2: return r / 2;
+    case 3: return r / 3;
+    case 4: return r / 4;
+    case 5: return r / 5;
+    case 6: return r / 6;
+    case 7: return r / 7;
+    case 8: return r / 8;
+    default: return r;
+  }
+}
+__host__ __device__ __forceinline__ uint32_t div_small32(uint32_t r, uint32_t d) {
+  switch (d) {
+    case 2: return r / 2;
+    case 3: return r / 3;
+    case 4: return r / 4;
+    case 5: return r / 5;
+    case 6: return r / 6;
+    case 7: return r / 7;
+    case 8: return r / 8;
+    default: return r;
+  }
+}
+
+// C(a, j) for 0 <= j <= 8 and 0 <= a < 2^31; exact whenever the result fits 64 bits: step i holds C(a-j+i, i), which grows with i,
+// and i / gcd(a-j+i, i) divides the previous value because it is coprime to the other factor.
+__host__ __device__ __forceinline__ uint64_t binom(int64_t a, int j) {
+  if (a < j) return 0;
+  uint64_t r = 1;
+  for (int i = 1; i <= j; ++i) {
+    const uint32_t t = (uint32_t)(a - j + i);
+    const uint32_t g = gcd_small(t % (uint32_t)i, (uint32_t)i);
+    r = div_small(r, (uint32_t)i / g) * div_small32(t, g);
+  }
+  return r;
+}
+
+// C(m, k) on the host, -1 when it does not fit a signed 64-bit integer (the intermediates grow with i, so the first one over decides)
+int64_t count_subsets(int64_t m, int k) {
+  if (m < k) return 0;
+  unsigned __int128 r = 1;
+  const unsigned __int128 lim = (unsigned __int128)1 << 63;
+  for (int i = 1; i <= k; ++i) {
+    r = r * (unsigned __int128)(m - k + i) / (unsigned __int128)i;
+    if (r >= lim) return -1;
+  }
+  return (int64_t)r;
+}
+
+bool kway_args_ok(int32_t n, int32_t k, int32_t min_gap) { return n >= 1 && k >= 2 && k <= kMaxK && min_gap >= 1; }
+
+int64_t kway_count(int32_t n, int32_t k, int32_t min_gap) {
+  if (!kway_args_ok(n, k, min_gap)) return -1;
+  const int64_t m = (int64_t)n - (int64_t)(k - 1) * (min_gap - 1);
+  return count_subsets(m, k);
+}
+
+// y[0 .. k): the k-subset of [0, m) of lexicographic rank r, 0 <= r < total = C(m, k)
+__device__ __forceinline__ void unrank(uint64_t r, uint64_t total, int32_t m, int k, int32_t (&y)[kMaxK]) {
+  const double fact[kMaxK + 1] = {1., 1., 2., 6., 24., 120., 720., 5040., 40320.};
+  uint64_t q = total - 1 - r;
+  int64_t upper = (int64_t)m - 1;                                      // invariant: q < C(upper + 1, j)
+#pragma unroll
+  for (int s = 0; s < kMaxK; ++s) {
+    if (s < k) {
+      const int j = k - s;
+      int64_t c;
+      if (j == 1) {
+        c = (int64_t)q;
+      } else {
+        c = (int64_t)(pow((double)q * fact[j], 1.0 / (double)j) + 0.5 * (double)(j - 1));
+        c = c < j - 1 ? j - 1 : c;
+        c = c > upper ? upper : c;
+        uint64_t b = binom(c, j);
+        while (b > q) { --c; b = binom(c, j); }                        // ends at c = j - 1 at the latest: C(j - 1, j) = 0
+        while (c < upper) {
+          const uint64_t b1 = binom(c + 1, j);
+          if (b1 > q) break;
+          ++c;
+          b = b1;
+        }
+        q -= b;
+      }
+      y[s] = (int32_t)((int64_t)m - 1 - c);
+      upper = c - 1;
+    }
+  }
+}
+
+__global__ __launch_bounds__(kRowsPerBlock) void kway_rows_kernel(int64_t lo, int32_t m, int32_t k, int32_t slack, uint64_t total, int64_t rank0,
+                                                                  const int64_t* __restrict__ ranks, int64_t count, int32_t L,
+                                                                  int64_t* __restrict__ x) {
+  __shared__ int64_t tile[kRowsPerBlock * kMaxK];
+  for (int64_t base = (int64_t)blockIdx.x * kRowsPerBlock; base < count; base += (int64_t)gridDim.x * kRowsPerBlock) {
+    const int64_t i = base + threadIdx.x;
+    if (i < count) {
+      const int64_t r = ranks ? ranks[i] : rank0 + i;
+      const bool ok = r >= 0 && (uint64_t)r < total;
+      int32_t y[kMaxK] = {0, 0, 0, 0, 0, 0, 0, 0};
+      if (ok) unrank((uint64_t)r, total, m, k, y);
+#pragma unroll
+      for (int c = 0; c < kMaxK; ++c)
+        if (c < L) tile[threadIdx.x * L + c] = (ok && c < k) ? lo + (int64_t)y[c] + (int64_t)c * slack : 0;
+    }
+    __syncthreads();
+    const int64_t rows = count - base < kRowsPerBlock ? count - base : kRowsPerBlock;
+    const int elems = (int)rows * L;
+    for (int e = threadIdx.x; e < elems; e += kRowsPerBlock) x[base * L + e] = tile[e];
+    __syncthreads();                                                   // the tile is reused by the next run of rows
+  }
+}
+
+// ---- selection ------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t score_key(float s) {
+  if (s != s) return kSentinel;
+  uint32_t b = __builtin_bit_cast(uint32_t, s);
+  if (b == 0x80000000u) b = 0;                                         // -0.0 == +0.0: one key, the rank decides
+  const uint32_t asc = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+  return ~asc;                                                         // ascending key = descending score
+}
+
+struct TopkPlan {
+  size_t off_key, off_score, off_rank;        // the state: K sorted pairs
+  size_t off_tkey, off_tscore, off_trank;     // the merged K before they are committed
+  size_t off_ckey, off_cidx, off_skey, off_sidx, off_sort, sort_bytes, total;
+};
+
+bool topk_args_ok(int64_t K, int64_t max_chunk) {
+  return K >= 1 && K <= ((int64_t)1 << 31) - 1 && max_chunk >= 1 && max_chunk <= ((int64_t)1 << 31) - 1;
+}
+
+// The radix sort's scratch is reserved by a bound (two buffers of keys and values plus its histograms and look-back state), not by asking
+// rocPRIM: sizing must work where there is no device.  matcha_topk_update checks the bound against what rocPRIM asks for.
+TopkPlan make_tplan(int64_t K, int64_t max_chunk) {
+  TopkPlan pl;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
+  pl.off_key = take((size_t)K * 4);
+  pl.off_score = take((size_t)K * 4);
+  pl.off_rank = take((size_t)K * 8);
+  pl.off_tkey = take((size_t)K * 4);
+  pl.off_tscore = take((size_t)K * 4);
+  pl.off_trank = take((size_t)K * 8);
+  pl.off_ckey = take((size_t)max_chunk * 4);
+  pl.off_cidx = take((size_t)max_chunk * 4);
+  pl.off_skey = take((size_t)max_chunk * 4);
+  pl.off_sidx = take((size_t)max_chunk * 4);
+  pl.sort_bytes = (size_t)max_chunk * 16 + ((size_t)4 << 20);
+  pl.off_sort = take(pl.sort_bytes);
+  pl.total = off;
+  return pl;
+}
+
+struct TopkState {
+  uint32_t* key;
+  float* score;
+  int64_t* rank;
+};
+
+TopkState state_at(void* base, size_t off_key, size_t off_score, size_t off_rank) {
+  char* w = (char*)base;
+  return TopkState{(uint32_t*)(w + off_key), (float*)(w + off_score), (int64_t*)(w + off_rank)};
+}
+
+__global__ __launch_bounds__(256) void topk_init_kernel(TopkState st, int64_t K) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= K) return;
+  st.key[p] = kSentinel;
+  st.score[p] = 0.f;
+  st.rank[p] = -1;
+}
+
+__global__ __launch_bounds__(256) void topk_keys_kernel(const float* __restrict__ scores, const int32_t* __restrict__ skip, int64_t n,
+                                                        uint32_t* __restrict__ key, uint32_t* __restrict__ idx) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const bool skipped = skip && skip[i] != 0;
+  key[i] = skipped ? kSentinel : score_key(scores[i]);
+  idx[i] = (uint32_t)i;
+}
+
+// (key, rank) of the state before (key, rank) of the chunk?  Equal pairs (the same rank fed twice) go either way: they are the same pair.
+__device__ __forceinline__ bool state_first(uint32_t ka, int64_t ra, uint32_t kb, int64_t rb) { return ka < kb || (ka == kb && ra <= rb); }
+
+__global__ __launch_bounds__(256) void topk_merge_kernel(TopkState a, int64_t K, const uint32_t* __restrict__ bkey, const uint32_t* __restrict__ bidx,
+                                                         int64_t nb, const float* __restrict__ scores, int64_t rank0, TopkState out) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= K) return;
+  // ia = how many of the first p merged elements come from the state: the smallest ia whose successor in the state does not precede the
+  // chunk element it would displace
+  int64_t lo = p > nb ? p - nb : 0, hi = p;                            // p < K, so ia <= p < K
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    const int64_t jb = p - 1 - mid;                                    // in [0, nb)
+    if (state_first(a.key[mid], a.rank[mid], bkey[jb], rank0 + (int64_t)bidx[jb])) lo = mid + 1;
+    else hi = mid;
+  }
+  const int64_t ia = lo, ib = p - lo;
+  bool from_a = true;
+  if (ib < nb) from_a = state_first(a.key[ia], a.rank[ia], bkey[ib], rank0 + (int64_t)bidx[ib]);
+  uint32_t key;
+  float score;
+  int64_t rank;
+  if (from_a) {
+    key = a.key[ia]; score = a.score[ia]; rank = a.rank[ia];
+  } else {
+    key = bkey[ib]; score = scores[bidx[ib]]; rank = rank0 + (int64_t)bidx[ib];
+  }
+  if (key == kSentinel) { score = 0.f; rank = -1; }
+  out.key[p] = key;
+  out.score[p] = score;
+  out.rank[p] = rank;
+}
+
+__global__ __launch_bounds__(256) void topk_commit_kernel(TopkState from, TopkState to, int64_t K) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= K) return;
+  to.key[p] = from.key[p];
+  to.score[p] = from.score[p];
+  to.rank[p] = from.rank[p];
+}
+
+__global__ __launch_bounds__(256) void topk_read_kernel(TopkState st, int64_t K, float* __restrict__ scores_out, int64_t* __restrict__ ranks_out,
+                                                        int64_t* __restrict__ n_out) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= K) return;
+  const bool valid = st.key[p] != kSentinel;
+  scores_out[p] = st.score[p];
+  ranks_out[p] = st.rank[p];
+  // the valid pairs are a prefix: its end has exactly one owner
+  if (valid && (p == K - 1 || st.key[p + 1] == kSentinel)) *n_out = p + 1;
+  if (!valid && p == 0) *n_out = 0;
+}
+
+}  // namespace
+}  // namespace matcha
+
+using namespace matcha;
+
+extern "C" int64_t matcha_kway_count(int32_t n, int32_t k, int32_t min_gap) { return kway_count(n, k, min_gap); }
+
+extern "C" int matcha_kway_rows(int64_t lo, int32_t n, int32_t k, int32_t min_gap, int64_t rank0, const int64_t* ranks, int64_t count, int32_t L,
+                                int64_t* x, matcha_stream_t stream) {
+  MATCHA_CHECK_ARG(kway_args_ok(n, k, min_gap), "matcha_kway_rows: need n >= 1, 2 <= k <= %d, min_gap >= 1 (n=%d k=%d min_gap=%d)", kMaxK, n, k, min_gap);
+  MATCHA_CHECK_ARG(L >= k && L <= kMaxK, "matcha_kway_rows: row width L=%d must be in [k, %d]", L, kMaxK);
+  MATCHA_CHECK_ARG(lo >= 0 && lo <= ((int64_t)1 << 62), "matcha_kway_rows: lo out of range");
+  const int64_t total = kway_count(n, k, min_gap);
+  MATCHA_CHECK_ARG(total >= 0, "matcha_kway_rows: C(m, k) does not fit 63 bits (n=%d k=%d min_gap=%d)", n, k, min_gap);
+  MATCHA_CHECK_ARG(count >= 0 && count <= ((int64_t)1 << 40), "matcha_kway_rows: count out of range");
+  if (!ranks)
+    MATCHA_CHECK_ARG(rank0 >= 0 && rank0 <= total && count <= total - rank0,
+                     "matcha_kway_rows: ranks [%lld, %lld) outside [0, %lld)", (long long)rank0, (long long)(rank0 + count), (long long)total);
+  if (count == 0) return MATCHA_OK;
+  MATCHA_CHECK_ARG(x, "matcha_kway_rows: null output");
+  const int32_t slack = min_gap - 1;
+  const int64_t m64 = (int64_t)n - (int64_t)(k - 1) * slack;
+  const int32_t m = m64 > 0 ? (int32_t)m64 : 0;
+  int64_t blocks = cdiv(count, kRowsPerBlock);
+  if (blocks > (1 << 20)) blocks = 1 << 20;
+  hipLaunchKernelGGL(kway_rows_kernel, dim3((unsigned)blocks), dim3(kRowsPerBlock), 0, (hipStream_t)stream, lo, m, k, slack, (uint64_t)total, rank0,
+                     ranks, count, L, x);
+  MATCHA_CHECK_LAUNCH("kway_rows_kernel");
+  return MATCHA_OK;
+}
+
+extern "C" size_t matcha_topk_bytes(int32_t K, int64_t max_chunk) {
+  if (!topk_args_ok(K, max_chunk)) return 0;
+  return make_tplan(K, max_chunk).total;
+}
+
+#define TOPK_COMMON_ARGS(fn)                                                                                                          \
+  MATCHA_CHECK_ARG(state, fn ": null state");                                                                                         \
+  MATCHA_CHECK_ARG(topk_args_ok(K, max_chunk), fn ": need 1 <= K < 2^31 and 1 <= max_chunk < 2^31 (K=%d max_chunk=%lld)", K,          \
+                   (long long)max_chunk);                                                                                             \
+  MATCHA_CHECK_ARG(((uintptr_t)state) % 8 == 0, fn ": state must be 8-byte aligned");                                                 \
+  const TopkPlan pl = make_tplan(K, max_chunk);                                                                                       \
+  MATCHA_CHECK_ARG(bytes >= pl.total, fn ": state too small (%zu bytes, matcha_topk_bytes says %zu)", bytes, pl.total)
+
+extern "C" int matcha_topk_init(void* state, size_t bytes, int32_t K, int64_t max_chunk, matcha_stream_t stream) {
+  TOPK_COMMON_ARGS("matcha_topk_init");
+  hipLaunchKernelGGL(topk_init_kernel, dim3((unsigned)cdiv(K, 256)), dim3(256), 0, (hipStream_t)stream,
+                     state_at(state, pl.off_key, pl.off_score, pl.off_rank), (int64_t)K);
+  MATCHA_CHECK_LAUNCH("topk_init_kernel");
+  return MATCHA_OK;
+}
+
+extern "C" int matcha_topk_update(void* state, size_t bytes, int32_t K, int64_t max_chunk, const float* scores, const int32_t* skip, int64_t n,
+                                  int64_t rank0, matcha_stream_t stream) {
+  TOPK_COMMON_ARGS("matcha_topk_update");
+  MATCHA_CHECK_ARG(n >= 0 && n <= max_chunk, "matcha_topk_update: n=%lld outside [0, max_chunk=%lld]", (long long)n, (long long)max_chunk);
+  MATCHA_CHECK_ARG(rank0 >= 0 && rank0 <= INT64_MAX - n, "matcha_topk_update: rank0 out of range");
+  if (n == 0) return MATCHA_OK;
+  MATCHA_CHECK_ARG(scores, "matcha_topk_update: null scores");
+  hipStream_t st = (hipStream_t)stream;
+  char* w = (char*)state;
+  uint32_t* ckey = (uint32_t*)(w + pl.off_ckey);
+  uint32_t* cidx = (uint32_t*)(w + pl.off_cidx);
+  uint32_t* skey = (uint32_t*)(w + pl.off_skey);
+  uint32_t* sidx = (uint32_t*)(w + pl.off_sidx);
+  size_t need = 0;
+  if (rocprim::radix_sort_pairs(nullptr, need, ckey, skey, cidx, sidx, (size_t)n, 0, 32, st) != hipSuccess || need > pl.sort_bytes) {
+    set_error("matcha_topk_update: the radix sort asks for %zu bytes of scratch, %zu are reserved", need, pl.sort_bytes);
+    return MATCHA_EHIP;
+  }
+  hipLaunchKernelGGL(topk_keys_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, scores, skip, n, ckey, cidx);
+  MATCHA_CHECK_LAUNCH("topk_keys_kernel");
+  size_t tb = pl.sort_bytes;
+  if (rocprim::radix_sort_pairs(w + pl.off_sort, tb, ckey, skey, cidx, sidx, (size_t)n, 0, 32, st) != hipSuccess) {
+    set_error("matcha_topk_update: radix sort failed");
+    return MATCHA_EHIP;
+  }
+  const TopkState cur = state_at(state, pl.off_key, pl.off_score, pl.off_rank);
+  const TopkState tmp = state_at(state, pl.off_tkey, pl.off_tscore, pl.off_trank);
+  const int64_t nb = n < K ? n : (int64_t)K;
+  const unsigned blocks = (unsigned)cdiv(K, 256);
+  hipLaunchKernelGGL(topk_merge_kernel, dim3(blocks), dim3(256), 0, st, cur, (int64_t)K, skey, sidx, nb, scores, rank0, tmp);
+  MATCHA_CHECK_LAUNCH("topk_merge_kernel");
+  hipLaunchKernelGGL(topk_commit_kernel, dim3(blocks), dim3(256), 0, st, tmp, cur, (int64_t)K);
+  MATCHA_CHECK_LAUNCH("topk_commit_kernel");
+  return MATCHA_OK;
+}
+
+extern "C" int matcha_topk_read(const void* state, size_t bytes, int32_t K, int64_t max_chunk, float* scores_out, int64_t* ranks_out,
+                                int64_t* n_out, matcha_stream_t stream) {
+  TOPK_COMMON_ARGS("matcha_topk_read");
+  MATCHA_CHECK_ARG(scores_out && ranks_out && n_out, "matcha_topk_read: null output");
+  hipLaunchKernelGGL(topk_read_kernel, dim3((unsigned)cdiv(K, 256)), dim3(256), 0, (hipStream_t)stream,
+                     state_at((void*)state, pl.off_key, pl.off_score, pl.off_rank), (int64_t)K, scores_out, ranks_out, n_out);
+  MATCHA_CHECK_LAUNCH("topk_read_kernel");
+  return MATCHA_OK;
+}

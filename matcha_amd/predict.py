@@ -12,7 +12,11 @@
 
 CLI:  python -m matcha_amd.predict multiway -i interactions.txt -o output.txt
       python -m matcha_amd.predict pairwise --chrom 0 -o chr1_proba.npy
-(both read ./config.JSON like the reference: temp_dir, resolution, chrom_list, min_distance).
+      python -m matcha_amd.predict kway --chrom 0 --k 3 --top 1000 [--start-bin A --end-bin B] [--exclude-known] -o top.tsv
+(all read ./config.JSON like the reference: temp_dir, resolution, chrom_list, min_distance).
+
+* ``kway`` -- the de novo sweep of matcha_amd/sweep.py: every candidate of size k in one chromosome (or a window of its bins)
+  with adjacent gaps > min_distance, scored on the device, the best ``--top`` written as ``chrom:start`` items and a probability.
 """
 from __future__ import annotations
 
@@ -152,6 +156,31 @@ def _load(config_path: str = "./config.JSON"):
     return config, temp_dir, model
 
 
+def _kway(args, config, temp_dir, model):
+    from . import sweep as SW
+    from .sampler import HyperedgeSet
+    chrom_range = np.load(os.path.join(temp_dir, "chrom_range.npy"))
+    node2bin = np.load(os.path.join(temp_dir, "node2bin.npy"), allow_pickle=True).item()
+    c_lo, c_hi = int(chrom_range[args.chrom][0]), int(chrom_range[args.chrom][1])
+    lo = c_lo + (args.start_bin if args.start_bin is not None else 0)
+    hi = c_lo + args.end_bin if args.end_bin is not None else c_hi
+    if not c_lo <= lo <= hi <= c_hi:
+        raise ValueError("the bin window [%s, %s) is not inside chromosome %d (%d bins)" % (args.start_bin, args.end_bin, args.chrom, c_hi - c_lo))
+    dev = model.layer_norm1.weight.device
+    exclude = None
+    if args.exclude_known:
+        known = np.load(os.path.join(temp_dir, "all_%d_counter.npy" % args.k)).astype(np.int64).reshape(-1, args.k)
+        exclude = HyperedgeSet(torch.from_numpy(known).to(dev))
+    out = SW.kway_sweep(model, lo, hi, args.k, int(config["min_distance"]) + 1, args.top, chunk_rows=args.chunk_rows, width=args.width,
+                        exclude=exclude, task_mode=args.task_mode)
+    rows, proba = out["rows"].cpu().numpy(), out["proba"].cpu().numpy()
+    with open(args.output, "w") as f:
+        for r, p in zip(rows, proba):
+            f.write("\t".join([node2bin[int(v)] for v in r[:args.k]] + [repr(float(p))]) + "\n")
+    np.savez(os.path.splitext(args.output)[0] + ".npz", rows=rows, logit=out["logit"].cpu().numpy(), proba=proba, rank=out["rank"].cpu().numpy())
+    print("%d candidates (%d known, skipped) -> %d in %s" % (out["n_candidates"], out["n_excluded"], len(rows), args.output))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="inference consumers of a trained MATCHA classifier on the MI355X path")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -162,10 +191,23 @@ def main(argv=None):
     b.add_argument("--chrom", type=int, required=True, help="index into config chrom_list")
     b.add_argument("-o", "--output", type=str, default="./pairwise.npy")
     b.add_argument("--task-mode", choices=["class", "regress"], default="class", help="the model's training objective: sigmoid or softplus outputs")
-    for q in (a, b):
+    c = sub.add_parser("kway", help="de novo sweep: the best --top candidates of size --k among all of one chromosome (or bin window)")
+    c.add_argument("--chrom", type=int, required=True, help="index into config chrom_list")
+    c.add_argument("--k", type=int, required=True, help="candidate size, 2 .. 8")
+    c.add_argument("--top", type=int, required=True, help="how many candidates to keep")
+    c.add_argument("--start-bin", type=int, default=None, help="first bin of the window, relative to the chromosome (default 0)")
+    c.add_argument("--end-bin", type=int, default=None, help="one past the last bin of the window (default: the chromosome's end)")
+    c.add_argument("--exclude-known", action="store_true", help="skip the hyperedges of temp_dir/all_<k>_counter.npy")
+    c.add_argument("--width", type=int, default=None, help="zero-pad rows to this width (default k): a logit depends on its batch's width")
+    c.add_argument("--chunk-rows", type=int, default=1 << 20)
+    c.add_argument("--task-mode", choices=["class", "regress"], default="class", help="the model's training objective: sigmoid or softplus outputs")
+    c.add_argument("-o", "--output", type=str, default="./kway.tsv")
+    for q in (a, b, c):
         q.add_argument("--config", type=str, default="./config.JSON")
     args = ap.parse_args(argv)
     config, temp_dir, model = _load(args.config)
+    if args.cmd == "kway":
+        return _kway(args, config, temp_dir, model)
     if args.cmd == "multiway":
         bin2node = np.load(os.path.join(temp_dir, "bin2node.npy"), allow_pickle=True).item()
         samples, proba = predict_multiway(model, args.file, bin2node, config["chrom_list"], config["resolution"], args.output)
