@@ -44,6 +44,10 @@ struct FrontBwdArgs {
   float* slab;                                    // [gridDim.x][kFrontSlab]
 };
 
+// NODE (the node route of the table front end, model.hip): the rows are the layout's NODES -- ids 0..n_nodes, X / x0 the per-node tables, dXs the
+// per-node sums node_scatter_kernel left (LayerNorm backward + static branch, already added over each node's tokens) -- so there is no d x_hat
+// term: its loads and the LayerNorm backward are compiled out, dZ0 = dXs (1 - X^2), and every table-gradient row has one writer.
+template <bool NODE>
 __global__ __launch_bounds__(256, 2) void front_bwd_kernel(FrontBwdArgs g) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* Ws = lds;                                // next_w, resident
@@ -79,7 +83,7 @@ __global__ __launch_bounds__(256, 2) void front_bwd_kernel(FrontBwdArgs g) {
       const int64_t t__ = tb__ + srow + 16 * i__;                                                        \
       const int64_t tc__ = t__ < T ? t__ : (int64_t)T - 1;                                               \
       pxv[i__] = *reinterpret_cast<const float4*>(g.X + tc__ * 64 + sc4);                                \
-      pdv[i__] = *reinterpret_cast<const float4*>(g.dxh + tc__ * 64 + sc4);                              \
+      if constexpr (!NODE) pdv[i__] = *reinterpret_cast<const float4*>(g.dxh + tc__ * 64 + sc4);         \
       psv[i__] = *reinterpret_cast<const float4*>(g.dXs + tc__ * 64 + sc4);                              \
       px0[i__] = *reinterpret_cast<const float4*>(g.x0 + tc__ * 64 + sc4);                               \
     }                                                                                                    \
@@ -105,6 +109,13 @@ __global__ __launch_bounds__(256, 2) void front_bwd_kernel(FrontBwdArgs g) {
       const bool valid = t < T;
       const int64_t tc = valid ? t : (int64_t)T - 1;
       const float4 xv = pxv[i];
+      const float4 s = psv[i];
+      const float m = valid ? 1.f : 0.f;
+      float4 z;
+      if constexpr (NODE) {
+        z.x = m * s.x * (1.f - xv.x * xv.x); z.y = m * s.y * (1.f - xv.y * xv.y);
+        z.z = m * s.z * (1.f - xv.z * xv.z); z.w = m * s.w * (1.f - xv.w * xv.w);
+      } else {
       float4 d = pdv[i];
       for (int hd = 1; hd < g.nslab; ++hd) {          // per-head slabs (deterministic / row-sparse modes): the other seven, added in order
         const float4 v = *reinterpret_cast<const float4*>(g.dxh + ((int64_t)hd * g.tcap + tc) * 64 + sc4);
@@ -117,13 +128,11 @@ __global__ __launch_bounds__(256, 2) void front_bwd_kernel(FrontBwdArgs g) {
       const float4 xh = make_float4(a0 * rs, a1 * rs, a2 * rs, a3 * rs);
       const float ma = group_sum16_dpp((d.x + d.y) + (d.z + d.w)) * (1.f / 64.f);
       const float mb = group_sum16_dpp((d.x * xh.x + d.y * xh.y) + (d.z * xh.z + d.w * xh.w)) * (1.f / 64.f);
-      const float4 s = psv[i];
-      const float m = valid ? 1.f : 0.f;
-      float4 z;
       z.x = m * (rs * (d.x - ma - xh.x * mb) + s.x) * (1.f - xv.x * xv.x);
       z.y = m * (rs * (d.y - ma - xh.y * mb) + s.y) * (1.f - xv.y * xv.y);
       z.z = m * (rs * (d.z - ma - xh.z * mb) + s.z) * (1.f - xv.z * xv.z);
       z.w = m * (rs * (d.w - ma - xh.w * mb) + s.w) * (1.f - xv.w * xv.w);
+      }
       *reinterpret_cast<float4*>(&Zs[row * kLd + sc4]) = z;
       const float4 x0v = px0[i];
       *reinterpret_cast<float4*>(&X0s[row * kLd + sc4]) = make_float4(x0v.x * m, x0v.y * m, x0v.z * m, x0v.w * m);
@@ -524,6 +533,82 @@ __global__ __launch_bounds__(256, 4) void front_fwd3_kernel(FrontFwdArgs g) {
 #undef F3_LOAD
 }
 
+// ---- node route, backward: the front end is linear in its upstream gradient with coefficients that depend on the NODE only, so the tokens'
+// rows  LNbwd_noaffine(d x_hat_t ; x_hat_node) + dXs_t  are added per node FIRST (here, once over the tokens) and tanh', next_w, attribute_nn and
+// the table row run once per node behind it (front_bwd_kernel<true>).  Per token: the d x_hat sum (the shared padding token's from dxpad, as in
+// front_bwd_kernel), dXs, the key, and the node's X row from the L2-resident table; 16 lanes x float4 per row for the loads and the two-level
+// DPP sums.  The float atomics leave in ANOTHER shape: through a wave-private LDS image each wave-instruction adds one whole 256-byte row
+// (64 lanes x 4 B of one node) -- 16 lanes of four different rows per instruction is the shape that serialises.
+// the node table's rows normalised ONCE (LayerNorm without affine; the arithmetic of fused_bwdh_kernel's staging, so the rows it would have
+// computed per (token, head)): 16 lanes x float4 per row
+__global__ __launch_bounds__(256) void node_xhat_kernel(const float* __restrict__ XN, const int32_t* __restrict__ count, float* __restrict__ xh) {
+  const int64_t row = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
+  const int c4 = (threadIdx.x & 15) * 4;
+  const int T = count[0];
+  const float4 xv = *reinterpret_cast<const float4*>(XN + (row < T ? row : (int64_t)T - 1) * 64 + c4);
+  const float mean = group_sum16_dpp((xv.x + xv.y) + (xv.z + xv.w)) * (1.f / 64.f);
+  const float a = xv.x - mean, b = xv.y - mean, c = xv.z - mean, e = xv.w - mean;
+  const float rs = __builtin_amdgcn_rsqf(group_sum16_dpp((a * a + b * b) + (c * c + e * e)) * (1.f / 64.f) + kEps);
+  if (row < T) *reinterpret_cast<float4*>(xh + row * 64 + c4) = make_float4(a * rs, b * rs, c * rs, e * rs);
+}
+
+struct NodeScatterArgs {
+  const float* XN; const float* dxh; const float* dxpad; const float* dXs; const int32_t* key; const int32_t* count;
+  float* G;                                       // [n_nodes + 1][64], zeroed by the forward's node launch
+};
+__global__ __launch_bounds__(256) void node_scatter_kernel(NodeScatterArgs g) {
+  __shared__ __attribute__((aligned(16))) float rows_s[2][16 * 64];
+  __shared__ int keys_s[2][16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int srow = tid >> 4, sc4 = (tid & 15) * 4;
+  const int T = g.count[0];                       // real tokens + the shared padding token (row T - 1)
+  const int ntrips = (T + 15) / 16;
+  const float4 dxp = *reinterpret_cast<const float4*>(g.dxpad + sc4);
+  // two-stage prefetch on clamped indices (no branch around a load): the key one trip ahead of the rows it addresses
+  const int stride = (int)gridDim.x;
+  auto tok_of = [&](int trip) { const int64_t t = (int64_t)trip * 16 + srow; return t < T ? t : (int64_t)T - 1; };
+  int kn = g.key[tok_of(blockIdx.x)], knn = g.key[tok_of(blockIdx.x + stride < ntrips ? blockIdx.x + stride : blockIdx.x)];
+  float4 xn, dn, sn;
+  {
+    const int64_t tc = tok_of(blockIdx.x);
+    xn = *reinterpret_cast<const float4*>(g.XN + (int64_t)kn * 64 + sc4);
+    dn = *reinterpret_cast<const float4*>(g.dxh + tc * 64 + sc4);
+    sn = *reinterpret_cast<const float4*>(g.dXs + tc * 64 + sc4);
+  }
+  int buf = 0;
+  for (int trip = blockIdx.x; trip < ntrips; trip += stride, buf ^= 1) {
+    const int64_t t = (int64_t)trip * 16 + srow;
+    const bool valid = t < T;
+    const int key = kn;
+    const float4 xv = xn, s = sn;
+    const float4 d = t >= (int64_t)T - 1 ? dxp : dn;
+    {
+      const int nxt = trip + stride < ntrips ? trip + stride : trip, nxt2 = nxt + stride < ntrips ? nxt + stride : nxt;
+      const int64_t tc = tok_of(nxt);
+      kn = knn;
+      xn = *reinterpret_cast<const float4*>(g.XN + (int64_t)kn * 64 + sc4);
+      dn = *reinterpret_cast<const float4*>(g.dxh + tc * 64 + sc4);
+      sn = *reinterpret_cast<const float4*>(g.dXs + tc * 64 + sc4);
+      knn = g.key[tok_of(nxt2)];
+    }
+    const float mean = group_sum16_dpp((xv.x + xv.y) + (xv.z + xv.w)) * (1.f / 64.f);
+    const float a0 = xv.x - mean, a1 = xv.y - mean, a2 = xv.z - mean, a3 = xv.w - mean;
+    const float rs = __builtin_amdgcn_rsqf(group_sum16_dpp((a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3)) * (1.f / 64.f) + kEps);
+    const float4 xh = make_float4(a0 * rs, a1 * rs, a2 * rs, a3 * rs);
+    const float ma = group_sum16_dpp((d.x + d.y) + (d.z + d.w)) * (1.f / 64.f);
+    const float mb = group_sum16_dpp((d.x * xh.x + d.y * xh.y) + (d.z * xh.z + d.w * xh.w)) * (1.f / 64.f);
+    *reinterpret_cast<float4*>(&rows_s[buf][srow * 64 + sc4]) =
+        make_float4(rs * (d.x - ma - xh.x * mb) + s.x, rs * (d.y - ma - xh.y * mb) + s.y, rs * (d.z - ma - xh.z * mb) + s.z, rs * (d.w - ma - xh.w * mb) + s.w);
+    if ((tid & 15) == 0) keys_s[buf][srow] = valid ? key : -1;
+    __syncthreads();                              // (the two images alternate: the trip after next overwrites this one behind the next trip's barrier)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int row = 4 * wave + i, k = keys_s[buf][row];
+      if (k >= 0) atomicAdd(g.G + (int64_t)k * 64 + lane, rows_s[buf][row * 64 + lane]);
+    }
+  }
+}
+
 struct FrontReduceArgs {
   const float* slab; int nwg; int n_attr;
   float* dWn; float* dWa; float* dbn; float* dba;
@@ -569,7 +654,7 @@ int front_grid() {
 }  // namespace
 
 int launch_front_fwd(const matcha_tensors& p, const int64_t* ids, const float* table, const float* dense, const matcha_frozen& f, int n_attr,
-                     const Ragged& rg, int64_t tcap, float* x0, float* X, hipStream_t st, const PrepSpec* prep) {
+                     const Ragged& rg, int64_t tcap, float* x0, float* X, hipStream_t st, const PrepSpec* prep, const int32_t* count) {
   // attr_mode 1: this forward (front_fwd3_kernel) rebuilds a token's attribute row from its node id and reads no table; front_bwd_kernel
   // keeps GATHERING the rows (padded to one 128-byte unit when the caller padded them, attr_ld): its row pieces are loaded by eight threads
   // per row inside a register prefetch pipeline, and rebuilding them there put a branch around the loads and cost 20 % of the kernel.  So the
@@ -580,7 +665,7 @@ int launch_front_fwd(const matcha_tensors& p, const int64_t* ids, const float* t
   // table: front_fwd_kernel gathers its rows (padded to one 128-byte unit when the caller padded them) for the K = 32 product
   const bool computed = f.attr_mode == 1 && f.attr_bounds && n_attr <= kAttrCols;
   g.ids = ids; g.table = table; g.dense = dense; g.attr = computed ? attr_src(f, n_attr) : attr_src_table_first(f, n_attr); g.n_attr = n_attr;
-  g.Wa = p.attr_w; g.ba = p.attr_b; g.Wn = p.next_w; g.bn = p.next_b; g.count = rg.count; g.x0 = x0; g.X = X;
+  g.Wa = p.attr_w; g.ba = p.attr_b; g.Wn = p.next_w; g.bn = p.next_b; g.count = count ? count : rg.count; g.x0 = x0; g.X = X;
   const int slots = front_grid() / 2 * 3;               // front_fwd_kernel: three workgroups per CU (44 KB of LDS each)
   const int64_t max_tiles = cdiv(tcap, 64);
   const size_t lds = ((size_t)2 * kTile + 64 * kLdA) * sizeof(float);
@@ -619,26 +704,50 @@ int launch_front_fwd(const matcha_tensors& p, const int64_t* ids, const float* t
   return MATCHA_OK;
 }
 
+int launch_node_xhat(const float* XN, const int32_t* node_count, int64_t rows_cap, float* xhatN, hipStream_t st) {
+  ProfScope ps(MATCHA_PROF_FRONT_FWD, (double)rows_cap * 512.0, st);
+  hipLaunchKernelGGL(node_xhat_kernel, dim3((unsigned)cdiv(rows_cap, 16)), dim3(256), 0, st, XN, node_count, xhatN);
+  MATCHA_CHECK_LAUNCH("node_xhat_kernel");
+  return MATCHA_OK;
+}
+
+// node route: one pass over the tokens that adds their front-end gradient rows per node (G, zeroed by the caller's forward)
+int launch_node_scatter(const float* XN, const float* dxh, const float* dxpad, const float* dXs, const Ragged& rg, int64_t tcap, float* G, hipStream_t st) {
+  NodeScatterArgs g;
+  g.XN = XN; g.dxh = dxh; g.dxpad = dxpad; g.dXs = dXs; g.key = rg.tok_key; g.count = rg.count; g.G = G;
+  int64_t grid = (int64_t)front_grid() * 4;                  // eight workgroups of four wavefronts per CU
+  const int64_t trips = cdiv(tcap, 16);
+  if (grid > trips) grid = trips;
+  // algorithmic bytes per token: the d x_hat sum + dXs read, the key, the node's X row (from L2), 256 B of atomics
+  ProfScope ps(MATCHA_PROF_FRONT_BWD, (double)tcap * (4.0 * 256.0 + 4.0), st);
+  hipLaunchKernelGGL(node_scatter_kernel, dim3((unsigned)grid), dim3(256), 0, st, g);
+  MATCHA_CHECK_LAUNCH("node_scatter_kernel");
+  return MATCHA_OK;
+}
+
 bool front_bwd_supported(int d, int n_attr) { return d == 64 && n_attr >= 4 && n_attr <= kAttrCols && n_attr % 4 == 0; }
 size_t front_bwd_ws_floats() { return (size_t)1024 * kFrontSlab; }
 
 int launch_front_bwd(const matcha_tensors& p, const float* X, const float* dxh, int nslab, int64_t tcap, const float* dxpad, const float* dXs, const float* x0,
                      const int64_t* ids, const matcha_frozen& f, int n_attr, const Ragged& rg, float* dX0, float* dtable, float* ws,
-                     matcha_tensors& grads, hipStream_t st, int32_t* touched) {
+                     matcha_tensors& grads, hipStream_t st, int32_t* touched, const int32_t* node_count) {
   MATCHA_CHECK_ARG(f.attr_table, "front end: attr_table is required (also under attr_mode 1)");
   FrontBwdArgs g;
   g.X = X; g.dxh = dxh; g.nslab = nslab; g.tcap = tcap; g.dxpad = dxpad; g.dXs = dXs; g.x0 = x0; g.ids = ids; g.attr = attr_src_table_first(f, n_attr); g.n_attr = n_attr;
-  g.Wn = p.next_w; g.count = rg.count; g.dX0 = dX0; g.dtable = dtable; g.slab = ws;
+  g.Wn = p.next_w; g.count = node_count ? node_count : rg.count; g.dX0 = dX0; g.dtable = dtable; g.slab = ws;
+  const bool node = node_count != nullptr;
   int grid = front_grid();
   const int64_t max_tiles = cdiv(tcap, 64);
   if (grid > max_tiles) grid = (int)max_tiles;
   const size_t lds = ((size_t)4 * kTile + 64 * kLdA + 64) * sizeof(float);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(front_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(node ? front_bwd_kernel<true> : front_bwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   {
     // algorithmic bytes per token: the d x_hat partials (8 per-head slabs, or 1 when the heads were added with atomics) + X + dXs + x0, id,
     // attribute row; table mode adds 256 B of atomics
-    ProfScope ps(MATCHA_PROF_FRONT_BWD, (double)tcap * ((3.0 + nslab) * 256.0 + 8.0 + (g.attr.mode == 1 ? 0.0 : 4.0 * n_attr) + 256.0), st);
-    hipLaunchKernelGGL(front_bwd_kernel, dim3(grid), dim3(256), lds, st, g);
+    // (node route: tcap = the node rows, no d x_hat partials)
+    ProfScope ps(MATCHA_PROF_FRONT_BWD, (double)tcap * ((3.0 + (node ? 0 : nslab)) * 256.0 + 8.0 + (g.attr.mode == 1 ? 0.0 : 4.0 * n_attr) + 256.0), st);
+    if (node) hipLaunchKernelGGL(front_bwd_kernel<true>, dim3(grid), dim3(256), lds, st, g);
+    else hipLaunchKernelGGL(front_bwd_kernel<false>, dim3(grid), dim3(256), lds, st, g);
     MATCHA_CHECK_LAUNCH("front_bwd_kernel");
   }
   FrontReduceArgs a;

@@ -213,10 +213,12 @@ struct FusedBwdHArgs {
   int dx_atomic;                                   // 1: every head adds into ONE [tcap][64] buffer with float atomics (zeroed by the launcher); 0: one slab per head
   float* wslab;                                    // [8][nchunks][kWgSlabM]
   const float* rimg;                               // [nhalves][8][kImgRecH]: r rows (register images) + attention probabilities of the forward
+  const int32_t* xrow;                             // NODE instances: X is the per-node table of NORMALISED rows [n_nodes + 1][64] (node_xhat_kernel) and token t reads
+                                                   // row xrow[t] (the plan's tok_key: 0 = padding) -- no LayerNorm in the staging
 };
 constexpr size_t kBwdLdsBytes = (size_t)2 * kTileH * 4 + (size_t)4 * kPT * 2 + (64 + 256 + 256 + 32) * 4;
 
-template <int ML>
+template <int ML, bool NODE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void fused_bwdh_kernel(FusedBwdHArgs g) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* Xs = lds;                                   // x_hat f32 (keys = values of the attention)
@@ -260,10 +262,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #endif
 
   if (tid < 16) {                     // the padding token's x_hat
-    const float4 xv = *reinterpret_cast<const float4*>(g.X + (int64_t)tr * 64 + sc4);
-    float m, rs;
-    ln_row16(xv, m, rs);
-    *reinterpret_cast<float4*>(&xpad[sc4]) = make_float4((xv.x - m) * rs, (xv.y - m) * rs, (xv.z - m) * rs, (xv.w - m) * rs);
+    const float4 xv = *reinterpret_cast<const float4*>(g.X + (NODE ? (int64_t)0 : (int64_t)tr * 64) + sc4);
+    if constexpr (NODE) {
+      *reinterpret_cast<float4*>(&xpad[sc4]) = xv;
+    } else {
+      float m, rs;
+      ln_row16(xv, m, rs);
+      *reinterpret_cast<float4*>(&xpad[sc4]) = make_float4((xv.x - m) * rs, (xv.y - m) * rs, (xv.z - m) * rs, (xv.w - m) * rs);
+    }
   }
 
   // weight-gradient accumulators: rows 16 mt + 4 kq + reg, column fb + c16 of dB_h and dM_h (four 16 x 16 tiles each)
@@ -279,12 +285,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   int4 mn = tile_lo + 1 < tile_hi ? meta[tile_lo + 1] : mzero;
   float4 xn0, xn1, dn0, dn1;
   int tpn = 0;
+  int kx0 = 0, kx1 = 0;               // NODE: the table rows of the half tile whose rows are fetched NEXT (loaded one half tile earlier: no dependent load in the prefetch)
+#define FBH_KEY_GLOAD(I, M)                                                                              \
+  do {                                                                                                   \
+    const int row__ = srow + 16 * (I);                                                                   \
+    kx##I = g.xrow[(M).x + (row__ < (M).y ? row__ : ((M).y > 0 ? (M).y - 1 : 0))];                       \
+  } while (0)
   f32x4 ri0, ri1, pn = {0.f, 0.f, 0.f, 0.f};
 #define FBH_ROW_GLOAD(I, M)                                                                              \
   do {                                                                                                   \
     const int row__ = srow + 16 * (I);                                                                   \
     const int64_t tok__ = (M).x + (row__ < (M).y ? row__ : ((M).y > 0 ? (M).y - 1 : 0));                 \
-    xn##I = *reinterpret_cast<const float4*>(g.X + tok__ * 64 + sc4);                                    \
+    xn##I = *reinterpret_cast<const float4*>(g.X + (NODE ? (int64_t)kx##I : tok__) * 64 + sc4);           \
     dn##I = *reinterpret_cast<const float4*>(g.dDyn + tok__ * 64 + sc4);                                 \
   } while (0)
 #define FBH_ROWS_GLOAD(M)                                                                                \
@@ -298,11 +310,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int row__ = srow + 16 * (I);                                                                   \
     const float msk__ = row__ < n_real ? 1.f : 0.f;                                                      \
     const float4 xv__ = xn##I, dv__ = dn##I;                                                             \
-    const float mean__ = group_sum16_dpp((xv__.x + xv__.y) + (xv__.z + xv__.w)) * (1.f / 64.f);          \
-    const float a__ = xv__.x - mean__, b__ = xv__.y - mean__, c__ = xv__.z - mean__, e__ = xv__.w - mean__; \
-    const float q__ = group_sum16_dpp((a__ * a__ + b__ * b__) + (c__ * c__ + e__ * e__));                \
-    const float rs__ = msk__ * __builtin_amdgcn_rsqf(q__ * (1.f / 64.f) + kEpsLn);                       \
-    const float4 xh__ = make_float4(a__ * rs__, b__ * rs__, c__ * rs__, e__ * rs__);                     \
+    float4 xh__;                                                                                         \
+    if constexpr (NODE) {                                                                                \
+      xh__ = make_float4(xv__.x * msk__, xv__.y * msk__, xv__.z * msk__, xv__.w * msk__);                \
+    } else {                                                                                             \
+      const float mean__ = group_sum16_dpp((xv__.x + xv__.y) + (xv__.z + xv__.w)) * (1.f / 64.f);        \
+      const float a__ = xv__.x - mean__, b__ = xv__.y - mean__, c__ = xv__.z - mean__, e__ = xv__.w - mean__; \
+      const float q__ = group_sum16_dpp((a__ * a__ + b__ * b__) + (c__ * c__ + e__ * e__));              \
+      const float rs__ = msk__ * __builtin_amdgcn_rsqf(q__ * (1.f / 64.f) + kEpsLn);                     \
+      xh__ = make_float4(a__ * rs__, b__ * rs__, c__ * rs__, e__ * rs__);                                \
+    }                                                                                                    \
     *reinterpret_cast<float4*>(&Xs[row__ * kLd + sc4]) = xh__;                                           \
     {                                                                                                    \
       const P3 p0__ = split2(xh__.x, xh__.y), p1__ = split2(xh__.z, xh__.w);                             \
@@ -330,7 +347,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // dZ^T = M_h^T dDyn^T (rows = features) and the B operand of d x_hat = dR B_h (columns = features); three planes each
   Frag3 Mf[2], Bf[2];
   {
+    if constexpr (NODE) { FBH_KEY_GLOAD(0, mc); FBH_KEY_GLOAD(1, mc); }
     FBH_ROWS_GLOAD(mc);
+    if constexpr (NODE) { FBH_KEY_GLOAD(0, mn); FBH_KEY_GLOAD(1, mn); }
     if (tile_lo < tile_hi) FBH_RIMG_GLOAD(tile_lo);
     const float* mp = g.mM + (int64_t)head * 4096 + (8 * kq) * 64 + fb + c16;
     const float* bp = g.mB + (int64_t)head * 4096 + (8 * kq) * 64 + fb + c16;
@@ -412,6 +431,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     __syncthreads();
     FB_T(7);
     FBH_ROWS_GLOAD(mn);                               // next half tile's rows: in flight during the GEMMs below
+    if constexpr (NODE) { FBH_KEY_GLOAD(0, mnn); FBH_KEY_GLOAD(1, mnn); }      // ... and the table rows of the one after
     // ---- this head's share of d x_hat = dR B_h + Gs ----
     if (g.dx_atomic) {
       // rows = tokens 4 kq + reg (+ 16), columns = features fb + c16: one atomic instruction covers 4 token rows x 64 contiguous bytes.  The
@@ -633,7 +653,7 @@ __global__ __launch_bounds__(256) void fbm_chain_kernel(ChainArgs a) {
 // ---- slab reduction + un-folding of the LayerNorm affines -------------------------------------------------------
 struct UnfoldArgs {
   const float* wslab; int nchunks;
-  const float* X; const int32_t* count;
+  const float* X; const int32_t* count; int x_pad_row0;        // x_pad_row0: X is the per-node table, the padding token's row is row 0
   const float* W[3]; const float* g[3]; const float* b[3];     // original projection weights [512, 64] and LN affines
   float* gW[3]; float* gfc1;                                    // accumulated into
   float* part;                                                  // [32][3][3][64]: {dg, db, dx_hat_pad} partials
@@ -679,7 +699,7 @@ __global__ __launch_bounds__(256) void fb_unfold_kernel(UnfoldArgs a) {
     if (mat > 0) dpad += vb[192 + (mat - 1) * 64 + row];
   }
   // the padding token's K / V rows are x_hat_pad . W'^T + c: its dK / dV enter dW' and dc like one more token
-  const float4 xv = *reinterpret_cast<const float4*>(a.X + (int64_t)a.count[1] * 64 + c4);
+  const float4 xv = *reinterpret_cast<const float4*>(a.X + (a.x_pad_row0 ? (int64_t)0 : (int64_t)a.count[1] * 64) + c4);
   float m, rs;
   ln_row16(xv, m, rs);
   s.x += dpad * (xv.x - m) * rs; s.y += dpad * (xv.y - m) * rs; s.z += dpad * (xv.z - m) * rs; s.w += dpad * (xv.w - m) * rs;
@@ -782,8 +802,9 @@ size_t fused_bwd_ws_floats(int64_t B, int L) {
 // merged heads: fused_bwdh_kernel -> fbm_chain_kernel -> the LayerNorm un-folding of launch_fused_bwd (one slab per head)
 int launch_fused_bwd_merged(const matcha_tensors& p, const float* folded, const float* merged, const float* X, const float* dDyn, const float* dXs,
                             const Ragged& rg, int64_t B, int L, float* dxh, float* ws, matcha_tensors& grads, float* dZ0, hipStream_t st, const float* rimg,
-                            bool dx_atomic, bool dx_zeroed, const TailReduceArgs* tail) {
+                            bool dx_atomic, bool dx_zeroed, const TailReduceArgs* tail, const int32_t* xrow, const float* xhatN) {
   const int64_t tcap = B * L + 1;
+  MATCHA_CHECK_ARG(!xrow || xhatN, "fused backward: the node route needs the table of normalised rows");
   if (dx_atomic && !dx_zeroed) MATCHA_TRY(zero_async(dxh, (size_t)tcap * 64 * sizeof(float), st));
   int nchunks = 2 * chunks_for(rg.nhalves);                  // two four-wave workgroups per CU
   if (nchunks > kMaxChunks) nchunks = kMaxChunks;
@@ -796,8 +817,8 @@ int launch_fused_bwd_merged(const matcha_tensors& p, const float* folded, const 
   const MergedView mv = merged_view(merged);
   {
     FusedBwdHArgs g;
-    g.X = X; g.dDyn = dDyn; g.count = rg.count; g.half_meta = rg.half_meta; g.tok_pos = rg.tok_pos; g.L = L; g.nhalves = rg.nhalves; g.nchunks = nchunks;
-    g.mB = mv.B; g.mM = mv.M; g.dxh = dxh; g.tcap = tcap; g.dx_atomic = dx_atomic ? 1 : 0; g.wslab = wslab; g.rimg = rimg;
+    g.X = xrow ? xhatN : X; g.dDyn = dDyn; g.count = rg.count; g.half_meta = rg.half_meta; g.tok_pos = rg.tok_pos; g.L = L; g.nhalves = rg.nhalves; g.nchunks = nchunks;
+    g.mB = mv.B; g.mM = mv.M; g.dxh = dxh; g.tcap = tcap; g.dx_atomic = dx_atomic ? 1 : 0; g.wslab = wslab; g.rimg = rimg; g.xrow = xrow;
     const size_t lds = kBwdLdsBytes;
     auto launch = [&](auto kfn) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -814,12 +835,12 @@ int launch_fused_bwd_merged(const matcha_tensors& p, const float* folded, const 
     // every run -- and is faster.  The Makefile sets the flag for the whole library; tests/test_hip_properties.py::test_full_size_train_step_is_reproducible
     // is the run-time guard.
     switch (L <= 2 ? 2 : (L <= 6 ? L : 8)) {
-      case 2: launch(fused_bwdh_kernel<2>); break;
-      case 3: launch(fused_bwdh_kernel<3>); break;
-      case 4: launch(fused_bwdh_kernel<4>); break;
-      case 5: launch(fused_bwdh_kernel<5>); break;
-      case 6: launch(fused_bwdh_kernel<6>); break;
-      default: launch(fused_bwdh_kernel<8>); break;
+      case 2: if (xrow) launch(fused_bwdh_kernel<2, true>); else launch(fused_bwdh_kernel<2, false>); break;
+      case 3: if (xrow) launch(fused_bwdh_kernel<3, true>); else launch(fused_bwdh_kernel<3, false>); break;
+      case 4: if (xrow) launch(fused_bwdh_kernel<4, true>); else launch(fused_bwdh_kernel<4, false>); break;
+      case 5: if (xrow) launch(fused_bwdh_kernel<5, true>); else launch(fused_bwdh_kernel<5, false>); break;
+      case 6: if (xrow) launch(fused_bwdh_kernel<6, true>); else launch(fused_bwdh_kernel<6, false>); break;
+      default: if (xrow) launch(fused_bwdh_kernel<8, true>); else launch(fused_bwdh_kernel<8, false>); break;
     }
     MATCHA_CHECK_LAUNCH("fused_bwdh_kernel");
   }
@@ -838,7 +859,7 @@ int launch_fused_bwd_merged(const matcha_tensors& p, const float* folded, const 
   }
   {
     UnfoldArgs a;
-    a.wslab = chain; a.nchunks = 1; a.X = X; a.count = rg.count;
+    a.wslab = chain; a.nchunks = 1; a.X = X; a.count = rg.count; a.x_pad_row0 = xrow ? 1 : 0;
     a.W[0] = p.w_q; a.W[1] = p.w_k; a.W[2] = p.w_v;
     a.g[0] = p.ln_q_g; a.g[1] = p.ln_k_g; a.g[2] = p.ln_v_g;
     a.b[0] = p.ln_q_b; a.b[1] = p.ln_k_b; a.b[2] = p.ln_v_b;
@@ -855,6 +876,7 @@ int launch_fused_bwd_merged(const matcha_tensors& p, const float* folded, const 
     MATCHA_CHECK_LAUNCH("fb_unfold2_kernel");
   }
   if (dZ0) {
+    MATCHA_CHECK_ARG(!xrow, "fused backward: the node route has no dZ0 output");
     hipLaunchKernelGGL(lnhat_bwd_kernel, dim3((unsigned)cdiv(tcap, 16)), dim3(256), 0, st, X, dxh, tcap, dxpad, dXs, dZ0, rg.count, dx_atomic ? 1 : MATCHA_N_HEAD);
     MATCHA_CHECK_LAUNCH("lnhat_bwd_kernel");
   }

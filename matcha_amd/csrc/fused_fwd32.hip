@@ -278,6 +278,7 @@ __global__ __launch_bounds__(256) void prep_heads_kernel(PrepArgs a) {
 
 struct Fwd32Args {
   const float* X;
+  const int32_t* xrow;             // null: token t reads X + 64 t; node route: X is the per-node table and t reads row xrow[t] (the plan's tok_key: 0 = padding)
   const int32_t* row_off; const int32_t* tok_slot; const int32_t* count; const int32_t* half_meta; const int32_t* tok_pos;
   int L;
   const u32x4* wfrag;              // the bf16 x 3 fragment stream + the f32 bias table behind it (prep_heads_kernel)
@@ -328,7 +329,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 #define F32_BIAS(ROW) fl_vec(TV + (ROW) * 64 + 4 * h)
 
   // ---- x_hat in layout FL straight from global memory ----
-  FL xh = fl_load(g.X + F32_ROW());
+  int64_t xoff = F32_ROW();
+  if (g.xrow) xoff = (int64_t)g.xrow[F32_TOK()] * 64 + 4 * h;
+  FL xh = fl_load(g.X + xoff);
   int pos = 0, k = 0;
   if (real) {
     const int tp = g.tok_pos[F32_TOK()];
@@ -676,8 +679,9 @@ int launch_prep_heads(const matcha_tensors& p, float* folded, float* merged, flo
 
 int launch_fused_fwd32(const matcha_tensors& p, const float* folded, const float* frag, const float* X, const Ragged& rg, int64_t B, int L, const float* y,
                        const float* w, float* Y, float* H1, float* H2, float* logits, float* row_loss, const uint64_t* seed, float p_fc1, float p_pff,
-                       hipStream_t st, float* ddyn0, float* dXs, float* tslab, float alpha, float* rimg, float* tail_dh2, int objective) {
+                       hipStream_t st, float* ddyn0, float* dXs, float* tslab, float alpha, float* rimg, float* tail_dh2, int objective, const int32_t* xrow) {
   Fwd32Args g;
+  g.xrow = xrow;
   g.tail_dh2 = nullptr;
   g.X = X; g.row_off = rg.row_off; g.tok_slot = rg.tok_slot; g.count = rg.count; g.half_meta = rg.half_meta; g.tok_pos = rg.tok_pos;
   g.L = L;
@@ -696,6 +700,7 @@ int launch_fused_fwd32(const matcha_tensors& p, const float* folded, const float
   const int ml = L <= 2 ? 2 : (L <= 6 ? L : 8);
   // small batches (at most two half tiles per CU even at the bound): the heads side by side in eight wavefronts per half tile
   if (fused_small_batch(rg)) {
+    MATCHA_CHECK_ARG(!xrow, "fused forward: the node route runs the large-batch kernel only");
     const size_t ldsh = ((size_t)10 * kHT + 64) * sizeof(float);
     auto launchh = [&](auto kfn) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsh);

@@ -57,7 +57,9 @@ size_t ragged_bytes(int64_t B, int L);
 int ragged_tiles_cap(int64_t B, int L);
 int ragged_halves_cap(int64_t B, int L);
 void ragged_carve(int64_t B, int L, char* base, Ragged& r);
-int launch_ragged_plan(const int64_t* x, int64_t B, int L, int64_t n_nodes, int32_t* status, const Ragged& r, hipStream_t st, int level = 2);
+int launch_ragged_plan(const int64_t* x, int64_t B, int L, int64_t n_nodes, int32_t* status, const Ragged& r, hipStream_t st, int level = 2,
+                       int64_t* node_ids = nullptr, int32_t* node_cnt = nullptr, float* node_zero = nullptr);
+// (node_ids != null: the plan also writes the id list 0..n_nodes and its length {n_nodes + 1, n_nodes}; node_zero != null: and zeroes [n_nodes + 1][64] floats)
 
 struct HeadParams {
   const float *gp, *bp, *g1, *b1, *g2, *b2, *wc, *bc;
@@ -110,6 +112,7 @@ struct Options {
   int disable_merged;        // the reference formulation of the heads (four products per head) on the layer-by-layer kernels: the A/B variant
   int disable_small_batch;   // the large-batch kernels at every size: one wavefront per half tile in the forward, the ragged plan as five launches
   int disable_wide_gemm;     // embed_dim >= 128: the 64-wide GEMM / attention kernels
+  int disable_node_front;    // the table front end once per TOKEN at every size (the node route -- once per node when tokens outnumber nodes -- off)
   int debug_nan, fused_dbg;  // development
 };
 Options& options();
@@ -129,7 +132,8 @@ int launch_head_fwd(const int32_t* row_off, const float* H2, const float* X, int
                     int objective = MATCHA_OBJECTIVE_BCE);
 int launch_head_bwd(const int32_t* row_off, const float* H2, const float* X, int64_t B, int L, int d, const HeadParams& hp,
                     const float* y, const float* w, const float* logits, const float* dlogits, float alpha, float* dH2,
-                    float* dXs, float* slab, const HeadParams& ghp, hipStream_t st, int objective = MATCHA_OBJECTIVE_BCE);
+                    float* dXs, float* slab, const HeadParams& ghp, hipStream_t st, int objective = MATCHA_OBJECTIVE_BCE,
+                    const int32_t* xrow = nullptr);      // xrow != null: X is a per-node table and token t reads row xrow[t] (node route)
 size_t colsum_slab_bytes(int64_t n, int nv, int d);
 int launch_loss_reduce(const float* row_loss, int64_t B, float* bce_out, hipStream_t st, bool zero_recon = false,     // zero_recon: losses[1..2] = 0 too
                        float* zero_buf = nullptr, size_t zero_bytes = 0);                                               // a buffer zeroed by extra blocks of the launch
@@ -156,7 +160,8 @@ int launch_prep_heads(const matcha_tensors& p, float* folded, float* merged, flo
 int launch_fused_fwd32(const matcha_tensors& p, const float* folded, const float* frag, const float* X, const Ragged& rg, int64_t B, int L, const float* y,
                        const float* w, float* Y, float* H1, float* H2, float* logits, float* row_loss, const uint64_t* seed, float p_fc1, float p_pff,
                        hipStream_t st, float* ddyn0 = nullptr, float* dXs = nullptr, float* tslab = nullptr, float alpha = 0.f, float* rimg = nullptr,
-                       float* tail_dh2 = nullptr, int objective = MATCHA_OBJECTIVE_BCE);       // tail_dh2 (large batches only): the convolutions' backward is left to launch_tail_bwd64
+                       float* tail_dh2 = nullptr, int objective = MATCHA_OBJECTIVE_BCE,
+                       const int32_t* xrow = nullptr);       // xrow (large batches only): X is a per-node table, token t reads row xrow[t];  tail_dh2 (large batches only): the convolutions' backward is left to launch_tail_bwd64
 // tail_bwd.hip: the backward of pff_n1's two convolutions as its own kernel behind fused_fwd32_kernel (large batches)
 int tail_bwd_grid();
 size_t tail_bwd_slab_floats();
@@ -171,7 +176,8 @@ struct TailReduceArgs;
 int launch_fused_bwd_merged(const matcha_tensors& p, const float* folded, const float* merged, const float* X, const float* dDyn, const float* dXs,
                             const Ragged& rg, int64_t B, int L, float* dxh, float* ws, matcha_tensors& grads, float* dZ0, hipStream_t st, const float* rimg,
                             bool dx_atomic, bool dx_zeroed = false,    // dx_zeroed: the caller already zeroed dxh[(B L + 1) x 64] on this stream
-                            const struct TailReduceArgs* tail = nullptr);   // tail != null: the launch that sums this kernel's slabs also sums the forward's tail slabs (tail_reduce.hpp)
+                            const struct TailReduceArgs* tail = nullptr, const int32_t* xrow = nullptr, const float* xhatN = nullptr);
+// xrow != null (with xhatN): X is the per-node table (row 0 = padding) and xhatN its normalised rows; token t stages row xrow[t] of xhatN as it is;  tail != null: the launch that sums this kernel's slabs also sums the forward's tail slabs (tail_reduce.hpp)
 size_t fused_qkv_floats(int64_t B, int L);         // what the training forward leaves for the fused backward, per (half tile, head):
 constexpr int kImgRecH = 2048 + 256;               // 32 r rows (r = B_h x_hat + b_h; register images) + their attention probabilities [32][8].
                                                    // (Round 6 measured the alternative -- the forward keeps only the probabilities, fused_bwdh_kernel recomputes r from its
@@ -197,11 +203,15 @@ bool front_bwd_supported(int d, int n_attr);
 // prep != null: the launch also builds the encoder's per-step weight forms (what launch_prep_heads does) in blocks of their own
 struct PrepSpec { const matcha_tensors* p; float* folded; float* merged; float* frag; };
 int launch_front_fwd(const matcha_tensors& p, const int64_t* ids, const float* table, const float* dense, const matcha_frozen& f, int n_attr,
-                     const Ragged& rg, int64_t tcap, float* x0, float* X, hipStream_t st, const PrepSpec* prep = nullptr);
+                     const Ragged& rg, int64_t tcap, float* x0, float* X, hipStream_t st, const PrepSpec* prep = nullptr,
+                     const int32_t* count = nullptr);      // count != null: the row count word to use instead of the plan's (node route: ids = 0..n_nodes)
 size_t front_bwd_ws_floats();
 int launch_front_bwd(const matcha_tensors& p, const float* X, const float* dxh, int nslab, int64_t tcap, const float* dxpad, const float* dXs, const float* x0,
                      const int64_t* ids, const matcha_frozen& f, int n_attr, const Ragged& rg, float* dX0, float* dtable, float* ws,
-                     matcha_tensors& grads, hipStream_t st, int32_t* touched = nullptr);
+                     matcha_tensors& grads, hipStream_t st, int32_t* touched = nullptr,
+                     const int32_t* node_count = nullptr);   // node_count != null: the node route -- rows = nodes, dXs = their summed gradient rows, no d x_hat term
+int launch_node_xhat(const float* XN, const int32_t* node_count, int64_t rows_cap, float* xhatN, hipStream_t st);     // x_hat = LayerNorm without affine, per node row
+int launch_node_scatter(const float* XN, const float* dxh, const float* dxpad, const float* dXs, const Ragged& rg, int64_t tcap, float* G, hipStream_t st);
 
 // attention.hip
 // shared_kv (embed_dim >= 128, merged heads): K and V are [T, d] tensors that every head attends (dK / dV still come back per head)

@@ -106,6 +106,9 @@ struct Workspace {
   float* qkv;                             // training forward -> fused backward: Q, K, V tiles of every (tile, head), 384 KB per tile
   float* front_ws;                        // fused front-end backward: workgroup slabs
   void* tg_ws;      size_t tg_ws_bytes;   // table mode: sort scratch of the deterministic table gradient (table_grad.hip)
+  // node route of the table front end (null when the shape cannot take it): X and x0 per NODE [n_nodes + 1][64] (row 0: the padding id), the
+  // backward's per-node sum of the tokens' gradient rows, the id list 0..n_nodes and its length {n_nodes + 1, n_nodes} (both written by the plan)
+  float *XN, *x0N, *xhN, *GN; int64_t* node_ids; int32_t* node_cnt;
   size_t total;
 };
 
@@ -120,12 +123,13 @@ struct Workspace {
 //                            forward, eight-wave / 64-row-tile / recompute backward, their five switches) are gone since round 4
 //   disable_small_batch      the kernels picked for small batches by size -- one workgroup of eight wavefronts (one per head) per half tile
 //                            in the forward, the ragged plan as one launch -- replaced by the large-batch kernels
+//   disable_node_front       the table front end per TOKEN at every size (node_front_shape / the rule in forward_impl decide otherwise)
 //   disable_wide_gemm        embed_dim >= 128: the 64-wide GEMM / attention kernels (gemm_lds.hip, gemm_f32.hip, attention.hip; four-product
 //                            heads) instead of gemm_wide.hip / attention_wide.hip
 struct OptionName { const char* name; int Options::*field; };
 static const OptionName kOptionNames[] = {
     {"disable_fused", &Options::disable_fused}, {"disable_merged", &Options::disable_merged}, {"disable_small_batch", &Options::disable_small_batch},
-    {"disable_wide_gemm", &Options::disable_wide_gemm}, {"debug_nan", &Options::debug_nan}, {"fused_dbg", &Options::fused_dbg}};
+    {"disable_wide_gemm", &Options::disable_wide_gemm}, {"disable_node_front", &Options::disable_node_front}, {"debug_nan", &Options::debug_nan}, {"fused_dbg", &Options::fused_dbg}};
 Options& options() {
   static Options o = [] {
     Options v;
@@ -155,6 +159,13 @@ static bool enc128_enabled(const matcha_shape& s, const matcha_step_opts& o) {
 }
 static bool fused_enabled(const matcha_shape& s) { return s.d == 64 && options().disable_fused != 1 && !options().disable_merged; }
 static bool fused_front_enabled() { return (options().disable_fused & 2) == 0; }
+// Node route of the table front end: everything in front of the encoder -- x0 = table[id] + attribute_nn(attr[id]), X = tanh(next_w(x0)) -- is a
+// function of the node id alone (no dropout in front of the attention), so when the tokens outnumber the nodes it is computed once per NODE
+// and the encoder kernels gather their rows by id; the backward adds the tokens' gradient rows per node first and runs tanh' / next_w /
+// attribute_nn / the table row once per node.  The SHAPE half of the rule (it sizes the workspace, so it must not depend on a switch):
+static bool node_front_shape(const matcha_shape& s, int64_t B, int L) {
+  return s.mode == 0 && s.d == 64 && front_bwd_supported(s.d, s.n_attr) && B * L + 1 >= 4 * ((int64_t)s.n_nodes + 1);
+}
 // the loss can be computed: BCE needs labels and weights, the softplus MSE only its targets
 static bool has_target(int objective, const float* y, const float* w) { return objective == MATCHA_OBJECTIVE_SOFTPLUS_MSE ? y != nullptr : (y && w); }
 static bool loss_in_forward(const matcha_shape& s, const matcha_step_opts& o, const float* y, const float* w, int objective) {
@@ -170,9 +181,9 @@ static int check_objective(int32_t objective, const char* fn) {
 // consume records nobody wrote.  Host-side record per workspace pointer (the decision picks a kernel, so it cannot live in device memory
 // without a synchronisation); bounded, evicted oldest-first, guarded by a mutex.  A backward on a workspace WITHOUT a record is refused.
 static std::mutex g_fwd_mu;
-static std::unordered_map<const void*, std::pair<int, uint64_t>> g_fwd_state;     // ws -> (bits, age); bit 0: merged heads, bit 1: fused d = 64 forward, bit 2: fused d = 128 attention block, bit 3: the tail's backward ran as tail_bwd64_kernel, bit 4: the forward zeroed the d x_hat rows of the backward kernel
+static std::unordered_map<const void*, std::pair<int, uint64_t>> g_fwd_state;     // ws -> (bits, age); bit 0: merged heads, bit 1: fused d = 64 forward, bit 2: fused d = 128 attention block, bit 3: the tail's backward ran as tail_bwd64_kernel, bit 4: the forward zeroed the d x_hat rows of the backward kernel, bit 5: the front end ran per node (node route)
 static uint64_t g_fwd_clock = 0;
-static void note_forward(const void* ws, bool merged, bool fused, bool enc = false, bool split_tail = false, bool dx_zeroed = false) {
+static void note_forward(const void* ws, bool merged, bool fused, bool enc = false, bool split_tail = false, bool dx_zeroed = false, bool node = false) {
   std::lock_guard<std::mutex> lk(g_fwd_mu);
   if (g_fwd_state.size() >= 4096 && g_fwd_state.find(ws) == g_fwd_state.end()) {
     auto old = g_fwd_state.begin();
@@ -180,7 +191,7 @@ static void note_forward(const void* ws, bool merged, bool fused, bool enc = fal
       if (it->second.second < old->second.second) old = it;
     g_fwd_state.erase(old);
   }
-  g_fwd_state[ws] = std::make_pair((merged ? 1 : 0) | (fused ? 2 : 0) | (enc ? 4 : 0) | (split_tail ? 8 : 0) | (dx_zeroed ? 16 : 0), ++g_fwd_clock);
+  g_fwd_state[ws] = std::make_pair((merged ? 1 : 0) | (fused ? 2 : 0) | (enc ? 4 : 0) | (split_tail ? 8 : 0) | (dx_zeroed ? 16 : 0) | (node ? 32 : 0), ++g_fwd_clock);
 }
 static int ws_state(const void* ws) {       // -1: no forward on record for this workspace
   std::lock_guard<std::mutex> lk(g_fwd_mu);
@@ -290,6 +301,12 @@ static size_t carve(const matcha_shape& s, int64_t B, int L, char* base, Workspa
   w.front_ws = take(front_bwd_supported(s.d, s.n_attr) ? front_bwd_ws_floats() : 0);
   w.tg_ws_bytes = (s.mode == 0 && !compact) ? table_grad_ws_bytes(Tn, s.n_nodes) : 0;
   w.tg_ws = take(w.tg_ws_bytes / sizeof(float));
+  {
+    const size_t nn = node_front_shape(s, B, L) ? (size_t)(s.n_nodes + 1) : 0;
+    w.XN = take_always(nn * 64); w.x0N = take(nn * 64); w.xhN = take(nn * 64); w.GN = take(nn * 64);
+    w.node_ids = reinterpret_cast<int64_t*>(take_always(nn * 2));
+    w.node_cnt = reinterpret_cast<int32_t*>(take_always(nn ? 64 : 0));
+  }
   w.total = off;
   return off;
 }
@@ -469,10 +486,14 @@ static int forward_impl(const matcha_shape* shp, const matcha_tensors* params, c
   // fit and runs layer by layer (it used to fail with MATCHA_ENOMEM)
   const bool enc = !force_layerwise && enc128_enabled(s, *opts) && (opts->forward_only || enc128_rec_floats(w.rg) <= w.enc_rec_floats);
   const int plan_level = (fused_enabled(s) || enc) ? 1 : 0;
-  MATCHA_TRY(launch_ragged_plan(x, B, L, s.n_nodes, opts->status, w.rg, st, plan_level));
+  const bool front = !force_layerwise && fused_enabled(s) && front_bwd_supported(s.d, s.n_attr) && fused_front_enabled();
+  // node route (node_front_shape): decided here from shapes and per-call options alone -- capturable -- and recorded for the backward
+  const bool node = front && fused_path && node_front_shape(s, B, L) && !fused_small_batch(w.rg) && !opts->deterministic && !opts->sparse_table_grad &&
+                    !options().disable_node_front;
+  MATCHA_TRY(launch_ragged_plan(x, B, L, s.n_nodes, opts->status, w.rg, st, plan_level, node ? w.node_ids : nullptr, node ? w.node_cnt : nullptr,
+                                (node && !opts->forward_only) ? w.GN : nullptr));      // ... which also writes the node route's id list and zeroes its accumulator
   // front end: node rows (K1) + attribute path (K6) + add (Modules.py:263-269)
   float* recon_out = losses ? losses + 1 : nullptr;
-  const bool front = !force_layerwise && fused_enabled(s) && front_bwd_supported(s.d, s.n_attr) && fused_front_enabled();
   // table front end: the two reconstruction-loss slots are zero; loss_reduce_kernel writes them when it runs anyway
   const bool recon_zero_in_loss = s.mode == 0 && recon_out && fused_path && tgt && losses;
   // adj front end at embed_dim 64: gather-GEMM, W1, attribute path and next_w in ONE kernel over the chromosome-sorted rows (adj_fused.hip)
@@ -494,6 +515,12 @@ static int forward_impl(const matcha_shape* shp, const matcha_tensors* params, c
     // (fused encoder behind it: the launch also builds the step's weight forms -- folded / merged / fragment-order -- in blocks of their own)
     const PrepSpec prep = {&p, w.folded, w.merged, w.frag};
     prep_in_front = fused_path;
+    if (node) {     // the same kernel, once over the ids 0..n_nodes: the per-node tables (the weight-form blocks keep riding in the launch)
+      MATCHA_TRY(launch_front_fwd(p, w.node_ids, p.table, nullptr, *frozen, s.n_attr, w.rg, (int64_t)s.n_nodes + 1, opts->forward_only ? nullptr : w.x0N, w.XN, st,
+                                  prep_in_front ? &prep : nullptr, w.node_cnt));
+      // ... and, for the backward kernel's staging, their normalised rows
+      if (!opts->forward_only) MATCHA_TRY(launch_node_xhat(w.XN, w.node_cnt, (int64_t)s.n_nodes + 1, w.xhN, st));
+    } else
     MATCHA_TRY(launch_front_fwd(p, ids, s.mode == 0 ? p.table : nullptr, s.mode == 0 ? nullptr : w.node, *frozen, s.n_attr, w.rg, Tn,
                                 opts->forward_only ? nullptr : w.x0, w.X, st, prep_in_front ? &prep : nullptr));     // x0 (pre-activation) is only read by the backward pass
   } else {
@@ -518,12 +545,14 @@ static int forward_impl(const matcha_shape* shp, const matcha_tensors* params, c
     // the backward kernel's heads ADD their d x_hat rows (float atomics) unless the sum has to be reproducible: the rows are zeroed by a launch
     // that runs anyway -- tail_bwd64_kernel, or for small batches the loss reduction's -- and the record says so
     const bool zero_dx = lif && !opts->deterministic && !opts->sparse_table_grad && (split_tail || fused_small_batch(w.rg)) && tgt && losses;
-    if (opts->forward_only) forget_forward(ws); else note_forward(ws, true, true, false, split_tail, zero_dx);
+    if (opts->forward_only) forget_forward(ws); else note_forward(ws, true, true, false, split_tail, zero_dx, node);
     // (with the tail's backward in the forward kernel, Y and H1 are still handed over: the single-wave kernel PARKS the two rows there
     // (and the normalised H2 row in H2's place) between the tail's forward and backward halves instead of holding 96 registers per lane -- fused_fwd32_tail.hpp)
-    MATCHA_TRY(launch_fused_fwd32(p, w.folded, w.frag, w.X, w.rg, B, L, y, w_bce, (save || lif) ? w.Y : nullptr, (save || lif) ? w.H1 : nullptr, (save || lif) ? w.H2 : nullptr,
+    // (node route: the kernel reads its row from the per-node table at the plan's sanitised id -- tok_key: 0 for the padding token and foreign ids)
+    MATCHA_TRY(launch_fused_fwd32(p, w.folded, w.frag, node ? w.XN : w.X, w.rg, B, L, y, w_bce, (save || lif) ? w.Y : nullptr, (save || lif) ? w.H1 : nullptr, (save || lif) ? w.H2 : nullptr,
                                   lg_out, w.row_loss, opts->seed, train ? opts->p_drop_fc1 : 0.f, train ? opts->p_drop_pff : 0.f, st,
-                                  lif ? w.ddyn0 : nullptr, w.dXs, w.tslab, opts->alpha, keep_rimg ? w.qkv : nullptr, split_tail ? w.dH2 : nullptr, objective));
+                                  lif ? w.ddyn0 : nullptr, w.dXs, w.tslab, opts->alpha, keep_rimg ? w.qkv : nullptr, split_tail ? w.dH2 : nullptr, objective,
+                                  node ? w.rg.tok_key : nullptr));
     if (split_tail)
       MATCHA_TRY(launch_tail_bwd64(p, w.dH2, w.Y, w.H1, w.rg, opts->seed, train ? opts->p_drop_fc1 : 0.f, train ? opts->p_drop_pff : 0.f, w.ddyn0, w.tslab2, w.tslab,
                                    zero_dx ? w.dO : nullptr, st, w.row_loss, B, tgt ? losses : nullptr, recon_zero_in_loss));      // ... zeroes the backward's d x_hat rows, reduces the loss
@@ -643,7 +672,8 @@ extern "C" int matcha_debug_layout(const matcha_shape* shp, int64_t B, int32_t L
       {"P", w.P}, {"O_dxh", w.O}, {"Y", w.Y}, {"H1", w.H1}, {"H2", w.H2}, {"row_loss", w.row_loss}, {"logits", w.logits}, {"node", w.node}, {"dH2", w.dH2},
       {"dXs", w.dXs}, {"dZ1", w.dZ1}, {"ddyn0", w.ddyn0}, {"dZ0", w.dZ0}, {"dX0", w.dX0}, {"slab", w.slab}, {"gemm_ws", w.gemm_ws}, {"adj_ws", w.adj_ws},
       {"folded", w.folded}, {"frag", w.frag}, {"merged", w.merged}, {"lwB", w.lwB}, {"lwM", w.lwM}, {"lwdB", w.lwdB}, {"lwdM", w.lwdM}, {"enc", w.enc}, {"fb_ws", w.fb_ws},
-      {"tpart", w.tpart}, {"tslab", w.tslab}, {"tslab2", w.tslab2}, {"qkv_records", w.qkv}, {"front_ws", w.front_ws}, {"tg_ws", w.tg_ws}};
+      {"tpart", w.tpart}, {"tslab", w.tslab}, {"tslab2", w.tslab2}, {"qkv_records", w.qkv}, {"front_ws", w.front_ws}, {"tg_ws", w.tg_ws}, {"XN", w.XN}, {"x0N", w.x0N}, {"xhN", w.xhN}, {"GN", w.GN},
+      {"node_ids", w.node_ids}, {"node_cnt", w.node_cnt}};
   size_t n = 0;
   for (const auto& e : f) {
     if (!e.p) continue;
@@ -723,6 +753,7 @@ static int backward_impl(const matcha_shape* shp, const matcha_tensors* params, 
   forget_forward(ws);                                   // one backward per forward: from here on the saved activations are being overwritten
   bool dx_zeroed = false, tail_in_bwd = false;
   TailReduceArgs tail_args;
+  const bool node = fused_fwd && (fwd_state & 32) != 0;        // the forward ran the front end per node: X lives in the per-node table, rows by tok_key
   if (lif) {
     // ddyn0 and dXs were produced by matcha_forward; only the per-half-tile parameter-gradient partials remain to be summed
     // (fused_fwd32.hip).  Small batches: one launch, which also zeroes the buffer the backward kernel's heads add their d x_hat into
@@ -742,7 +773,8 @@ static int backward_impl(const matcha_shape* shp, const matcha_tensors* params, 
   // tail: dH2, dXs and the gradients of pff_n1.layer_norm, layer_norm1/2, pff_classifier
   HeadParams hp = {p.pff_ln_g, p.pff_ln_b, p.ln1_g, p.ln1_b, p.ln2_g, p.ln2_b, p.cls_w, p.cls_b};
   HeadParams ghp = {g_.pff_ln_g, g_.pff_ln_b, g_.ln1_g, g_.ln1_b, g_.ln2_g, g_.ln2_b, g_.cls_w, g_.cls_b};
-  MATCHA_TRY(launch_head_bwd(w.rg.row_off, w.H2, w.X, B, L, d, hp, y, w_bce, w.logits, dlogits, opts->alpha, w.dH2, w.dXs, w.slab, ghp, st, objective));
+  MATCHA_TRY(launch_head_bwd(w.rg.row_off, w.H2, node ? w.XN : w.X, B, L, d, hp, y, w_bce, w.logits, dlogits, opts->alpha, w.dH2, w.dXs, w.slab, ghp, st, objective,
+                             node ? w.rg.tok_key : nullptr));
   // pff_n1 conv1: dW1 += dH2^T H1 ; db1 += colsum(dH2) ; dZ1 = (dH2 W1) * dropmask * (1 - tanh^2)
   MATCHA_TRY(launch_gemm_tn(w.dH2, w.H1, g_.pff1_w, g_.pff1_b, d, d, Tn, d, d, nullptr, true, w.gemm_ws, w.gemm_ws_bytes, st, cnt));
   {
@@ -763,17 +795,26 @@ static int backward_impl(const matcha_shape* shp, const matcha_tensors* params, 
   if (fused_fwd) {
     // attention block (fc1, attention, Q/K/V projections, the three LayerNorms) from X and ddyn0 in one head-major kernel;
     // the forward pass left the folded weights in w.folded.  w.dO doubles as the 8 per-head d x_hat slabs.
-    const bool front = front_bwd_supported(s.d, s.n_attr) && fused_front_enabled();
+    const bool front = node || (front_bwd_supported(s.d, s.n_attr) && fused_front_enabled());
     // the eight heads add their d x_hat into ONE buffer with float atomics (they meet in L2; per-head slabs are 8 x 256 B per token written
     // and read back).  `deterministic` and the row-sparse table gradient (whose sum is bitwise reproducible) keep the slabs and their
     // fixed summation order
     const bool dx_atomic = !opts->deterministic && !opts->sparse_table_grad;
-    MATCHA_TRY(launch_fused_bwd_merged(p, w.folded, w.merged, w.X, w.ddyn0, w.dXs, w.rg, B, L, w.dO, w.fb_ws, g_, front ? nullptr : w.dZ0, st, w.qkv, dx_atomic, dx_zeroed,
-                                       tail_in_bwd ? &tail_args : nullptr));
+    MATCHA_CHECK_ARG(!node || dx_atomic, "matcha_backward: deterministic / sparse_table_grad differ from the forward's on this workspace");
+    MATCHA_TRY(launch_fused_bwd_merged(p, w.folded, w.merged, node ? w.XN : w.X, w.ddyn0, w.dXs, w.rg, B, L, w.dO, w.fb_ws, g_, front ? nullptr : w.dZ0, st, w.qkv, dx_atomic, dx_zeroed,
+                                       tail_in_bwd ? &tail_args : nullptr, node ? w.rg.tok_key : nullptr, node ? w.xhN : nullptr));
     MATCHA_TRY(encoder_done(*opts, st));
     if (front) {
       // LayerNorm backward of the summed partials + next_w + attribute_nn backward + embedding scatter in one kernel
       if (s.mode == 0) MATCHA_CHECK_ARG(g_.table, "matcha_backward: table mode without a table gradient buffer");
+      if (node) {
+        // the tokens' rows LNbwd(d x_hat) + dXs added per node (one pass over the tokens), then tanh' / next_w / attribute_nn / the table row
+        // once per node: front_bwd_kernel over the ids 0..n_nodes with the sums in dXs' place, one writer per table-gradient row
+        MATCHA_TRY(launch_node_scatter(w.XN, w.dO, fused_bwd_dxpad(w.fb_ws), w.dXs, w.rg, Tn, w.GN, st));
+        MATCHA_TRY(launch_front_bwd(p, w.XN, nullptr, 1, (int64_t)s.n_nodes + 1, fused_bwd_dxpad(w.fb_ws), w.GN, w.x0N, w.node_ids, *frozen, s.n_attr, w.rg,
+                                    nullptr, g_.table, w.front_ws, g_, st, touched, w.node_cnt));
+        return MATCHA_OK;
+      }
       const bool rows_out = s.mode == 1 || opts->deterministic || opts->sparse_table_grad;     // dX0 rows instead of float atomics
       MATCHA_TRY(launch_front_bwd(p, w.X, w.dO, dx_atomic ? 1 : MATCHA_N_HEAD, Tn, fused_bwd_dxpad(w.fb_ws), w.dXs, w.x0, ids, *frozen, s.n_attr, w.rg,
                                   rows_out ? w.dX0 : nullptr, rows_out ? nullptr : g_.table, w.front_ws, g_, st, s.mode == 0 ? touched : nullptr));

@@ -95,7 +95,8 @@ __global__ __launch_bounds__(256) void row_fill_kernel(const int64_t* __restrict
                                                        const int32_t* __restrict__ count, int32_t* __restrict__ row_off,
                                                        int32_t* __restrict__ tok_slot, int64_t* __restrict__ tok_id,
                                                        int32_t* __restrict__ tok_pos, int32_t* __restrict__ sb_first, int super_tok,
-                                                       int32_t* __restrict__ tok_key, int64_t n_nodes, int32_t* __restrict__ status) {
+                                                       int32_t* __restrict__ tok_key, int64_t n_nodes, int32_t* __restrict__ status,
+                                                       int64_t* __restrict__ node_ids, int32_t* __restrict__ node_cnt, float* __restrict__ node_zero) {
   __shared__ int lds4[4];
   const int64_t b0 = (int64_t)blockIdx.x * kRowsPerBlock + threadIdx.x * kRpt;
   // this thread's rows (and the row in front of them) in registers: ONE round of loads, all in flight together, on clamped
@@ -161,6 +162,14 @@ __global__ __launch_bounds__(256) void row_fill_kernel(const int64_t* __restrict
   // tok_key of every slot behind the real tokens is 0 (the padding token's included): written here instead of a memset of the whole
   // array in front of the plan (the real tokens' keys are written above by their owners; nobody else touches slots >= tr)
   for (int64_t i = tr + (int64_t)blockIdx.x * 256 + threadIdx.x; i < B * L + 1; i += (int64_t)gridDim.x * 256) tok_key[i] = 0;
+  // node route of the table front end (model.hip): the id list 0..n_nodes and its length, written here like tok_key's zeros -- no memset, no copy
+  if (node_ids) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i <= n_nodes; i += (int64_t)gridDim.x * 256) node_ids[i] = i;
+    if (blockIdx.x == 0 && threadIdx.x == 0) { node_cnt[0] = (int32_t)(n_nodes + 1); node_cnt[1] = (int32_t)n_nodes; }
+  }
+  if (node_zero)      // ... and the zeros of the backward's per-node accumulator [n_nodes + 1][64]
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < (n_nodes + 1) * 16; i += (int64_t)gridDim.x * 256)
+      reinterpret_cast<float4*>(node_zero)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
 // Tiles of the fused kernels: runs of whole consecutive hyperedges with at most 63 tokens (+ the shared padding token = 64
@@ -315,6 +324,7 @@ struct PlanSmallArgs {
   int nsb, level;
   int32_t* sb_tiles[2]; int cap_per_sb[2]; int ntiles_cap[2]; int32_t* meta[2];
   int32_t* tok_tile;
+  float* node_zero; int64_t* node_ids; int32_t* node_cnt;      // node route of the table front end: the id list 0..n_nodes and its length (null: not asked)
 };
 __global__ __launch_bounds__(1024) void plan_small_kernel(PlanSmallArgs a) {
   __shared__ int wtot[16];
@@ -377,6 +387,12 @@ __global__ __launch_bounds__(1024) void plan_small_kernel(PlanSmallArgs a) {
     if (a.level <= 0) { a.count[2] = 0; a.count[3] = 0; }
   }
   for (int64_t i = total + tid; i < B * L + 1; i += 1024) a.tok_key[i] = 0;
+  if (a.node_ids) {
+    for (int64_t i = tid; i <= a.n_nodes; i += 1024) a.node_ids[i] = i;
+    if (tid == 0) { a.node_cnt[0] = (int32_t)(a.n_nodes + 1); a.node_cnt[1] = (int32_t)a.n_nodes; }
+  }
+  if (a.node_zero)
+    for (int64_t i = tid; i < (a.n_nodes + 1) * 16; i += 1024) reinterpret_cast<float4*>(a.node_zero)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
   __syncthreads();                                       // row_off (global) and sbf (LDS) are complete
   if (tid <= a.nsb) a.sb_first[tid] = sbf[tid < kSmallSb ? tid : kSmallSb];
   if (a.level <= 0) return;
@@ -471,7 +487,8 @@ void ragged_carve(int64_t B, int L, char* base, Ragged& r) {
 
 // level 2: everything; 1: no 64-row tile list and no token -> tile map (the fused kernels that run work on half tiles only); 0: rows and
 // tokens only (no fused kernel will read a tile list)
-int launch_ragged_plan(const int64_t* x, int64_t B, int L, int64_t n_nodes, int32_t* status, const Ragged& r, hipStream_t st, int level) {
+int launch_ragged_plan(const int64_t* x, int64_t B, int L, int64_t n_nodes, int32_t* status, const Ragged& r, hipStream_t st, int level,
+                       int64_t* node_ids, int32_t* node_cnt, float* node_zero) {
   if (B <= kSmallRows && r.nsb <= kSmallSb && !options().disable_small_batch) {
     PlanSmallArgs a;
     a.x = x; a.B = B; a.L = L; a.n_nodes = n_nodes; a.status = status;
@@ -480,6 +497,7 @@ int launch_ragged_plan(const int64_t* x, int64_t B, int L, int64_t n_nodes, int3
     a.sb_tiles[0] = r.sb_tiles; a.cap_per_sb[0] = r.sb_cap; a.ntiles_cap[0] = r.ntiles; a.meta[0] = r.tile_meta;
     a.sb_tiles[1] = r.sb_htiles; a.cap_per_sb[1] = r.sb_hcap; a.ntiles_cap[1] = r.nhalves; a.meta[1] = r.half_meta;
     a.tok_tile = r.tok_tile;
+    a.node_ids = node_ids; a.node_cnt = node_cnt; a.node_zero = node_zero;
     hipLaunchKernelGGL(plan_small_kernel, dim3(1), dim3(1024), 0, st, a);
     MATCHA_CHECK_LAUNCH("plan_small_kernel");
     return MATCHA_OK;
@@ -489,7 +507,7 @@ int launch_ragged_plan(const int64_t* x, int64_t B, int L, int64_t n_nodes, int3
   hipLaunchKernelGGL(row_scan_kernel, dim3(1), dim3(1024), 0, st, r.blk_sum, r.nblk, r.count, r.sb_first, r.nsb, (int32_t)B);
   MATCHA_CHECK_LAUNCH("row_scan_kernel");
   hipLaunchKernelGGL(row_fill_kernel, dim3(r.nblk), dim3(256), 0, st, x, B, L, r.blk_sum, r.count, r.row_off, r.tok_slot, r.tok_id, r.tok_pos, r.sb_first, kSuperTok,
-                     r.tok_key, n_nodes, status);
+                     r.tok_key, n_nodes, status, node_ids, node_cnt, node_zero);
   MATCHA_CHECK_LAUNCH("row_fill_kernel");
   if (level <= 0) return MATCHA_OK;
   const int first = level >= 2 ? 0 : 1;                // list 0: 64-row tiles, list 1: half tiles

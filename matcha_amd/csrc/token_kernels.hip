@@ -538,7 +538,8 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const int32_t* __restrict
                                                        const float* __restrict__ y, const float* __restrict__ w,
                                                        const float* __restrict__ logits, const float* __restrict__ dlogits,
                                                        float alpha, float* __restrict__ dH2, float* __restrict__ dXs,
-                                                       float* __restrict__ slab, int rows_per_blk, int objective) {
+                                                       float* __restrict__ slab, int rows_per_blk, int objective,
+                                                       const int32_t* __restrict__ xrow) {      // xrow != null: X is a per-node table, token t reads row xrow[t]
   __shared__ float lds[16 * 256];
   __shared__ float lds_bc[16];
   const int s = threadIdx.x & 15, slot = threadIdx.x >> 4;
@@ -575,7 +576,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const int32_t* __restrict
       load_row<NCH>(H2 + t * d, s, d, h);
       row_stats<NCH>(h, s, d, m, rh); normalize<NCH>(h, s, d, m, rh, hh); affine<NCH>(hh, Gp, Bp, u);
       row_stats<NCH>(u, s, d, m, ru); normalize<NCH>(u, s, d, m, ru, uh); affine<NCH>(uh, G1, B1, dn);
-      load_row<NCH>(X + t * d, s, d, xr);
+      load_row<NCH>(X + (xrow ? (int64_t)xrow[t] : t) * d, s, d, xr);
       row_stats<NCH>(xr, s, d, m, rx); normalize<NCH>(xr, s, d, m, rx, xh); affine<NCH>(xh, G2, B2, sn);
       Row ddn, dsn, tmp, du, dhh, dh, dxs;
 #pragma unroll
@@ -807,13 +808,13 @@ int launch_head_fwd(const int32_t* row_off, const float* H2, const float* X, int
 
 int launch_head_bwd(const int32_t* row_off, const float* H2, const float* X, int64_t B, int L, int d, const HeadParams& hp,
                     const float* y, const float* w, const float* logits, const float* dlogits, float alpha, float* dH2,
-                    float* dXs, float* slab, const HeadParams& ghp, hipStream_t st, int objective) {
+                    float* dXs, float* slab, const HeadParams& ghp, hipStream_t st, int objective, const int32_t* xrow) {
   if (B <= 0) return MATCHA_OK;
   int per;
   const int nblk = colsum_blocks(B, &per);
   {
     ProfScope ps(MATCHA_PROF_HEAD_BWD, (double)B * L * (16.0 * d + 8.0), st);  // read H2, X; write dH2, dXs
-    DISPATCH_NCH(d, hipLaunchKernelGGL((head_bwd_kernel<NCH>), dim3(nblk), dim3(256), 0, st, row_off, H2, X, B, L, d, hp, y, w, logits, dlogits, alpha, dH2, dXs, slab, per, objective));
+    DISPATCH_NCH(d, hipLaunchKernelGGL((head_bwd_kernel<NCH>), dim3(nblk), dim3(256), 0, st, row_off, H2, X, B, L, d, hp, y, w, logits, dlogits, alpha, dH2, dXs, slab, per, objective, xrow));
   }
   MATCHA_CHECK_LAUNCH("head_bwd_kernel");
   ColsumDst dst = {{(float*)ghp.gp, (float*)ghp.bp, (float*)ghp.g1, (float*)ghp.b1, (float*)ghp.g2, (float*)ghp.b2, (float*)ghp.wc, (float*)ghp.bc}};
