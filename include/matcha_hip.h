@@ -84,14 +84,16 @@ int matcha_launch_log_read(char* out, size_t cap);
 
 /* A/B switches for tests and profiling.  Each option is read from the environment variable MATCHA_<NAME> (upper case) ONCE,
  * when the library is loaded, and can be changed afterwards only through matcha_set_option -- no entry point reads the
- * environment per call.  FIVE switches: "disable_fused" (1 = layer-by-layer kernels at every embed_dim, also instead of the fused
+ * environment per call.  SIX switches: "disable_fused" (1 = layer-by-layer kernels at every embed_dim, also instead of the fused
  * attention block of embed_dim 128; 2 = only the front end as separate kernels, the encoder stays fused), "disable_merged" (the reference's four products per attention head instead of the
  * merged two; they live on the layer-by-layer kernels, so at embed_dim 64 this implies disable_fused), "disable_small_batch" (the
  * large-batch forward and plan kernels at every size), "disable_wide_gemm" (embed_dim >= 128: the 64-wide GEMM / attention kernels
  * instead of the 128 x 128 ones), "disable_node_front" (the table front end once per TOKEN at every size: without it, a step at embed_dim 64
  * whose token capacity B L + 1 is at least 4 (n_nodes + 1) -- large-batch kernels, not deterministic, no row-sparse table gradient --
  * computes x0, X and the front end's backward once per NODE and gathers the rows by node id; same logits and losses bit for bit, the
- * gradients differ in summation order only); development: "debug_nan", "fused_dbg" (bit 0: the backward of
+ * gradients differ in summation order only), "disable_node_r" (on the node route: the heads' r rows r = B_h x_hat + b_h computed per TOKEN inside
+ * the forward kernel and handed to the backward in the per-half-tile record; without it node_r_kernel computes them once per (node, head)
+ * and both encoder kernels gather them by node id -- same logits and losses bit for bit); development: "debug_nan", "fused_dbg" (bit 0: the backward of
  * pff_n1's convolutions inside the forward kernel at every batch size, instead of tail_bwd64_kernel for large batches).  (Whether the tail's backward runs inside the forward
  * kernel is a per-call choice: matcha_step_opts.loss_in_forward.)  Returns MATCHA_EINVAL for an unknown name;
  * matcha_get_option returns -1 for one.

@@ -215,6 +215,7 @@ struct FusedBwdHArgs {
   const float* rimg;                               // [nhalves][8][kImgRecH]: r rows (register images) + attention probabilities of the forward
   const int32_t* xrow;                             // NODE instances: X is the per-node table of NORMALISED rows [n_nodes + 1][64] (node_xhat_kernel) and token t reads
                                                    // row xrow[t] (the plan's tok_key: 0 = padding) -- no LayerNorm in the staging
+  const float* rn; int64_t rn_head;                // NODE instances, non-null: the heads' r rows per node [8][rn_head / 64][64] (node_r_kernel); the record holds probabilities only
 };
 constexpr size_t kBwdLdsBytes = (size_t)2 * kTileH * 4 + (size_t)4 * kPT * 2 + (64 + 256 + 256 + 32) * 4;
 
@@ -304,6 +305,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     FBH_ROW_GLOAD(0, M); FBH_ROW_GLOAD(1, M);                                                            \
     if (tid < 32) tpn = g.tok_pos[(M).x + (tid < (M).y ? tid : ((M).y > 0 ? (M).y - 1 : 0))];           \
   } while (0)
+  // NODE with the r table: this head's r rows of the same two table rows, row-major like the x_hat rows (16 lanes per 256-byte row).  Issued
+  // next to FBH_ROWS_GLOAD while kx0 / kx1 still hold that half tile's keys
+  const bool r_tab = NODE && g.rn != nullptr;
+#define FBH_R_GLOAD()                                                                                    \
+  do {                                                                                                   \
+    const float* rh__ = g.rn + (int64_t)head * g.rn_head + sc4;                                          \
+    ri0 = *reinterpret_cast<const f32x4*>(rh__ + (int64_t)kx0 * 64); ri1 = *reinterpret_cast<const f32x4*>(rh__ + (int64_t)kx1 * 64); \
+  } while (0)
   // x_hat row -> Xs (f32) and Xp (planes); dDyn row (zero past the tokens) -> Dp (planes) + its column sums
 #define FBH_ROW_STAGE(I)                                                                                 \
   do {                                                                                                   \
@@ -341,7 +350,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   do {                                                                                                   \
     const f32x4* r__ = reinterpret_cast<const f32x4*>(g.rimg + ((int64_t)(HALF) * MATCHA_N_HEAD + head) * kImgRecH);  \
     if (tid < 64) pn = __builtin_nontemporal_load(r__ + 512 + tid);                                      \
-    ri0 = __builtin_nontemporal_load(r__ + tid); ri1 = __builtin_nontemporal_load(r__ + 256 + tid);      \
+    if (!r_tab) { ri0 = __builtin_nontemporal_load(r__ + tid); ri1 = __builtin_nontemporal_load(r__ + 256 + tid); } \
   } while (0)
   // B_h and M_h as register fragments for the whole walk: lane (c16, kq), step s holds W[32 s + 8 kq + {0..7}][fb + c16] -- the A operand of
   // dZ^T = M_h^T dDyn^T (rows = features) and the B operand of d x_hat = dR B_h (columns = features); three planes each
@@ -349,7 +358,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   {
     if constexpr (NODE) { FBH_KEY_GLOAD(0, mc); FBH_KEY_GLOAD(1, mc); }
     FBH_ROWS_GLOAD(mc);
-    if constexpr (NODE) { FBH_KEY_GLOAD(0, mn); FBH_KEY_GLOAD(1, mn); }
+    if constexpr (NODE) { if (r_tab) FBH_R_GLOAD(); FBH_KEY_GLOAD(0, mn); FBH_KEY_GLOAD(1, mn); }
     if (tile_lo < tile_hi) FBH_RIMG_GLOAD(tile_lo);
     const float* mp = g.mM + (int64_t)head * 4096 + (8 * kq) * 64 + fb + c16;
     const float* bp = g.mB + (int64_t)head * 4096 + (8 * kq) * 64 + fb + c16;
@@ -372,8 +381,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     {
       FBH_ROW_STAGE(0); FBH_ROW_STAGE(1);
       if (tid < 32) tinfo[tid] = tid < n_real ? ((tid - (tpn & 255)) | (tpn & ~255)) : 0;
-      f32x4* d__ = reinterpret_cast<f32x4*>(&Rs[(lane & 31) * kLd + 8 * wave + 4 * (lane >> 5)]);
-      d__[0] = ri0; d__[8] = ri1;
+      if (r_tab) {
+        *reinterpret_cast<f32x4*>(&Rs[srow * kLd + sc4]) = ri0; *reinterpret_cast<f32x4*>(&Rs[(srow + 16) * kLd + sc4]) = ri1;
+      } else {
+        f32x4* d__ = reinterpret_cast<f32x4*>(&Rs[(lane & 31) * kLd + 8 * wave + 4 * (lane >> 5)]);
+        d__[0] = ri0; d__[8] = ri1;
+      }
       if (tid < 64) reinterpret_cast<f32x4*>(Ps)[tid] = pn;
     }
     __syncthreads();
@@ -431,7 +444,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     __syncthreads();
     FB_T(7);
     FBH_ROWS_GLOAD(mn);                               // next half tile's rows: in flight during the GEMMs below
-    if constexpr (NODE) { FBH_KEY_GLOAD(0, mnn); FBH_KEY_GLOAD(1, mnn); }      // ... and the table rows of the one after
+    if constexpr (NODE) { if (r_tab) FBH_R_GLOAD(); FBH_KEY_GLOAD(0, mnn); FBH_KEY_GLOAD(1, mnn); }      // ... its r rows (r table), and the table rows of the one after
     // ---- this head's share of d x_hat = dR B_h + Gs ----
     if (g.dx_atomic) {
       // rows = tokens 4 kq + reg (+ 16), columns = features fb + c16: one atomic instruction covers 4 token rows x 64 contiguous bytes.  The
@@ -802,9 +815,10 @@ size_t fused_bwd_ws_floats(int64_t B, int L) {
 // merged heads: fused_bwdh_kernel -> fbm_chain_kernel -> the LayerNorm un-folding of launch_fused_bwd (one slab per head)
 int launch_fused_bwd_merged(const matcha_tensors& p, const float* folded, const float* merged, const float* X, const float* dDyn, const float* dXs,
                             const Ragged& rg, int64_t B, int L, float* dxh, float* ws, matcha_tensors& grads, float* dZ0, hipStream_t st, const float* rimg,
-                            bool dx_atomic, bool dx_zeroed, const TailReduceArgs* tail, const int32_t* xrow, const float* xhatN) {
+                            bool dx_atomic, bool dx_zeroed, const TailReduceArgs* tail, const int32_t* xrow, const float* xhatN, const float* rn, int64_t rn_rows) {
   const int64_t tcap = B * L + 1;
   MATCHA_CHECK_ARG(!xrow || xhatN, "fused backward: the node route needs the table of normalised rows");
+  MATCHA_CHECK_ARG(!rn || xrow, "fused backward: the r table belongs to the node route");
   if (dx_atomic && !dx_zeroed) MATCHA_TRY(zero_async(dxh, (size_t)tcap * 64 * sizeof(float), st));
   int nchunks = 2 * chunks_for(rg.nhalves);                  // two four-wave workgroups per CU
   if (nchunks > kMaxChunks) nchunks = kMaxChunks;
@@ -819,6 +833,7 @@ int launch_fused_bwd_merged(const matcha_tensors& p, const float* folded, const 
     FusedBwdHArgs g;
     g.X = xrow ? xhatN : X; g.dDyn = dDyn; g.count = rg.count; g.half_meta = rg.half_meta; g.tok_pos = rg.tok_pos; g.L = L; g.nhalves = rg.nhalves; g.nchunks = nchunks;
     g.mB = mv.B; g.mM = mv.M; g.dxh = dxh; g.tcap = tcap; g.dx_atomic = dx_atomic ? 1 : 0; g.wslab = wslab; g.rimg = rimg; g.xrow = xrow;
+    g.rn = rn; g.rn_head = rn_rows * 64;
     const size_t lds = kBwdLdsBytes;
     auto launch = [&](auto kfn) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);

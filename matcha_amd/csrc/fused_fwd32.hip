@@ -292,6 +292,8 @@ struct Fwd32Args {
   int objective;      // MATCHA_OBJECTIVE_*: the per-hyperedge loss and its logit gradient (fused_fwd32_tail.hpp)
   float* qkv;         // training: the record per (half tile, head) -- this wavefront's own r rows + probabilities, kImgRecH floats (fused_bwdh_kernel)
   float* tail_dh2;    // single-wave kernel, training: [T][64] dH2 rows -- the tail's backward stops behind its LayerNorms, tail_bwd64_kernel does the convolutions
+  const float* rn;    // node route, single-wave kernel: the heads' r rows per NODE, [8][rn_rows][64] (node_r_kernel) -- gathered by xrow instead of computed per token
+  int rn_rows;
 };
 
 // Merged per-head matrices (two products per head: r = B_h x + b_h, dyn += M_h z).
@@ -321,7 +323,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
   // ---- weight stream: prime the window with the first chunk of R_0; the f32 bias table -> TV (free until the tail) ----
   const u32x4* wp;
   u32x4 W_[F32_WIN];
-  W32_PRIME_AT(0);
+  W32_PRIME_AT(g.rn ? 2 : 0);          // (r table: the stream starts at M_0)
   {
     const f32x4* bsrc = reinterpret_cast<const f32x4*>(g.wfrag + (kNMat + 1) * kFragU4);
     for (int i4 = lane; i4 < kNBias * 16; i4 += 64) reinterpret_cast<f32x4*>(TV)[i4] = bsrc[i4];
@@ -436,11 +438,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 
   FF_T(0);
   fl_store(krow, xh);
+  FL dyn;
+  if (!g.rn) {
   // x_hat as three bf16 planes: the token-side operand of all eight r products (x_hat in f32 is dead until the tail, which reads its row back)
   B3 xs[4];
   FL_SPLIT(xs[0], xh, 0); FL_SPLIT(xs[1], xh, 1); FL_SPLIT(xs[2], xh, 2); FL_SPLIT(xs[3], xh, 3);
   F32_WAVE_SYNC();                                    // x_hat rows and the bias table visible (one wavefront = the whole workgroup)
-  FL dyn = F32_BIAS(kBiasDyn);                        // the merged fc1 bias enters once
+  dyn = F32_BIAS(kBiasDyn);                           // the merged fc1 bias enters once
   {
     // ======================= merged heads: two products per head, keys = values = the x_hat rows (written to TK once) =======================
     // pieces of head hd (five per step of the NEXT head's r product): score half-dots, softmax, probabilities out, z half-rows
@@ -491,6 +495,35 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     F32_STAGE8(F32_MG_ONLY);
     FF_T(2);
     W32_CHAIN(dyn, o, true);
+    FF_T(5);
+  }
+  } else {
+    // ======================= node route with the r table (node_r_kernel): r = B_h x_hat + b_h depends on (node, head) only, so the row is GATHERED
+    // (bit for bit what the product above leaves in `q`: an MFMA output column depends on the same column of the token-side operand alone).  No
+    // x_hat planes, no R_h fragments, no r rows in the record; the next head's row is in flight during this head's attention pieces, in the
+    // registers the r product's accumulator has above; the stream is re-primed from M_h to M_{h+1} (R_{h+2} sits between them)
+    F32_WAVE_SYNC();
+    dyn = F32_BIAS(kBiasDyn);
+    int roff = g.xrow[F32_TOK()] * 64 + 4 * h;
+    const float* rnh = g.rn;
+    FL q = fl_load(rnh + roff), o;
+    FF_T(1);
+    int hd = 0;
+    for (; hd + 1 < MATCHA_N_HEAD; ++hd) {
+      o = fl_zero();
+      rnh += (int64_t)g.rn_rows * 64;
+      const FL acc = fl_load(rnh + roff);             // r_{hd+1}
+      F32_STAGE8(F32_MG_ONLY);
+      FF_T(2);
+      W32_CHAIN(dyn, o, false);                       // dyn += M_hd z
+      W32_PRIME_AT(hd + 1 < MATCHA_N_HEAD - 1 ? 2 * hd + 4 : 15);      // M_{hd+1}
+      q = acc;
+      FF_T(5);
+    }
+    o = fl_zero();
+    F32_STAGE8(F32_MG_ONLY);
+    FF_T(2);
+    W32_CHAIN(dyn, o, true);                          // ... M_7; conv0 follows it in the stream
     FF_T(5);
   }
   // =========================== tail: pff_n1, LayerNorms, classifier (all in registers) ===========================
@@ -647,6 +680,45 @@ __global__ __launch_bounds__(512) void fused_fwd32h_kernel(Fwd32Args g) {
 #endif
 }
 
+// ---- the heads' r rows once per NODE (node route) -------------------------------------------------------------------------
+// r = B_h x_hat + b_h is a function of (node, head) alone -- nothing per token sits in front of it -- and at the headline a node has ~75
+// tokens.  One wavefront takes 32 consecutive rows of the per-node table XN and one head and runs fused_fwd32_kernel's OWN text on them: the
+// prologue (load, statistics, normalise, split) and the r product (the same WB_MMA sequence and plane order, the bias entering the
+// accumulator the same way).  An MFMA output column depends only on the same column of the token-side operand, so every token of a node
+// gathers bit for bit the row the per-token product computes.  Rows row-major: RN[(h rows + node) 64 + f].
+struct NodeRArgs { const float* X; const u32x4* wfrag; float* rn; int rows; };
+__global__ __launch_bounds__(64) void node_r_kernel(NodeRArgs g) {
+  const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
+  const int hd = blockIdx.y;
+  const int row = (int)blockIdx.x * 32 + r;
+  const bool live = row < g.rows;
+  const u32x4* wp;
+  u32x4 W_[F32_WIN];
+  W32_PRIME_AT(hd == 0 ? 0 : 2 * hd - 1);             // R_hd (prep_heads_kernel's stream order)
+  FL xh = fl_load(g.X + (int64_t)(live ? row : g.rows - 1) * 64 + 4 * h);
+  {
+    float mean, rx;
+    fl_stats(xh, mean, rx);
+#pragma unroll
+    for (int e = 0; e < 16; ++e) { xh.lo[e] = (xh.lo[e] - mean) * rx; xh.hi[e] = (xh.hi[e] - mean) * rx; }
+  }
+  B3 xs[4];
+  FL_SPLIT(xs[0], xh, 0); FL_SPLIT(xs[1], xh, 1); FL_SPLIT(xs[2], xh, 2); FL_SPLIT(xs[3], xh, 3);
+  FL q = F32_BIAS(kBiasR + hd);
+  W32_CHAIN_XS(q, xs, false);
+  if (live) fl_store_global(g.rn + ((int64_t)hd * g.rows + row) * 64 + 4 * h, q);
+}
+
+size_t node_r_floats(int64_t rows) { return (size_t)MATCHA_N_HEAD * rows * 64; }
+int launch_node_r(const float* XN, const float* frag, int64_t rows, float* rn, hipStream_t st) {
+  NodeRArgs g;
+  g.X = XN; g.wfrag = reinterpret_cast<const u32x4*>(frag); g.rn = rn; g.rows = (int)rows;
+  ProfScope ps(MATCHA_PROF_FUSED_FWD, 0.0, st);       // part of the fused forward; no algorithmic work of its own
+  hipLaunchKernelGGL(node_r_kernel, dim3((unsigned)cdiv(rows, 32), MATCHA_N_HEAD), dim3(64), 0, st, g);
+  MATCHA_CHECK_LAUNCH("node_r_kernel");
+  return MATCHA_OK;
+}
+
 static int fwd32h_max_halves() { return 2 * device_cu_count(); }
 
 bool fused_small_batch(const Ragged& rg) { return rg.nhalves <= fwd32h_max_halves() && !options().disable_small_batch; }
@@ -679,9 +751,12 @@ int launch_prep_heads(const matcha_tensors& p, float* folded, float* merged, flo
 
 int launch_fused_fwd32(const matcha_tensors& p, const float* folded, const float* frag, const float* X, const Ragged& rg, int64_t B, int L, const float* y,
                        const float* w, float* Y, float* H1, float* H2, float* logits, float* row_loss, const uint64_t* seed, float p_fc1, float p_pff,
-                       hipStream_t st, float* ddyn0, float* dXs, float* tslab, float alpha, float* rimg, float* tail_dh2, int objective, const int32_t* xrow) {
+                       hipStream_t st, float* ddyn0, float* dXs, float* tslab, float alpha, float* rimg, float* tail_dh2, int objective, const int32_t* xrow,
+                       const float* rn, int64_t rn_rows) {
   Fwd32Args g;
   g.xrow = xrow;
+  MATCHA_CHECK_ARG(!rn || xrow, "fused forward: the r table belongs to the node route");
+  g.rn = rn; g.rn_rows = (int)rn_rows;
   g.tail_dh2 = nullptr;
   g.X = X; g.row_off = rg.row_off; g.tok_slot = rg.tok_slot; g.count = rg.count; g.half_meta = rg.half_meta; g.tok_pos = rg.tok_pos;
   g.L = L;

@@ -113,6 +113,7 @@ struct Options {
   int disable_small_batch;   // the large-batch kernels at every size: one wavefront per half tile in the forward, the ragged plan as five launches
   int disable_wide_gemm;     // embed_dim >= 128: the 64-wide GEMM / attention kernels
   int disable_node_front;    // the table front end once per TOKEN at every size (the node route -- once per node when tokens outnumber nodes -- off)
+  int disable_node_r;        // node route: the heads' r rows computed per TOKEN inside the forward kernel and handed to the backward in the record (the per-node r table off)
   int debug_nan, fused_dbg;  // development
 };
 Options& options();
@@ -161,7 +162,11 @@ int launch_fused_fwd32(const matcha_tensors& p, const float* folded, const float
                        const float* w, float* Y, float* H1, float* H2, float* logits, float* row_loss, const uint64_t* seed, float p_fc1, float p_pff,
                        hipStream_t st, float* ddyn0 = nullptr, float* dXs = nullptr, float* tslab = nullptr, float alpha = 0.f, float* rimg = nullptr,
                        float* tail_dh2 = nullptr, int objective = MATCHA_OBJECTIVE_BCE,
-                       const int32_t* xrow = nullptr);       // xrow (large batches only): X is a per-node table, token t reads row xrow[t];  tail_dh2 (large batches only): the convolutions' backward is left to launch_tail_bwd64
+                       const int32_t* xrow = nullptr,        // xrow (large batches only): X is a per-node table, token t reads row xrow[t];  tail_dh2 (large batches only): the convolutions' backward is left to launch_tail_bwd64
+                       const float* rn = nullptr, int64_t rn_rows = 0);      // rn (with xrow): the heads' r rows per node [8][rn_rows][64] (launch_node_r) -- gathered, not computed per token
+// the r rows of every (head, node): rows of the per-node table XN -> RN[8][rows][64]; needs this step's fragment stream (launch_prep_heads / the front end's launch)
+size_t node_r_floats(int64_t rows);
+int launch_node_r(const float* XN, const float* frag, int64_t rows, float* rn, hipStream_t st);
 // tail_bwd.hip: the backward of pff_n1's two convolutions as its own kernel behind fused_fwd32_kernel (large batches)
 int tail_bwd_grid();
 size_t tail_bwd_slab_floats();
@@ -176,7 +181,8 @@ struct TailReduceArgs;
 int launch_fused_bwd_merged(const matcha_tensors& p, const float* folded, const float* merged, const float* X, const float* dDyn, const float* dXs,
                             const Ragged& rg, int64_t B, int L, float* dxh, float* ws, matcha_tensors& grads, float* dZ0, hipStream_t st, const float* rimg,
                             bool dx_atomic, bool dx_zeroed = false,    // dx_zeroed: the caller already zeroed dxh[(B L + 1) x 64] on this stream
-                            const struct TailReduceArgs* tail = nullptr, const int32_t* xrow = nullptr, const float* xhatN = nullptr);
+                            const struct TailReduceArgs* tail = nullptr, const int32_t* xrow = nullptr, const float* xhatN = nullptr,
+                            const float* rn = nullptr, int64_t rn_rows = 0);      // rn (with xrow): the forward gathered r from this table and left no r rows in the record
 // xrow != null (with xhatN): X is the per-node table (row 0 = padding) and xhatN its normalised rows; token t stages row xrow[t] of xhatN as it is;  tail != null: the launch that sums this kernel's slabs also sums the forward's tail slabs (tail_reduce.hpp)
 size_t fused_qkv_floats(int64_t B, int L);         // what the training forward leaves for the fused backward, per (half tile, head):
 constexpr int kImgRecH = 2048 + 256;               // 32 r rows (r = B_h x_hat + b_h; register images) + their attention probabilities [32][8].

@@ -109,6 +109,7 @@ struct Workspace {
   // node route of the table front end (null when the shape cannot take it): X and x0 per NODE [n_nodes + 1][64] (row 0: the padding id), the
   // backward's per-node sum of the tokens' gradient rows, the id list 0..n_nodes and its length {n_nodes + 1, n_nodes} (both written by the plan)
   float *XN, *x0N, *xhN, *GN; int64_t* node_ids; int32_t* node_cnt;
+  float* RN;                              // ... and the heads' r rows per node [8][n_nodes + 1][64] (node_r_kernel), rebuilt by every forward on the route
   size_t total;
 };
 
@@ -124,12 +125,14 @@ struct Workspace {
 //   disable_small_batch      the kernels picked for small batches by size -- one workgroup of eight wavefronts (one per head) per half tile
 //                            in the forward, the ragged plan as one launch -- replaced by the large-batch kernels
 //   disable_node_front       the table front end per TOKEN at every size (node_front_shape / the rule in forward_impl decide otherwise)
+//   disable_node_r           node route: r = B_h x_hat + b_h per TOKEN inside the forward kernel, the rows handed to the backward in the record (without it:
+//                            once per (node, head) by node_r_kernel, both encoder kernels gather the rows by tok_key)
 //   disable_wide_gemm        embed_dim >= 128: the 64-wide GEMM / attention kernels (gemm_lds.hip, gemm_f32.hip, attention.hip; four-product
 //                            heads) instead of gemm_wide.hip / attention_wide.hip
 struct OptionName { const char* name; int Options::*field; };
 static const OptionName kOptionNames[] = {
     {"disable_fused", &Options::disable_fused}, {"disable_merged", &Options::disable_merged}, {"disable_small_batch", &Options::disable_small_batch},
-    {"disable_wide_gemm", &Options::disable_wide_gemm}, {"disable_node_front", &Options::disable_node_front}, {"debug_nan", &Options::debug_nan}, {"fused_dbg", &Options::fused_dbg}};
+    {"disable_wide_gemm", &Options::disable_wide_gemm}, {"disable_node_front", &Options::disable_node_front}, {"disable_node_r", &Options::disable_node_r}, {"debug_nan", &Options::debug_nan}, {"fused_dbg", &Options::fused_dbg}};
 Options& options() {
   static Options o = [] {
     Options v;
@@ -181,9 +184,9 @@ static int check_objective(int32_t objective, const char* fn) {
 // consume records nobody wrote.  Host-side record per workspace pointer (the decision picks a kernel, so it cannot live in device memory
 // without a synchronisation); bounded, evicted oldest-first, guarded by a mutex.  A backward on a workspace WITHOUT a record is refused.
 static std::mutex g_fwd_mu;
-static std::unordered_map<const void*, std::pair<int, uint64_t>> g_fwd_state;     // ws -> (bits, age); bit 0: merged heads, bit 1: fused d = 64 forward, bit 2: fused d = 128 attention block, bit 3: the tail's backward ran as tail_bwd64_kernel, bit 4: the forward zeroed the d x_hat rows of the backward kernel, bit 5: the front end ran per node (node route)
+static std::unordered_map<const void*, std::pair<int, uint64_t>> g_fwd_state;     // ws -> (bits, age); bit 0: merged heads, bit 1: fused d = 64 forward, bit 2: fused d = 128 attention block, bit 3: the tail's backward ran as tail_bwd64_kernel, bit 4: the forward zeroed the d x_hat rows of the backward kernel, bit 5: the front end ran per node (node route), bit 6: ... and the forward gathered the heads' r rows from the per-node table (no r rows in the record)
 static uint64_t g_fwd_clock = 0;
-static void note_forward(const void* ws, bool merged, bool fused, bool enc = false, bool split_tail = false, bool dx_zeroed = false, bool node = false) {
+static void note_forward(const void* ws, bool merged, bool fused, bool enc = false, bool split_tail = false, bool dx_zeroed = false, bool node = false, bool node_r = false) {
   std::lock_guard<std::mutex> lk(g_fwd_mu);
   if (g_fwd_state.size() >= 4096 && g_fwd_state.find(ws) == g_fwd_state.end()) {
     auto old = g_fwd_state.begin();
@@ -191,7 +194,7 @@ static void note_forward(const void* ws, bool merged, bool fused, bool enc = fal
       if (it->second.second < old->second.second) old = it;
     g_fwd_state.erase(old);
   }
-  g_fwd_state[ws] = std::make_pair((merged ? 1 : 0) | (fused ? 2 : 0) | (enc ? 4 : 0) | (split_tail ? 8 : 0) | (dx_zeroed ? 16 : 0) | (node ? 32 : 0), ++g_fwd_clock);
+  g_fwd_state[ws] = std::make_pair((merged ? 1 : 0) | (fused ? 2 : 0) | (enc ? 4 : 0) | (split_tail ? 8 : 0) | (dx_zeroed ? 16 : 0) | (node ? 32 : 0) | (node_r ? 64 : 0), ++g_fwd_clock);
 }
 static int ws_state(const void* ws) {       // -1: no forward on record for this workspace
   std::lock_guard<std::mutex> lk(g_fwd_mu);
@@ -306,6 +309,10 @@ static size_t carve(const matcha_shape& s, int64_t B, int L, char* base, Workspa
     w.XN = take_always(nn * 64); w.x0N = take(nn * 64); w.xhN = take(nn * 64); w.GN = take(nn * 64);
     w.node_ids = reinterpret_cast<int64_t*>(take_always(nn * 2));
     w.node_cnt = reinterpret_cast<int32_t*>(take_always(nn ? 64 : 0));
+    // The r table: 8 (n_nodes + 1) rows.  A workspace that can be differentiated keeps it in Q's buffer -- the fused d = 64 kernels never touch
+    // Q / K / V (see above), and Tn >= 4 (n_nodes + 1) rows of 8 d floats hold it four times over -- so the route costs a training step no memory;
+    // the compact layout of a forward-only call has no Q and takes the rows
+    w.RN = nn ? (compact ? take_always(node_r_floats((int64_t)nn)) : w.Q) : nullptr;
   }
   w.total = off;
   return off;
@@ -490,6 +497,7 @@ static int forward_impl(const matcha_shape* shp, const matcha_tensors* params, c
   // node route (node_front_shape): decided here from shapes and per-call options alone -- capturable -- and recorded for the backward
   const bool node = front && fused_path && node_front_shape(s, B, L) && !fused_small_batch(w.rg) && !opts->deterministic && !opts->sparse_table_grad &&
                     !options().disable_node_front;
+  const bool node_r = node && !options().disable_node_r;      // ... with the heads' r rows once per node (recorded like the route itself)
   MATCHA_TRY(launch_ragged_plan(x, B, L, s.n_nodes, opts->status, w.rg, st, plan_level, node ? w.node_ids : nullptr, node ? w.node_cnt : nullptr,
                                 (node && !opts->forward_only) ? w.GN : nullptr));      // ... which also writes the node route's id list and zeroes its accumulator
   // front end: node rows (K1) + attribute path (K6) + add (Modules.py:263-269)
@@ -520,6 +528,8 @@ static int forward_impl(const matcha_shape* shp, const matcha_tensors* params, c
                                   prep_in_front ? &prep : nullptr, w.node_cnt));
       // ... and, for the backward kernel's staging, their normalised rows
       if (!opts->forward_only) MATCHA_TRY(launch_node_xhat(w.XN, w.node_cnt, (int64_t)s.n_nodes + 1, w.xhN, st));
+      // ... and the heads' r rows, from the fragment stream the launch above just wrote (training and inference alike)
+      if (node_r) MATCHA_TRY(launch_node_r(w.XN, w.frag, (int64_t)s.n_nodes + 1, w.RN, st));
     } else
     MATCHA_TRY(launch_front_fwd(p, ids, s.mode == 0 ? p.table : nullptr, s.mode == 0 ? nullptr : w.node, *frozen, s.n_attr, w.rg, Tn,
                                 opts->forward_only ? nullptr : w.x0, w.X, st, prep_in_front ? &prep : nullptr));     // x0 (pre-activation) is only read by the backward pass
@@ -545,14 +555,14 @@ static int forward_impl(const matcha_shape* shp, const matcha_tensors* params, c
     // the backward kernel's heads ADD their d x_hat rows (float atomics) unless the sum has to be reproducible: the rows are zeroed by a launch
     // that runs anyway -- tail_bwd64_kernel, or for small batches the loss reduction's -- and the record says so
     const bool zero_dx = lif && !opts->deterministic && !opts->sparse_table_grad && (split_tail || fused_small_batch(w.rg)) && tgt && losses;
-    if (opts->forward_only) forget_forward(ws); else note_forward(ws, true, true, false, split_tail, zero_dx, node);
+    if (opts->forward_only) forget_forward(ws); else note_forward(ws, true, true, false, split_tail, zero_dx, node, node_r);
     // (with the tail's backward in the forward kernel, Y and H1 are still handed over: the single-wave kernel PARKS the two rows there
     // (and the normalised H2 row in H2's place) between the tail's forward and backward halves instead of holding 96 registers per lane -- fused_fwd32_tail.hpp)
     // (node route: the kernel reads its row from the per-node table at the plan's sanitised id -- tok_key: 0 for the padding token and foreign ids)
     MATCHA_TRY(launch_fused_fwd32(p, w.folded, w.frag, node ? w.XN : w.X, w.rg, B, L, y, w_bce, (save || lif) ? w.Y : nullptr, (save || lif) ? w.H1 : nullptr, (save || lif) ? w.H2 : nullptr,
                                   lg_out, w.row_loss, opts->seed, train ? opts->p_drop_fc1 : 0.f, train ? opts->p_drop_pff : 0.f, st,
                                   lif ? w.ddyn0 : nullptr, w.dXs, w.tslab, opts->alpha, keep_rimg ? w.qkv : nullptr, split_tail ? w.dH2 : nullptr, objective,
-                                  node ? w.rg.tok_key : nullptr));
+                                  node ? w.rg.tok_key : nullptr, node_r ? w.RN : nullptr, (int64_t)s.n_nodes + 1));
     if (split_tail)
       MATCHA_TRY(launch_tail_bwd64(p, w.dH2, w.Y, w.H1, w.rg, opts->seed, train ? opts->p_drop_fc1 : 0.f, train ? opts->p_drop_pff : 0.f, w.ddyn0, w.tslab2, w.tslab,
                                    zero_dx ? w.dO : nullptr, st, w.row_loss, B, tgt ? losses : nullptr, recon_zero_in_loss));      // ... zeroes the backward's d x_hat rows, reduces the loss
@@ -673,7 +683,7 @@ extern "C" int matcha_debug_layout(const matcha_shape* shp, int64_t B, int32_t L
       {"dXs", w.dXs}, {"dZ1", w.dZ1}, {"ddyn0", w.ddyn0}, {"dZ0", w.dZ0}, {"dX0", w.dX0}, {"slab", w.slab}, {"gemm_ws", w.gemm_ws}, {"adj_ws", w.adj_ws},
       {"folded", w.folded}, {"frag", w.frag}, {"merged", w.merged}, {"lwB", w.lwB}, {"lwM", w.lwM}, {"lwdB", w.lwdB}, {"lwdM", w.lwdM}, {"enc", w.enc}, {"fb_ws", w.fb_ws},
       {"tpart", w.tpart}, {"tslab", w.tslab}, {"tslab2", w.tslab2}, {"qkv_records", w.qkv}, {"front_ws", w.front_ws}, {"tg_ws", w.tg_ws}, {"XN", w.XN}, {"x0N", w.x0N}, {"xhN", w.xhN}, {"GN", w.GN},
-      {"node_ids", w.node_ids}, {"node_cnt", w.node_cnt}};
+      {"node_ids", w.node_ids}, {"node_cnt", w.node_cnt}, {"RN", w.RN}};
   size_t n = 0;
   for (const auto& e : f) {
     if (!e.p) continue;
@@ -754,6 +764,7 @@ static int backward_impl(const matcha_shape* shp, const matcha_tensors* params, 
   bool dx_zeroed = false, tail_in_bwd = false;
   TailReduceArgs tail_args;
   const bool node = fused_fwd && (fwd_state & 32) != 0;        // the forward ran the front end per node: X lives in the per-node table, rows by tok_key
+  const bool node_r = node && (fwd_state & 64) != 0;           // ... and gathered r from the per-node table: the record holds probabilities only
   if (lif) {
     // ddyn0 and dXs were produced by matcha_forward; only the per-half-tile parameter-gradient partials remain to be summed
     // (fused_fwd32.hip).  Small batches: one launch, which also zeroes the buffer the backward kernel's heads add their d x_hat into
@@ -802,7 +813,8 @@ static int backward_impl(const matcha_shape* shp, const matcha_tensors* params, 
     const bool dx_atomic = !opts->deterministic && !opts->sparse_table_grad;
     MATCHA_CHECK_ARG(!node || dx_atomic, "matcha_backward: deterministic / sparse_table_grad differ from the forward's on this workspace");
     MATCHA_TRY(launch_fused_bwd_merged(p, w.folded, w.merged, node ? w.XN : w.X, w.ddyn0, w.dXs, w.rg, B, L, w.dO, w.fb_ws, g_, front ? nullptr : w.dZ0, st, w.qkv, dx_atomic, dx_zeroed,
-                                       tail_in_bwd ? &tail_args : nullptr, node ? w.rg.tok_key : nullptr, node ? w.xhN : nullptr));
+                                       tail_in_bwd ? &tail_args : nullptr, node ? w.rg.tok_key : nullptr, node ? w.xhN : nullptr,
+                                       node_r ? w.RN : nullptr, (int64_t)s.n_nodes + 1));
     MATCHA_TRY(encoder_done(*opts, st));
     if (front) {
       // LayerNorm backward of the summed partials + next_w + attribute_nn backward + embedding scatter in one kernel
