@@ -577,6 +577,43 @@ int matcha_topk_update(void* state, size_t bytes, int32_t K, int64_t max_chunk, 
 int matcha_topk_read(const void* state, size_t bytes, int32_t K, int64_t max_chunk, float* scores_out, int64_t* ranks_out,
                      int64_t* n_out, matcha_stream_t stream);
 
+/* ---- anchored k-way sweep ------------------------------------------------------------------------------
+ * The best K completions of every anchor.  An anchor row is s fixed node ids (1 <= s <= k - 1); the free part is a candidate of
+ * size f = k - s of the partner region [lo, lo + n) under the rule above (f = 1: every node, C_f = n; otherwise
+ * C_f = C(n - (f - 1)(min_gap - 1), f)), ranked lexicographically from 0.  With A anchor rows the global rank is g = a C_f + r
+ * (anchor index a, free rank r), 0 <= g < A C_f < 2^63.  The candidate is the k ids sorted ascending (duplicates kept), zero-padded
+ * to L; it is valid iff every adjacent difference is >= min_gap.  Invalid candidates keep their rank and their row; a flag marks them.
+ * matcha_kway_anchor_count  host only: A C_f, or -1 for invalid arguments (A < 0, n < 1, k outside [2, 8], s outside [1, k - 1],
+ *     min_gap < 1) or a total >= 2^63.
+ * matcha_kway_anchor_rows   anchors device int64 [A, s]; writes x, device int64 [count, L] with k <= L <= 8, and flag, device int32
+ *     [count] (non-zero = invalid; the layout matcha_hashset_contains writes, so the two can be OR-ed): row i is the candidate of
+ *     global rank rank0 + i (ranks == NULL; the range must lie inside [0, A C_f), else refused) or ranks[i] (device int64 [count];
+ *     a rank outside [0, A C_f) gives an all-zero row with its flag set).  One 64-bit division per row; count = 0 launches nothing.
+ *
+ * Segmented streaming selection: for each of A segments of seg_len consecutive global ranks, the best K (score, rank) pairs under
+ * exactly the order of matcha_topk_* (NaN scores and skipped rows never kept, the stored score keeps its bits).  The state covers
+ * the segments seg0 .. seg0 + A - 1, i.e. the ranks [seg0 seg_len, (seg0 + A) seg_len); the segment of a row is rank / seg_len.
+ * A chunk may begin and end inside a segment and cover a fraction of one or thousands of them.  No atomics: the state after any
+ * sequence of updates depends only on the pairs seen; segments a chunk does not touch are neither read nor written.
+ * matcha_segtopk_bytes   bytes of one state (1 <= K, 1 <= A, A K < 2^31, seg_len >= 1, 1 <= max_chunk < 2^31); 0 when out of range.
+ *     Sized without asking the device.  A, K, seg_len and max_chunk are passed again to the other three calls.
+ * matcha_segtopk_init    empties every segment (a kernel, no memset).
+ * matcha_segtopk_update  scores device float32 [n], row i has global rank g0 + i; skip optional device int32 [n]; 0 <= n <=
+ *     max_chunk, n = 0 is a no-op that launches nothing; a range outside the state's segments is refused.
+ * matcha_segtopk_read    scores_out device float32 [A, K], ranks_out device int64 [A, K] (global ranks), each segment sorted in the
+ *     order above; counts_out device int64 [A]: the valid pairs of each segment (entries beyond are score 0, rank -1).
+ * All refuse, before any device call: a null pointer, an argument out of range, a state smaller than matcha_segtopk_bytes. */
+int64_t matcha_kway_anchor_count(int64_t A, int32_t s, int32_t n, int32_t k, int32_t min_gap);
+int matcha_kway_anchor_rows(const int64_t* anchors, int64_t A, int32_t s, int64_t lo, int32_t n, int32_t k, int32_t min_gap,
+                            int64_t rank0, const int64_t* ranks, int64_t count, int32_t L, int64_t* x, int32_t* flag,
+                            matcha_stream_t stream);
+size_t matcha_segtopk_bytes(int64_t A, int32_t K, int64_t seg_len, int64_t max_chunk);
+int matcha_segtopk_init(void* state, size_t bytes, int64_t A, int32_t K, int64_t seg_len, int64_t max_chunk, matcha_stream_t stream);
+int matcha_segtopk_update(void* state, size_t bytes, int64_t A, int32_t K, int64_t seg_len, int64_t max_chunk, int64_t seg0,
+                          const float* scores, const int32_t* skip, int64_t n, int64_t g0, matcha_stream_t stream);
+int matcha_segtopk_read(const void* state, size_t bytes, int64_t A, int32_t K, int64_t seg_len, int64_t max_chunk, float* scores_out,
+                        int64_t* ranks_out, int64_t* counts_out, matcha_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -128,6 +128,12 @@ SIGNATURES = {
     "matcha_topk_init": (C.c_int, [_fp, _SZ, _I32, _I64, _fp]),
     "matcha_topk_update": (C.c_int, [_fp, _SZ, _I32, _I64, _fp, _fp, _I64, _I64, _fp]),
     "matcha_topk_read": (C.c_int, [_fp, _SZ, _I32, _I64, _fp, _fp, _fp, _fp]),
+    "matcha_kway_anchor_count": (_I64, [_I64, _I32, _I32, _I32, _I32]),
+    "matcha_kway_anchor_rows": (C.c_int, [_fp, _I64, _I32, _I64, _I32, _I32, _I32, _I64, _fp, _I64, _I32, _fp, _fp, _fp]),
+    "matcha_segtopk_bytes": (_SZ, [_I64, _I32, _I64, _I64]),
+    "matcha_segtopk_init": (C.c_int, [_fp, _SZ, _I64, _I32, _I64, _I64, _fp]),
+    "matcha_segtopk_update": (C.c_int, [_fp, _SZ, _I64, _I32, _I64, _I64, _I64, _fp, _fp, _I64, _I64, _fp]),
+    "matcha_segtopk_read": (C.c_int, [_fp, _SZ, _I64, _I32, _I64, _I64, _fp, _fp, _fp, _fp]),
 }
 
 OBJECTIVE_BCE, OBJECTIVE_SOFTPLUS_MSE = 0, 1      # MATCHA_OBJECTIVE_* of include/matcha_hip.h

@@ -383,3 +383,356 @@ extern "C" int matcha_topk_read(const void* state, size_t bytes, int32_t K, int6
   MATCHA_CHECK_LAUNCH("topk_read_kernel");
   return MATCHA_OK;
 }
+
+// ==== anchored sweep ================================================================================================
+// The best K completions of every anchor.  An anchor row holds s fixed node ids (1 <= s <= k - 1); the free part is a candidate of
+// size f = k - s of the partner region [lo, lo + n) under the rule above (f = 1: every node of the region, C_f = n).  With A anchor
+// rows the global rank is g = a C_f + r: anchor index a, free rank r.  The row is the k ids sorted ascending (duplicates kept); it is
+// valid iff every adjacent difference is >= min_gap, which rejects a free node on or near an anchor and every row of an anchor that
+// breaks the rule itself.  Invalid rows keep their place in the rank space and hold real node ids; a flag marks them.
+//
+//   kway_anchor_rows_kernel  one thread per row: g / C_f once per row (32-bit when both fit), unrank() of the free rank, the anchor's
+//                            ids read from the device table, a 19-exchange sorting network over 8 registers (pads = INT64_MAX), the
+//                            gap test on unsigned differences.  Rows leave through LDS as in kway_rows_kernel, flags directly.
+//
+// Segmented selection: one top-K per segment of seg_len consecutive global ranks (the anchored sweep: seg_len = C_f, segment = anchor),
+// under exactly the order of the plain selection.  A chunk may cover a fraction of one segment or thousands of them.
+//
+//   segtopk_init_kernel    sentinels into all A K slots.
+//   segtopk_keys_kernel    64-bit key = (segment index within the chunk) << 32 | score key; value = the row's index in the chunk.
+//   rocPRIM radix sort of (key, index) over the bits in use: stable, every row stays in its segment's group (sentinel rows last), so
+//                          the sorted run of chunk segment t begins at max(0, t seg_len - off0), known by arithmetic.
+//   segtopk_merge_kernel   one thread per (touched segment, position p < K): the merge path of topk_merge_kernel between the segment's
+//                          state and the best min(K, run length) rows of its run.
+//   segtopk_commit_kernel  copies the merged rows of the touched segments (a contiguous range of the state) back.
+//   segtopk_read_kernel    scores, ranks and per-segment counts.
+//
+// No atomics; segments a chunk does not touch are neither read nor written.
+namespace matcha {
+namespace {
+
+bool anchor_args_ok(int64_t A, int32_t s, int32_t n, int32_t k, int32_t min_gap) {
+  return A >= 0 && n >= 1 && k >= 2 && k <= kMaxK && s >= 1 && s <= k - 1 && min_gap >= 1;
+}
+
+// C_f = C(n - (f - 1)(min_gap - 1), f) for f >= 1 (f = 1: n), -1 when it does not fit 63 bits
+int64_t free_count(int32_t n, int32_t f, int32_t min_gap) {
+  return count_subsets((int64_t)n - (int64_t)(f - 1) * (min_gap - 1), f);
+}
+
+// A C_f, -1 for invalid arguments or a total >= 2^63; *cf_out = C_f
+int64_t anchor_count(int64_t A, int32_t s, int32_t n, int32_t k, int32_t min_gap, int64_t* cf_out) {
+  if (!anchor_args_ok(A, s, n, k, min_gap)) return -1;
+  const int64_t cf = free_count(n, k - s, min_gap);
+  if (cf < 0) return -1;
+  const unsigned __int128 total = (unsigned __int128)(uint64_t)A * (uint64_t)cf;
+  if (total >= ((unsigned __int128)1 << 63)) return -1;
+  if (cf_out) *cf_out = cf;
+  return (int64_t)total;
+}
+
+__device__ __forceinline__ void order2(int64_t& a, int64_t& b) {
+  const int64_t lo = a < b ? a : b, hi = a < b ? b : a;
+  a = lo;
+  b = hi;
+}
+
+__global__ __launch_bounds__(kRowsPerBlock) void kway_anchor_rows_kernel(const int64_t* __restrict__ anchors, int32_t s, int64_t lo, int32_t m, int32_t f,
+                                                                         int32_t slack, int32_t min_gap, uint64_t cf, uint64_t total, int64_t rank0,
+                                                                         const int64_t* __restrict__ ranks, int64_t count, int32_t L,
+                                                                         int64_t* __restrict__ x, int32_t* __restrict__ flag) {
+  __shared__ int64_t tile[kRowsPerBlock * kMaxK];
+  const int k = s + f;
+  for (int64_t base = (int64_t)blockIdx.x * kRowsPerBlock; base < count; base += (int64_t)gridDim.x * kRowsPerBlock) {
+    const int64_t i = base + threadIdx.x;
+    if (i < count) {
+      const int64_t g = ranks ? ranks[i] : rank0 + i;
+      const bool ok = g >= 0 && (uint64_t)g < total;                   // total > 0 here, so cf > 0
+      int64_t v[kMaxK] = {0, 0, 0, 0, 0, 0, 0, 0};
+      bool bad = !ok;
+      if (ok) {
+        uint64_t a, r;
+        if (((uint64_t)g | cf) >> 32) {                                // the one 64-bit division of the row
+          a = (uint64_t)g / cf;
+          r = (uint64_t)g - a * cf;
+        } else {
+          const uint32_t a32 = (uint32_t)g / (uint32_t)cf;
+          a = a32;
+          r = (uint32_t)g - a32 * (uint32_t)cf;
+        }
+        int32_t y[kMaxK] = {0, 0, 0, 0, 0, 0, 0, 0};
+        unrank(r, cf, m, f, y);
+        const int64_t* __restrict__ arow = anchors + a * (uint64_t)s;
+#pragma unroll
+        for (int c = 0; c < kMaxK; ++c) {
+          if (c < f) v[c] = lo + (int64_t)y[c] + (int64_t)c * slack;
+          else if (c < k) v[c] = arow[c - f];
+          else v[c] = INT64_MAX;
+        }
+        order2(v[0], v[2]); order2(v[1], v[3]); order2(v[4], v[6]); order2(v[5], v[7]);
+        order2(v[0], v[4]); order2(v[1], v[5]); order2(v[2], v[6]); order2(v[3], v[7]);
+        order2(v[0], v[1]); order2(v[2], v[3]); order2(v[4], v[5]); order2(v[6], v[7]);
+        order2(v[2], v[4]); order2(v[3], v[5]);
+        order2(v[1], v[4]); order2(v[3], v[6]);
+        order2(v[1], v[2]); order2(v[3], v[4]); order2(v[5], v[6]);
+#pragma unroll
+        for (int c = 1; c < kMaxK; ++c)                                // sorted, so the unsigned difference is exact for any int64 ids
+          if (c < k) bad |= (uint64_t)v[c] - (uint64_t)v[c - 1] < (uint64_t)min_gap;
+      }
+#pragma unroll
+      for (int c = 0; c < kMaxK; ++c)
+        if (c < L) tile[threadIdx.x * L + c] = (ok && c < k) ? v[c] : 0;
+      flag[i] = bad ? 1 : 0;
+    }
+    __syncthreads();
+    const int64_t rows = count - base < kRowsPerBlock ? count - base : kRowsPerBlock;
+    const int elems = (int)rows * L;
+    for (int e = threadIdx.x; e < elems; e += kRowsPerBlock) x[base * L + e] = tile[e];
+    __syncthreads();                                                   // the tile is reused by the next run of rows
+  }
+}
+
+// ---- segmented selection ---------------------------------------------------------------------------------------------------------
+struct SegPlan {
+  size_t off_key, off_score, off_rank;        // the state: A segments of K sorted pairs
+  size_t off_tkey, off_tscore, off_trank;     // the merged rows of the touched segments before they are committed
+  size_t off_ckey, off_cidx, off_skey, off_sidx, off_sort, sort_bytes, total;
+  int64_t tmax;                               // the most segments one update can touch
+};
+
+bool seg_args_ok(int64_t A, int64_t K, int64_t seg_len, int64_t max_chunk) {
+  const int64_t lim = ((int64_t)1 << 31) - 1;
+  return K >= 1 && K <= lim && A >= 1 && A <= lim / K && seg_len >= 1 && max_chunk >= 1 && max_chunk <= lim;
+}
+
+// As make_tplan: the sort's scratch is a bound (64-bit keys and 32-bit values twice over plus histograms), checked in the update.
+SegPlan make_splan(int64_t A, int64_t K, int64_t seg_len, int64_t max_chunk) {
+  SegPlan pl;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
+  const int64_t by_chunk = (max_chunk - 1) / seg_len + 2;              // off0 < seg_len: (off0 + n - 1) / seg_len + 1 <= (n - 2) / seg_len + 2
+  pl.tmax = A < by_chunk ? A : by_chunk;
+  const size_t slots = (size_t)A * (size_t)K, tslots = (size_t)pl.tmax * (size_t)K;
+  pl.off_key = take(slots * 4);
+  pl.off_score = take(slots * 4);
+  pl.off_rank = take(slots * 8);
+  pl.off_tkey = take(tslots * 4);
+  pl.off_tscore = take(tslots * 4);
+  pl.off_trank = take(tslots * 8);
+  pl.off_ckey = take((size_t)max_chunk * 8);
+  pl.off_cidx = take((size_t)max_chunk * 4);
+  pl.off_skey = take((size_t)max_chunk * 8);
+  pl.off_sidx = take((size_t)max_chunk * 4);
+  pl.sort_bytes = (size_t)max_chunk * 24 + ((size_t)4 << 20);
+  pl.off_sort = take(pl.sort_bytes);
+  pl.total = off;
+  return pl;
+}
+
+__global__ __launch_bounds__(256) void segtopk_init_kernel(TopkState st, int64_t slots) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= slots) return;
+  st.key[p] = kSentinel;
+  st.score[p] = 0.f;
+  st.rank[p] = -1;
+}
+
+// off0 = (rank of row 0) mod seg_len.  wide (seg_len >= 2^31 > n): a chunk touches at most two segments, one comparison; otherwise
+// off0 + i < 2^32 and the division is a 32-bit one.
+__global__ __launch_bounds__(256) void segtopk_keys_kernel(const float* __restrict__ scores, const int32_t* __restrict__ skip, int64_t n, uint64_t off0,
+                                                           uint64_t seg_len, int wide, uint64_t* __restrict__ key, uint32_t* __restrict__ idx) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const bool skipped = skip && skip[i] != 0;
+  const uint32_t k32 = skipped ? kSentinel : score_key(scores[i]);
+  const uint32_t t = wide ? (uint32_t)(off0 + (uint64_t)i >= seg_len) : (uint32_t)(off0 + (uint64_t)i) / (uint32_t)seg_len;
+  key[i] = ((uint64_t)t << 32) | k32;
+  idx[i] = (uint32_t)i;
+}
+
+// thread (t, p): chunk segment t is state segment seg_first + t; its sorted run is [start, end) of the sorted chunk
+__global__ __launch_bounds__(256) void segtopk_merge_kernel(TopkState st, uint32_t K, int64_t T, int64_t seg_first, uint64_t off0, uint64_t seg_len, int64_t n,
+                                                            const uint64_t* __restrict__ skey, const uint32_t* __restrict__ sidx,
+                                                            const float* __restrict__ scores, int64_t g0, TopkState out) {
+  const int64_t flat = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (flat >= T * (int64_t)K) return;                                  // T K < 2^31
+  const uint32_t t = (uint32_t)flat / K;
+  const int64_t p = (int64_t)((uint32_t)flat - t * K);
+  // t >= 1 only when seg_len <= off0 + n - 1 < 2^32, so the products below cannot overflow
+  const int64_t start = t == 0 ? 0 : (int64_t)((uint64_t)t * seg_len - off0);
+  const uint64_t room = ((uint64_t)t + 1) * seg_len - off0;            // rows of the chunk before the next segment begins
+  const int64_t end = room < (uint64_t)n ? (int64_t)room : n;
+  const int64_t len = end - start;
+  const int64_t nb = len < (int64_t)K ? len : (int64_t)K;
+  const int64_t sbase = (seg_first + (int64_t)t) * (int64_t)K;
+  const uint32_t* __restrict__ akey = st.key + sbase;
+  const int64_t* __restrict__ arank = st.rank + sbase;
+  const uint64_t* __restrict__ bkey = skey + start;
+  const uint32_t* __restrict__ bidx = sidx + start;
+  int64_t lo = p > nb ? p - nb : 0, hi = p;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    const int64_t jb = p - 1 - mid;                                    // in [0, nb)
+    if (state_first(akey[mid], arank[mid], (uint32_t)bkey[jb], g0 + (int64_t)bidx[jb])) lo = mid + 1;
+    else hi = mid;
+  }
+  const int64_t ia = lo, ib = p - lo;
+  bool from_a = true;
+  if (ib < nb) from_a = state_first(akey[ia], arank[ia], (uint32_t)bkey[ib], g0 + (int64_t)bidx[ib]);
+  uint32_t key;
+  float score;
+  int64_t rank;
+  if (from_a) {
+    key = akey[ia]; score = st.score[sbase + ia]; rank = arank[ia];
+  } else {
+    key = (uint32_t)bkey[ib]; score = scores[bidx[ib]]; rank = g0 + (int64_t)bidx[ib];
+  }
+  if (key == kSentinel) { score = 0.f; rank = -1; }
+  out.key[flat] = key;
+  out.score[flat] = score;
+  out.rank[flat] = rank;
+}
+
+__global__ __launch_bounds__(256) void segtopk_commit_kernel(TopkState from, TopkState to, int64_t to_base, int64_t slots) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= slots) return;
+  to.key[to_base + p] = from.key[p];
+  to.score[to_base + p] = from.score[p];
+  to.rank[to_base + p] = from.rank[p];
+}
+
+__global__ __launch_bounds__(256) void segtopk_read_kernel(TopkState st, uint32_t K, int64_t slots, float* __restrict__ scores_out,
+                                                           int64_t* __restrict__ ranks_out, int64_t* __restrict__ counts_out) {
+  const int64_t flat = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (flat >= slots) return;
+  const uint32_t a = (uint32_t)flat / K, p = (uint32_t)flat - a * K;
+  const bool valid = st.key[flat] != kSentinel;
+  scores_out[flat] = st.score[flat];
+  ranks_out[flat] = st.rank[flat];
+  // the valid pairs of a segment are a prefix: its end has exactly one owner
+  if (valid && (p == K - 1 || st.key[flat + 1] == kSentinel)) counts_out[a] = (int64_t)p + 1;
+  if (!valid && p == 0) counts_out[a] = 0;
+}
+
+}  // namespace
+}  // namespace matcha
+
+extern "C" int64_t matcha_kway_anchor_count(int64_t A, int32_t s, int32_t n, int32_t k, int32_t min_gap) {
+  return anchor_count(A, s, n, k, min_gap, nullptr);
+}
+
+extern "C" int matcha_kway_anchor_rows(const int64_t* anchors, int64_t A, int32_t s, int64_t lo, int32_t n, int32_t k, int32_t min_gap, int64_t rank0,
+                                       const int64_t* ranks, int64_t count, int32_t L, int64_t* x, int32_t* flag, matcha_stream_t stream) {
+  MATCHA_CHECK_ARG(anchor_args_ok(A, s, n, k, min_gap),
+                   "matcha_kway_anchor_rows: need A >= 0, n >= 1, 2 <= k <= %d, 1 <= s <= k - 1, min_gap >= 1 (A=%lld s=%d n=%d k=%d min_gap=%d)", kMaxK,
+                   (long long)A, s, n, k, min_gap);
+  MATCHA_CHECK_ARG(L >= k && L <= kMaxK, "matcha_kway_anchor_rows: row width L=%d must be in [k, %d]", L, kMaxK);
+  MATCHA_CHECK_ARG(lo >= 0 && lo <= ((int64_t)1 << 62), "matcha_kway_anchor_rows: lo out of range");
+  int64_t cf = 0;
+  const int64_t total = anchor_count(A, s, n, k, min_gap, &cf);
+  MATCHA_CHECK_ARG(total >= 0, "matcha_kway_anchor_rows: A C_f does not fit 63 bits (A=%lld s=%d n=%d k=%d min_gap=%d)", (long long)A, s, n, k, min_gap);
+  MATCHA_CHECK_ARG(count >= 0 && count <= ((int64_t)1 << 40), "matcha_kway_anchor_rows: count out of range");
+  if (!ranks)
+    MATCHA_CHECK_ARG(rank0 >= 0 && rank0 <= total && count <= total - rank0,
+                     "matcha_kway_anchor_rows: ranks [%lld, %lld) outside [0, %lld)", (long long)rank0, (long long)(rank0 + count), (long long)total);
+  if (count == 0) return MATCHA_OK;
+  MATCHA_CHECK_ARG(x && flag, "matcha_kway_anchor_rows: null output");
+  MATCHA_CHECK_ARG(anchors || total == 0, "matcha_kway_anchor_rows: null anchors");
+  const int32_t f = k - s, slack = min_gap - 1;
+  const int64_t m64 = (int64_t)n - (int64_t)(f - 1) * slack;
+  const int32_t m = m64 > 0 ? (int32_t)m64 : 0;
+  int64_t blocks = cdiv(count, kRowsPerBlock);
+  if (blocks > (1 << 20)) blocks = 1 << 20;
+  hipLaunchKernelGGL(kway_anchor_rows_kernel, dim3((unsigned)blocks), dim3(kRowsPerBlock), 0, (hipStream_t)stream, anchors, s, lo, m, f, slack, min_gap,
+                     (uint64_t)cf, (uint64_t)total, rank0, ranks, count, L, x, flag);
+  MATCHA_CHECK_LAUNCH("kway_anchor_rows_kernel");
+  return MATCHA_OK;
+}
+
+extern "C" size_t matcha_segtopk_bytes(int64_t A, int32_t K, int64_t seg_len, int64_t max_chunk) {
+  if (!seg_args_ok(A, K, seg_len, max_chunk)) return 0;
+  return make_splan(A, K, seg_len, max_chunk).total;
+}
+
+#define SEGTOPK_COMMON_ARGS(fn)                                                                                                       \
+  MATCHA_CHECK_ARG(state, fn ": null state");                                                                                         \
+  MATCHA_CHECK_ARG(seg_args_ok(A, K, seg_len, max_chunk),                                                                             \
+                   fn ": need 1 <= K, 1 <= A, A K < 2^31, seg_len >= 1 and 1 <= max_chunk < 2^31 (A=%lld K=%d seg_len=%lld max_chunk=%lld)",   \
+                   (long long)A, K, (long long)seg_len, (long long)max_chunk);                                                       \
+  MATCHA_CHECK_ARG(((uintptr_t)state) % 8 == 0, fn ": state must be 8-byte aligned");                                                 \
+  const SegPlan pl = make_splan(A, K, seg_len, max_chunk);                                                                            \
+  MATCHA_CHECK_ARG(bytes >= pl.total, fn ": state too small (%zu bytes, matcha_segtopk_bytes says %zu)", bytes, pl.total)
+
+extern "C" int matcha_segtopk_init(void* state, size_t bytes, int64_t A, int32_t K, int64_t seg_len, int64_t max_chunk, matcha_stream_t stream) {
+  SEGTOPK_COMMON_ARGS("matcha_segtopk_init");
+  const int64_t slots = A * K;
+  hipLaunchKernelGGL(segtopk_init_kernel, dim3((unsigned)cdiv(slots, 256)), dim3(256), 0, (hipStream_t)stream,
+                     state_at(state, pl.off_key, pl.off_score, pl.off_rank), slots);
+  MATCHA_CHECK_LAUNCH("segtopk_init_kernel");
+  return MATCHA_OK;
+}
+
+extern "C" int matcha_segtopk_update(void* state, size_t bytes, int64_t A, int32_t K, int64_t seg_len, int64_t max_chunk, int64_t seg0, const float* scores,
+                                     const int32_t* skip, int64_t n, int64_t g0, matcha_stream_t stream) {
+  SEGTOPK_COMMON_ARGS("matcha_segtopk_update");
+  MATCHA_CHECK_ARG(n >= 0 && n <= max_chunk, "matcha_segtopk_update: n=%lld outside [0, max_chunk=%lld]", (long long)n, (long long)max_chunk);
+  MATCHA_CHECK_ARG(g0 >= 0 && g0 <= INT64_MAX - n && seg0 >= 0, "matcha_segtopk_update: g0 or seg0 out of range");
+  {
+    const __int128 first = (__int128)seg0 * seg_len, past = ((__int128)seg0 + A) * seg_len;
+    MATCHA_CHECK_ARG((__int128)g0 >= first && (__int128)g0 + n <= past,
+                     "matcha_segtopk_update: ranks [%lld, %lld) outside the %lld segments of %lld ranks from segment %lld", (long long)g0,
+                     (long long)(g0 + n), (long long)A, (long long)seg_len, (long long)seg0);
+  }
+  if (n == 0) return MATCHA_OK;
+  MATCHA_CHECK_ARG(scores, "matcha_segtopk_update: null scores");
+  const int64_t seg_first = g0 / seg_len - seg0;                       // in [0, A)
+  const uint64_t off0 = (uint64_t)(g0 % seg_len);
+  const int64_t T = (int64_t)((off0 + (uint64_t)n - 1) / (uint64_t)seg_len) + 1;   // touched segments, <= pl.tmax
+  if (T > pl.tmax || seg_first + T > A) {
+    set_error("matcha_segtopk_update: %lld touched segments, room for %lld", (long long)T, (long long)pl.tmax);
+    return MATCHA_EINVAL;
+  }
+  int bits = 0;
+  while (((int64_t)1 << bits) < T) ++bits;
+  const unsigned end_bit = 32u + (unsigned)bits;
+  hipStream_t st = (hipStream_t)stream;
+  char* w = (char*)state;
+  uint64_t* ckey = (uint64_t*)(w + pl.off_ckey);
+  uint32_t* cidx = (uint32_t*)(w + pl.off_cidx);
+  uint64_t* skey = (uint64_t*)(w + pl.off_skey);
+  uint32_t* sidx = (uint32_t*)(w + pl.off_sidx);
+  size_t need = 0;
+  if (rocprim::radix_sort_pairs(nullptr, need, ckey, skey, cidx, sidx, (size_t)n, 0, end_bit, st) != hipSuccess || need > pl.sort_bytes) {
+    set_error("matcha_segtopk_update: the radix sort asks for %zu bytes of scratch, %zu are reserved", need, pl.sort_bytes);
+    return MATCHA_EHIP;
+  }
+  const int wide = seg_len >= ((int64_t)1 << 31);
+  hipLaunchKernelGGL(segtopk_keys_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, scores, skip, n, off0, (uint64_t)seg_len, wide, ckey, cidx);
+  MATCHA_CHECK_LAUNCH("segtopk_keys_kernel");
+  size_t tb = pl.sort_bytes;
+  if (rocprim::radix_sort_pairs(w + pl.off_sort, tb, ckey, skey, cidx, sidx, (size_t)n, 0, end_bit, st) != hipSuccess) {
+    set_error("matcha_segtopk_update: radix sort failed");
+    return MATCHA_EHIP;
+  }
+  const TopkState cur = state_at(state, pl.off_key, pl.off_score, pl.off_rank);
+  const TopkState tmp = state_at(state, pl.off_tkey, pl.off_tscore, pl.off_trank);
+  const int64_t slots = T * K;
+  const unsigned blocks = (unsigned)cdiv(slots, 256);
+  hipLaunchKernelGGL(segtopk_merge_kernel, dim3(blocks), dim3(256), 0, st, cur, (uint32_t)K, T, seg_first, off0, (uint64_t)seg_len, n, skey, sidx, scores, g0,
+                     tmp);
+  MATCHA_CHECK_LAUNCH("segtopk_merge_kernel");
+  hipLaunchKernelGGL(segtopk_commit_kernel, dim3(blocks), dim3(256), 0, st, tmp, cur, seg_first * K, slots);
+  MATCHA_CHECK_LAUNCH("segtopk_commit_kernel");
+  return MATCHA_OK;
+}
+
+extern "C" int matcha_segtopk_read(const void* state, size_t bytes, int64_t A, int32_t K, int64_t seg_len, int64_t max_chunk, float* scores_out,
+                                   int64_t* ranks_out, int64_t* counts_out, matcha_stream_t stream) {
+  SEGTOPK_COMMON_ARGS("matcha_segtopk_read");
+  MATCHA_CHECK_ARG(scores_out && ranks_out && counts_out, "matcha_segtopk_read: null output");
+  const int64_t slots = A * K;
+  hipLaunchKernelGGL(segtopk_read_kernel, dim3((unsigned)cdiv(slots, 256)), dim3(256), 0, (hipStream_t)stream,
+                     state_at((void*)state, pl.off_key, pl.off_score, pl.off_rank), (uint32_t)K, slots, scores_out, ranks_out, counts_out);
+  MATCHA_CHECK_LAUNCH("segtopk_read_kernel");
+  return MATCHA_OK;
+}

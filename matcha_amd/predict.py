@@ -13,10 +13,13 @@
 CLI:  python -m matcha_amd.predict multiway -i interactions.txt -o output.txt
       python -m matcha_amd.predict pairwise --chrom 0 -o chr1_proba.npy
       python -m matcha_amd.predict kway --chrom 0 --k 3 --top 1000 [--start-bin A --end-bin B] [--exclude-known] -o top.tsv
+      python -m matcha_amd.predict anchored --k 3 --top 20 --chrom 5 (--anchor-file loci.tsv | --anchor-chrom 0) -o anchored.tsv
 (all read ./config.JSON like the reference: temp_dir, resolution, chrom_list, min_distance).
 
 * ``kway`` -- the de novo sweep of matcha_amd/sweep.py: every candidate of size k in one chromosome (or a window of its bins)
   with adjacent gaps > min_distance, scored on the device, the best ``--top`` written as ``chrom:start`` items and a probability.
+* ``anchored`` -- the anchored sweep of matcha_amd/sweep.py: for every anchor (a line of ``--anchor-file``, or every bin of
+  ``--anchor-chrom``) the best ``--top`` candidates of size k that contain it, the other nodes taken from ``--chrom``.
 """
 from __future__ import annotations
 
@@ -181,6 +184,73 @@ def _kway(args, config, temp_dir, model):
     print("%d candidates (%d known, skipped) -> %d in %s" % (out["n_candidates"], out["n_excluded"], len(rows), args.output))
 
 
+def parse_anchor_file(filepath: str, bin2node: Dict[str, int], chrom_list: Sequence[str], res: int) -> np.ndarray:
+    """int64 [A, s]: one anchor row per non-empty line, s tab-separated ``chrom:position`` loci with parse_file's coordinate
+    handling (positions floored to their bin, an item without ``:`` raises EOFError, an unknown bin KeyError), each row sorted.
+    Unlike parse_file nothing is dropped: a locus of an unknown chromosome, a repeated locus or lines of different lengths raise
+    ValueError, because every line is one anchor and all anchors share s."""
+    rows = []
+    with open(filepath, "r") as f:
+        for line in f:
+            if not line.strip():
+                continue
+            temp = []
+            for info in line.strip().split("\t"):
+                try:
+                    chrom, bin_ = info.split(":")
+                except ValueError:
+                    raise EOFError(info)
+                if chrom not in chrom_list:
+                    raise ValueError("anchor locus %s: chromosome not in chrom_list" % info)
+                b = int(math.floor(int(bin_) / res)) * res
+                temp.append(bin2node["%s:%d" % (chrom, b)])
+            if len(set(temp)) != len(temp):
+                raise ValueError("anchor line %r repeats a bin" % line.strip())
+            rows.append(sorted(temp))
+    if len(set(len(r) for r in rows)) > 1:
+        raise ValueError("all anchor lines must have the same number of loci")
+    return np.asarray(rows, dtype=np.int64).reshape(len(rows), len(rows[0]) if rows else 1)
+
+
+def _anchored(args, config, temp_dir, model):
+    from . import sweep as SW
+    from .sampler import HyperedgeSet
+    chrom_range = np.load(os.path.join(temp_dir, "chrom_range.npy"))
+    node2bin = np.load(os.path.join(temp_dir, "node2bin.npy"), allow_pickle=True).item()
+
+    def window(chrom, start_bin, end_bin):
+        c_lo, c_hi = int(chrom_range[chrom][0]), int(chrom_range[chrom][1])
+        lo = c_lo + (start_bin if start_bin is not None else 0)
+        hi = c_lo + end_bin if end_bin is not None else c_hi
+        if not c_lo <= lo <= hi <= c_hi:
+            raise ValueError("the bin window [%s, %s) is not inside chromosome %d (%d bins)" % (start_bin, end_bin, chrom, c_hi - c_lo))
+        return lo, hi
+
+    lo, hi = window(args.chrom, args.start_bin, args.end_bin)
+    if args.anchor_file is not None:
+        bin2node = {v: key for key, v in node2bin.items()}
+        anchors = parse_anchor_file(args.anchor_file, bin2node, config["chrom_list"], config["resolution"])
+    else:
+        a_lo, a_hi = window(args.anchor_chrom, args.anchor_start_bin, args.anchor_end_bin)
+        anchors = np.arange(a_lo, a_hi, dtype=np.int64).reshape(-1, 1)
+    dev = model.layer_norm1.weight.device
+    exclude = None
+    if args.exclude_known:
+        known = np.load(os.path.join(temp_dir, "all_%d_counter.npy" % args.k)).astype(np.int64).reshape(-1, args.k)
+        exclude = HyperedgeSet(torch.from_numpy(known).to(dev))
+    out = SW.anchored_sweep(model, anchors, lo, hi, args.k, int(config["min_distance"]) + 1, args.top, chunk_rows=args.chunk_rows,
+                            width=args.width, exclude=exclude, task_mode=args.task_mode)
+    rows, proba, count = out["rows"].cpu().numpy(), out["proba"].cpu().numpy(), out["count"].cpu().numpy()
+    with open(args.output, "w") as f:
+        for a in range(len(anchors)):
+            for r, p in zip(rows[a, :count[a]], proba[a, :count[a]]):
+                f.write("\t".join([node2bin[int(v)] for v in r[:args.k]] + [repr(float(p))]) + "\n")
+    np.savez(os.path.splitext(args.output)[0] + ".npz", anchors=anchors, rows=rows, logit=out["logit"].cpu().numpy(), proba=proba,
+             rank=out["rank"].cpu().numpy(), count=count)
+    print("%d anchors, %d candidates (%d against the gap rule, %d known, skipped) -> %d in %s"
+          % (len(anchors), out["n_candidates"], out["n_invalid"], out["n_excluded"], int(count.sum()), args.output))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="inference consumers of a trained MATCHA classifier on the MI355X path")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -202,12 +272,31 @@ def main(argv=None):
     c.add_argument("--chunk-rows", type=int, default=1 << 20)
     c.add_argument("--task-mode", choices=["class", "regress"], default="class", help="the model's training objective: sigmoid or softplus outputs")
     c.add_argument("-o", "--output", type=str, default="./kway.tsv")
+    d = sub.add_parser("anchored", help="anchored sweep: for every anchor the best --top candidates of size --k that contain it")
+    d.add_argument("--chrom", type=int, required=True, help="the partner region: index into config chrom_list")
+    d.add_argument("--k", type=int, required=True, help="candidate size, 2 .. 8 (anchor loci included)")
+    d.add_argument("--top", type=int, required=True, help="how many candidates to keep per anchor")
+    src = d.add_mutually_exclusive_group(required=True)
+    src.add_argument("--anchor-file", type=str, default=None, help="one anchor per line: s tab-separated chrom:position loci, the same s on every line")
+    src.add_argument("--anchor-chrom", type=int, default=None, help="every bin of this chromosome (or of its --anchor-*-bin window) as a single anchor")
+    d.add_argument("--anchor-start-bin", type=int, default=None, help="first anchor bin, relative to --anchor-chrom (default 0)")
+    d.add_argument("--anchor-end-bin", type=int, default=None, help="one past the last anchor bin (default: the chromosome's end)")
+    d.add_argument("--start-bin", type=int, default=None, help="first bin of the partner window, relative to --chrom (default 0)")
+    d.add_argument("--end-bin", type=int, default=None, help="one past the last bin of the partner window (default: the chromosome's end)")
+    d.add_argument("--exclude-known", action="store_true", help="skip the hyperedges of temp_dir/all_<k>_counter.npy")
+    d.add_argument("--width", type=int, default=None, help="zero-pad rows to this width (default k): a logit depends on its batch's width")
+    d.add_argument("--chunk-rows", type=int, default=1 << 20)
+    d.add_argument("--task-mode", choices=["class", "regress"], default="class", help="the model's training objective: sigmoid or softplus outputs")
+    d.add_argument("-o", "--output", type=str, default="./anchored.tsv")
+    d.add_argument("--config", type=str, default="./config.JSON")
     for q in (a, b, c):
         q.add_argument("--config", type=str, default="./config.JSON")
     args = ap.parse_args(argv)
     config, temp_dir, model = _load(args.config)
     if args.cmd == "kway":
         return _kway(args, config, temp_dir, model)
+    if args.cmd == "anchored":
+        return _anchored(args, config, temp_dir, model)
     if args.cmd == "multiway":
         bin2node = np.load(os.path.join(temp_dir, "bin2node.npy"), allow_pickle=True).item()
         samples, proba = predict_multiway(model, args.file, bin2node, config["chrom_list"], config["resolution"], args.output)

@@ -199,3 +199,226 @@ def kway_sweep(model, lo: int, hi: int, k: int, min_gap: int, top: int, chunk_ro
     logit, rank = sel.result()
     rows = kway_rows(lo, n, k, min_gap, ranks=rank, width=width, device=dev)
     return {"rows": rows, "logit": logit, "proba": act(logit), "rank": rank, "n_candidates": total, "n_excluded": int(n_exc.item())}
+
+
+# ---- anchored sweep: the best K completions of every anchor -------------------------------------------------------
+def _check_anchor_args(A: int, s: int, n: int, k: int, min_gap: int):
+    if not (A >= 0 and n >= 1 and 2 <= k <= _lib.MAX_L and 1 <= s <= k - 1 and min_gap >= 1):
+        raise ValueError(f"need A >= 0, n >= 1, 2 <= k <= {_lib.MAX_L}, 1 <= s <= k - 1, min_gap >= 1 (A={A} s={s} n={n} k={k} min_gap={min_gap})")
+
+
+def _free_count(n: int, f: int, min_gap: int) -> int:
+    """C_f: the gap-constrained subsets of size f >= 1 of a region of n nodes (f = 1: n)."""
+    m = n - (f - 1) * (min_gap - 1)
+    return math.comb(m, f) if m >= f else 0
+
+
+def anchored_count(A: int, s: int, n: int, k: int, min_gap: int) -> int:
+    """Number of global ranks, A * C_f with C_f = C(n - (f - 1)(min_gap - 1), f) and f = k - s free nodes per candidate; a total
+    >= 2^63 is refused (ValueError), not truncated."""
+    A, s, n, k, min_gap = int(A), int(s), int(n), int(k), int(min_gap)
+    _check_anchor_args(A, s, n, k, min_gap)
+    total = A * _free_count(n, k - s, min_gap)
+    if total >= 1 << 63:
+        raise ValueError(f"{total} candidates (A={A} s={s} n={n} k={k} min_gap={min_gap}) do not fit 63 bits")
+    return total
+
+
+def anchored_unrank(rank: int, anchor_row, lo: int, n: int, k: int, min_gap: int) -> Tuple[Tuple[int, ...], bool]:
+    """(row, valid) of one anchor's candidate of FREE rank ``rank`` (a global rank g is anchor g // C_f, free rank g % C_f), in
+    Python integers (no GPU).  The row is the anchor's ids and the free part -- the gap-constrained subset of size k - s of
+    [lo, lo + n) of that lexicographic rank -- sorted ascending, duplicates kept; it is valid iff every adjacent difference is
+    >= min_gap."""
+    anchor_row = [int(v) for v in anchor_row]
+    s, lo, n, k, min_gap = len(anchor_row), int(lo), int(n), int(k), int(min_gap)
+    _check_anchor_args(1, s, n, k, min_gap)
+    f = k - s
+    total = _free_count(n, f, min_gap)
+    rank = int(rank)
+    if not 0 <= rank < total:
+        raise IndexError(f"rank {rank} outside [0, {total})")
+    m = n - (f - 1) * (min_gap - 1)
+    free, q, upper = [], total - 1 - rank, m - 1                         # as kway_unrank, which refuses a single free node
+    for j in range(f, 0, -1):
+        a, b = j - 1, upper
+        while a < b:
+            mid = (a + b + 1) // 2
+            if math.comb(mid, j) <= q:
+                a = mid
+            else:
+                b = mid - 1
+        q -= math.comb(a, j)
+        free.append(lo + (m - 1 - a) + (f - j) * (min_gap - 1))
+        upper = a - 1
+    row = tuple(sorted(anchor_row + free))
+    return row, all(b - a >= min_gap for a, b in zip(row, row[1:]))
+
+
+def _anchor_table(anchors, device) -> torch.Tensor:
+    """int64 [A, s] on the device; a 1-D input is A single anchors."""
+    t = torch.as_tensor(anchors)
+    if t.dim() == 1:
+        t = t.view(-1, 1)
+    if t.dim() != 2 or t.is_floating_point():
+        raise ValueError("anchors must be an integer [A, s] (or [A]) tensor or array")
+    return t.to(device=device, dtype=torch.long).contiguous()
+
+
+def anchored_rows(anchors, lo: int, n: int, k: int, min_gap: int, rank0: int = 0, count: Optional[int] = None,
+                  ranks: Optional[torch.Tensor] = None, width: Optional[int] = None, device="cuda", out: Optional[torch.Tensor] = None,
+                  flag_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(x int64 [count, width], flag int32 [count]) on the device: the candidates of the global ranks rank0 .. rank0 + count - 1, or
+    of the device list ``ranks`` (a rank outside [0, A * C_f) gives an all-zero row with its flag set); flag != 0 marks an invalid
+    candidate.  ``anchors``: int64 [A, s] (a device tensor is used as it is).  ``out`` / ``flag_out`` reuse buffers of at least
+    count * width / count elements."""
+    lib = _lib.load()
+    if isinstance(anchors, torch.Tensor) and anchors.is_cuda and ranks is None and out is None:
+        device = anchors.device
+    if ranks is not None:
+        ranks = ranks.to(device=device, dtype=torch.long).contiguous().view(-1)
+        device = ranks.device
+    elif out is not None:
+        device = out.device
+    anchors = _anchor_table(anchors, device)
+    A, s = int(anchors.shape[0]), int(anchors.shape[1])
+    total = anchored_count(A, s, n, k, min_gap)
+    width = int(k if width is None else width)
+    if not k <= width <= _lib.MAX_L:
+        raise ValueError(f"width must be in [k, {_lib.MAX_L}]")
+    if ranks is not None:
+        count = int(ranks.numel())
+    else:
+        count = total - int(rank0) if count is None else int(count)
+        if rank0 < 0 or count < 0 or rank0 + count > total:
+            raise IndexError(f"ranks [{rank0}, {rank0 + count}) outside [0, {total})")
+    if out is None:
+        x = torch.empty(count, width, dtype=torch.long, device=device)
+    else:
+        if out.dtype != torch.long or not out.is_contiguous() or out.numel() < count * width:
+            raise ValueError("out must be a contiguous int64 tensor of at least count * width elements")
+        x = out.view(-1)[:count * width].view(count, width)
+    if flag_out is None:
+        flag = torch.empty(count, dtype=torch.int32, device=device)
+    else:
+        if flag_out.dtype != torch.int32 or not flag_out.is_contiguous() or flag_out.numel() < count or flag_out.device != x.device:
+            raise ValueError("flag_out must be a contiguous int32 tensor of at least count elements on out's device")
+        flag = flag_out.view(-1)[:count]
+    if not x.is_cuda:
+        raise _lib.MatchaHipError("anchored_rows needs a cuda device (no CPU fallback)")
+    with torch.cuda.device(x.device):
+        _lib.check(lib.matcha_kway_anchor_rows(_lib.ptr(anchors), A, s, int(lo), n, k, min_gap, int(rank0), _lib.ptr(ranks), count, width,
+                                               _lib.ptr(x), _lib.ptr(flag), _stream(x.device)), "matcha_kway_anchor_rows")
+    return x, flag
+
+
+class SegTopK:
+    """One streaming top-K per segment, on the device: the state covers ``A`` segments of ``seg_len`` consecutive global ranks
+    starting at segment ``first_segment``; after any sequence of ``update`` calls segment a holds its best min(K, valid rows seen)
+    (score, global rank) pairs in TopK's order -- bit for bit the same however the rows were cut into updates.  A chunk may begin
+    and end inside a segment and cover a fraction of one or thousands of them; segments it does not touch are left alone."""
+
+    def __init__(self, A: int, K: int, seg_len: int, max_chunk: int, device="cuda", first_segment: int = 0):
+        lib = _lib.load()
+        self.A, self.K, self.seg_len, self.max_chunk, self.first_segment = int(A), int(K), int(seg_len), int(max_chunk), int(first_segment)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.MatchaHipError("SegTopK needs a cuda device (no CPU fallback)")
+        fits = 1 <= self.K < 1 << 31 and 1 <= self.A < 1 << 31 and 1 <= self.seg_len < 1 << 63 and 1 <= self.max_chunk < 1 << 31
+        self.bytes = int(lib.matcha_segtopk_bytes(self.A, self.K, self.seg_len, self.max_chunk)) if fits else 0
+        if self.bytes == 0 or not 0 <= self.first_segment < 1 << 62:
+            raise ValueError(f"SegTopK: need 1 <= K, 1 <= A, A * K < 2^31, seg_len >= 1 and 1 <= max_chunk < 2^31 "
+                             f"(A={A} K={K} seg_len={seg_len} max_chunk={max_chunk})")
+        self._dims = (self.A, self.K, self.seg_len, self.max_chunk)
+        self.state = torch.empty(self.bytes, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(lib.matcha_segtopk_init(_lib.ptr(self.state), self.bytes, *self._dims, _stream(self.device)), "matcha_segtopk_init")
+
+    def update(self, scores: torch.Tensor, g0: int, skip: Optional[torch.Tensor] = None):
+        """``scores`` float32 [n] on the device (n <= max_chunk), row i of global rank g0 + i (segment (g0 + i) // seg_len);
+        ``skip`` int32 / bool [n], non-zero = never keep.  Enqueued on the current stream; nothing is read back."""
+        lib = _lib.load()
+        scores = scores.reshape(-1)
+        if scores.dtype != torch.float32 or scores.device != self.state.device:
+            raise ValueError("scores must be a float32 tensor on the SegTopK's device")
+        scores = scores.contiguous()
+        if skip is not None:
+            skip = skip.reshape(-1).to(device=scores.device, dtype=torch.int32).contiguous()
+            if skip.numel() != scores.numel():
+                raise ValueError("skip and scores differ in length")
+        with torch.cuda.device(self.device):
+            _lib.check(lib.matcha_segtopk_update(_lib.ptr(self.state), self.bytes, *self._dims, self.first_segment, _lib.ptr(scores),
+                                                 _lib.ptr(skip), scores.numel(), int(g0), _stream(self.device)), "matcha_segtopk_update")
+
+    def read(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(scores [A, K], global ranks [A, K], counts [A]) on the device, without a synchronisation; best first within a segment,
+        entries from counts[a] on are (0, -1)."""
+        lib = _lib.load()
+        scores = torch.empty(self.A, self.K, dtype=torch.float32, device=self.device)
+        ranks = torch.empty(self.A, self.K, dtype=torch.long, device=self.device)
+        counts = torch.empty(self.A, dtype=torch.long, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(lib.matcha_segtopk_read(_lib.ptr(self.state), self.bytes, *self._dims, _lib.ptr(scores), _lib.ptr(ranks),
+                                               _lib.ptr(counts), _stream(self.device)), "matcha_segtopk_read")
+        return scores, ranks, counts
+
+
+def anchored_sweep(model, anchors, lo: int, hi: int, k: int, min_gap: int, top: int, chunk_rows: int = 1 << 20, width: Optional[int] = None,
+                   exclude=None, task_mode: str = "class") -> dict:
+    """For every anchor row (``anchors`` int64 [A, s], 1-D = single anchors, 1 <= s <= k - 1) score all its completions by a
+    gap-constrained subset of size k - s of the partner region [lo, hi) and keep the ``top`` best PER ANCHOR.  Anchors may lie inside
+    the region, outside it or on another chromosome; the gap rule is on node-id differences only.
+
+    Returns, on the model's device and best first within each anchor, with K = min(top, C_f): ``rows`` int64 [A, K, width],
+    ``logit`` and ``proba`` [A, K], ``rank`` int64 [A, K] (the FREE rank; decode with anchored_unrank(rank, anchors[a], ...)) and
+    ``count`` int64 [A]; beyond count[a] the rank is -1 and rows, logit and proba are 0.  The integers ``n_candidates`` = A * C_f,
+    ``n_invalid`` (candidates that break the rule: a free node on or too near an anchor, or an anchor row that breaks it itself;
+    they are scored but never kept) and ``n_excluded`` (valid candidates found in ``exclude``).
+
+    The loop is kway_sweep's: eval mode, no grad, the large-batch route pinned, one reused row buffer, nothing synchronises until
+    the end, where the node-id check of the whole sweep is raised once (IndexError, also for an anchor beyond the model's tables)."""
+    if task_mode not in ("class", "regress"):
+        raise ValueError("task_mode must be 'class' or 'regress'")
+    lo, hi, k, min_gap, top, chunk_rows = int(lo), int(hi), int(k), int(min_gap), int(top), int(chunk_rows)
+    n = hi - lo
+    width = int(k if width is None else width)
+    if not k <= width <= _lib.MAX_L:
+        raise ValueError(f"width must be in [k, {_lib.MAX_L}]")
+    if top < 1 or chunk_rows < 1:
+        raise ValueError("top and chunk_rows must be >= 1")
+    act = torch.nn.functional.softplus if task_mode == "regress" else torch.sigmoid
+    model.eval()
+    dev = model.layer_norm1.weight.device
+    anchors = _anchor_table(anchors, dev)
+    A, s = int(anchors.shape[0]), int(anchors.shape[1])
+    total = anchored_count(A, s, n, k, min_gap) if n >= 1 else 0
+    cf = total // A if A else 0
+    K = min(top, cf)
+    if total == 0:
+        e = torch.zeros(A, K, dtype=torch.float32, device=dev)
+        return {"rows": torch.zeros(A, K, width, dtype=torch.long, device=dev), "logit": e, "proba": e.clone(),
+                "rank": torch.full((A, K), -1, dtype=torch.long, device=dev), "count": torch.zeros(A, dtype=torch.long, device=dev),
+                "n_candidates": 0, "n_invalid": 0, "n_excluded": 0}
+    chunk_rows = min(chunk_rows, total)
+    sel = SegTopK(A, K, cf, chunk_rows, dev)
+    buf = torch.empty(chunk_rows * width, dtype=torch.long, device=dev)
+    fbuf = torch.empty(chunk_rows, dtype=torch.int32, device=dev)
+    n_inv = torch.zeros((), dtype=torch.long, device=dev)
+    n_exc = torch.zeros((), dtype=torch.long, device=dev)
+    with torch.no_grad(), model.deferred_id_check(), _lib.option("disable_small_batch"):
+        for g0 in range(0, total, chunk_rows):
+            x, flag = anchored_rows(anchors, lo, n, k, min_gap, rank0=g0, count=min(chunk_rows, total - g0), width=width, out=buf, flag_out=fbuf)
+            logits = model(x).reshape(-1)
+            skip = flag != 0
+            n_inv += skip.sum()
+            if exclude is not None:
+                known = exclude.contains(x)
+                n_exc += (known & ~skip).sum()
+                skip = skip | known
+            sel.update(logits, g0, skip)
+    logit, grank, count = sel.read()
+    rows, _ = anchored_rows(anchors, lo, n, k, min_gap, ranks=grank, width=width, device=dev)
+    kept = grank >= 0
+    rank = torch.where(kept, grank - torch.arange(A, dtype=torch.long, device=dev).view(-1, 1) * cf, grank)
+    proba = torch.where(kept, act(logit), torch.zeros_like(logit))
+    return {"rows": rows.view(A, K, width), "logit": logit, "proba": proba, "rank": rank, "count": count, "n_candidates": total,
+            "n_invalid": int(n_inv.item()), "n_excluded": int(n_exc.item())}

@@ -1,6 +1,7 @@
 """Cost of the de novo k-way sweep (csrc/sweep.hip, matcha_amd/sweep.py) beside the forward it feeds.
 
   python tools/sweep_bench.py [--top 10000] [--chunk-rows 1048576] [--sweep-only] [--stats kernel_stats.csv]
+  python tools/sweep_bench.py --anchored [--chunk-rows 1048576] [--sweep-only]
 
 d = 64 table model, hg38 at 1 Mb, chr1 (250 bins), min_gap 1: k = 3 over the whole chromosome (2 573 000 candidates) and k = 4 over
 its first 2^26 ranks, timed end to end with device events after a warm-up (candidates/s); then, on one steady-state chunk of k = 4
@@ -9,7 +10,10 @@ stand next to the forward of the same chunk in the same run.  By bytes kway_rows
 (the radix sort of the chunk's 32-bit keys and indices is on top: four passes over 8 bytes per row, read and written).
 --sweep-only runs the k = 4 sweep alone (the run to put under rocprofv3 --kernel-trace --stats); --stats reads that run's
 kernel_stats.csv and prints the share of kway_rows_kernel, of the selection (topk_* and the radix sort) and of everything else (the
-forward)."""
+forward).
+--anchored: the anchored sweep at k = 3 with every bin of chr1 an anchor and chr1 as partner region (250 x 31 125
+global ranks), top 100 per anchor, beside the plain k = 3 kway_sweep (top 100) in the same run, rows/s by device events after a
+warm-up; with --sweep-only the anchored sweep alone (the run to put under rocprofv3 --kernel-trace --stats)."""
 import argparse
 import sys
 
@@ -87,13 +91,30 @@ def bench(top, chunk_rows, sweep_only):
               f"forward {t_fwd:.3f} ms ({rows / t_fwd / 1e3:.1f} M rows/s), TopK update {t_upd:.3f} ms ({100 * t_upd / t_fwd:.1f} % of the forward)", flush=True)
 
 
+def bench_anchored(chunk_rows, sweep_only):
+    clf, lo, hi = model()
+    anchors = torch.arange(lo, hi, device="cuda")
+    total = SW.anchored_count(hi - lo, 1, hi - lo, 3, 1)
+    run = lambda: SW.anchored_sweep(clf, anchors, lo, hi, 3, 1, 100, chunk_rows=chunk_rows)
+    if sweep_only:
+        run()
+        torch.cuda.synchronize()
+        return
+    ta = timed(run, 3)
+    print(f"anchored k=3, 250 anchors x chr1: {total} global ranks, top 100 per anchor, chunk {chunk_rows}: {ta:.1f} ms end to end, "
+          f"{total / ta / 1e3:.1f} M rows/s", flush=True)
+    total3 = SW.kway_count(hi - lo, 3, 1)
+    t3 = timed(lambda: SW.kway_sweep(clf, lo, hi, 3, 1, 100, chunk_rows=chunk_rows), 3)
+    print(f"plain kway_sweep k=3: {total3} candidates, top 100, chunk {chunk_rows}: {t3:.1f} ms end to end, {total3 / t3 / 1e3:.1f} M rows/s", flush=True)
+
+
 def stats(path):
     import csv
     rows = list(csv.DictReader(open(path)))
     groups = {"kway_rows_kernel": 0.0, "selection (topk_* + radix sort)": 0.0, "everything else (the forward)": 0.0}
     for r in rows:
         name, ns = r["Name"], float(r["TotalDurationNs"])
-        if "kway_rows_kernel" in name:
+        if "kway_rows_kernel" in name or "kway_anchor_rows_kernel" in name:
             groups["kway_rows_kernel"] += ns
         elif "topk_" in name or "rocprim" in name.lower() or "radix" in name.lower():
             groups["selection (topk_* + radix sort)"] += ns
@@ -113,8 +134,11 @@ if __name__ == "__main__":
     ap.add_argument("--chunk-rows", type=int, default=1 << 20)
     ap.add_argument("--sweep-only", action="store_true")
     ap.add_argument("--stats", type=str, default=None)
+    ap.add_argument("--anchored", action="store_true")
     a = ap.parse_args()
     if a.stats:
         stats(a.stats)
+    elif a.anchored:
+        bench_anchored(a.chunk_rows, a.sweep_only)
     else:
         bench(a.top, a.chunk_rows, a.sweep_only)
