@@ -614,6 +614,48 @@ int matcha_segtopk_update(void* state, size_t bytes, int64_t A, int32_t K, int64
 int matcha_segtopk_read(const void* state, size_t bytes, int64_t A, int32_t K, int64_t seg_len, int64_t max_chunk, float* scores_out,
                         int64_t* ranks_out, int64_t* counts_out, matcha_stream_t stream);
 
+/* ---- k-way pair maps -----------------------------------------------------------------------------------
+ * The values of k-way rows projected onto pairs of node ids and accumulated on the device.  A map covers the row region
+ * R = [lo_r, lo_r + n_r) and the column region C = [lo_c, lo_c + n_c): R == C (symmetric) or R and C disjoint (rectangular); any
+ * other overlap, n_r n_c >= 2^31, an empty or unknown plane mask and a vmax outside (0, 2^20] are refused.
+ * Row i of an update (x device int64 [n, L], 2 <= L <= 8, 0 = padding; value device float32 [n]; skip optional device int32 [n],
+ * the layout matcha_hashset_contains and matcha_kway_anchor_rows write) contributes nothing when skip[i] != 0 (not counted), or
+ * when value[i] is NaN, < 0 or > vmax (counted in n_rejected; -0.0 is accepted as 0, +inf is rejected).  Every other row counts in
+ * n_rows and contributes value[i] once for each pair of positions ci < cj with a = x[ci], b = x[cj] both non-zero, a != b, and
+ *   rectangular: cell (a - lo_r, b - lo_c) if a in R and b in C, else (b - lo_r, a - lo_c) if b in R and a in C, else none;
+ *   symmetric:   cell (min(a, b) - lo, max(a, b) - lo) if both are in R, else none (the read mirrors it; the diagonal reads 0).
+ * Rows need not be sorted or duplicate-free: (5, 5, 9) adds twice to {5, 9}.
+ * Planes (a bit mask; only the planes asked for take memory):
+ *   MATCHA_PAIRMAP_SUM       int64, the sum of rint((double)v * 2^32): fixed point with 32 fractional bits (exact for v >= 2^-8),
+ *                            so the plane is bitwise independent of arrival order and of how the stream is cut into updates.
+ *                            Exact while a cell's true sum stays below 2^31; capacity is the caller's to declare.
+ *   MATCHA_PAIRMAP_COUNT     int64, the number of contributions.
+ *   MATCHA_PAIRMAP_COUNT_GE  int64, the number of contributions with v >= threshold (compared in float32).
+ *   MATCHA_PAIRMAP_MAX       float32, the largest contributing v (-inf in a cell never hit).
+ * State blob (caller-owned, 8-byte aligned, matcha_pairmap_bytes bytes): a 256-byte header {int64 n_rows, int64 n_rejected, zero
+ * padding}, then the planes present in the order SUM, COUNT, COUNT_GE (n_r n_c int64 each), MAX (n_r n_c uint32 keys: 0 = never
+ * hit, else the float's bits | 0x80000000), every plane row-major [n_r][n_c] and padded to a multiple of 256 bytes; a symmetric map
+ * only ever writes its upper triangle.  The regions, the mask, vmax and threshold are passed to every call: the library keeps nothing
+ * on the host between calls, never allocates and never reads the state back; all calls are asynchronous on the caller's stream.
+ * matcha_pairmap_bytes   host only; 0 for invalid arguments.
+ * matcha_pairmap_init    zeroes the state (a kernel, no memset).
+ * matcha_pairmap_update  n = 0 is a no-op that launches nothing.  Integer atomics only: every plane is deterministic.
+ * matcha_pairmap_read    plane = ONE bit of the mask; out device int64 [n_r, n_c] (the raw fixed-point sums for SUM) or float32
+ *     [n_r, n_c] for MAX; counters_out optional device int64 [2] = {n_rows, n_rejected}.
+ * All refuse, before any device call: a null pointer, arguments out of range, L outside [2, 8], n < 0, a state that is too small. */
+#define MATCHA_PAIRMAP_SUM 1
+#define MATCHA_PAIRMAP_COUNT 2
+#define MATCHA_PAIRMAP_COUNT_GE 4
+#define MATCHA_PAIRMAP_MAX 8
+size_t matcha_pairmap_bytes(int64_t lo_r, int32_t n_r, int64_t lo_c, int32_t n_c, int32_t planes, float vmax, float threshold);
+int matcha_pairmap_init(void* state, size_t bytes, int64_t lo_r, int32_t n_r, int64_t lo_c, int32_t n_c, int32_t planes, float vmax,
+                        float threshold, matcha_stream_t stream);
+int matcha_pairmap_update(void* state, size_t bytes, int64_t lo_r, int32_t n_r, int64_t lo_c, int32_t n_c, int32_t planes, float vmax,
+                          float threshold, const int64_t* x, const float* value, const int32_t* skip, int64_t n, int32_t L,
+                          matcha_stream_t stream);
+int matcha_pairmap_read(const void* state, size_t bytes, int64_t lo_r, int32_t n_r, int64_t lo_c, int32_t n_c, int32_t planes,
+                        float vmax, float threshold, int32_t plane, void* out, int64_t* counters_out, matcha_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -64,7 +64,7 @@ class GemmEpilogue(C.Structure):
 
 
 # name -> (restype, argtypes)   -- every symbol include/matcha_hip.h declares
-_I64, _I32, _SZ, _D = C.c_int64, C.c_int32, C.c_size_t, C.c_double
+_I64, _I32, _SZ, _D, _F = C.c_int64, C.c_int32, C.c_size_t, C.c_double, C.c_float
 SIGNATURES = {
     "matcha_abi_version": (C.c_int, []),
     "matcha_last_error": (C.c_char_p, []),
@@ -134,7 +134,15 @@ SIGNATURES = {
     "matcha_segtopk_init": (C.c_int, [_fp, _SZ, _I64, _I32, _I64, _I64, _fp]),
     "matcha_segtopk_update": (C.c_int, [_fp, _SZ, _I64, _I32, _I64, _I64, _I64, _fp, _fp, _I64, _I64, _fp]),
     "matcha_segtopk_read": (C.c_int, [_fp, _SZ, _I64, _I32, _I64, _I64, _fp, _fp, _fp, _fp]),
+    "matcha_pairmap_bytes": (_SZ, [_I64, _I32, _I64, _I32, _I32, _F, _F]),
+    "matcha_pairmap_init": (C.c_int, [_fp, _SZ, _I64, _I32, _I64, _I32, _I32, _F, _F, _fp]),
+    "matcha_pairmap_update": (C.c_int, [_fp, _SZ, _I64, _I32, _I64, _I32, _I32, _F, _F, _fp, _fp, _fp, _I64, _I32, _fp]),
+    "matcha_pairmap_read": (C.c_int, [_fp, _SZ, _I64, _I32, _I64, _I32, _I32, _F, _F, _I32, _fp, _fp, _fp]),
 }
+
+PAIRMAP_SUM, PAIRMAP_COUNT, PAIRMAP_COUNT_GE, PAIRMAP_MAX = 1, 2, 4, 8      # MATCHA_PAIRMAP_* of include/matcha_hip.h
+PAIRMAP_PLANES = {"sum": PAIRMAP_SUM, "count": PAIRMAP_COUNT, "count_ge": PAIRMAP_COUNT_GE, "max": PAIRMAP_MAX}
+PAIRMAP_ALL = 15
 
 OBJECTIVE_BCE, OBJECTIVE_SOFTPLUS_MSE = 0, 1      # MATCHA_OBJECTIVE_* of include/matcha_hip.h
 OBJECTIVES = {"class": OBJECTIVE_BCE, "regress": OBJECTIVE_SOFTPLUS_MSE}      # the reference's task_mode (main.py:532)

@@ -14,12 +14,16 @@ CLI:  python -m matcha_amd.predict multiway -i interactions.txt -o output.txt
       python -m matcha_amd.predict pairwise --chrom 0 -o chr1_proba.npy
       python -m matcha_amd.predict kway --chrom 0 --k 3 --top 1000 [--start-bin A --end-bin B] [--exclude-known] -o top.tsv
       python -m matcha_amd.predict anchored --k 3 --top 20 --chrom 5 (--anchor-file loci.tsv | --anchor-chrom 0) -o anchored.tsv
+      python -m matcha_amd.predict kmap --chrom 0 --k 3 [--start-bin A --end-bin B] [--threshold 0.5] [--exclude-known] -o map.npz
 (all read ./config.JSON like the reference: temp_dir, resolution, chrom_list, min_distance).
 
 * ``kway`` -- the de novo sweep of matcha_amd/sweep.py: every candidate of size k in one chromosome (or a window of its bins)
   with adjacent gaps > min_distance, scored on the device, the best ``--top`` written as ``chrom:start`` items and a probability.
 * ``anchored`` -- the anchored sweep of matcha_amd/sweep.py: for every anchor (a line of ``--anchor-file``, or every bin of
   ``--anchor-chrom``) the best ``--top`` candidates of size k that contain it, the other nodes taken from ``--chrom``.
+* ``kmap`` -- the pair map of matcha_amd/sweep.py: the probabilities of ALL candidates of size k of one chromosome (or bin window)
+  projected onto pairs of bins -- per pair the summed probability, the mean, the best candidate, the number of candidates and the
+  number at or above ``--threshold`` -- written as one .npz of [n, n] matrices.
 """
 from __future__ import annotations
 
@@ -184,6 +188,29 @@ def _kway(args, config, temp_dir, model):
     print("%d candidates (%d known, skipped) -> %d in %s" % (out["n_candidates"], out["n_excluded"], len(rows), args.output))
 
 
+def _kmap(args, config, temp_dir, model):
+    from . import sweep as SW
+    from .sampler import HyperedgeSet
+    chrom_range = np.load(os.path.join(temp_dir, "chrom_range.npy"))
+    c_lo, c_hi = int(chrom_range[args.chrom][0]), int(chrom_range[args.chrom][1])
+    lo = c_lo + (args.start_bin if args.start_bin is not None else 0)
+    hi = c_lo + args.end_bin if args.end_bin is not None else c_hi
+    if not c_lo <= lo <= hi <= c_hi:
+        raise ValueError("the bin window [%s, %s) is not inside chromosome %d (%d bins)" % (args.start_bin, args.end_bin, args.chrom, c_hi - c_lo))
+    dev = model.layer_norm1.weight.device
+    exclude = None
+    if args.exclude_known:
+        known = np.load(os.path.join(temp_dir, "all_%d_counter.npy" % args.k)).astype(np.int64).reshape(-1, args.k)
+        exclude = HyperedgeSet(torch.from_numpy(known).to(dev))
+    min_gap = int(config["min_distance"]) + 1
+    out = SW.kway_map(model, lo, hi, args.k, min_gap, chunk_rows=args.chunk_rows, width=args.width, exclude=exclude, task_mode=args.task_mode,
+                      threshold=args.threshold, value_max=args.value_max)
+    np.savez(args.output, **{name: out[name].cpu().numpy() for name in ("sum", "mean", "max", "count", "count_ge")}, lo=np.int64(lo),
+             n=np.int64(hi - lo), k=np.int64(args.k), min_gap=np.int64(min_gap), threshold=np.float32(args.threshold))
+    print("%d candidates (%d known, skipped; %d rejected) -> %d x %d map in %s"
+          % (out["n_candidates"], out["n_excluded"], out["n_rejected"], hi - lo, hi - lo, args.output))
+
+
 def parse_anchor_file(filepath: str, bin2node: Dict[str, int], chrom_list: Sequence[str], res: int) -> np.ndarray:
     """int64 [A, s]: one anchor row per non-empty line, s tab-separated ``chrom:position`` loci with parse_file's coordinate
     handling (positions floored to their bin, an item without ``:`` raises EOFError, an unknown bin KeyError), each row sorted.
@@ -288,8 +315,20 @@ def main(argv=None):
     d.add_argument("--chunk-rows", type=int, default=1 << 20)
     d.add_argument("--task-mode", choices=["class", "regress"], default="class", help="the model's training objective: sigmoid or softplus outputs")
     d.add_argument("-o", "--output", type=str, default="./anchored.tsv")
+    e = sub.add_parser("kmap", help="pair map: the probabilities of all candidates of size --k projected onto pairs of bins")
+    e.add_argument("--chrom", type=int, required=True, help="index into config chrom_list")
+    e.add_argument("--k", type=int, required=True, help="candidate size, 2 .. 8")
+    e.add_argument("--start-bin", type=int, default=None, help="first bin of the window, relative to the chromosome (default 0)")
+    e.add_argument("--end-bin", type=int, default=None, help="one past the last bin of the window (default: the chromosome's end)")
+    e.add_argument("--threshold", type=float, default=0.5, help="count_ge counts the candidates of a pair with a value >= this")
+    e.add_argument("--exclude-known", action="store_true", help="skip the hyperedges of temp_dir/all_<k>_counter.npy")
+    e.add_argument("--width", type=int, default=None, help="zero-pad rows to this width (default k): a logit depends on its batch's width")
+    e.add_argument("--chunk-rows", type=int, default=1 << 20)
+    e.add_argument("--task-mode", choices=["class", "regress"], default="class", help="the model's training objective: sigmoid or softplus outputs")
+    e.add_argument("--value-max", type=float, default=None, help="task-mode regress: the largest value a candidate may contribute (<= 2^20)")
+    e.add_argument("-o", "--output", type=str, default="./kmap.npz")
     d.add_argument("--config", type=str, default="./config.JSON")
-    for q in (a, b, c):
+    for q in (a, b, c, e):
         q.add_argument("--config", type=str, default="./config.JSON")
     args = ap.parse_args(argv)
     config, temp_dir, model = _load(args.config)
@@ -297,6 +336,8 @@ def main(argv=None):
         return _kway(args, config, temp_dir, model)
     if args.cmd == "anchored":
         return _anchored(args, config, temp_dir, model)
+    if args.cmd == "kmap":
+        return _kmap(args, config, temp_dir, model)
     if args.cmd == "multiway":
         bin2node = np.load(os.path.join(temp_dir, "bin2node.npy"), allow_pickle=True).item()
         samples, proba = predict_multiway(model, args.file, bin2node, config["chrom_list"], config["resolution"], args.output)

@@ -10,6 +10,9 @@ A candidate of size k in the region [lo, lo + n) is a strictly ascending k-tuple
 >= min_gap (min_gap = min_distance + 1: generate_kmers.py:18, :33 and the sampler).  Candidates are ordered lexicographically; the
 rank of one is its position, from 0.  With m = n - (k - 1)(min_gap - 1), y_j = x_j - lo - j (min_gap - 1) maps them, order
 preserved, onto the k-subsets of [0, m): C(m, k) candidates.
+
+``anchored_sweep`` keeps the best K per anchor instead of one global list; ``kway_map`` / ``PairMap`` (DESIGN.md 7.5,
+csrc/pairmap.hip) project the scores of all candidates onto pairs of bins instead of keeping a list at all.
 """
 from __future__ import annotations
 
@@ -422,3 +425,201 @@ def anchored_sweep(model, anchors, lo: int, hi: int, k: int, min_gap: int, top: 
     proba = torch.where(kept, act(logit), torch.zeros_like(logit))
     return {"rows": rows.view(A, K, width), "logit": logit, "proba": proba, "rank": rank, "count": count, "n_candidates": total,
             "n_invalid": int(n_inv.item()), "n_excluded": int(n_exc.item())}
+
+
+# ---- pair maps: a sweep's scores projected onto pairs of bins ------------------------------------------------------
+_PLANE_ORDER = ("sum", "count", "count_ge", "max")
+
+
+def _plane_mask(planes) -> int:
+    if planes is None or planes == "all":
+        return _lib.PAIRMAP_ALL
+    if isinstance(planes, int):
+        mask = int(planes)
+    else:
+        names = [planes] if isinstance(planes, str) else list(planes)
+        unknown = [p for p in names if p not in _lib.PAIRMAP_PLANES]
+        if unknown:
+            raise ValueError(f"unknown planes {unknown}: choose among {_PLANE_ORDER}")
+        mask = sum(_lib.PAIRMAP_PLANES[p] for p in set(names))
+    if not 1 <= mask <= _lib.PAIRMAP_ALL:
+        raise ValueError(f"the plane mask must be in [1, {_lib.PAIRMAP_ALL}] (got {mask})")
+    return mask
+
+
+class PairMap:
+    """Pair map on the device (csrc/pairmap.hip): ``rows`` = (lo, n) and ``cols`` = (lo, n) are two regions of node ids, equal
+    (symmetric map) or disjoint (rectangular map).  Every accepted row of an ``update`` adds its value to the cell of each pair of its
+    positions (see ``update``).  ``planes``: 'all', a bit mask, or names among 'sum', 'count', 'count_ge', 'max' -- only those take
+    memory.  The sum is kept in fixed point (int64, 32 fractional bits) and everything is accumulated with integer atomics, so every
+    plane is bit for bit the same whatever the order of the rows and however they were cut into updates.  ``vmax``: the largest value
+    accepted, 0 < vmax <= 2^20; a cell's sum is exact while it stays below 2^31.  ``threshold``: what 'count_ge' counts (value >=
+    threshold, in float32)."""
+
+    def __init__(self, rows, cols, planes="all", vmax: float = 1.0, threshold: float = 0.5, device="cuda"):
+        lib = _lib.load()
+        (self.lo_r, self.n_r), (self.lo_c, self.n_c) = (int(rows[0]), int(rows[1])), (int(cols[0]), int(cols[1]))
+        self.planes = _plane_mask(planes)
+        self.vmax, self.threshold = float(vmax), float(threshold)
+        self.symmetric = (self.lo_r, self.n_r) == (self.lo_c, self.n_c)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.MatchaHipError("PairMap needs a cuda device (no CPU fallback)")
+        fits = all(0 <= lo < 1 << 62 for lo in (self.lo_r, self.lo_c)) and all(1 <= n < 1 << 31 for n in (self.n_r, self.n_c))
+        self._dims = (self.lo_r, self.n_r, self.lo_c, self.n_c, self.planes, self.vmax, self.threshold)
+        self.bytes = int(lib.matcha_pairmap_bytes(*self._dims)) if fits else 0
+        if self.bytes == 0:
+            raise ValueError(f"PairMap: need two regions (lo >= 0, n >= 1) that are equal or disjoint, n_r * n_c < 2^31 and 0 < vmax <= 2^20 "
+                             f"(rows={rows} cols={cols} vmax={vmax})")
+        self.state = torch.empty(self.bytes, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(lib.matcha_pairmap_init(_lib.ptr(self.state), self.bytes, *self._dims, _stream(self.device)), "matcha_pairmap_init")
+
+    def update(self, x: torch.Tensor, value: torch.Tensor, skip: Optional[torch.Tensor] = None):
+        """``x`` int64 [n, L] on the device (2 <= L <= 8, 0 = padding; rows need not be sorted), ``value`` float32 [n], ``skip``
+        int32 / bool [n] (non-zero = the row contributes nothing; anchored_rows' flag and HyperedgeSet.contains fit).  A row whose
+        value is NaN, negative or > vmax is counted as rejected and contributes nothing.  For each pair of positions ci < cj with
+        ids a, b both non-zero and different: rectangular, cell (a - lo_r, b - lo_c) if a is a row id and b a column id, or the
+        other way round; symmetric, the unordered pair.  Enqueued on the current stream; nothing is read back."""
+        lib = _lib.load()
+        if x.dim() != 2 or x.dtype != torch.long or x.device != self.state.device:
+            raise ValueError("x must be an int64 [n, L] tensor on the PairMap's device")
+        value = value.reshape(-1)
+        if value.dtype != torch.float32 or value.device != self.state.device or value.numel() != x.shape[0]:
+            raise ValueError("value must be a float32 [n] tensor on the PairMap's device")
+        x, value = x.contiguous(), value.contiguous()
+        if skip is not None:
+            skip = skip.reshape(-1).to(device=value.device, dtype=torch.int32).contiguous()
+            if skip.numel() != value.numel():
+                raise ValueError("skip and value differ in length")
+        with torch.cuda.device(self.device):
+            _lib.check(lib.matcha_pairmap_update(_lib.ptr(self.state), self.bytes, *self._dims, _lib.ptr(x), _lib.ptr(value), _lib.ptr(skip),
+                                                 int(x.shape[0]), int(x.shape[1]), _stream(self.device)), "matcha_pairmap_update")
+
+    def read(self) -> dict:
+        """The planes present as they are kept, on the device and without a synchronisation: 'sum' int64 [n_r, n_c] (fixed point,
+        value * 2^32), 'count' and 'count_ge' int64, 'max' float32 (-inf where nothing landed); a symmetric map comes mirrored
+        with a zero diagonal.  'counters' int64 [2] = (accepted rows, rejected rows)."""
+        lib = _lib.load()
+        out = {}
+        counters = torch.empty(2, dtype=torch.long, device=self.device)
+        with torch.cuda.device(self.device):
+            for name in _PLANE_ORDER:
+                bit = _lib.PAIRMAP_PLANES[name]
+                if not self.planes & bit:
+                    continue
+                t = torch.empty(self.n_r, self.n_c, dtype=torch.float32 if name == "max" else torch.long, device=self.device)
+                _lib.check(lib.matcha_pairmap_read(_lib.ptr(self.state), self.bytes, *self._dims, bit, _lib.ptr(t), _lib.ptr(counters),
+                                                   _stream(self.device)), "matcha_pairmap_read")
+                out[name] = t
+        out["counters"] = counters
+        return out
+
+    def result(self) -> dict:
+        """The planes present, on the device: 'sum' float64 (the fixed-point sum / 2^32), 'count', 'count_ge', 'max', and -- when
+        sum and count are both kept -- 'mean' float32 = sum / count (0 where count is 0); 'n_rows' and 'n_rejected' as 0-d int64
+        tensors."""
+        raw = self.read()
+        counters = raw.pop("counters")
+        out = dict(raw)
+        if "sum" in out:
+            out["sum"] = out["sum"].to(torch.float64) / 4294967296.0
+        if "sum" in out and "count" in out:
+            hit = out["count"] > 0
+            out["mean"] = torch.where(hit, out["sum"] / out["count"].clamp(min=1).to(torch.float64), torch.zeros_like(out["sum"])).to(torch.float32)
+        out["n_rows"], out["n_rejected"] = counters[0], counters[1]
+        return out
+
+
+def _empty_map(n_r: int, n_c: int, mask: int, dev) -> dict:
+    out = {}
+    if mask & _lib.PAIRMAP_SUM:
+        out["sum"] = torch.zeros(n_r, n_c, dtype=torch.float64, device=dev)
+    if mask & _lib.PAIRMAP_COUNT:
+        out["count"] = torch.zeros(n_r, n_c, dtype=torch.long, device=dev)
+    if mask & _lib.PAIRMAP_COUNT_GE:
+        out["count_ge"] = torch.zeros(n_r, n_c, dtype=torch.long, device=dev)
+    if mask & _lib.PAIRMAP_MAX:
+        out["max"] = torch.full((n_r, n_c), float("-inf"), dtype=torch.float32, device=dev)
+        if n_r == n_c:
+            out["max"].fill_diagonal_(0.0)
+    if "sum" in out and "count" in out:
+        out["mean"] = torch.zeros(n_r, n_c, dtype=torch.float32, device=dev)
+    return out
+
+
+def kway_map(model, lo: int, hi: int, k: int, min_gap: int, chunk_rows: int = 1 << 20, width: Optional[int] = None, exclude=None,
+             task_mode: str = "class", threshold: float = 0.5, planes="all", value_max: Optional[float] = None,
+             row_window: Optional[Tuple[int, int]] = None, col_window: Optional[Tuple[int, int]] = None) -> dict:
+    """Score every candidate of size k in the region [lo, hi) (kway_sweep's candidates, in its order, through its loop) and project
+    the probabilities onto pairs of bins: for every pair, the summed probability of the candidates that contain it ('sum', float64),
+    their number ('count'), how many reach ``threshold`` ('count_ge'), the best of them ('max', -inf where there is none) and
+    'mean' = sum / count -- the multi-way counterpart of the pairwise probability matrix.
+
+    The default map is symmetric over [lo, hi) ([n, n], mirrored, zero diagonal).  ``row_window`` and ``col_window``, two disjoint
+    (lo, n) windows inside the region, give the rectangular block [row bins, column bins] of the same map instead.  The value of a
+    candidate is sigmoid(logit), or softplus(logit) for task_mode 'regress', where ``value_max`` (the largest value accepted, <= 2^20)
+    is required: larger values, and NaN, are counted in ``n_rejected`` and contribute nothing.  The sum is exact in fixed point while
+    a cell's total stays below 2^31; a sweep whose bound per cell, C(m, k - 2) * vmax with m = n - (k - 1)(min_gap - 1), reaches
+    2^31 is refused before anything is launched.  ``exclude``, ``width`` and ``chunk_rows`` as in kway_sweep; the planes do not depend
+    on ``chunk_rows``, bit for bit.
+
+    Returns the planes (device tensors) and the integers ``n_candidates``, ``n_excluded`` and ``n_rejected``.  Nothing synchronises
+    until the end, where the node-id check of the whole sweep is raised once (IndexError)."""
+    if task_mode not in ("class", "regress"):
+        raise ValueError("task_mode must be 'class' or 'regress'")
+    lo, hi, k, min_gap, chunk_rows = int(lo), int(hi), int(k), int(min_gap), int(chunk_rows)
+    n = hi - lo
+    width = int(k if width is None else width)
+    if not k <= width <= _lib.MAX_L:
+        raise ValueError(f"width must be in [k, {_lib.MAX_L}]")
+    if chunk_rows < 1:
+        raise ValueError("chunk_rows must be >= 1")
+    if task_mode == "regress":
+        if value_max is None:
+            raise ValueError("task_mode 'regress' needs value_max: the largest value a candidate may contribute")
+        vmax, act = float(value_max), torch.nn.functional.softplus
+    else:
+        vmax, act = 1.0, torch.sigmoid
+    if not 0.0 < vmax <= float(1 << 20):
+        raise ValueError("value_max must be in (0, 2^20]")
+    mask = _plane_mask(planes)
+    if (row_window is None) != (col_window is None):
+        raise ValueError("row_window and col_window go together")
+    if row_window is None:
+        rows = cols = (lo, n)
+    else:
+        rows, cols = (int(row_window[0]), int(row_window[1])), (int(col_window[0]), int(col_window[1]))
+        inside = all(w[1] >= 1 and lo <= w[0] and w[0] + w[1] <= hi for w in (rows, cols))
+        if not inside or not (rows[0] + rows[1] <= cols[0] or cols[0] + cols[1] <= rows[0]):
+            raise ValueError(f"row_window and col_window must be two disjoint (lo, n) windows inside [{lo}, {hi})")
+    if n >= 1:
+        _check_args(n, k, min_gap)
+    m = n - (k - 1) * (min_gap - 1)
+    if m >= k and math.comb(m, k - 2) * vmax >= float(1 << 31):
+        raise ValueError(f"a cell may receive C({m}, {k - 2}) = {math.comb(m, k - 2)} candidates of value <= {vmax}: the sum's capacity of 2^31 "
+                         "per cell is not enough (sweep a smaller region)")
+    model.eval()
+    dev = model.layer_norm1.weight.device
+    total = kway_count(n, k, min_gap) if n >= 1 else 0
+    if total == 0:
+        out = _empty_map(max(rows[1], 0), max(cols[1], 0), mask, dev)
+        out.update(n_candidates=0, n_excluded=0, n_rejected=0)
+        return out
+    chunk_rows = min(chunk_rows, total)
+    pm = PairMap(rows, cols, mask, vmax=vmax, threshold=threshold, device=dev)
+    buf = torch.empty(chunk_rows * width, dtype=torch.long, device=dev)
+    n_exc = torch.zeros((), dtype=torch.long, device=dev)
+    with torch.no_grad(), model.deferred_id_check(), _lib.option("disable_small_batch"):      # as kway_sweep: one forward route
+        for r0 in range(0, total, chunk_rows):
+            x = kway_rows(lo, n, k, min_gap, rank0=r0, count=min(chunk_rows, total - r0), width=width, out=buf)
+            value = act(model(x).reshape(-1))
+            skip = None
+            if exclude is not None:
+                skip = exclude.contains(x)
+                n_exc += skip.sum()
+            pm.update(x, value, skip)
+    out = pm.result()
+    out.pop("n_rows")
+    out.update(n_candidates=total, n_excluded=int(n_exc.item()), n_rejected=int(out["n_rejected"].item()))
+    return out

@@ -2,6 +2,7 @@
 
   python tools/sweep_bench.py [--top 10000] [--chunk-rows 1048576] [--sweep-only] [--stats kernel_stats.csv]
   python tools/sweep_bench.py --anchored [--chunk-rows 1048576] [--sweep-only]
+  python tools/sweep_bench.py --map [--chunk-rows 1048576] [--sweep-only]
 
 d = 64 table model, hg38 at 1 Mb, chr1 (250 bins), min_gap 1: k = 3 over the whole chromosome (2 573 000 candidates) and k = 4 over
 its first 2^26 ranks, timed end to end with device events after a warm-up (candidates/s); then, on one steady-state chunk of k = 4
@@ -13,7 +14,11 @@ kernel_stats.csv and prints the share of kway_rows_kernel, of the selection (top
 forward).
 --anchored: the anchored sweep at k = 3 with every bin of chr1 an anchor and chr1 as partner region (250 x 31 125
 global ranks), top 100 per anchor, beside the plain k = 3 kway_sweep (top 100) in the same run, rows/s by device events after a
-warm-up; with --sweep-only the anchored sweep alone (the run to put under rocprofv3 --kernel-trace --stats)."""
+warm-up; with --sweep-only the anchored sweep alone (the run to put under rocprofv3 --kernel-trace --stats).
+--map: kway_map over the whole of chr1 at k = 3 and k = 4 (all four planes) beside kway_sweep (top ``--top``) on the
+same region in the same run, by device events after a warm-up; then, on one chunk of each k, the forward and PairMap.update (all
+planes, and the sum alone) each on their own.  With --sweep-only the k = 3 map alone, three times (the run to put under rocprofv3
+--kernel-trace --stats; --stats then also lists the share of pairmap_*)."""
 import argparse
 import sys
 
@@ -108,20 +113,56 @@ def bench_anchored(chunk_rows, sweep_only):
     print(f"plain kway_sweep k=3: {total3} candidates, top 100, chunk {chunk_rows}: {t3:.1f} ms end to end, {total3 / t3 / 1e3:.1f} M rows/s", flush=True)
 
 
+def bench_map(top, chunk_rows, sweep_only):
+    clf, lo, hi = model()
+    n = hi - lo
+    if sweep_only:
+        for _ in range(3):
+            SW.kway_map(clf, lo, hi, 3, 1, chunk_rows=chunk_rows)
+        torch.cuda.synchronize()
+        return
+    for k, reps in ((3, 5), (4, 1)):
+        total = SW.kway_count(n, k, 1)
+        tm = timed(lambda: SW.kway_map(clf, lo, hi, k, 1, chunk_rows=chunk_rows), reps)
+        ts = timed(lambda: SW.kway_sweep(clf, lo, hi, k, 1, top, chunk_rows=chunk_rows), reps)
+        print(f"k={k} chr1: {total} candidates, chunk {chunk_rows}: kway_map {tm:.1f} ms ({total / tm / 1e3:.1f} M candidates/s), "
+              f"kway_sweep top {top} {ts:.1f} ms ({total / ts / 1e3:.1f} M candidates/s), map / sweep {tm / ts:.3f}", flush=True)
+    for k in (3, 4):
+        rows = min(chunk_rows, SW.kway_count(n, k, 1))
+        buf = torch.empty(rows * k, dtype=torch.long, device="cuda")
+        with torch.no_grad(), clf.deferred_id_check():
+            x = SW.kway_rows(lo, n, k, 1, rank0=0, count=rows, out=buf)
+            value = torch.sigmoid(clf(x).reshape(-1))
+            t_fwd = timed(lambda: clf(x), 10)
+            line = f"k={k} chunk of {rows} rows: forward {t_fwd:.3f} ms"
+            for planes in ("all", ["sum"]):
+                pm = SW.PairMap((lo, n), (lo, n), planes)
+                t_upd = timed(lambda: pm.update(x, value), 10)
+                cells = rows * k * (k - 1) // 2
+                line += f"; PairMap.update {planes} {t_upd:.3f} ms ({100 * t_upd / t_fwd:.1f} % of the forward, {cells / t_upd / 1e6:.2f} G cell updates/s)"
+            shuffled = x[torch.randperm(rows, device="cuda")].contiguous()
+            pm = SW.PairMap((lo, n), (lo, n), "all")
+            t_shuf = timed(lambda: pm.update(shuffled, value), 10)
+            line += f"; the same rows shuffled (no runs to merge) {t_shuf:.3f} ms"
+        print(line, flush=True)
+
+
 def stats(path):
     import csv
     rows = list(csv.DictReader(open(path)))
-    groups = {"kway_rows_kernel": 0.0, "selection (topk_* + radix sort)": 0.0, "everything else (the forward)": 0.0}
+    groups = {"kway_rows_kernel": 0.0, "selection (topk_* + radix sort)": 0.0, "pair map (pairmap_*)": 0.0, "everything else (the forward)": 0.0}
     for r in rows:
         name, ns = r["Name"], float(r["TotalDurationNs"])
         if "kway_rows_kernel" in name or "kway_anchor_rows_kernel" in name:
             groups["kway_rows_kernel"] += ns
+        elif "pairmap_" in name:
+            groups["pair map (pairmap_*)"] += ns
         elif "topk_" in name or "rocprim" in name.lower() or "radix" in name.lower():
             groups["selection (topk_* + radix sort)"] += ns
         else:
             groups["everything else (the forward)"] += ns
     total = sum(groups.values())
-    print(f"kernel time of the k = 4 sweep over 2^26 ranks ({path}): {total / 1e6:.1f} ms")
+    print(f"kernel time of the profiled run ({path}): {total / 1e6:.1f} ms")
     for g, ns in groups.items():
         print(f"  {g:34s} {ns / 1e6:9.2f} ms  {100 * ns / total:5.1f} %")
     for r in sorted(rows, key=lambda r: -float(r["TotalDurationNs"]))[:12]:
@@ -135,9 +176,12 @@ if __name__ == "__main__":
     ap.add_argument("--sweep-only", action="store_true")
     ap.add_argument("--stats", type=str, default=None)
     ap.add_argument("--anchored", action="store_true")
+    ap.add_argument("--map", action="store_true")
     a = ap.parse_args()
     if a.stats:
         stats(a.stats)
+    elif a.map:
+        bench_map(a.top, a.chunk_rows, a.sweep_only)
     elif a.anchored:
         bench_anchored(a.chunk_rows, a.sweep_only)
     else:
