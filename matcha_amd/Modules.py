@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import os
 import weakref
 from typing import Dict, List, Optional
 
@@ -540,7 +541,12 @@ class _Runtime:
         n = query(C.byref(self.shape), B, L)
         if n == 0:
             raise _lib.MatchaHipError(self.lib.matcha_last_error().decode())
-        return torch.empty(n, dtype=torch.uint8, device=self.device)
+        ws = torch.empty(n, dtype=torch.uint8, device=self.device)
+        # development: a read of workspace bytes nobody wrote shows up as NaN / garbage -- the Trainer's workspaces and the ones model(x) takes
+        # per call (the autograd path's forward and backward are two calls on one of these)
+        if os.environ.get("MATCHA_POISON_WS"):
+            ws.fill_(0xFF if os.environ["MATCHA_POISON_WS"] == "nan" else 0x5B)
+        return ws
 
     def stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)

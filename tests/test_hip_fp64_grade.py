@@ -2,7 +2,13 @@
 Trainer.forward_backward step and the eval-mode model(x) of each case, every output within K = 8 times the fp32 oracle's own noise.
 The parity tests elsewhere allow 1e-4 (the north star); a kernel that silently loses a factor of 20 -- a dropped bf16 plane product,
 a tanh that is only accurate in absolute terms -- passes them and fails here.  Each case also asserts its kernel set (a size rule that
-moves a case onto other kernels fails it) and that its bound is tight enough to reject the three-product witness.  GPU only (-m gpu).
+moves a case onto other kernels fails it) and that its bound is tight enough to reject the three-product witness.
+
+The d = 64 table front end has three routes (model.hip: node_front_shape, the options disable_node_r / disable_node_front), and every case
+NAMES the one it runs (``Case.table``): the option it runs under and the node kernels it must / must not launch are derived from that name, for
+every case of the table.  Every graded condition of the large-batch table step -- default weights, the four stresses, the regression
+objective, L = 8, the separate tail, the first size past the small-batch kernels -- runs on all three routes from one batch and one set of
+references, and the size rule is crossed by size alone at wide_adj (3 300 / 3 400 rows).  GPU only (-m gpu).
 """
 import contextlib
 from dataclasses import dataclass, field, replace
@@ -32,6 +38,11 @@ _LAYERWISE = frozenset({"attn_fwd_kernel", "attn_bwd_kernel", "ln3_fwd_kernel", 
 _SORTED_TABLE = frozenset({"tg_hist_kernel", "tg_idscan_kernel", "tg_place_kernel", "tg_runsum_kernel", "tg_colscan_kernel"})
 _SMALL = frozenset({"fused_fwd32h_kernel", "plan_small_kernel"})
 _NOT_FUSED = frozenset({"fused_fwd32_kernel", "fused_fwd32h_kernel", "fused_bwdh_kernel", "enc128_fwd_kernel", "attn_fwd_wide_kernel"})
+# the table front end's route (Case.table): the node kernels that must / must not run, and the option that switches a node-shaped case there
+_NODE = frozenset({"node_scatter_kernel", "node_xhat_kernel", "node_r_kernel"})
+_TABLE_SETS = {"node_r": (_NODE, frozenset()), "node_rec": (_NODE - {"node_r_kernel"}, frozenset({"node_r_kernel"})),
+               "token": (frozenset(), _NODE), "": (frozenset(), _NODE)}
+_TABLE_OPTION = {"node_rec": "disable_node_r", "token": "disable_node_front"}
 
 
 @dataclass(frozen=True)
@@ -48,35 +59,39 @@ class Case:
     route: str = ""                        # "det" | "nolif" | "fourprod" | "layerwise"
     objective: str = "class"
     stress: str = ""                       # "small" | "sharp" | "saturated" | "hot"
+    # route of the d = 64 table front end: "node_r" (per node, r table) | "node_rec" (per node, r rows in the record: disable_node_r) | "token"
+    # (per token: disable_node_front, or with by_size a batch below the size rule and NO option); "": a case the rule cannot reach
+    table: str = ""
+    by_size: bool = False
     must: FrozenSet[str] = frozenset()
     must_not: FrozenSet[str] = frozenset()
     k_of: Dict[str, float] = field(default_factory=dict, hash=False, compare=False)
 
 
-T64 = Case("hg38_1mb", 64, "table", 81, must=_BIG64 | _FRONT64,
+T64 = Case("hg38_1mb", 64, "table", 81, table="node_r", must=_BIG64 | _FRONT64,
            must_not=_SMALL | _SORTED_TABLE | {"embed_fwd_kernel", "front_fwd_kernel", "head_bwd_kernel", "attn_fwd_kernel"})
 A64 = Case("hg38_1mb", 64, "adj", 82, must=_BIG64 | _ADJ64, must_not=_SMALL | {"adj_encode_fwd_kernel", "front_fwd3_kernel", "attn_fwd_kernel"})
 T128 = Case("c1", 128, "table", 83, ks=(2, 3, 4, 5, 6, 7, 8), rows_per_k=585, must=_ENC128,
             must_not={"attn_fwd_wide_kernel", "attn_bwd_wide_kernel", "attn_fwd_kernel", "attn_bwd_kernel"})
-_TINY = dict(batch_seed=1009, must=_SMALL | _FRONT64 | {"fused_bwdh_kernel"}, must_not={"fused_fwd32_kernel", "tail_bwd64_kernel"})
+_TINY = dict(batch_seed=1009, table="", must=_SMALL | _FRONT64 | {"fused_bwdh_kernel"}, must_not={"fused_fwd32_kernel", "tail_bwd64_kernel"})
 
 CASES = {
     "t64_big": T64,
-    "t64_det": replace(T64, route="det", must=T64.must | _SORTED_TABLE, must_not=T64.must_not - _SORTED_TABLE),
+    "t64_det": replace(T64, route="det", table="", must=T64.must | _SORTED_TABLE, must_not=T64.must_not - _SORTED_TABLE),
     "t64_nolif": replace(T64, route="nolif", must=(T64.must - {"tail_bwd64_kernel"}) | {"head_bwd_kernel"},
                          must_not=(T64.must_not - {"head_bwd_kernel"}) | {"tail_bwd64_kernel"}),
     # at embed_dim 64 both switches land on the layer-by-layer kernels with the reference's four products per head
-    "t64_fourprod": replace(T64, route="fourprod", must=_LAYERWISE, must_not=_BIG64 | _FRONT64 | _SMALL),
-    "t64_layerwise": replace(T64, route="layerwise", must=_LAYERWISE, must_not=_BIG64 | _FRONT64 | _SMALL),
+    "t64_fourprod": replace(T64, route="fourprod", table="", must=_LAYERWISE, must_not=_BIG64 | _FRONT64 | _SMALL),
+    "t64_layerwise": replace(T64, route="layerwise", table="", must=_LAYERWISE, must_not=_BIG64 | _FRONT64 | _SMALL),
     # the last batch size whose half tiles fit two per CU (the one-workgroup-per-half forward; the plan there is already the multi-launch
     # one) and the first that does not
-    "t64_edge-": replace(T64, rows="edge-", must={"fused_fwd32h_kernel", "fused_bwdh_kernel"} | _FRONT64, must_not={"fused_fwd32_kernel", "tail_bwd64_kernel"}),
+    "t64_edge-": replace(T64, rows="edge-", table="", must={"fused_fwd32h_kernel", "fused_bwdh_kernel"} | _FRONT64, must_not={"fused_fwd32_kernel", "tail_bwd64_kernel"}),
     "t64_edge+": replace(T64, rows="edge+"),
     # (a batch whose first rows let the witness show: at one to three rows its logit error is a matter of the rows drawn)
     "t64_tiny1": replace(T64, rows=1, **_TINY),
     "t64_tiny2": replace(T64, rows=2, **_TINY),
     "t64_tiny3": replace(T64, rows=3, **_TINY),
-    "t64_k8": Case("c23", 64, "table", 84, ks=(2, 3, 4, 5, 6, 7, 8), rows_per_k=585, L=8, must=T64.must, must_not=T64.must_not),
+    "t64_k8": Case("c23", 64, "table", 84, ks=(2, 3, 4, 5, 6, 7, 8), rows_per_k=585, L=8, table="node_r", must=T64.must, must_not=T64.must_not),
     "t64_nattr5": Case("c1", 64, "table", 85, rows_per_k=512, must={"embed_fwd_kernel", "embed_scatter_kernel", "fused_fwd32h_kernel",
                                                                      "fused_bwdh_kernel", "lnhat_bwd_kernel"}, must_not=_FRONT64),
     "a64_hg38": A64,
@@ -97,7 +112,21 @@ for _base in ("t64_big", "a64_hg38", "t128"):
         _c = CASES[_base]
         CASES[f"{_base}_{_s}"] = replace(_c, stress=_s, rows_per_k=3 * _c.rows_per_k if _s == "hot" else _c.rows_per_k)
 CASES["t128_hot"] = replace(CASES["t128_hot"], batch_seed=1101)          # (the default batch leaves the witness only 2.0x out)
-CASES["t64_big_hot_det"] = replace(CASES["t64_big_hot"], route="det", must=CASES["t64_det"].must, must_not=CASES["t64_det"].must_not)
+CASES["t64_big_hot_det"] = replace(CASES["t64_big_hot"], route="det", table="", must=CASES["t64_det"].must, must_not=CASES["t64_det"].must_not)
+# Every graded condition of the large-batch table step on the two other routes as well: same weights, batch and references (_data drops
+# ``table``), only the option differs.  At these sizes the rule picks the node route (20 481 >= 12 272 at hg38_1mb's 4 096 rows), so without
+# the counterparts the per-token kernels -- what every table with 4 (N + 1) > B L + 1 runs: front_bwd_kernel's float atomics into the table, > 10^4
+# addends into one row in `hot` -- and the node route's r-in-the-record backward would be graded at c23 with default weights only.
+TABLE_BASES = ("t64_big", "t64_big_small", "t64_big_sharp", "t64_big_saturated", "t64_big_hot", "r64", "t64_k8", "t64_nolif", "t64_edge+")
+for _base in TABLE_BASES:
+    assert CASES[_base].table == "node_r", _base
+    for _t in ("token", "node_rec"):
+        CASES[f"{_base}_{_t}"] = replace(CASES[_base], table=_t)
+# Both sides of the size rule reached by SIZE, no option set: wide_adj as a table layout has N + 1 = 4 157 rows, 4 (N + 1) = 16 628; 3 300 rows
+# (capacity 16 501) stay per token -- the one graded per-token workspace carved WITHOUT the node tables --, 3 400 rows (17 001) take the node route
+# (tests/test_hip_node_front.py::test_size_rule_and_exclusions).  n_attr is 8 there.
+CASES["t64_wide_below"] = replace(T64, layout="wide_adj", seed=91, rows_per_k=825, table="token", by_size=True)
+CASES["t64_wide_above"] = replace(T64, layout="wide_adj", seed=91, rows_per_k=850, table="node_r")
 
 RESULTS = {}
 
@@ -108,7 +137,7 @@ def _ratio_table():
     if RESULTS:
         print("\nfp32 grade: worst e(HIP) / noise per case (step: logits, losses, every gradient; eval: model(x) logits)")
         for name, (step, ev, wit) in RESULTS.items():
-            print(f"  {name:22s} step {step:5.2f}   eval {ev:5.2f}   witness {wit:6.1f} x bound")
+            print(f"  {name:26s} step {step:5.2f}   eval {ev:5.2f}   witness {wit:6.1f} x bound")
 
 
 _DATA = {}
@@ -116,7 +145,7 @@ _DATA = {}
 
 def _data(c: Case):
     """(sd, fe, x, y, w, chrom, references, three-product witness) of a case; cached, several routes share one batch."""
-    key = replace(c, route="", must=frozenset(), must_not=frozenset())
+    key = replace(c, route="", table="", by_size=False, must=frozenset(), must_not=frozenset())
     if key in _DATA:
         return _DATA[key]
     num = synth.LAYOUTS[c.layout]
@@ -157,6 +186,15 @@ def test_step_and_eval_at_fp32_grade(name):
             m.p = 0.0
     clf.train()
     switch = {"fourprod": "disable_merged", "layerwise": "disable_fused"}.get(c.route)
+    # the table route: named by every case, reachable only by the fused d = 64 table step, switched by its option unless the size decides
+    assert c.table in _TABLE_SETS and (not c.by_size or c.table == "token"), (name, c.table)
+    assert not c.table or (c.d == 64 and c.mode == "table" and c.route in ("", "nolif")), (name, c.table)
+    must_node, must_not_node = _TABLE_SETS[c.table]
+    table_switch = None if c.by_size else _TABLE_OPTION.get(c.table)
+    assert not (switch and table_switch)
+    switch = switch or table_switch
+    if c.layout == "wide_adj" and c.mode == "table":
+        assert (len(x) * x.shape[1] + 1 >= 4 * (int(np.sum(synth.LAYOUTS[c.layout])) + 1)) == (c.table == "node_r"), (name, x.shape)
     with (_lib.option(switch) if switch else contextlib.nullcontext()):
         tr = Trainer(clf, lr=1e-3, deterministic=(c.route == "det"), objective=c.objective)
         if c.route == "nolif":
@@ -174,12 +212,13 @@ def test_step_and_eval_at_fp32_grade(name):
         with torch.no_grad():
             lg_eval = clf(xd).cpu().double().numpy()
     ran = {k for k, n in log.counts.items() if n > 0}
-    print(f"{name}: B = {len(x)}, L = {x.shape[1]}, kernels {sorted(ran)}")
+    print(f"{name}: B = {len(x)}, L = {x.shape[1]}, table route {c.table or '-'}, kernels {sorted(ran)}")
     ratio = G.assert_grade(f"{name} step", G.grade(got, ref, c.k_of))
     ratio_eval = G.assert_grade(f"{name} eval", G.logit_rows(lg_eval, ref, c.k_of.get("logits", G.K)))
     # the bound must be tight enough to reject the three-product witness (its forward is enough)
     wit_over = max(r.err / (r.k * r.noise) for r in G.logit_rows(wit.logits, ref, c.k_of.get("logits", G.K)))
     RESULTS[name] = (ratio, ratio_eval, wit_over)
     assert wit_over >= 2.0, (name, wit_over)
-    assert set(c.must) <= ran, (name, sorted(set(c.must) - ran), sorted(ran))
-    assert not (set(c.must_not) & ran), (name, sorted(set(c.must_not) & ran))
+    must, must_not = set(c.must) | must_node, set(c.must_not) | must_not_node
+    assert must <= ran, (name, sorted(must - ran), sorted(ran))
+    assert not (must_not & ran), (name, sorted(must_not & ran))
