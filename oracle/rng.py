@@ -15,6 +15,12 @@ the sampler's accept/reject rules) is what is checked against the reference.
     lowbias32(x):  x ^= x>>16; x *= 0x7feb352d; x ^= x>>15; x *= 0x846ca68b; x ^= x>>16
     key(seed64, stream) = lowbias32(seed_lo ^ lowbias32(seed_hi ^ lowbias32(stream + 0x9E3779B9)))
     rand_u32(key, hi, lo) = lowbias32(lo ^ lowbias32(hi ^ key))
+
+The dropout keep threshold is part of the specification: the C ABI carries p as a
+``float``, and common.hpp's dropout_threshold(float p) takes floor((double)p * 2^32) of
+THAT value, so ``dropout_threshold`` here rounds p through float32 first.  The double
+0.3 gives 1288490188, the float 0.3 gives 1288490240: a draw in between is kept by one
+and dropped by the other (about 1.2e-8 of all elements, an O(1) error in one logit).
 """
 import numpy as np
 
@@ -53,8 +59,8 @@ def rand_u32(key, hi, lo):
 
 
 def dropout_threshold(p):
-    """keep  <=>  rand_u32 >= threshold ;  threshold = floor(p * 2^32)."""
-    return np.uint32(min(int(float(p) * 4294967296.0), 0xFFFFFFFF))
+    """keep  <=>  rand_u32 >= threshold ;  threshold = floor(float32(p) * 2^32), the product taken in double (exact)."""
+    return np.uint32(min(int(float(np.float32(p)) * 4294967296.0), 0xFFFFFFFF))
 
 
 def dropout_mask(seed, stream, p, n_rows, n_cols, row_ids=None):

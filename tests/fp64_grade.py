@@ -28,6 +28,7 @@ import torch.nn.functional as F
 
 from matcha_amd import synth
 from oracle import hypersagnn as O
+from oracle import rng as R
 from tests.helpers import logit_err
 
 K = 8.0
@@ -112,10 +113,12 @@ def main_loss_name(objective):
 
 
 def oracle_step(sd, fe, x, y, w, *, alpha=1.0, beta=0.001, chrom=0, dtype=torch.float32, perm=None, ops=O.TORCH_OPS,
-                objective="class", backward=True) -> StepOut:
-    """One dropout-free step of the oracle in ``dtype`` on the state dict ``sd`` (numpy, fp32) and the batch x [B, L], y / w [B]:
+                objective="class", backward=True, masks=None) -> StepOut:
+    """One step of the oracle in ``dtype`` on the state dict ``sd`` (numpy, fp32) and the batch x [B, L], y / w [B]:
     loss = objective * alpha + recon * beta (bce: main.py:56; regress: mse of softplus, main.py:60-66).  ``perm`` permutes the batch
-    rows before the step; the logits come back in the original order."""
+    rows before the step; the logits come back in the original order.  ``masks`` (None: dropout-free) are the float32 multiplier masks of
+    ``step_masks``, rows in token-slot order b L + l: they are inputs like the weights -- the f32 value 1 / (1 - p) is cast to ``dtype``, exact
+    in fp64 -- and are permuted with their rows."""
     P = {k: torch.from_numpy(np.array(v)).to(dtype).requires_grad_(backward and k not in FROZEN_NAMES) for k, v in sd.items()}
     fe = fe.to(dtype)
     x, y = torch.as_tensor(x), torch.as_tensor(y).reshape(-1, 1).to(dtype)
@@ -123,8 +126,12 @@ def oracle_step(sd, fe, x, y, w, *, alpha=1.0, beta=0.001, chrom=0, dtype=torch.
     if perm is not None:
         p = torch.as_tensor(perm)
         x, y, w = x[p], y[p], (None if w is None else w[p])
+    if masks is not None:
+        B, L = x.shape
+        masks = {k: torch.from_numpy(np.asarray(m, dtype=np.float32)).to(dtype).view(B, L, -1) for k, m in masks.items()}
+        masks = {k: (m if perm is None else m[p]).reshape(B * L, -1) for k, m in masks.items()}
     with torch.set_grad_enabled(backward):
-        logits, recon = O.classifier_forward(P, fe, x, random_chrom=chrom, ops=ops)
+        logits, recon = O.classifier_forward(P, fe, x, random_chrom=chrom, ops=ops, masks=masks)
         if objective == "regress":
             main = F.mse_loss(F.softplus(logits), y)
         else:
@@ -142,6 +149,19 @@ def oracle_step(sd, fe, x, y, w, *, alpha=1.0, beta=0.001, chrom=0, dtype=torch.
     return StepOut(lg, {main_loss_name(objective): float(main.detach()), "recon": float(recon.detach().reshape(-1)[0])}, grads)
 
 
+def step_masks(seed, ps, n_tokens, d, num=None, wrap=None):
+    """The multiplier masks {"fc1", "pff"[, "adj"]: float32 [n_tokens, d | max(num)]} of a step with dropout seed ``seed`` and
+    ps = (p_adj, p_fc1, p_pff) (Classifier._dropout_p()), as the kernels draw them (oracle/rng.py): the counter's high word is the token slot
+    b L + l over all B L slots, padding included.  ``num`` is the layout on the adj front end, None on the table front end.  ``wrap`` is
+    applied to each mask (tests/state_twin.py::call_masks: torch.from_numpy).  A Trainer(clf, base_seed=S) draws its first step with S + 1."""
+    p_adj, p_fc1, p_pff = ps
+    masks = {"fc1": R.dropout_mask(seed, R.STREAM_DROP_FC1, p_fc1, n_tokens, d),
+             "pff": R.dropout_mask(seed, R.STREAM_DROP_PFF, p_pff, n_tokens, d)}
+    if num is not None:
+        masks["adj"] = R.dropout_mask(seed, R.STREAM_DROP_ADJ, p_adj, n_tokens, int(max(num)))
+    return {k: wrap(m) for k, m in masks.items()} if wrap else masks
+
+
 @dataclass
 class References:
     r64: StepOut
@@ -150,7 +170,7 @@ class References:
 
 
 def references(sd, fe, x, y, w, *, perm_seed=0, **kw) -> References:
-    """R64, R32a and R32b of one step (module docstring)."""
+    """R64, R32a and R32b of one step (module docstring); ``masks=`` of oracle_step goes to all three."""
     perm = np.random.default_rng(perm_seed).permutation(len(x))
     return References(oracle_step(sd, fe, x, y, w, dtype=torch.float64, **kw), oracle_step(sd, fe, x, y, w, **kw),
                       oracle_step(sd, fe, x, y, w, perm=perm, **kw))
@@ -254,6 +274,24 @@ def saturated_logits(sd, fe, x, chrom=0, target=40.0):
     s = np.float32(target / float(lg.abs().max()))
     out = dict(sd)
     for k in ("pff_classifier.PWF_Conv0.weight", "pff_classifier.PWF_Conv0.bias"):
+        out[k] = (np.asarray(sd[k]) * s).astype(np.float32)
+    return out
+
+
+def saturated_pff(sd, fe, x, chrom=0, target=4.0):
+    """encode1.pff_n1's first layer (weight and bias) scaled so that the 99th percentile of |pre-activation| over the batch's real tokens is
+    ``target``: at 4, tanh' = 1 - t^2 ~ 1e-3, where a backward that recovers t from a stored t / (1 - p) as (t / (1 - p)) (1 - p) loses the
+    most.  The scale is taken from the dropout-free forward."""
+    pp = "encode1.pff_n1.PWF_Conv0."
+    with torch.no_grad():
+        P = {k: torch.from_numpy(np.array(v)) for k, v in sd.items()}
+        xt = torch.as_tensor(x)
+        _, _, mid = O.classifier_forward(P, fe, xt, random_chrom=chrom, return_intermediates=True)
+        pre = mid["y"] @ P[pp + "weight"][:, :, 0].t() + P[pp + "bias"]
+        q = float(np.quantile(pre[xt != 0].abs().numpy().astype(np.float64), 0.99))
+    s = np.float32(target / q)
+    out = dict(sd)
+    for k in (pp + "weight", pp + "bias"):
         out[k] = (np.asarray(sd[k]) * s).astype(np.float32)
     return out
 

@@ -301,11 +301,7 @@ def call_masks(cfg: Config, clf, seed: int, n_tokens: int):
     p_adj, p_fc1, p_pff = clf._dropout_p()
     if not clf.training or max(p_adj, p_fc1, p_pff) <= 0:
         return None
-    masks = {"fc1": torch.from_numpy(R.dropout_mask(seed, R.STREAM_DROP_FC1, p_fc1, n_tokens, cfg.d)),
-             "pff": torch.from_numpy(R.dropout_mask(seed, R.STREAM_DROP_PFF, p_pff, n_tokens, cfg.d))}
-    if cfg.mode == "adj":
-        masks["adj"] = torch.from_numpy(R.dropout_mask(seed, R.STREAM_DROP_ADJ, p_adj, n_tokens, max(cfg.num)))
-    return masks
+    return G.step_masks(seed, (p_adj, p_fc1, p_pff), n_tokens, cfg.d, cfg.num if cfg.mode == "adj" else None, wrap=torch.from_numpy)
 
 
 def ran_kernels(log) -> set:

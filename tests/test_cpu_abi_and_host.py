@@ -204,6 +204,14 @@ def test_rng_spec_is_stable():
     m = R.dropout_mask(7, R.STREAM_DROP_PFF, 0.4, 2000, 16)
     assert set(np.unique(m).tolist()) == {0.0, np.float32(1.0) / (np.float32(1.0) - np.float32(0.4))}
     assert abs(float((m == 0).mean()) - 0.4) < 0.02
+    # the keep threshold is floor((double)(float)p * 2^32), what common.hpp::dropout_threshold computes from the ABI's float p -- not
+    # floor(p * 2^32) of the Python double (858993459 / 1288490188 / 1717986918 / 3865470566 for the first four)
+    want = {0.2: 858993472, 0.3: 1288490240, 0.4: 1717986944, 0.9: 3865470464, 0.5: 1 << 31}
+    assert {p: int(R.dropout_threshold(p)) for p in want} == want
+    # (seed 13, fc1, token slot 75458, feature 5) draws 1288490204, between the two thresholds of 0.3: dropped
+    assert int(R.rand_u32(R.make_key(13, R.STREAM_DROP_FC1), 75458, 5)) == 1288490204
+    assert R.dropout_mask(13, R.STREAM_DROP_FC1, 0.3, 1, 6, row_ids=[75458])[0, 5] == 0.0
+    assert R.dropout_mask(13, R.STREAM_DROP_FC1, 0.3, 75459, 6)[75458, 5] == 0.0
 
 
 def test_attribute_structure_detection_is_exact():

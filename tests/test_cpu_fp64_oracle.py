@@ -2,7 +2,8 @@
 
 (a) At three shapes, a third legitimate fp32 summation order (the oracle on another row permutation) passes the criterion, and the
     three-product witness -- every product as Ah Bh + Ah Bm + Am Bh, its backward too -- fails it by at least 2x on the logits and on
-    the gradients of the products it replaces.  The fast_tanh witness fails it on a small-amplitude model.
+    the gradients of the products it replaces.  The fast_tanh witness fails it on a small-amplitude model.  The same with dropout ON
+    (masks injected into every reference), plus: all-ones masks change nothing, a wrong mask is rejected.
 (b) The oracle's formulation is pinned at fp32 grade, not just at the 2e-5 of tests/test_oracle_golden.py: every reference fixture's
     fp32 output (in the role the HIP path plays on the GPU) meets the criterion against the fp64 oracle.  CPU only.
 """
@@ -33,17 +34,62 @@ def _power_case(name):
     return sd, fe, x, y, w, seed % fe.n_chrom
 
 
-@pytest.mark.parametrize("name", sorted(POWER))
-def test_reordered_fp32_passes_and_the_three_product_witness_fails(name):
-    sd, fe, x, y, w, chrom = _power_case(name)
-    ref = G.references(sd, fe, x, y, w, chrom=chrom)
-    third = G.oracle_step(sd, fe, x, y, w, chrom=chrom, perm=np.random.default_rng(1).permutation(len(x)))
-    G.assert_grade(f"{name} fp32, third row order", G.grade(third, ref))
-    rows = {r.what: r for r in G.grade(G.oracle_step(sd, fe, x, y, w, chrom=chrom, ops=G.THREE_PRODUCT), ref)}
+def _power_masks(name, x, ps, seed=77):
+    """The masks of a step on POWER[name]'s batch ``x`` with ps = (p_adj, p_fc1, p_pff) and dropout seed ``seed``."""
+    layout, d, mode = POWER[name][:3]
+    return G.step_masks(seed, ps, x.size, d, synth.LAYOUTS[layout] if mode == "adj" else None)
+
+
+def _assert_power(label, sd, fe, x, y, w, chrom, masks=None):
+    """A third row order of the fp32 oracle passes the criterion, the three-product witness is >= 2x over its bound on the logits and on
+    every one of WITNESS_TARGETS; returns the references."""
+    ref = G.references(sd, fe, x, y, w, chrom=chrom, masks=masks)
+    third = G.oracle_step(sd, fe, x, y, w, chrom=chrom, perm=np.random.default_rng(1).permutation(len(x)), masks=masks)
+    G.assert_grade(f"{label} fp32, third row order", G.grade(third, ref))
+    rows = {r.what: r for r in G.grade(G.oracle_step(sd, fe, x, y, w, chrom=chrom, ops=G.THREE_PRODUCT, masks=masks), ref)}
     over = {t: rows[t].err / (rows[t].k * rows[t].noise) for t in ["logits", "logits (element-wise)"] + WITNESS_TARGETS}
     over["logits"] = max(over.pop("logits"), over.pop("logits (element-wise)"))
-    print(f"{name}: three-product witness, e / bound: " + ", ".join(f"{t.split('.')[-2] if '.' in t else t} {v:.1f}" for t, v in over.items()))
+    print(f"{label}: three-product witness, e / bound: " + ", ".join(f"{t.split('.')[-2] if '.' in t else t} {v:.1f}" for t, v in over.items()))
     assert min(over.values()) >= 2.0, over
+    return ref
+
+
+@pytest.mark.parametrize("name", sorted(POWER))
+def test_reordered_fp32_passes_and_the_three_product_witness_fails(name):
+    _assert_power(name, *_power_case(name))
+
+
+# The criterion under dropout: the masks are inputs of the step (float32 multipliers 0 or 1 / (1 - p), exact in fp64), so the noise floor and
+# the witness's margin must survive them -- at the model's default p and at p no float represents, where nine tenths of pff_n1's hidden
+# layer is dropped and the rest scaled by 10.
+P_DEFAULT, P_HIGH = (0.2, 0.3, 0.4), (0.6, 0.7, 0.9)
+
+
+@pytest.mark.parametrize("name,ps", [(n, P_DEFAULT) for n in sorted(POWER)] + [("hg38_table_d64", P_HIGH)])
+def test_criterion_has_power_with_dropout_on(name, ps):
+    sd, fe, x, y, w, chrom = _power_case(name)
+    _assert_power(f"{name} p {ps}", sd, fe, x, y, w, chrom, masks=_power_masks(name, x, ps))
+
+
+@pytest.mark.parametrize("name", ["hg38_table_d64", "wide_adj_d64"])
+def test_masks_reach_every_reference(name):
+    """All-ones masks (every p = 0) are the mask-free step bit for bit, in every reference; and a candidate that differs from the references
+    in ONE mask only (another seed's) fails the criterion, whichever mask it is -- a reference that dropped a mask, or left it in place
+    under the row permutation, would make the three disagree or the candidate pass."""
+    sd, fe, x, y, w, chrom = _power_case(name)
+    plain = G.references(sd, fe, x, y, w, chrom=chrom)
+    ones = G.references(sd, fe, x, y, w, chrom=chrom, masks=_power_masks(name, x, (0.0, 0.0, 0.0)))
+    for a, b in zip((plain.r64, plain.r32a, plain.r32b), (ones.r64, ones.r32a, ones.r32b)):
+        assert np.array_equal(a.logits, b.logits) and a.losses == b.losses and a.grads.keys() == b.grads.keys()
+        assert all((a.grads[n] is None and b.grads[n] is None) or np.array_equal(a.grads[n], b.grads[n]) for n in a.grads)
+    masks, other = _power_masks(name, x, P_DEFAULT), _power_masks(name, x, P_DEFAULT, seed=78)
+    ref = G.references(sd, fe, x, y, w, chrom=chrom, masks=masks)
+    G.assert_grade(f"{name} own masks", G.grade(G.oracle_step(sd, fe, x, y, w, chrom=chrom, masks=masks), ref))
+    for key in masks:
+        rows = G.grade(G.oracle_step(sd, fe, x, y, w, chrom=chrom, masks={**masks, key: other[key]}), ref)
+        worst = max(rows, key=lambda r: r.ratio)
+        print(f"{name}: {key} mask of another seed, worst e / bound {worst.err / (worst.k * worst.noise):.3g} ({worst.what})")
+        assert worst.err >= 100.0 * worst.k * worst.noise, (key, worst.what, worst.ratio)
 
 
 def test_fast_tanh_witness_fails_at_small_amplitude():

@@ -1,5 +1,8 @@
 """Every kernel route of the training step held to fp32 grade against the fp64 oracle (tests/fp64_grade.py): one dropout-free
 Trainer.forward_backward step and the eval-mode model(x) of each case, every output within K = 8 times the fp32 oracle's own noise.
+The ``_drop`` / ``_highp`` / ``saturated_pff`` cases run the same step with dropout ON -- what the benchmark and every published number run --
+against the oracle with the kernels' own masks injected (oracle/rng.py, G.step_masks): the masks' regeneration in the backward's epilogues,
+the tanh recovered from the stored post-dropout H1, gemm_wide's and the layer-by-layer kernels' dropout epilogues are dead code at p = 0.
 The parity tests elsewhere allow 1e-4 (the north star); a kernel that silently loses a factor of 20 -- a dropped bf16 plane product,
 a tanh that is only accurate in absolute terms -- passes them and fails here.  Each case also asserts its kernel set (a size rule that
 moves a case onto other kernels fails it) and that its bound is tight enough to reject the three-product witness.
@@ -12,7 +15,7 @@ references, and the size rule is crossed by size alone at wide_adj (3 300 / 3 40
 """
 import contextlib
 from dataclasses import dataclass, field, replace
-from typing import Dict, FrozenSet, Tuple
+from typing import Dict, FrozenSet, Optional, Tuple
 
 import numpy as np
 import pytest
@@ -58,7 +61,9 @@ class Case:
     batch_seed: int = 0                    # 0: seed + 500
     route: str = ""                        # "det" | "nolif" | "fourprod" | "layerwise"
     objective: str = "class"
-    stress: str = ""                       # "small" | "sharp" | "saturated" | "hot"
+    stress: str = ""                       # "small" | "sharp" | "saturated" | "hot" | "saturated_pff"
+    drop: Optional[Tuple[float, float, float]] = None      # (p_adj, p_fc1, p_pff): the step runs with dropout ON; None: every Dropout.p = 0
+    drop_seed: int = 0                     # the step's dropout seed (Trainer base_seed = drop_seed - 1); 0: seed + 700
     # route of the d = 64 table front end: "node_r" (per node, r table) | "node_rec" (per node, r rows in the record: disable_node_r) | "token"
     # (per token: disable_node_front, or with by_size a batch below the size rule and NO option); "": a case the rule cannot reach
     table: str = ""
@@ -128,6 +133,29 @@ for _base in TABLE_BASES:
 CASES["t64_wide_below"] = replace(T64, layout="wide_adj", seed=91, rows_per_k=825, table="token", by_size=True)
 CASES["t64_wide_above"] = replace(T64, layout="wide_adj", seed=91, rows_per_k=850, table="node_r")
 
+# ---- dropout ON -----------------------------------------------------------------------------------------------------------------------------
+# Twins of the cases above at the model's default p (same shapes: already the smallest that reach each kernel set), the kernel sets, the table
+# route and the witness assertion unchanged.  The high-p twins take p that no float represents, the widest gap between floor(p 2^32) of the double
+# and of the float (oracle/rng.py) and (1 / (1 - p)) (1 - p) furthest from 1.
+P_DEFAULT, P_HIGH = (0.2, 0.3, 0.4), (0.6, 0.7, 0.9)
+DROP_BASES = ("t64_big", "t64_big_token", "t64_big_node_rec", "t64_det", "t64_nolif", "t64_fourprod", "t64_layerwise", "t64_edge-", "t64_edge+",
+              "t64_tiny2", "t64_k8", "t64_nattr5", "t64_wide_below", "a64_hg38", "a64_wide", "t128", "a128_wide", "t256", "t16", "a32", "r64")
+for _base in DROP_BASES:
+    CASES[f"{_base}_drop"] = replace(CASES[_base], drop=P_DEFAULT)
+for _base in ("t64_big", "a64_hg38", "t128"):
+    CASES[f"{_base}_highp"] = replace(CASES[_base], drop=P_HIGH)
+# pff_n1's first layer saturated (G.saturated_pff): tail_bwd64_kernel (t64_big) and the in-kernel tail's own copy of that code
+# (fused_fwd32_tail.hpp: t64_nolif, t64_edge-) compute 1 - t^2 from t = H1 (1 - p_pff), H1 stored AFTER the dropout, where 1 - t^2 is ~1e-3
+for _base in ("t64_big", "t64_nolif", "t64_edge-"):
+    CASES[f"{_base}_saturated_pff_drop"] = replace(CASES[_base], stress="saturated_pff", drop=P_DEFAULT)
+CASES["t64_big_saturated_pff"] = replace(CASES["t64_big"], stress="saturated_pff")              # the control: the same stress, dropout-free
+
+
+def _drop_ps(c: Case):
+    """(p_adj, p_fc1, p_pff) as Classifier._dropout_p() must report them for the case (the table front end has no adj dropout)."""
+    return (c.drop[0] if c.mode == "adj" else 0.0, c.drop[1], c.drop[2])
+
+
 RESULTS = {}
 
 
@@ -144,7 +172,8 @@ _DATA = {}
 
 
 def _data(c: Case):
-    """(sd, fe, x, y, w, chrom, references, three-product witness) of a case; cached, several routes share one batch."""
+    """(sd, fe, x, y, w, chrom, references, three-product witness, the eval logits' references) of a case; cached, several routes share
+    one batch.  With ``drop`` the step's references and the witness get the step's masks, the eval references stay mask-free."""
     key = replace(c, route="", table="", by_size=False, must=frozenset(), must_not=frozenset())
     if key in _DATA:
         return _DATA[key]
@@ -164,14 +193,20 @@ def _data(c: Case):
         sd = G.saturated_logits(sd, fe, x, chrom)
         w = w.copy()
         w[::5] = 0.0
+    elif c.stress == "saturated_pff":
+        sd = G.saturated_pff(sd, fe, x, chrom)
     elif c.stress == "hot":
         x = G.hot_node(x, 0.85)                             # 85 % of 12 285 - 12 288 rows: > 10^4 addends into one table row
     if c.objective == "regress":
         y = np.where(y > 0, w, 0.0).astype(np.float32)       # positive rows carry a target in [0.5, 4), negatives 0
         w = None
-    ref = G.references(sd, fe, x, y, w, chrom=chrom, objective=c.objective)
-    wit = G.oracle_step(sd, fe, x, y, w, chrom=chrom, objective=c.objective, ops=G.THREE_PRODUCT, backward=False)
-    _DATA[key] = (sd, fe, x, y, w, chrom, ref, wit)
+    masks, ref_eval = None, None
+    if c.drop is not None:
+        masks = G.step_masks(c.drop_seed or c.seed + 700, _drop_ps(c), x.size, c.d, num if c.mode == "adj" else None)
+        ref_eval = G.references(sd, fe, x, y, w, chrom=chrom, objective=c.objective, backward=False)      # eval mode draws no mask
+    ref = G.references(sd, fe, x, y, w, chrom=chrom, objective=c.objective, masks=masks)
+    wit = G.oracle_step(sd, fe, x, y, w, chrom=chrom, objective=c.objective, ops=G.THREE_PRODUCT, backward=False, masks=masks)
+    _DATA[key] = (sd, fe, x, y, w, chrom, ref, wit, ref_eval or ref)
     return _DATA[key]
 
 
@@ -179,11 +214,18 @@ def _data(c: Case):
 def test_step_and_eval_at_fp32_grade(name):
     from matcha_amd.engine import Trainer
     c = CASES[name]
-    sd, fe, x, y, w, chrom, ref, wit = _data(c)
+    sd, fe, x, y, w, chrom, ref, wit, ref_eval = _data(c)
     clf, _ = hip_model(synth.LAYOUTS[c.layout], c.d, c.mode, c.seed, sd=sd)
     for m in clf.modules():
         if isinstance(m, torch.nn.Dropout):
             m.p = 0.0
+    base_seed = 0
+    if c.drop is not None:
+        for m, p in zip((getattr(clf.node_embedding, "dropout", None), clf.encode1.mul_head_attn.dropout, clf.encode1.pff_n1.dropout), c.drop):
+            if m is not None:
+                m.p = p
+        assert clf._dropout_p() == _drop_ps(c), (name, clf._dropout_p())       # the masks of _data are the model's own p
+        base_seed = (c.drop_seed or c.seed + 700) - 1                          # the first step draws with base_seed + 1
     clf.train()
     switch = {"fourprod": "disable_merged", "layerwise": "disable_fused"}.get(c.route)
     # the table route: named by every case, reachable only by the fused d = 64 table step, switched by its option unless the size decides
@@ -196,7 +238,7 @@ def test_step_and_eval_at_fp32_grade(name):
     if c.layout == "wide_adj" and c.mode == "table":
         assert (len(x) * x.shape[1] + 1 >= 4 * (int(np.sum(synth.LAYOUTS[c.layout])) + 1)) == (c.table == "node_r"), (name, x.shape)
     with (_lib.option(switch) if switch else contextlib.nullcontext()):
-        tr = Trainer(clf, lr=1e-3, deterministic=(c.route == "det"), objective=c.objective)
+        tr = Trainer(clf, lr=1e-3, deterministic=(c.route == "det"), objective=c.objective, base_seed=base_seed)
         if c.route == "nolif":
             tr.loss_in_forward = False
         xd = torch.from_numpy(x).cuda().contiguous()
@@ -214,7 +256,7 @@ def test_step_and_eval_at_fp32_grade(name):
     ran = {k for k, n in log.counts.items() if n > 0}
     print(f"{name}: B = {len(x)}, L = {x.shape[1]}, table route {c.table or '-'}, kernels {sorted(ran)}")
     ratio = G.assert_grade(f"{name} step", G.grade(got, ref, c.k_of))
-    ratio_eval = G.assert_grade(f"{name} eval", G.logit_rows(lg_eval, ref, c.k_of.get("logits", G.K)))
+    ratio_eval = G.assert_grade(f"{name} eval", G.logit_rows(lg_eval, ref_eval, c.k_of.get("logits", G.K)))
     # the bound must be tight enough to reject the three-product witness (its forward is enough)
     wit_over = max(r.err / (r.k * r.noise) for r in G.logit_rows(wit.logits, ref, c.k_of.get("logits", G.K)))
     RESULTS[name] = (ratio, ratio_eval, wit_over)

@@ -142,6 +142,35 @@ def test_gemm_epilogues():
     assert (out2 - ref2).abs().max() <= 2e-5 * max(1.0, ref2.abs().max())
 
 
+# (seed, row, column) of an element whose draw lies between floor((double)(float)0.9 * 2^32) = 3865470464, the kernels' keep threshold, and
+# floor(0.9 * 2^32) = 3865470566 of the Python double: the first hit of
+#   for seed in range(1, 5000): r = R.rand_u32(R.make_key(seed, R.STREAM_DROP_FC1), arange(4000)[:, None], arange(64)[None, :]); 3865470464 <= r < 3865470566
+_THRESHOLD_GAP = (75, 1987, 7, 3865470561)
+
+
+def test_gemm_dropout_pattern_is_the_specifications_at_a_threshold_gap():
+    """One EPI_DROPOUT GEMM whose zero pattern equals oracle/rng.py's dropout_mask bit for bit at p = 0.9, a p no float represents, with an
+    element in the tested rows that the float's threshold keeps and the double's would drop: the specification takes the threshold of
+    float32(p), as common.hpp::dropout_threshold does with the ABI's float."""
+    seed_v, row, col, draw = _THRESHOLD_GAP
+    M, N, K, p = 4000, 64, 64, 0.9
+    assert int(R.rand_u32(R.make_key(seed_v, R.STREAM_DROP_FC1), row, col)) == draw and row < M and col < N
+    assert int(R.dropout_threshold(p)) == 3865470464 <= draw < int(p * 4294967296.0) == 3865470566
+    g = torch.Generator().manual_seed(5)
+    A, W = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) * 0.2
+    seed = torch.tensor([seed_v], dtype=torch.int64).to(DEV)
+    epi = _lib.GemmEpilogue()
+    epi.flags, epi.seed = _lib.EPI_DROPOUT, seed.data_ptr()
+    epi.stream_id, epi.p_drop, epi.aux_scale = R.STREAM_DROP_FC1, p, 1.0
+    out = _gemm(_lib.GEMM_NT, A.to(DEV), W.to(DEV), M, N, K, epi=epi).cpu()
+    mask = torch.from_numpy(R.dropout_mask(seed_v, R.STREAM_DROP_FC1, p, M, N))
+    lin = (A.double() @ W.double().t()).float()
+    assert float(lin.abs().min()) > 0                                   # a zero of the output is a dropped element
+    assert mask[row, col] != 0 and out[row, col] != 0                   # kept: the draw is at or above the float's threshold
+    assert torch.equal(out == 0, mask == 0)
+    assert (out - lin * mask).abs().max() <= 2e-5 * float((lin * mask).abs().max())
+
+
 @pytest.mark.parametrize("M,N,K", [(300, 128, 128), (1000, 1024, 128), (130, 128, 1024)])
 def test_gemm_wide_tiles_equal_narrow_tiles_and_epilogues(M, N, K):
     """gemm_wide.hip against the 64-wide kernels it replaces at embed_dim >= 128 (option disable_wide_gemm) with the epilogues
