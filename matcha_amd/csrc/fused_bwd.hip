@@ -132,6 +132,84 @@ __device__ __forceinline__ void attn_row8_kv(const float* __restrict__ Qs, const
   }
 }
 
+// The row phase of the VALUE-TABLE instance (node route): y_j = M_h x_hat_j is gathered per node (Ys), so
+//   d_j = dz_i . x_hat_j = dDyn_i . y_j,   d_pad = dDyn_i . y_pad
+// needs neither dZ nor Z.  TWO passes: the y rows give d_j and sig, then the x_hat rows take dS_ij directly,
+//   d r_i = sum_j dS_ij x_hat_j + dS_i,pad x_hat_pad
+// -- no z sum (Z is never formed), no A - sig z cancellation, eight packed operations per key instead of twelve and one running sum alive
+// per pass.  (The one-pass form -- A - sig z with the y row read next to the x_hat row -- was measured in the same call: step 1.189-1.192 ms
+// against 1.176-1.181 ms for this one, parent 1.200-1.204 ms; profiles/r10_node_v.md.)
+// accU += n_pad p_i,pad dDyn_i (u_pad: what the padding key's VALUE contributes to dM_h and to its own d x_hat).
+#define FB_PIN1(addr, s) asm volatile("" : "+v"(addr), "+v"(s))
+template <int ML>
+__device__ __forceinline__ void attn_row8_v(const float* __restrict__ Qs, const float* __restrict__ Xs, const float* __restrict__ Ys, const float* __restrict__ Ds,
+                                            const float* __restrict__ xpad, const float* __restrict__ ypad, const float* __restrict__ Ps, float* __restrict__ dSs,
+                                            int li, int li0, int k, int n_pad, int sub, float inv_temp, V8& gq, V8& accK, V8& accU) {
+  const float padf = (float)n_pad;
+  const bool hp = n_pad > 0;
+  float p[ML], ds[ML], pp;
+  {
+    const float4 pa = *reinterpret_cast<const float4*>(&Ps[li * 8]), pb = *reinterpret_cast<const float4*>(&Ps[li * 8 + 4]);
+    const float w[8] = {pa.x, pa.y, pa.z, pa.w, pb.x, pb.y, pb.z, pb.w};
+#pragma unroll
+    for (int j = 0; j < ML; ++j) p[j] = (j < k) ? w[j] : 0.f;
+    pp = hp ? w[7] : 0.f;
+  }
+  const float ppf = padf * pp;
+  const int ro0 = li0 * kLd + 8 * sub;                   // row j (clamped to the hyperedge): ro0 + min(j, k - 1) rows
+  const V8 go = ld8(&Ds[li * kLd + 8 * sub]);
+  const float dsp_raw = group_sum8_dpp(dot8(go, ld8(ypad + 8 * sub)));
+  float sig = ppf * dsp_raw;
+  {
+    V8 vn = ld8(&Ys[ro0]), vn2 = ld8(&Ys[ro0 + (1 < k ? 1 : 0) * kLd]);      // two rows in flight
+    float part = 0.f;                                      // the pin chains the load of row j + 2 to row j - 1's dot product, NOT to its DPP reduction
+#pragma unroll
+    for (int j = 0; j < ML; ++j) {
+      const V8 v = vn;
+      vn = vn2;
+      if (j + 2 < ML) {
+        int ad = ro0 + (j + 2 < k ? j + 2 : 0) * kLd;
+        FB_PIN1(ad, part);
+        vn2 = ld8(&Ys[ad]);
+      }
+      part = dot8(go, v);
+      const float d = group_sum8_dpp(part);
+      ds[j] = d;
+      sig += p[j] * d;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < ML; ++j) ds[j] = p[j] * (ds[j] - sig) * inv_temp;
+  const float dspf = padf * (pp * (dsp_raw - sig) * inv_temp);
+  axpy8(accU, ppf, go);
+  gq = scale8(dspf, ld8(xpad + 8 * sub));
+  {
+    V8 vn = ld8(&Xs[ro0]), vn2 = ld8(&Xs[ro0 + (1 < k ? 1 : 0) * kLd]);
+#pragma unroll
+    for (int j = 0; j < ML; ++j) {
+      const V8 v = vn;
+      vn = vn2;
+      if (j + 2 < ML) {
+        int ad = ro0 + (j + 2 < k ? j + 2 : 0) * kLd;
+        FB_PIN(ad, gq);
+        vn2 = ld8(&Xs[ad]);
+      }
+      axpy8(gq, ds[j], v);
+    }
+  }
+  {
+    int ad = li * kLd + 8 * sub;
+    FB_PIN(ad, gq);
+    const V8 q = ld8(&Qs[ad]);
+    axpy8(accK, dspf, q);
+  }
+  if (sub == 1) {                                          // row i of dS for the column phase (P is in Ps already)
+    float* dst = dSs + li * 8;
+    *reinterpret_cast<float4*>(dst) = make_float4(ds[0], ds[1 % ML], ML > 2 ? ds[2 % ML] : 0.f, ML > 3 ? ds[3 % ML] : 0.f);
+    if (ML > 4) *reinterpret_cast<float4*>(dst + 4) = make_float4(ds[4 % ML], ML > 5 ? ds[5 % ML] : 0.f, ML > 6 ? ds[6 % ML] : 0.f, ML > 7 ? ds[7 % ML] : 0.f);
+  }
+}
+
 template <int ML>
 __device__ __forceinline__ void attn_col8(const float* __restrict__ Qs, const float* __restrict__ Fs, const float* __restrict__ Ps,
                                           const float* __restrict__ dSs, int li, int li0, int k, int sub, V8& gk, V8& gv) {
@@ -216,11 +294,18 @@ struct FusedBwdHArgs {
   const int32_t* xrow;                             // NODE instances: X is the per-node table of NORMALISED rows [n_nodes + 1][64] (node_xhat_kernel) and token t reads
                                                    // row xrow[t] (the plan's tok_key: 0 = padding) -- no LayerNorm in the staging
   const float* rn; int64_t rn_head;                // NODE instances, non-null: the heads' r rows per node [8][rn_head / 64][64] (node_r_kernel); the record holds probabilities only
+  const float* vn;                                 // VTAB instances: the heads' value rows per node, y = M_h x_hat, laid out like rn (node_r_kernel's V role)
 };
 constexpr size_t kBwdLdsBytes = (size_t)2 * kTileH * 4 + (size_t)4 * kPT * 2 + (64 + 256 + 256 + 32) * 4;
 
-template <int ML, bool NODE>
+// VTAB (node route with the r AND the value table): per (half tile, head) THREE products and five barrier phases.  With
+// y_j = M_h x_hat_j gathered per node and U_j = sum_i p_ij dDyn_i in the column phase's value accumulator,
+//   d_j = dDyn_i . y_j;   d x_hat = [dR | U] [B_h ; M_h] + GK;   dM_h = U^T x_hat + u_pad (x) x_hat_pad;   d x_hat_pad = accK + u_pad M_h
+// (u_pad = sum_i n_pad p_i,pad dDyn_i) -- no dZ product, no Z, dDyn only a vector operand.  LDS regions by lifetime: Dp = dDyn f32 rows (+ y_pad
+// behind them), FBp = y f32 rows -> U planes (written by the column phase: nobody reads y behind the row phase's barrier), Gs = GK only.
+template <int ML, bool NODE, bool VTAB = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void fused_bwdh_kernel(FusedBwdHArgs g) {
+  static_assert(NODE || !VTAB, "the value table belongs to the node route");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* Xs = lds;                                   // x_hat f32 (keys = values of the attention)
   float* Gs = lds + kTileH;                          // attention's gradient into the x_hat rows (keys + values)
@@ -230,6 +315,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   short* FBp = RBp + kPT;                            // dZ f32 -> Z planes
   float* Rs = reinterpret_cast<float*>(RBp);
   float* Fs = reinterpret_cast<float*>(FBp);
+  float* Ds = reinterpret_cast<float*>(Dp);          // VTAB: dDyn f32 rows [32][kLd], zero past the tokens
+  float* ypad = Ds + kTileH;                         // VTAB: y of the padding token (VN[head][0]) behind them, inside the Dp region
   float* sm = reinterpret_cast<float*>(FBp + kPT);
   float* xpad = sm;
   float* dSs = xpad + 64;             // [32][8]
@@ -272,6 +359,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       *reinterpret_cast<float4*>(&xpad[sc4]) = make_float4((xv.x - m) * rs, (xv.y - m) * rs, (xv.z - m) * rs, (xv.w - m) * rs);
     }
   }
+  if constexpr (VTAB) {
+    static_assert((size_t)(kTileH + 64) * 4 <= (size_t)kPT * 2, "dDyn rows + y_pad fit the Dp region");
+    if (tid >= 64 && tid < 80) *reinterpret_cast<float4*>(&ypad[sc4]) = *reinterpret_cast<const float4*>(g.vn + (int64_t)head * g.rn_head + sc4);
+  }
 
   // weight-gradient accumulators: rows 16 mt + 4 kq + reg, column fb + c16 of dB_h and dM_h (four 16 x 16 tiles each)
   f32x4 ab0 = {0.f, 0.f, 0.f, 0.f}, ab1 = ab0, ab2 = ab0, ab3 = ab0, am0 = ab0, am1 = ab0, am2 = ab0, am3 = ab0;
@@ -292,7 +383,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int row__ = srow + 16 * (I);                                                                   \
     kx##I = g.xrow[(M).x + (row__ < (M).y ? row__ : ((M).y > 0 ? (M).y - 1 : 0))];                       \
   } while (0)
-  f32x4 ri0, ri1, pn = {0.f, 0.f, 0.f, 0.f};
+  f32x4 ri0, ri1, yi0, yi1, pn = {0.f, 0.f, 0.f, 0.f};
 #define FBH_ROW_GLOAD(I, M)                                                                              \
   do {                                                                                                   \
     const int row__ = srow + 16 * (I);                                                                   \
@@ -307,11 +398,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   } while (0)
   // NODE with the r table: this head's r rows of the same two table rows, row-major like the x_hat rows (16 lanes per 256-byte row).  Issued
   // next to FBH_ROWS_GLOAD while kx0 / kx1 still hold that half tile's keys
-  const bool r_tab = NODE && g.rn != nullptr;
+  const bool r_tab = VTAB || (NODE && g.rn != nullptr);
 #define FBH_R_GLOAD()                                                                                    \
   do {                                                                                                   \
     const float* rh__ = g.rn + (int64_t)head * g.rn_head + sc4;                                          \
     ri0 = *reinterpret_cast<const f32x4*>(rh__ + (int64_t)kx0 * 64); ri1 = *reinterpret_cast<const f32x4*>(rh__ + (int64_t)kx1 * 64); \
+    if constexpr (VTAB) {                                                                                \
+      const float* vh__ = g.vn + (int64_t)head * g.rn_head + sc4;                                        \
+      yi0 = *reinterpret_cast<const f32x4*>(vh__ + (int64_t)kx0 * 64); yi1 = *reinterpret_cast<const f32x4*>(vh__ + (int64_t)kx1 * 64); \
+    }                                                                                                    \
   } while (0)
   // x_hat row -> Xs (f32) and Xp (planes); dDyn row (zero past the tokens) -> Dp (planes) + its column sums
 #define FBH_ROW_STAGE(I)                                                                                 \
@@ -337,7 +432,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       *reinterpret_cast<u32x2*>(d__ + 2 * kPlane) = (u32x2){p0__.l, p1__.l};                             \
     }                                                                                                    \
     const float4 dm__ = make_float4(dv__.x * msk__, dv__.y * msk__, dv__.z * msk__, dv__.w * msk__);     \
-    {                                                                                                    \
+    if constexpr (VTAB) {                                                                                \
+      *reinterpret_cast<float4*>(&Ds[row__ * kLd + sc4]) = dm__;                                         \
+    } else {                                                                                             \
       const P3 p0__ = split2(dm__.x, dm__.y), p1__ = split2(dm__.z, dm__.w);                             \
       short* d__ = Dp + row__ * kPS + sc4;                                                               \
       *reinterpret_cast<u32x2*>(d__) = (u32x2){p0__.h, p1__.h}; *reinterpret_cast<u32x2*>(d__ + kPlane) = (u32x2){p0__.m, p1__.m}; \
@@ -381,6 +478,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     {
       FBH_ROW_STAGE(0); FBH_ROW_STAGE(1);
       if (tid < 32) tinfo[tid] = tid < n_real ? ((tid - (tpn & 255)) | (tpn & ~255)) : 0;
+      if constexpr (VTAB) {
+        *reinterpret_cast<f32x4*>(&Fs[srow * kLd + sc4]) = yi0; *reinterpret_cast<f32x4*>(&Fs[(srow + 16) * kLd + sc4]) = yi1;
+      }
       if (r_tab) {
         *reinterpret_cast<f32x4*>(&Rs[srow * kLd + sc4]) = ri0; *reinterpret_cast<f32x4*>(&Rs[(srow + 16) * kLd + sc4]) = ri1;
       } else {
@@ -400,7 +500,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int sub = lane & 7;
     (void)srow; (void)sc4;
     // ---- dZ^T = M_h^T . dDyn^T: lane (c16, kq) ends with token c16 (+ 16) and features fb + 4 kq + {0..3} ----
-    {
+    if constexpr (!VTAB) {
       f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
       const short* dp = Dp + c16 * kPS + 8 * kq;
 #pragma unroll
@@ -410,12 +510,36 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       }
       *reinterpret_cast<f32x4*>(&Fs[c16 * kLd + fb + 4 * kq]) = acc0;
       *reinterpret_cast<f32x4*>(&Fs[(16 + c16) * kLd + fb + 4 * kq]) = acc1;
+      FB_T(1);
+      __syncthreads();
+      FB_T(7);
     }
-    FB_T(1);
-    __syncthreads();
-    FB_T(7);
     // ---- attention forward + backward in x_hat space: 8 lanes per token, all 32 rows in one pass ----
-    {
+    if constexpr (VTAB) {
+      FB_T(1);                                        // (this column is "stage + dZ product" in the other instances: the staging alone here)
+      V8 q0, k0, v0;
+      const int la = wave * 8 + (lane >> 3);
+      const bool acta = la < n_real;
+      int ia = 0;
+      if (acta) { ia = tinfo[la]; attn_row8_v<ML>(Rs, Xs, Fs, Ds, xpad, ypad, Ps, dSs, la, ia & 255, ia >> 8, g.L - (ia >> 8), sub, inv_temp, q0, accK, accV); }
+      __builtin_amdgcn_sched_barrier(0);
+      FB_T(2);
+      __syncthreads();                                // the y rows are dead from here: the column phase writes the U planes over them
+      FB_T(7);
+      if (acta) {
+        attn_col8<ML>(Rs, Ds, Ps, dSs, la, ia & 255, ia >> 8, sub, k0, v0);      // GK_j = sum_i dS_ij r_i,  U_j = sum_i p_ij dDyn_i
+        st8(&Gs[la * kLd + 8 * sub], k0);
+      } else {
+        ZR8(&Gs[la * kLd + 8 * sub]);
+        v0 = zero8(); q0 = zero8();                   // rows past the tokens: zero planes (they are contraction slots of the weight gradients)
+      }
+      frag_store(FBp + la * kPS + 8 * sub, split8(v0));
+      FB_T(3);
+      __syncthreads();                                // every column phase is done with the r rows: they become the dR PLANES
+      FB_T(7);
+      frag_store(RBp + la * kPS + 8 * sub, split8(q0));
+      accR.a += q0.a; accR.b += q0.b; accR.c += q0.c; accR.d += q0.d;
+    } else {
       V8 o0, q0, k0, v0;
       const int la = wave * 8 + (lane >> 3);
       const bool acta = la < n_real;
@@ -458,6 +582,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const Frag3 a0 = frag_row(arow + 32 * s), a1 = frag_row(arow + 16 * kPS + 32 * s);
         dx0 = mma6(dx0, a0, Bf[s]); dx1 = mma6(dx1, a1, Bf[s]);
       }
+      if constexpr (VTAB) {                           // ... + U M_h: the value part of the attention's gradient, as a longer contraction
+        const short* urow = FBp + c16 * kPS + 8 * kq;
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          const Frag3 a0 = frag_row(urow + 32 * s), a1 = frag_row(urow + 16 * kPS + 32 * s);
+          dx0 = mma6(dx0, a0, Mf[s]); dx1 = mma6(dx1, a1, Mf[s]);
+        }
+      }
       float* out = g.dxh + ((int64_t)t0 + 4 * kq) * 64 + fb + c16;
 #pragma unroll
       for (int reg = 0; reg < 4; ++reg) {
@@ -473,6 +605,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const Frag3 a0 = frag_row(arow + 32 * s), a1 = frag_row(arow + 16 * kPS + 32 * s);
         dx0 = mma6(dx0, Bf[s], a0); dx1 = mma6(dx1, Bf[s], a1);
       }
+      if constexpr (VTAB) {
+        const short* urow = FBp + c16 * kPS + 8 * kq;
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          const Frag3 a0 = frag_row(urow + 32 * s), a1 = frag_row(urow + 16 * kPS + 32 * s);
+          dx0 = mma6(dx0, Mf[s], a0); dx1 = mma6(dx1, Mf[s], a1);
+        }
+      }
       float* out = g.dxh + ((int64_t)head * g.tcap + t0 + c16) * 64 + fb + 4 * kq;
       if (c16 < n_real) *reinterpret_cast<f32x4*>(out) = dx0;
       if (16 + c16 < n_real) *reinterpret_cast<f32x4*>(out + 16 * 64) = dx1;
@@ -482,14 +622,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // ---- weight gradients: dB[a][b] += sum_t dR[t][a] x_hat[t][b];  dM[n][m] += sum_t dDyn[t][n] Z[t][m]: ONE 32-token step, column fragments ----
     {
       const int blk = ((4 * kq + ((lane & 15) >> 2)) * kPS) + 4 * (lane & 3);      // this lane's address inside a 4 x 16 transpose block
-      const Frag3 xb = frag_col(Xp + blk + fb), zb = frag_col(FBp + blk + fb);
+      const Frag3 xb = frag_col(Xp + blk + fb);
+      Frag3 zb;
+      if constexpr (!VTAB) zb = frag_col(FBp + blk + fb);
       {
         const Frag3 r0 = frag_col(RBp + blk), r1 = frag_col(RBp + blk + 16);
         ab0 = mma6(ab0, r0, xb); ab1 = mma6(ab1, r1, xb);
         const Frag3 r2 = frag_col(RBp + blk + 32), r3 = frag_col(RBp + blk + 48);
         ab2 = mma6(ab2, r2, xb); ab3 = mma6(ab3, r3, xb);
       }
-      {
+      if constexpr (VTAB) {                           // dM[n][m] += sum_t U[t][n] x_hat[t][m]: the same x_hat column fragment
+        const Frag3 u0 = frag_col(FBp + blk), u1 = frag_col(FBp + blk + 16);
+        am0 = mma6(am0, u0, xb); am1 = mma6(am1, u1, xb);
+        const Frag3 u2 = frag_col(FBp + blk + 32), u3 = frag_col(FBp + blk + 48);
+        am2 = mma6(am2, u2, xb); am3 = mma6(am3, u3, xb);
+      } else {
         const Frag3 d0 = frag_col(Dp + blk), d1 = frag_col(Dp + blk + 16);
         am0 = mma6(am0, d0, zb); am1 = mma6(am1, d1, zb);
         const Frag3 d2 = frag_col(Dp + blk + 32), d3 = frag_col(Dp + blk + 48);
@@ -515,8 +662,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       const int row = 4 * kq + reg;
       slab[0 * 4096 + row * 64 + col] = ab0[reg]; slab[0 * 4096 + (row + 16) * 64 + col] = ab1[reg];
       slab[0 * 4096 + (row + 32) * 64 + col] = ab2[reg]; slab[0 * 4096 + (row + 48) * 64 + col] = ab3[reg];
-      slab[1 * 4096 + row * 64 + col] = am0[reg]; slab[1 * 4096 + (row + 16) * 64 + col] = am1[reg];
-      slab[1 * 4096 + (row + 32) * 64 + col] = am2[reg]; slab[1 * 4096 + (row + 48) * 64 + col] = am3[reg];
+      if constexpr (!VTAB) {
+        slab[1 * 4096 + row * 64 + col] = am0[reg]; slab[1 * 4096 + (row + 16) * 64 + col] = am1[reg];
+        slab[1 * 4096 + (row + 32) * 64 + col] = am2[reg]; slab[1 * 4096 + (row + 48) * 64 + col] = am3[reg];
+      }
     }
   }
   // column sums of dDyn: thread (srow, sc4) staged rows srow, srow + 16 of every half tile -- the four row groups of a wave in a fixed xor order,
@@ -535,6 +684,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // column sums of dR and d x_hat of the padding token: the 8 lanes with equal `sub` of a wave (fixed xor tree), then the 4 waves in order
   float* redr = lds + 4 * 64;           // [4][64]
   float* redp = lds + 8 * 64;           // [4][64]
+  // VTAB: accV holds u_pad's partials; they are reduced on their own (redu), because u_pad enters dM_h and d x_hat_pad through products
+  float* redu = lds + 12 * 64;          // [4][64]
+  float* upad = lds + 16 * 64;          // [64]
+  if constexpr (VTAB) {
+    const float accu[8] = {accV.a.x, accV.a.y, accV.b.x, accV.b.y, accV.c.x, accV.c.y, accV.d.x, accV.d.y};
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      float v = accu[i];
+      v += __shfl_xor(v, 8, 64);
+      v += __shfl_xor(v, 16, 64);
+      v += __shfl_xor(v, 32, 64);
+      if (lane < 8) redu[wave * 64 + 8 * lane + i] = v;
+    }
+    accV = zero8();
+  }
   const float accp[16] = {accK.a.x + accV.a.x, accK.a.y + accV.a.y, accK.b.x + accV.b.x, accK.b.y + accV.b.y,
                           accK.c.x + accV.c.x, accK.c.y + accV.c.y, accK.d.x + accV.d.x, accK.d.y + accV.d.y,
                           accR.a.x, accR.a.y, accR.b.x, accR.b.y, accR.c.x, accR.c.y, accR.d.x, accR.d.y};
@@ -550,7 +714,30 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   if (tid < 64) {
     slab[kVecOffM + 64 + tid] = (redd[tid] + redd[64 + tid]) + (redd[128 + tid] + redd[192 + tid]);    // d bdyn partial
     slab[kVecOffM + tid] = (redr[tid] + redr[64 + tid]) + (redr[128 + tid] + redr[192 + tid]);         // db_h partial
-    slab[kVecOffM + 128 + tid] = (redp[tid] + redp[64 + tid]) + (redp[128 + tid] + redp[192 + tid]);   // dxpad partial
+    if constexpr (!VTAB) slab[kVecOffM + 128 + tid] = (redp[tid] + redp[64 + tid]) + (redp[128 + tid] + redp[192 + tid]);   // dxpad partial
+  }
+  if constexpr (VTAB) {
+    // the two padding terms: dM_h += u_pad (x) x_hat_pad (rank one, into the accumulators before their store) and d x_hat_pad = accK + u_pad M_h
+    if (tid < 64) upad[tid] = (redu[tid] + redu[64 + tid]) + (redu[128 + tid] + redu[192 + tid]);
+    __syncthreads();
+    {
+      const float xc = xpad[fb + c16];
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int row = 4 * kq + reg, col = fb + c16;
+        slab[1 * 4096 + row * 64 + col] = am0[reg] + upad[row] * xc; slab[1 * 4096 + (row + 16) * 64 + col] = am1[reg] + upad[row + 16] * xc;
+        slab[1 * 4096 + (row + 32) * 64 + col] = am2[reg] + upad[row + 32] * xc; slab[1 * 4096 + (row + 48) * 64 + col] = am3[reg] + upad[row + 48] * xc;
+      }
+    }
+    if (tid < 64) {
+      const float* mp = g.mM + (int64_t)head * 4096 + tid;
+      float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;         // four chains in a fixed order
+#pragma unroll 4
+      for (int n = 0; n < 64; n += 4) {
+        s0 += upad[n] * mp[n * 64]; s1 += upad[n + 1] * mp[(n + 1) * 64]; s2 += upad[n + 2] * mp[(n + 2) * 64]; s3 += upad[n + 3] * mp[(n + 3) * 64];
+      }
+      slab[kVecOffM + 128 + tid] = ((redp[tid] + redp[64 + tid]) + (redp[128 + tid] + redp[192 + tid])) + ((s0 + s1) + (s2 + s3));
+    }
   }
 }
 
@@ -815,10 +1002,11 @@ size_t fused_bwd_ws_floats(int64_t B, int L) {
 // merged heads: fused_bwdh_kernel -> fbm_chain_kernel -> the LayerNorm un-folding of launch_fused_bwd (one slab per head)
 int launch_fused_bwd_merged(const matcha_tensors& p, const float* folded, const float* merged, const float* X, const float* dDyn, const float* dXs,
                             const Ragged& rg, int64_t B, int L, float* dxh, float* ws, matcha_tensors& grads, float* dZ0, hipStream_t st, const float* rimg,
-                            bool dx_atomic, bool dx_zeroed, const TailReduceArgs* tail, const int32_t* xrow, const float* xhatN, const float* rn, int64_t rn_rows) {
+                            bool dx_atomic, bool dx_zeroed, const TailReduceArgs* tail, const int32_t* xrow, const float* xhatN, const float* rn, int64_t rn_rows, const float* vn) {
   const int64_t tcap = B * L + 1;
   MATCHA_CHECK_ARG(!xrow || xhatN, "fused backward: the node route needs the table of normalised rows");
   MATCHA_CHECK_ARG(!rn || xrow, "fused backward: the r table belongs to the node route");
+  MATCHA_CHECK_ARG(!vn || rn, "fused backward: the value table needs the r table");
   if (dx_atomic && !dx_zeroed) MATCHA_TRY(zero_async(dxh, (size_t)tcap * 64 * sizeof(float), st));
   int nchunks = 2 * chunks_for(rg.nhalves);                  // two four-wave workgroups per CU
   if (nchunks > kMaxChunks) nchunks = kMaxChunks;
@@ -833,7 +1021,7 @@ int launch_fused_bwd_merged(const matcha_tensors& p, const float* folded, const 
     FusedBwdHArgs g;
     g.X = xrow ? xhatN : X; g.dDyn = dDyn; g.count = rg.count; g.half_meta = rg.half_meta; g.tok_pos = rg.tok_pos; g.L = L; g.nhalves = rg.nhalves; g.nchunks = nchunks;
     g.mB = mv.B; g.mM = mv.M; g.dxh = dxh; g.tcap = tcap; g.dx_atomic = dx_atomic ? 1 : 0; g.wslab = wslab; g.rimg = rimg; g.xrow = xrow;
-    g.rn = rn; g.rn_head = rn_rows * 64;
+    g.rn = rn; g.rn_head = rn_rows * 64; g.vn = vn;
     const size_t lds = kBwdLdsBytes;
     auto launch = [&](auto kfn) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -850,12 +1038,12 @@ int launch_fused_bwd_merged(const matcha_tensors& p, const float* folded, const 
     // every run -- and is faster.  The Makefile sets the flag for the whole library; tests/test_hip_properties.py::test_full_size_train_step_is_reproducible
     // is the run-time guard.
     switch (L <= 2 ? 2 : (L <= 6 ? L : 8)) {
-      case 2: if (xrow) launch(fused_bwdh_kernel<2, true>); else launch(fused_bwdh_kernel<2, false>); break;
-      case 3: if (xrow) launch(fused_bwdh_kernel<3, true>); else launch(fused_bwdh_kernel<3, false>); break;
-      case 4: if (xrow) launch(fused_bwdh_kernel<4, true>); else launch(fused_bwdh_kernel<4, false>); break;
-      case 5: if (xrow) launch(fused_bwdh_kernel<5, true>); else launch(fused_bwdh_kernel<5, false>); break;
-      case 6: if (xrow) launch(fused_bwdh_kernel<6, true>); else launch(fused_bwdh_kernel<6, false>); break;
-      default: if (xrow) launch(fused_bwdh_kernel<8, true>); else launch(fused_bwdh_kernel<8, false>); break;
+      case 2: if (vn) launch(fused_bwdh_kernel<2, true, true>); else if (xrow) launch(fused_bwdh_kernel<2, true>); else launch(fused_bwdh_kernel<2, false>); break;
+      case 3: if (vn) launch(fused_bwdh_kernel<3, true, true>); else if (xrow) launch(fused_bwdh_kernel<3, true>); else launch(fused_bwdh_kernel<3, false>); break;
+      case 4: if (vn) launch(fused_bwdh_kernel<4, true, true>); else if (xrow) launch(fused_bwdh_kernel<4, true>); else launch(fused_bwdh_kernel<4, false>); break;
+      case 5: if (vn) launch(fused_bwdh_kernel<5, true, true>); else if (xrow) launch(fused_bwdh_kernel<5, true>); else launch(fused_bwdh_kernel<5, false>); break;
+      case 6: if (vn) launch(fused_bwdh_kernel<6, true, true>); else if (xrow) launch(fused_bwdh_kernel<6, true>); else launch(fused_bwdh_kernel<6, false>); break;
+      default: if (vn) launch(fused_bwdh_kernel<8, true, true>); else if (xrow) launch(fused_bwdh_kernel<8, true>); else launch(fused_bwdh_kernel<8, false>); break;
     }
     MATCHA_CHECK_LAUNCH("fused_bwdh_kernel");
   }

@@ -686,15 +686,18 @@ __global__ __launch_bounds__(512) void fused_fwd32h_kernel(Fwd32Args g) {
 // prologue (load, statistics, normalise, split) and the r product (the same WB_MMA sequence and plane order, the bias entering the
 // accumulator the same way).  An MFMA output column depends only on the same column of the token-side operand, so every token of a node
 // gathers bit for bit the row the per-token product computes.  Rows row-major: RN[(h rows + node) 64 + f].
-struct NodeRArgs { const float* X; const u32x4* wfrag; float* rn; int rows; };
+// The V role (blockIdx.y >= 8, launched only by a forward that will be differentiated): the value rows y = M_h x_hat of the same nodes for the
+// backward's VTAB instance (fused_bwd.hip) -- the same prologue and chain, primed at M_hd's position in the stream, into a zero accumulator.
+struct NodeRArgs { const float* X; const u32x4* wfrag; float* rn; int rows; float* vn; };
 __global__ __launch_bounds__(64) void node_r_kernel(NodeRArgs g) {
   const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
-  const int hd = blockIdx.y;
+  const int hd = blockIdx.y & 7;
+  const bool vrole = blockIdx.y >= MATCHA_N_HEAD;
   const int row = (int)blockIdx.x * 32 + r;
   const bool live = row < g.rows;
   const u32x4* wp;
   u32x4 W_[F32_WIN];
-  W32_PRIME_AT(hd == 0 ? 0 : 2 * hd - 1);             // R_hd (prep_heads_kernel's stream order)
+  W32_PRIME_AT(vrole ? (hd < 7 ? 2 * hd + 2 : 15) : (hd == 0 ? 0 : 2 * hd - 1));      // M_hd | R_hd (prep_heads_kernel's stream order)
   FL xh = fl_load(g.X + (int64_t)(live ? row : g.rows - 1) * 64 + 4 * h);
   {
     float mean, rx;
@@ -705,16 +708,17 @@ __global__ __launch_bounds__(64) void node_r_kernel(NodeRArgs g) {
   B3 xs[4];
   FL_SPLIT(xs[0], xh, 0); FL_SPLIT(xs[1], xh, 1); FL_SPLIT(xs[2], xh, 2); FL_SPLIT(xs[3], xh, 3);
   FL q = F32_BIAS(kBiasR + hd);
+  if (vrole) q = fl_zero();
   W32_CHAIN_XS(q, xs, false);
-  if (live) fl_store_global(g.rn + ((int64_t)hd * g.rows + row) * 64 + 4 * h, q);
+  if (live) fl_store_global((vrole ? g.vn : g.rn) + ((int64_t)hd * g.rows + row) * 64 + 4 * h, q);
 }
 
 size_t node_r_floats(int64_t rows) { return (size_t)MATCHA_N_HEAD * rows * 64; }
-int launch_node_r(const float* XN, const float* frag, int64_t rows, float* rn, hipStream_t st) {
+int launch_node_r(const float* XN, const float* frag, int64_t rows, float* rn, hipStream_t st, float* vn) {
   NodeRArgs g;
-  g.X = XN; g.wfrag = reinterpret_cast<const u32x4*>(frag); g.rn = rn; g.rows = (int)rows;
+  g.X = XN; g.wfrag = reinterpret_cast<const u32x4*>(frag); g.rn = rn; g.rows = (int)rows; g.vn = vn;
   ProfScope ps(MATCHA_PROF_FUSED_FWD, 0.0, st);       // part of the fused forward; no algorithmic work of its own
-  hipLaunchKernelGGL(node_r_kernel, dim3((unsigned)cdiv(rows, 32), MATCHA_N_HEAD), dim3(64), 0, st, g);
+  hipLaunchKernelGGL(node_r_kernel, dim3((unsigned)cdiv(rows, 32), vn ? 2 * MATCHA_N_HEAD : MATCHA_N_HEAD), dim3(64), 0, st, g);
   MATCHA_CHECK_LAUNCH("node_r_kernel");
   return MATCHA_OK;
 }

@@ -114,6 +114,7 @@ struct Options {
   int disable_wide_gemm;     // embed_dim >= 128: the 64-wide GEMM / attention kernels
   int disable_node_front;    // the table front end once per TOKEN at every size (the node route -- once per node when tokens outnumber nodes -- off)
   int disable_node_r;        // node route: the heads' r rows computed per TOKEN inside the forward kernel and handed to the backward in the record (the per-node r table off)
+  int disable_node_v;        // node route with the r table: the backward forms dZ / Z per token (the per-node value table y = M_h x_hat and the kernel instance on it off)
   int debug_nan, fused_dbg;  // development
 };
 Options& options();
@@ -165,8 +166,9 @@ int launch_fused_fwd32(const matcha_tensors& p, const float* folded, const float
                        const int32_t* xrow = nullptr,        // xrow (large batches only): X is a per-node table, token t reads row xrow[t];  tail_dh2 (large batches only): the convolutions' backward is left to launch_tail_bwd64
                        const float* rn = nullptr, int64_t rn_rows = 0);      // rn (with xrow): the heads' r rows per node [8][rn_rows][64] (launch_node_r) -- gathered, not computed per token
 // the r rows of every (head, node): rows of the per-node table XN -> RN[8][rows][64]; needs this step's fragment stream (launch_prep_heads / the front end's launch)
+// vn != null: the same launch also writes the value rows y = M_h x_hat (no bias) -> VN[8][rows][64] for the backward's VTAB instance
 size_t node_r_floats(int64_t rows);
-int launch_node_r(const float* XN, const float* frag, int64_t rows, float* rn, hipStream_t st);
+int launch_node_r(const float* XN, const float* frag, int64_t rows, float* rn, hipStream_t st, float* vn = nullptr);
 // tail_bwd.hip: the backward of pff_n1's two convolutions as its own kernel behind fused_fwd32_kernel (large batches)
 int tail_bwd_grid();
 size_t tail_bwd_slab_floats();
@@ -182,7 +184,8 @@ int launch_fused_bwd_merged(const matcha_tensors& p, const float* folded, const 
                             const Ragged& rg, int64_t B, int L, float* dxh, float* ws, matcha_tensors& grads, float* dZ0, hipStream_t st, const float* rimg,
                             bool dx_atomic, bool dx_zeroed = false,    // dx_zeroed: the caller already zeroed dxh[(B L + 1) x 64] on this stream
                             const struct TailReduceArgs* tail = nullptr, const int32_t* xrow = nullptr, const float* xhatN = nullptr,
-                            const float* rn = nullptr, int64_t rn_rows = 0);      // rn (with xrow): the forward gathered r from this table and left no r rows in the record
+                            const float* rn = nullptr, int64_t rn_rows = 0,       // rn (with xrow): the forward gathered r from this table and left no r rows in the record
+                            const float* vn = nullptr);                           // vn (with rn): the value table y = M_h x_hat [8][rn_rows][64] -- the VTAB instance, no dZ product
 // xrow != null (with xhatN): X is the per-node table (row 0 = padding) and xhatN its normalised rows; token t stages row xrow[t] of xhatN as it is;  tail != null: the launch that sums this kernel's slabs also sums the forward's tail slabs (tail_reduce.hpp)
 size_t fused_qkv_floats(int64_t B, int L);         // what the training forward leaves for the fused backward, per (half tile, head):
 constexpr int kImgRecH = 2048 + 256;               // 32 r rows (r = B_h x_hat + b_h; register images) + their attention probabilities [32][8].

@@ -110,6 +110,7 @@ struct Workspace {
   // backward's per-node sum of the tokens' gradient rows, the id list 0..n_nodes and its length {n_nodes + 1, n_nodes} (both written by the plan)
   float *XN, *x0N, *xhN, *GN; int64_t* node_ids; int32_t* node_cnt;
   float* RN;                              // ... and the heads' r rows per node [8][n_nodes + 1][64] (node_r_kernel), rebuilt by every forward on the route
+  float* VN;                              // ... and their value rows y = M_h x_hat, same shape, written by the same launch of a differentiated forward (null in the compact layout)
   size_t total;
 };
 
@@ -127,12 +128,16 @@ struct Workspace {
 //   disable_node_front       the table front end per TOKEN at every size (node_front_shape / the rule in forward_impl decide otherwise)
 //   disable_node_r           node route: r = B_h x_hat + b_h per TOKEN inside the forward kernel, the rows handed to the backward in the record (without it:
 //                            once per (node, head) by node_r_kernel, both encoder kernels gather the rows by tok_key)
+//   disable_node_v           node route with the r table: the backward kernel forms dZ = dDyn M_h and Z per token, as without the r table (without
+//                            the switch: node_r_kernel also writes y = M_h x_hat per (node, head) in a differentiated forward and the backward's
+//                            VTAB instance gathers the rows -- no dZ product, no Z; the forward's outputs are the same bits either way; only
+//                            from node_v_shape's size on: below it the table does not pay and this switch changes nothing)
 //   disable_wide_gemm        embed_dim >= 128: the 64-wide GEMM / attention kernels (gemm_lds.hip, gemm_f32.hip, attention.hip; four-product
 //                            heads) instead of gemm_wide.hip / attention_wide.hip
 struct OptionName { const char* name; int Options::*field; };
 static const OptionName kOptionNames[] = {
     {"disable_fused", &Options::disable_fused}, {"disable_merged", &Options::disable_merged}, {"disable_small_batch", &Options::disable_small_batch},
-    {"disable_wide_gemm", &Options::disable_wide_gemm}, {"disable_node_front", &Options::disable_node_front}, {"disable_node_r", &Options::disable_node_r}, {"debug_nan", &Options::debug_nan}, {"fused_dbg", &Options::fused_dbg}};
+    {"disable_wide_gemm", &Options::disable_wide_gemm}, {"disable_node_front", &Options::disable_node_front}, {"disable_node_r", &Options::disable_node_r}, {"disable_node_v", &Options::disable_node_v}, {"debug_nan", &Options::debug_nan}, {"fused_dbg", &Options::fused_dbg}};
 Options& options() {
   static Options o = [] {
     Options v;
@@ -169,6 +174,11 @@ static bool fused_front_enabled() { return (options().disable_fused & 2) == 0; }
 static bool node_front_shape(const matcha_shape& s, int64_t B, int L) {
   return s.mode == 0 && s.d == 64 && front_bwd_supported(s.d, s.n_attr) && B * L + 1 >= 4 * ((int64_t)s.n_nodes + 1);
 }
+// ... and the value table of that route (VN: y = M_h x_hat per node for the backward, fused_bwd.hip VTAB) on top of the r table.  It costs
+// node_r_kernel's V role per NODE and saves the backward kernel work per TOKEN.  Measured against the parent's library at hg38 1 Mb (3 068
+// table rows), same call, three alternations: no difference that the runs' own spread lets through at 8 192, 16 384 and 32 768 rows (capacity /
+// rows of the table = 13, 27, 53), -15 to -24 us of 1.2 ms at 65 536 rows (107) -- profiles/r10_node_v.md.  So the table is built from 64 on.
+static bool node_v_shape(const matcha_shape& s, int64_t B, int L) { return B * L + 1 >= 64 * ((int64_t)s.n_nodes + 1); }
 // the loss can be computed: BCE needs labels and weights, the softplus MSE only its targets
 static bool has_target(int objective, const float* y, const float* w) { return objective == MATCHA_OBJECTIVE_SOFTPLUS_MSE ? y != nullptr : (y && w); }
 static bool loss_in_forward(const matcha_shape& s, const matcha_step_opts& o, const float* y, const float* w, int objective) {
@@ -184,9 +194,9 @@ static int check_objective(int32_t objective, const char* fn) {
 // consume records nobody wrote.  Host-side record per workspace pointer (the decision picks a kernel, so it cannot live in device memory
 // without a synchronisation); bounded, evicted oldest-first, guarded by a mutex.  A backward on a workspace WITHOUT a record is refused.
 static std::mutex g_fwd_mu;
-static std::unordered_map<const void*, std::pair<int, uint64_t>> g_fwd_state;     // ws -> (bits, age); bit 0: merged heads, bit 1: fused d = 64 forward, bit 2: fused d = 128 attention block, bit 3: the tail's backward ran as tail_bwd64_kernel, bit 4: the forward zeroed the d x_hat rows of the backward kernel, bit 5: the front end ran per node (node route), bit 6: ... and the forward gathered the heads' r rows from the per-node table (no r rows in the record)
+static std::unordered_map<const void*, std::pair<int, uint64_t>> g_fwd_state;     // ws -> (bits, age); bit 0: merged heads, bit 1: fused d = 64 forward, bit 2: fused d = 128 attention block, bit 3: the tail's backward ran as tail_bwd64_kernel, bit 4: the forward zeroed the d x_hat rows of the backward kernel, bit 5: the front end ran per node (node route), bit 6: ... and the forward gathered the heads' r rows from the per-node table (no r rows in the record), bit 7: ... and left the value table VN for the backward
 static uint64_t g_fwd_clock = 0;
-static void note_forward(const void* ws, bool merged, bool fused, bool enc = false, bool split_tail = false, bool dx_zeroed = false, bool node = false, bool node_r = false) {
+static void note_forward(const void* ws, bool merged, bool fused, bool enc = false, bool split_tail = false, bool dx_zeroed = false, bool node = false, bool node_r = false, bool node_v = false) {
   std::lock_guard<std::mutex> lk(g_fwd_mu);
   if (g_fwd_state.size() >= 4096 && g_fwd_state.find(ws) == g_fwd_state.end()) {
     auto old = g_fwd_state.begin();
@@ -194,7 +204,7 @@ static void note_forward(const void* ws, bool merged, bool fused, bool enc = fal
       if (it->second.second < old->second.second) old = it;
     g_fwd_state.erase(old);
   }
-  g_fwd_state[ws] = std::make_pair((merged ? 1 : 0) | (fused ? 2 : 0) | (enc ? 4 : 0) | (split_tail ? 8 : 0) | (dx_zeroed ? 16 : 0) | (node ? 32 : 0) | (node_r ? 64 : 0), ++g_fwd_clock);
+  g_fwd_state[ws] = std::make_pair((merged ? 1 : 0) | (fused ? 2 : 0) | (enc ? 4 : 0) | (split_tail ? 8 : 0) | (dx_zeroed ? 16 : 0) | (node ? 32 : 0) | (node_r ? 64 : 0) | (node_v ? 128 : 0), ++g_fwd_clock);
 }
 static int ws_state(const void* ws) {       // -1: no forward on record for this workspace
   std::lock_guard<std::mutex> lk(g_fwd_mu);
@@ -313,6 +323,8 @@ static size_t carve(const matcha_shape& s, int64_t B, int L, char* base, Workspa
     // Q / K / V (see above), and Tn >= 4 (n_nodes + 1) rows of 8 d floats hold it four times over -- so the route costs a training step no memory;
     // the compact layout of a forward-only call has no Q and takes the rows
     w.RN = nn ? (compact ? take_always(node_r_floats((int64_t)nn)) : w.Q) : nullptr;
+    // the value table sits behind it in Q's buffer (two of the four); a forward-only layout never writes it
+    w.VN = (nn && !compact && w.Q) ? w.Q + node_r_floats((int64_t)nn) : nullptr;      // (w.Q is null while the layout is only being sized)
   }
   w.total = off;
   return off;
@@ -498,6 +510,7 @@ static int forward_impl(const matcha_shape* shp, const matcha_tensors* params, c
   const bool node = front && fused_path && node_front_shape(s, B, L) && !fused_small_batch(w.rg) && !opts->deterministic && !opts->sparse_table_grad &&
                     !options().disable_node_front;
   const bool node_r = node && !options().disable_node_r;      // ... with the heads' r rows once per node (recorded like the route itself)
+  const bool node_v = node_r && !opts->forward_only && w.VN && node_v_shape(s, B, L) && !options().disable_node_v;      // ... and, for the backward alone, their value rows
   MATCHA_TRY(launch_ragged_plan(x, B, L, s.n_nodes, opts->status, w.rg, st, plan_level, node ? w.node_ids : nullptr, node ? w.node_cnt : nullptr,
                                 (node && !opts->forward_only) ? w.GN : nullptr));      // ... which also writes the node route's id list and zeroes its accumulator
   // front end: node rows (K1) + attribute path (K6) + add (Modules.py:263-269)
@@ -529,7 +542,7 @@ static int forward_impl(const matcha_shape* shp, const matcha_tensors* params, c
       // ... and, for the backward kernel's staging, their normalised rows
       if (!opts->forward_only) MATCHA_TRY(launch_node_xhat(w.XN, w.node_cnt, (int64_t)s.n_nodes + 1, w.xhN, st));
       // ... and the heads' r rows, from the fragment stream the launch above just wrote (training and inference alike)
-      if (node_r) MATCHA_TRY(launch_node_r(w.XN, w.frag, (int64_t)s.n_nodes + 1, w.RN, st));
+      if (node_r) MATCHA_TRY(launch_node_r(w.XN, w.frag, (int64_t)s.n_nodes + 1, w.RN, st, node_v ? w.VN : nullptr));
     } else
     MATCHA_TRY(launch_front_fwd(p, ids, s.mode == 0 ? p.table : nullptr, s.mode == 0 ? nullptr : w.node, *frozen, s.n_attr, w.rg, Tn,
                                 opts->forward_only ? nullptr : w.x0, w.X, st, prep_in_front ? &prep : nullptr));     // x0 (pre-activation) is only read by the backward pass
@@ -555,7 +568,7 @@ static int forward_impl(const matcha_shape* shp, const matcha_tensors* params, c
     // the backward kernel's heads ADD their d x_hat rows (float atomics) unless the sum has to be reproducible: the rows are zeroed by a launch
     // that runs anyway -- tail_bwd64_kernel, or for small batches the loss reduction's -- and the record says so
     const bool zero_dx = lif && !opts->deterministic && !opts->sparse_table_grad && (split_tail || fused_small_batch(w.rg)) && tgt && losses;
-    if (opts->forward_only) forget_forward(ws); else note_forward(ws, true, true, false, split_tail, zero_dx, node, node_r);
+    if (opts->forward_only) forget_forward(ws); else note_forward(ws, true, true, false, split_tail, zero_dx, node, node_r, node_v);
     // (with the tail's backward in the forward kernel, Y and H1 are still handed over: the single-wave kernel PARKS the two rows there
     // (and the normalised H2 row in H2's place) between the tail's forward and backward halves instead of holding 96 registers per lane -- fused_fwd32_tail.hpp)
     // (node route: the kernel reads its row from the per-node table at the plan's sanitised id -- tok_key: 0 for the padding token and foreign ids)
@@ -683,7 +696,7 @@ extern "C" int matcha_debug_layout(const matcha_shape* shp, int64_t B, int32_t L
       {"dXs", w.dXs}, {"dZ1", w.dZ1}, {"ddyn0", w.ddyn0}, {"dZ0", w.dZ0}, {"dX0", w.dX0}, {"slab", w.slab}, {"gemm_ws", w.gemm_ws}, {"adj_ws", w.adj_ws},
       {"folded", w.folded}, {"frag", w.frag}, {"merged", w.merged}, {"lwB", w.lwB}, {"lwM", w.lwM}, {"lwdB", w.lwdB}, {"lwdM", w.lwdM}, {"enc", w.enc}, {"fb_ws", w.fb_ws},
       {"tpart", w.tpart}, {"tslab", w.tslab}, {"tslab2", w.tslab2}, {"qkv_records", w.qkv}, {"front_ws", w.front_ws}, {"tg_ws", w.tg_ws}, {"XN", w.XN}, {"x0N", w.x0N}, {"xhN", w.xhN}, {"GN", w.GN},
-      {"node_ids", w.node_ids}, {"node_cnt", w.node_cnt}, {"RN", w.RN}};
+      {"node_ids", w.node_ids}, {"node_cnt", w.node_cnt}, {"RN", w.RN}, {"VN", w.VN}};
   size_t n = 0;
   for (const auto& e : f) {
     if (!e.p) continue;
@@ -765,6 +778,7 @@ static int backward_impl(const matcha_shape* shp, const matcha_tensors* params, 
   TailReduceArgs tail_args;
   const bool node = fused_fwd && (fwd_state & 32) != 0;        // the forward ran the front end per node: X lives in the per-node table, rows by tok_key
   const bool node_r = node && (fwd_state & 64) != 0;           // ... and gathered r from the per-node table: the record holds probabilities only
+  const bool node_v = node_r && (fwd_state & 128) != 0;        // ... and left the value table: the backward's VTAB instance
   if (lif) {
     // ddyn0 and dXs were produced by matcha_forward; only the per-half-tile parameter-gradient partials remain to be summed
     // (fused_fwd32.hip).  Small batches: one launch, which also zeroes the buffer the backward kernel's heads add their d x_hat into
@@ -814,7 +828,7 @@ static int backward_impl(const matcha_shape* shp, const matcha_tensors* params, 
     MATCHA_CHECK_ARG(!node || dx_atomic, "matcha_backward: deterministic / sparse_table_grad differ from the forward's on this workspace");
     MATCHA_TRY(launch_fused_bwd_merged(p, w.folded, w.merged, node ? w.XN : w.X, w.ddyn0, w.dXs, w.rg, B, L, w.dO, w.fb_ws, g_, front ? nullptr : w.dZ0, st, w.qkv, dx_atomic, dx_zeroed,
                                        tail_in_bwd ? &tail_args : nullptr, node ? w.rg.tok_key : nullptr, node ? w.xhN : nullptr,
-                                       node_r ? w.RN : nullptr, (int64_t)s.n_nodes + 1));
+                                       node_r ? w.RN : nullptr, (int64_t)s.n_nodes + 1, node_v ? w.VN : nullptr));
     MATCHA_TRY(encoder_done(*opts, st));
     if (front) {
       // LayerNorm backward of the summed partials + next_w + attribute_nn backward + embedding scatter in one kernel
