@@ -380,7 +380,7 @@ static inline int chunk_of(int d) {
   return per_lane >= 8 ? 8 : per_lane;   // 8, 4, 2, 1 (or the exact count when it is 3, 5, 6, 7: handled as CH = 1)
 }
 // register arrays are sized by the smallest supported width >= L (2,3,4,5,6,8)
-static inline int width_of(int L) { return L <= 2 ? 2 : (L <= 6 ? L : 8); }
+static inline int width_of(int L) { return ml_of(L); }
 static inline int attn_blocks(int64_t B) { return (int)cdiv(B, 4 * kAttnRowsPerWave); }
 
 size_t attn_bwd_slab_bytes(int64_t B, int d) { return align_up((size_t)attn_blocks(B) * 2 * MATCHA_N_HEAD * d * sizeof(float), 256); }

@@ -331,7 +331,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_wide_kernel(const float* Q, c
     out[i] = ((lds[i] + lds[2 * hd + i]) + lds[4 * hd + i]) + lds[6 * hd + i];
 }
 
-int attn_wide_width(int L) { return L <= 2 ? 2 : (L <= 6 ? L : 8); }
+int attn_wide_width(int L) { return ml_of(L); }
 
 }  // namespace
 

@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <stdarg.h>
 
+#include <type_traits>
+
 #include "../../include/matcha_hip.h"
 
 namespace matcha {
@@ -59,6 +61,21 @@ int device_cu_count();
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// Kernels templated on the hyperedge width keep register arrays of the smallest instantiated width >= L: 2, 3, 4, 5, 6 or 8.
+inline int ml_of(int L) { return L <= 2 ? 2 : (L <= 6 ? L : 8); }
+// ... and their launchers pick the instance through a generic lambda: f(std::integral_constant<int, ML>{})
+template <class F>
+inline void dispatch_ml(int L, F&& f) {
+  switch (ml_of(L)) {
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    case 6: f(std::integral_constant<int, 6>{}); break;
+    default: f(std::integral_constant<int, 8>{}); break;
+  }
+}
 
 // ---- counter-based RNG: the specification is oracle/rng.py (bit-identical) ---------------------
 __host__ __device__ __forceinline__ uint32_t lowbias32(uint32_t x) {

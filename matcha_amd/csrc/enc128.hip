@@ -865,7 +865,6 @@ __global__ __launch_bounds__(256) void enc128_lnhat_bwd_kernel(const float* __re
   st8(dZ0 + t * kD + c8, o);
 }
 
-int ml_of(int L) { return L <= 2 ? 2 : (L <= 6 ? L : 8); }
 int cu_count() { return device_cu_count(); }
 
 struct WsView { float* fold; float* bvec; u32x4* frag; float* wslab; float* red; float* colpart; float* dc; };

@@ -1000,14 +1000,16 @@ size_t fused_bwd_ws_floats(int64_t B, int L) {
 }
 
 // merged heads: fused_bwdh_kernel -> fbm_chain_kernel -> the LayerNorm un-folding of launch_fused_bwd (one slab per head)
-int launch_fused_bwd_merged(const matcha_tensors& p, const float* folded, const float* merged, const float* X, const float* dDyn, const float* dXs,
-                            const Ragged& rg, int64_t B, int L, float* dxh, float* ws, matcha_tensors& grads, float* dZ0, hipStream_t st, const float* rimg,
-                            bool dx_atomic, bool dx_zeroed, const TailReduceArgs* tail, const int32_t* xrow, const float* xhatN, const float* rn, int64_t rn_rows, const float* vn) {
+int launch_fused_bwd_merged(const matcha_tensors& p, const Ragged& rg, int64_t B, int L, const FusedBwdLaunch& a, matcha_tensors& grads, hipStream_t st) {
   const int64_t tcap = B * L + 1;
+  const float *folded = a.folded, *X = a.x.X, *xhatN = a.x.xhat, *rn = a.x.rn, *vn = a.x.vn, *dXs = a.dXs;
+  const int32_t* xrow = a.x.xrow;
+  const bool dx_atomic = a.dx_atomic;
+  float *dxh = a.dxh, *ws = a.ws;
   MATCHA_CHECK_ARG(!xrow || xhatN, "fused backward: the node route needs the table of normalised rows");
   MATCHA_CHECK_ARG(!rn || xrow, "fused backward: the r table belongs to the node route");
   MATCHA_CHECK_ARG(!vn || rn, "fused backward: the value table needs the r table");
-  if (dx_atomic && !dx_zeroed) MATCHA_TRY(zero_async(dxh, (size_t)tcap * 64 * sizeof(float), st));
+  if (dx_atomic && !a.dx_zeroed) MATCHA_TRY(zero_async(dxh, (size_t)tcap * 64 * sizeof(float), st));
   int nchunks = 2 * chunks_for(rg.nhalves);                  // two four-wave workgroups per CU
   if (nchunks > kMaxChunks) nchunks = kMaxChunks;
   if (nchunks > rg.nhalves) nchunks = rg.nhalves > 0 ? rg.nhalves : 1;
@@ -1016,12 +1018,12 @@ int launch_fused_bwd_merged(const matcha_tensors& p, const float* folded, const 
   float* part = ws + (size_t)MATCHA_N_HEAD * kMaxChunks * kWgSlab;
   float* dxpad = part + 32 * 3 * 3 * 64;
   const size_t wsz = (size_t)MATCHA_N_HEAD * 64 * 64, csz = (size_t)MATCHA_N_HEAD * 64;
-  const MergedView mv = merged_view(merged);
+  const MergedView mv = merged_view(a.merged);
   {
     FusedBwdHArgs g;
-    g.X = xrow ? xhatN : X; g.dDyn = dDyn; g.count = rg.count; g.half_meta = rg.half_meta; g.tok_pos = rg.tok_pos; g.L = L; g.nhalves = rg.nhalves; g.nchunks = nchunks;
-    g.mB = mv.B; g.mM = mv.M; g.dxh = dxh; g.tcap = tcap; g.dx_atomic = dx_atomic ? 1 : 0; g.wslab = wslab; g.rimg = rimg; g.xrow = xrow;
-    g.rn = rn; g.rn_head = rn_rows * 64; g.vn = vn;
+    g.X = xrow ? xhatN : X; g.dDyn = a.dDyn; g.count = rg.count; g.half_meta = rg.half_meta; g.tok_pos = rg.tok_pos; g.L = L; g.nhalves = rg.nhalves; g.nchunks = nchunks;
+    g.mB = mv.B; g.mM = mv.M; g.dxh = dxh; g.tcap = tcap; g.dx_atomic = dx_atomic ? 1 : 0; g.wslab = wslab; g.rimg = a.rimg; g.xrow = xrow;
+    g.rn = rn; g.rn_head = a.x.rows * 64; g.vn = vn;
     const size_t lds = kBwdLdsBytes;
     auto launch = [&](auto kfn) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1037,14 +1039,10 @@ int launch_fused_bwd_merged(const matcha_tensors& p, const float* folded, const 
     // plain shuffles and unpinned loads did not cure it; -fno-slp-vectorize (no packed f32 in that loop) does -- 0 differing workgroups in
     // every run -- and is faster.  The Makefile sets the flag for the whole library; tests/test_hip_properties.py::test_full_size_train_step_is_reproducible
     // is the run-time guard.
-    switch (L <= 2 ? 2 : (L <= 6 ? L : 8)) {
-      case 2: if (vn) launch(fused_bwdh_kernel<2, true, true>); else if (xrow) launch(fused_bwdh_kernel<2, true>); else launch(fused_bwdh_kernel<2, false>); break;
-      case 3: if (vn) launch(fused_bwdh_kernel<3, true, true>); else if (xrow) launch(fused_bwdh_kernel<3, true>); else launch(fused_bwdh_kernel<3, false>); break;
-      case 4: if (vn) launch(fused_bwdh_kernel<4, true, true>); else if (xrow) launch(fused_bwdh_kernel<4, true>); else launch(fused_bwdh_kernel<4, false>); break;
-      case 5: if (vn) launch(fused_bwdh_kernel<5, true, true>); else if (xrow) launch(fused_bwdh_kernel<5, true>); else launch(fused_bwdh_kernel<5, false>); break;
-      case 6: if (vn) launch(fused_bwdh_kernel<6, true, true>); else if (xrow) launch(fused_bwdh_kernel<6, true>); else launch(fused_bwdh_kernel<6, false>); break;
-      default: if (vn) launch(fused_bwdh_kernel<8, true, true>); else if (xrow) launch(fused_bwdh_kernel<8, true>); else launch(fused_bwdh_kernel<8, false>); break;
-    }
+    dispatch_ml(L, [&](auto ml) {       // <ML, NODE, VTAB>: per token, per node, per node with the value table
+      constexpr int ML = decltype(ml)::value;
+      if (vn) launch(fused_bwdh_kernel<ML, true, true>); else if (xrow) launch(fused_bwdh_kernel<ML, true>); else launch(fused_bwdh_kernel<ML, false>);
+    });
     MATCHA_CHECK_LAUNCH("fused_bwdh_kernel");
   }
   {
@@ -1053,8 +1051,8 @@ int launch_fused_bwd_merged(const matcha_tensors& p, const float* folded, const 
     c.wq = folded; c.wk = folded + wsz; c.wv = folded + 2 * wsz; c.cq = folded + 3 * wsz; c.cv = c.cq + 2 * csz;
     c.fc1_w = p.fc1_w; c.out = chain; c.dxpad = dxpad;
     TailReduceArgs tl;
-    if (tail) tl = *tail; else memset(&tl, 0, sizeof(tl));
-    const int tail_blocks = tail ? kTailRoleBlocks : 0;
+    if (a.tail) tl = *a.tail; else memset(&tl, 0, sizeof(tl));
+    const int tail_blocks = a.tail ? kTailRoleBlocks : 0;
     hipLaunchKernelGGL(fbm_reduce_kernel, dim3((unsigned)(kFbmReduceBlocks + tail_blocks)), dim3(256), 0, st, c, tl, tail_blocks);
     MATCHA_CHECK_LAUNCH("fbm_reduce_kernel");
     hipLaunchKernelGGL(fbm_chain_kernel, dim3(4, 4, MATCHA_N_HEAD), dim3(256), 0, st, c);
@@ -1078,7 +1076,7 @@ int launch_fused_bwd_merged(const matcha_tensors& p, const float* folded, const 
     hipLaunchKernelGGL(fb_unfold2_kernel, dim3(1), dim3(512), 0, st, b);
     MATCHA_CHECK_LAUNCH("fb_unfold2_kernel");
   }
-  if (dZ0) {
+  if (float* dZ0 = a.dZ0) {
     MATCHA_CHECK_ARG(!xrow, "fused backward: the node route has no dZ0 output");
     hipLaunchKernelGGL(lnhat_bwd_kernel, dim3((unsigned)cdiv(tcap, 16)), dim3(256), 0, st, X, dxh, tcap, dxpad, dXs, dZ0, rg.count, dx_atomic ? 1 : MATCHA_N_HEAD);
     MATCHA_CHECK_LAUNCH("lnhat_bwd_kernel");

@@ -725,6 +725,7 @@ int launch_node_r(const float* XN, const float* frag, int64_t rows, float* rn, h
 
 static int fwd32h_max_halves() { return 2 * device_cu_count(); }
 
+// the ONE definition of the size rule; the step's route calls it once (model.hip, decide_route) and hands the answer to the launcher below
 bool fused_small_batch(const Ragged& rg) { return rg.nhalves <= fwd32h_max_halves() && !options().disable_small_batch; }
 
 size_t fused_frag_floats() { return (size_t)(kNMat + 1) * kFragU4 * 4 + (size_t)kNBias * 64; }
@@ -753,58 +754,38 @@ int launch_prep_heads(const matcha_tensors& p, float* folded, float* merged, flo
   return MATCHA_OK;
 }
 
-int launch_fused_fwd32(const matcha_tensors& p, const float* folded, const float* frag, const float* X, const Ragged& rg, int64_t B, int L, const float* y,
-                       const float* w, float* Y, float* H1, float* H2, float* logits, float* row_loss, const uint64_t* seed, float p_fc1, float p_pff,
-                       hipStream_t st, float* ddyn0, float* dXs, float* tslab, float alpha, float* rimg, float* tail_dh2, int objective, const int32_t* xrow,
-                       const float* rn, int64_t rn_rows) {
+int launch_fused_fwd32(const matcha_tensors& p, const Ragged& rg, int64_t B, int L, const FusedFwdLaunch& a, hipStream_t st) {
   Fwd32Args g;
-  g.xrow = xrow;
-  MATCHA_CHECK_ARG(!rn || xrow, "fused forward: the r table belongs to the node route");
-  g.rn = rn; g.rn_rows = (int)rn_rows;
+  g.xrow = a.x.xrow;
+  MATCHA_CHECK_ARG(!a.x.rn || a.x.xrow, "fused forward: the r table belongs to the node route");
+  g.rn = a.x.rn; g.rn_rows = (int)a.x.rows;
   g.tail_dh2 = nullptr;
-  g.X = X; g.row_off = rg.row_off; g.tok_slot = rg.tok_slot; g.count = rg.count; g.half_meta = rg.half_meta; g.tok_pos = rg.tok_pos;
+  g.X = a.x.X; g.row_off = rg.row_off; g.tok_slot = rg.tok_slot; g.count = rg.count; g.half_meta = rg.half_meta; g.tok_pos = rg.tok_pos;
   g.L = L;
-  g.wfrag = reinterpret_cast<const u32x4*>(frag);
-  (void)folded;
+  g.wfrag = reinterpret_cast<const u32x4*>(a.frag);
   g.hp = HeadParams{p.pff_ln_g, p.pff_ln_b, p.ln1_g, p.ln1_b, p.ln2_g, p.ln2_b, p.cls_w, p.cls_b};
-  const bool target = objective == MATCHA_OBJECTIVE_SOFTPLUS_MSE ? y != nullptr : (y && w);
-  g.objective = objective;
-  g.y = y; g.w = w; g.Y = Y; g.H1 = H1; g.H2 = H2; g.logits = logits; g.row_loss = target ? row_loss : nullptr;
-  g.seed = seed; g.p_fc1 = p_fc1; g.p_pff = p_pff;
-  g.ddyn0 = target ? ddyn0 : nullptr; g.dXs = dXs; g.tslab = tslab; g.alpha_over_B = alpha / (float)B; g.qkv = rimg;
-  size_t lds = ((size_t)2 * kHT + 64) * sizeof(float);
-  auto launch = [&](auto kfn) { hipLaunchKernelGGL(kfn, dim3(rg.nhalves), dim3(64), lds, st, g); };
+  const bool target = a.objective == MATCHA_OBJECTIVE_SOFTPLUS_MSE ? a.y != nullptr : (a.y && a.w);
+  g.objective = a.objective;
+  g.y = a.y; g.w = a.w; g.Y = a.Y; g.H1 = a.H1; g.H2 = a.H2; g.logits = a.logits; g.row_loss = target ? a.row_loss : nullptr;
+  g.seed = a.seed; g.p_fc1 = a.p_fc1; g.p_pff = a.p_pff;
+  g.ddyn0 = target ? a.ddyn0 : nullptr; g.dXs = a.dXs; g.tslab = a.tslab; g.alpha_over_B = a.alpha / (float)B; g.qkv = a.rimg;
   // algorithmic flops per token (the reference formulation's): 8 heads x 4 GEMMs (Q, K, V, fc1 block) + the two pff GEMMs, 2*64*64 each
   ProfScope ps(MATCHA_PROF_FUSED_FWD, (double)(B * L + 1) * (MATCHA_N_HEAD * 4.0 + 2.0) * 2.0 * 64.0 * 64.0, st);
-  const int ml = L <= 2 ? 2 : (L <= 6 ? L : 8);
   // small batches (at most two half tiles per CU even at the bound): the heads side by side in eight wavefronts per half tile
-  if (fused_small_batch(rg)) {
-    MATCHA_CHECK_ARG(!xrow, "fused forward: the node route runs the large-batch kernel only");
+  if (a.small) {
+    MATCHA_CHECK_ARG(!a.x.xrow, "fused forward: the node route runs the large-batch kernel only");
     const size_t ldsh = ((size_t)10 * kHT + 64) * sizeof(float);
-    auto launchh = [&](auto kfn) {
+    dispatch_ml(L, [&](auto ml) {
+      auto kfn = fused_fwd32h_kernel<decltype(ml)::value>;
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsh);
       hipLaunchKernelGGL(kfn, dim3(rg.nhalves), dim3(512), ldsh, st, g);
-    };
-    switch (ml) {
-      case 2: launchh(fused_fwd32h_kernel<2>); break;
-      case 3: launchh(fused_fwd32h_kernel<3>); break;
-      case 4: launchh(fused_fwd32h_kernel<4>); break;
-      case 5: launchh(fused_fwd32h_kernel<5>); break;
-      case 6: launchh(fused_fwd32h_kernel<6>); break;
-      default: launchh(fused_fwd32h_kernel<8>); break;
-    }
+    });
     MATCHA_CHECK_LAUNCH("fused_fwd32h_kernel");
     return MATCHA_OK;
   }
-  g.tail_dh2 = g.ddyn0 ? tail_dh2 : nullptr;
-  switch (ml) {
-    case 2: launch(fused_fwd32_kernel<2>); break;
-    case 3: launch(fused_fwd32_kernel<3>); break;
-    case 4: launch(fused_fwd32_kernel<4>); break;
-    case 5: launch(fused_fwd32_kernel<5>); break;
-    case 6: launch(fused_fwd32_kernel<6>); break;
-    default: launch(fused_fwd32_kernel<8>); break;
-  }
+  g.tail_dh2 = g.ddyn0 ? a.tail_dh2 : nullptr;
+  const size_t lds = ((size_t)2 * kHT + 64) * sizeof(float);
+  dispatch_ml(L, [&](auto ml) { hipLaunchKernelGGL(fused_fwd32_kernel<decltype(ml)::value>, dim3(rg.nhalves), dim3(64), lds, st, g); });
   MATCHA_CHECK_LAUNCH("fused_fwd32_kernel");
   return MATCHA_OK;
 }

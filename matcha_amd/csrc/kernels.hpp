@@ -159,12 +159,30 @@ size_t fused_merged_floats();
 struct MergedView { const float* B; const float* M; const float* bvec; const float* bdyn; };
 MergedView merged_view(const float* merged);
 int launch_prep_heads(const matcha_tensors& p, float* folded, float* merged, float* frag, hipStream_t st);     // the three per-step weight forms, one launch
-int launch_fused_fwd32(const matcha_tensors& p, const float* folded, const float* frag, const float* X, const Ragged& rg, int64_t B, int L, const float* y,
-                       const float* w, float* Y, float* H1, float* H2, float* logits, float* row_loss, const uint64_t* seed, float p_fc1, float p_pff,
-                       hipStream_t st, float* ddyn0 = nullptr, float* dXs = nullptr, float* tslab = nullptr, float alpha = 0.f, float* rimg = nullptr,
-                       float* tail_dh2 = nullptr, int objective = MATCHA_OBJECTIVE_BCE,
-                       const int32_t* xrow = nullptr,        // xrow (large batches only): X is a per-node table, token t reads row xrow[t];  tail_dh2 (large batches only): the convolutions' backward is left to launch_tail_bwd64
-                       const float* rn = nullptr, int64_t rn_rows = 0);      // rn (with xrow): the heads' r rows per node [8][rn_rows][64] (launch_node_r) -- gathered, not computed per token
+// Node route of the table front end: what the encoder kernels read in place of the per-token X.  Filled in one place (model.hip, node_operands)
+// and shared by the forward and the backward launcher; off the route X is the per-token buffer and every other pointer is null.
+struct NodeOperands {
+  float* X;              // X per token [B L + 1][64], or on the route the per-node table [rows][64] (row 0: the padding id)
+  const int32_t* xrow;   // on the route: token t reads row xrow[t] of the tables (the plan's sanitised id, Ragged::tok_key); null off it
+  float* xhat;           // ... the table's normalised rows, staged as they are by the backward kernel (null in a forward-only layout)
+  float* rn;             // ... the heads' r rows per node [8][rows][64] (launch_node_r): gathered, not computed per token; null: per token, rows in the record
+  float* vn;             // ... with rn: their value rows y = M_h x_hat, same shape -- the backward's VTAB instance, no dZ product; null: dZ / Z per token
+  int64_t rows;          // n_nodes + 1
+};
+struct FusedFwdLaunch {
+  const float* frag;     // this step's weights in MFMA-fragment order (launch_prep_heads / the front end's launch)
+  NodeOperands x;
+  bool small;            // the small-batch kernel (fused_small_batch, decided by the caller): no node route, no split tail
+  const float *y, *w;    // targets (null: no loss)
+  int objective;
+  float *Y, *H1, *H2;    // saved for the backward, or parked between the halves of the in-kernel tail backward (null: a forward only)
+  float *logits, *row_loss;
+  const uint64_t* seed; float p_fc1, p_pff;
+  float *ddyn0, *dXs, *tslab; float alpha;   // ddyn0 != null: the tail's backward runs in the kernel (needs targets)
+  float* rimg;           // r rows + probabilities per (half tile, head) for the fused backward (null: a forward only)
+  float* tail_dh2;       // large batches only: the convolutions' backward is left to launch_tail_bwd64
+};
+int launch_fused_fwd32(const matcha_tensors& p, const Ragged& rg, int64_t B, int L, const FusedFwdLaunch& a, hipStream_t st);
 // the r rows of every (head, node): rows of the per-node table XN -> RN[8][rows][64]; needs this step's fragment stream (launch_prep_heads / the front end's launch)
 // vn != null: the same launch also writes the value rows y = M_h x_hat (no bias) -> VN[8][rows][64] for the backward's VTAB instance
 size_t node_r_floats(int64_t rows);
@@ -180,13 +198,18 @@ int launch_tail_bwd64(const matcha_tensors& p, const float* dH2, const float* Y,
 // three LayerNorm affines in front of them, fc1 (weight + bias) and writes dZ0 (gradient at the next_w pre-activation)
 size_t fused_bwd_ws_floats(int64_t B, int L);
 struct TailReduceArgs;
-int launch_fused_bwd_merged(const matcha_tensors& p, const float* folded, const float* merged, const float* X, const float* dDyn, const float* dXs,
-                            const Ragged& rg, int64_t B, int L, float* dxh, float* ws, matcha_tensors& grads, float* dZ0, hipStream_t st, const float* rimg,
-                            bool dx_atomic, bool dx_zeroed = false,    // dx_zeroed: the caller already zeroed dxh[(B L + 1) x 64] on this stream
-                            const struct TailReduceArgs* tail = nullptr, const int32_t* xrow = nullptr, const float* xhatN = nullptr,
-                            const float* rn = nullptr, int64_t rn_rows = 0,       // rn (with xrow): the forward gathered r from this table and left no r rows in the record
-                            const float* vn = nullptr);                           // vn (with rn): the value table y = M_h x_hat [8][rn_rows][64] -- the VTAB instance, no dZ product
-// xrow != null (with xhatN): X is the per-node table (row 0 = padding) and xhatN its normalised rows; token t stages row xrow[t] of xhatN as it is;  tail != null: the launch that sums this kernel's slabs also sums the forward's tail slabs (tail_reduce.hpp)
+struct FusedBwdLaunch {
+  const float *folded, *merged;   // the forward left the step's weight forms here
+  NodeOperands x;                 // on the node route token t stages row xrow[t] of xhat as it is
+  const float *dDyn, *dXs;
+  const float* rimg;              // the forward's record per (half tile, head)
+  float* dxh;                     // d x_hat: one buffer the heads add into (dx_atomic) or eight per-head slabs
+  float* ws;                      // fused_bwd_ws_floats()
+  float* dZ0;                     // null: the fused front-end backward follows (always on the node route)
+  bool dx_atomic, dx_zeroed;      // dx_zeroed: the caller already zeroed dxh[(B L + 1) x 64] on this stream
+  const TailReduceArgs* tail;     // != null: the launch that sums this kernel's slabs also sums the forward's tail slabs (tail_reduce.hpp)
+};
+int launch_fused_bwd_merged(const matcha_tensors& p, const Ragged& rg, int64_t B, int L, const FusedBwdLaunch& a, matcha_tensors& grads, hipStream_t st);
 size_t fused_qkv_floats(int64_t B, int L);         // what the training forward leaves for the fused backward, per (half tile, head):
 constexpr int kImgRecH = 2048 + 256;               // 32 r rows (r = B_h x_hat + b_h; register images) + their attention probabilities [32][8].
                                                    // (Round 6 measured the alternative -- the forward keeps only the probabilities, fused_bwdh_kernel recomputes r from its

@@ -162,18 +162,13 @@ static bool merged_layerwise_shape(const matcha_shape& s) { return s.d >= 128 &&
 static bool merged_layerwise(const matcha_shape& s) { return merged_layerwise_shape(s) && attn_wide_eligible(s.d) && !options().disable_merged; }
 // embed_dim 128: attention block as one fused forward / backward kernel pair (enc128.hip).  The heads' d x_hat meet through float atomics, so the
 // callers that need a bitwise reproducible embedding gradient stay on the layer-by-layer kernels.
-static bool enc128_enabled(const matcha_shape& s, const matcha_step_opts& o) {
-  return enc128_shape(s.d) && merged_layerwise(s) && options().disable_fused != 1 && !o.deterministic && !o.sparse_table_grad;
-}
+static bool enc128_enabled(const matcha_shape& s, const matcha_step_opts& o) { return enc128_shape(s.d) && merged_layerwise(s) && options().disable_fused != 1 && !o.deterministic && !o.sparse_table_grad; }
 static bool fused_enabled(const matcha_shape& s) { return s.d == 64 && options().disable_fused != 1 && !options().disable_merged; }
-static bool fused_front_enabled() { return (options().disable_fused & 2) == 0; }
 // Node route of the table front end: everything in front of the encoder -- x0 = table[id] + attribute_nn(attr[id]), X = tanh(next_w(x0)) -- is a
 // function of the node id alone (no dropout in front of the attention), so when the tokens outnumber the nodes it is computed once per NODE
 // and the encoder kernels gather their rows by id; the backward adds the tokens' gradient rows per node first and runs tanh' / next_w /
 // attribute_nn / the table row once per node.  The SHAPE half of the rule (it sizes the workspace, so it must not depend on a switch):
-static bool node_front_shape(const matcha_shape& s, int64_t B, int L) {
-  return s.mode == 0 && s.d == 64 && front_bwd_supported(s.d, s.n_attr) && B * L + 1 >= 4 * ((int64_t)s.n_nodes + 1);
-}
+static bool node_front_shape(const matcha_shape& s, int64_t B, int L) { return s.mode == 0 && s.d == 64 && front_bwd_supported(s.d, s.n_attr) && B * L + 1 >= 4 * ((int64_t)s.n_nodes + 1); }
 // ... and the value table of that route (VN: y = M_h x_hat per node for the backward, fused_bwd.hip VTAB) on top of the r table.  It costs
 // node_r_kernel's V role per NODE and saves the backward kernel work per TOKEN.  Measured against the parent's library at hg38 1 Mb (3 068
 // table rows), same call, three alternations: no difference that the runs' own spread lets through at 8 192, 16 384 and 32 768 rows (capacity /
@@ -181,22 +176,34 @@ static bool node_front_shape(const matcha_shape& s, int64_t B, int L) {
 static bool node_v_shape(const matcha_shape& s, int64_t B, int L) { return B * L + 1 >= 64 * ((int64_t)s.n_nodes + 1); }
 // the loss can be computed: BCE needs labels and weights, the softplus MSE only its targets
 static bool has_target(int objective, const float* y, const float* w) { return objective == MATCHA_OBJECTIVE_SOFTPLUS_MSE ? y != nullptr : (y && w); }
-static bool loss_in_forward(const matcha_shape& s, const matcha_step_opts& o, const float* y, const float* w, int objective) {
-  return o.loss_in_forward && !o.forward_only && has_target(objective, y, w) && fused_enabled(s);
-}
 static int check_objective(int32_t objective, const char* fn) {
   if (objective == MATCHA_OBJECTIVE_BCE || objective == MATCHA_OBJECTIVE_SOFTPLUS_MSE) return MATCHA_OK;
   set_error("%s: unknown objective %d (MATCHA_OBJECTIVE_BCE or MATCHA_OBJECTIVE_SOFTPLUS_MSE)", fn, (int)objective);
   return MATCHA_EINVAL;
 }
-// Which formulation the forward that last ran on a workspace used.  matcha_backward keys off THIS record, not off the option: flipping
-// disable_merged between a forward and its backward (two separate calls on the autograd path) would otherwise make the merged backward
-// consume records nobody wrote.  Host-side record per workspace pointer (the decision picks a kernel, so it cannot live in device memory
-// without a synchronisation); bounded, evicted oldest-first, guarded by a mutex.  A backward on a workspace WITHOUT a record is refused.
+// The kernel route of one step: every decision of the forward that a later line of it, or the backward on the same workspace, depends on.
+// decide_route (behind the workspace layout it reads) fills it ONCE per forward -- it and the predicates above are the only routing code that
+// reads the option table -- and the record below hands it to matcha_backward as it is.
+struct StepRoute {
+  bool compact;                  // workspace layout of a forward that will not be differentiated (carve)
+  bool half_plan;                // the ragged plan stops at the half tiles (level 1: no 64-row tile list, no token -> tile map)
+  bool fused;                    // embed_dim 64: X -> logits in one forward kernel, the attention block's backward in one (fused_fwd32.hip, fused_bwd.hip)
+  bool merged_layerwise, enc128; // layer by layer at embed_dim >= 128: merged heads;  at 128 the attention block as ONE kernel pair (enc128.hip)
+  bool front, adj_fused;         // fused front end and its backward (front_fused.hip);  the adj front end as ONE kernel over the chromosome-sorted rows (adj_fused.hip)
+  bool small;                    // the small-batch kernels (fused_small_batch)
+  bool lif;                      // the tail's backward ran inside the forward kernel: Y / H1 / H2 hold parked rows, ddyn0 and dXs are final
+  bool split_tail, dx_zeroed;    // ... up to its LayerNorms, the convolutions' as tail_bwd64_kernel;  the forward zeroed the d x_hat rows the backward's heads add into
+  bool node;                     // table front end per NODE: X lives in the per-node table, rows by tok_key
+  bool node_r, node_v;           // ... the heads' r rows gathered from the per-node table (none in the record);  ... and the value table VN left for the backward
+};
+// Which route the forward that last ran on a workspace took.  matcha_backward keys off THIS record and reads no option: the two calls are
+// separate on the autograd path and the switches are process-wide, so a flip between them would otherwise make the backward consume records
+// nobody wrote.  Host-side record per workspace pointer (the decision picks a kernel, so it cannot live in device memory without a
+// synchronisation); bounded, evicted oldest-first, guarded by a mutex.  A backward on a workspace WITHOUT a record is refused.
 static std::mutex g_fwd_mu;
-static std::unordered_map<const void*, std::pair<int, uint64_t>> g_fwd_state;     // ws -> (bits, age); bit 0: merged heads, bit 1: fused d = 64 forward, bit 2: fused d = 128 attention block, bit 3: the tail's backward ran as tail_bwd64_kernel, bit 4: the forward zeroed the d x_hat rows of the backward kernel, bit 5: the front end ran per node (node route), bit 6: ... and the forward gathered the heads' r rows from the per-node table (no r rows in the record), bit 7: ... and left the value table VN for the backward
+static std::unordered_map<const void*, std::pair<StepRoute, uint64_t>> g_fwd_state;     // ws -> (route, age)
 static uint64_t g_fwd_clock = 0;
-static void note_forward(const void* ws, bool merged, bool fused, bool enc = false, bool split_tail = false, bool dx_zeroed = false, bool node = false, bool node_r = false, bool node_v = false) {
+static void note_forward(const void* ws, const StepRoute& route) {
   std::lock_guard<std::mutex> lk(g_fwd_mu);
   if (g_fwd_state.size() >= 4096 && g_fwd_state.find(ws) == g_fwd_state.end()) {
     auto old = g_fwd_state.begin();
@@ -204,12 +211,13 @@ static void note_forward(const void* ws, bool merged, bool fused, bool enc = fal
       if (it->second.second < old->second.second) old = it;
     g_fwd_state.erase(old);
   }
-  g_fwd_state[ws] = std::make_pair((merged ? 1 : 0) | (fused ? 2 : 0) | (enc ? 4 : 0) | (split_tail ? 8 : 0) | (dx_zeroed ? 16 : 0) | (node ? 32 : 0) | (node_r ? 64 : 0) | (node_v ? 128 : 0), ++g_fwd_clock);
+  g_fwd_state[ws] = std::make_pair(route, ++g_fwd_clock);
 }
-static int ws_state(const void* ws) {       // -1: no forward on record for this workspace
+static bool recorded_route(const void* ws, StepRoute& route) {       // false: no forward on record for this workspace
   std::lock_guard<std::mutex> lk(g_fwd_mu);
   auto it = g_fwd_state.find(ws);
-  return it != g_fwd_state.end() ? it->second.first : -1;
+  if (it != g_fwd_state.end()) route = it->second.first;
+  return it != g_fwd_state.end();
 }
 // The record of a workspace is dropped by a forward_only forward on it (which keeps nothing a backward could read and overwrites what an
 // earlier training forward left there) and by the backward that consumed it (matcha_backward overwrites the saved activations with their
@@ -328,6 +336,47 @@ static size_t carve(const matcha_shape& s, int64_t B, int L, char* base, Workspa
   }
   w.total = off;
   return off;
+}
+
+// a forward with opts->forward_only set on the fused kernels needs no more than the compact layout; settled before carve(), which it sizes
+static bool compact_forward(const matcha_shape& s, const matcha_step_opts& o, bool force_layerwise) { return !force_layerwise && o.forward_only && fused_enabled(s); }
+// The route of one forward, from shapes, per-call options and the option table alone -- no device state, so a captured step replays it.  force_layerwise:
+// the separate kernels whatever the shape (matcha_get_embedding needs H2 and X in HBM);  want_losses: the caller passed `losses`.
+static StepRoute decide_route(const matcha_shape& s, const matcha_step_opts& o, int64_t B, int L, const Workspace& w, const matcha_frozen& f,
+                              const float* y, const float* w_bce, int objective, bool force_layerwise, bool want_losses) {
+  StepRoute r;
+  r.compact = compact_forward(s, o, force_layerwise);
+  r.fused = !force_layerwise && fused_enabled(s);
+  r.merged_layerwise = merged_layerwise(s);
+  // embed_dim 128: the attention block as one kernel (enc128.hip) -- when a training forward's records fit where the layer-wise path keeps
+  // Q / K / V / P / O: the records are sized per HALF TILE (at least two, 8 x 4352 floats each), so a batch of one to three rows does not
+  // fit and runs layer by layer (ADVICE r05: it used to fail with MATCHA_ENOMEM)
+  r.enc128 = !force_layerwise && enc128_enabled(s, o) && (o.forward_only || enc128_rec_floats(w.rg) <= w.enc_rec_floats);
+  // CSR plan: real tokens + one shared padding token; the fused kernels walk the HALF tiles (matcha_ragged_plan still builds the 64-row tiles
+  // for callers that ask).  Follows the shape, not force_layerwise: the layer-by-layer kernels read neither tiling
+  r.half_plan = fused_enabled(s) || r.enc128;
+  r.front = r.fused && front_bwd_supported(s.d, s.n_attr) && (options().disable_fused & 2) == 0;
+  r.adj_fused = r.front && s.mode == 1 && adj_fused_eligible(s, f);
+  r.small = r.fused && fused_small_batch(w.rg);
+  // node route (node_front_shape), large-batch kernels only.  Its backward adds the tokens' gradient rows per node with float atomics and leaves
+  // no row per TOKEN, so `deterministic` and the row-sparse table gradient (whose sum is bitwise reproducible) stay on the per-token front end
+  const bool atomics = !o.deterministic && !o.sparse_table_grad;
+  r.node = r.front && node_front_shape(s, B, L) && !r.small && atomics && !options().disable_node_front;
+  r.node_r = r.node && !options().disable_node_r;      // ... with the heads' r rows once per node
+  r.node_v = r.node_r && !o.forward_only && w.VN && node_v_shape(s, B, L) && !options().disable_node_v;      // ... and, for the backward alone, their value rows
+  r.lif = r.fused && o.loss_in_forward && !o.forward_only && has_target(objective, y, w_bce);
+  // large batches: the tail's backward inside the forward kernel stops behind its LayerNorms; pff_n1's two convolutions (dZ1, d dyn, the
+  // weight gradients) are a kernel of their own right behind it (tail_bwd.hip).  Development switch fused_dbg bit 0: all of it in-kernel.
+  r.split_tail = r.lif && !r.small && (options().fused_dbg & 1) == 0;
+  // the backward kernel's heads ADD their d x_hat rows (float atomics) unless the sum has to be reproducible: the rows are zeroed by a launch
+  // that runs anyway -- tail_bwd64_kernel, or for small batches the loss reduction's (which needs `losses`) -- and the record says so
+  r.dx_zeroed = r.lif && atomics && (r.split_tail || r.small) && want_losses;
+  return r;
+}
+// what the encoder kernels and head_bwd read for X on this route (kernels.hpp): the per-node tables by tok_key, or X per token
+static NodeOperands node_operands(const StepRoute& r, const matcha_shape& s, const Workspace& w) {
+  const int64_t rows = (int64_t)s.n_nodes + 1;
+  return r.node ? NodeOperands{w.XN, w.rg.tok_key, w.xhN, r.node_r ? w.RN : nullptr, r.node_v ? w.VN : nullptr, rows} : NodeOperands{w.X, nullptr, nullptr, nullptr, nullptr, rows};
 }
 
 // Table mode, after the backward pass left one gradient row per compact token in w.dX0 (ids in w.rg.tok_key): add them into the
@@ -457,7 +506,6 @@ extern "C" size_t matcha_workspace_bytes(const matcha_shape* shp, int64_t B, int
 }
 
 // a forward with opts->forward_only set needs no more than this (equal to matcha_workspace_bytes when the shape has no fused path)
-static bool compact_forward(const matcha_shape& s, const matcha_step_opts& o) { return o.forward_only && fused_enabled(s); }
 extern "C" size_t matcha_workspace_bytes_forward(const matcha_shape* shp, int64_t B, int32_t L) {
   if (check_shape(shp, B, L) != MATCHA_OK) return 0;
   Workspace w;
@@ -477,7 +525,7 @@ static int forward_impl(const matcha_shape* shp, const matcha_tensors* params, c
   const matcha_tensors& p = *params;
   hipStream_t st = (hipStream_t)stream;
   Workspace w;
-  const size_t need = carve(s, B, L, (char*)ws, w, !force_layerwise && compact_forward(s, *opts));
+  const size_t need = carve(s, B, L, (char*)ws, w, compact_forward(s, *opts, force_layerwise));
   if (ws_bytes < need) { set_error("matcha_forward: workspace %zu < %zu bytes", ws_bytes, need); return MATCHA_ENOMEM; }
   const int64_t Tn = B * L + 1;                 // upper bound; the true count is *w.rg.count
   const int d = s.d;
@@ -492,95 +540,65 @@ static int forward_impl(const matcha_shape* shp, const matcha_tensors* params, c
   const int32_t* cnt = w.rg.count;
   const int64_t* ids = w.rg.tok_id;
 
-  // which fused kernels will run on this workspace (decided here: the plan, the front end and the saved records depend on it)
-  const bool fused_path = !force_layerwise && fused_enabled(s);
+  // which kernels will run on this workspace: decided once, here (the plan, the front end and the saved records depend on it), and recorded
+  const StepRoute route = decide_route(s, *opts, B, L, w, *frozen, y, w_bce, objective, force_layerwise, losses != nullptr);
+  const bool keep = !opts->forward_only;       // a backward may follow: x0, the records and the saved rows are written
+  const NodeOperands nx = node_operands(route, s, w);
   const bool tgt = has_target(objective, y, w_bce);
-  const bool lif = fused_path && loss_in_forward(s, *opts, y, w_bce, objective);      // the tail's backward runs in the forward kernel: nothing saved
-  // a training forward leaves r rows + probabilities per (half tile, head) for fused_bwdh_kernel (merged heads: fused_fwd32.hip)
-  const bool keep_rimg = !opts->forward_only;
-  // CSR plan: real tokens + one shared padding token; the fused kernels walk the HALF tiles (level 1: no 64-row tile list, no token -> tile
-  // map -- matcha_ragged_plan still builds those for callers that ask)
-  // embed_dim 128: the attention block as one kernel (enc128.hip) -- when a training forward's records fit where the layer-wise path keeps
-  // Q / K / V / P / O: the records are sized per HALF TILE (at least two, 8 x 4352 floats each), so a batch of one to three rows does not
-  // fit and runs layer by layer (ADVICE r05: it used to fail with MATCHA_ENOMEM)
-  const bool enc = !force_layerwise && enc128_enabled(s, *opts) && (opts->forward_only || enc128_rec_floats(w.rg) <= w.enc_rec_floats);
-  const int plan_level = (fused_enabled(s) || enc) ? 1 : 0;
-  const bool front = !force_layerwise && fused_enabled(s) && front_bwd_supported(s.d, s.n_attr) && fused_front_enabled();
-  // node route (node_front_shape): decided here from shapes and per-call options alone -- capturable -- and recorded for the backward
-  const bool node = front && fused_path && node_front_shape(s, B, L) && !fused_small_batch(w.rg) && !opts->deterministic && !opts->sparse_table_grad &&
-                    !options().disable_node_front;
-  const bool node_r = node && !options().disable_node_r;      // ... with the heads' r rows once per node (recorded like the route itself)
-  const bool node_v = node_r && !opts->forward_only && w.VN && node_v_shape(s, B, L) && !options().disable_node_v;      // ... and, for the backward alone, their value rows
-  MATCHA_TRY(launch_ragged_plan(x, B, L, s.n_nodes, opts->status, w.rg, st, plan_level, node ? w.node_ids : nullptr, node ? w.node_cnt : nullptr,
-                                (node && !opts->forward_only) ? w.GN : nullptr));      // ... which also writes the node route's id list and zeroes its accumulator
+  MATCHA_TRY(launch_ragged_plan(x, B, L, s.n_nodes, opts->status, w.rg, st, route.half_plan ? 1 : 0, route.node ? w.node_ids : nullptr, route.node ? w.node_cnt : nullptr,
+                                (route.node && keep) ? w.GN : nullptr));      // ... which also writes the node route's id list and zeroes its accumulator
   // front end: node rows (K1) + attribute path (K6) + add (Modules.py:263-269)
   float* recon_out = losses ? losses + 1 : nullptr;
   // table front end: the two reconstruction-loss slots are zero; loss_reduce_kernel writes them when it runs anyway
-  const bool recon_zero_in_loss = s.mode == 0 && recon_out && fused_path && tgt && losses;
-  // adj front end at embed_dim 64: gather-GEMM, W1, attribute path and next_w in ONE kernel over the chromosome-sorted rows (adj_fused.hip)
-  const bool adj_fused = front && fused_path && s.mode == 1 && adj_fused_eligible(s, *frozen);
+  const bool recon_zero_in_loss = s.mode == 0 && recon_out && route.fused && tgt;
   if (s.mode == 0) {
     MATCHA_CHECK_ARG(p.table, "matcha_forward: table mode without table");
     if (recon_out && !recon_zero_in_loss) MATCHA_TRY(zero_async(recon_out, 2 * sizeof(float), st));
-  } else if (adj_fused) {
-    MATCHA_TRY(adj_forward(s, p, *frozen, *opts, ids, Tn, nullptr, recon_out, w.adj_ws, w.adj_ws_bytes, st, cnt, w.rg.tok_slot,
-                           opts->forward_only ? nullptr : w.x0, w.X, !opts->forward_only));
+  } else if (route.adj_fused) {
+    MATCHA_TRY(adj_forward(s, p, *frozen, *opts, ids, Tn, nullptr, recon_out, w.adj_ws, w.adj_ws_bytes, st, cnt, w.rg.tok_slot, keep ? w.x0 : nullptr, w.X, keep));
   } else {
     MATCHA_TRY(adj_forward(s, p, *frozen, *opts, ids, Tn, w.node, recon_out, w.adj_ws, w.adj_ws_bytes, st, cnt, w.rg.tok_slot));
   }
-  bool prep_in_front = false;
-  if (adj_fused) {
-    // x0 and X are already there
-  } else if (front) {
+  const bool prep_in_front = route.front && !route.adj_fused;      // (adj_fused: x0 and X are already there)
+  if (prep_in_front) {
     // gather (or the adj front end's rows) + attribute path + add + next_w + tanh in one kernel (Modules.py:263-270)
     // (fused encoder behind it: the launch also builds the step's weight forms -- folded / merged / fragment-order -- in blocks of their own)
     const PrepSpec prep = {&p, w.folded, w.merged, w.frag};
-    prep_in_front = fused_path;
-    if (node) {     // the same kernel, once over the ids 0..n_nodes: the per-node tables (the weight-form blocks keep riding in the launch)
-      MATCHA_TRY(launch_front_fwd(p, w.node_ids, p.table, nullptr, *frozen, s.n_attr, w.rg, (int64_t)s.n_nodes + 1, opts->forward_only ? nullptr : w.x0N, w.XN, st,
-                                  prep_in_front ? &prep : nullptr, w.node_cnt));
+    if (route.node) {     // the same kernel, once over the ids 0..n_nodes: the per-node tables (the weight-form blocks keep riding in the launch)
+      MATCHA_TRY(launch_front_fwd(p, w.node_ids, p.table, nullptr, *frozen, s.n_attr, w.rg, nx.rows, keep ? w.x0N : nullptr, nx.X, st, &prep, w.node_cnt));
       // ... and, for the backward kernel's staging, their normalised rows
-      if (!opts->forward_only) MATCHA_TRY(launch_node_xhat(w.XN, w.node_cnt, (int64_t)s.n_nodes + 1, w.xhN, st));
+      if (keep) MATCHA_TRY(launch_node_xhat(nx.X, w.node_cnt, nx.rows, nx.xhat, st));
       // ... and the heads' r rows, from the fragment stream the launch above just wrote (training and inference alike)
-      if (node_r) MATCHA_TRY(launch_node_r(w.XN, w.frag, (int64_t)s.n_nodes + 1, w.RN, st, node_v ? w.VN : nullptr));
+      if (nx.rn) MATCHA_TRY(launch_node_r(nx.X, w.frag, nx.rows, nx.rn, st, nx.vn));
     } else
-    MATCHA_TRY(launch_front_fwd(p, ids, s.mode == 0 ? p.table : nullptr, s.mode == 0 ? nullptr : w.node, *frozen, s.n_attr, w.rg, Tn,
-                                opts->forward_only ? nullptr : w.x0, w.X, st, prep_in_front ? &prep : nullptr));     // x0 (pre-activation) is only read by the backward pass
-  } else {
-    MATCHA_TRY(launch_embed_fwd(ids, Tn, d, s.mode == 0 ? p.table : nullptr, s.mode == 0 ? nullptr : w.node, *frozen, s.n_attr, p.attr_w,
-                                p.attr_b, w.x0, st, cnt));
+    MATCHA_TRY(launch_front_fwd(p, ids, s.mode == 0 ? p.table : nullptr, s.mode == 0 ? nullptr : w.node, *frozen, s.n_attr, w.rg, Tn, keep ? w.x0 : nullptr, w.X, st, &prep));     // x0 (pre-activation) is only read by the backward pass
+  } else if (!route.adj_fused) {
+    MATCHA_TRY(launch_embed_fwd(ids, Tn, d, s.mode == 0 ? p.table : nullptr, s.mode == 0 ? nullptr : w.node, *frozen, s.n_attr, p.attr_w, p.attr_b, w.x0, st, cnt));
     // X = tanh(next_w(x0))   (Modules.py:270)
     GemmArgs g = gemm1(w, w.x0, p.next_w, w.X, Tn, d, d, false);
     g.flags = MATCHA_EPI_BIAS | MATCHA_EPI_TANH; g.bias[0] = p.next_b;
     MATCHA_TRY(launch_gemm_rm(false, g, st));
   }
-  if (fused_path) {
-    // everything from X to the logits in one kernel; a forward that will be differentiated saves Y, H1, H2 (768 B per
-    // token); every training forward also leaves its Q/K/V tiles and attention probabilities for the fused backward (w.qkv)
-    const bool save = !opts->forward_only && !lif;
+  if (keep) note_forward(ws, route); else forget_forward(ws);      // the backward pass on this workspace must follow the same route
+  if (route.fused) {
+    // everything from X to the logits in one kernel; a forward that will be differentiated saves Y, H1, H2 (768 B per token) -- or, with the
+    // tail's backward in the kernel, has the single-wave kernel PARK the rows there between the tail's two halves instead of holding 96 registers
+    // per lane (fused_fwd32_tail.hpp) -- and leaves r rows + probabilities per (half tile, head) for fused_bwdh_kernel (w.qkv)
+    const bool save = keep && !route.lif;
     if (!prep_in_front) MATCHA_TRY(launch_prep_heads(p, w.folded, w.merged, w.frag, st));      // folded / merged / fragment-order weights of this step
-    // the logits go straight to the caller's buffer when no later kernel reads them from the workspace (a differentiated forward
-    // keeps them there for head_bwd): one device-to-device copy less per step / per inference call
+    // the logits go straight to the caller's buffer when no later kernel reads them from the workspace (head_bwd does): one copy less per call
     float* lg_out = (logits && !save) ? logits : w.logits;
-    // large batches: the tail's backward inside the forward kernel stops behind its LayerNorms; pff_n1's two convolutions (dZ1, d dyn, the
-    // weight gradients) are a kernel of their own right behind it (tail_bwd.hip).  Development switch fused_dbg bit 0: all of it in-kernel.
-    const bool split_tail = lif && !fused_small_batch(w.rg) && (options().fused_dbg & 1) == 0;
-    // the backward kernel's heads ADD their d x_hat rows (float atomics) unless the sum has to be reproducible: the rows are zeroed by a launch
-    // that runs anyway -- tail_bwd64_kernel, or for small batches the loss reduction's -- and the record says so
-    const bool zero_dx = lif && !opts->deterministic && !opts->sparse_table_grad && (split_tail || fused_small_batch(w.rg)) && tgt && losses;
-    if (opts->forward_only) forget_forward(ws); else note_forward(ws, true, true, false, split_tail, zero_dx, node, node_r, node_v);
-    // (with the tail's backward in the forward kernel, Y and H1 are still handed over: the single-wave kernel PARKS the two rows there
-    // (and the normalised H2 row in H2's place) between the tail's forward and backward halves instead of holding 96 registers per lane -- fused_fwd32_tail.hpp)
-    // (node route: the kernel reads its row from the per-node table at the plan's sanitised id -- tok_key: 0 for the padding token and foreign ids)
-    MATCHA_TRY(launch_fused_fwd32(p, w.folded, w.frag, node ? w.XN : w.X, w.rg, B, L, y, w_bce, (save || lif) ? w.Y : nullptr, (save || lif) ? w.H1 : nullptr, (save || lif) ? w.H2 : nullptr,
-                                  lg_out, w.row_loss, opts->seed, train ? opts->p_drop_fc1 : 0.f, train ? opts->p_drop_pff : 0.f, st,
-                                  lif ? w.ddyn0 : nullptr, w.dXs, w.tslab, opts->alpha, keep_rimg ? w.qkv : nullptr, split_tail ? w.dH2 : nullptr, objective,
-                                  node ? w.rg.tok_key : nullptr, node_r ? w.RN : nullptr, (int64_t)s.n_nodes + 1));
-    if (split_tail)
-      MATCHA_TRY(launch_tail_bwd64(p, w.dH2, w.Y, w.H1, w.rg, opts->seed, train ? opts->p_drop_fc1 : 0.f, train ? opts->p_drop_pff : 0.f, w.ddyn0, w.tslab2, w.tslab,
-                                   zero_dx ? w.dO : nullptr, st, w.row_loss, B, tgt ? losses : nullptr, recon_zero_in_loss));      // ... zeroes the backward's d x_hat rows, reduces the loss
-    const bool zero_in_loss = zero_dx && !split_tail;
-    if (tgt && losses && !split_tail)
+    FusedFwdLaunch a;
+    a.frag = w.frag; a.small = route.small; a.y = y; a.w = w_bce; a.objective = objective; a.logits = lg_out; a.row_loss = w.row_loss;
+    a.x = nx;      // (node route: the kernel reads its row from the per-node table at the plan's sanitised id -- tok_key: 0 for the padding token and foreign ids)
+    a.Y = keep ? w.Y : nullptr; a.H1 = keep ? w.H1 : nullptr; a.H2 = keep ? w.H2 : nullptr; a.rimg = keep ? w.qkv : nullptr;
+    a.seed = opts->seed; a.p_fc1 = train ? opts->p_drop_fc1 : 0.f; a.p_pff = train ? opts->p_drop_pff : 0.f; a.alpha = opts->alpha;
+    a.ddyn0 = route.lif ? w.ddyn0 : nullptr; a.dXs = w.dXs; a.tslab = w.tslab; a.tail_dh2 = route.split_tail ? w.dH2 : nullptr;
+    MATCHA_TRY(launch_fused_fwd32(p, w.rg, B, L, a, st));
+    if (route.split_tail)
+      MATCHA_TRY(launch_tail_bwd64(p, w.dH2, w.Y, w.H1, w.rg, opts->seed, a.p_fc1, a.p_pff, w.ddyn0, w.tslab2, w.tslab, route.dx_zeroed ? w.dO : nullptr, st, w.row_loss, B, tgt ? losses : nullptr, recon_zero_in_loss));      // ... zeroes the backward's d x_hat rows, reduces the loss
+    const bool zero_in_loss = route.dx_zeroed && !route.split_tail;
+    if (tgt && losses && !route.split_tail)
       MATCHA_TRY(launch_loss_reduce(w.row_loss, B, losses, st, recon_zero_in_loss, zero_in_loss ? w.dO : nullptr, zero_in_loss ? (size_t)Tn * 64 * sizeof(float) : 0));
     if (logits && lg_out != logits && hipMemcpyAsync(logits, w.logits, B * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) {
       set_error("logits copy failed"); return MATCHA_EHIP;
@@ -589,19 +607,15 @@ static int forward_impl(const matcha_shape* shp, const matcha_tensors* params, c
   }
   nan_check("x0", w.x0, cnt, 0, d, st);
   nan_check("X", w.X, cnt, 0, d, st);
-  const bool mlw = merged_layerwise(s);
-  if (opts->forward_only) forget_forward(ws); else note_forward(ws, mlw, false, enc);      // the backward pass on this workspace must use the same formulation
-  if (enc) {
+  if (route.enc128) {
     // LayerNorms, merged heads, attention, fc1 + dropout + mask: X -> Y in one kernel; a training forward leaves r rows + probabilities
     MATCHA_TRY(merged_weights(s, p, w, st));
-    const bool keep = !opts->forward_only;
-    if (keep && enc128_rec_floats(w.rg) > w.enc_rec_floats) { set_error("matcha_forward: the fused d = 128 records do not fit the workspace"); return MATCHA_ENOMEM; }
     MATCHA_TRY(launch_enc128_fwd(p, w.lwB, w.lwM, w.X, w.rg, B, L, w.Y, keep ? w.enc_rec : nullptr, w.enc, w.rg.tok_slot, opts->seed,
                                  (train && opts->p_drop_fc1 > 0.f) ? opts->p_drop_fc1 : 0.f, st));
   } else {
   // three LayerNorms on the same row (Modules.py:519-521), then Q/K/V projections (:527-529), one batched launch
   MATCHA_TRY(launch_ln3_fwd(w.X, Tn, d, p.ln_q_g, p.ln_q_b, p.ln_k_g, p.ln_k_b, p.ln_v_g, p.ln_v_b, w.qin, w.kin, w.vin, w.stats, st, cnt));
-  if (mlw) {
+  if (route.merged_layerwise) {
     MATCHA_TRY(merged_weights(s, p, w, st));
     GemmArgs g = gemm1(w, w.qin, w.lwB, w.Q, Tn, hd, d, false);                 // r = qin B_all^T  (in Q's buffer)
     MATCHA_TRY(launch_gemm_rm(false, g, st));
@@ -616,12 +630,12 @@ static int forward_impl(const matcha_shape* shp, const matcha_tensors* params, c
   nan_check("Q", w.Q, cnt, 0, hd, st);
   nan_check("K", w.K, cnt, 0, hd, st);
   nan_check("V", w.V, cnt, 0, hd, st);
-  if (mlw) MATCHA_TRY(launch_attn_fwd(w.Q, w.kin, w.vin, w.rg.row_off, B, L, d, w.O, w.P, st, true));     // O = Z = P . vin per head
+  if (route.merged_layerwise) MATCHA_TRY(launch_attn_fwd(w.Q, w.kin, w.vin, w.rg.row_off, B, L, d, w.O, w.P, st, true));     // O = Z = P . vin per head
   else MATCHA_TRY(launch_attn_fwd(w.Q, w.K, w.V, w.rg.row_off, B, L, d, w.O, w.P, st));
   nan_check("O", w.O, cnt + 1, 0, hd, st);
   // Y = (dropout(fc1(O))) * non_pad_mask    (Modules.py:572, :614); the mask only zeroes the shared padding token's row
   {
-    GemmArgs g = gemm1(w, w.O, mlw ? w.lwM : p.fc1_w, w.Y, Tn, d, hd, false);
+    GemmArgs g = gemm1(w, w.O, route.merged_layerwise ? w.lwM : p.fc1_w, w.Y, Tn, d, hd, false);
     g.flags = MATCHA_EPI_BIAS | MATCHA_EPI_ROWMASK; g.bias[0] = p.fc1_b; g.row_ids = ids;
     if (train && opts->p_drop_fc1 > 0.f) { g.flags |= MATCHA_EPI_DROPOUT; g.seed = opts->seed; g.stream_id = kStreamDropFc1; g.p_drop = opts->p_drop_fc1; }
     MATCHA_TRY(launch_gemm_rm(false, g, st));
@@ -768,38 +782,30 @@ static int backward_impl(const matcha_shape* shp, const matcha_tensors* params, 
   const int32_t* cnt = w.rg.count;             // the plan (row_off, tok_id, tok_slot, count) is still in the workspace
   const int64_t* ids = w.rg.tok_id;
 
-  const int fwd_state = ws_state(ws);
-  MATCHA_CHECK_ARG(fwd_state >= 0, "matcha_backward: no matcha_forward on record for this workspace (one backward per forward, same ws pointer)");
-  const bool fused_fwd = (fwd_state & 2) != 0;          // which kernels the forward ran is what decides, not the option table now
-  const bool lif = fused_fwd && loss_in_forward(s, *opts, y, w_bce, objective);
-  MATCHA_CHECK_ARG(!(lif && dlogits), "matcha_backward: opts->loss_in_forward excludes an explicit dlogits");
+  // which kernels the forward ran on this workspace is what decides, not the option table now: everything below follows `route`
+  StepRoute route;
+  MATCHA_CHECK_ARG(recorded_route(ws, route), "matcha_backward: no matcha_forward on record for this workspace (one backward per forward, same ws pointer)");
+  // fused route: this call's options and targets must ask for the loss where the forward computed it (head_bwd over rows the forward only parked, or no ddyn0)
+  MATCHA_CHECK_ARG(!route.fused || route.lif == (opts->loss_in_forward && has_target(objective, y, w_bce)),
+                   "matcha_backward: loss_in_forward / targets differ from the forward's on this workspace");
+  MATCHA_CHECK_ARG(!(route.lif && dlogits), "matcha_backward: opts->loss_in_forward excludes an explicit dlogits");
   forget_forward(ws);                                   // one backward per forward: from here on the saved activations are being overwritten
-  bool dx_zeroed = false, tail_in_bwd = false;
+  const bool tail_in_bwd = route.lif && (route.split_tail || route.small);     // the launch that sums the backward kernel's slabs sums the forward's tail slabs too
+  const bool dx_zeroed = route.dx_zeroed && !opts->deterministic && !opts->sparse_table_grad;      // tail_bwd64_kernel / the loss reduction zeroed the heads' d x_hat buffer
   TailReduceArgs tail_args;
-  const bool node = fused_fwd && (fwd_state & 32) != 0;        // the forward ran the front end per node: X lives in the per-node table, rows by tok_key
-  const bool node_r = node && (fwd_state & 64) != 0;           // ... and gathered r from the per-node table: the record holds probabilities only
-  const bool node_v = node_r && (fwd_state & 128) != 0;        // ... and left the value table: the backward's VTAB instance
-  if (lif) {
-    // ddyn0 and dXs were produced by matcha_forward; only the per-half-tile parameter-gradient partials remain to be summed
-    // (fused_fwd32.hip).  Small batches: one launch, which also zeroes the buffer the backward kernel's heads add their d x_hat into
-    const bool small = fused_small_batch(w.rg);
-    dx_zeroed = (fwd_state & 16) != 0 && !opts->deterministic && !opts->sparse_table_grad;      // tail_bwd64_kernel / the loss reduction zeroed the rows
-    if ((fwd_state & 8) != 0) {
-      // one row-major slab per workgroup of tail_bwd64_kernel: the convolutions' gradients and the half tiles' LayerNorm / classifier vectors
-      // (summed along its walk): 512 slabs.  Summed by blocks of the launch that sums the backward kernel's slabs (fused_bwd.hip)
-      tail_reduce_args(w.tslab2, w.rg, L, g_, true, tail_bwd_grid(), true, tail_args);
-      tail_in_bwd = true;
-    } else if (small) {
-      tail_reduce_args(w.tslab, w.rg, L, g_, true, -1, false, tail_args);     // one slab per half tile (a few dozen)
-      tail_in_bwd = true;
-    } else
-      MATCHA_TRY(launch_tail_reduce(w.tslab, w.rg, L, g_, st, true, w.tpart));
+  const NodeOperands nx = node_operands(route, s, w);   // node route: X lives in the per-node table, rows by tok_key
+  if (route.lif) {
+    // ddyn0 and dXs were produced by matcha_forward; only the parameter-gradient partials remain to be summed (fused_fwd32.hip).  Split tail: one
+    // row-major slab per workgroup of tail_bwd64_kernel -- the convolutions' gradients and the half tiles' LayerNorm / classifier vectors (summed
+    // along its walk), 512 slabs;  small batches: one slab per half tile (a few dozen);  otherwise two passes of their own
+    if (route.split_tail) tail_reduce_args(w.tslab2, w.rg, L, g_, true, tail_bwd_grid(), true, tail_args);
+    else if (route.small) tail_reduce_args(w.tslab, w.rg, L, g_, true, -1, false, tail_args);
+    else MATCHA_TRY(launch_tail_reduce(w.tslab, w.rg, L, g_, st, true, w.tpart));
   } else {
   // tail: dH2, dXs and the gradients of pff_n1.layer_norm, layer_norm1/2, pff_classifier
   HeadParams hp = {p.pff_ln_g, p.pff_ln_b, p.ln1_g, p.ln1_b, p.ln2_g, p.ln2_b, p.cls_w, p.cls_b};
   HeadParams ghp = {g_.pff_ln_g, g_.pff_ln_b, g_.ln1_g, g_.ln1_b, g_.ln2_g, g_.ln2_b, g_.cls_w, g_.cls_b};
-  MATCHA_TRY(launch_head_bwd(w.rg.row_off, w.H2, node ? w.XN : w.X, B, L, d, hp, y, w_bce, w.logits, dlogits, opts->alpha, w.dH2, w.dXs, w.slab, ghp, st, objective,
-                             node ? w.rg.tok_key : nullptr));
+  MATCHA_TRY(launch_head_bwd(w.rg.row_off, w.H2, nx.X, B, L, d, hp, y, w_bce, w.logits, dlogits, opts->alpha, w.dH2, w.dXs, w.slab, ghp, st, objective, nx.xrow));
   // pff_n1 conv1: dW1 += dH2^T H1 ; db1 += colsum(dH2) ; dZ1 = (dH2 W1) * dropmask * (1 - tanh^2)
   MATCHA_TRY(launch_gemm_tn(w.dH2, w.H1, g_.pff1_w, g_.pff1_b, d, d, Tn, d, d, nullptr, true, w.gemm_ws, w.gemm_ws_bytes, st, cnt));
   {
@@ -817,50 +823,45 @@ static int backward_impl(const matcha_shape* shp, const matcha_tensors* params, 
     MATCHA_TRY(launch_gemm_rm(true, g, st));
   }
   }
-  if (fused_fwd) {
+  if (route.fused) {
     // attention block (fc1, attention, Q/K/V projections, the three LayerNorms) from X and ddyn0 in one head-major kernel;
     // the forward pass left the folded weights in w.folded.  w.dO doubles as the 8 per-head d x_hat slabs.
-    const bool front = node || (front_bwd_supported(s.d, s.n_attr) && fused_front_enabled());
-    // the eight heads add their d x_hat into ONE buffer with float atomics (they meet in L2; per-head slabs are 8 x 256 B per token written
-    // and read back).  `deterministic` and the row-sparse table gradient (whose sum is bitwise reproducible) keep the slabs and their
-    // fixed summation order
+    // the eight heads add their d x_hat into ONE buffer with float atomics (they meet in L2; per-head slabs are 8 x 256 B per token written and read
+    // back).  `deterministic` and the row-sparse table gradient (whose sum is bitwise reproducible) keep the slabs and their fixed order: per call
     const bool dx_atomic = !opts->deterministic && !opts->sparse_table_grad;
-    MATCHA_CHECK_ARG(!node || dx_atomic, "matcha_backward: deterministic / sparse_table_grad differ from the forward's on this workspace");
-    MATCHA_TRY(launch_fused_bwd_merged(p, w.folded, w.merged, node ? w.XN : w.X, w.ddyn0, w.dXs, w.rg, B, L, w.dO, w.fb_ws, g_, front ? nullptr : w.dZ0, st, w.qkv, dx_atomic, dx_zeroed,
-                                       tail_in_bwd ? &tail_args : nullptr, node ? w.rg.tok_key : nullptr, node ? w.xhN : nullptr,
-                                       node_r ? w.RN : nullptr, (int64_t)s.n_nodes + 1, node_v ? w.VN : nullptr));
+    MATCHA_CHECK_ARG(!route.node || dx_atomic, "matcha_backward: deterministic / sparse_table_grad differ from the forward's on this workspace");
+    FusedBwdLaunch a;
+    a.folded = w.folded; a.merged = w.merged; a.x = nx; a.dDyn = w.ddyn0; a.dXs = w.dXs; a.rimg = w.qkv;
+    a.dxh = w.dO; a.ws = w.fb_ws; a.dZ0 = route.front ? nullptr : w.dZ0;
+    a.dx_atomic = dx_atomic; a.dx_zeroed = dx_zeroed; a.tail = tail_in_bwd ? &tail_args : nullptr;
+    MATCHA_TRY(launch_fused_bwd_merged(p, w.rg, B, L, a, g_, st));
     MATCHA_TRY(encoder_done(*opts, st));
-    if (front) {
+    if (route.front) {
       // LayerNorm backward of the summed partials + next_w + attribute_nn backward + embedding scatter in one kernel
       if (s.mode == 0) MATCHA_CHECK_ARG(g_.table, "matcha_backward: table mode without a table gradient buffer");
-      if (node) {
+      if (route.node) {
         // the tokens' rows LNbwd(d x_hat) + dXs added per node (one pass over the tokens), then tanh' / next_w / attribute_nn / the table row
         // once per node: front_bwd_kernel over the ids 0..n_nodes with the sums in dXs' place, one writer per table-gradient row
-        MATCHA_TRY(launch_node_scatter(w.XN, w.dO, fused_bwd_dxpad(w.fb_ws), w.dXs, w.rg, Tn, w.GN, st));
-        MATCHA_TRY(launch_front_bwd(p, w.XN, nullptr, 1, (int64_t)s.n_nodes + 1, fused_bwd_dxpad(w.fb_ws), w.GN, w.x0N, w.node_ids, *frozen, s.n_attr, w.rg,
-                                    nullptr, g_.table, w.front_ws, g_, st, touched, w.node_cnt));
+        MATCHA_TRY(launch_node_scatter(nx.X, w.dO, fused_bwd_dxpad(w.fb_ws), w.dXs, w.rg, Tn, w.GN, st));
+        MATCHA_TRY(launch_front_bwd(p, nx.X, nullptr, 1, nx.rows, fused_bwd_dxpad(w.fb_ws), w.GN, w.x0N, w.node_ids, *frozen, s.n_attr, w.rg, nullptr, g_.table, w.front_ws, g_, st, touched, w.node_cnt));
         return MATCHA_OK;
       }
       const bool rows_out = s.mode == 1 || opts->deterministic || opts->sparse_table_grad;     // dX0 rows instead of float atomics
       MATCHA_TRY(launch_front_bwd(p, w.X, w.dO, dx_atomic ? 1 : MATCHA_N_HEAD, Tn, fused_bwd_dxpad(w.fb_ws), w.dXs, w.x0, ids, *frozen, s.n_attr, w.rg,
                                   rows_out ? w.dX0 : nullptr, rows_out ? nullptr : g_.table, w.front_ws, g_, st, s.mode == 0 ? touched : nullptr));
-      if (s.mode == 0) {
-        MATCHA_TRY(table_gradient(s, *opts, w, Tn, g_, st));       // (the two `touched` flags were set by front_slab_reduce_kernel)
-      } else {
-        MATCHA_TRY(adj_backward(s, p, *frozen, *opts, ids, Tn, w.dX0, drecon, g_, touched, w.adj_ws, w.adj_ws_bytes, w.gemm_ws, w.gemm_ws_bytes, st,
-                                w.rg.tok_slot, adj_fused_eligible(s, *frozen)));
-      }
+      if (s.mode == 0) MATCHA_TRY(table_gradient(s, *opts, w, Tn, g_, st));       // (the two `touched` flags were set by front_slab_reduce_kernel)
+      else MATCHA_TRY(adj_backward(s, p, *frozen, *opts, ids, Tn, w.dX0, drecon, g_, touched, w.adj_ws, w.adj_ws_bytes, w.gemm_ws, w.gemm_ws_bytes, st, w.rg.tok_slot, route.adj_fused));
       return MATCHA_OK;
     }
   } else {
-  if ((fwd_state & 4) != 0) {
+  if (route.enc128) {
     // embed_dim 128, fused attention block: dB_all / dM_all (LayerNorm affines taken back out) + d x_hat in one kernel, then the chain rule to
     // w_qs / w_ks / w_vs / fc1 and the LayerNorm backward (enc128.hip); dxh lives in qin's buffer
     MATCHA_TRY(launch_enc128_bwd(p, w.lwB, w.lwM, w.X, w.ddyn0, w.dXs, w.rg, B, L, w.dqin, w.enc_rec, w.enc, w.lwdB, w.lwdM, g_, w.dZ0, st));
     MATCHA_TRY(merged_chain(s, p, g_, w, st));
     MATCHA_TRY(encoder_done(*opts, st));
   } else {
-  if ((fwd_state & 1) != 0) {
+  if (route.merged_layerwise) {
     // merged heads: dM_all = ddyn0^T Z ; d fc1_b += colsum ; dZ = ddyn0 M_all   (the scratch gradients start from zero: the TN GEMM
     // accumulates C and the column sums alike, and fc1_b's gradient must accumulate)
     MATCHA_TRY(zero_async(w.lwdM, (size_t)hd * d * sizeof(float), st));

@@ -9,6 +9,8 @@
 //   * the workspace carving of model.hip / ragged.hip: every region inside the buffer, ordered, aligned -- checked by writing
 //     the first and last byte of every region into an exactly-sized heap buffer (ASan traps an overrun);
 //   * the option table (matcha_set_option / environment parsing);
+//   * the step's kernel route (decide_route: implications over a sweep of shapes, options and switches, the sizes the history fixed) and the
+//     per-workspace record of it;
 //   * the C restatement of the ragged plan (oracle/c/ragged_plan.c), fuzzed with its invariants.
 // model.hip is included as source so that its static functions (carve, check_shape) are reachable.
 #include <stdio.h>
@@ -195,6 +197,128 @@ static void check_options() {
   CHECK(a < b && b == matcha_workspace_bytes(&s, 1024, 5));          // the compact layout exists only with the fused kernels
 }
 
+// ---- the step's kernel route (model.hip: StepRoute, decide_route, the per-workspace record): decided without a device, so checked here ----
+static bool same_route(const StepRoute& a, const StepRoute& b) {
+  return a.compact == b.compact && a.half_plan == b.half_plan && a.fused == b.fused && a.merged_layerwise == b.merged_layerwise && a.enc128 == b.enc128 &&
+         a.front == b.front && a.adj_fused == b.adj_fused && a.small == b.small && a.lif == b.lif && a.split_tail == b.split_tail &&
+         a.dx_zeroed == b.dx_zeroed && a.node == b.node && a.node_r == b.node_r && a.node_v == b.node_v;
+}
+static StepRoute route_of(const matcha_shape& s, const matcha_step_opts& o, int64_t B, int L, bool targets, bool force_layerwise = false) {
+  Workspace w;
+  char* const base = reinterpret_cast<char*>((uintptr_t)1 << 20);      // the layout only: nothing is dereferenced
+  carve(s, B, L, base, w, compact_forward(s, o, force_layerwise));
+  matcha_frozen f;
+  memset(&f, 0, sizeof(f));
+  f.feat_row_pad = 64;                                                 // what the fused adj kernels take
+  static const float t[1] = {0.f};
+  return decide_route(s, o, B, L, w, f, targets ? t : nullptr, targets ? t : nullptr, MATCHA_OBJECTIVE_BCE, force_layerwise, true);
+}
+static matcha_step_opts train_opts() {
+  matcha_step_opts o;
+  memset(&o, 0, sizeof(o));
+  o.training = 1; o.loss_in_forward = 1;
+  return o;
+}
+
+static void check_routes() {
+  const int dbg = matcha_get_option("fused_dbg");
+  matcha_set_option("fused_dbg", 0);                  // (bit 0 keeps the whole tail in the forward kernel: no split tail to check)
+  CHECK(device_cu_count() == 256 || matcha_device_count() > 0);      // without a device the small-batch bound is 512 half tiles
+  // implications, over shapes x front ends x per-call options x every switch
+  const char* switches[] = {"", "disable_fused", "disable_fused", "disable_merged", "disable_small_batch", "disable_wide_gemm", "disable_node_front", "disable_node_r", "disable_node_v"};
+  const int values[] = {0, 1, 2, 1, 1, 1, 1, 1, 1};
+  int seen[14] = {0};
+  for (int sw = 0; sw < 9; ++sw) {
+    if (sw) CHECK(matcha_set_option(switches[sw], values[sw]) == MATCHA_OK);
+    for (int d : {16, 64, 128, 256})
+      for (int mode = 0; mode < 2; ++mode)
+        for (int64_t B : {2ll, 1024ll, 8192ll, 65536ll})
+          for (int bits = 0; bits < 32; ++bits) {
+            const matcha_shape s = mode ? shape(d, 24, 3068, 23, 1, 250) : shape(d, 24, 3068, 0, 0, 0);
+            matcha_step_opts o = train_opts();
+            o.forward_only = bits & 1; o.deterministic = (bits >> 1) & 1; o.loss_in_forward = (bits >> 2) & 1;
+            const bool targets = (bits >> 3) & 1, force = (bits >> 4) & 1;
+            const StepRoute r = route_of(s, o, B, 5, targets, force);
+            CHECK(!r.node_v || r.node_r);
+            CHECK(!r.node_r || r.node);
+            CHECK(!r.node || (r.fused && r.front && !r.small && !o.deterministic && !o.sparse_table_grad && mode == 0));
+            CHECK(!r.split_tail || r.lif);
+            CHECK(!r.lif || (r.fused && targets && o.loss_in_forward));
+            CHECK(!r.dx_zeroed || (r.lif && !o.deterministic));
+            CHECK(!r.enc128 || (!r.fused && d == 128 && r.merged_layerwise));
+            CHECK(!r.fused || d == 64);
+            CHECK(!r.front || r.fused);
+            CHECK(!r.adj_fused || (r.front && mode == 1));
+            CHECK(!r.small || r.fused);
+            CHECK(!r.compact || (r.fused && o.forward_only));
+            CHECK(!o.forward_only || (!r.node_v && !r.lif));
+            CHECK(!force || (!r.fused && !r.enc128 && !r.node && !r.compact));
+            const bool f[14] = {r.compact, r.half_plan, r.fused, r.merged_layerwise, r.enc128, r.front, r.adj_fused, r.small, r.lif, r.split_tail, r.dx_zeroed, r.node, r.node_r, r.node_v};
+            if (!sw) for (int i = 0; i < 14; ++i) seen[i] += f[i];
+          }
+    if (sw) matcha_set_option(switches[sw], 0);
+  }
+  for (int i = 0; i < 14; ++i) CHECK(seen[i] > 0);      // the default sweep reaches every field: none of the implications is vacuous
+
+  // the table front end at hg38 1 Mb (3 068 nodes), k <= 5, a training step with targets: the node route from 8 192 rows, its value table at 65 536
+  const matcha_shape t64 = shape(64, 24, 3068, 0, 0, 0);
+  const matcha_step_opts o = train_opts();
+  for (int64_t B : {8192ll, 16384ll, 32768ll, 65536ll}) {
+    const StepRoute r = route_of(t64, o, B, 5, true);
+    CHECK(r.fused && r.front && !r.small && r.node && r.node_r && r.node_v == (B == 65536));
+    CHECK(r.lif && r.split_tail && r.dx_zeroed && !r.compact && r.half_plan && !r.adj_fused && !r.enc128 && !r.merged_layerwise);
+  }
+  const StepRoute small = route_of(t64, o, 1024, 5, true);
+  CHECK(small.fused && small.front && small.small && !small.node && !small.node_r && !small.node_v && small.lif && !small.split_tail && small.dx_zeroed);
+  // each switch of the node route takes out its own field and the fields that depend on it, nothing else
+  const StepRoute base = route_of(t64, o, 65536, 5, true);
+  const char* node_sw[] = {"disable_node_v", "disable_node_r", "disable_node_front"};
+  for (int i = 0; i < 3; ++i) {
+    matcha_set_option(node_sw[i], 1);
+    const StepRoute r = route_of(t64, o, 65536, 5, true);
+    matcha_set_option(node_sw[i], 0);
+    StepRoute want = base;
+    want.node_v = false;
+    if (i >= 1) want.node_r = false;
+    if (i >= 2) want.node = false;
+    CHECK(same_route(r, want));
+  }
+  {
+    matcha_set_option("disable_small_batch", 1);
+    const StepRoute r = route_of(t64, o, 1024, 5, true);
+    matcha_set_option("disable_small_batch", 0);
+    CHECK(!r.small && r.split_tail && r.dx_zeroed && !r.node);            // 5 121 token rows: below the node route's size rule
+  }
+  CHECK(same_route(base, route_of(t64, o, 65536, 5, true)));             // every switch restored
+
+  // the record: field for field, dropped by forget_forward, the 4 096 most recent workspaces kept
+  g_fwd_state.clear();
+  auto pattern = [&](int i) {
+    StepRoute r = base;
+    r.compact = i & 1; r.half_plan = i & 2; r.fused = i & 4; r.merged_layerwise = i & 8; r.enc128 = i & 16; r.front = i & 32; r.adj_fused = i & 64;
+    r.small = i & 128; r.lif = i & 256; r.split_tail = i & 512; r.dx_zeroed = i & 1024; r.node = i & 2048; r.node_r = i & 4096; r.node_v = i % 3 == 0;
+    return r;
+  };
+  auto ws_ptr = [](int i) { return reinterpret_cast<const void*>((uintptr_t)(i + 1) << 12); };
+  StepRoute got;
+  CHECK(!recorded_route(ws_ptr(0), got));
+  for (int i = 0; i < 14; ++i) {                     // one field set at a time
+    note_forward(ws_ptr(0), pattern(1 << i));
+    CHECK(recorded_route(ws_ptr(0), got) && same_route(got, pattern(1 << i)) && g_fwd_state.size() == 1);
+  }
+  forget_forward(ws_ptr(0));
+  CHECK(!recorded_route(ws_ptr(0), got) && g_fwd_state.empty());
+  for (int i = 0; i < 4097; ++i) note_forward(ws_ptr(i), pattern(i));
+  CHECK(g_fwd_state.size() == 4096 && !recorded_route(ws_ptr(0), got));
+  int kept = 0;
+  for (int i = 1; i < 4097; ++i) kept += recorded_route(ws_ptr(i), got) && same_route(got, pattern(i));
+  CHECK(kept == 4096);
+  note_forward(ws_ptr(1), pattern(7));               // a pointer already on record is refreshed, nothing evicted
+  CHECK(g_fwd_state.size() == 4096 && recorded_route(ws_ptr(2), got) && recorded_route(ws_ptr(1), got) && same_route(got, pattern(7)));
+  g_fwd_state.clear();
+  matcha_set_option("fused_dbg", dbg);
+}
+
 static void fuzz_plan_oracle() {
   std::mt19937_64 rng(7);
   for (int it = 0; it < 300; ++it) {
@@ -255,6 +379,7 @@ int main() {
   check_options();                      // first: the option table must see the environment of the process start
   check_sizes_and_validation();
   check_entry_point_errors();
+  check_routes();
   fuzz_plan_oracle();
   if (g_fail) { fprintf(stderr, "%d of %d host checks FAILED\n", g_fail, g_checks); return 1; }
   printf("ALL HOST CHECKS PASSED (%d checks, device_count=%d)\n", g_checks, matcha_device_count());

@@ -1,7 +1,7 @@
 """The autograd path over the three routes of the d = 64 table front end, with the switches flipped BETWEEN model(x) and loss.backward().
 
 matcha_forward and matcha_backward are two calls there, and the options (disable_node_r, disable_node_front) are process-wide, so the backward
-must follow what the forward recorded for its workspace (model.hip: g_fwd_state bits 5 and 6), not the option table it finds: a backward that
+must follow what the forward recorded for its workspace (model.hip: StepRoute::node and ::node_r in g_fwd_state), not the option table it finds: a backward that
 believed the options would gather r rows nobody wrote, read X from the wrong table or run the front end's backward over the wrong rows.
 All six ordered pairs of {default, disable_node_r, disable_node_front}, each against the un-flipped run of the forward's setting (logits and
 losses bitwise, gradients to the repository's route-against-route bound) and against the fp64 oracle at fp32 grade (tests/fp64_grade.py, K = 8).
