@@ -34,6 +34,7 @@ extern "C" {
 #define MATCHA_ENOMEM (-12) /* workspace too small                             */
 
 #define MATCHA_MAX_L 8      /* widest hyperedge (BASELINE.json configs[4]: k in 2..8) */
+#define MATCHA_MAX_LONG_L 32 /* widest row of the inference-only long forward (matcha_forward_long) */
 #define MATCHA_N_HEAD 8     /* main.py:616 */
 
 typedef void* matcha_stream_t; /* hipStream_t */
@@ -255,6 +256,22 @@ int matcha_forward(const matcha_shape* shp, const matcha_tensors* params, const 
                    const matcha_step_opts* opts, const int64_t* x, int64_t B, int32_t L,
                    const float* y, const float* w, float* logits, float* losses,
                    void* ws, size_t ws_bytes, matcha_stream_t stream);
+
+/* Long rows: the inference forward for x [B, L] with 2 <= L <= MATCHA_MAX_LONG_L (32), B >= 1, B*L < 2^31 - 2 and at most
+ * 65 535 * 128 token rows (the layer-by-layer kernels' launch bound); every shape matcha_forward accepts, both front ends.
+ * Every other entry point keeps MATCHA_MAX_L.  L <= 8 is accepted too, so that the long kernels can be held against
+ * matcha_forward on identical input.
+ *   opts->training must be 0 and opts->forward_only 1 (anything else: MATCHA_EINVAL before any device call -- dropout and the
+ *   backward for long rows do not exist); opts->status and, for the adj front end, opts->random_chrom are honoured as in
+ *   matcha_forward (opts->random_chrom_dev: MATCHA_EINVAL).
+ *   logits float [B] out;  losses float [3] as matcha_forward (bce unused: slot 0 is not written), may be NULL.
+ * Caller-owned memory, asynchronous on `stream`, no allocation, no memset node, no read-back; every refusal before any launch.
+ * matcha_workspace_bytes_long is host only and returns 0 (+ matcha_last_error) for a bad argument; the layout is forward-only:
+ * 12 d floats per token where embed_dim is a multiple of 64 (merged heads), 28 d otherwise, + 20 B of plan per token and 8 B per row (+ d floats, adj). */
+size_t matcha_workspace_bytes_long(const matcha_shape* shp, int64_t B, int32_t L);
+int matcha_forward_long(const matcha_shape* shp, const matcha_tensors* params, const matcha_frozen* frozen,
+                        const matcha_step_opts* opts, const int64_t* x, int64_t B, int32_t L,
+                        float* logits, float* losses, void* ws, size_t ws_bytes, matcha_stream_t stream);
 
 /* loss.backward() of main.py:179 for loss = bce*alpha + recon*beta, or, when `dlogits` is not NULL,
  * the vector-Jacobian product for an arbitrary upstream gradient on the logits (autograd glue).

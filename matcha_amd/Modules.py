@@ -536,8 +536,10 @@ class _Runtime:
             return False            # (nothing rewrites these with the same bytes -- they are not in the state dict --, so any change rebuilds)
         return all(p.data_ptr() == e for p, e in zip(self.live, self.expected_ptrs))
 
-    def workspace(self, B: int, L: int, forward_only: bool = False) -> torch.Tensor:
+    def workspace(self, B: int, L: int, forward_only: bool = False, long_rows: bool = False) -> torch.Tensor:
         query = self.lib.matcha_workspace_bytes_forward if forward_only else self.lib.matcha_workspace_bytes
+        if long_rows:      # rows of 9 .. MAX_LONG_L columns: the inference-only long forward has a layout of its own
+            query = self.lib.matcha_workspace_bytes_long
         n = query(C.byref(self.shape), B, L)
         if n == 0:
             raise _lib.MatchaHipError(self.lib.matcha_last_error().decode())
@@ -694,13 +696,37 @@ class Classifier(nn.Module):
         if x.dim() != 2:
             raise ValueError("x must be [B, L] node ids (0 = padding)")
         x = x.contiguous()
+        if x.shape[1] > _lib.MAX_LONG_L:
+            raise ValueError(f"hyperedges wider than {_lib.MAX_LONG_L} are not supported (x has {x.shape[1]} columns)")
         if x.shape[1] > _lib.MAX_L:
-            raise ValueError(f"hyperedges wider than {_lib.MAX_L} are not supported")
+            return self._forward_long(x, rt, return_recon)
         opts, seed_t = self._opts(rt, return_recon)
         logits, recon = _ClassifierFn.apply(x, rt, opts, seed_t, *rt.live)
         if self.check_ids and not torch.cuda.is_current_stream_capturing():
             rt.check_status("Classifier.forward")          # IndexError for ids outside [0, N], like the reference's nn.Embedding
         return (logits, recon) if return_recon else logits
+
+    def _forward_long(self, x, rt: _Runtime, return_recon: bool):
+        """Rows of MAX_L + 1 .. MAX_LONG_L columns (9 .. 32): the inference-only long forward (matcha_forward_long).  Same surface as
+        the short path -- logits [B, 1], return_recon, check_ids / deferred_id_check, one np.random.choice per call in adj mode --
+        but eval mode without an autograd graph only: training, dropout and the backward stay at MAX_L columns."""
+        if self.training or (torch.is_grad_enabled() and any(p.requires_grad for p in rt.live)):
+            raise NotImplementedError(
+                f"hyperedges of more than {_lib.MAX_L} nodes are inference-only (x has {x.shape[1]} columns): call model.eval() and "
+                "run the forward under torch.no_grad()")
+        opts, _ = self._opts(rt, return_recon)       # eval + no graph: training = 0, forward_only = 1, no seed
+        B, L = x.shape
+        ws = rt.workspace(B, L, long_rows=True)
+        logits = torch.empty(B, dtype=torch.float32, device=rt.device)
+        losses = torch.zeros(3, dtype=torch.float32, device=rt.device)
+        opts.status = rt.status.data_ptr()
+        _lib.check(rt.lib.matcha_forward_long(C.byref(rt.shape), C.byref(rt.params), C.byref(rt.frozen), C.byref(opts), _lib.ptr(x), B, L,
+                                              _lib.ptr(logits), _lib.ptr(losses), _lib.ptr(ws), ws.numel(), rt.stream()),
+                   "matcha_forward_long")
+        if self.check_ids and not torch.cuda.is_current_stream_capturing():
+            rt.check_status("Classifier.forward")
+        logits = logits.view(B, 1)
+        return (logits, losses[1:2]) if return_recon else logits
 
     def get_node_embeddings(self, x, return_recon=False):
         """Rows of the node-embedding front end, [B, L, d] (reference Modules.py:252-259).  Inference surface
@@ -731,7 +757,8 @@ class Classifier(nn.Module):
         arguments are accepted and ignored exactly as far as the reference ignores them: non_pad_mask is recomputed from x, the
         key-pad mask never reaches the softmax (SURVEY.md headline fact 7).  Runs the layer-by-layer kernels (the fused path
         keeps these tensors on chip); inference surface, not differentiable.  Rows of padding QUERIES in ``attn`` are zero
-        (the reference computes a softmax there that nothing reads)."""
+        (the reference computes a softmax there that nothing reads).  L <= 8: the long forward of model(x) (9 .. 32 columns) returns
+        logits only."""
         rt = self._runtime()
         x = torch.as_tensor(x).to(device=rt.device, dtype=torch.long).contiguous()
         B, L = x.shape

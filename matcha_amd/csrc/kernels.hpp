@@ -261,4 +261,14 @@ int launch_attn_bwd_wide(const float* Q, const float* K, const float* V, const f
                          int d, float inv_temp, float* dQ, float* dK, float* dV, float* slab, int nblk, hipStream_t st, bool shared_kv = false,
                          float* dKs = nullptr, float* dVs = nullptr);
 
+// ragged_long.hip: the plan for rows of up to MATCHA_MAX_LONG_L columns -- the fields of Ragged the token-level kernels read (row_off, tok_slot,
+// tok_id, tok_key, tok_pos, count), no tile lists; `mask` [B] is its scratch (the bit set of a row's real columns)
+size_t long_plan_bytes(int64_t B, int L);
+void long_plan_carve(int64_t B, int L, char* base, Ragged& r, uint32_t** mask);
+int launch_long_plan(const int64_t* x, int64_t B, int L, int64_t n_nodes, int32_t* status, const Ragged& r, uint32_t* mask, hipStream_t st);
+// attention_long.hip: per-hyperedge attention for k <= 32 real tokens, one wavefront per (hyperedge, head), O may alias Q.  kv_ld / kv_head: row
+// stride and per-head offset of K and V (8 d and d for per-head rows; d and 0 for the merged heads' shared key / value rows)
+int launch_attn_long(const float* Q, const float* K, const float* V, const int32_t* row_off, int64_t B, int L, int d, int64_t kv_ld, int kv_head,
+                     float* O, hipStream_t st);
+
 }  // namespace matcha

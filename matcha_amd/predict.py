@@ -35,18 +35,20 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import _lib
 from . import utils as U
 
 CHUNK_ROWS = 10000            # predict_multiway.py:77, denoise_contact.py:79
 
 
-def parse_file(filepath: str, bin2node: Dict[str, int], chrom_list: Sequence[str], res: int) -> List[List[int]]:
+def parse_file(filepath: str, bin2node: Dict[str, int], chrom_list: Sequence[str], res: int, max_size: Optional[int] = None) -> List[List[int]]:
     """predict_multiway.py:24-59: items of unknown chromosomes are skipped, positions are floored to their bin, node ids
     are de-duplicated and sorted, lines with fewer than two nodes are dropped.  An item without ``:`` raises EOFError and
-    an unknown bin raises KeyError, as in the reference."""
+    an unknown bin raises KeyError, as in the reference.  ``max_size`` (not in the reference): a line with more distinct bins
+    raises ValueError naming the 1-based line and its size."""
     final = []
     with open(filepath, "r") as f:
-        for line in f:
+        for lineno, line in enumerate(f, 1):
             temp = []
             for info in line.strip().split("\t"):
                 try:
@@ -58,6 +60,8 @@ def parse_file(filepath: str, bin2node: Dict[str, int], chrom_list: Sequence[str
                 b = int(math.floor(int(bin_) / res)) * res
                 temp.append(bin2node["%s:%d" % (chrom, b)])
             temp = sorted(set(temp))
+            if max_size is not None and len(temp) > max_size:
+                raise ValueError("%s: line %d has %d distinct bins: model(x) scores rows of at most %d" % (filepath, lineno, len(temp), max_size))
             if len(temp) > 1:
                 final.append(temp)
     return final
@@ -65,7 +69,9 @@ def parse_file(filepath: str, bin2node: Dict[str, int], chrom_list: Sequence[str
 
 def predict(model, samples, batch_size: int = CHUNK_ROWS) -> np.ndarray:
     """Logits [n, 1] (numpy) of a list / array of hyperedges: eval mode, no grad, chunks of ``batch_size`` rows, each chunk
-    zero-padded to ITS longest row (predict_multiway.py:74-87 == denoise_contact.py:76-88)."""
+    zero-padded to ITS longest row (predict_multiway.py:74-87 == denoise_contact.py:76-88).  Rows of up to 32 nodes: a chunk wider
+    than 8 takes the model's inference-only long forward; a longer row raises ValueError naming it, before anything is scored."""
+    U.check_row_sizes(samples, _lib.MAX_LONG_L)
     model.eval()
     dev = model.layer_norm1.weight.device
     out = []
@@ -80,8 +86,9 @@ def predict(model, samples, batch_size: int = CHUNK_ROWS) -> np.ndarray:
 
 def predict_multiway(model, filepath: str, bin2node: Dict[str, int], chrom_list: Sequence[str], res: int,
                      output: Optional[str] = None) -> Tuple[List[List[int]], np.ndarray]:
-    """predict_multiway.py:104-113: parse, score, sigmoid, optionally ``np.savetxt`` (one probability per line)."""
-    samples = parse_file(filepath, bin2node, chrom_list, res)
+    """predict_multiway.py:104-113: parse, score, sigmoid, optionally ``np.savetxt`` (one probability per line).  Lines of up to 32
+    distinct bins; a longer one fails with its line number before anything is scored."""
+    samples = parse_file(filepath, bin2node, chrom_list, res, max_size=_lib.MAX_LONG_L)
     proba = torch.sigmoid(torch.from_numpy(predict(model, samples))).numpy()
     if output is not None:
         np.savetxt(output, proba)

@@ -11,7 +11,8 @@ from . import _lib
 
 
 class HyperedgeSet:
-    """Exact membership set of known hyperedges (all sizes in one table).  ``edges``: int64 [M, L] zero-padded,
+    """Exact membership set of known hyperedges (all sizes in one table).  ``edges``: int64 [M, L] zero-padded, L <= 8 (the long rows of
+    the inference forward, 9 .. 32 nodes, have no membership set),
     each row ascending.  ``HyperedgeSet.empty(device, L)`` reproduces the reference's phase 1, where the
     "dict" is a list of empty python sets (main.py:589) and negatives come out equal to their positives."""
 

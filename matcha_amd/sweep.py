@@ -72,7 +72,7 @@ def _stream(dev):
 def kway_rows(lo: int, n: int, k: int, min_gap: int, rank0: int = 0, count: Optional[int] = None, ranks: Optional[torch.Tensor] = None,
               width: Optional[int] = None, device="cuda", out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """int64 [count, width] on the device: the candidates of ranks rank0 .. rank0 + count - 1, or of the device list ``ranks``
-    (a rank outside [0, total) gives an all-zero row).  Columns k .. width - 1 are zero; ``out`` reuses a buffer of at least
+    (a rank outside [0, total) gives an all-zero row).  Columns k .. width - 1 are zero (k <= width <= 8); ``out`` reuses a buffer of at least
     count * width elements."""
     lib = _lib.load()
     total = kway_count(n, k, min_gap)
@@ -160,7 +160,7 @@ def kway_sweep(model, lo: int, hi: int, k: int, min_gap: int, top: int, chunk_ro
     in pairwise_probabilities), ``rank`` int64 [K'] (decode one with kway_unrank), all on the model's device and best first, and
     the integers ``n_candidates`` and ``n_excluded``.  Selection is on the logits: the sigmoid saturates into ties, and the logit
     order is the probability order.  ``width`` (default k) zero-pads the rows: a row's logit depends on its batch's width because
-    pads are attended, so ask for the width the other predictions used.  ``exclude``: a HyperedgeSet of known hyperedges; its
+    pads are attended, so ask for the width the other predictions used (k and width stay at most 8 here: the long forward of model(x), 9 .. 32 columns, has no sweep).  ``exclude``: a HyperedgeSet of known hyperedges; its
     members are skipped and counted, which is what makes the result de novo.
 
     Eval mode, no grad; per chunk: rows into one reused buffer, model(x), TopK.update -- nothing is copied to the host and nothing

@@ -102,7 +102,10 @@ def save_embeddings(model: Classifier, n_nodes: int, path: Optional[str] = "../e
 
 @torch.no_grad()
 def predict(model: Classifier, rows, batch_size: int = 100000) -> np.ndarray:
-    """Logits [n,1] for a list / array of hyperedges, zero-padded per chunk like pad_sequence (main.py:482-494)."""
+    """Logits [n,1] for a list / array of hyperedges, zero-padded per chunk like pad_sequence (main.py:482-494).  Rows of up to 32
+    nodes (chunks wider than 8 take the model's inference-only long forward); a longer row raises ValueError naming it, before
+    anything is scored."""
+    U.check_row_sizes(rows, _lib.MAX_LONG_L)
     model.eval()
     dev = model.layer_norm1.weight.device
     outs = []

@@ -37,6 +37,18 @@ def pad_rows(rows) -> torch.Tensor:
     return t
 
 
+def check_row_sizes(rows, limit: int, what: str = "row") -> None:
+    """ValueError naming the first (1-based) row with more than ``limit`` nodes -- the widest row model(x) scores -- before
+    anything is scored: a chunk is padded to its longest row, so one such row would fail its whole chunk mid-run."""
+    if isinstance(rows, (np.ndarray, torch.Tensor)) and rows.ndim == 2:
+        if rows.shape[1] > limit:
+            raise ValueError("%s 1 has %d nodes: model(x) scores rows of at most %d" % (what, rows.shape[1], limit))
+        return
+    for i, r in enumerate(rows):
+        if len(r) > limit:
+            raise ValueError("%s %d has %d nodes: model(x) scores rows of at most %d" % (what, i + 1, len(r), limit))
+
+
 def sync_shuffle(sample_list: Sequence, max_num: int = -1) -> List:
     """Same random permutation applied to every array of the list, optionally truncated (reference utils.py:142-149)."""
     index = torch.randperm(len(sample_list[0]))
