@@ -85,7 +85,7 @@ int matcha_launch_log_read(char* out, size_t cap);
 
 /* A/B switches for tests and profiling.  Each option is read from the environment variable MATCHA_<NAME> (upper case) ONCE,
  * when the library is loaded, and can be changed afterwards only through matcha_set_option -- no entry point reads the
- * environment per call.  SEVEN switches: "disable_fused" (1 = layer-by-layer kernels at every embed_dim, also instead of the fused
+ * environment per call.  EIGHT switches: "disable_fused" (1 = layer-by-layer kernels at every embed_dim, also instead of the fused
  * attention block of embed_dim 128; 2 = only the front end as separate kernels, the encoder stays fused), "disable_merged" (the reference's four products per attention head instead of the
  * merged two; they live on the layer-by-layer kernels, so at embed_dim 64 this implies disable_fused), "disable_small_batch" (the
  * large-batch forward and plan kernels at every size), "disable_wide_gemm" (embed_dim >= 128: the 64-wide GEMM / attention kernels
@@ -97,7 +97,10 @@ int matcha_launch_log_read(char* out, size_t cap);
  * and both encoder kernels gather them by node id -- same logits and losses bit for bit), "disable_node_v" (on the node route with the r
  * table: the backward forms dZ = dDyn M_h and Z per token; without it a differentiated forward also leaves y = M_h x_hat per (node, head) and
  * the backward gathers the rows, from a token capacity of 64 (n_nodes + 1) on -- forward outputs bit for bit the same, gradients equal to
- * rounding); development: "debug_nan", "fused_dbg" (bit 0: the backward of
+ * rounding), "disable_node_dx" (on the node route with the value table: the encoder's input gradients -- d x_hat of the eight heads, the
+ * static branch's dXs -- are left per TOKEN and node_scatter_kernel adds them per node in one walk over the tokens; without it both producers
+ * add into per-node rows, one replica per head, and node_scatter_kernel finishes each node row -- forward outputs and the encoder's gradients
+ * bit for bit the same, the front end's gradients the same sums in another order); development: "debug_nan", "fused_dbg" (bit 0: the backward of
  * pff_n1's convolutions inside the forward kernel at every batch size, instead of tail_bwd64_kernel for large batches).  (Whether the tail's backward runs inside the forward
  * kernel is a per-call choice: matcha_step_opts.loss_in_forward.)  Returns MATCHA_EINVAL for an unknown name;
  * matcha_get_option returns -1 for one.

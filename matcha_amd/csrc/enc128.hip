@@ -523,7 +523,7 @@ __global__ __launch_bounds__(512) void enc128_bwd_kernel(BwdArgs g) {
 
   const int tid = threadIdx.x;
   int head, chunk;
-  if ((g.nchunks & 7) == 0) {          // the eight heads of a chunk on one XCD: their d x_hat atomics meet in that L2
+  if ((g.nchunks & 7) == 0) {          // the eight heads of a chunk on one XCD (their d x_hat atomics still execute at the memory side, not in that L2)
     const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
     head = j & 7;
     chunk = (j >> 3) * 8 + xcd;

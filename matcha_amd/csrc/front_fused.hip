@@ -555,8 +555,46 @@ __global__ __launch_bounds__(256) void node_xhat_kernel(const float* __restrict_
 struct NodeScatterArgs {
   const float* XN; const float* dxh; const float* dxpad; const float* dXs; const int32_t* key; const int32_t* count;
   float* G;                                       // [n_nodes + 1][64], zeroed by the forward's node launch
+  const int32_t* ncount; int64_t rows;            // per-node finisher (ncount != null): dxh = the heads' replicas [8][rows][64], G holds the per-node dXs sums
 };
+// The per-node finisher (StepRoute::node_dx): both producers added per node already -- the heads of fused_bwdh_kernel into one replica each, the
+// forward's tail its dXs rows into G -- and LNbwd_noaffine(. ; x_hat_node) is linear with per-node coefficients, so
+//   G[node] = LNbwd(sum_h AH[h][node] ; x_hat_node) + G[node]
+// with the heads summed in a fixed order.  Row 0 (the padding id; foreign ids land there too) also takes the shared padding token's dxpad, which
+// the token walk below adds as row T - 1.  16 lanes x float4 per node row, no atomics, no token is read.
+__device__ __forceinline__ void node_finish(const NodeScatterArgs& g) {
+  const int64_t row = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
+  const int c4 = (threadIdx.x & 15) * 4;
+  const int T = g.ncount[0];                      // n_nodes + 1
+  const int64_t rc = row < T ? row : (int64_t)T - 1;      // (clamped, not skipped: the DPP sums want whole 16-lane groups)
+  const float4 xv = *reinterpret_cast<const float4*>(g.XN + rc * 64 + c4);
+  float4 a[MATCHA_N_HEAD];
+#pragma unroll
+  for (int h = 0; h < MATCHA_N_HEAD; ++h) a[h] = *reinterpret_cast<const float4*>(g.dxh + ((int64_t)h * g.rows + rc) * 64 + c4);
+  // (the clamped groups of the last block read row T - 1 of G while its own group writes it: no race that matters -- `s` is used only in
+  // the store below, which rows >= T skip)
+  const float4 s = *reinterpret_cast<const float4*>(g.G + rc * 64 + c4);
+  float4 d;
+  d.x = ((a[0].x + a[1].x) + (a[2].x + a[3].x)) + ((a[4].x + a[5].x) + (a[6].x + a[7].x));
+  d.y = ((a[0].y + a[1].y) + (a[2].y + a[3].y)) + ((a[4].y + a[5].y) + (a[6].y + a[7].y));
+  d.z = ((a[0].z + a[1].z) + (a[2].z + a[3].z)) + ((a[4].z + a[5].z) + (a[6].z + a[7].z));
+  d.w = ((a[0].w + a[1].w) + (a[2].w + a[3].w)) + ((a[4].w + a[5].w) + (a[6].w + a[7].w));
+  if (rc == 0) {
+    const float4 dxp = *reinterpret_cast<const float4*>(g.dxpad + c4);
+    d.x += dxp.x; d.y += dxp.y; d.z += dxp.z; d.w += dxp.w;
+  }
+  const float mean = group_sum16_dpp((xv.x + xv.y) + (xv.z + xv.w)) * (1.f / 64.f);
+  const float a0 = xv.x - mean, a1 = xv.y - mean, a2 = xv.z - mean, a3 = xv.w - mean;
+  const float rs = __builtin_amdgcn_rsqf(group_sum16_dpp((a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3)) * (1.f / 64.f) + kEps);
+  const float4 xh = make_float4(a0 * rs, a1 * rs, a2 * rs, a3 * rs);
+  const float ma = group_sum16_dpp((d.x + d.y) + (d.z + d.w)) * (1.f / 64.f);
+  const float mb = group_sum16_dpp((d.x * xh.x + d.y * xh.y) + (d.z * xh.z + d.w * xh.w)) * (1.f / 64.f);
+  if (row < T)
+    *reinterpret_cast<float4*>(g.G + row * 64 + c4) =
+        make_float4(rs * (d.x - ma - xh.x * mb) + s.x, rs * (d.y - ma - xh.y * mb) + s.y, rs * (d.z - ma - xh.z * mb) + s.z, rs * (d.w - ma - xh.w * mb) + s.w);
+}
 __global__ __launch_bounds__(256) void node_scatter_kernel(NodeScatterArgs g) {
+  if (g.ncount) { node_finish(g); return; }       // (a launch parameter: the whole grid takes one body)
   __shared__ __attribute__((aligned(16))) float rows_s[2][16 * 64];
   __shared__ int keys_s[2][16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -712,9 +750,18 @@ int launch_node_xhat(const float* XN, const int32_t* node_count, int64_t rows_ca
 }
 
 // node route: one pass over the tokens that adds their front-end gradient rows per node (G, zeroed by the caller's forward)
-int launch_node_scatter(const float* XN, const float* dxh, const float* dxpad, const float* dXs, const Ragged& rg, int64_t tcap, float* G, hipStream_t st) {
+int launch_node_scatter(const float* XN, const float* dxh, const float* dxpad, const float* dXs, const Ragged& rg, int64_t tcap, float* G, hipStream_t st,
+                        const int32_t* node_count, int64_t rows) {
   NodeScatterArgs g;
-  g.XN = XN; g.dxh = dxh; g.dxpad = dxpad; g.dXs = dXs; g.key = rg.tok_key; g.count = rg.count; g.G = G;
+  g.XN = XN; g.dxh = dxh; g.dxpad = dxpad; g.dXs = dXs; g.key = rg.tok_key; g.count = rg.count; g.G = G; g.ncount = node_count; g.rows = rows;
+  if (node_count) {
+    // the per-node finisher: per node row the eight replicas, X and the dXs sum read, G written
+    MATCHA_CHECK_ARG(rows > 0, "node_scatter: the per-node finisher needs the table's row count");
+    ProfScope ps(MATCHA_PROF_FRONT_BWD, (double)rows * (MATCHA_N_HEAD + 3.0) * 256.0, st);
+    hipLaunchKernelGGL(node_scatter_kernel, dim3((unsigned)cdiv(rows, 16)), dim3(256), 0, st, g);
+    MATCHA_CHECK_LAUNCH("node_scatter_kernel");
+    return MATCHA_OK;
+  }
   int64_t grid = (int64_t)front_grid() * 4;                  // eight workgroups of four wavefronts per CU
   const int64_t trips = cdiv(tcap, 16);
   if (grid > trips) grid = trips;

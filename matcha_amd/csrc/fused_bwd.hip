@@ -295,8 +295,11 @@ struct FusedBwdHArgs {
                                                    // row xrow[t] (the plan's tok_key: 0 = padding) -- no LayerNorm in the staging
   const float* rn; int64_t rn_head;                // NODE instances, non-null: the heads' r rows per node [8][rn_head / 64][64] (node_r_kernel); the record holds probabilities only
   const float* vn;                                 // VTAB instances: the heads' value rows per node, y = M_h x_hat, laid out like rn (node_r_kernel's V role)
+  float* dx_node;                                  // VTAB instances, non-null: d x_hat is added per NODE -- [8][rn_head / 64][64], one replica per head (zeroed by the caller), token t
+                                                   // into row xrow[t]: the same atomic bytes as into dxh, and no row per token is left to walk (node_scatter_kernel finishes per node)
 };
-constexpr size_t kBwdLdsBytes = (size_t)2 * kTileH * 4 + (size_t)4 * kPT * 2 + (64 + 256 + 256 + 32) * 4;
+constexpr size_t kBwdLdsBytes = (size_t)2 * kTileH * 4 + (size_t)4 * kPT * 2 + (64 + 256 + 256 + 32 + 32) * 4;
+static_assert(2 * kBwdLdsBytes <= 160 * 1024, "two workgroups per CU");
 
 // VTAB (node route with the r AND the value table): per (half tile, head) THREE products and five barrier phases.  With
 // y_j = M_h x_hat_j gathered per node and U_j = sum_i p_ij dDyn_i in the column phase's value accumulator,
@@ -322,6 +325,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   float* dSs = xpad + 64;             // [32][8]
   float* Ps = dSs + 256;              // [32][8]
   int* tinfo = reinterpret_cast<int*>(Ps + 256);     // [32]
+  int* keys_s = tinfo + 32;                          // [32] dx_node: the half tile's table rows (tok_key), read by the d x_hat phase
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int c16 = lane & 15, kq = lane >> 4;           // 16x16x32 fragments: row / column c16, contraction slots 8 kq + {0..7}
@@ -376,7 +380,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   int4 mc = tile_lo < tile_hi ? meta[tile_lo] : mzero;
   int4 mn = tile_lo + 1 < tile_hi ? meta[tile_lo + 1] : mzero;
   float4 xn0, xn1, dn0, dn1;
-  int tpn = 0;
+  int tpn = 0, kyn = 0;               // (kyn, dx_node: the token's table row, fetched with tok_pos one half tile ahead)
   int kx0 = 0, kx1 = 0;               // NODE: the table rows of the half tile whose rows are fetched NEXT (loaded one half tile earlier: no dependent load in the prefetch)
 #define FBH_KEY_GLOAD(I, M)                                                                              \
   do {                                                                                                   \
@@ -394,7 +398,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #define FBH_ROWS_GLOAD(M)                                                                                \
   do {                                                                                                   \
     FBH_ROW_GLOAD(0, M); FBH_ROW_GLOAD(1, M);                                                            \
-    if (tid < 32) tpn = g.tok_pos[(M).x + (tid < (M).y ? tid : ((M).y > 0 ? (M).y - 1 : 0))];           \
+    if (tid < 32) {                                                                                      \
+      const int i__ = (M).x + (tid < (M).y ? tid : ((M).y > 0 ? (M).y - 1 : 0));                         \
+      tpn = g.tok_pos[i__];                                                                              \
+      if (VTAB && g.dx_node) kyn = g.xrow[i__];                                                          \
+    }                                                                                                    \
   } while (0)
   // NODE with the r table: this head's r rows of the same two table rows, row-major like the x_hat rows (16 lanes per 256-byte row).  Issued
   // next to FBH_ROWS_GLOAD while kx0 / kx1 still hold that half tile's keys
@@ -478,6 +486,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     {
       FBH_ROW_STAGE(0); FBH_ROW_STAGE(1);
       if (tid < 32) tinfo[tid] = tid < n_real ? ((tid - (tpn & 255)) | (tpn & ~255)) : 0;
+      if (VTAB && g.dx_node && tid < 32) keys_s[tid] = kyn;
       if constexpr (VTAB) {
         *reinterpret_cast<f32x4*>(&Fs[srow * kLd + sc4]) = yi0; *reinterpret_cast<f32x4*>(&Fs[(srow + 16) * kLd + sc4]) = yi1;
       }
@@ -571,8 +580,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if constexpr (NODE) { if (r_tab) FBH_R_GLOAD(); FBH_KEY_GLOAD(0, mnn); FBH_KEY_GLOAD(1, mnn); }      // ... its r rows (r table), and the table rows of the one after
     // ---- this head's share of d x_hat = dR B_h + Gs ----
     if (g.dx_atomic) {
-      // rows = tokens 4 kq + reg (+ 16), columns = features fb + c16: one atomic instruction covers 4 token rows x 64 contiguous bytes.  The
-      // eight heads of a chunk run on the same XCD at about the same time: the adds meet in that L2, and d x_hat leaves it once
+      // rows = tokens 4 kq + reg (+ 16), columns = features fb + c16: one atomic instruction covers 4 token rows x 64 contiguous bytes.  Float
+      // atomics execute at the memory side, not in an XCD's L2 (every 64-byte segment leaves L2 as one uncached request), so the eight heads' adds do
+      // NOT meet on chip: 0.47 GB of added bytes per launch at the headline, a floor of ~0.36 ms at the chip-wide ~1.3 TB/s
       const float* gp = Gs + (4 * kq) * kLd + fb + c16;
       f32x4 dx0 = {gp[0], gp[kLd], gp[2 * kLd], gp[3 * kLd]};
       f32x4 dx1 = {gp[16 * kLd], gp[17 * kLd], gp[18 * kLd], gp[19 * kLd]};
@@ -590,11 +600,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           dx0 = mma6(dx0, a0, Mf[s]); dx1 = mma6(dx1, a1, Mf[s]);
         }
       }
+      if (VTAB && g.dx_node) {
+        // per NODE, this head's replica: the same mask, the same four 64-byte segments per instruction, the same bytes -- the row is the token's
+        // table row instead of the token.  Wave-uniform base + a 32-bit lane offset: no address pairs held in registers
+        const int4 ka = *reinterpret_cast<const int4*>(&keys_s[4 * kq]), kb = *reinterpret_cast<const int4*>(&keys_s[16 + 4 * kq]);
+        const int k0[4] = {ka.x, ka.y, ka.z, ka.w}, k1[4] = {kb.x, kb.y, kb.z, kb.w};
+        float* ah = g.dx_node + (int64_t)head * g.rn_head;
+        const uint32_t col = (uint32_t)(fb + c16);
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          if (4 * kq + reg < n_real) unsafeAtomicAdd(ah + ((uint32_t)k0[reg] * 64u + col), dx0[reg]);
+          if (16 + 4 * kq + reg < n_real) unsafeAtomicAdd(ah + ((uint32_t)k1[reg] * 64u + col), dx1[reg]);
+        }
+      } else {
       float* out = g.dxh + ((int64_t)t0 + 4 * kq) * 64 + fb + c16;
 #pragma unroll
       for (int reg = 0; reg < 4; ++reg) {
         if (4 * kq + reg < n_real) unsafeAtomicAdd(out + reg * 64, dx0[reg]);
         if (16 + 4 * kq + reg < n_real) unsafeAtomicAdd(out + (16 + reg) * 64, dx1[reg]);
+      }
       }
     } else {
       f32x4 dx0 = *reinterpret_cast<const f32x4*>(&Gs[c16 * kLd + fb + 4 * kq]);
@@ -1009,6 +1033,7 @@ int launch_fused_bwd_merged(const matcha_tensors& p, const Ragged& rg, int64_t B
   MATCHA_CHECK_ARG(!xrow || xhatN, "fused backward: the node route needs the table of normalised rows");
   MATCHA_CHECK_ARG(!rn || xrow, "fused backward: the r table belongs to the node route");
   MATCHA_CHECK_ARG(!vn || rn, "fused backward: the value table needs the r table");
+  MATCHA_CHECK_ARG(!a.dx_node || (vn && dx_atomic && a.dx_zeroed), "fused backward: per-node d x_hat sums need the value table, the atomics and a caller that zeroed them");
   if (dx_atomic && !a.dx_zeroed) MATCHA_TRY(zero_async(dxh, (size_t)tcap * 64 * sizeof(float), st));
   int nchunks = 2 * chunks_for(rg.nhalves);                  // two four-wave workgroups per CU
   if (nchunks > kMaxChunks) nchunks = kMaxChunks;
@@ -1023,7 +1048,7 @@ int launch_fused_bwd_merged(const matcha_tensors& p, const Ragged& rg, int64_t B
     FusedBwdHArgs g;
     g.X = xrow ? xhatN : X; g.dDyn = a.dDyn; g.count = rg.count; g.half_meta = rg.half_meta; g.tok_pos = rg.tok_pos; g.L = L; g.nhalves = rg.nhalves; g.nchunks = nchunks;
     g.mB = mv.B; g.mM = mv.M; g.dxh = dxh; g.tcap = tcap; g.dx_atomic = dx_atomic ? 1 : 0; g.wslab = wslab; g.rimg = a.rimg; g.xrow = xrow;
-    g.rn = rn; g.rn_head = a.x.rows * 64; g.vn = vn;
+    g.rn = rn; g.rn_head = a.x.rows * 64; g.vn = vn; g.dx_node = a.dx_node ? dxh : nullptr;
     const size_t lds = kBwdLdsBytes;
     auto launch = [&](auto kfn) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);

@@ -294,6 +294,7 @@ struct Fwd32Args {
   float* tail_dh2;    // single-wave kernel, training: [T][64] dH2 rows -- the tail's backward stops behind its LayerNorms, tail_bwd64_kernel does the convolutions
   const float* rn;    // node route, single-wave kernel: the heads' r rows per NODE, [8][rn_rows][64] (node_r_kernel) -- gathered by xrow instead of computed per token
   int rn_rows;
+  float* dxs_node;    // node route, single-wave kernel, training: [rn_rows][64] per-NODE sums of the dXs rows (zeroed by the caller) -- added here by xrow, no row per token
 };
 
 // Merged per-head matrices (two products per head: r = B_h x + b_h, dyn += M_h z).
@@ -539,7 +540,28 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 #define F32_UNPARK_H1() fl_unpark(g.H1, F32_ROW())
 #define F32_PARK_HH(V) do { if (g.H2) fl_store_global(g.H2 + F32_ROW(), V); } while (0)
 #define F32_UNPARK_HH() fl_unpark(g.H2, F32_ROW())
+  // dXs.  Node route with per-node sums: the 32 rows go through T1 (dead between two column walks; x_hat lives in registers since F32_XH_RELOAD), then
+  // ONE wave-instruction adds one whole 256-byte row of one node (64 lanes x 4 B; the key is wave-uniform: readlane) -- the shape that runs at the
+  // atomics' full rate, as in node_scatter_kernel; lane-per-row adds straight from layout FL are the shape that serialises.  Rows i < n only: the
+  // padding token's row is zero
+#define F32_DXS_OUT(V)                                                                                   \
+  do {                                                                                                   \
+    if (g.dxs_node) {                                                                                    \
+      const int key__ = g.xrow[F32_TOK()];                                                               \
+      F32_TAIL_SYNC();                                                                                   \
+      fl_store(myrow, V);                                                                                \
+      F32_TAIL_SYNC();                                                                                   \
+      float v__ = T1[lane];                           /* (row i + 1 is read while row i's add is issued) */ \
+      for (int i__ = 0; i__ < n; ++i__) {                                                                \
+        const float vn__ = T1[(i__ + 1 < n ? i__ + 1 : i__) * kLdH + lane];                              \
+        const int k__ = __builtin_amdgcn_readlane(key__, i__);                                           \
+        unsafeAtomicAdd(g.dxs_node + (int64_t)k__ * 64 + lane, v__);                                     \
+        v__ = vn__;                                                                                      \
+      }                                                                                                  \
+    } else if (r <= n) fl_store_global(g.dXs + F32_ROW(), V);                                            \
+  } while (0)
 #include "fused_fwd32_tail.hpp"
+#undef F32_DXS_OUT
 #undef F32_TAIL_SYNC
 #undef F32_PARK_Y
 #undef F32_PARK_H1
@@ -652,7 +674,9 @@ __global__ __launch_bounds__(512) void fused_fwd32h_kernel(Fwd32Args g) {
 #define F32_UNPARK_H1() fl_unpark_lds(Pd + kHT, r * kLdH + 4 * h)
 #define F32_PARK_HH(V) fl_store(Pd + 2 * kHT + r * kLdH + 4 * h, V)
 #define F32_UNPARK_HH() fl_unpark_lds(Pd + 2 * kHT, r * kLdH + 4 * h)
+#define F32_DXS_OUT(V) do { if (r <= n) fl_store_global(g.dXs + F32_ROW(), V); } while (0)
 #include "fused_fwd32_tail.hpp"
+#undef F32_DXS_OUT
 #undef F32_TAIL_SYNC
 #undef F32_PARK_Y
 #undef F32_PARK_H1
@@ -759,7 +783,7 @@ int launch_fused_fwd32(const matcha_tensors& p, const Ragged& rg, int64_t B, int
   g.xrow = a.x.xrow;
   MATCHA_CHECK_ARG(!a.x.rn || a.x.xrow, "fused forward: the r table belongs to the node route");
   g.rn = a.x.rn; g.rn_rows = (int)a.x.rows;
-  g.tail_dh2 = nullptr;
+  g.tail_dh2 = nullptr; g.dxs_node = nullptr;
   g.X = a.x.X; g.row_off = rg.row_off; g.tok_slot = rg.tok_slot; g.count = rg.count; g.half_meta = rg.half_meta; g.tok_pos = rg.tok_pos;
   g.L = L;
   g.wfrag = reinterpret_cast<const u32x4*>(a.frag);
@@ -784,6 +808,8 @@ int launch_fused_fwd32(const matcha_tensors& p, const Ragged& rg, int64_t B, int
     return MATCHA_OK;
   }
   g.tail_dh2 = g.ddyn0 ? a.tail_dh2 : nullptr;
+  MATCHA_CHECK_ARG(!a.dxs_node || (a.x.xrow && g.ddyn0), "fused forward: per-node dXs sums belong to the node route with the tail's backward in the kernel");
+  g.dxs_node = a.dxs_node;
   const size_t lds = ((size_t)2 * kHT + 64) * sizeof(float);
   dispatch_ml(L, [&](auto ml) { hipLaunchKernelGGL(fused_fwd32_kernel<decltype(ml)::value>, dim3(rg.nhalves), dim3(64), lds, st, g); });
   MATCHA_CHECK_LAUNCH("fused_fwd32_kernel");

@@ -4,7 +4,8 @@
 // fused_fwd32h_kernel (eight wavefronts per half tile, one per head; wavefront 0 runs the tail alone).  ONE wavefront executes this text in
 // both kernels, so no workgroup barrier appears in it: F32_TAIL_SYNC is a wave-local ordering point (s_waitcnt lgkmcnt(0) + a compiler
 // memory barrier; a wavefront's LDS operations execute in order).  The including kernel defines it, the locals the tail works on
-// (g, lane, r, h, n, n_h, b0, t0, real, xh, rx, dyn, TK, TV, outs, douts, krow, wp, W_, F32_BIAS, F32_XH_RELOAD) and
+// (g, lane, r, h, n, n_h, b0, t0, real, xh, rx, dyn, TK, TV, outs, douts, krow, wp, W_, F32_BIAS, F32_XH_RELOAD), where the
+// static branch's gradient rows go (F32_DXS_OUT: a store per token, or on the node route of the single-wave kernel adds per node) and
 // where Y, H1 and hh are PARKED between the forward and the backward half of the tail -- F32_PARK_Y / _H1 / _HH (store this lane's row) and
 // F32_UNPARK_Y / _H1 / _HH (an FL loaded back through a laundered pointer, so that the values do not stay in registers): the
 // single-wave kernel parks them in the workspace rows the layer-wise backward reads (Y, H1: L2-resident, 2 x 256 B per token), the
@@ -190,7 +191,7 @@
       const float a = xhalf_sum(fl_sum(t)) * (1.f / 64.f), b = xhalf_sum(fl_dot(t, xh)) * (1.f / 64.f);
 #pragma unroll
       for (int e = 0; e < 16; ++e) { t.lo[e] = rx * (t.lo[e] - a - xh.lo[e] * b); t.hi[e] = rx * (t.hi[e] - a - xh.hi[e] * b); }
-      if (r <= n) fl_store_global(g.dXs + F32_ROW(), t);      // the padding token's row is zero (dout = 0)
+      F32_DXS_OUT(t);                                 // the padding token's row is zero (dout = 0)
     }
     // layer_norm1 (dynamic branch)
     {

@@ -115,6 +115,7 @@ struct Options {
   int disable_node_front;    // the table front end once per TOKEN at every size (the node route -- once per node when tokens outnumber nodes -- off)
   int disable_node_r;        // node route: the heads' r rows computed per TOKEN inside the forward kernel and handed to the backward in the record (the per-node r table off)
   int disable_node_v;        // node route with the r table: the backward forms dZ / Z per token (the per-node value table y = M_h x_hat and the kernel instance on it off)
+  int disable_node_dx;       // node route with the value table: d x_hat / dXs per TOKEN and node_scatter_kernel's walk over the tokens (their per-node sums at the producers off)
   int debug_nan, fused_dbg;  // development
 };
 Options& options();
@@ -181,6 +182,7 @@ struct FusedFwdLaunch {
   float *ddyn0, *dXs, *tslab; float alpha;   // ddyn0 != null: the tail's backward runs in the kernel (needs targets)
   float* rimg;           // r rows + probabilities per (half tile, head) for the fused backward (null: a forward only)
   float* tail_dh2;       // large batches only: the convolutions' backward is left to launch_tail_bwd64
+  float* dxs_node = nullptr;   // node route, single-wave kernel with the tail's backward: dXs rows are ADDED per node into [x.rows][64] (zeroed by the caller) instead of stored per token
 };
 int launch_fused_fwd32(const matcha_tensors& p, const Ragged& rg, int64_t B, int L, const FusedFwdLaunch& a, hipStream_t st);
 // the r rows of every (head, node): rows of the per-node table XN -> RN[8][rows][64]; needs this step's fragment stream (launch_prep_heads / the front end's launch)
@@ -191,7 +193,7 @@ int launch_node_r(const float* XN, const float* frag, int64_t rows, float* rn, h
 int tail_bwd_grid();
 size_t tail_bwd_slab_floats();
 int launch_tail_bwd64(const matcha_tensors& p, const float* dH2, const float* Y, const float* H1, const Ragged& rg, const uint64_t* seed, float p_fc1,
-                      float p_pff, float* ddyn0, float* slab, const float* vslab, float* zero_rows, hipStream_t st,
+                      float p_pff, float* ddyn0, float* slab, const float* vslab, float* zero_rows, int64_t zero_floats, hipStream_t st,     // zero_floats > 0: zero_rows is that many floats (a multiple of 4), not [T][64]
                       const float* row_loss = nullptr, int64_t B = 0, float* losses = nullptr, bool zero_recon = false);   // losses != null: launch_loss_reduce's work in one extra block
 
 // fused_bwd.hip (embed_dim 64): attention-block backward from X and dDyn; accumulates the gradients of w_q/w_k/w_v, the
@@ -207,6 +209,7 @@ struct FusedBwdLaunch {
   float* ws;                      // fused_bwd_ws_floats()
   float* dZ0;                     // null: the fused front-end backward follows (always on the node route)
   bool dx_atomic, dx_zeroed;      // dx_zeroed: the caller already zeroed dxh[(B L + 1) x 64] on this stream
+  bool dx_node = false;           // VTAB instance: dxh is [8][x.rows][64] (zeroed by the caller), head h adds token t's row into row xrow[t] of its own replica
   const TailReduceArgs* tail;     // != null: the launch that sums this kernel's slabs also sums the forward's tail slabs (tail_reduce.hpp)
 };
 int launch_fused_bwd_merged(const matcha_tensors& p, const Ragged& rg, int64_t B, int L, const FusedBwdLaunch& a, matcha_tensors& grads, hipStream_t st);
@@ -243,7 +246,9 @@ int launch_front_bwd(const matcha_tensors& p, const float* X, const float* dxh, 
                      matcha_tensors& grads, hipStream_t st, int32_t* touched = nullptr,
                      const int32_t* node_count = nullptr);   // node_count != null: the node route -- rows = nodes, dXs = their summed gradient rows, no d x_hat term
 int launch_node_xhat(const float* XN, const int32_t* node_count, int64_t rows_cap, float* xhatN, hipStream_t st);     // x_hat = LayerNorm without affine, per node row
-int launch_node_scatter(const float* XN, const float* dxh, const float* dxpad, const float* dXs, const Ragged& rg, int64_t tcap, float* G, hipStream_t st);
+// node_count != null: dxh = the heads' per-node replicas [8][rows][64] and G already holds the per-node dXs sums -- the launch finishes G per node (no token walk)
+int launch_node_scatter(const float* XN, const float* dxh, const float* dxpad, const float* dXs, const Ragged& rg, int64_t tcap, float* G, hipStream_t st,
+                        const int32_t* node_count = nullptr, int64_t rows = 0);
 
 // attention.hip
 // shared_kv (embed_dim >= 128, merged heads): K and V are [T, d] tensors that every head attends (dK / dV still come back per head)

@@ -132,12 +132,16 @@ struct Workspace {
 //                            the switch: node_r_kernel also writes y = M_h x_hat per (node, head) in a differentiated forward and the backward's
 //                            VTAB instance gathers the rows -- no dZ product, no Z; the forward's outputs are the same bits either way; only
 //                            from node_v_shape's size on: below it the table does not pay and this switch changes nothing)
+//   disable_node_dx          node route with the value table: the encoder's input gradients (d x_hat of the eight heads, dXs of the tail) per TOKEN, added per
+//                            node by node_scatter_kernel's walk over the tokens (without the switch: both producers add into per-node rows where they
+//                            are produced -- one replica per head -- and node_scatter_kernel is the per-node finisher; the forward's outputs are the
+//                            same bits either way)
 //   disable_wide_gemm        embed_dim >= 128: the 64-wide GEMM / attention kernels (gemm_lds.hip, gemm_f32.hip, attention.hip; four-product
 //                            heads) instead of gemm_wide.hip / attention_wide.hip
 struct OptionName { const char* name; int Options::*field; };
 static const OptionName kOptionNames[] = {
     {"disable_fused", &Options::disable_fused}, {"disable_merged", &Options::disable_merged}, {"disable_small_batch", &Options::disable_small_batch},
-    {"disable_wide_gemm", &Options::disable_wide_gemm}, {"disable_node_front", &Options::disable_node_front}, {"disable_node_r", &Options::disable_node_r}, {"disable_node_v", &Options::disable_node_v}, {"debug_nan", &Options::debug_nan}, {"fused_dbg", &Options::fused_dbg}};
+    {"disable_wide_gemm", &Options::disable_wide_gemm}, {"disable_node_front", &Options::disable_node_front}, {"disable_node_r", &Options::disable_node_r}, {"disable_node_v", &Options::disable_node_v}, {"disable_node_dx", &Options::disable_node_dx}, {"debug_nan", &Options::debug_nan}, {"fused_dbg", &Options::fused_dbg}};
 Options& options() {
   static Options o = [] {
     Options v;
@@ -174,6 +178,10 @@ static bool node_front_shape(const matcha_shape& s, int64_t B, int L) { return s
 // table rows), same call, three alternations: no difference that the runs' own spread lets through at 8 192, 16 384 and 32 768 rows (capacity /
 // rows of the table = 13, 27, 53), -15 to -24 us of 1.2 ms at 65 536 rows (107) -- profiles/r10_node_v.md.  So the table is built from 64 on.
 static bool node_v_shape(const matcha_shape& s, int64_t B, int L) { return B * L + 1 >= 64 * ((int64_t)s.n_nodes + 1); }
+// ... and the per-node sums of the encoder's input gradients at their producers (StepRoute::node_dx): the per-head replicas live
+// in dO (8 (n_nodes + 1) rows of the 8 (B L + 1) there) and are zeroed by tail_bwd64_kernel, 6 MB instead of 59 MB at the headline shape.  Measured
+// against the parent's library like the value table (profiles/r12_node_dx.md); the rule is the value table's.
+static bool node_dx_shape(const matcha_shape& s, int64_t B, int L) { return node_v_shape(s, B, L); }
 // the loss can be computed: BCE needs labels and weights, the softplus MSE only its targets
 static bool has_target(int objective, const float* y, const float* w) { return objective == MATCHA_OBJECTIVE_SOFTPLUS_MSE ? y != nullptr : (y && w); }
 static int check_objective(int32_t objective, const char* fn) {
@@ -195,6 +203,7 @@ struct StepRoute {
   bool split_tail, dx_zeroed;    // ... up to its LayerNorms, the convolutions' as tail_bwd64_kernel;  the forward zeroed the d x_hat rows the backward's heads add into
   bool node;                     // table front end per NODE: X lives in the per-node table, rows by tok_key
   bool node_r, node_v;           // ... the heads' r rows gathered from the per-node table (none in the record);  ... and the value table VN left for the backward
+  bool node_dx;                  // ... d x_hat and dXs added per NODE by their producers (AH in dO, AS in GN): node_scatter_kernel is the per-node finisher
 };
 // Which route the forward that last ran on a workspace took.  matcha_backward keys off THIS record and reads no option: the two calls are
 // separate on the autograd path and the switches are process-wide, so a flip between them would otherwise make the backward consume records
@@ -371,6 +380,8 @@ static StepRoute decide_route(const matcha_shape& s, const matcha_step_opts& o, 
   // the backward kernel's heads ADD their d x_hat rows (float atomics) unless the sum has to be reproducible: the rows are zeroed by a launch
   // that runs anyway -- tail_bwd64_kernel, or for small batches the loss reduction's (which needs `losses`) -- and the record says so
   r.dx_zeroed = r.lif && atomics && (r.split_tail || r.small) && want_losses;
+  // node route with the value table: the forward's tail adds dXs per node, tail_bwd64_kernel zeroes the heads' per-node replicas behind it
+  r.node_dx = r.node_v && r.lif && r.split_tail && r.dx_zeroed && node_dx_shape(s, B, L) && !options().disable_node_dx;
   return r;
 }
 // what the encoder kernels and head_bwd read for X on this route (kernels.hpp): the per-node tables by tok_key, or X per token
@@ -594,9 +605,12 @@ static int forward_impl(const matcha_shape* shp, const matcha_tensors* params, c
     a.Y = keep ? w.Y : nullptr; a.H1 = keep ? w.H1 : nullptr; a.H2 = keep ? w.H2 : nullptr; a.rimg = keep ? w.qkv : nullptr;
     a.seed = opts->seed; a.p_fc1 = train ? opts->p_drop_fc1 : 0.f; a.p_pff = train ? opts->p_drop_pff : 0.f; a.alpha = opts->alpha;
     a.ddyn0 = route.lif ? w.ddyn0 : nullptr; a.dXs = w.dXs; a.tslab = w.tslab; a.tail_dh2 = route.split_tail ? w.dH2 : nullptr;
+    a.dxs_node = route.node_dx ? w.GN : nullptr;      // (zeroed by the plan's launch above)
+    MATCHA_CHECK_ARG(!route.node_dx || nx.rows <= Tn, "matcha_forward: the heads' per-node d x_hat rows do not fit dO");
     MATCHA_TRY(launch_fused_fwd32(p, w.rg, B, L, a, st));
     if (route.split_tail)
-      MATCHA_TRY(launch_tail_bwd64(p, w.dH2, w.Y, w.H1, w.rg, opts->seed, a.p_fc1, a.p_pff, w.ddyn0, w.tslab2, w.tslab, route.dx_zeroed ? w.dO : nullptr, st, w.row_loss, B, tgt ? losses : nullptr, recon_zero_in_loss));      // ... zeroes the backward's d x_hat rows, reduces the loss
+      MATCHA_TRY(launch_tail_bwd64(p, w.dH2, w.Y, w.H1, w.rg, opts->seed, a.p_fc1, a.p_pff, w.ddyn0, w.tslab2, w.tslab, route.dx_zeroed ? w.dO : nullptr,
+                                   route.node_dx ? (int64_t)MATCHA_N_HEAD * nx.rows * 64 : 0, st, w.row_loss, B, tgt ? losses : nullptr, recon_zero_in_loss));      // ... zeroes the backward's d x_hat rows, reduces the loss
     const bool zero_in_loss = route.dx_zeroed && !route.split_tail;
     if (tgt && losses && !route.split_tail)
       MATCHA_TRY(launch_loss_reduce(w.row_loss, B, losses, st, recon_zero_in_loss, zero_in_loss ? w.dO : nullptr, zero_in_loss ? (size_t)Tn * 64 * sizeof(float) : 0));
@@ -826,14 +840,16 @@ static int backward_impl(const matcha_shape* shp, const matcha_tensors* params, 
   if (route.fused) {
     // attention block (fc1, attention, Q/K/V projections, the three LayerNorms) from X and ddyn0 in one head-major kernel;
     // the forward pass left the folded weights in w.folded.  w.dO doubles as the 8 per-head d x_hat slabs.
-    // the eight heads add their d x_hat into ONE buffer with float atomics (they meet in L2; per-head slabs are 8 x 256 B per token written and read
-    // back).  `deterministic` and the row-sparse table gradient (whose sum is bitwise reproducible) keep the slabs and their fixed order: per call
+    // the eight heads add their d x_hat into ONE buffer with float atomics (executed at the memory side; per-head slabs are 8 x 256 B per token written
+    // and read back) -- or, node_dx, into one per-node replica each.  `deterministic` and the row-sparse table gradient (whose sum is bitwise reproducible) keep the slabs and their fixed order: per call
     const bool dx_atomic = !opts->deterministic && !opts->sparse_table_grad;
     MATCHA_CHECK_ARG(!route.node || dx_atomic, "matcha_backward: deterministic / sparse_table_grad differ from the forward's on this workspace");
     FusedBwdLaunch a;
     a.folded = w.folded; a.merged = w.merged; a.x = nx; a.dDyn = w.ddyn0; a.dXs = w.dXs; a.rimg = w.qkv;
     a.dxh = w.dO; a.ws = w.fb_ws; a.dZ0 = route.front ? nullptr : w.dZ0;
     a.dx_atomic = dx_atomic; a.dx_zeroed = dx_zeroed; a.tail = tail_in_bwd ? &tail_args : nullptr;
+    a.dx_node = route.node_dx;      // dxh = the heads' per-node replicas [8][n_nodes + 1][64] (zeroed by tail_bwd64_kernel)
+    MATCHA_CHECK_ARG(!route.node_dx || (dx_zeroed && nx.rows <= Tn), "matcha_backward: the heads' per-node d x_hat rows do not fit dO");
     MATCHA_TRY(launch_fused_bwd_merged(p, w.rg, B, L, a, g_, st));
     MATCHA_TRY(encoder_done(*opts, st));
     if (route.front) {
@@ -842,7 +858,8 @@ static int backward_impl(const matcha_shape* shp, const matcha_tensors* params, 
       if (route.node) {
         // the tokens' rows LNbwd(d x_hat) + dXs added per node (one pass over the tokens), then tanh' / next_w / attribute_nn / the table row
         // once per node: front_bwd_kernel over the ids 0..n_nodes with the sums in dXs' place, one writer per table-gradient row
-        MATCHA_TRY(launch_node_scatter(nx.X, w.dO, fused_bwd_dxpad(w.fb_ws), w.dXs, w.rg, Tn, w.GN, st));
+        // (node_dx: the producers added per node already -- the launch sums the heads' replicas in a fixed order and finishes each node row in place)
+        MATCHA_TRY(launch_node_scatter(nx.X, w.dO, fused_bwd_dxpad(w.fb_ws), w.dXs, w.rg, Tn, w.GN, st, route.node_dx ? w.node_cnt : nullptr, nx.rows));
         MATCHA_TRY(launch_front_bwd(p, nx.X, nullptr, 1, nx.rows, fused_bwd_dxpad(w.fb_ws), w.GN, w.x0N, w.node_ids, *frozen, s.n_attr, w.rg, nullptr, g_.table, w.front_ws, g_, st, touched, w.node_cnt));
         return MATCHA_OK;
       }

@@ -47,6 +47,8 @@ struct TailBwdArgs {
   float* ddyn0; float* slab;                        // slab [gridDim.x][kSlab]: dW1 | dW0 | the ten vector slots
   float* zero_rows;                                 // [T][64] or null: the buffer the attention block's backward adds its d x_hat into with float atomics --
                                                     // zeroed here row by row (a 13 us launch of its own otherwise)
+  int64_t zero_floats;                              // > 0 (node route, per-node d x_hat replicas): zero_rows is this many floats (a multiple of 4) that the workgroups zero in
+                                                    // their prologue, each its share -- nothing per token
   const float* row_loss; int64_t B; float* losses; int zero_recon;     // losses != null: ONE extra block (the last) reduces the forward's per-hyperedge losses
                                                     // to their mean (loss_reduce.hpp) -- a 7 us launch of its own otherwise
   const float* vslab;                               // the forward kernel's per-half-tile slabs: their vector slots 0-6 and 9 (LayerNorm / classifier
@@ -76,6 +78,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int tile_lo = blockIdx.x * per;
   const int tile_hi = tile_lo + per < nh ? tile_lo + per : nh;
 
+  if (g.zero_floats > 0) {
+    f32x4* z = reinterpret_cast<f32x4*>(g.zero_rows);
+    const int64_t n4 = g.zero_floats >> 2;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + tid; i < n4; i += (int64_t)nwg * 256) z[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+  const bool zero_tok = g.zero_rows && g.zero_floats == 0;
   if (blockIdx.x == 0 && tid < 16)                  // the shared padding token receives no gradient from the tail (its rows are masked)
     *reinterpret_cast<f32x4*>(g.ddyn0 + (int64_t)tr * 64 + 4 * tid) = (f32x4){0.f, 0.f, 0.f, 0.f};
   const bool drop1 = g.p_fc1 > 0.f, drop2 = g.p_pff > 0.f;
@@ -153,7 +161,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // ---- stage: this thread's 8 features of its row -> planes (rows past the tokens: zero gradient rows) ----
     {
       const V8 dh2 = scale8(row < n_real ? 1.f : 0.f, dn);
-      if (g.zero_rows && row < n_real) st8(g.zero_rows + ((int64_t)t0 + row) * 64 + 8 * sub, zero8());
+      if (zero_tok && row < n_real) st8(g.zero_rows + ((int64_t)t0 + row) * 64 + 8 * sub, zero8());
       add8(a_c1, dh2);
       st8(&Ds[row * kLd + 8 * sub], dh2);
       st8(&Hs[row * kLd + 8 * sub], hn);
@@ -301,11 +309,12 @@ size_t tail_bwd_slab_floats() { return (size_t)tail_bwd_grid() * kSlab; }
 // ddyn0 and one slab of parameter-gradient partials per workgroup (tail_bwd_slab_floats() floats at `slab`: the convolutions' gradients + the
 // forward's per-half-tile vector slots of `vslab` summed along the walk; launch_tail_reduce(..., n_slabs = tail_bwd_grid(), rowmajor) sums them)
 int launch_tail_bwd64(const matcha_tensors& p, const float* dH2, const float* Y, const float* H1, const Ragged& rg, const uint64_t* seed, float p_fc1,
-                      float p_pff, float* ddyn0, float* slab, const float* vslab, float* zero_rows, hipStream_t st, const float* row_loss, int64_t B,
+                      float p_pff, float* ddyn0, float* slab, const float* vslab, float* zero_rows, int64_t zero_floats, hipStream_t st, const float* row_loss, int64_t B,
                       float* losses, bool zero_recon) {
   TailBwdArgs g;
   g.row_loss = row_loss; g.B = B; g.losses = losses; g.zero_recon = zero_recon ? 1 : 0;
-  g.vslab = vslab; g.zero_rows = zero_rows;
+  g.vslab = vslab; g.zero_rows = zero_rows; g.zero_floats = zero_rows ? zero_floats : 0;
+  MATCHA_CHECK_ARG(zero_floats >= 0 && zero_floats % 4 == 0, "tail backward: the zeroed range is a whole number of float4");
   g.dH2 = dH2; g.Y = Y; g.H1 = H1; g.count = rg.count; g.half_meta = rg.half_meta; g.tok_slot = rg.tok_slot; g.nhalves = rg.nhalves;
   g.W0 = p.pff0_w; g.W1 = p.pff1_w; g.seed = seed; g.p_fc1 = p_fc1; g.p_pff = p_pff;
   g.ddyn0 = ddyn0; g.slab = slab;
