@@ -85,7 +85,7 @@ int matcha_launch_log_read(char* out, size_t cap);
 
 /* A/B switches for tests and profiling.  Each option is read from the environment variable MATCHA_<NAME> (upper case) ONCE,
  * when the library is loaded, and can be changed afterwards only through matcha_set_option -- no entry point reads the
- * environment per call.  EIGHT switches: "disable_fused" (1 = layer-by-layer kernels at every embed_dim, also instead of the fused
+ * environment per call.  NINE switches: "disable_fused" (1 = layer-by-layer kernels at every embed_dim, also instead of the fused
  * attention block of embed_dim 128; 2 = only the front end as separate kernels, the encoder stays fused), "disable_merged" (the reference's four products per attention head instead of the
  * merged two; they live on the layer-by-layer kernels, so at embed_dim 64 this implies disable_fused), "disable_small_batch" (the
  * large-batch forward and plan kernels at every size), "disable_wide_gemm" (embed_dim >= 128: the 64-wide GEMM / attention kernels
@@ -100,7 +100,12 @@ int matcha_launch_log_read(char* out, size_t cap);
  * rounding), "disable_node_dx" (on the node route with the value table: the encoder's input gradients -- d x_hat of the eight heads, the
  * static branch's dXs -- are left per TOKEN and node_scatter_kernel adds them per node in one walk over the tokens; without it both producers
  * add into per-node rows, one replica per head, and node_scatter_kernel finishes each node row -- forward outputs and the encoder's gradients
- * bit for bit the same, the front end's gradients the same sums in another order); development: "debug_nan", "fused_dbg" (bit 0: the backward of
+ * bit for bit the same, the front end's gradients the same sums in another order), "disable_launch_pairs" (the fused embed_dim 64 step with
+ * every small launch on its own; without it independent small launches share a launch as block roles: the chain rule's blocks of
+ * fbm_chain_kernel un-fold their own rows -- no fb_unfold_kernel --, and on the node route fb_unfold2's vectors ride in node_scatter_kernel, the
+ * plan's tile_pack pass in the table front end's forward and its tile_compact pass in node_r_kernel -- four launches fewer per node-route step,
+ * one fewer elsewhere; every role runs the text of the stand-alone kernel, so the plan and every output are the same bits either way;
+ * matcha_backward follows what the forward recorded); development: "debug_nan", "fused_dbg" (bit 0: the backward of
  * pff_n1's convolutions inside the forward kernel at every batch size, instead of tail_bwd64_kernel for large batches).  (Whether the tail's backward runs inside the forward
  * kernel is a per-call choice: matcha_step_opts.loss_in_forward.)  Returns MATCHA_EINVAL for an unknown name;
  * matcha_get_option returns -1 for one.

@@ -20,6 +20,8 @@
 #include "attr_src.hpp"
 #include "kernels.hpp"
 #include "prep_heads.hpp"
+#include "fb_unfold.hpp"
+#include "ragged_roles.hpp"
 
 namespace matcha {
 
@@ -224,6 +226,8 @@ struct FrontFwdArgs {
   float* x0; float* X;
   int nprep; PrepArgs prep;      // the first nprep blocks build the step's weight forms instead (prep_heads.hpp): they depend on the parameters only
   int prep_walks;                // ... and then walk tiles like the other blocks (the launch has one block per slot of the chip) or leave
+  int npack; TilePackArgs pack;  // the LAST npack blocks pack the plan's tile lists instead (ragged_roles.hpp; node route: this launch depends on the parameters
+                                 // only, the plan on the batch only), one task per wavefront, and leave.  Only in a launch that is not one block per slot
 };
 
 __global__ __launch_bounds__(256, 3) void front_fwd_kernel(FrontFwdArgs g) {
@@ -234,6 +238,11 @@ __global__ __launch_bounds__(256, 3) void front_fwd_kernel(FrontFwdArgs g) {
   // front-end blocks late and stretch the kernel by what they took --, so the role blocks build weight forms and THEN walk tiles like the
   // others, and the last (partial) round of tiles goes to the blocks without a role first.
   const int nprep = g.nprep;
+  const int nblk = (int)gridDim.x - g.npack;            // the blocks of the front end and its weight forms
+  if ((int)blockIdx.x >= nblk) {
+    tile_pack_role(g.pack, ((int)blockIdx.x - nblk) * 4 + ((int)threadIdx.x >> 6), (int)threadIdx.x & 63);
+    return;
+  }
   if ((int)blockIdx.x < nprep) {
     const int b = blockIdx.x;
     prep_heads_role(g.prep, b % kPrepGridX, (b / kPrepGridX) % kPrepGridY, b / (kPrepGridX * kPrepGridY), lds);
@@ -241,7 +250,7 @@ __global__ __launch_bounds__(256, 3) void front_fwd_kernel(FrontFwdArgs g) {
     __syncthreads();
   }
   const int nlate = g.prep_walks ? nprep : 0;           // front-end blocks that start late
-  const int vb = (int)blockIdx.x - (nprep - nlate), Gf = (int)gridDim.x - (nprep - nlate);
+  const int vb = (int)blockIdx.x - (nprep - nlate), Gf = nblk - (nprep - nlate);
   // The two weight matrices live in REGISTERS as MFMA operand fragments (32 + 16 per lane) instead of LDS tiles: 44 KB of LDS per
   // workgroup instead of 70, i.e. three workgroups per CU gathering rows -- this kernel is a gather, bytes in flight are what it needs
   float* Es = lds;                                // node rows, then x0 in place
@@ -423,6 +432,11 @@ __global__ __launch_bounds__(256, 4) void front_fwd3_kernel(FrontFwdArgs g) {
   const int nprep = g.nprep;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   bool late = false;
+  const int nblk = (int)gridDim.x - g.npack;            // the blocks of the front end and its weight forms
+  if ((int)blockIdx.x >= nblk) {
+    tile_pack_role(g.pack, ((int)blockIdx.x - nblk) * 4 + wave, lane);
+    return;
+  }
   if ((int)blockIdx.x < nprep) {
     const int b = blockIdx.x;
     prep_heads_role(g.prep, b % kPrepGridX, (b / kPrepGridX) % kPrepGridY, b / (kPrepGridX * kPrepGridY), lds);
@@ -458,7 +472,7 @@ __global__ __launch_bounds__(256, 4) void front_fwd3_kernel(FrontFwdArgs g) {
   const int ngroups = (T + 15) / 16;
   // group list: rounds over the wavefronts that are walking -- the role blocks join from round g.prep_walks - 1 on (they start late by about
   // what the weight forms take)
-  const int W = (int)gridDim.x * 4, Wn_ = W - nprep * 4;               // all wavefronts / the ones without a role
+  const int W = nblk * 4, Wn_ = W - nprep * 4;               // all wavefronts / the ones without a role
   const int r0 = g.prep_walks > 0 ? g.prep_walks - 1 : 0x3FFFFF;       // first round of the role blocks (never, when they do not walk: small batches)
   const int wv = late ? (int)blockIdx.x * 4 + wave : ((int)blockIdx.x - nprep) * 4 + wave;      // role waves: index among all, others: among the role-free
   const float scale = g.attr.scale;
@@ -556,6 +570,8 @@ struct NodeScatterArgs {
   const float* XN; const float* dxh; const float* dxpad; const float* dXs; const int32_t* key; const int32_t* count;
   float* G;                                       // [n_nodes + 1][64], zeroed by the forward's node launch
   const int32_t* ncount; int64_t rows;            // per-node finisher (ncount != null): dxh = the heads' replicas [8][rows][64], G holds the per-node dXs sums
+  int node_blocks;                                // the launch's own blocks (either body); the kUnfold2RoleBlocks blocks behind them (if launched) run fb_unfold2's vectors
+  Unfold2Args unfold2;
 };
 // The per-node finisher (StepRoute::node_dx): both producers added per node already -- the heads of fused_bwdh_kernel into one replica each, the
 // forward's tail its dXs rows into G -- and LNbwd_noaffine(. ; x_hat_node) is linear with per-node coefficients, so
@@ -594,6 +610,9 @@ __device__ __forceinline__ void node_finish(const NodeScatterArgs& g) {
         make_float4(rs * (d.x - ma - xh.x * mb) + s.x, rs * (d.y - ma - xh.y * mb) + s.y, rs * (d.z - ma - xh.z * mb) + s.z, rs * (d.w - ma - xh.w * mb) + s.w);
 }
 __global__ __launch_bounds__(256) void node_scatter_kernel(NodeScatterArgs g) {
+  // block role (StepRoute::paired): the attention block's final 64-vectors -- sums of fb_unfold's partials into ln_*_g / ln_*_b / fc1_b -- have
+  // nothing to do with the node rows; dxpad, which both bodies read, is final before this launch and the role leaves it alone (dxpad_add = 2)
+  if ((int)blockIdx.x >= g.node_blocks) { fb_unfold2_role(g.unfold2, (int)blockIdx.x - g.node_blocks); return; }
   if (g.ncount) { node_finish(g); return; }       // (a launch parameter: the whole grid takes one body)
   __shared__ __attribute__((aligned(16))) float rows_s[2][16 * 64];
   __shared__ int keys_s[2][16];
@@ -603,7 +622,7 @@ __global__ __launch_bounds__(256) void node_scatter_kernel(NodeScatterArgs g) {
   const int ntrips = (T + 15) / 16;
   const float4 dxp = *reinterpret_cast<const float4*>(g.dxpad + sc4);
   // two-stage prefetch on clamped indices (no branch around a load): the key one trip ahead of the rows it addresses
-  const int stride = (int)gridDim.x;
+  const int stride = g.node_blocks;
   auto tok_of = [&](int trip) { const int64_t t = (int64_t)trip * 16 + srow; return t < T ? t : (int64_t)T - 1; };
   int kn = g.key[tok_of(blockIdx.x)], knn = g.key[tok_of(blockIdx.x + stride < ntrips ? blockIdx.x + stride : blockIdx.x)];
   float4 xn, dn, sn;
@@ -692,7 +711,7 @@ int front_grid() {
 }  // namespace
 
 int launch_front_fwd(const matcha_tensors& p, const int64_t* ids, const float* table, const float* dense, const matcha_frozen& f, int n_attr,
-                     const Ragged& rg, int64_t tcap, float* x0, float* X, hipStream_t st, const PrepSpec* prep, const int32_t* count) {
+                     const Ragged& rg, int64_t tcap, float* x0, float* X, hipStream_t st, const PrepSpec* prep, const int32_t* count, const TilePackArgs* pack) {
   // attr_mode 1: this forward (front_fwd3_kernel) rebuilds a token's attribute row from its node id and reads no table; front_bwd_kernel
   // keeps GATHERING the rows (padded to one 128-byte unit when the caller padded them, attr_ld): its row pieces are loaded by eight threads
   // per row inside a register prefetch pipeline, and rebuilding them there put a branch around the loads and cost 20 % of the kernel.  So the
@@ -719,6 +738,16 @@ int launch_front_fwd(const matcha_tensors& p, const int64_t* ids, const float* t
   g.prep_walks = (g.nprep > 0 && max_tiles + g.nprep > slots) ? 1 : 0;      // (measured against 72 blocks on top of a full grid: 5 us per 65 536-row step)
   int64_t grid = g.prep_walks ? slots : g.nprep + (max_tiles < slots ? max_tiles : slots);
   if (grid < g.nprep + 1) grid = g.nprep + 1;
+  // the plan's tile_pack pass as a role: four tasks per block behind the launch's own -- unless that would oversubscribe the chip's slots (DESIGN.md
+  // 4.10: a role never rides on top of a full grid); then it runs as its own launch in front
+  g.npack = 0;
+  memset(&g.pack, 0, sizeof(g.pack));
+  const int pack_blocks = pack ? (int)cdiv(pack->ntasks, 4) : 0;
+  auto host_pack = [&](int64_t own_blocks, int64_t chip_slots) {
+    if (!pack) return MATCHA_OK;
+    if (own_blocks + pack_blocks <= chip_slots) { g.npack = pack_blocks; g.pack = *pack; return MATCHA_OK; }
+    return launch_tile_pack(*pack, st);
+  };
   // algorithmic bytes per token: id 8 + node row 256 + attribute row read (attr_mode 1: rebuilt from the id, nothing read); x0 and X rows
   // written (x0 == null: an inference forward -- nobody reads the pre-activation rows, they are not written)
   ProfScope ps(MATCHA_PROF_FRONT_FWD, (double)tcap * (8.0 + 256.0 + (computed ? 0.0 : 4.0 * n_attr) + (x0 ? 512.0 : 256.0)), st);
@@ -730,12 +759,16 @@ int launch_front_fwd(const matcha_tensors& p, const int64_t* ids, const float* t
     g.prep_walks = (g.nprep > 0 && rounds >= 4) ? 3 : 0;                       // (3: the role blocks skip the first two rounds)
     int64_t grid3 = g.prep_walks ? slots4 : g.nprep + (cdiv(ngroups, 4) < slots4 ? cdiv(ngroups, 4) : slots4);
     if (grid3 < g.nprep + 1) grid3 = g.nprep + 1;
+    MATCHA_TRY(host_pack(grid3, slots4));
+    grid3 += g.npack;
     const size_t lds3 = (size_t)kF3Lds * sizeof(float);
     static_assert(kF3Lds >= kPrepLdsFloats, "the weight-form role needs its LDS inside the front end's");
     if (x0) hipLaunchKernelGGL(front_fwd3_kernel<true>, dim3((unsigned)grid3), dim3(256), lds3, st, g);
     else hipLaunchKernelGGL(front_fwd3_kernel<false>, dim3((unsigned)grid3), dim3(256), lds3, st, g);
     MATCHA_CHECK_LAUNCH("front_fwd3_kernel");
   } else {
+    MATCHA_TRY(host_pack(grid, slots));
+    grid += g.npack;
     hipLaunchKernelGGL(front_fwd_kernel, dim3((unsigned)grid), dim3(256), lds, st, g);
     MATCHA_CHECK_LAUNCH("front_fwd_kernel");
   }
@@ -751,23 +784,29 @@ int launch_node_xhat(const float* XN, const int32_t* node_count, int64_t rows_ca
 
 // node route: one pass over the tokens that adds their front-end gradient rows per node (G, zeroed by the caller's forward)
 int launch_node_scatter(const float* XN, const float* dxh, const float* dxpad, const float* dXs, const Ragged& rg, int64_t tcap, float* G, hipStream_t st,
-                        const int32_t* node_count, int64_t rows) {
+                        const int32_t* node_count, int64_t rows, const Unfold2Args* unfold2) {
   NodeScatterArgs g;
+  MATCHA_CHECK_ARG(!unfold2 || unfold2->dxpad_add == 2, "node_scatter: the launch hosts fb_unfold2's vectors only with dxpad final");
+  g.node_blocks = node_count ? (int)cdiv(rows, 16) : 0;
+  if (unfold2) g.unfold2 = *unfold2; else memset(&g.unfold2, 0, sizeof(g.unfold2));
   g.XN = XN; g.dxh = dxh; g.dxpad = dxpad; g.dXs = dXs; g.key = rg.tok_key; g.count = rg.count; g.G = G; g.ncount = node_count; g.rows = rows;
   if (node_count) {
     // the per-node finisher: per node row the eight replicas, X and the dXs sum read, G written
     MATCHA_CHECK_ARG(rows > 0, "node_scatter: the per-node finisher needs the table's row count");
     ProfScope ps(MATCHA_PROF_FRONT_BWD, (double)rows * (MATCHA_N_HEAD + 3.0) * 256.0, st);
-    hipLaunchKernelGGL(node_scatter_kernel, dim3((unsigned)cdiv(rows, 16)), dim3(256), 0, st, g);
+    hipLaunchKernelGGL(node_scatter_kernel, dim3((unsigned)(g.node_blocks + (unfold2 ? kUnfold2RoleBlocks : 0))), dim3(256), 0, st, g);
     MATCHA_CHECK_LAUNCH("node_scatter_kernel");
     return MATCHA_OK;
   }
   int64_t grid = (int64_t)front_grid() * 4;                  // eight workgroups of four wavefronts per CU
   const int64_t trips = cdiv(tcap, 16);
   if (grid > trips) grid = trips;
+  // (the role's two blocks are taken FROM a full grid, not put on top of it: DESIGN.md 4.10)
+  if (unfold2 && grid > 4 * kUnfold2RoleBlocks) grid -= kUnfold2RoleBlocks;
+  g.node_blocks = (int)grid;
   // algorithmic bytes per token: the d x_hat sum + dXs read, the key, the node's X row (from L2), 256 B of atomics
   ProfScope ps(MATCHA_PROF_FRONT_BWD, (double)tcap * (4.0 * 256.0 + 4.0), st);
-  hipLaunchKernelGGL(node_scatter_kernel, dim3((unsigned)grid), dim3(256), 0, st, g);
+  hipLaunchKernelGGL(node_scatter_kernel, dim3((unsigned)(grid + (unfold2 ? kUnfold2RoleBlocks : 0))), dim3(256), 0, st, g);
   MATCHA_CHECK_LAUNCH("node_scatter_kernel");
   return MATCHA_OK;
 }

@@ -23,6 +23,7 @@
 #include "bf16x3.hpp"
 #include "kernels.hpp"
 #include "tail_reduce.hpp"
+#include "fb_unfold.hpp"
 
 namespace matcha {
 
@@ -31,9 +32,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 namespace {
 
 constexpr int kLd = 68;              // LDS row stride (floats)
-constexpr float kEpsLn = 1e-5f;
-constexpr int kWgSlab = 4 * 4096 + 6 * 64;   // dW'q dW'k dW'v dWfc1 | dcq dck dcv dKpad dVpad dfc1_b
-constexpr int kVecOff = 4 * 4096;
+// (kWgSlab / kVecOff -- the slab format dW'q dW'k dW'v dWfc1 | dcq dck dcv dKpad dVpad dfc1_b -- and ln_row16: fb_unfold.hpp)
 constexpr int kMaxChunks = 64;
 
 #define ZR8(p)                                                                                           \
@@ -41,14 +40,6 @@ constexpr int kMaxChunks = 64;
     *reinterpret_cast<float4*>(p) = make_float4(0.f, 0.f, 0.f, 0.f);                                     \
     *reinterpret_cast<float4*>((p) + 4) = make_float4(0.f, 0.f, 0.f, 0.f);                               \
   } while (0)
-
-__device__ __forceinline__ void ln_row16(const float4& v, float& mean, float& rstd) {
-  const float s = group_sum<16>((v.x + v.y) + (v.z + v.w));
-  mean = s * (1.f / 64.f);
-  const float a = v.x - mean, b = v.y - mean, c = v.z - mean, e = v.w - mean;
-  const float q = group_sum<16>((a * a + b * b) + (c * c + e * e));
-  rstd = __builtin_amdgcn_rsqf(q * (1.f / 64.f) + kEpsLn);
-}
 
 // Attention forward + backward on LDS tiles, token-parallel: one 8-lane group per QUERY token (lane `sub` owns features
 // [8 sub, 8 sub + 8)), so a tile's <= 63 tokens fill the 32 groups of the workgroup in two passes and the work per group
@@ -803,9 +794,10 @@ __global__ __launch_bounds__(256) void fbm_reduce_kernel(ChainArgs a, TailReduce
   a.red[(int64_t)head * kWgSlabM + i] = ((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7));
 }
 // out[i][j] (16 rows of a 64 x 64 product per block) = sum_x A(i, x) B(x, j) [+ u[i] v[j]] with strided operands staged through LDS
+// (lds_out, uniform over the block: the 16 rows are left in As[i * 65 + j] instead of `out` -- the paired body un-folds them from there)
 __device__ __forceinline__ void mm64_slice(const float* __restrict__ A, int a_rs, int a_cs, const float* __restrict__ B, int b_rs, int b_cs,
                                            const float* __restrict__ u, const float* __restrict__ v, float* __restrict__ out, int slice,
-                                           float* __restrict__ As, float* __restrict__ Bs) {
+                                           float* __restrict__ As, float* __restrict__ Bs, bool lds_out = false) {
   const int tid = threadIdx.x;
   {
     // every load of the two operand tiles in flight before the first LDS store (strided operands: scalar loads)
@@ -827,16 +819,40 @@ __device__ __forceinline__ void mm64_slice(const float* __restrict__ A, int a_rs
   for (int kk = 0; kk < 16; ++kk) acc = MFMA16(As[c16 * 65 + 4 * kk + kq], Bs[(4 * kk + kq) * 65 + 16 * wave + c16], acc);
   const int j = 16 * wave + c16;
   const float vj = u ? v[j] : 0.f;
+  if (lds_out) __syncthreads();                        // every wavefront's fragment reads of As are behind it
 #pragma unroll
   for (int reg = 0; reg < 4; ++reg) {
     const int i = 4 * kq + reg;
-    out[(16 * slice + i) * 64 + j] = acc[reg] + (u ? u[16 * slice + i] * vj : 0.f);
+    const float o = acc[reg] + (u ? u[16 * slice + i] * vj : 0.f);
+    if (lds_out) As[i * 65 + j] = o; else out[(16 * slice + i) * 64 + j] = o;
   }
 }
-// grid (4 row slices, 4 jobs, 8 heads): the four matrix gradients of a head in fused_bwd8_kernel's slab format; slice 0 also the vectors
-__global__ __launch_bounds__(256) void fbm_chain_kernel(ChainArgs a) {
+// the two vector gradients of the chain rule, element m: two chains over the contraction index, even and odd (ONE text for block (0, 0, head),
+// which writes the vectors, and for the paired body's blocks, which need sixteen elements of one of them each)
+__device__ __forceinline__ float chain_dcq(const float* __restrict__ Wk, const float* __restrict__ db, int m) {      // dcq[m] = sum_a W'k[m][a] db[a]
+  float s0 = 0.f, s1 = 0.f;
+#pragma unroll 8
+  for (int x = 0; x < 64; x += 2) { s0 += Wk[m * 64 + x] * db[x]; s1 += Wk[m * 64 + x + 1] * db[x + 1]; }
+  return s0 + s1;
+}
+__device__ __forceinline__ float chain_dcv(const float* __restrict__ Wf, const float* __restrict__ dbdyn, int m) {   // dcv[m] = sum_n Wf[n][m] dbdyn[n]
+  float t0 = 0.f, t1 = 0.f;
+#pragma unroll 8
+  for (int x = 0; x < 64; x += 2) { t0 += Wf[x * 512 + m] * dbdyn[x]; t1 += Wf[(x + 1) * 512 + m] * dbdyn[x + 1]; }
+  return t0 + t1;
+}
+// grid (4 row slices, 4 jobs, 8 heads): the four matrix gradients of a head in fused_bwd8_kernel's slab format; slice 0 also the vectors.
+// paired (a launch parameter: the whole grid takes one body; StepRoute::paired): block (slice, job, head) of fb_unfold_kernel reads only the 16 rows
+// that this block writes, plus 16 elements of dcq (job 0) or dcv (job 2) from block (0, 0, head) -- so the block keeps its rows in LDS, computes
+// those elements itself in the same order, and un-folds them here (fb_unfold_rows, the text fb_unfold_kernel runs): one launch less, and the
+// matrices never go to the slab.  What fb_unfold_kernel makes of the slab with one chunk: s = 0 + row, dc = 0 + dcq | dck (= 0) | dcv,
+// dpad = 0 + dK_pad | dV_pad = 0 -- taken over literally, additions of zero included, so every gradient is the same bits.
+// dxpad_final (with paired, where fb_unfold2 rides in node_scatter_kernel, which READS dxpad): the term fb_unfold2's vec 6 adds to dxpad is a sum
+// of products with dpad = +0, which is +0 for finite weights, and dxpad + (+0) is what is stored here -- vec 6 is then not run at all.
+__global__ __launch_bounds__(256) void fbm_chain_kernel(ChainArgs a, UnfoldArgs uf, int paired, int dxpad_final) {
   __shared__ float As[16 * 65];
   __shared__ float Bs[64 * 65];
+  static_assert(sizeof(float) * 64 * 65 >= sizeof(float) * 16 * 3 * 64, "the un-folding's partials live in Bs");
   const int slice = blockIdx.x, job = blockIdx.y, head = blockIdx.z, tid = threadIdx.x;
   const float* red = a.red + (int64_t)head * kWgSlabM;
   const float* dB = red; const float* dM = red + 4096; const float* db = red + kVecOffM;
@@ -844,23 +860,18 @@ __global__ __launch_bounds__(256) void fbm_chain_kernel(ChainArgs a) {
   const float* Wq = a.wq + (int64_t)head * 4096; const float* Wk = a.wk + (int64_t)head * 4096; const float* Wv = a.wv + (int64_t)head * 4096;
   const float* Wf = a.fc1_w + head * 64;                  // Wf[n][m] = fc1_w[n * 512 + head * 64 + m]
   float* out = a.out + (int64_t)head * kWgSlab;
+  const bool lds_out = paired != 0;
   if (job == 0) {          // dW'q[m][b] = sum_a W'k[m][a] dB[a][b]
-    mm64_slice(Wk, 64, 1, dB, 64, 1, nullptr, nullptr, out + 0 * 4096, slice, As, Bs);
+    mm64_slice(Wk, 64, 1, dB, 64, 1, nullptr, nullptr, out + 0 * 4096, slice, As, Bs, lds_out);
   } else if (job == 1) {   // dW'k[m][a] = sum_b W'q[m][b] dB[a][b] + cq[m] db[a]
-    mm64_slice(Wq, 64, 1, dB, 1, 64, a.cq + head * 64, db, out + 1 * 4096, slice, As, Bs);
+    mm64_slice(Wq, 64, 1, dB, 1, 64, a.cq + head * 64, db, out + 1 * 4096, slice, As, Bs, lds_out);
   } else if (job == 2) {   // dW'v[m][b] = sum_n Wf[n][m] dM[n][b]
-    mm64_slice(Wf, 1, 512, dM, 64, 1, nullptr, nullptr, out + 2 * 4096, slice, As, Bs);
+    mm64_slice(Wf, 1, 512, dM, 64, 1, nullptr, nullptr, out + 2 * 4096, slice, As, Bs, lds_out);
   } else {                 // dWf[n][m] = sum_b dM[n][b] W'v[m][b] + dbdyn[n] cv[m]
-    mm64_slice(dM, 64, 1, Wv, 1, 64, dbdyn, a.cv + head * 64, out + 3 * 4096, slice, As, Bs);
+    mm64_slice(dM, 64, 1, Wv, 1, 64, dbdyn, a.cv + head * 64, out + 3 * 4096, slice, As, Bs, lds_out);
   }
   if (slice == 0 && job == 0 && tid < 64) {
-    float s0 = 0.f, s1 = 0.f, t0 = 0.f, t1 = 0.f;
-#pragma unroll 8
-    for (int x = 0; x < 64; x += 2) {
-      s0 += Wk[tid * 64 + x] * db[x]; s1 += Wk[tid * 64 + x + 1] * db[x + 1];
-      t0 += Wf[x * 512 + tid] * dbdyn[x]; t1 += Wf[(x + 1) * 512 + tid] * dbdyn[x + 1];
-    }
-    const float s = s0 + s1, t = t0 + t1;
+    const float s = chain_dcq(Wk, db, tid), t = chain_dcv(Wf, dbdyn, tid);
     out[kVecOff + tid] = s;                          // dcq[m] = sum_a W'k[m][a] db[a]
     out[kVecOff + 64 + tid] = 0.f;                   // dck: the K bias only shifts all scores of a query (no gradient)
     out[kVecOff + 128 + tid] = t;                    // dcv[m] = sum_n Wf[n][m] dbdyn[n]
@@ -869,19 +880,23 @@ __global__ __launch_bounds__(256) void fbm_chain_kernel(ChainArgs a) {
     if (head == 0) {
       float p = 0.f;
       for (int hh = 0; hh < MATCHA_N_HEAD; ++hh) p += a.red[(int64_t)hh * kWgSlabM + kVecOffM + 128 + tid];
-      a.dxpad[tid] = p;
+      a.dxpad[tid] = dxpad_final ? p + 0.f : p;
     }
   }
+  if (!paired) return;
+  const int rl = tid >> 4, c4 = (tid & 15) * 4, row = slice * 16 + rl;
+  float dc = 0.f, dpad = 0.f;
+  if (job == 0) dc += chain_dcq(Wk, db, row);        // (sixteen lanes per row compute the same element: loads of one address, no exchange)
+  else if (job == 1) dc += 0.f;
+  else if (job == 2) dc += chain_dcv(Wf, dbdyn, row);
+  if (job == 1 || job == 2) dpad += 0.f;
+  __syncthreads();                                   // the 16 rows are in As; nobody reads Bs any more
+  float4 s;
+  s.x = 0.f + As[rl * 65 + c4]; s.y = 0.f + As[rl * 65 + c4 + 1]; s.z = 0.f + As[rl * 65 + c4 + 2]; s.w = 0.f + As[rl * 65 + c4 + 3];
+  fb_unfold_rows(uf, slice, job, head, s, dc, dpad, reinterpret_cast<float (*)[3][64]>(Bs));
 }
 
-// ---- slab reduction + un-folding of the LayerNorm affines -------------------------------------------------------
-struct UnfoldArgs {
-  const float* wslab; int nchunks;
-  const float* X; const int32_t* count; int x_pad_row0;        // x_pad_row0: X is the per-node table, the padding token's row is row 0
-  const float* W[3]; const float* g[3]; const float* b[3];     // original projection weights [512, 64] and LN affines
-  float* gW[3]; float* gfc1;                                    // accumulated into
-  float* part;                                                  // [32][3][3][64]: {dg, db, dx_hat_pad} partials
-};
+// ---- slab reduction + un-folding of the LayerNorm affines (the per-row and per-vector texts: fb_unfold.hpp) --------------------------
 // grid (4 row slices, 4 matrices {q, k, v, fc1}, 8 heads), 256 threads = 16 rows x 16 lanes (float4)
 __global__ __launch_bounds__(256) void fb_unfold_kernel(UnfoldArgs a) {
   __shared__ float red[16][3][64];
@@ -909,68 +924,19 @@ __global__ __launch_bounds__(256) void fb_unfold_kernel(UnfoldArgs a) {
     s.x = (t0.x + t1.x) + (t2.x + t3.x); s.y = (t0.y + t1.y) + (t2.y + t3.y);
     s.z = (t0.z + t1.z) + (t2.z + t3.z); s.w = (t0.w + t1.w) + (t2.w + t3.w);
   }
-  if (mat == 3) {       // dfc1[n][head*64 + k]
-    float4* o = reinterpret_cast<float4*>(a.gfc1 + (int64_t)row * 512 + head * 64 + c4);
-    float4 v = *o;
-    v.x += s.x; v.y += s.y; v.z += s.z; v.w += s.w;
-    *o = v;
-    return;
-  }
   float dc = 0.f, dpad = 0.f;
-  for (int c = 0; c < a.nchunks; ++c) {
-    const float* vb = base + (int64_t)c * kWgSlab + kVecOff;
-    dc += vb[mat * 64 + row];
-    if (mat > 0) dpad += vb[192 + (mat - 1) * 64 + row];
-  }
-  // the padding token's K / V rows are x_hat_pad . W'^T + c: its dK / dV enter dW' and dc like one more token
-  const float4 xv = *reinterpret_cast<const float4*>(a.X + (a.x_pad_row0 ? (int64_t)0 : (int64_t)a.count[1] * 64) + c4);
-  float m, rs;
-  ln_row16(xv, m, rs);
-  s.x += dpad * (xv.x - m) * rs; s.y += dpad * (xv.y - m) * rs; s.z += dpad * (xv.z - m) * rs; s.w += dpad * (xv.w - m) * rs;
-  dc += dpad;
-  const int64_t wi = ((int64_t)head * 64 + row) * 64 + c4;
-  const float4 W = *reinterpret_cast<const float4*>(a.W[mat] + wi);
-  const float4 G = *reinterpret_cast<const float4*>(a.g[mat] + c4), Bv = *reinterpret_cast<const float4*>(a.b[mat] + c4);
-  {
-    float4* o = reinterpret_cast<float4*>(a.gW[mat] + wi);
-    float4 v = *o;
-    v.x += s.x * G.x + dc * Bv.x; v.y += s.y * G.y + dc * Bv.y; v.z += s.z * G.z + dc * Bv.z; v.w += s.w * G.w + dc * Bv.w;
-    *o = v;
-  }
-  *reinterpret_cast<float4*>(&red[rl][0][c4]) = make_float4(s.x * W.x, s.y * W.y, s.z * W.z, s.w * W.w);                              // dg
-  *reinterpret_cast<float4*>(&red[rl][1][c4]) = make_float4(dc * W.x, dc * W.y, dc * W.z, dc * W.w);                                  // db
-  *reinterpret_cast<float4*>(&red[rl][2][c4]) = make_float4(dpad * W.x * G.x, dpad * W.y * G.y, dpad * W.z * G.z, dpad * W.w * G.w);  // dx_hat_pad
-  __syncthreads();
-  if (tid < 192) {
-    const int which = tid >> 6, k = tid & 63;
-    float t = 0.f;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) t += red[q][which][k];
-    a.part[(((int64_t)(head * 4 + slice) * 3 + mat) * 3 + which) * 64 + k] = t;
-  }
+  if (mat < 3)
+    for (int c = 0; c < a.nchunks; ++c) {
+      const float* vb = base + (int64_t)c * kWgSlab + kVecOff;
+      dc += vb[mat * 64 + row];
+      if (mat > 0) dpad += vb[192 + (mat - 1) * 64 + row];
+    }
+  fb_unfold_rows(a, slice, mat, head, s, dc, dpad, red);
 }
 
-struct Unfold2Args {
-  const float* part; const float* wslab; int nchunks;
-  float* dg[3]; float* db[3]; float* dfc1_b; float* dxpad;
-  int dxpad_add;     // merged heads: dxpad already holds the attention's gradient into the padding token's x_hat (fbm_chain_kernel)
-};
-// one block, 512 threads: vec 0..5 = {dg, db} x {q, k, v}; vec 6 = dx_hat of the padding token; vec 7 = fc1 bias gradient
+// one block, 512 threads: eight 64-vectors
 __global__ __launch_bounds__(512) void fb_unfold2_kernel(Unfold2Args a) {
-  const int vec = threadIdx.x >> 6, k = threadIdx.x & 63;
-  float s = 0.f;
-  if (vec < 6) {
-    const int mat = vec >> 1, which = vec & 1;
-    for (int p = 0; p < 32; ++p) s += a.part[(((int64_t)p * 3 + mat) * 3 + which) * 64 + k];
-    float* o = (which == 0 ? a.dg[mat] : a.db[mat]) + k;
-    *o += s;
-  } else if (vec == 6) {
-    for (int p = 0; p < 32; ++p) s += a.part[(((int64_t)p * 3 + 1) * 3 + 2) * 64 + k] + a.part[(((int64_t)p * 3 + 2) * 3 + 2) * 64 + k];
-    a.dxpad[k] = a.dxpad_add ? a.dxpad[k] + s : s;
-  } else {
-    for (int c = 0; c < a.nchunks; ++c) s += a.wslab[(int64_t)c * kWgSlab + kVecOff + 320 + k];     // head 0's slabs
-    a.dfc1_b[k] += s;
-  }
+  fb_unfold2_vec(a, threadIdx.x >> 6, threadIdx.x & 63);
 }
 
 // dZ0 = ( LNbwd_noaffine( sum_h dxh[h] ) + dXs ) * (1 - X^2)     (Modules.py:519-521 backward, :270 tanh')
@@ -1080,26 +1046,33 @@ int launch_fused_bwd_merged(const matcha_tensors& p, const Ragged& rg, int64_t B
     const int tail_blocks = a.tail ? kTailRoleBlocks : 0;
     hipLaunchKernelGGL(fbm_reduce_kernel, dim3((unsigned)(kFbmReduceBlocks + tail_blocks)), dim3(256), 0, st, c, tl, tail_blocks);
     MATCHA_CHECK_LAUNCH("fbm_reduce_kernel");
-    hipLaunchKernelGGL(fbm_chain_kernel, dim3(4, 4, MATCHA_N_HEAD), dim3(256), 0, st, c);
+    UnfoldArgs u;
+    u.wslab = chain; u.nchunks = 1; u.X = X; u.count = rg.count; u.x_pad_row0 = xrow ? 1 : 0;
+    u.W[0] = p.w_q; u.W[1] = p.w_k; u.W[2] = p.w_v;
+    u.g[0] = p.ln_q_g; u.g[1] = p.ln_k_g; u.g[2] = p.ln_v_g;
+    u.b[0] = p.ln_q_b; u.b[1] = p.ln_k_b; u.b[2] = p.ln_v_b;
+    u.gW[0] = grads.w_q; u.gW[1] = grads.w_k; u.gW[2] = grads.w_v; u.gfc1 = grads.fc1_w;
+    u.part = part;
+    // paired (the step's record): the chain rule's blocks un-fold their own rows -- no fb_unfold_kernel launch;  unfold2 != null on top of it: the
+    // final vectors ride in the caller's node_scatter launch, which reads dxpad -- so the chain launch leaves dxpad final (fbm_chain_kernel says why it can)
+    MATCHA_CHECK_ARG(!a.unfold2 || a.paired, "fused backward: handing the final vectors on belongs to the paired launches");
+    hipLaunchKernelGGL(fbm_chain_kernel, dim3(4, 4, MATCHA_N_HEAD), dim3(256), 0, st, c, u, a.paired ? 1 : 0, a.unfold2 ? 1 : 0);
     MATCHA_CHECK_LAUNCH("fbm_chain_kernel");
-  }
-  {
-    UnfoldArgs a;
-    a.wslab = chain; a.nchunks = 1; a.X = X; a.count = rg.count; a.x_pad_row0 = xrow ? 1 : 0;
-    a.W[0] = p.w_q; a.W[1] = p.w_k; a.W[2] = p.w_v;
-    a.g[0] = p.ln_q_g; a.g[1] = p.ln_k_g; a.g[2] = p.ln_v_g;
-    a.b[0] = p.ln_q_b; a.b[1] = p.ln_k_b; a.b[2] = p.ln_v_b;
-    a.gW[0] = grads.w_q; a.gW[1] = grads.w_k; a.gW[2] = grads.w_v; a.gfc1 = grads.fc1_w;
-    a.part = part;
-    hipLaunchKernelGGL(fb_unfold_kernel, dim3(4, 4, MATCHA_N_HEAD), dim3(256), 0, st, a);
-    MATCHA_CHECK_LAUNCH("fb_unfold_kernel");
+    if (!a.paired) {
+      hipLaunchKernelGGL(fb_unfold_kernel, dim3(4, 4, MATCHA_N_HEAD), dim3(256), 0, st, u);
+      MATCHA_CHECK_LAUNCH("fb_unfold_kernel");
+    }
     Unfold2Args b;
     b.part = part; b.wslab = chain; b.nchunks = 1;
     b.dg[0] = grads.ln_q_g; b.dg[1] = grads.ln_k_g; b.dg[2] = grads.ln_v_g;
     b.db[0] = grads.ln_q_b; b.db[1] = grads.ln_k_b; b.db[2] = grads.ln_v_b;
-    b.dfc1_b = grads.fc1_b; b.dxpad = dxpad; b.dxpad_add = 1;
-    hipLaunchKernelGGL(fb_unfold2_kernel, dim3(1), dim3(512), 0, st, b);
-    MATCHA_CHECK_LAUNCH("fb_unfold2_kernel");
+    b.dfc1_b = grads.fc1_b; b.dxpad = dxpad; b.dxpad_add = a.unfold2 ? 2 : 1;
+    if (a.unfold2) {
+      *a.unfold2 = b;
+    } else {
+      hipLaunchKernelGGL(fb_unfold2_kernel, dim3(1), dim3(512), 0, st, b);
+      MATCHA_CHECK_LAUNCH("fb_unfold2_kernel");
+    }
   }
   if (float* dZ0 = a.dZ0) {
     MATCHA_CHECK_ARG(!xrow, "fused backward: the node route has no dZ0 output");

@@ -26,6 +26,7 @@
 // fused_fwd32h_kernel (below) is the same forward for small batches: eight wavefronts per half tile, one per head.
 #include "kernels.hpp"
 #include "prep_heads.hpp"
+#include "ragged_roles.hpp"
 
 #ifndef F32_ABL
 #define F32_ABL 0                     // timing ablations (tools/debug/abl_fwd32.sh; results are wrong on purpose): 1 no attention pieces, 2 no record stores,
@@ -712,11 +713,20 @@ __global__ __launch_bounds__(512) void fused_fwd32h_kernel(Fwd32Args g) {
 // gathers bit for bit the row the per-token product computes.  Rows row-major: RN[(h rows + node) 64 + f].
 // The V role (blockIdx.y >= 8, launched only by a forward that will be differentiated): the value rows y = M_h x_hat of the same nodes for the
 // backward's VTAB instance (fused_bwd.hip) -- the same prologue and chain, primed at M_hd's position in the stream, into a zero accumulator.
-struct NodeRArgs { const float* X; const u32x4* wfrag; float* rn; int rows; float* vn; };
+// The compaction role (blockIdx.y == 0 when ncompact = 1; StepRoute::paired): the plan's tile_compact pass -- it depends on the batch only, this
+// launch on the parameters only -- in the gridDim.x one-wavefront blocks of one more grid row (ragged_roles.hpp).  Row 0, so that its blocks, the
+// longest dependent chain of the launch, are dispatched first.
+struct NodeRArgs { const float* X; const u32x4* wfrag; float* rn; int rows; float* vn; int ncompact; CompactArgs compact; };
 __global__ __launch_bounds__(64) void node_r_kernel(NodeRArgs g) {
   const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
-  const int hd = blockIdx.y & 7;
-  const bool vrole = blockIdx.y >= MATCHA_N_HEAD;
+  if ((int)blockIdx.y < g.ncompact) {
+    __shared__ int offs[kCompactRoleSb + 1];
+    tile_compact_role(g.compact, (int)blockIdx.x, (int)gridDim.x, lane, offs);
+    return;
+  }
+  const int by = (int)blockIdx.y - g.ncompact;
+  const int hd = by & 7;
+  const bool vrole = by >= MATCHA_N_HEAD;
   const int row = (int)blockIdx.x * 32 + r;
   const bool live = row < g.rows;
   const u32x4* wp;
@@ -738,11 +748,18 @@ __global__ __launch_bounds__(64) void node_r_kernel(NodeRArgs g) {
 }
 
 size_t node_r_floats(int64_t rows) { return (size_t)MATCHA_N_HEAD * rows * 64; }
-int launch_node_r(const float* XN, const float* frag, int64_t rows, float* rn, hipStream_t st, float* vn) {
+int launch_node_r(const float* XN, const float* frag, int64_t rows, float* rn, hipStream_t st, float* vn, const CompactArgs* compact) {
   NodeRArgs g;
   g.X = XN; g.wfrag = reinterpret_cast<const u32x4*>(frag); g.rn = rn; g.rows = (int)rows; g.vn = vn;
+  g.ncompact = 0;
+  g.compact = CompactArgs{};
+  if (compact) {
+    // the role form takes one list and keeps the superblocks' offsets in LDS; anything else: the stand-alone kernel, in front
+    if (compact->first == 1 && compact->nsb <= kCompactRoleSb) { g.ncompact = 1; g.compact = *compact; }
+    else MATCHA_TRY(launch_tile_compact(*compact, st));
+  }
   ProfScope ps(MATCHA_PROF_FUSED_FWD, 0.0, st);       // part of the fused forward; no algorithmic work of its own
-  hipLaunchKernelGGL(node_r_kernel, dim3((unsigned)cdiv(rows, 32), vn ? 2 * MATCHA_N_HEAD : MATCHA_N_HEAD), dim3(64), 0, st, g);
+  hipLaunchKernelGGL(node_r_kernel, dim3((unsigned)cdiv(rows, 32), (vn ? 2 * MATCHA_N_HEAD : MATCHA_N_HEAD) + g.ncompact), dim3(64), 0, st, g);
   MATCHA_CHECK_LAUNCH("node_r_kernel");
   return MATCHA_OK;
 }

@@ -57,8 +57,10 @@ size_t ragged_bytes(int64_t B, int L);
 int ragged_tiles_cap(int64_t B, int L);
 int ragged_halves_cap(int64_t B, int L);
 void ragged_carve(int64_t B, int L, char* base, Ragged& r);
+struct PlanDeferred; struct TilePackArgs; struct CompactArgs;      // ragged_roles.hpp
 int launch_ragged_plan(const int64_t* x, int64_t B, int L, int64_t n_nodes, int32_t* status, const Ragged& r, hipStream_t st, int level = 2,
-                       int64_t* node_ids = nullptr, int32_t* node_cnt = nullptr, float* node_zero = nullptr);
+                       int64_t* node_ids = nullptr, int32_t* node_cnt = nullptr, float* node_zero = nullptr,
+                       PlanDeferred* defer = nullptr);      // != null: the two tile-list passes may be left to the caller (ragged.hip)
 // (node_ids != null: the plan also writes the id list 0..n_nodes and its length {n_nodes + 1, n_nodes}; node_zero != null: and zeroes [n_nodes + 1][64] floats)
 
 struct HeadParams {
@@ -116,6 +118,7 @@ struct Options {
   int disable_node_r;        // node route: the heads' r rows computed per TOKEN inside the forward kernel and handed to the backward in the record (the per-node r table off)
   int disable_node_v;        // node route with the r table: the backward forms dZ / Z per token (the per-node value table y = M_h x_hat and the kernel instance on it off)
   int disable_node_dx;       // node route with the value table: d x_hat / dXs per TOKEN and node_scatter_kernel's walk over the tokens (their per-node sums at the producers off)
+  int disable_launch_pairs;  // every small launch of the step on its own (StepRoute::paired off: the launches of the step as they were before the pairs)
   int debug_nan, fused_dbg;  // development
 };
 Options& options();
@@ -188,7 +191,8 @@ int launch_fused_fwd32(const matcha_tensors& p, const Ragged& rg, int64_t B, int
 // the r rows of every (head, node): rows of the per-node table XN -> RN[8][rows][64]; needs this step's fragment stream (launch_prep_heads / the front end's launch)
 // vn != null: the same launch also writes the value rows y = M_h x_hat (no bias) -> VN[8][rows][64] for the backward's VTAB instance
 size_t node_r_floats(int64_t rows);
-int launch_node_r(const float* XN, const float* frag, int64_t rows, float* rn, hipStream_t st, float* vn = nullptr);
+// compact != null: the plan's deferred compaction pass rides in the launch as a block role (or, beyond the role's reach, is launched in front of it)
+int launch_node_r(const float* XN, const float* frag, int64_t rows, float* rn, hipStream_t st, float* vn = nullptr, const CompactArgs* compact = nullptr);
 // tail_bwd.hip: the backward of pff_n1's two convolutions as its own kernel behind fused_fwd32_kernel (large batches)
 int tail_bwd_grid();
 size_t tail_bwd_slab_floats();
@@ -200,6 +204,7 @@ int launch_tail_bwd64(const matcha_tensors& p, const float* dH2, const float* Y,
 // three LayerNorm affines in front of them, fc1 (weight + bias) and writes dZ0 (gradient at the next_w pre-activation)
 size_t fused_bwd_ws_floats(int64_t B, int L);
 struct TailReduceArgs;
+struct Unfold2Args;               // fb_unfold.hpp
 struct FusedBwdLaunch {
   const float *folded, *merged;   // the forward left the step's weight forms here
   NodeOperands x;                 // on the node route token t stages row xrow[t] of xhat as it is
@@ -211,6 +216,8 @@ struct FusedBwdLaunch {
   bool dx_atomic, dx_zeroed;      // dx_zeroed: the caller already zeroed dxh[(B L + 1) x 64] on this stream
   bool dx_node = false;           // VTAB instance: dxh is [8][x.rows][64] (zeroed by the caller), head h adds token t's row into row xrow[t] of its own replica
   const TailReduceArgs* tail;     // != null: the launch that sums this kernel's slabs also sums the forward's tail slabs (tail_reduce.hpp)
+  bool paired = false;            // StepRoute::paired: fbm_chain_kernel's blocks un-fold their own rows (no fb_unfold_kernel launch)
+  Unfold2Args* unfold2 = nullptr; // with paired: fb_unfold2_kernel is NOT launched -- its arguments are left here for launch_node_scatter, which hosts it
 };
 int launch_fused_bwd_merged(const matcha_tensors& p, const Ragged& rg, int64_t B, int L, const FusedBwdLaunch& a, matcha_tensors& grads, hipStream_t st);
 size_t fused_qkv_floats(int64_t B, int L);         // what the training forward leaves for the fused backward, per (half tile, head):
@@ -239,7 +246,8 @@ bool front_bwd_supported(int d, int n_attr);
 struct PrepSpec { const matcha_tensors* p; float* folded; float* merged; float* frag; };
 int launch_front_fwd(const matcha_tensors& p, const int64_t* ids, const float* table, const float* dense, const matcha_frozen& f, int n_attr,
                      const Ragged& rg, int64_t tcap, float* x0, float* X, hipStream_t st, const PrepSpec* prep = nullptr,
-                     const int32_t* count = nullptr);      // count != null: the row count word to use instead of the plan's (node route: ids = 0..n_nodes)
+                     const int32_t* count = nullptr,       // count != null: the row count word to use instead of the plan's (node route: ids = 0..n_nodes)
+                     const TilePackArgs* pack = nullptr);  // != null: the plan's deferred tile_pack pass rides in the launch as a block role (or, where the launch is one block per slot of the chip, is launched in front of it)
 size_t front_bwd_ws_floats();
 int launch_front_bwd(const matcha_tensors& p, const float* X, const float* dxh, int nslab, int64_t tcap, const float* dxpad, const float* dXs, const float* x0,
                      const int64_t* ids, const matcha_frozen& f, int n_attr, const Ragged& rg, float* dX0, float* dtable, float* ws,
@@ -248,7 +256,8 @@ int launch_front_bwd(const matcha_tensors& p, const float* X, const float* dxh, 
 int launch_node_xhat(const float* XN, const int32_t* node_count, int64_t rows_cap, float* xhatN, hipStream_t st);     // x_hat = LayerNorm without affine, per node row
 // node_count != null: dxh = the heads' per-node replicas [8][rows][64] and G already holds the per-node dXs sums -- the launch finishes G per node (no token walk)
 int launch_node_scatter(const float* XN, const float* dxh, const float* dxpad, const float* dXs, const Ragged& rg, int64_t tcap, float* G, hipStream_t st,
-                        const int32_t* node_count = nullptr, int64_t rows = 0);
+                        const int32_t* node_count = nullptr, int64_t rows = 0,
+                        const Unfold2Args* unfold2 = nullptr);      // != null: two blocks behind the launch's own run fb_unfold2's vectors (fb_unfold.hpp)
 
 // attention.hip
 // shared_kv (embed_dim >= 128, merged heads): K and V are [T, d] tensors that every head attends (dK / dV still come back per head)

@@ -13,6 +13,8 @@
 
 #include "kernels.hpp"
 #include "tail_reduce.hpp"
+#include "fb_unfold.hpp"
+#include "ragged_roles.hpp"
 
 namespace matcha {
 
@@ -136,12 +138,16 @@ struct Workspace {
 //                            node by node_scatter_kernel's walk over the tokens (without the switch: both producers add into per-node rows where they
 //                            are produced -- one replica per head -- and node_scatter_kernel is the per-node finisher; the forward's outputs are the
 //                            same bits either way)
+//   disable_launch_pairs     the fused d = 64 step with every small launch on its own, as before the pairs of DESIGN.md 4.10 (without the switch:
+//                            fbm_chain_kernel's blocks un-fold their own rows -- no fb_unfold_kernel --; on the node route fb_unfold2's vectors ride in
+//                            node_scatter_kernel and the plan's tile_pack / tile_compact passes in the table front end's forward / node_r_kernel;
+//                            every output is the same bits either way)
 //   disable_wide_gemm        embed_dim >= 128: the 64-wide GEMM / attention kernels (gemm_lds.hip, gemm_f32.hip, attention.hip; four-product
 //                            heads) instead of gemm_wide.hip / attention_wide.hip
 struct OptionName { const char* name; int Options::*field; };
 static const OptionName kOptionNames[] = {
     {"disable_fused", &Options::disable_fused}, {"disable_merged", &Options::disable_merged}, {"disable_small_batch", &Options::disable_small_batch},
-    {"disable_wide_gemm", &Options::disable_wide_gemm}, {"disable_node_front", &Options::disable_node_front}, {"disable_node_r", &Options::disable_node_r}, {"disable_node_v", &Options::disable_node_v}, {"disable_node_dx", &Options::disable_node_dx}, {"debug_nan", &Options::debug_nan}, {"fused_dbg", &Options::fused_dbg}};
+    {"disable_wide_gemm", &Options::disable_wide_gemm}, {"disable_node_front", &Options::disable_node_front}, {"disable_node_r", &Options::disable_node_r}, {"disable_node_v", &Options::disable_node_v}, {"disable_node_dx", &Options::disable_node_dx}, {"disable_launch_pairs", &Options::disable_launch_pairs}, {"debug_nan", &Options::debug_nan}, {"fused_dbg", &Options::fused_dbg}};
 Options& options() {
   static Options o = [] {
     Options v;
@@ -204,6 +210,8 @@ struct StepRoute {
   bool node;                     // table front end per NODE: X lives in the per-node table, rows by tok_key
   bool node_r, node_v;           // ... the heads' r rows gathered from the per-node table (none in the record);  ... and the value table VN left for the backward
   bool node_dx;                  // ... d x_hat and dXs added per NODE by their producers (AH in dO, AS in GN): node_scatter_kernel is the per-node finisher
+  bool paired;                   // fused route: independent small launches share a launch -- the chain rule's blocks un-fold their own rows; with node_dx
+                                 // the node route the final vectors ride in node_scatter_kernel and the plan's tile lists in the table launches.  Off: the launches of the step one by one
 };
 // Which route the forward that last ran on a workspace took.  matcha_backward keys off THIS record and reads no option: the two calls are
 // separate on the autograd path and the switches are process-wide, so a flip between them would otherwise make the backward consume records
@@ -382,6 +390,7 @@ static StepRoute decide_route(const matcha_shape& s, const matcha_step_opts& o, 
   r.dx_zeroed = r.lif && atomics && (r.split_tail || r.small) && want_losses;
   // node route with the value table: the forward's tail adds dXs per node, tail_bwd64_kernel zeroes the heads' per-node replicas behind it
   r.node_dx = r.node_v && r.lif && r.split_tail && r.dx_zeroed && node_dx_shape(s, B, L) && !options().disable_node_dx;
+  r.paired = r.fused && !options().disable_launch_pairs;
   return r;
 }
 // what the encoder kernels and head_bwd read for X on this route (kernels.hpp): the per-node tables by tok_key, or X per token
@@ -556,8 +565,13 @@ static int forward_impl(const matcha_shape* shp, const matcha_tensors* params, c
   const bool keep = !opts->forward_only;       // a backward may follow: x0, the records and the saved rows are written
   const NodeOperands nx = node_operands(route, s, w);
   const bool tgt = has_target(objective, y, w_bce);
+  PlanDeferred deferred;
+  deferred.pending = false;
   MATCHA_TRY(launch_ragged_plan(x, B, L, s.n_nodes, opts->status, w.rg, st, route.half_plan ? 1 : 0, route.node ? w.node_ids : nullptr, route.node ? w.node_cnt : nullptr,
-                                (route.node && keep) ? w.GN : nullptr));      // ... which also writes the node route's id list and zeroes its accumulator
+                                (route.node && keep) ? w.GN : nullptr,        // ... which also writes the node route's id list and zeroes its accumulator
+                                (route.paired && route.node) ? &deferred : nullptr));
+  // (paired, node route: the plan's two tile-list passes -- batch only -- ride in the table launches below -- parameters only; the plan stops behind
+  // row_fill_kernel, which those launches need for their id list anyway.  deferred.pending: the five-launch plan ran and left them)
   // front end: node rows (K1) + attribute path (K6) + add (Modules.py:263-269)
   float* recon_out = losses ? losses + 1 : nullptr;
   // table front end: the two reconstruction-loss slots are zero; loss_reduce_kernel writes them when it runs anyway
@@ -576,11 +590,13 @@ static int forward_impl(const matcha_shape* shp, const matcha_tensors* params, c
     // (fused encoder behind it: the launch also builds the step's weight forms -- folded / merged / fragment-order -- in blocks of their own)
     const PrepSpec prep = {&p, w.folded, w.merged, w.frag};
     if (route.node) {     // the same kernel, once over the ids 0..n_nodes: the per-node tables (the weight-form blocks keep riding in the launch)
-      MATCHA_TRY(launch_front_fwd(p, w.node_ids, p.table, nullptr, *frozen, s.n_attr, w.rg, nx.rows, keep ? w.x0N : nullptr, nx.X, st, &prep, w.node_cnt));
+      MATCHA_TRY(launch_front_fwd(p, w.node_ids, p.table, nullptr, *frozen, s.n_attr, w.rg, nx.rows, keep ? w.x0N : nullptr, nx.X, st, &prep, w.node_cnt,
+                                  deferred.pending ? &deferred.pack : nullptr));
       // ... and, for the backward kernel's staging, their normalised rows
       if (keep) MATCHA_TRY(launch_node_xhat(nx.X, w.node_cnt, nx.rows, nx.xhat, st));
       // ... and the heads' r rows, from the fragment stream the launch above just wrote (training and inference alike)
-      if (nx.rn) MATCHA_TRY(launch_node_r(nx.X, w.frag, nx.rows, nx.rn, st, nx.vn));
+      if (nx.rn) MATCHA_TRY(launch_node_r(nx.X, w.frag, nx.rows, nx.rn, st, nx.vn, deferred.pending ? &deferred.compact : nullptr));
+      else if (deferred.pending) MATCHA_TRY(launch_tile_compact(deferred.compact, st));
     } else
     MATCHA_TRY(launch_front_fwd(p, ids, s.mode == 0 ? p.table : nullptr, s.mode == 0 ? nullptr : w.node, *frozen, s.n_attr, w.rg, Tn, keep ? w.x0 : nullptr, w.X, st, &prep));     // x0 (pre-activation) is only read by the backward pass
   } else if (!route.adj_fused) {
@@ -849,9 +865,14 @@ static int backward_impl(const matcha_shape* shp, const matcha_tensors* params, 
     a.dxh = w.dO; a.ws = w.fb_ws; a.dZ0 = route.front ? nullptr : w.dZ0;
     a.dx_atomic = dx_atomic; a.dx_zeroed = dx_zeroed; a.tail = tail_in_bwd ? &tail_args : nullptr;
     a.dx_node = route.node_dx;      // dxh = the heads' per-node replicas [8][n_nodes + 1][64] (zeroed by tail_bwd64_kernel)
+    // paired launches follow the record like every other choice here.  On the node route the last launch that writes an encoder gradient is then
+    // node_scatter_kernel (either body hosts fb_unfold2's vectors): encoder_done is recorded behind IT
+    Unfold2Args unfold2;
+    const bool unfold2_in_scatter = route.paired && route.front && route.node;
+    a.paired = route.paired; a.unfold2 = unfold2_in_scatter ? &unfold2 : nullptr;
     MATCHA_CHECK_ARG(!route.node_dx || (dx_zeroed && nx.rows <= Tn), "matcha_backward: the heads' per-node d x_hat rows do not fit dO");
     MATCHA_TRY(launch_fused_bwd_merged(p, w.rg, B, L, a, g_, st));
-    MATCHA_TRY(encoder_done(*opts, st));
+    if (!unfold2_in_scatter) MATCHA_TRY(encoder_done(*opts, st));
     if (route.front) {
       // LayerNorm backward of the summed partials + next_w + attribute_nn backward + embedding scatter in one kernel
       if (s.mode == 0) MATCHA_CHECK_ARG(g_.table, "matcha_backward: table mode without a table gradient buffer");
@@ -859,7 +880,9 @@ static int backward_impl(const matcha_shape* shp, const matcha_tensors* params, 
         // the tokens' rows LNbwd(d x_hat) + dXs added per node (one pass over the tokens), then tanh' / next_w / attribute_nn / the table row
         // once per node: front_bwd_kernel over the ids 0..n_nodes with the sums in dXs' place, one writer per table-gradient row
         // (node_dx: the producers added per node already -- the launch sums the heads' replicas in a fixed order and finishes each node row in place)
-        MATCHA_TRY(launch_node_scatter(nx.X, w.dO, fused_bwd_dxpad(w.fb_ws), w.dXs, w.rg, Tn, w.GN, st, route.node_dx ? w.node_cnt : nullptr, nx.rows));
+        MATCHA_TRY(launch_node_scatter(nx.X, w.dO, fused_bwd_dxpad(w.fb_ws), w.dXs, w.rg, Tn, w.GN, st, route.node_dx ? w.node_cnt : nullptr, nx.rows,
+                                       unfold2_in_scatter ? &unfold2 : nullptr));
+        if (unfold2_in_scatter) MATCHA_TRY(encoder_done(*opts, st));
         MATCHA_TRY(launch_front_bwd(p, nx.X, nullptr, 1, nx.rows, fused_bwd_dxpad(w.fb_ws), w.GN, w.x0N, w.node_ids, *frozen, s.n_attr, w.rg, nullptr, g_.table, w.front_ws, g_, st, touched, w.node_cnt));
         return MATCHA_OK;
       }

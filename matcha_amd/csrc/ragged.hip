@@ -22,6 +22,7 @@
 //   tok_tile [T+1]  compact token -> (tile << 6) | row inside that tile: where the forward's wavefront stores the token's Q / K / V
 //                   rows for the backward kernel, whose 64-row tiles cut the stream at other places than the half tiles
 #include "kernels.hpp"
+#include "ragged_roles.hpp"
 
 namespace matcha {
 
@@ -172,70 +173,17 @@ __global__ __launch_bounds__(256) void row_fill_kernel(const int64_t* __restrict
       reinterpret_cast<float4*>(node_zero)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-// Tiles of the fused kernels: runs of whole consecutive hyperedges with at most 63 tokens (+ the shared padding token = 64
-// rows), packed greedily so the MFMA tiles are ~96 % full (fixed windows of 64 - L first-token indices gave 90 %).
-// Greedy packing is sequential, so it runs per SUPERBLOCK (the hyperedges whose first token lies in a window of kSuperTok
-// tokens, ~32 tiles): one wavefront per superblock loads 64 row offsets at a time; a ballot finds the first hyperedge that
-// ends beyond the open tile, which closes it (about 4 closes per 64 hyperedges); only a superblock's last tile is partial.  A second kernel compacts the per-superblock lists.
-// tile_meta[w] = {first token t0, tokens, first hyperedge b0, hyperedges}; entries past the tile count are zero.
-constexpr int kFullTok = 63;
-constexpr int kHalfTok = 31;
-constexpr int kSuperTok = 63 * 32;
-
-// one wavefront packs superblock s of one list (half = the <= 31-token list); returns the number of tiles written to out[0 .. cap_per_sb)
-__device__ __forceinline__ int tile_pack_wave(const int32_t* __restrict__ row_off, int64_t B, int nsb, int s, bool half, int cap_per_sb,
-                                              const int32_t* __restrict__ sb_first, int4* __restrict__ out, int lane) {
-  const int kTileTok = half ? kHalfTok : kFullTok;
-  const int b_lo = sb_first[s];                        // marked by the fill pass (B: nothing starts here)
-  int b_hi = (int)B;
-  for (int q = s + 1; q < nsb; ++q)                    // next superblock that has a first hyperedge (normally s + 1)
-    if (sb_first[q] < (int)B) { b_hi = sb_first[q]; break; }
-  int nt = 0;
-  if (b_lo < b_hi) {
-    int tile_b0 = b_lo;
-    int tile_tok0 = __builtin_amdgcn_readfirstlane(row_off[b_lo]);
-    for (int base = b_lo; base < b_hi; base += 64) {
-      const int idx = base + lane;
-      const bool valid = idx < b_hi;
-      const int so = valid ? row_off[idx] : 0;         // first token of hyperedge idx
-      const int eo = valid ? row_off[idx + 1] : 0;     // one past its last token (monotone over idx)
-      for (;;) {
-        const uint64_t over = __ballot(valid && eo - tile_tok0 > kTileTok);   // hyperedges that end beyond the open tile
-        if (over == 0) break;
-        const int i = __ffsll((long long)over) - 1;    // the first of them closes the tile and opens the next one
-        const int start = __builtin_amdgcn_readlane(so, i);
-        if (lane == 0 && nt < cap_per_sb) out[nt] = make_int4(tile_tok0, start - tile_tok0, tile_b0, base + i - tile_b0);
-        ++nt;
-        tile_b0 = base + i;
-        tile_tok0 = start;
-      }
-    }
-    const int end = __builtin_amdgcn_readfirstlane(row_off[b_hi]);
-    if (lane == 0 && nt < cap_per_sb) out[nt] = make_int4(tile_tok0, end - tile_tok0, tile_b0, b_hi - tile_b0);
-    ++nt;
-  }
-  return nt < cap_per_sb ? nt : cap_per_sb;
-}
-
-// blockIdx.y = 0: tiles of <= 63 tokens; 1: half tiles of <= 31 tokens (same superblocks, own lists)
-__global__ __launch_bounds__(64) void tile_pack_kernel(const int32_t* __restrict__ row_off, int64_t B, int nsb, int cap_per_sb0, int cap_per_sb1,
-                                                       const int32_t* __restrict__ sb_first, int32_t* __restrict__ sb_tiles0,
-                                                       int32_t* __restrict__ sb_cnt0, int32_t* __restrict__ sb_tiles1, int32_t* __restrict__ sb_cnt1, int y0) {
-  const int s = blockIdx.x, lane = threadIdx.x;
-  const bool half = (int)blockIdx.y + y0 != 0;
-  const int cap_per_sb = half ? cap_per_sb1 : cap_per_sb0;
-  int32_t* sb_tiles = half ? sb_tiles1 : sb_tiles0;
-  int32_t* sb_cnt = half ? sb_cnt1 : sb_cnt0;
-  const int nt = tile_pack_wave(row_off, B, nsb, s, half, cap_per_sb, sb_first, reinterpret_cast<int4*>(sb_tiles) + (int64_t)s * cap_per_sb, lane);
-  if (lane == 0) sb_cnt[s] = nt;
+// (the tiles' definition, tile_pack_wave and the argument blocks of the two tile-list passes: ragged_roles.hpp -- both passes also run as block
+// roles of the node route's table launches, model.hip)
+__global__ __launch_bounds__(64) void tile_pack_kernel(TilePackArgs a) {
+  tile_pack_role(a, (int)blockIdx.y * a.nsb + (int)blockIdx.x, threadIdx.x);
 }
 
 // exclusive scan of the superblock tile counts (one block, 1024 counts per pass), compaction, zero fill; count[2] = tiles
-struct CompactArgs {
-  const int32_t* sb_tiles[2]; int32_t* sb_cnt[2]; int cap_per_sb[2]; int ntiles_cap[2]; int32_t* meta[2];
-};
 // blockIdx.x = 0: tiles -> tile_meta, count[2];  1: half tiles -> half_meta, count[3]
-__global__ __launch_bounds__(1024) void tile_compact_kernel(CompactArgs a, int nsb, int32_t* __restrict__ count, int x0) {
+__global__ __launch_bounds__(1024) void tile_compact_kernel(CompactArgs a) {
+  const int nsb = a.nsb, x0 = a.first;
+  int32_t* __restrict__ count = a.count;
   const int which = (int)blockIdx.x + x0;
   if (x0 != 0 && threadIdx.x == 0) count[2] = 0;       // half tiles only: no 64-row tile list this time
   const int32_t* __restrict__ sb_tiles = a.sb_tiles[which];
@@ -485,10 +433,25 @@ void ragged_carve(int64_t B, int L, char* base, Ragged& r) {
   r.tok_tile = (int32_t*)take((size_t)(T + 1) * 4);
 }
 
+// the two tile-list passes as launches of their own (the plan below; a host kernel that cannot take the role)
+int launch_tile_pack(const TilePackArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(tile_pack_kernel, dim3(a.nsb, 2 - a.first), dim3(64), 0, st, a);
+  MATCHA_CHECK_LAUNCH("tile_pack_kernel");
+  return MATCHA_OK;
+}
+int launch_tile_compact(const CompactArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(tile_compact_kernel, dim3(2 - a.first), dim3(1024), 0, st, a);
+  MATCHA_CHECK_LAUNCH("tile_compact_kernel");
+  return MATCHA_OK;
+}
+
 // level 2: everything; 1: no 64-row tile list and no token -> tile map (the fused kernels that run work on half tiles only); 0: rows and
 // tokens only (no fused kernel will read a tile list)
+// defer != null: with the five-launch plan at level 1 the two tile-list passes are NOT launched -- their argument blocks are left in *defer
+// (pending = true) for the caller, who runs them as roles of later launches or through launch_tile_pack / launch_tile_compact, in that order
 int launch_ragged_plan(const int64_t* x, int64_t B, int L, int64_t n_nodes, int32_t* status, const Ragged& r, hipStream_t st, int level,
-                       int64_t* node_ids, int32_t* node_cnt, float* node_zero) {
+                       int64_t* node_ids, int32_t* node_cnt, float* node_zero, PlanDeferred* defer) {
+  if (defer) defer->pending = false;
   if (B <= kSmallRows && r.nsb <= kSmallSb && !options().disable_small_batch) {
     PlanSmallArgs a;
     a.x = x; a.B = B; a.L = L; a.n_nodes = n_nodes; a.status = status;
@@ -511,14 +474,20 @@ int launch_ragged_plan(const int64_t* x, int64_t B, int L, int64_t n_nodes, int3
   MATCHA_CHECK_LAUNCH("row_fill_kernel");
   if (level <= 0) return MATCHA_OK;
   const int first = level >= 2 ? 0 : 1;                // list 0: 64-row tiles, list 1: half tiles
-  hipLaunchKernelGGL(tile_pack_kernel, dim3(r.nsb, 2 - first), dim3(64), 0, st, r.row_off, B, r.nsb, r.sb_cap, r.sb_hcap, r.sb_first, r.sb_tiles, r.sb_cnt,
-                     r.sb_htiles, r.sb_hcnt, first);
-  MATCHA_CHECK_LAUNCH("tile_pack_kernel");
+  TilePackArgs pa;
+  pa.row_off = r.row_off; pa.B = B; pa.nsb = r.nsb; pa.sb_first = r.sb_first; pa.first = first; pa.ntasks = r.nsb * (2 - first);
+  pa.cap_per_sb[0] = r.sb_cap; pa.sb_tiles[0] = r.sb_tiles; pa.sb_cnt[0] = r.sb_cnt;
+  pa.cap_per_sb[1] = r.sb_hcap; pa.sb_tiles[1] = r.sb_htiles; pa.sb_cnt[1] = r.sb_hcnt;
   CompactArgs ca;
   ca.sb_tiles[0] = r.sb_tiles; ca.sb_cnt[0] = r.sb_cnt; ca.cap_per_sb[0] = r.sb_cap; ca.ntiles_cap[0] = r.ntiles; ca.meta[0] = r.tile_meta;
   ca.sb_tiles[1] = r.sb_htiles; ca.sb_cnt[1] = r.sb_hcnt; ca.cap_per_sb[1] = r.sb_hcap; ca.ntiles_cap[1] = r.nhalves; ca.meta[1] = r.half_meta;
-  hipLaunchKernelGGL(tile_compact_kernel, dim3(2 - first), dim3(1024), 0, st, ca, r.nsb, r.count, first);
-  MATCHA_CHECK_LAUNCH("tile_compact_kernel");
+  ca.nsb = r.nsb; ca.count = r.count; ca.first = first;
+  if (defer && level == 1) {
+    defer->pending = true; defer->pack = pa; defer->compact = ca;
+    return MATCHA_OK;
+  }
+  MATCHA_TRY(launch_tile_pack(pa, st));
+  MATCHA_TRY(launch_tile_compact(ca, st));
   if (level >= 2) {
     hipLaunchKernelGGL(tok_tile_kernel, dim3(r.ntiles), dim3(64), 0, st, r.tile_meta, r.tok_tile);
     MATCHA_CHECK_LAUNCH("tok_tile_kernel");

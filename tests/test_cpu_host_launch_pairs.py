@@ -1,0 +1,23 @@
+"""decide_route's `paired` field (model.hip: independent small launches of the fused step share a launch) under AddressSanitizer +
+UndefinedBehaviorSanitizer on the host: tests/host/route_pairs.hip, a driver of its own on the host-only objects of
+tests/test_cpu_host_sanitizers.py -- the field over shapes, front ends, per-call options and every switch, that its switch takes out this
+field alone, the shapes of the headline and of tests/test_hip_launch_pairs.py, the record.  No kernel is launched."""
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_paired_route_under_asan_ubsan():
+    csrc = os.path.join(ROOT, "matcha_amd", "csrc")
+    build = subprocess.run(["make", "-C", csrc, "-j", str(min(8, os.cpu_count() or 1)), "host-asan-launch-pairs"], capture_output=True, text=True)
+    assert build.returncode == 0, build.stdout[-3000:] + build.stderr[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    for k in list(env):
+        if k.startswith("MATCHA_DISABLE") or k == "MATCHA_FUSED_DBG":
+            env.pop(k)
+    run = subprocess.run([os.path.join(ROOT, "build", "host_asan", "route_pairs")], capture_output=True, text=True, env=env, timeout=600)
+    out = run.stdout + run.stderr
+    assert run.returncode == 0, out[-4000:]
+    assert "ALL LAUNCH PAIR ROUTE CHECKS PASSED" in out
+    assert "AddressSanitizer" not in out and "runtime error" not in out, out[-4000:]
