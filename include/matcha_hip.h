@@ -34,7 +34,7 @@ extern "C" {
 #define MATCHA_ENOMEM (-12) /* workspace too small                             */
 
 #define MATCHA_MAX_L 8      /* widest hyperedge (BASELINE.json configs[4]: k in 2..8) */
-#define MATCHA_MAX_LONG_L 32 /* widest row of the inference-only long forward (matcha_forward_long) */
+#define MATCHA_MAX_LONG_L 32 /* widest row of the long forward (matcha_forward_long) and the long training pair (matcha_forward_long_train, matcha_backward_long) */
 #define MATCHA_N_HEAD 8     /* main.py:616 */
 
 typedef void* matcha_stream_t; /* hipStream_t */
@@ -280,6 +280,42 @@ size_t matcha_workspace_bytes_long(const matcha_shape* shp, int64_t B, int32_t L
 int matcha_forward_long(const matcha_shape* shp, const matcha_tensors* params, const matcha_frozen* frozen,
                         const matcha_step_opts* opts, const int64_t* x, int64_t B, int32_t L,
                         float* logits, float* losses, void* ws, size_t ws_bytes, matcha_stream_t stream);
+
+/* Long rows, training: matcha_forward_long_train is the chain of matcha_forward_long with every activation the backward needs kept in a
+ * buffer of its own (x0, X, the LayerNorm statistics, qin / kin / vin, Q or r, O or Z -- not written over Q --, Y, H1, H2, the logits);
+ * matcha_backward_long is the layer-by-layer chain of matcha_backward on that layout, with the attention backward of
+ * attention_long_bwd.hip (one 32 x 32 MFMA tile per head, the probabilities recomputed from Q and K, no float atomics).  Both head
+ * formulations: merged where embed_dim is a multiple of 64, the four products otherwise.  Same shapes and bounds as matcha_forward_long
+ * (2 <= L <= 32; L <= 8 too, so that the pair can be held against matcha_forward / matcha_backward on identical input).
+ *   opts->training, p_drop_adj / p_drop_fc1 / p_drop_pff and seed are honoured through the GEMM epilogues; the dropout counter is keyed by
+ *   the token slot b L + l.  opts->status, opts->random_chrom, opts->alpha and opts->encoder_done_event as in matcha_forward /
+ *   matcha_backward.  opts->deterministic, sparse_table_grad, loss_in_forward and random_chrom_dev: MATCHA_EINVAL before any device call
+ *   (they belong to the L <= 8 step; the table gradient is added with float atomics as in matcha_backward without `deterministic`).
+ *   logits float [B] out;  losses float [3] as matcha_forward_long, may be NULL.
+ *   matcha_backward_long: dlogits float [B] (required: the loss lives with the caller), drecon float [1] or NULL, gradients ACCUMULATE
+ *   into `grads`, `touched` as matcha_backward.  One backward per forward: without a matcha_forward_long_train on record for this
+ *   workspace pointer (host-side record, consumed by the backward; dropped by a matcha_forward_long on the pointer) it returns
+ *   MATCHA_EINVAL before any launch.
+ * Caller-owned memory, asynchronous on `stream`, no allocation, no host read-back.  matcha_workspace_bytes_long_train is host only and
+ * returns 0 (+ matcha_last_error) for a bad argument; per token 41 d floats with merged heads, 73 d without (+ d, adj), + 8 B of
+ * LayerNorm statistics and the plan's 20 B (8 B per row). */
+size_t matcha_workspace_bytes_long_train(const matcha_shape* shp, int64_t B, int32_t L);
+int matcha_forward_long_train(const matcha_shape* shp, const matcha_tensors* params, const matcha_frozen* frozen,
+                              const matcha_step_opts* opts, const int64_t* x, int64_t B, int32_t L,
+                              float* logits, float* losses, void* ws, size_t ws_bytes, matcha_stream_t stream);
+int matcha_backward_long(const matcha_shape* shp, const matcha_tensors* params, const matcha_frozen* frozen,
+                         const matcha_step_opts* opts, const int64_t* x, int64_t B, int32_t L,
+                         const float* dlogits, const float* drecon, matcha_tensors* grads, int32_t* touched,
+                         void* ws, size_t ws_bytes, matcha_stream_t stream);
+
+/* The long rows' attention backward alone (tests): Q, dO, dQ float [T + 1, 8 d]; row_off int32 [B + 1] (row_off[B] = T: the shared padding
+ * token's row).  shared_kv = 0: K, V, dK, dV float [T + 1, 8 d] per head;  shared_kv = 1 (the merged heads): K, V float [T + 1, d] that
+ * every head attends, dK / dV float [T + 1, d] = the sums over the heads.  Every row of the outputs is written (dQ[T] = 0); the same call
+ * gives the same bits.  No output may alias an input or another output.  2 <= L <= 32, d a multiple of 8 up to 256.
+ * ws: matcha_attn_long_bwd_workspace_bytes(B, d) bytes (bounded: a fixed number of workgroups walks the hyperedges). */
+size_t matcha_attn_long_bwd_workspace_bytes(int64_t B, int32_t d);
+int matcha_attn_long_bwd(const float* Q, const float* K, const float* V, const float* dO, const int32_t* row_off, int64_t B, int32_t L,
+                         int32_t d, int32_t shared_kv, float* dQ, float* dK, float* dV, void* ws, size_t ws_bytes, matcha_stream_t stream);
 
 /* loss.backward() of main.py:179 for loss = bce*alpha + recon*beta, or, when `dlogits` is not NULL,
  * the vector-Jacobian product for an arbitrary upstream gradient on the logits (autograd glue).

@@ -536,10 +536,12 @@ class _Runtime:
             return False            # (nothing rewrites these with the same bytes -- they are not in the state dict --, so any change rebuilds)
         return all(p.data_ptr() == e for p, e in zip(self.live, self.expected_ptrs))
 
-    def workspace(self, B: int, L: int, forward_only: bool = False, long_rows: bool = False) -> torch.Tensor:
+    def workspace(self, B: int, L: int, forward_only: bool = False, long_rows: bool = False, long_train: bool = False) -> torch.Tensor:
         query = self.lib.matcha_workspace_bytes_forward if forward_only else self.lib.matcha_workspace_bytes
-        if long_rows:      # rows of 9 .. MAX_LONG_L columns: the inference-only long forward has a layout of its own
+        if long_rows:      # rows of 9 .. MAX_LONG_L columns: the long forward has a layout of its own ...
             query = self.lib.matcha_workspace_bytes_long
+        if long_train:     # ... and so has the pair matcha_forward_long_train / matcha_backward_long, which keeps the activations
+            query = self.lib.matcha_workspace_bytes_long_train
         n = query(C.byref(self.shape), B, L)
         if n == 0:
             raise _lib.MatchaHipError(self.lib.matcha_last_error().decode())
@@ -552,6 +554,22 @@ class _Runtime:
 
     def stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+
+def _grad_outputs(rt: "_Runtime", gflat: torch.Tensor, touched: torch.Tensor):
+    """The per-parameter gradient views of a backward's flat buffer.  adj front end: the reference leaves .grad None for the encoders /
+    recon heads of chromosomes that did not occur in the batch, and torch.optim.AdamW skips such tensors (no weight decay, no moment
+    decay): reproducing that through autograd needs the flags on the host, i.e. one synchronisation per backward of THIS path
+    (loss.backward() with torch optimisers).  The training path proper (engine.Trainer) keeps the flags on the device and never
+    synchronises."""
+    tl = touched.tolist() if rt.mode == 1 else None
+    outs = []
+    for p, o, g in zip(rt.live, rt.seg_off_list[:-1], rt.seg_group_list):
+        if tl is not None and g >= 2 and tl[g] == 0:
+            outs.append(None)
+        else:
+            outs.append(gflat[o:o + p.numel()].view(p.shape))
+    return outs
 
 
 class _ClassifierFn(torch.autograd.Function):
@@ -586,18 +604,42 @@ class _ClassifierFn(torch.autograd.Function):
                                           None, None, _lib.ptr(dl), _lib.ptr(dr), C.byref(grads), _lib.ptr(touched), _lib.ptr(ctx.ws),
                                           ctx.ws.numel(), rt.stream()), "matcha_backward")
         ctx.ws = None
-        outs = []
-        # adj front end: the reference leaves .grad None for the encoders / recon heads of chromosomes that did not occur in the batch,
-        # and torch.optim.AdamW skips such tensors (no weight decay, no moment decay): reproducing that through autograd needs the
-        # flags on the host, i.e. one synchronisation per backward of THIS path (loss.backward() with torch optimisers).  The
-        # training path proper (engine.Trainer) keeps the flags on the device and never synchronises.
-        tl = touched.tolist() if rt.mode == 1 else None
-        for p, o, g in zip(rt.live, rt.seg_off_list[:-1], rt.seg_group_list):
-            if tl is not None and g >= 2 and tl[g] == 0:
-                outs.append(None)
-            else:
-                outs.append(gflat[o:o + p.numel()].view(p.shape))
-        return (None, None, None, None, *outs)
+        return (None, None, None, None, *_grad_outputs(rt, gflat, touched))
+
+
+class _ClassifierLongFn(torch.autograd.Function):
+    """Autograd glue around matcha_forward_long_train / matcha_backward_long: rows of 9 .. MAX_LONG_L columns, the surface of _ClassifierFn."""
+
+    @staticmethod
+    def forward(ctx, x, rt: _Runtime, opts: "_lib.StepOpts", seed_t, *live):
+        B, L = x.shape
+        ws = rt.workspace(B, L, long_train=True)
+        logits = torch.empty(B, dtype=torch.float32, device=rt.device)
+        losses = torch.zeros(3, dtype=torch.float32, device=rt.device)
+        opts.status = rt.status.data_ptr()
+        _lib.check(rt.lib.matcha_forward_long_train(C.byref(rt.shape), C.byref(rt.params), C.byref(rt.frozen), C.byref(opts), _lib.ptr(x), B, L,
+                                                    _lib.ptr(logits), _lib.ptr(losses), _lib.ptr(ws), ws.numel(), rt.stream()),
+                   "matcha_forward_long_train")
+        ctx.rt, ctx.opts, ctx.ws, ctx.x, ctx.seed_t = rt, opts, ws, x, seed_t
+        return logits.view(B, 1), losses[1:2]
+
+    @staticmethod
+    def backward(ctx, dlogits, drecon):
+        rt, opts, x = ctx.rt, ctx.opts, ctx.x
+        B, L = x.shape
+        if ctx.ws is None:
+            raise RuntimeError("matcha_amd: second backward through the same forward (retain_graph=True is not supported: "
+                               "the backward pass consumes the forward's workspace, as torch frees its saved tensors)")
+        gflat = torch.zeros(rt.n_flat, dtype=torch.float32, device=rt.device)
+        grads = rt.tensors_for(gflat)
+        touched = torch.zeros(rt.n_touched, dtype=torch.int32, device=rt.device)
+        dl = dlogits.reshape(-1).to(torch.float32).contiguous()
+        dr = drecon.reshape(-1).to(torch.float32).contiguous() if drecon is not None else None
+        _lib.check(rt.lib.matcha_backward_long(C.byref(rt.shape), C.byref(rt.params), C.byref(rt.frozen), C.byref(opts), _lib.ptr(x), B, L,
+                                               _lib.ptr(dl), _lib.ptr(dr), C.byref(grads), _lib.ptr(touched), _lib.ptr(ctx.ws),
+                                               ctx.ws.numel(), rt.stream()), "matcha_backward_long")
+        ctx.ws = None
+        return (None, None, None, None, *_grad_outputs(rt, gflat, touched))
 
 
 class Classifier(nn.Module):
@@ -640,6 +682,12 @@ class Classifier(nn.Module):
     # reference's IndexError.  Bulk callers that issue many forwards back to back (predict.py's sweeps) switch it off and call
     # check_status() once at the end.  Class attribute, so that models pickled by the reference get it too.
     check_ids = True
+
+    # Rows of 9 .. 32 columns train through autograd when this is set (model.long_row_training = True): model(x) in train mode, or with grad
+    # enabled and trainable parameters, then runs matcha_forward_long_train / matcha_backward_long -- loss.backward() and torch optimisers, as
+    # with the reference.  Off by default: such a call raises NotImplementedError as before.  engine.Trainer, the sampler and the sweeps
+    # stay at 8 columns either way.  Class attribute, like check_ids, so that models pickled by the reference get it too.
+    long_row_training = False
 
     def check_status(self):
         self._runtime().check_status("Classifier")
@@ -707,13 +755,21 @@ class Classifier(nn.Module):
         return (logits, recon) if return_recon else logits
 
     def _forward_long(self, x, rt: _Runtime, return_recon: bool):
-        """Rows of MAX_L + 1 .. MAX_LONG_L columns (9 .. 32): the inference-only long forward (matcha_forward_long).  Same surface as
-        the short path -- logits [B, 1], return_recon, check_ids / deferred_id_check, one np.random.choice per call in adj mode --
-        but eval mode without an autograd graph only: training, dropout and the backward stay at MAX_L columns."""
+        """Rows of MAX_L + 1 .. MAX_LONG_L columns (9 .. 32).  Eval mode without an autograd graph: the long forward (matcha_forward_long)
+        and its small workspace.  Same surface as the short path -- logits [B, 1], return_recon, check_ids / deferred_id_check, one
+        np.random.choice per call in adj mode.  Train mode, or a graph: NotImplementedError unless ``long_row_training`` is set; then
+        the training pair behind _ClassifierLongFn (dropout, loss.backward(), a RuntimeError on a second backward)."""
         if self.training or (torch.is_grad_enabled() and any(p.requires_grad for p in rt.live)):
-            raise NotImplementedError(
-                f"hyperedges of more than {_lib.MAX_L} nodes are inference-only (x has {x.shape[1]} columns): call model.eval() and "
-                "run the forward under torch.no_grad()")
+            if not self.long_row_training:
+                raise NotImplementedError(
+                    f"hyperedges of more than {_lib.MAX_L} nodes are inference-only (x has {x.shape[1]} columns): call model.eval() and "
+                    "run the forward under torch.no_grad(), or set model.long_row_training = True to train on them through autograd")
+            opts, seed_t = self._opts(rt, return_recon)       # one np.random.choice in adj mode, the dropout seed from rt.seed_counter
+            opts.forward_only = 0                             # (train mode under no_grad: the training layout all the same -- dropout lives there)
+            logits, recon = _ClassifierLongFn.apply(x, rt, opts, seed_t, *rt.live)
+            if self.check_ids and not torch.cuda.is_current_stream_capturing():
+                rt.check_status("Classifier.forward")
+            return (logits, recon) if return_recon else logits
         opts, _ = self._opts(rt, return_recon)       # eval + no graph: training = 0, forward_only = 1, no seed
         B, L = x.shape
         ws = rt.workspace(B, L, long_rows=True)

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MATCHA_HIP_LIB") or os.path.join(_HERE, "lib", "libmatcha_hip.so")   # override: A/B builds
 
 MAX_L = 8
-MAX_LONG_L = 32      # widest row of the inference-only long forward (matcha_forward_long)
+MAX_LONG_L = 32      # widest row of the long forward (matcha_forward_long) and of the long training pair (matcha_forward_long_train / matcha_backward_long)
 N_HEAD = 8
 
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
@@ -81,6 +81,13 @@ SIGNATURES = {
     "matcha_workspace_bytes_long": (_SZ, [C.POINTER(Shape), _I64, _I32]),
     "matcha_forward_long": (C.c_int, [C.POINTER(Shape), C.POINTER(Tensors), C.POINTER(Frozen), C.POINTER(StepOpts), _fp, _I64,
                                       _I32, _fp, _fp, _fp, _SZ, _fp]),
+    "matcha_workspace_bytes_long_train": (_SZ, [C.POINTER(Shape), _I64, _I32]),
+    "matcha_forward_long_train": (C.c_int, [C.POINTER(Shape), C.POINTER(Tensors), C.POINTER(Frozen), C.POINTER(StepOpts), _fp, _I64,
+                                            _I32, _fp, _fp, _fp, _SZ, _fp]),
+    "matcha_backward_long": (C.c_int, [C.POINTER(Shape), C.POINTER(Tensors), C.POINTER(Frozen), C.POINTER(StepOpts), _fp, _I64,
+                                       _I32, _fp, _fp, C.POINTER(Tensors), _fp, _fp, _SZ, _fp]),
+    "matcha_attn_long_bwd_workspace_bytes": (_SZ, [_I64, _I32]),
+    "matcha_attn_long_bwd": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _I64, _I32, _I32, _I32, _fp, _fp, _fp, _fp, _SZ, _fp]),
     "matcha_backward": (C.c_int, [C.POINTER(Shape), C.POINTER(Tensors), C.POINTER(Frozen), C.POINTER(StepOpts), _fp, _I64,
                                   _I32, _fp, _fp, _fp, _fp, C.POINTER(Tensors), _fp, _fp, _SZ, _fp]),
     "matcha_forward_objective": (C.c_int, [_I32, C.POINTER(Shape), C.POINTER(Tensors), C.POINTER(Frozen), C.POINTER(StepOpts), _fp, _I64,

@@ -19,11 +19,9 @@
 // shared padding token's K / V row (token index Tr) and enter as ONE extra key column j = k with multiplicity n_pad -- denominator
 // += n_pad exp(s_pad), output += n_pad P_pad V_pad; padding queries are not evaluated; k = 1 attends the padding slots only; k = L has
 // no padding column (k = 32 fills the tile, and then n_pad = 0).
-#include "kernels.hpp"
+#include "attention_long.hpp"
 
 namespace matcha {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // Q / O rows are [T, 8 d]; O may be the same buffer as Q (a wavefront reads its (hyperedge, head) slice of Q completely before it writes
 // the same slice of O, and no other wavefront touches that slice), hence no __restrict__ on them
@@ -43,53 +41,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   // tile row r as a key / as a query: real token r, else the padding token (column k when n_pad > 0; behind it rows nobody weighs)
   const int64_t trow = r < k ? (int64_t)t0 + r : tp;
 
-  // ---- S^T = K Q^T: per 8 features the two lane halves take the two adjacent float4 of their row (a row's pair shares a 32-byte sector), one
-  // feature per k-step: the order of the contraction is free as long as both operands follow it
-  f32x16 acc = {0};
+  // ---- S^T = K Q^T and the softmax of query i = r over its keys (attention_long.hpp: shared with the backward kernel, which recomputes the same bits)
+  float p[16];
   {
     const float4* kp = reinterpret_cast<const float4*>(K + trow * kv_ld + (int64_t)head * kv_head) + h;
     const float4* qp = reinterpret_cast<const float4*>(Q + trow * hd + (int64_t)head * d) + h;
-    const int n4 = d / 8;
-    auto step4 = [&](const float4& a, const float4& q) {
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, q.x, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, q.y, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, q.z, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, q.w, acc, 0, 0, 0);
-    };
-    int c = 0;
-    for (; c + 4 <= n4; c += 4) {                 // four float4 pairs in flight in front of their sixteen steps
-      const float4 a0 = kp[2 * c], q0 = qp[2 * c], a1 = kp[2 * c + 2], q1 = qp[2 * c + 2];
-      const float4 a2 = kp[2 * c + 4], q2 = qp[2 * c + 4], a3 = kp[2 * c + 6], q3 = qp[2 * c + 6];
-      step4(a0, q0); step4(a1, q1); step4(a2, q2); step4(a3, q3);
-    }
-    for (; c < n4; ++c) step4(kp[2 * c], qp[2 * c]);
+    const f32x16 acc = long_tile_nt(kp, qp, d / 8);
+    long_softmax(acc, k, n_pad, r, h, inv_temp, p);
   }
-
-  // ---- softmax of query i = r over its keys: weight 1 for a real key j != i, n_pad for the padding column j = k, 0 behind it
-  const float padf = (float)n_pad;
-  float p[16];
-  float mx = -3.4e38f;
-#pragma unroll
-  for (int v = 0; v < 16; ++v) {
-    const int j = 8 * (v >> 2) + 4 * h + (v & 3);
-    const bool on = (j < k && j != r) || (j == k && n_pad > 0);
-    p[v] = acc[v] * inv_temp;
-    if (on) mx = fmaxf(mx, p[v]);
-  }
-  mx = fmaxf(mx, __shfl_xor(mx, 32, kWave));
-  float den = 0.f;
-#pragma unroll
-  for (int v = 0; v < 16; ++v) {
-    const int j = 8 * (v >> 2) + 4 * h + (v & 3);
-    const bool on = (j < k && j != r) || (j == k && n_pad > 0);
-    const float e = on ? __expf(p[v] - mx) : 0.f;      // (one v_exp, like the fused forward's softmax: the fp32 grade holds, tests/test_hip_long_rows.py)
-    p[v] = j == k ? padf * e : e;
-    den += p[v];
-  }
-  den += __shfl_xor(den, 32, kWave);
-  const float inv = 1.f / den;                    // (a query r >= k is never stored; every stored query has a key: L >= 2)
-#pragma unroll
-  for (int v = 0; v < 16; ++v) p[v] *= inv;
 
   // ---- O = P V, 32 features at a time: A operand = the probabilities as they stand (lane = query), B operand = 32 consecutive features of the
   // step's two value rows (one 128-byte line per lane half); in the result lane r holds feature f0 + r of the sixteen queries

@@ -284,5 +284,10 @@ int launch_long_plan(const int64_t* x, int64_t B, int L, int64_t n_nodes, int32_
 // stride and per-head offset of K and V (8 d and d for per-head rows; d and 0 for the merged heads' shared key / value rows)
 int launch_attn_long(const float* Q, const float* K, const float* V, const int32_t* row_off, int64_t B, int L, int d, int64_t kv_ld, int kv_head,
                      float* O, hipStream_t st);
+// attention_long_bwd.hip: its backward on the same two operand forms; P is recomputed from Q and K.  dK / dV have K / V's layout (merged heads:
+// the sums over the heads [T, d], written by the kernel); the padding token's rows are summed through `slab` (attn_long_bwd_slab_bytes), dQ[Tr] = 0
+size_t attn_long_bwd_slab_bytes(int64_t B, int d);
+int launch_attn_long_bwd(const float* Q, const float* K, const float* V, const float* dO, const int32_t* row_off, int64_t B, int L, int d,
+                         int64_t kv_ld, int kv_head, float* dQ, float* dK, float* dV, float* slab, hipStream_t st);
 
 }  // namespace matcha
