@@ -429,6 +429,21 @@ int matcha_neg_sample(const void* set, const int64_t* set_edges, int64_t n_set_e
                       const int64_t* pos, int64_t P, int32_t L, int32_t neg_num, int32_t min_dis,
                       const int32_t* node2chrom, int32_t n_nodes, const int32_t* chrom_range, int32_t n_chrom,
                       const uint64_t* seed, int64_t* neg, int32_t* status, matcha_stream_t stream);
+/* The same three for rows of up to MATCHA_MAX_LONG_L (32) columns: 1 <= L <= 32 and 1 <= L_set <= 32, every other check as above.
+ * ONE table format: a row's hash runs over its non-zero prefix and does not depend on the container's width, so a table built by
+ * either build entry is read by either contains / sample entry whose width bound is met (a stored row of k <= 8 nodes in a width-25
+ * set is found by a width-5 query).  matcha_hashset_bytes serves both.  matcha_neg_sample_long runs neg_sample_long_kernel: 32
+ * adjacent lanes per negative, lane i = position i.  Random stream: the key, the hi counter (the negative's index) and the mask
+ * counters of matcha_neg_sample; the replacement counter is S*trial + position with S = 8 when L <= 8 -- bit for bit
+ * matcha_neg_sample's negatives -- and S = 32 when L > 8.  P * neg_num < 2^31. */
+int matcha_hashset_build_long(void* set, size_t set_bytes, const int64_t* edges, int64_t n_edges, int32_t L,
+                              matcha_stream_t stream);
+int matcha_hashset_contains_long(const void* set, const int64_t* edges, int32_t L_set, const int64_t* rows,
+                                 int64_t n, int32_t L, int32_t* out, matcha_stream_t stream);
+int matcha_neg_sample_long(const void* set, const int64_t* set_edges, int64_t n_set_edges, int32_t L_set,
+                           const int64_t* pos, int64_t P, int32_t L, int32_t neg_num, int32_t min_dis,
+                           const int32_t* node2chrom, int32_t n_nodes, const int32_t* chrom_range, int32_t n_chrom,
+                           const uint64_t* seed, int64_t* neg, int32_t* status, matcha_stream_t stream);
 
 /* The bookkeeping of one step of the reference's epoch loop (main.py:155-188) on the device, so that an epoch can replay one captured
  * step (matcha_amd/train.py).  `it` is a device int64 step counter.

@@ -12,7 +12,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MATCHA_HIP_LIB") or os.path.join(_HERE, "lib", "libmatcha_hip.so")   # override: A/B builds
 
 MAX_L = 8
-MAX_LONG_L = 32      # widest row of the long forward (matcha_forward_long) and of the long training pair (matcha_forward_long_train / matcha_backward_long)
+MAX_LONG_L = 32      # widest row of the long forward (matcha_forward_long), of the long training pair (matcha_forward_long_train / matcha_backward_long)
+                     # and of the long set / sampler (matcha_hashset_build_long, matcha_hashset_contains_long, matcha_neg_sample_long)
 N_HEAD = 8
 
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
@@ -114,6 +115,9 @@ SIGNATURES = {
     "matcha_step_record": (C.c_int, [_fp, _fp, _fp, _I64, _I32, _fp, _I64, _fp, _fp, _fp, _fp]),
     "matcha_step_record_pairs": (C.c_int, [_fp, _fp, _fp, _fp, _I64, _I32, _fp, _I64, _fp, _fp, _fp, _fp, _fp, _fp]),
     "matcha_neg_sample": (C.c_int, [_fp, _fp, _I64, _I32, _fp, _I64, _I32, _I32, _I32, _fp, _I32, _fp, _I32, _fp, _fp, _fp, _fp]),
+    "matcha_hashset_build_long": (C.c_int, [_fp, _SZ, _fp, _I64, _I32, _fp]),
+    "matcha_hashset_contains_long": (C.c_int, [_fp, _fp, _I32, _fp, _I64, _I32, _fp, _fp]),
+    "matcha_neg_sample_long": (C.c_int, [_fp, _fp, _I64, _I32, _fp, _I64, _I32, _I32, _I32, _fp, _I32, _fp, _I32, _fp, _fp, _fp, _fp]),
     "matcha_gemm_tn_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
     "matcha_gemm": (C.c_int, [_I32, _fp, _fp, _fp, _I64, _I64, _I64, C.POINTER(GemmEpilogue), _fp, _fp, _fp, _SZ, _fp]),
     "matcha_embed_fwd": (C.c_int, [_fp, _I64, _I32, _fp, _fp, _fp, _I32, _fp, _fp, _fp, _fp]),

@@ -10,6 +10,7 @@
 //                       (each position chosen with prob 1/2, conditioned on >= 1 chosen  ==  the reference's
 //                        Binomial(k, 1/2) != 0 count (main.py:371-372) + uniform choice of positions (:389))
 //         replacement : rand(key, n, 8*trial + position)     -> start + floor(u * (end - start))    (:405-407)
+//                       (rows of more than 8 columns, neg_sample_long_kernel: 32*trial + position)
 #include "kernels.hpp"
 
 namespace matcha {
@@ -248,6 +249,135 @@ __global__ __launch_bounds__(256) void neg_sample_kernel(const int32_t* __restri
     if (i < L) out[i] = done ? cand[i] : orig[i];
 }
 
+// ---- rows of up to MATCHA_MAX_LONG_L = 32 columns: one LANE per position ---------------------------------------------------------------------
+// neg_sample_kernel keeps a row in 8 int64 registers per lane and sorts it with an 8-slot network; at 32 slots that is ~200 live VGPRs.  Here a
+// GROUP of 32 adjacent lanes owns one negative and lane i holds position i: two negatives per wavefront, eight per 256-thread block.  The row
+// is one register pair per lane; sorting, the gap test, the hash chain and the comparison with a stored row are cross-lane exchanges and
+// ballots.  No LDS, no scratch.  The table format (hash, tag, slots, linear probing) is the one above: either build serves either sampler.
+//
+// Every cross-lane operation below is executed by ALL 64 lanes of the wavefront: the two groups of a wavefront run the same wave-uniform
+// loops (their conditions are __any over the wavefront) and a group that has nothing left to do is predicated off (`want`, `active`), never
+// branched around a shuffle or a ballot.  Only loads, stores and atomics sit inside divergent ifs.
+constexpr int kGroup = 32;             // lanes per negative
+static_assert(MATCHA_MAX_LONG_L == kGroup && kWave == 2 * kGroup, "one lane per position, two negatives per wavefront");
+
+__device__ __forceinline__ uint32_t group_ballot(bool p, int half) { return (uint32_t)(__ballot(p) >> (kGroup * half)); }
+__device__ __forceinline__ int first_bit(uint32_t m) { return m ? __ffs((int)m) - 1 : kGroup; }      // kGroup when no bit is set
+
+// Membership of the group's row (`val` = this lane's id, 0 at and behind the row's end and at lanes >= L) -- row_hash / set_contains above,
+// one lane per position.  `want` is group-uniform; a group with want == false loads nothing and gets false.
+__device__ __forceinline__ bool group_contains(const int32_t* __restrict__ set, const int64_t* __restrict__ edges, int L_set, int64_t val, int L,
+                                               int lane, int half, bool want) {
+  const int64_t cap = reinterpret_cast<const int64_t*>(set)[0];
+  const unsigned long long* slots = reinterpret_cast<const unsigned long long*>(set + kSetHeader);
+  // the hash chain is sequential in the position: every lane runs it on values broadcast from their owners
+  uint64_t h = 0x9E3779B97F4A7C15ull;
+  bool live = want;
+  for (int i = 0; i < L; ++i) {
+    if (!__any(live)) break;
+    const uint64_t v = (uint64_t)__shfl((long long)val, i, kGroup);
+    live = live && v != 0;
+    uint64_t t = h ^ (v + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2));
+    t *= 0xBF58476D1CE4E5B9ull;
+    t ^= t >> 31;
+    h = live ? t : h;
+  }
+  const uint32_t tag = row_tag(h);
+  uint64_t p = h & (uint64_t)(cap - 1);
+  bool found = false, searching = want;
+  for (int64_t probe = 0; probe < cap; probe += kGroup) {
+    if (!__any(searching)) break;
+    // a window of 32 consecutive slots, one per lane: one round trip (cap >= 1024)
+    unsigned long long w = ~0ull;
+    if (searching) w = slots[(p + (uint64_t)lane) & (uint64_t)(cap - 1)];
+    const int32_t idx = (int32_t)(uint32_t)(w & 0xFFFFFFFFull);
+    const uint32_t empty = group_ballot(idx < 0, half);
+    const int fe = first_bit(empty);
+    const uint32_t before = fe >= kGroup ? 0xFFFFFFFFu : ((1u << fe) - 1u);        // the slots in front of the first empty one
+    uint32_t m = group_ballot(searching && idx >= 0 && (uint32_t)(w >> 32) == tag, half) & before;
+    while (__any(m != 0)) {
+      // a tag match: the stored row, one coalesced read, compared position by position (rows_equal: equal up to the first common zero)
+      const int32_t ci = __shfl(idx, m ? first_bit(m) : 0, kGroup);
+      int64_t sv = 0;
+      if (m != 0 && lane < L_set) sv = edges[(int64_t)ci * L_set + lane];
+      const int fm = first_bit(group_ballot(sv != val, half)), fz = first_bit(group_ballot(sv == 0 && val == 0, half));
+      if (m != 0 && fm >= fz) { found = true; m = 0; }
+      m &= m - 1u;
+    }
+    if (found || empty != 0) searching = false;
+    p = (p + (uint64_t)kGroup) & (uint64_t)(cap - 1);
+  }
+  return found;
+}
+
+__global__ __launch_bounds__(256) void neg_sample_long_kernel(const int32_t* __restrict__ set, const int64_t* __restrict__ set_edges,
+                                                              int64_t n_set, int L_set, const int64_t* __restrict__ pos, int64_t P,
+                                                              int L, int neg_num, int min_dis, const int32_t* __restrict__ node2chrom, int n_nodes,
+                                                              const int32_t* __restrict__ chrom_range, int n_chrom,
+                                                              const uint64_t* __restrict__ seed, int64_t* __restrict__ neg, int32_t* __restrict__ status) {
+  const int lane = (int)threadIdx.x & (kGroup - 1), half = ((int)threadIdx.x / kGroup) & 1;
+  const int64_t n = (int64_t)blockIdx.x * (256 / kGroup) + (int64_t)(threadIdx.x / kGroup);
+  const bool valid = n < P * neg_num;             // group-uniform; a group behind the end takes part in the exchanges and stores nothing
+  const int64_t j = valid ? n / neg_num : 0;
+  const int64_t orig = (valid && lane < L) ? pos[j * L + lane] : 0;        // one coalesced row read
+  const uint32_t nz = group_ballot(orig != 0, half);
+  const int k = nz ? 32 - __clz((int)nz) : 0;                              // index of the last non-zero + 1
+  // node -> chromosome -> [start, end) of this lane's own node, once, before the membership test of the positive (clamped indices)
+  const bool in = lane < k && orig >= 1 && orig <= n_nodes;
+  const int c = node2chrom[in ? orig : 0];
+  const int cidx = (in && c >= 0 && c < n_chrom) ? c : -1;
+  const int2 crange = reinterpret_cast<const int2*>(chrom_range)[cidx >= 0 ? cidx : 0];
+  const uint64_t seed_v = *seed;
+  // `while neighbor_check(temp, dict)` with temp == the positive on entry (main.py:390-392): not a member (empty set: phase 1) -> copied
+  bool resample = false;
+  if (n_set > 0) resample = group_contains(set, set_edges, L_set, orig, L, lane, half, valid && k > 0);       // n_set is kernel-uniform
+  int64_t result = orig;
+  if (__any(resample)) {
+    const uint32_t key = rng_key(seed_v, kStreamNeg);
+    const uint32_t kmask = k >= 32 ? 0xFFFFFFFFu : ((1u << k) - 1u);       // k = 32 uses all 32 bits: no shift by 32
+    uint32_t mask = 0;
+    if (resample)
+      for (uint32_t a = 0; mask == 0; ++a) mask = rng_u32(key, (uint32_t)n, 0xFFFF0000u + a) & kmask;
+    // a node outside [1, n_nodes] or without a chromosome cannot be redrawn: it is kept and the call is flagged (neg_sample_kernel)
+    const bool chosen = resample && lane < k && ((mask >> lane) & 1u);
+    const bool redraw = chosen && cidx >= 0;
+    if (chosen && cidx < 0 && status) atomicOr(status, MATCHA_STATUS_BAD_CHROM);
+    const int64_t cstart = crange.x, clen = (int64_t)crange.y - (int64_t)crange.x;
+    const uint32_t stride = L <= MATCHA_MAX_L ? 8u : 32u;                  // L <= 8: the counters of neg_sample_kernel, bit for bit
+    constexpr int64_t kBig = 0x7FFFFFFFFFFFFFFFll;                         // unused lanes sort behind every node id
+    bool active = resample;
+    for (int trial = 0; trial < kMaxTrials; ++trial) {
+      if (!__any(active)) break;
+      int64_t cand = lane < k ? orig : kBig;
+      if (redraw) {
+        const uint32_t r = rng_u32(key, (uint32_t)n, stride * (uint32_t)trial + (uint32_t)lane);
+        cand = cstart + (int64_t)(((uint64_t)r * (uint64_t)clen) >> 32);
+      }
+      // bitonic sort over the group's 32 lanes, ascending: 15 compare-exchanges with the lane at distance st
+#pragma unroll
+      for (int sz = 2; sz <= kGroup; sz <<= 1) {
+#pragma unroll
+        for (int st = sz >> 1; st > 0; st >>= 1) {
+          const int64_t other = (int64_t)__shfl_xor((long long)cand, st, kGroup);
+          const bool take_min = ((lane & sz) == 0) == ((lane & st) == 0);
+          const int64_t lo = cand < other ? cand : other, hi = cand < other ? other : cand;
+          cand = take_min ? lo : hi;
+        }
+      }
+      // duplicates / close neighbours (main.py:410-421): every lane against its left neighbour
+      const int64_t gap = cand - (int64_t)__shfl_up((long long)cand, 1, kGroup);
+      const bool bad = lane >= 1 && lane < k && (gap == 0 || gap <= min_dis);
+      const bool ok = active && group_ballot(bad, half) == 0;
+      cand = lane < k ? cand : 0;
+      const bool known = group_contains(set, set_edges, L_set, cand, L, lane, half, ok);
+      if (ok && !known) { result = cand; active = false; }
+    }
+    // trials exhausted: the row is returned equal to its positive and counted once (the reference would loop forever, main.py:392)
+    if (active && lane == 0 && status) atomicAdd(status + 1, 1);
+  }
+  if (valid && lane < L) neg[n * L + lane] = result;                       // one coalesced store
+}
+
 }  // namespace matcha
 
 using namespace matcha;
@@ -262,12 +392,14 @@ extern "C" size_t matcha_hashset_bytes(int64_t n_edges) {
   return (size_t)kSetHeader * sizeof(int32_t) + (size_t)set_capacity(n_edges < 0 ? 0 : n_edges) * sizeof(SetSlot);
 }
 
-extern "C" int matcha_hashset_build(void* set, size_t set_bytes, const int64_t* edges, int64_t n_edges, int32_t L,
-                                    matcha_stream_t stream) {
-  MATCHA_CHECK_ARG(set && (edges || n_edges == 0), "matcha_hashset_build: null pointer");
-  MATCHA_CHECK_ARG(L >= 1 && L <= MATCHA_MAX_L, "matcha_hashset_build: L=%d", L);
-  MATCHA_CHECK_ARG(n_edges >= 0 && n_edges < (1ll << 31), "matcha_hashset_build: n_edges=%lld", (long long)n_edges);
-  MATCHA_CHECK_ARG(set_bytes >= matcha_hashset_bytes(n_edges), "matcha_hashset_build: set buffer too small");
+// The three entry points below exist twice: the short ones (rows of up to MATCHA_MAX_L = 8 columns, neg_sample_kernel) and the `_long` ones (up
+// to MATCHA_MAX_LONG_L = 32, neg_sample_long_kernel).  The set kernels loop to a run-time width and serve both; the checks are shared.
+static int hashset_build_impl(const char* fn, int max_l, void* set, size_t set_bytes, const int64_t* edges, int64_t n_edges, int32_t L,
+                              matcha_stream_t stream) {
+  MATCHA_CHECK_ARG(set && (edges || n_edges == 0), "%s: null pointer", fn);
+  MATCHA_CHECK_ARG(L >= 1 && L <= max_l, "%s: L=%d", fn, L);
+  MATCHA_CHECK_ARG(n_edges >= 0 && n_edges < (1ll << 31), "%s: n_edges=%lld", fn, (long long)n_edges);
+  MATCHA_CHECK_ARG(set_bytes >= matcha_hashset_bytes(n_edges), "%s: set buffer too small", fn);
   hipStream_t st = (hipStream_t)stream;
   const int64_t cap = set_capacity(n_edges);
   hipLaunchKernelGGL(hashset_clear_kernel, dim3((unsigned)cdiv(cap, 256)), dim3(256), 0, st, (int32_t*)set, cap);
@@ -279,15 +411,33 @@ extern "C" int matcha_hashset_build(void* set, size_t set_bytes, const int64_t* 
   return MATCHA_OK;
 }
 
-extern "C" int matcha_hashset_contains(const void* set, const int64_t* edges, int32_t L_set, const int64_t* rows, int64_t n,
-                                       int32_t L, int32_t* out, matcha_stream_t stream) {
-  MATCHA_CHECK_ARG(set && rows && out, "matcha_hashset_contains: null pointer");
-  MATCHA_CHECK_ARG(L >= 1 && L <= MATCHA_MAX_L && L_set >= 1 && L_set <= MATCHA_MAX_L, "matcha_hashset_contains: bad width");
+static int hashset_contains_impl(const char* fn, int max_l, const void* set, const int64_t* edges, int32_t L_set, const int64_t* rows, int64_t n,
+                                 int32_t L, int32_t* out, matcha_stream_t stream) {
+  MATCHA_CHECK_ARG(set && rows && out, "%s: null pointer", fn);
+  MATCHA_CHECK_ARG(L >= 1 && L <= max_l && L_set >= 1 && L_set <= max_l, "%s: bad width", fn);
   if (n <= 0) return MATCHA_OK;
   hipLaunchKernelGGL(hashset_contains_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, (const int32_t*)set,
                      edges, L_set, rows, n, L, out);
   MATCHA_CHECK_LAUNCH("hashset_contains_kernel");
   return MATCHA_OK;
+}
+
+extern "C" int matcha_hashset_build(void* set, size_t set_bytes, const int64_t* edges, int64_t n_edges, int32_t L,
+                                    matcha_stream_t stream) {
+  return hashset_build_impl("matcha_hashset_build", MATCHA_MAX_L, set, set_bytes, edges, n_edges, L, stream);
+}
+extern "C" int matcha_hashset_build_long(void* set, size_t set_bytes, const int64_t* edges, int64_t n_edges, int32_t L,
+                                         matcha_stream_t stream) {
+  return hashset_build_impl("matcha_hashset_build_long", MATCHA_MAX_LONG_L, set, set_bytes, edges, n_edges, L, stream);
+}
+
+extern "C" int matcha_hashset_contains(const void* set, const int64_t* edges, int32_t L_set, const int64_t* rows, int64_t n,
+                                       int32_t L, int32_t* out, matcha_stream_t stream) {
+  return hashset_contains_impl("matcha_hashset_contains", MATCHA_MAX_L, set, edges, L_set, rows, n, L, out, stream);
+}
+extern "C" int matcha_hashset_contains_long(const void* set, const int64_t* edges, int32_t L_set, const int64_t* rows, int64_t n,
+                                            int32_t L, int32_t* out, matcha_stream_t stream) {
+  return hashset_contains_impl("matcha_hashset_contains_long", MATCHA_MAX_LONG_L, set, edges, L_set, rows, n, L, out, stream);
 }
 
 extern "C" int matcha_neg_sample(const void* set, const int64_t* set_edges, int64_t n_set_edges, int32_t L_set,
@@ -305,5 +455,27 @@ extern "C" int matcha_neg_sample(const void* set, const int64_t* set_edges, int6
                      (const int32_t*)set, set_edges, n_set_edges, L_set > 0 ? L_set : L, pos, P, L, neg_num, min_dis, node2chrom, n_nodes,
                      chrom_range, n_chrom, seed, neg, status);
   MATCHA_CHECK_LAUNCH("neg_sample_kernel");
+  return MATCHA_OK;
+}
+
+extern "C" int matcha_neg_sample_long(const void* set, const int64_t* set_edges, int64_t n_set_edges, int32_t L_set,
+                                      const int64_t* pos, int64_t P, int32_t L, int32_t neg_num, int32_t min_dis,
+                                      const int32_t* node2chrom, int32_t n_nodes, const int32_t* chrom_range, int32_t n_chrom,
+                                      const uint64_t* seed, int64_t* neg, int32_t* status, matcha_stream_t stream) {
+  MATCHA_CHECK_ARG(pos && neg && node2chrom && chrom_range && seed, "matcha_neg_sample_long: null pointer");
+  MATCHA_CHECK_ARG(((uintptr_t)chrom_range) % 8 == 0, "matcha_neg_sample_long: chrom_range must be 8-byte aligned (the kernel reads [lo, hi] pairs as one int2)");
+  MATCHA_CHECK_ARG(n_nodes >= 1 && n_chrom >= 1, "matcha_neg_sample_long: n_nodes=%d n_chrom=%d", n_nodes, n_chrom);
+  MATCHA_CHECK_ARG(n_set_edges == 0 || (set && set_edges), "matcha_neg_sample_long: non-empty set without buffers");
+  MATCHA_CHECK_ARG(L >= 1 && L <= MATCHA_MAX_LONG_L && neg_num >= 1, "matcha_neg_sample_long: L=%d neg_num=%d", L, neg_num);
+  MATCHA_CHECK_ARG(L_set >= 1 && L_set <= MATCHA_MAX_LONG_L, "matcha_neg_sample_long: L_set=%d", L_set);
+  MATCHA_CHECK_ARG(n_set_edges >= 0 && n_set_edges < (1ll << 31), "matcha_neg_sample_long: n_set_edges=%lld", (long long)n_set_edges);
+  if (P <= 0) return MATCHA_OK;
+  // the negative's index is the random stream's 32-bit hi counter, and a block owns eight negatives
+  MATCHA_CHECK_ARG(P <= ((1ll << 31) - 1) / neg_num, "matcha_neg_sample_long: P=%lld x neg_num=%d negatives", (long long)P, neg_num);
+  ProfScope ps(MATCHA_PROF_NEG_SAMPLE, (double)P * L * 8.0 * (1.0 + neg_num), (hipStream_t)stream);
+  hipLaunchKernelGGL(neg_sample_long_kernel, dim3((unsigned)cdiv(P * neg_num, 256 / kGroup)), dim3(256), 0, (hipStream_t)stream,
+                     (const int32_t*)set, set_edges, n_set_edges, L_set, pos, P, L, neg_num, min_dis, node2chrom, n_nodes,
+                     chrom_range, n_chrom, seed, neg, status);
+  MATCHA_CHECK_LAUNCH("neg_sample_long_kernel");
   return MATCHA_OK;
 }
