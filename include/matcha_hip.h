@@ -294,8 +294,9 @@ int matcha_forward_long(const matcha_shape* shp, const matcha_tensors* params, c
  *   logits float [B] out;  losses float [3] as matcha_forward_long, may be NULL.
  *   matcha_backward_long: dlogits float [B] (required: the loss lives with the caller), drecon float [1] or NULL, gradients ACCUMULATE
  *   into `grads`, `touched` as matcha_backward.  One backward per forward: without a matcha_forward_long_train on record for this
- *   workspace pointer (host-side record, consumed by the backward; dropped by a matcha_forward_long on the pointer) it returns
- *   MATCHA_EINVAL before any launch.
+ *   workspace pointer it returns MATCHA_EINVAL before any launch.  The record is the one matcha_backward describes below -- one per
+ *   workspace pointer for both pairs: it is consumed by the backward, dropped by a matcha_forward_long on the pointer and REPLACED by a
+ *   differentiable matcha_forward there, whose record is none of matcha_backward_long's (MATCHA_EINVAL, the record stays).
  * Caller-owned memory, asynchronous on `stream`, no allocation, no host read-back.  matcha_workspace_bytes_long_train is host only and
  * returns 0 (+ matcha_last_error) for a bad argument; per token 41 d floats with merged heads, 73 d without (+ d, adj), + 8 B of
  * LayerNorm statistics and the plan's 20 B (8 B per row). */
@@ -327,9 +328,11 @@ int matcha_attn_long_bwd(const float* Q, const float* K, const float* V, const f
  * as loss.backward() without retain_graph.  The library keeps a host-side record per workspace pointer of the last
  * differentiable forward: it is written by a forward without opts->forward_only, dropped by a forward WITH it (which
  * keeps nothing for a backward and overwrites what was there) and dropped by the backward that consumed it.
- * matcha_backward on a workspace without a record -- never used, last used by a forward_only forward, already
- * consumed by a backward, or evicted (the 4096 most recent workspaces are remembered) -- returns MATCHA_EINVAL
- * before any launch. */
+ * matcha_forward_long_train and matcha_forward_long write and drop the SAME record, so whichever forward ran last on
+ * a pointer decides which backward it takes.
+ * matcha_backward on a workspace without a record of a matcha_forward -- never used, last used by a forward_only
+ * forward or by one of the long rows' forwards, already consumed by a backward, or evicted (the 4096 most recent
+ * workspaces are remembered) -- returns MATCHA_EINVAL before any launch. */
 int matcha_backward(const matcha_shape* shp, const matcha_tensors* params, const matcha_frozen* frozen,
                     const matcha_step_opts* opts, const int64_t* x, int64_t B, int32_t L,
                     const float* y, const float* w, const float* dlogits, const float* drecon,

@@ -5,13 +5,16 @@
 // Token layout: ragged (ragged.hip).  The token-level layers run on Tn = Tr + 1 rows -- the Tr real tokens of the
 // batch plus ONE shared padding token -- instead of B*L slots; Tr is only known on the device, so every launch is
 // sized for the upper bound B*L + 1 and reads the true count from `count` (m_dev / r_dev / t_dev).
+//
+// This file holds the step's workspace layout (carve), its kernel route (decide_route) and the fused routes' launches.  Where a route runs
+// layer by layer -- every embed_dim but 64, embed_dim 64 under a switch, matcha_get_embedding, the pieces around enc128 and around the fused
+// encoder -- forward_impl / backward_impl call the chain's pieces of layerwise.hip, which the long rows' entry points (forward_long.hip) call too.
 #include <stdlib.h>
 #include <string.h>
 
-#include <mutex>
 #include <unordered_map>
 
-#include "kernels.hpp"
+#include "layerwise.hpp"
 #include "tail_reduce.hpp"
 #include "fb_unfold.hpp"
 #include "ragged_roles.hpp"
@@ -75,28 +78,11 @@ void note_launch(const char* name) {
   if (g_launch_names < kLaunchNames) g_launches[g_launch_names++] = LaunchCount{name, 1};
 }
 
-// adj_frontend.hip
-int adj_forward(const matcha_shape& s, const matcha_tensors& p, const matcha_frozen& f, const matcha_step_opts& o,
-                const int64_t* x, int64_t T, float* node_out, float* recon_out, void* ws, size_t ws_bytes, hipStream_t st,
-                const int32_t* t_dev, const int32_t* slot_map, float* fused_x0 = nullptr, float* fused_X = nullptr, bool save = false,
-                bool fused_node = false);
-int adj_backward(const matcha_shape& s, const matcha_tensors& p, const matcha_frozen& f, const matcha_step_opts& o,
-                 const int64_t* x, int64_t T, float* dnode, const float* drecon, matcha_tensors& g, int32_t* touched,
-                 void* ws, size_t ws_bytes, void* gemm_ws, size_t gemm_ws_bytes, hipStream_t st, const int32_t* slot_map, bool fused = false);
-size_t adj_workspace_bytes(const matcha_shape& s, int64_t T);
 bool adj_fused_eligible(const matcha_shape& s, const matcha_frozen& f);     // adj_fused.hip
 
-struct Workspace {
-  Ragged rg;
-  // saved by forward
-  float *x0, *X, *qin, *kin, *vin, *stats, *Q, *K, *V, *P, *O, *Y, *H1, *H2, *row_loss, *logits, *node;
-  // backward temporaries
-  float *dH2, *dXs, *dZ1, *ddyn0, *dO, *dQ, *dK, *dV, *dqin, *dkin, *dvin, *dZ0, *dX0;
-  float* slab;      size_t slab_bytes;    // column-sum slabs (LayerNorm / tail parameter gradients, attention pad-token grads)
-  float* gemm_ws;   size_t gemm_ws_bytes; // TN GEMM slabs
-  void* adj_ws;     size_t adj_ws_bytes;
+// The L <= 8 step's workspace: the chain's buffers (layerwise.hpp) + what only the fused routes use.
+struct Workspace : TokenChain {
   float* folded;                          // LayerNorm-folded projection weights of the fused d = 64 kernels
-  float* lwB; float* lwM; float* lwdB; float* lwdM;   // embed_dim >= 128, merged heads: B_all [8d, d], M_all [d, 8d] and their gradients
   float* enc;                             // embed_dim 128: the fused attention block's folded weights, fragments and slabs (enc128.hip)
   float* enc_rec; size_t enc_rec_floats;  // ... and its forward records, over the Q / K / V / P / O buffers the fused path does not use
   float* merged;                          // merged per-head matrices B_h = W'k^T W'q, M_h = Wfc1_h W'v (two products per head instead of four)
@@ -107,7 +93,6 @@ struct Workspace {
   float* tslab2;                          // large batches: one slab of weight-gradient partials per workgroup of tail_bwd64_kernel
   float* qkv;                             // training forward -> fused backward: Q, K, V tiles of every (tile, head), 384 KB per tile
   float* front_ws;                        // fused front-end backward: workgroup slabs
-  void* tg_ws;      size_t tg_ws_bytes;   // table mode: sort scratch of the deterministic table gradient (table_grad.hip)
   // node route of the table front end (null when the shape cannot take it): X and x0 per NODE [n_nodes + 1][64] (row 0: the padding id), the
   // backward's per-node sum of the tokens' gradient rows, the id list 0..n_nodes and its length {n_nodes + 1, n_nodes} (both written by the plan)
   float *XN, *x0N, *xhN, *GN; int64_t* node_ids; int32_t* node_cnt;
@@ -195,76 +180,6 @@ static int check_objective(int32_t objective, const char* fn) {
   set_error("%s: unknown objective %d (MATCHA_OBJECTIVE_BCE or MATCHA_OBJECTIVE_SOFTPLUS_MSE)", fn, (int)objective);
   return MATCHA_EINVAL;
 }
-// The kernel route of one step: every decision of the forward that a later line of it, or the backward on the same workspace, depends on.
-// decide_route (behind the workspace layout it reads) fills it ONCE per forward -- it and the predicates above are the only routing code that
-// reads the option table -- and the record below hands it to matcha_backward as it is.
-struct StepRoute {
-  bool compact;                  // workspace layout of a forward that will not be differentiated (carve)
-  bool half_plan;                // the ragged plan stops at the half tiles (level 1: no 64-row tile list, no token -> tile map)
-  bool fused;                    // embed_dim 64: X -> logits in one forward kernel, the attention block's backward in one (fused_fwd32.hip, fused_bwd.hip)
-  bool merged_layerwise, enc128; // layer by layer at embed_dim >= 128: merged heads;  at 128 the attention block as ONE kernel pair (enc128.hip)
-  bool front, adj_fused;         // fused front end and its backward (front_fused.hip);  the adj front end as ONE kernel over the chromosome-sorted rows (adj_fused.hip)
-  bool small;                    // the small-batch kernels (fused_small_batch)
-  bool lif;                      // the tail's backward ran inside the forward kernel: Y / H1 / H2 hold parked rows, ddyn0 and dXs are final
-  bool split_tail, dx_zeroed;    // ... up to its LayerNorms, the convolutions' as tail_bwd64_kernel;  the forward zeroed the d x_hat rows the backward's heads add into
-  bool node;                     // table front end per NODE: X lives in the per-node table, rows by tok_key
-  bool node_r, node_v;           // ... the heads' r rows gathered from the per-node table (none in the record);  ... and the value table VN left for the backward
-  bool node_dx;                  // ... d x_hat and dXs added per NODE by their producers (AH in dO, AS in GN): node_scatter_kernel is the per-node finisher
-  bool paired;                   // fused route: independent small launches share a launch -- the chain rule's blocks un-fold their own rows; with node_dx
-                                 // the node route the final vectors ride in node_scatter_kernel and the plan's tile lists in the table launches.  Off: the launches of the step one by one
-};
-// Which route the forward that last ran on a workspace took.  matcha_backward keys off THIS record and reads no option: the two calls are
-// separate on the autograd path and the switches are process-wide, so a flip between them would otherwise make the backward consume records
-// nobody wrote.  Host-side record per workspace pointer (the decision picks a kernel, so it cannot live in device memory without a
-// synchronisation); bounded, evicted oldest-first, guarded by a mutex.  A backward on a workspace WITHOUT a record is refused.
-static std::mutex g_fwd_mu;
-static std::unordered_map<const void*, std::pair<StepRoute, uint64_t>> g_fwd_state;     // ws -> (route, age)
-static uint64_t g_fwd_clock = 0;
-static void note_forward(const void* ws, const StepRoute& route) {
-  std::lock_guard<std::mutex> lk(g_fwd_mu);
-  if (g_fwd_state.size() >= 4096 && g_fwd_state.find(ws) == g_fwd_state.end()) {
-    auto old = g_fwd_state.begin();
-    for (auto it = g_fwd_state.begin(); it != g_fwd_state.end(); ++it)
-      if (it->second.second < old->second.second) old = it;
-    g_fwd_state.erase(old);
-  }
-  g_fwd_state[ws] = std::make_pair(route, ++g_fwd_clock);
-}
-static bool recorded_route(const void* ws, StepRoute& route) {       // false: no forward on record for this workspace
-  std::lock_guard<std::mutex> lk(g_fwd_mu);
-  auto it = g_fwd_state.find(ws);
-  if (it != g_fwd_state.end()) route = it->second.first;
-  return it != g_fwd_state.end();
-}
-// The record of a workspace is dropped by a forward_only forward on it (which keeps nothing a backward could read and overwrites what an
-// earlier training forward left there) and by the backward that consumed it (matcha_backward overwrites the saved activations with their
-// gradients): a backward then finds no record and is refused before any launch.
-static void forget_forward(const void* ws) {
-  std::lock_guard<std::mutex> lk(g_fwd_mu);
-  g_fwd_state.erase(ws);
-}
-
-// B_all[h d + a][b] = sum_m W_k[h d + m][a] W_q[h d + m][b];   M_all[n][h d + b] = sum_m Wfc1[n][h d + m] W_v[h d + m][b]   (16 small GEMMs)
-static int merged_weights(const matcha_shape& s, const matcha_tensors& p, Workspace& w, hipStream_t st) {
-  const int64_t d = s.d, hd = (int64_t)MATCHA_N_HEAD * d;
-  // both products, all heads, one launch (bmm_heads.hip; every embed_dim the merged layer-wise path takes is a multiple of 64)
-  const BmmProduct pr[2] = {
-      {p.w_k, 1, d, d * d, p.w_q, d, 1, d * d, w.lwB, d, d * d, 0},            // B_h[a][b] = sum_m W_k[h d + m][a] W_q[h d + m][b]
-      {p.fc1_w, hd, 1, d, p.w_v, d, 1, d * d, w.lwM, hd, d, 0}};               // M_all[n][h d + b] = sum_m Wfc1[n][h d + m] W_v[h d + m][b]
-  return launch_bmm_heads(pr, 2, s.d, st);
-}
-// chain rule from dB_all, dM_all to the projections (accumulating):  dW_q[h] += W_k[h] dB_h;  dW_k[h] += W_q[h] dB_h^T;
-//   dWfc1[:, h] += dM_h W_v[h]^T;  dW_v[h] += Wfc1[:, h]^T dM_h
-static int merged_chain(const matcha_shape& s, const matcha_tensors& p, matcha_tensors& g_, Workspace& w, hipStream_t st) {
-  const int64_t d = s.d, hd = (int64_t)MATCHA_N_HEAD * d;
-  const BmmProduct pr[4] = {
-      {p.w_k, d, 1, d * d, w.lwdB, d, 1, d * d, g_.w_q, d, d * d, 1},          // dW_q[h][m][b] += sum_a W_k[h][m][a] dB_h[a][b]
-      {p.w_q, d, 1, d * d, w.lwdB, 1, d, d * d, g_.w_k, d, d * d, 1},          // dW_k[h][m][a] += sum_b W_q[h][m][b] dB_h[a][b]
-      {w.lwdM, hd, 1, d, p.w_v, 1, d, d * d, g_.fc1_w, hd, d, 1},              // dWfc1[n][h d + m] += sum_b dM[n][h d + b] W_v[h d + m][b]
-      {p.fc1_w, 1, hd, d, w.lwdM, hd, 1, d, g_.w_v, d, d * d, 1}};             // dW_v[h][m][b] += sum_n Wfc1[n][h d + m] dM[n][h d + b]
-  return launch_bmm_heads(pr, 4, s.d, st);
-}
-
 // `compact`: layout of a forward that will not be differentiated and runs the fused kernels (d = 64): only the ragged plan,
 // x0, X, the adj front end's buffers, the folded weights and the per-row outputs exist; everything else has size 0.
 static size_t carve(const matcha_shape& s, int64_t B, int L, char* base, Workspace& w, bool compact = false) {
@@ -300,24 +215,9 @@ static size_t carve(const matcha_shape& s, int64_t B, int L, char* base, Workspa
   w.dO = w.O; w.dQ = w.K; w.dK = w.Q; w.dV = w.V;
   w.dqin = w.qin; w.dkin = w.kin; w.dvin = w.vin;
   w.dZ0 = take(Tn * d); w.dX0 = take(Tn * d);
-  size_t sb = colsum_slab_bytes(Tn, 6, (int)d);
-  size_t sb2 = colsum_slab_bytes(B, 7, (int)d);
-  if (sb2 > sb) sb = sb2;
-  sb2 = attn_bwd_slab_bytes(B, (int)d);
-  if (sb2 > sb) sb = sb2;
-  w.slab_bytes = sb; w.slab = take(sb / sizeof(float));
-  size_t gb = gemm_tn_ws_bytes(hd, d, Tn);                       // dWq/dWk/dWv
-  size_t g2 = gemm_tn_ws_bytes(d, hd, Tn); if (g2 > gb) gb = g2; // dfc1
-  g2 = gemm_tn_ws_bytes(d, d, Tn); if (g2 > gb) gb = g2;
-  g2 = gemm_tn_ws_bytes(d, s.n_attr, Tn); if (g2 > gb) gb = g2;
-  if (s.mode == 1) {   // recon head gradient [n_r, d] for any chromosome r: the slab count depends on ceil(n_r/64)
-    for (int64_t m = 64;; m += 64) {
-      const int64_t mm = m < s.max_bins ? m : s.max_bins;
-      g2 = gemm_tn_ws_bytes(mm, d, Tn); if (g2 > gb) gb = g2;
-      if (mm >= s.max_bins) break;
-    }
-  }
-  w.gemm_ws_bytes = gb; w.gemm_ws = take(gb / sizeof(float));
+  chain_scratch_bytes(s, B, L, false, w);
+  w.slab = take(w.slab_bytes / sizeof(float));
+  w.gemm_ws = take(w.gemm_ws_bytes / sizeof(float));
   w.adj_ws_bytes = (s.mode == 1) ? adj_workspace_bytes(s, Tn) : 0;
   w.adj_ws = take_always(w.adj_ws_bytes / sizeof(float));
   w.folded = take_always(s.d == 64 ? fused_fold_floats() : 0);
@@ -391,6 +291,7 @@ static StepRoute decide_route(const matcha_shape& s, const matcha_step_opts& o, 
   // node route with the value table: the forward's tail adds dXs per node, tail_bwd64_kernel zeroes the heads' per-node replicas behind it
   r.node_dx = r.node_v && r.lif && r.split_tail && r.dx_zeroed && node_dx_shape(s, B, L) && !options().disable_node_dx;
   r.paired = r.fused && !options().disable_launch_pairs;
+  r.long_rows = false;      // (matcha_forward_long_train notes its own record)
   return r;
 }
 // what the encoder kernels and head_bwd read for X on this route (kernels.hpp): the per-node tables by tok_key, or X per token
@@ -399,71 +300,15 @@ static NodeOperands node_operands(const StepRoute& r, const matcha_shape& s, con
   return r.node ? NodeOperands{w.XN, w.rg.tok_key, w.xhN, r.node_r ? w.RN : nullptr, r.node_v ? w.VN : nullptr, rows} : NodeOperands{w.X, nullptr, nullptr, nullptr, nullptr, rows};
 }
 
-// Table mode, after the backward pass left one gradient row per compact token in w.dX0 (ids in w.rg.tok_key): add them into the
-// dense table gradient deterministically (table_grad.hip; opts.deterministic) -- unless the caller asked for the row-sparse form
-// (opts.sparse_table_grad: the list stays in the workspace for matcha_table_grad_rows / the data-parallel exchange).
-static int table_gradient(const matcha_shape& s, const matcha_step_opts& o, const Workspace& w, int64_t Tn, matcha_tensors& g, hipStream_t st) {
-  if (o.sparse_table_grad) return MATCHA_OK;
-  if (!o.deterministic) return MATCHA_OK;                 // the front-end kernel already added the rows with float atomics
-  return launch_table_grad(w.rg.tok_key, w.dX0, Tn, s.d, s.n_nodes, g.table, w.tg_ws, w.tg_ws_bytes, st);
-}
-
-// opts->encoder_done_event: every gradient from ln_q_g to cls_b is final at this point of the stream (include/matcha_hip.h)
-static int encoder_done(const matcha_step_opts& o, hipStream_t st) {
-  if (o.encoder_done_event && hipEventRecord((hipEvent_t)o.encoder_done_event, st) != hipSuccess) {
-    set_error("matcha_backward: recording encoder_done_event failed"); return MATCHA_EHIP;
-  }
-  return MATCHA_OK;
-}
-
 static int check_shape(const matcha_shape* s, int64_t B, int32_t L) {
-  MATCHA_CHECK_ARG(s, "null shape");
-  MATCHA_CHECK_ARG(s->d >= 8 && s->d <= 256 && s->d % 8 == 0 && (s->d <= 64 || s->d % 64 == 0),
-                   "embed_dim d=%d unsupported (multiples of 8 up to 64, then 128, 192, 256)", s->d);
-  MATCHA_CHECK_ARG(s->d % 4 == 0, "d must be a multiple of 4");
+  MATCHA_TRY(check_shape_fields(s, nullptr));
   MATCHA_CHECK_ARG(L >= 1 && L <= MATCHA_MAX_L, "L=%d outside 1..%d", L, MATCHA_MAX_L);
   MATCHA_CHECK_ARG(B >= 1 && B * (int64_t)L < (1ll << 31) - 2, "B=%lld must be >= 1 and B*L < 2^31", (long long)B);
   // the layer-by-layer kernels (every embed_dim but 64) put token tiles on grid.y (<= 65 535 tiles of 128 tokens) and launch
   // T * d / 256 workgroups on grid.x: 8.38 M token rows is what they support
   MATCHA_CHECK_ARG(s->d == 64 || B * (int64_t)L + 1 <= 65535ll * 128, "B*L=%lld exceeds the %lld token rows the layer-by-layer kernels (embed_dim != 64) launch",
                    (long long)(B * (int64_t)L), 65535ll * 128);
-  MATCHA_CHECK_ARG(s->n_nodes >= 1, "n_nodes=%d must be >= 1", s->n_nodes);
-  MATCHA_CHECK_ARG(s->mode == 0 || s->mode == 1, "mode=%d must be 0 (table) or 1 (adj)", s->mode);
-  MATCHA_CHECK_ARG(s->n_attr >= 1 && (size_t)s->n_attr * s->d * 4 <= 160 * 1024, "n_attr=%d does not fit the LDS staging", s->n_attr);
   return MATCHA_OK;
-}
-
-static GemmArgs gemm1(const Workspace& w, const float* A, const float* B, float* C, int64_t M, int64_t N, int64_t K, bool b_kn) {
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.A[0] = A; g.B[0] = B; g.C[0] = C; g.batch = 1;
-  g.M = M; g.N = N; g.K = K; g.lda = K; g.ldb = b_kn ? N : K; g.ldc = N;
-  g.aux_scale = 1.f;
-  g.m_dev = w.rg.count;            // true token count (Tr + 1) lives on the device
-  g.rng_row_map = w.rg.tok_slot;   // dropout counters follow the original [B, L] slots
-  return g;
-}
-
-// MATCHA_DEBUG_NAN=1: after selected stages count the non-finite values in the VALID rows of a buffer and print them
-// (synchronises; development only -- it found reads of uninitialised workspace rows)
-__global__ void nan_count_kernel(const float* __restrict__ p, const int32_t* __restrict__ rows_dev, int64_t rows, int64_t width, int* __restrict__ out) {
-  if (rows_dev) rows = *rows_dev;
-  int bad = 0;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows * width; i += (int64_t)gridDim.x * blockDim.x)
-    bad += isfinite(p[i]) ? 0 : 1;
-  if (bad) atomicAdd(out, bad);
-}
-static void nan_check(const char* name, const float* p, const int32_t* rows_dev, int64_t rows, int64_t width, hipStream_t st) {
-  if (!options().debug_nan || !p) return;
-  int* d = nullptr;
-  int h = 0;
-  if (hipMalloc(&d, sizeof(int)) != hipSuccess) return;
-  (void)hipMemsetAsync(d, 0, sizeof(int), st);
-  hipLaunchKernelGGL(nan_count_kernel, dim3(256), dim3(256), 0, st, p, rows_dev, rows, width, d);
-  (void)hipMemcpyAsync(&h, d, sizeof(int), hipMemcpyDeviceToHost, st);
-  (void)hipStreamSynchronize(st);
-  (void)hipFree(d);
-  fprintf(stderr, "[matcha nan-check] %-10s %d non-finite values in the valid rows\n", name, h);
 }
 
 }  // namespace matcha
@@ -548,15 +393,10 @@ static int forward_impl(const matcha_shape* shp, const matcha_tensors* params, c
   const size_t need = carve(s, B, L, (char*)ws, w, compact_forward(s, *opts, force_layerwise));
   if (ws_bytes < need) { set_error("matcha_forward: workspace %zu < %zu bytes", ws_bytes, need); return MATCHA_ENOMEM; }
   const int64_t Tn = B * L + 1;                 // upper bound; the true count is *w.rg.count
-  const int d = s.d;
-  const int64_t hd = (int64_t)MATCHA_N_HEAD * d;
   const bool train = opts->training != 0;
   MATCHA_CHECK_ARG(!train || opts->seed || (opts->p_drop_adj <= 0 && opts->p_drop_fc1 <= 0 && opts->p_drop_pff <= 0),
                    "matcha_forward: training with dropout needs opts->seed");
-  MATCHA_CHECK_ARG((frozen->attr_table || frozen->attr_mode == 1) && p.attr_w && p.attr_b && p.next_w && p.next_b && p.w_q && p.w_k && p.w_v && p.fc1_w &&
-                       p.fc1_b && p.pff0_w && p.pff0_b && p.pff1_w && p.pff1_b && p.pff_ln_g && p.pff_ln_b && p.ln1_g && p.ln1_b &&
-                       p.ln2_g && p.ln2_b && p.cls_w && p.cls_b && p.ln_q_g && p.ln_q_b && p.ln_k_g && p.ln_k_b && p.ln_v_g && p.ln_v_b,
-                   "matcha_forward: a parameter pointer is null");
+  MATCHA_TRY(check_chain_params(p, *frozen, "matcha_forward"));
   const int32_t* cnt = w.rg.count;
   const int64_t* ids = w.rg.tok_id;
 
@@ -576,8 +416,12 @@ static int forward_impl(const matcha_shape* shp, const matcha_tensors* params, c
   float* recon_out = losses ? losses + 1 : nullptr;
   // table front end: the two reconstruction-loss slots are zero; loss_reduce_kernel writes them when it runs anyway
   const bool recon_zero_in_loss = s.mode == 0 && recon_out && route.fused && tgt;
-  if (s.mode == 0) {
-    MATCHA_CHECK_ARG(p.table, "matcha_forward: table mode without table");
+  if (s.mode == 0) MATCHA_CHECK_ARG(p.table, "matcha_forward: table mode without table");
+  // (merged / keep: what the layer-by-layer pieces below read of the route)
+  const ChainCall chain{s, p, *frozen, *opts, B, L, st, {route.merged_layerwise, false, keep}, "matcha_forward"};
+  if (!route.front) {
+    MATCHA_TRY(chain_front_fwd(chain, w, recon_out, !recon_zero_in_loss));      // the separate kernels: adj rows or zero slots, x0, X = tanh(next_w(x0))
+  } else if (s.mode == 0) {
     if (recon_out && !recon_zero_in_loss) MATCHA_TRY(zero_async(recon_out, 2 * sizeof(float), st));
   } else if (route.adj_fused) {
     MATCHA_TRY(adj_forward(s, p, *frozen, *opts, ids, Tn, nullptr, recon_out, w.adj_ws, w.adj_ws_bytes, st, cnt, w.rg.tok_slot, keep ? w.x0 : nullptr, w.X, keep));
@@ -599,12 +443,6 @@ static int forward_impl(const matcha_shape* shp, const matcha_tensors* params, c
       else if (deferred.pending) MATCHA_TRY(launch_tile_compact(deferred.compact, st));
     } else
     MATCHA_TRY(launch_front_fwd(p, ids, s.mode == 0 ? p.table : nullptr, s.mode == 0 ? nullptr : w.node, *frozen, s.n_attr, w.rg, Tn, keep ? w.x0 : nullptr, w.X, st, &prep));     // x0 (pre-activation) is only read by the backward pass
-  } else if (!route.adj_fused) {
-    MATCHA_TRY(launch_embed_fwd(ids, Tn, d, s.mode == 0 ? p.table : nullptr, s.mode == 0 ? nullptr : w.node, *frozen, s.n_attr, p.attr_w, p.attr_b, w.x0, st, cnt));
-    // X = tanh(next_w(x0))   (Modules.py:270)
-    GemmArgs g = gemm1(w, w.x0, p.next_w, w.X, Tn, d, d, false);
-    g.flags = MATCHA_EPI_BIAS | MATCHA_EPI_TANH; g.bias[0] = p.next_b;
-    MATCHA_TRY(launch_gemm_rm(false, g, st));
   }
   if (keep) note_forward(ws, route); else forget_forward(ws);      // the backward pass on this workspace must follow the same route
   if (route.fused) {
@@ -635,65 +473,16 @@ static int forward_impl(const matcha_shape* shp, const matcha_tensors* params, c
     }
     return MATCHA_OK;
   }
-  nan_check("x0", w.x0, cnt, 0, d, st);
-  nan_check("X", w.X, cnt, 0, d, st);
+  // layer by layer (layerwise.hip): the attention block -- at embed_dim 128 as one kernel: LayerNorms, merged heads, attention, fc1 + dropout + mask,
+  // X -> Y; a training forward leaves r rows + probabilities -- then pff_n1 and the head
   if (route.enc128) {
-    // LayerNorms, merged heads, attention, fc1 + dropout + mask: X -> Y in one kernel; a training forward leaves r rows + probabilities
     MATCHA_TRY(merged_weights(s, p, w, st));
     MATCHA_TRY(launch_enc128_fwd(p, w.lwB, w.lwM, w.X, w.rg, B, L, w.Y, keep ? w.enc_rec : nullptr, w.enc, w.rg.tok_slot, opts->seed,
                                  (train && opts->p_drop_fc1 > 0.f) ? opts->p_drop_fc1 : 0.f, st));
   } else {
-  // three LayerNorms on the same row (Modules.py:519-521), then Q/K/V projections (:527-529), one batched launch
-  MATCHA_TRY(launch_ln3_fwd(w.X, Tn, d, p.ln_q_g, p.ln_q_b, p.ln_k_g, p.ln_k_b, p.ln_v_g, p.ln_v_b, w.qin, w.kin, w.vin, w.stats, st, cnt));
-  if (route.merged_layerwise) {
-    MATCHA_TRY(merged_weights(s, p, w, st));
-    GemmArgs g = gemm1(w, w.qin, w.lwB, w.Q, Tn, hd, d, false);                 // r = qin B_all^T  (in Q's buffer)
-    MATCHA_TRY(launch_gemm_rm(false, g, st));
-  } else {
-    GemmArgs g = gemm1(w, w.qin, p.w_q, w.Q, Tn, hd, d, false);
-    g.A[1] = w.kin; g.B[1] = p.w_k; g.C[1] = w.K;
-    g.A[2] = w.vin; g.B[2] = p.w_v; g.C[2] = w.V;
-    g.batch = 3;
-    MATCHA_TRY(launch_gemm_rm(false, g, st));
+    MATCHA_TRY(chain_attn_fwd(chain, w));
   }
-  nan_check("qin", w.qin, cnt, 0, d, st);
-  nan_check("Q", w.Q, cnt, 0, hd, st);
-  nan_check("K", w.K, cnt, 0, hd, st);
-  nan_check("V", w.V, cnt, 0, hd, st);
-  if (route.merged_layerwise) MATCHA_TRY(launch_attn_fwd(w.Q, w.kin, w.vin, w.rg.row_off, B, L, d, w.O, w.P, st, true));     // O = Z = P . vin per head
-  else MATCHA_TRY(launch_attn_fwd(w.Q, w.K, w.V, w.rg.row_off, B, L, d, w.O, w.P, st));
-  nan_check("O", w.O, cnt + 1, 0, hd, st);
-  // Y = (dropout(fc1(O))) * non_pad_mask    (Modules.py:572, :614); the mask only zeroes the shared padding token's row
-  {
-    GemmArgs g = gemm1(w, w.O, route.merged_layerwise ? w.lwM : p.fc1_w, w.Y, Tn, d, hd, false);
-    g.flags = MATCHA_EPI_BIAS | MATCHA_EPI_ROWMASK; g.bias[0] = p.fc1_b; g.row_ids = ids;
-    if (train && opts->p_drop_fc1 > 0.f) { g.flags |= MATCHA_EPI_DROPOUT; g.seed = opts->seed; g.stream_id = kStreamDropFc1; g.p_drop = opts->p_drop_fc1; }
-    MATCHA_TRY(launch_gemm_rm(false, g, st));
-  }
-  }
-  // pff_n1: H1 = dropout(tanh(conv0(Y)));  H2 = conv1(H1) + Y      (Modules.py:353-371)
-  {
-    GemmArgs g = gemm1(w, w.Y, p.pff0_w, w.H1, Tn, d, d, false);
-    g.flags = MATCHA_EPI_BIAS | MATCHA_EPI_TANH; g.bias[0] = p.pff0_b;
-    if (train && opts->p_drop_pff > 0.f) { g.flags |= MATCHA_EPI_DROPOUT; g.seed = opts->seed; g.stream_id = kStreamDropPff; g.p_drop = opts->p_drop_pff; }
-    MATCHA_TRY(launch_gemm_rm(false, g, st));
-  }
-  {
-    GemmArgs g = gemm1(w, w.H1, p.pff1_w, w.H2, Tn, d, d, false);
-    g.flags = MATCHA_EPI_BIAS | MATCHA_EPI_RESIDUAL; g.bias[0] = p.pff1_b; g.residual = w.Y;
-    MATCHA_TRY(launch_gemm_rm(false, g, st));
-  }
-  nan_check("Y", w.Y, cnt, 0, d, st);
-  nan_check("H1", w.H1, cnt, 0, d, st);
-  nan_check("H2", w.H2, cnt, 0, d, st);
-  if (stop_before_head) return MATCHA_OK;
-  // LayerNorms, (dynamic-static)^2, Conv1d(d->1), masked mean, weighted BCE   (Modules.py:373-374, :290-311; main.py:56)
-  HeadParams hp = {p.pff_ln_g, p.pff_ln_b, p.ln1_g, p.ln1_b, p.ln2_g, p.ln2_b, p.cls_w, p.cls_b};
-  MATCHA_TRY(launch_head_fwd(w.rg.row_off, w.H2, w.X, B, L, d, hp, y, w_bce, w.logits, w.row_loss, losses, st, objective));
-  if (logits && hipMemcpyAsync(logits, w.logits, B * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) {
-    set_error("logits copy failed"); return MATCHA_EHIP;
-  }
-  return MATCHA_OK;
+  return chain_tail_fwd(chain, w, y, w_bce, logits, losses, objective, stop_before_head);
 }
 
 extern "C" int matcha_forward(const matcha_shape* shp, const matcha_tensors* params, const matcha_frozen* frozen,
@@ -805,16 +594,13 @@ static int backward_impl(const matcha_shape* shp, const matcha_tensors* params, 
   const size_t need = carve(s, B, L, (char*)ws, w);
   if (ws_bytes < need) { set_error("matcha_backward: workspace %zu < %zu bytes", ws_bytes, need); return MATCHA_ENOMEM; }
   const int64_t Tn = B * L + 1;
-  const int d = s.d;
-  const int64_t hd = (int64_t)MATCHA_N_HEAD * d;
-  const bool train = opts->training != 0;
-  const bool drop_fc1 = train && opts->p_drop_fc1 > 0.f, drop_pff = train && opts->p_drop_pff > 0.f;
-  const int32_t* cnt = w.rg.count;             // the plan (row_off, tok_id, tok_slot, count) is still in the workspace
-  const int64_t* ids = w.rg.tok_id;
+  const int64_t* ids = w.rg.tok_id;            // the plan (row_off, tok_id, tok_slot, count) is still in the workspace
 
   // which kernels the forward ran on this workspace is what decides, not the option table now: everything below follows `route`
   StepRoute route;
-  MATCHA_CHECK_ARG(recorded_route(ws, route), "matcha_backward: no matcha_forward on record for this workspace (one backward per forward, same ws pointer)");
+  // (a record of matcha_forward_long_train is none of this entry point's: refused like no record, and left for matcha_backward_long)
+  MATCHA_CHECK_ARG(recorded_route(ws, route) && !route.long_rows,
+                   "matcha_backward: no matcha_forward on record for this workspace (one backward per forward, same ws pointer)");
   // fused route: this call's options and targets must ask for the loss where the forward computed it (head_bwd over rows the forward only parked, or no ddyn0)
   MATCHA_CHECK_ARG(!route.fused || route.lif == (opts->loss_in_forward && has_target(objective, y, w_bce)),
                    "matcha_backward: loss_in_forward / targets differ from the forward's on this workspace");
@@ -824,6 +610,7 @@ static int backward_impl(const matcha_shape* shp, const matcha_tensors* params, 
   const bool dx_zeroed = route.dx_zeroed && !opts->deterministic && !opts->sparse_table_grad;      // tail_bwd64_kernel / the loss reduction zeroed the heads' d x_hat buffer
   TailReduceArgs tail_args;
   const NodeOperands nx = node_operands(route, s, w);   // node route: X lives in the per-node table, rows by tok_key
+  const ChainCall chain{s, p, *frozen, *opts, B, L, st, {route.merged_layerwise, false, true}, "matcha_backward"};
   if (route.lif) {
     // ddyn0 and dXs were produced by matcha_forward; only the parameter-gradient partials remain to be summed (fused_fwd32.hip).  Split tail: one
     // row-major slab per workgroup of tail_bwd64_kernel -- the convolutions' gradients and the half tiles' LayerNorm / classifier vectors (summed
@@ -832,26 +619,7 @@ static int backward_impl(const matcha_shape* shp, const matcha_tensors* params, 
     else if (route.small) tail_reduce_args(w.tslab, w.rg, L, g_, true, -1, false, tail_args);
     else MATCHA_TRY(launch_tail_reduce(w.tslab, w.rg, L, g_, st, true, w.tpart));
   } else {
-  // tail: dH2, dXs and the gradients of pff_n1.layer_norm, layer_norm1/2, pff_classifier
-  HeadParams hp = {p.pff_ln_g, p.pff_ln_b, p.ln1_g, p.ln1_b, p.ln2_g, p.ln2_b, p.cls_w, p.cls_b};
-  HeadParams ghp = {g_.pff_ln_g, g_.pff_ln_b, g_.ln1_g, g_.ln1_b, g_.ln2_g, g_.ln2_b, g_.cls_w, g_.cls_b};
-  MATCHA_TRY(launch_head_bwd(w.rg.row_off, w.H2, nx.X, B, L, d, hp, y, w_bce, w.logits, dlogits, opts->alpha, w.dH2, w.dXs, w.slab, ghp, st, objective, nx.xrow));
-  // pff_n1 conv1: dW1 += dH2^T H1 ; db1 += colsum(dH2) ; dZ1 = (dH2 W1) * dropmask * (1 - tanh^2)
-  MATCHA_TRY(launch_gemm_tn(w.dH2, w.H1, g_.pff1_w, g_.pff1_b, d, d, Tn, d, d, nullptr, true, w.gemm_ws, w.gemm_ws_bytes, st, cnt));
-  {
-    GemmArgs g = gemm1(w, w.dH2, p.pff1_w, w.dZ1, Tn, d, d, true);
-    g.flags = MATCHA_EPI_DTANH; g.aux = w.H1;
-    if (drop_pff) { g.flags |= MATCHA_EPI_DROPOUT; g.seed = opts->seed; g.stream_id = kStreamDropPff; g.p_drop = opts->p_drop_pff; g.aux_scale = 1.f - opts->p_drop_pff; }
-    MATCHA_TRY(launch_gemm_rm(true, g, st));
-  }
-  // pff_n1 conv0: dW0 += dZ1^T Y ; ddyn0 = (dZ1 W0 + dH2[residual]) * dropmask_fc1 * non_pad
-  MATCHA_TRY(launch_gemm_tn(w.dZ1, w.Y, g_.pff0_w, g_.pff0_b, d, d, Tn, d, d, nullptr, true, w.gemm_ws, w.gemm_ws_bytes, st, cnt));
-  {
-    GemmArgs g = gemm1(w, w.dZ1, p.pff0_w, w.ddyn0, Tn, d, d, true);
-    g.flags = MATCHA_EPI_RESIDUAL | MATCHA_EPI_ROWMASK; g.residual = w.dH2; g.row_ids = ids;
-    if (drop_fc1) { g.flags |= MATCHA_EPI_DROPOUT; g.seed = opts->seed; g.stream_id = kStreamDropFc1; g.p_drop = opts->p_drop_fc1; }
-    MATCHA_TRY(launch_gemm_rm(true, g, st));
-  }
+    MATCHA_TRY(chain_tail_bwd(chain, w, nx.X, nx.xrow, y, w_bce, dlogits, objective, g_));      // head_bwd and pff_n1's products: dH2, dXs, dZ1, ddyn0
   }
   if (route.fused) {
     // attention block (fc1, attention, Q/K/V projections, the three LayerNorms) from X and ddyn0 in one head-major kernel;
@@ -893,81 +661,17 @@ static int backward_impl(const matcha_shape* shp, const matcha_tensors* params, 
       else MATCHA_TRY(adj_backward(s, p, *frozen, *opts, ids, Tn, w.dX0, drecon, g_, touched, w.adj_ws, w.adj_ws_bytes, w.gemm_ws, w.gemm_ws_bytes, st, w.rg.tok_slot, route.adj_fused));
       return MATCHA_OK;
     }
-  } else {
-  if (route.enc128) {
+  } else if (route.enc128) {
     // embed_dim 128, fused attention block: dB_all / dM_all (LayerNorm affines taken back out) + d x_hat in one kernel, then the chain rule to
     // w_qs / w_ks / w_vs / fc1 and the LayerNorm backward (enc128.hip); dxh lives in qin's buffer
     MATCHA_TRY(launch_enc128_bwd(p, w.lwB, w.lwM, w.X, w.ddyn0, w.dXs, w.rg, B, L, w.dqin, w.enc_rec, w.enc, w.lwdB, w.lwdM, g_, w.dZ0, st));
     MATCHA_TRY(merged_chain(s, p, g_, w, st));
     MATCHA_TRY(encoder_done(*opts, st));
   } else {
-  if (route.merged_layerwise) {
-    // merged heads: dM_all = ddyn0^T Z ; d fc1_b += colsum ; dZ = ddyn0 M_all   (the scratch gradients start from zero: the TN GEMM
-    // accumulates C and the column sums alike, and fc1_b's gradient must accumulate)
-    MATCHA_TRY(zero_async(w.lwdM, (size_t)hd * d * sizeof(float), st));
-    MATCHA_TRY(zero_async(w.lwdB, (size_t)hd * d * sizeof(float), st));
-    MATCHA_TRY(launch_gemm_tn(w.ddyn0, w.O, w.lwdM, g_.fc1_b, d, hd, Tn, d, hd, nullptr, true, w.gemm_ws, w.gemm_ws_bytes, st, cnt));
-    {
-      GemmArgs g = gemm1(w, w.ddyn0, w.lwM, w.dO, Tn, hd, d, true);
-      MATCHA_TRY(launch_gemm_rm(true, g, st));
-    }
-    // attention backward on the shared key / value rows: dR in K's (unused) buffer, dK / dV per head in Q's and V's buffers
-    // d kin / d vin = the sums over the heads, added inside the kernel (kin / vin themselves are read by it: separate buffers)
-    MATCHA_TRY(launch_attn_bwd(w.Q, w.kin, w.vin, w.P, w.dO, w.rg.row_off, B, L, d, w.dQ, w.dK, w.dV, w.slab, st, true, w.dkin, w.dvin));
-    // dB_all = dR^T qin ; dqin = dR B_all ; then the chain rule to w_qs / w_ks / w_vs / fc1
-    MATCHA_TRY(launch_gemm_tn(w.dQ, w.qin, w.lwdB, nullptr, hd, d, Tn, hd, d, nullptr, true, w.gemm_ws, w.gemm_ws_bytes, st, cnt));
-    {
-      GemmArgs g = gemm1(w, w.dQ, w.lwB, w.dqin, Tn, d, hd, true);
-      MATCHA_TRY(launch_gemm_rm(true, g, st));
-    }
-    MATCHA_TRY(merged_chain(s, p, g_, w, st));
-  } else {
-  // fc1: dW += ddyn0^T O ; db += colsum ; dO = ddyn0 Wfc1
-  MATCHA_TRY(launch_gemm_tn(w.ddyn0, w.O, g_.fc1_w, g_.fc1_b, d, hd, Tn, d, hd, nullptr, true, w.gemm_ws, w.gemm_ws_bytes, st, cnt));
-  {
-    GemmArgs g = gemm1(w, w.ddyn0, p.fc1_w, w.dO, Tn, hd, d, true);
-    MATCHA_TRY(launch_gemm_rm(true, g, st));
+    MATCHA_TRY(chain_attn_bwd(chain, w, g_));      // the heads in the forward's formulation, ln3_bwd, the encoder_done event
   }
-  MATCHA_TRY(launch_attn_bwd(w.Q, w.K, w.V, w.P, w.dO, w.rg.row_off, B, L, d, w.dQ, w.dK, w.dV, w.slab, st));
-  // Q/K/V projections: dW += dQ^T qin ; dqin = dQ Wq  (batched x3)
-  MATCHA_TRY(launch_gemm_tn(w.dQ, w.qin, g_.w_q, nullptr, hd, d, Tn, hd, d, nullptr, true, w.gemm_ws, w.gemm_ws_bytes, st, cnt));
-  MATCHA_TRY(launch_gemm_tn(w.dK, w.kin, g_.w_k, nullptr, hd, d, Tn, hd, d, nullptr, true, w.gemm_ws, w.gemm_ws_bytes, st, cnt));
-  MATCHA_TRY(launch_gemm_tn(w.dV, w.vin, g_.w_v, nullptr, hd, d, Tn, hd, d, nullptr, true, w.gemm_ws, w.gemm_ws_bytes, st, cnt));
-  {
-    GemmArgs g = gemm1(w, w.dQ, p.w_q, w.dqin, Tn, d, hd, true);
-    g.A[1] = w.dK; g.B[1] = p.w_k; g.C[1] = w.dkin;
-    g.A[2] = w.dV; g.B[2] = p.w_v; g.C[2] = w.dvin;
-    g.batch = 3;
-    MATCHA_TRY(launch_gemm_rm(true, g, st));
-  }
-  }
-  // LayerNorm x3 backward + static-branch gradient + tanh'
-  MATCHA_TRY(launch_ln3_bwd(w.X, w.dqin, w.dkin, w.dvin, w.dXs, Tn, d, p.ln_q_g, p.ln_k_g, p.ln_v_g, w.dZ0, w.slab, g_.ln_q_g,
-                            g_.ln_q_b, g_.ln_k_g, g_.ln_k_b, g_.ln_v_g, g_.ln_v_b, st, cnt));
-  MATCHA_TRY(encoder_done(*opts, st));
-  }
-  }
-  // next_w: dW += dZ0^T x0 ; db += colsum ; dX0 = dZ0 Wn
-  MATCHA_TRY(launch_gemm_tn(w.dZ0, w.x0, g_.next_w, g_.next_b, d, d, Tn, d, d, nullptr, true, w.gemm_ws, w.gemm_ws_bytes, st, cnt));
-  {
-    GemmArgs g = gemm1(w, w.dZ0, p.next_w, w.dX0, Tn, d, d, true);
-    MATCHA_TRY(launch_gemm_rm(true, g, st));
-  }
-  // attribute_nn: dWa += dX0^T attr_table[id] ; dba += colsum(dX0)
-  MATCHA_CHECK_ARG(frozen->attr_table, "matcha_backward: the layer-by-layer attribute_nn backward gathers attr_table rows (also under attr_mode 1)");
-  MATCHA_TRY(launch_gemm_tn(w.dX0, frozen->attr_table, g_.attr_w, g_.attr_b, d, s.n_attr, Tn, d, frozen->attr_ld > 0 ? frozen->attr_ld : s.n_attr, ids, true,
-                            w.gemm_ws, w.gemm_ws_bytes, st, cnt));
-  // node embedding
-  if (s.mode == 0) {
-    MATCHA_CHECK_ARG(g_.table, "matcha_backward: table mode without a table gradient buffer");
-    if (opts->deterministic || opts->sparse_table_grad) MATCHA_TRY(table_gradient(s, *opts, w, Tn, g_, st));
-    else MATCHA_TRY(launch_embed_scatter(ids, Tn, d, w.dX0, g_.table, st, cnt));
-    if (touched) MATCHA_TRY(launch_fill_i32(touched, 2, 1, st));
-  } else {
-    MATCHA_TRY(adj_backward(s, p, *frozen, *opts, ids, Tn, w.dX0, drecon, g_, touched, w.adj_ws, w.adj_ws_bytes, w.gemm_ws, w.gemm_ws_bytes, st,
-                            w.rg.tok_slot));
-  }
-  return MATCHA_OK;
+  // next_w, attribute_nn, the node embedding's gradient (layerwise.hip)
+  return chain_front_bwd(chain, w, drecon, g_, touched);
 }
 
 extern "C" int matcha_backward(const matcha_shape* shp, const matcha_tensors* params, const matcha_frozen* frozen,

@@ -201,7 +201,7 @@ static void check_options() {
 static bool same_route(const StepRoute& a, const StepRoute& b) {
   return a.compact == b.compact && a.half_plan == b.half_plan && a.fused == b.fused && a.merged_layerwise == b.merged_layerwise && a.enc128 == b.enc128 &&
          a.front == b.front && a.adj_fused == b.adj_fused && a.small == b.small && a.lif == b.lif && a.split_tail == b.split_tail &&
-         a.dx_zeroed == b.dx_zeroed && a.node == b.node && a.node_r == b.node_r && a.node_v == b.node_v;
+         a.dx_zeroed == b.dx_zeroed && a.node == b.node && a.node_r == b.node_r && a.node_v == b.node_v && a.long_rows == b.long_rows;
 }
 static StepRoute route_of(const matcha_shape& s, const matcha_step_opts& o, int64_t B, int L, bool targets, bool force_layerwise = false) {
   Workspace w;
@@ -297,12 +297,14 @@ static void check_routes() {
     StepRoute r = base;
     r.compact = i & 1; r.half_plan = i & 2; r.fused = i & 4; r.merged_layerwise = i & 8; r.enc128 = i & 16; r.front = i & 32; r.adj_fused = i & 64;
     r.small = i & 128; r.lif = i & 256; r.split_tail = i & 512; r.dx_zeroed = i & 1024; r.node = i & 2048; r.node_r = i & 4096; r.node_v = i % 3 == 0;
+    r.long_rows = i & 8192;
     return r;
   };
   auto ws_ptr = [](int i) { return reinterpret_cast<const void*>((uintptr_t)(i + 1) << 12); };
   StepRoute got;
   CHECK(!recorded_route(ws_ptr(0), got));
-  for (int i = 0; i < 14; ++i) {                     // one field set at a time
+  CHECK(!base.long_rows);                             // decide_route never sets it: the long training forward notes its own record
+  for (int i = 0; i < 14; ++i) {                     // one field set at a time (bit 13: long_rows)
     note_forward(ws_ptr(0), pattern(1 << i));
     CHECK(recorded_route(ws_ptr(0), got) && same_route(got, pattern(1 << i)) && g_fwd_state.size() == 1);
   }
