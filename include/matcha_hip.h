@@ -34,7 +34,7 @@ extern "C" {
 #define MATCHA_ENOMEM (-12) /* workspace too small                             */
 
 #define MATCHA_MAX_L 8      /* widest hyperedge (BASELINE.json configs[4]: k in 2..8) */
-#define MATCHA_MAX_LONG_L 32 /* widest row of the long forward (matcha_forward_long) and the long training pair (matcha_forward_long_train, matcha_backward_long) */
+#define MATCHA_MAX_LONG_L 32 /* widest row of the long forward (matcha_forward_long), of matcha_get_embedding_long and of the long training pair (matcha_forward_long_train, matcha_backward_long) */
 #define MATCHA_N_HEAD 8     /* main.py:616 */
 
 typedef void* matcha_stream_t; /* hipStream_t */
@@ -267,7 +267,7 @@ int matcha_forward(const matcha_shape* shp, const matcha_tensors* params, const 
 
 /* Long rows: the inference forward for x [B, L] with 2 <= L <= MATCHA_MAX_LONG_L (32), B >= 1, B*L < 2^31 - 2 and at most
  * 65 535 * 128 token rows (the layer-by-layer kernels' launch bound); every shape matcha_forward accepts, both front ends.
- * Every other entry point keeps MATCHA_MAX_L.  L <= 8 is accepted too, so that the long kernels can be held against
+ * The entry points without "long" in their name keep MATCHA_MAX_L.  L <= 8 is accepted too, so that the long kernels can be held against
  * matcha_forward on identical input.
  *   opts->training must be 0 and opts->forward_only 1 (anything else: MATCHA_EINVAL before any device call -- dropout and the
  *   backward for long rows do not exist); opts->status and, for the adj front end, opts->random_chrom are honoured as in
@@ -280,6 +280,22 @@ size_t matcha_workspace_bytes_long(const matcha_shape* shp, int64_t B, int32_t L
 int matcha_forward_long(const matcha_shape* shp, const matcha_tensors* params, const matcha_frozen* frozen,
                         const matcha_step_opts* opts, const int64_t* x, int64_t B, int32_t L,
                         float* logits, float* losses, void* ws, size_t ws_bytes, matcha_stream_t stream);
+
+/* Long rows: Classifier.get_embedding(x) (Modules.py:261-276) for x [B, L], 2 <= L <= MATCHA_MAX_LONG_L.  The bounds, option rules and
+ * refusals of matcha_forward_long (training 0, forward_only 1, no random_chrom_dev, opts->status honoured; L <= 8 accepted so that it can be
+ * held against matcha_get_embedding), its workspace (matcha_workspace_bytes_long) and its chain up to pff_n1's convolutions; then
+ *   dynamic float [B,L,d], static float [B,L,d] as matcha_get_embedding;
+ *   attn    float [8B,L,L], optional (may be NULL): the probabilities in the REFERENCE's layout -- block h*B + b, row = query slot, column =
+ *           key slot, both as they stand in x.  The attention kernel (attn_long_prob_kernel) writes every element itself: real query x
+ *           real key from its tile, every padding key slot the padding column's probability (one value per query, bitwise equal across its
+ *           padding slots), the diagonal 0, rows of padding queries 0, the whole block of an all-padding row 0.  The buffer needs no memset
+ *           and nothing runs behind the kernel.  NULL: the plain attn_long_kernel runs, and dynamic / static_ are the same bits either way;
+ *   losses  float [3] as matcha_forward_long, may be NULL.
+ * A workspace below the query's size is refused as an argument error (MATCHA_EINVAL), like every other refusal before any device call.
+ * Caller-owned memory, asynchronous on `stream`, no allocation, no memset node, no read-back.  Not differentiable. */
+int matcha_get_embedding_long(const matcha_shape* shp, const matcha_tensors* params, const matcha_frozen* frozen,
+                              const matcha_step_opts* opts, const int64_t* x, int64_t B, int32_t L, float* dynamic,
+                              float* static_, float* attn, float* losses, void* ws, size_t ws_bytes, matcha_stream_t stream);
 
 /* Long rows, training: matcha_forward_long_train is the chain of matcha_forward_long with every activation the backward needs kept in a
  * buffer of its own (x0, X, the LayerNorm statistics, qin / kin / vin, Q or r, O or Z -- not written over Q --, Y, H1, H2, the logits);

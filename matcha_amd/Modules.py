@@ -796,7 +796,8 @@ class Classifier(nn.Module):
         ws = None
         if rt.mode == 1:
             np.random.choice(np.arange(rt.n_chrom), 1)      # keep numpy's global stream in step with Modules.py:192
-            ws = rt.workspace(sz_b, len_seq)
+            # (only its size matters -- the adj front end's scratch for sz_b * len_seq ids: past MAX_L columns the long query covers it)
+            ws = rt.workspace(sz_b, len_seq, long_rows=len_seq > _lib.MAX_L)
         _lib.check(rt.lib.matcha_node_embeddings(C.byref(rt.shape), C.byref(rt.params), C.byref(rt.frozen), _lib.ptr(ids), ids.numel(),
                                                  _lib.ptr(out), _lib.ptr(ws), 0 if ws is None else ws.numel(), _lib.ptr(rt.status),
                                                  rt.stream()),
@@ -813,11 +814,19 @@ class Classifier(nn.Module):
         arguments are accepted and ignored exactly as far as the reference ignores them: non_pad_mask is recomputed from x, the
         key-pad mask never reaches the softmax (SURVEY.md headline fact 7).  Runs the layer-by-layer kernels (the fused path
         keeps these tensors on chip); inference surface, not differentiable.  Rows of padding QUERIES in ``attn`` are zero
-        (the reference computes a softmax there that nothing reads).  L <= 8: the long forward of model(x) (9 .. 32 columns) returns
-        logits only."""
+        (the reference computes a softmax there that nothing reads).
+
+        Every width model(x) takes, 2 .. 32 columns.  Rows of 9 .. 32 columns (eval mode only: NotImplementedError in train mode -- their
+        dropout lives in the training layout, and no width has a differentiable get_embedding) run the long chain, whose attention kernel
+        writes ``attn`` itself, in this layout, once.  ``attn`` holds 32 * B * L**2 bytes -- 32 KB per row at L = 32, 328 MB for 10 000
+        rows: chunk the input accordingly (predict.attention_maps does)."""
         rt = self._runtime()
         x = torch.as_tensor(x).to(device=rt.device, dtype=torch.long).contiguous()
         B, L = x.shape
+        if L > _lib.MAX_LONG_L:
+            raise ValueError(f"hyperedges wider than {_lib.MAX_LONG_L} are not supported (x has {L} columns)")
+        if L > _lib.MAX_L:
+            return self._get_embedding_long(x, rt, return_recon)
         opts, seed_t = self._opts(rt, return_recon)
         opts.forward_only = 0
         opts.status = rt.status.data_ptr()
@@ -844,6 +853,31 @@ class Classifier(nn.Module):
         # select, do not multiply
         p = torch.where(real.view(B, 1, L, 1), p, torch.zeros((), dtype=p.dtype, device=p.device))
         attn = p.permute(1, 0, 2, 3).reshape(_lib.N_HEAD * B, L, L)
+        if return_recon:
+            return dyn, sta, attn, losses[1:2]
+        return dyn, sta, attn
+
+    def _get_embedding_long(self, x, rt: _Runtime, return_recon: bool):
+        """get_embedding for rows of MAX_L + 1 .. MAX_LONG_L columns: matcha_get_embedding_long on the long forward's workspace.  ``attn`` is
+        allocated once and every element of it is written by attn_long_prob_kernel -- no memset, no gather passes."""
+        if self.training:
+            raise NotImplementedError(
+                f"get_embedding on hyperedges of more than {_lib.MAX_L} nodes is inference-only (x has {x.shape[1]} columns): call model.eval() first")
+        opts, _ = self._opts(rt, return_recon)       # one np.random.choice in adj mode; training = 0, no seed
+        opts.forward_only = 1
+        opts.status = rt.status.data_ptr()
+        B, L = x.shape
+        ws = rt.workspace(B, L, long_rows=True)
+        dyn = torch.empty(B, L, rt.d, dtype=torch.float32, device=rt.device)
+        sta = torch.empty_like(dyn)
+        attn = torch.empty(_lib.N_HEAD * B, L, L, dtype=torch.float32, device=rt.device)
+        losses = torch.zeros(3, dtype=torch.float32, device=rt.device)
+        _lib.check(rt.lib.matcha_get_embedding_long(C.byref(rt.shape), C.byref(rt.params), C.byref(rt.frozen), C.byref(opts), _lib.ptr(x), B, L,
+                                                    _lib.ptr(dyn), _lib.ptr(sta), _lib.ptr(attn), _lib.ptr(losses), _lib.ptr(ws), ws.numel(),
+                                                    rt.stream()),
+                   "matcha_get_embedding_long")
+        if self.check_ids and not torch.cuda.is_current_stream_capturing():
+            rt.check_status("Classifier.get_embedding")
         if return_recon:
             return dyn, sta, attn, losses[1:2]
         return dyn, sta, attn

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MATCHA_HIP_LIB") or os.path.join(_HERE, "lib", "libmatcha_hip.so")   # override: A/B builds
 
 MAX_L = 8
-MAX_LONG_L = 32      # widest row of the long forward (matcha_forward_long), of the long training pair (matcha_forward_long_train / matcha_backward_long)
+MAX_LONG_L = 32      # widest row of the long forward (matcha_forward_long), of matcha_get_embedding_long, of the long training pair (matcha_forward_long_train / matcha_backward_long)
                      # and of the long set / sampler (matcha_hashset_build_long, matcha_hashset_contains_long, matcha_neg_sample_long)
 N_HEAD = 8
 
@@ -82,6 +82,8 @@ SIGNATURES = {
     "matcha_workspace_bytes_long": (_SZ, [C.POINTER(Shape), _I64, _I32]),
     "matcha_forward_long": (C.c_int, [C.POINTER(Shape), C.POINTER(Tensors), C.POINTER(Frozen), C.POINTER(StepOpts), _fp, _I64,
                                       _I32, _fp, _fp, _fp, _SZ, _fp]),
+    "matcha_get_embedding_long": (C.c_int, [C.POINTER(Shape), C.POINTER(Tensors), C.POINTER(Frozen), C.POINTER(StepOpts), _fp, _I64, _I32,
+                                            _fp, _fp, _fp, _fp, _fp, _SZ, _fp]),
     "matcha_workspace_bytes_long_train": (_SZ, [C.POINTER(Shape), _I64, _I32]),
     "matcha_forward_long_train": (C.c_int, [C.POINTER(Shape), C.POINTER(Tensors), C.POINTER(Frozen), C.POINTER(StepOpts), _fp, _I64,
                                             _I32, _fp, _fp, _fp, _SZ, _fp]),

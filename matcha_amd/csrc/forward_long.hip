@@ -1,7 +1,8 @@
-// Rows of up to MATCHA_MAX_LONG_L = 32 columns (include/matcha_hip.h): matcha_forward_long, the inference forward, and the training pair
+// Rows of up to MATCHA_MAX_LONG_L = 32 columns (include/matcha_hip.h): matcha_forward_long, the inference forward, matcha_get_embedding_long,
+// the same chain stopped in front of the classifier head with the attention probabilities written out, and the training pair
 // matcha_forward_long_train / matcha_backward_long.
 //
-// The token-level layers do not care about L: all three entry points run the layer-by-layer chain of layerwise.hip -- the one matcha_forward /
+// The token-level layers do not care about L: all four entry points run the layer-by-layer chain of layerwise.hip -- the one matcha_forward /
 // matcha_backward run at embed_dim != 64 -- on the Tr real tokens + ONE shared padding token of the plan.  What is bound to L <= 8 there has
 // its long counterpart: the plan (ragged_long.hip) and the attention (attention_long.hip, attention_long_bwd.hip; ChainOpts::long_attn).
 // embed_dim a multiple of 64 runs the merged heads (r = qin B_all^T, every head attends the shared rows kin / vin, dyn = Z M_all^T), every
@@ -23,9 +24,7 @@ namespace matcha {
 
 namespace {
 
-struct LongWs : TokenChain {
-  uint32_t* mask;      // the plan's scratch (ragged_long.hip)
-};
+typedef TokenChain LongWs;      // (the plan's scratch `mask` is a field of the chain: the attention's probability instance reads it)
 
 // one bump allocator for both layouts: 256-byte granules, null for a buffer the layout does not have (and while the layout is only being sized)
 struct Bump {
@@ -141,6 +140,36 @@ extern "C" int matcha_forward_long(const matcha_shape* shp, const matcha_tensors
   // (keep off: the padding token's O row, which the attention never writes, still holds the projection's finite row under fc1's row mask)
   MATCHA_TRY(chain_attn_fwd(chain, w));
   return chain_tail_fwd(chain, w, nullptr, nullptr, logits, nullptr, MATCHA_OBJECTIVE_BCE, false);
+}
+
+// Classifier.get_embedding at up to 32 columns: the inference chain up to pff_n1's convolutions (X and H2 live in the inference layout), the
+// attention's probability instance writing the caller's padded `attn` completely (null: the plain kernel), then expand_embedding_kernel.
+extern "C" int matcha_get_embedding_long(const matcha_shape* shp, const matcha_tensors* params, const matcha_frozen* frozen, const matcha_step_opts* opts,
+                                         const int64_t* x, int64_t B, int32_t L, float* dynamic, float* static_, float* attn, float* losses, void* ws,
+                                         size_t ws_bytes, matcha_stream_t stream) {
+  static const char fn[] = "matcha_get_embedding_long";
+  MATCHA_TRY(check_shape_long(shp, B, L, fn));
+  MATCHA_CHECK_ARG(params && frozen && opts && x && ws && dynamic && static_, "%s: null pointer (only attn and losses are optional)", fn);
+  MATCHA_CHECK_ARG(opts->training == 0 && opts->forward_only == 1,
+                   "matcha_get_embedding_long: inference-only (opts->training must be 0 and opts->forward_only 1; got %d, %d)",
+                   (int)opts->training, (int)opts->forward_only);
+  MATCHA_CHECK_ARG(!opts->random_chrom_dev, "matcha_get_embedding_long: opts->random_chrom_dev needs the fused adj front end; pass opts->random_chrom");
+  const matcha_shape& s = *shp;
+  MATCHA_TRY(check_forward_long(s, *params, *frozen, *opts, ws, fn));
+  const bool merged = long_merged(s);
+  LongWs w;
+  const size_t need = carve_long(s, B, L, (char*)ws, w, merged);
+  MATCHA_CHECK_ARG(ws_bytes >= need, "matcha_get_embedding_long: workspace %zu < %zu bytes", ws_bytes, need);
+  hipStream_t st = (hipStream_t)stream;
+  const ChainCall chain{s, *params, *frozen, *opts, B, L, st, {merged, true, false}, fn};
+  w.P = attn;              // the caller's [8 B, L, L]: chain_attn_fwd launches attn_long_prob_kernel when it is there
+
+  forget_forward(ws);
+  MATCHA_TRY(launch_long_plan(x, B, L, s.n_nodes, opts->status, w.rg, w.mask, st));
+  MATCHA_TRY(chain_front_fwd(chain, w, losses ? losses + 1 : nullptr, true));
+  MATCHA_TRY(chain_attn_fwd(chain, w));
+  MATCHA_TRY(chain_tail_fwd(chain, w, nullptr, nullptr, nullptr, nullptr, MATCHA_OBJECTIVE_BCE, true));
+  return launch_expand_embedding(x, B, L, s.d, w.rg.row_off, w.H2, w.X, params->pff_ln_g, params->pff_ln_b, dynamic, static_, st);
 }
 
 extern "C" size_t matcha_workspace_bytes_long_train(const matcha_shape* shp, int64_t B, int32_t L) {

@@ -282,8 +282,10 @@ void long_plan_carve(int64_t B, int L, char* base, Ragged& r, uint32_t** mask);
 int launch_long_plan(const int64_t* x, int64_t B, int L, int64_t n_nodes, int32_t* status, const Ragged& r, uint32_t* mask, hipStream_t st);
 // attention_long.hip: per-hyperedge attention for k <= 32 real tokens, one wavefront per (hyperedge, head), O may alias Q.  kv_ld / kv_head: row
 // stride and per-head offset of K and V (8 d and d for per-head rows; d and 0 for the merged heads' shared key / value rows)
+// attn != null: attn_long_prob_kernel instead -- the same O, and the probabilities in the reference's padded [8 B, L, L] layout, every element
+// written (mask: the plan's column sets)
 int launch_attn_long(const float* Q, const float* K, const float* V, const int32_t* row_off, int64_t B, int L, int d, int64_t kv_ld, int kv_head,
-                     float* O, hipStream_t st);
+                     float* O, hipStream_t st, const uint32_t* mask = nullptr, float* attn = nullptr);
 // attention_long_bwd.hip: its backward on the same two operand forms; P is recomputed from Q and K.  dK / dV have K / V's layout (merged heads:
 // the sums over the heads [T, d], written by the kernel); the padding token's rows are summed through `slab` (attn_long_bwd_slab_bytes), dQ[Tr] = 0
 size_t attn_long_bwd_slab_bytes(int64_t B, int d);

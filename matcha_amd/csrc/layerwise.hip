@@ -177,8 +177,9 @@ int chain_attn_fwd(const ChainCall& c, const TokenChain& w) {
   nan_check("V", w.V, cnt, 0, hd, c.st);
   // merged heads: every head attends the shared rows kin / vin, O = Z = P . vin per head
   if (c.c.long_attn) {
-    if (c.c.merged) MATCHA_TRY(launch_attn_long(w.Q, w.kin, w.vin, w.rg.row_off, B, L, d, d, 0, w.O, c.st));
-    else MATCHA_TRY(launch_attn_long(w.Q, w.K, w.V, w.rg.row_off, B, L, d, hd, d, w.O, c.st));
+    // (w.P, null in every long layout, is the caller's padded attention tensor when matcha_get_embedding_long set it: the kernel's other instance)
+    if (c.c.merged) MATCHA_TRY(launch_attn_long(w.Q, w.kin, w.vin, w.rg.row_off, B, L, d, d, 0, w.O, c.st, w.mask, w.P));
+    else MATCHA_TRY(launch_attn_long(w.Q, w.K, w.V, w.rg.row_off, B, L, d, hd, d, w.O, c.st, w.mask, w.P));
     // that attention writes the real tokens' O rows only.  The padding token's row feeds fc1 under a row mask -- which selects zero whatever
     // finite row stands there (without `keep`: the projection's) -- and, with a backward, dM / dWfc1 as a factor of a zero gradient row
     if (c.c.keep) MATCHA_TRY(launch_long_zero_row(w.O, w.rg.row_off + B, hd, c.st));

@@ -2,7 +2,7 @@
 // fc1, pff_n1 and the classifier head, and their backward, as a fixed sequence of launches over the Tr real tokens + ONE shared padding token
 // of a plan.  Every entry point that runs the chain calls these pieces on a TokenChain filled by its own workspace layout:
 //   matcha_forward / matcha_backward off the fused embed_dim-64 route and matcha_get_embedding (model.hip: Workspace, rows of up to 8 columns),
-//   matcha_forward_long, matcha_forward_long_train / matcha_backward_long (forward_long.hip: LongWs, rows of up to 32).
+//   matcha_forward_long, matcha_get_embedding_long, matcha_forward_long_train / matcha_backward_long (forward_long.hip: LongWs, rows of up to 32).
 // What differs between them -- the plan, the attention kernels, which buffers alias which -- stays with the caller; the forward record per
 // workspace pointer (StepRoute) is shared too, so a forward of either kind voids what the other left on the same pointer.
 #pragma once
@@ -26,7 +26,9 @@ size_t adj_workspace_bytes(const matcha_shape& s, int64_t T);
 // forward_long.hip: carve_long, carve_long_train); a buffer the layout does not have is null.
 struct TokenChain {
   Ragged rg;
-  // saved by the forward (merged heads: Q holds r, O holds Z, every head attends the shared rows kin / vin; P: the short attention's probabilities)
+  // saved by the forward (merged heads: Q holds r, O holds Z, every head attends the shared rows kin / vin; P: the short attention's probabilities
+  // [B, 8, L, L] in the workspace -- under long_attn, where no layout keeps them, null or the CALLER's padded [8 B, L, L] tensor, which
+  // attn_long_prob_kernel then fills completely (matcha_get_embedding_long))
   float *x0, *X, *qin, *kin, *vin, *stats, *Q, *K, *V, *P, *O, *Y, *H1, *H2, *row_loss, *logits, *node;
   // the backward's
   float *dH2, *dXs, *dZ1, *ddyn0, *dO, *dQ, *dK, *dV, *dqin, *dkin, *dvin, *dZ0, *dX0;
@@ -35,12 +37,13 @@ struct TokenChain {
   void* adj_ws;     size_t adj_ws_bytes;
   void* tg_ws;      size_t tg_ws_bytes;   // table mode: sort scratch of the deterministic table gradient (table_grad.hip)
   float *lwB, *lwM, *lwdB, *lwdM;         // merged heads: B_all [8d, d], M_all [d, 8d] and their gradients
+  uint32_t* mask;                         // long rows: the plan's scratch, a row's real columns as a bit set [B] (ragged_long.hip); read under long_attn only
 };
 
 // What the call sites differ in.
 struct ChainOpts {
   bool merged;      // merged heads (r = qin B_all^T, dyn = Z M_all^T: two products per head) instead of the reference's four
-  bool long_attn;   // attention_long.hip / attention_long_bwd.hip (k <= 32, no P) instead of attention.hip / attention_wide.hip (k <= 8, P kept).
+  bool long_attn;   // attention_long.hip / attention_long_bwd.hip (k <= 32, no P kept) instead of attention.hip / attention_wide.hip (k <= 8, P kept).
                     // A flag of its own, not L > 8: the long entry points take L from 2
   bool keep;        // a backward follows: activations are kept.  With long_attn the padding token's O row -- which that attention does not write, and
                     // which then feeds dM / dWfc1 as a factor of a zero gradient row -- is zeroed; a layout whose O lies over Q must not ask for it

@@ -15,6 +15,7 @@ CLI:  python -m matcha_amd.predict multiway -i interactions.txt -o output.txt
       python -m matcha_amd.predict kway --chrom 0 --k 3 --top 1000 [--start-bin A --end-bin B] [--exclude-known] -o top.tsv
       python -m matcha_amd.predict anchored --k 3 --top 20 --chrom 5 (--anchor-file loci.tsv | --anchor-chrom 0) -o anchored.tsv
       python -m matcha_amd.predict kmap --chrom 0 --k 3 [--start-bin A --end-bin B] [--threshold 0.5] [--exclude-known] -o map.npz
+      python -m matcha_amd.predict attention -i interactions.txt -o attn.npz [--per-head]
 (all read ./config.JSON like the reference: temp_dir, resolution, chrom_list, min_distance).
 
 * ``kway`` -- the de novo sweep of matcha_amd/sweep.py: every candidate of size k in one chromosome (or a window of its bins)
@@ -24,6 +25,8 @@ CLI:  python -m matcha_amd.predict multiway -i interactions.txt -o output.txt
 * ``kmap`` -- the pair map of matcha_amd/sweep.py: the probabilities of ALL candidates of size k of one chromosome (or bin window)
   projected onto pairs of bins -- per pair the summed probability, the mean, the best candidate, the number of candidates and the
   number at or above ``--threshold`` -- written as one .npz of [n, n] matrices.
+* ``attention`` -- ``attention_maps``: the lines of ``multiway``'s input (2 to 32 loci each), scored in the same chunks, and per line the
+  k x k block of attention probabilities among its loci (``Classifier.get_embedding``), mean over the heads, as one .npz.
 """
 from __future__ import annotations
 
@@ -93,6 +96,50 @@ def predict_multiway(model, filepath: str, bin2node: Dict[str, int], chrom_list:
     if output is not None:
         np.savetxt(output, proba)
     return samples, proba
+
+
+def block_offsets(sizes: np.ndarray) -> np.ndarray:
+    """int64 [n + 1]: where row i's k_i x k_i block starts in the ragged ``attn_mean`` of ``attention_maps`` (offsets[n]: its length)."""
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1)
+    return np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum(sizes * sizes)])
+
+
+def attention_maps(model, samples, batch_size: int = CHUNK_ROWS, per_head: bool = False) -> Dict[str, np.ndarray]:
+    """Which nodes of a hyperedge attend to which: the attention probabilities of ``model.get_embedding`` on a list / array of hyperedges of
+    2 .. 32 nodes, reduced to the rows' REAL slots.  Chunks of ``batch_size`` rows, each zero-padded to ITS longest row exactly as ``predict``
+    does it: padding slots are attended keys, so a row's probabilities depend on its chunk's width, and a row's block sums to less than 1 per
+    query by what its pads received.  Returns numpy arrays
+
+      sizes     int64 [n]        k_i, the nodes of row i
+      offsets   int64 [n + 1]    block i is attn_mean[offsets[i]:offsets[i + 1]].reshape(k_i, k_i)
+      attn_mean float32          the ragged blocks, row-major (query, key), mean over the eight heads
+      attn_heads float32         per_head only: block i is attn_heads[8 * offsets[i]:8 * offsets[i + 1]].reshape(8, k_i, k_i)
+
+    The head mean and the selection of the real slots run on the device, chunk by chunk; only the blocks come back.  A row of more than 32
+    nodes raises ValueError naming it, before anything is scored."""
+    U.check_row_sizes(samples, _lib.MAX_LONG_L)
+    sizes, mean, heads = [], [], []
+    if len(samples):
+        model.eval()
+        dev = model.layer_norm1.weight.device
+        with torch.no_grad():
+            for j in range(0, len(samples), batch_size):
+                x = U.pad_rows(samples[j:j + batch_size]).to(dev)
+                B, L = x.shape
+                attn = model.get_embedding(x)[2].view(_lib.N_HEAD, B, L, L)
+                real = x != 0
+                pair = real.unsqueeze(2) & real.unsqueeze(1)                      # [B, L, L]: real query x real key
+                sizes.append(real.sum(1).cpu().numpy().astype(np.int64))
+                mean.append(attn.mean(0)[pair].cpu().numpy())                     # (b, query, key) order: row-major blocks, row after row
+                if per_head:
+                    heads.append(attn.permute(1, 0, 2, 3)[pair.unsqueeze(1).expand(B, _lib.N_HEAD, L, L)].cpu().numpy())
+    cat = lambda parts, dt: np.concatenate(parts) if parts else np.zeros(0, dtype=dt)
+    out = {"sizes": cat(sizes, np.int64)}
+    out["offsets"] = block_offsets(out["sizes"])
+    out["attn_mean"] = cat(mean, np.float32)
+    if per_head:
+        out["attn_heads"] = cat(heads, np.float32)
+    return out
 
 
 def generate_pair_wise(chrom_range, chrom_id: int, min_dis: int, device=None) -> torch.Tensor:
@@ -334,6 +381,11 @@ def main(argv=None):
     e.add_argument("--task-mode", choices=["class", "regress"], default="class", help="the model's training objective: sigmoid or softplus outputs")
     e.add_argument("--value-max", type=float, default=None, help="task-mode regress: the largest value a candidate may contribute (<= 2^20)")
     e.add_argument("-o", "--output", type=str, default="./kmap.npz")
+    g = sub.add_parser("attention", help="attention maps: per interaction of a text file, the head-mean attention among its loci")
+    g.add_argument("-i", "--file", type=str, required=True)
+    g.add_argument("-o", "--output", type=str, default="./attn.npz")
+    g.add_argument("--per-head", action="store_true", help="also write the eight heads' blocks (attn_heads)")
+    g.add_argument("--config", type=str, default="./config.JSON")
     d.add_argument("--config", type=str, default="./config.JSON")
     for q in (a, b, c, e):
         q.add_argument("--config", type=str, default="./config.JSON")
@@ -345,6 +397,12 @@ def main(argv=None):
         return _anchored(args, config, temp_dir, model)
     if args.cmd == "kmap":
         return _kmap(args, config, temp_dir, model)
+    if args.cmd == "attention":
+        bin2node = np.load(os.path.join(temp_dir, "bin2node.npy"), allow_pickle=True).item()
+        samples = parse_file(args.file, bin2node, config["chrom_list"], config["resolution"], max_size=_lib.MAX_LONG_L)
+        np.savez(args.output, **attention_maps(model, samples, per_head=args.per_head))
+        print("%d interactions -> %s" % (len(samples), args.output))
+        return
     if args.cmd == "multiway":
         bin2node = np.load(os.path.join(temp_dir, "bin2node.npy"), allow_pickle=True).item()
         samples, proba = predict_multiway(model, args.file, bin2node, config["chrom_list"], config["resolution"], args.output)
