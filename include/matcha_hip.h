@@ -712,6 +712,27 @@ int matcha_segtopk_update(void* state, size_t bytes, int64_t A, int32_t K, int64
 int matcha_segtopk_read(const void* state, size_t bytes, int64_t A, int32_t K, int64_t seg_len, int64_t max_chunk, float* scores_out,
                         int64_t* ranks_out, int64_t* counts_out, matcha_stream_t stream);
 
+/* ---- cluster completion -------------------------------------------------------------------------------
+ * Which further bins best extend clusters of 1 to 31 loci: the anchored sweep's candidates for ragged anchors and rows of up to
+ * MATCHA_MAX_LONG_L columns.  A cluster table is int64 [A, S], 1 <= S <= 31; row a holds s_a non-zero node ids followed by zeros,
+ * 0 <= s_a <= S: the leading non-zero run is read, entries behind the first zero are ignored.  The free part is a candidate of size
+ * f, 1 <= f <= 8, of the partner region [lo, lo + n) under the rule above (C_f values, ranked lexicographically from 0); the global
+ * rank is g = a C_f + r, 0 <= g < A C_f < 2^63.  The candidate is the s_a + f ids sorted ascending (duplicates kept), zero-padded to
+ * L, S + f <= L <= 32.  It is valid iff s_a >= 1, the cluster's own ids are non-descending and every adjacent difference is
+ * >= min_gap.  Invalid candidates keep their rank and their row; a flag marks them.  A row with s_a = 0 is the free part alone,
+ * flagged; a cluster row that descends somewhere leaves unmerged (its ids in their order, then the free ids), flagged.
+ * matcha_kway_complete_count  host only: A C_f, or -1 for invalid arguments (A < 0, S outside [1, 31], n < 1, f outside [1, 8],
+ *     min_gap < 1) or a total >= 2^63.
+ * matcha_kway_complete_rows   clusters device int64 [A, S]; writes x, device int64 [count, L], and flag, device int32 [count]
+ *     (non-zero = invalid): row i is the candidate of global rank rank0 + i (ranks == NULL; the range must lie inside [0, A C_f),
+ *     else refused) or ranks[i] (device int64 [count]; a rank outside [0, A C_f) gives an all-zero row with its flag set).
+ *     count = 0 launches nothing.  Every refusal is MATCHA_EINVAL with a message, before any device call; caller-owned memory,
+ *     asynchronous on the caller's stream, no allocation, no memset, no read-back.  Selection: matcha_segtopk_* with seg_len = C_f. */
+int64_t matcha_kway_complete_count(int64_t A, int32_t S, int32_t n, int32_t f, int32_t min_gap);
+int matcha_kway_complete_rows(const int64_t* clusters, int64_t A, int32_t S, int64_t lo, int32_t n, int32_t f, int32_t min_gap,
+                              int64_t rank0, const int64_t* ranks, int64_t count, int32_t L, int64_t* x, int32_t* flag,
+                              matcha_stream_t stream);
+
 /* ---- k-way pair maps -----------------------------------------------------------------------------------
  * The values of k-way rows projected onto pairs of node ids and accumulated on the device.  A map covers the row region
  * R = [lo_r, lo_r + n_r) and the column region C = [lo_c, lo_c + n_c): R == C (symmetric) or R and C disjoint (rectangular); any

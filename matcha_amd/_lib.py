@@ -151,6 +151,8 @@ SIGNATURES = {
     "matcha_segtopk_init": (C.c_int, [_fp, _SZ, _I64, _I32, _I64, _I64, _fp]),
     "matcha_segtopk_update": (C.c_int, [_fp, _SZ, _I64, _I32, _I64, _I64, _I64, _fp, _fp, _I64, _I64, _fp]),
     "matcha_segtopk_read": (C.c_int, [_fp, _SZ, _I64, _I32, _I64, _I64, _fp, _fp, _fp, _fp]),
+    "matcha_kway_complete_count": (_I64, [_I64, _I32, _I32, _I32, _I32]),
+    "matcha_kway_complete_rows": (C.c_int, [_fp, _I64, _I32, _I64, _I32, _I32, _I32, _I64, _fp, _I64, _I32, _fp, _fp, _fp]),
     "matcha_pairmap_bytes": (_SZ, [_I64, _I32, _I64, _I32, _I32, _F, _F]),
     "matcha_pairmap_init": (C.c_int, [_fp, _SZ, _I64, _I32, _I64, _I32, _I32, _F, _F, _fp]),
     "matcha_pairmap_update": (C.c_int, [_fp, _SZ, _I64, _I32, _I64, _I32, _I32, _F, _F, _fp, _fp, _fp, _I64, _I32, _fp]),

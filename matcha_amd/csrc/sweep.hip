@@ -736,3 +736,171 @@ extern "C" int matcha_segtopk_read(const void* state, size_t bytes, int64_t A, i
   MATCHA_CHECK_LAUNCH("segtopk_read_kernel");
   return MATCHA_OK;
 }
+
+// ==== cluster completion =============================================================================================
+// Which further bins best extend clusters of 1 to 31 loci.  A cluster table is int64 [A, S], 1 <= S <= 31: row a holds s_a non-zero ids
+// followed by zeros; only the leading non-zero run is read.  The free part is a candidate of size f (1 <= f <= 8) of the partner region
+// under the rule above, the global rank g = a C_f + r as in the anchored sweep.  The candidate is the s_a + f ids sorted ascending
+// (duplicates kept, a cluster id before an equal free id), zero-padded to L, S + f <= L <= 32.  It is valid iff s_a >= 1, the cluster's
+// own ids are non-descending and every adjacent difference of the row is >= min_gap.  The free part keeps the gap by construction, so
+// the test is: every cluster id against its predecessor in the cluster (v < prev, or v - prev < min_gap unsigned) and against every free
+// id (|v - free| < min_gap) -- a pair closer than the gap has an adjacent pair closer than the gap between them, and the reverse.  A
+// cluster row that descends somewhere cannot be merged by counting; its ids leave in their order with the free ids behind them, flagged.
+//
+//   kway_complete_rows_kernel  a wavefront serves 64 consecutive ranks.  Each lane divides and unranks ONE of them (free ids relative to
+//                              lo, int32).  Then the two 32-lane halves walk the 64 rows, one row each per step: the row's owner
+//                              broadcasts its cluster index and free ids (__shfl), lane j < S reads cluster id j (consecutive ranks share
+//                              the cluster: a cache hit), s_a is the first zero of a ballot.  Lane j < s_a writes its id to column
+//                              j + #(free ids below it), lane s_a + i writes free id i to column i + #(cluster ids <= it) -- a popcount of
+//                              a ballot --, the lanes behind write the zero padding: one store instruction per row, its lanes covering one
+//                              contiguous run of 8 L bytes.  No LDS, no scratch.  Every shuffle and ballot is executed by all 64 lanes:
+//                              a half without a row, or a lane without an id, is predicated, never branched around (the step count is
+//                              the same for the whole wavefront).  Flags are collected in the owner lanes and leave as one coalesced run.
+namespace matcha {
+namespace {
+
+constexpr int kMaxWide = MATCHA_MAX_LONG_L;    // the widest row: S + f <= L <= 32
+
+bool complete_args_ok(int64_t A, int32_t S, int32_t n, int32_t f, int32_t min_gap) {
+  return A >= 0 && S >= 1 && S <= kMaxWide - 1 && n >= 1 && f >= 1 && f <= kMaxK && min_gap >= 1;
+}
+
+// A C_f, -1 for invalid arguments or a total >= 2^63; *cf_out = C_f
+int64_t complete_count(int64_t A, int32_t S, int32_t n, int32_t f, int32_t min_gap, int64_t* cf_out) {
+  if (!complete_args_ok(A, S, n, f, min_gap)) return -1;
+  const int64_t cf = free_count(n, f, min_gap);
+  if (cf < 0) return -1;
+  const unsigned __int128 total = (unsigned __int128)(uint64_t)A * (uint64_t)cf;
+  if (total >= ((unsigned __int128)1 << 63)) return -1;
+  if (cf_out) *cf_out = cf;
+  return (int64_t)total;
+}
+
+__device__ __forceinline__ int64_t shfl64(int64_t v, int src) {
+  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src), hi = (uint32_t)__shfl((int)((uint64_t)v >> 32), src);
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+__global__ __launch_bounds__(kRowsPerBlock) void kway_complete_rows_kernel(const int64_t* __restrict__ clusters, int32_t S, int64_t lo, int32_t m, int32_t f,
+                                                                           int32_t slack, int32_t min_gap, uint64_t cf, uint64_t total, int64_t rank0,
+                                                                           const int64_t* __restrict__ ranks, int64_t count, int32_t L,
+                                                                           int64_t* __restrict__ x, int32_t* __restrict__ flag) {
+  const int lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31;
+  const int64_t wave0 = (int64_t)(threadIdx.x >> 6) * 64;
+  const uint64_t gap = (uint64_t)min_gap;
+  for (int64_t base = (int64_t)blockIdx.x * kRowsPerBlock; base < count; base += (int64_t)gridDim.x * kRowsPerBlock) {
+    const int64_t w0 = base + wave0;                                   // the wavefront's first row; the same in all its lanes
+    const int64_t left = count - w0;
+    const int steps = left >= 64 ? 32 : left > 0 ? (int)((left + 1) >> 1) : 0;
+    // ---- one rank per lane: cluster index and free ids ----
+    const int64_t i = w0 + lane;
+    const int64_t g = i < count ? (ranks ? ranks[i] : rank0 + i) : -1;
+    const int ok = g >= 0 && (uint64_t)g < total;                      // total > 0 then, so cf > 0
+    uint64_t a = 0;
+    int32_t fid[kMaxK] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (ok) {
+      uint64_t r;
+      if (((uint64_t)g | cf) >> 32) {                                  // the one 64-bit division of the row
+        a = (uint64_t)g / cf;
+        r = (uint64_t)g - a * cf;
+      } else {
+        const uint32_t a32 = (uint32_t)g / (uint32_t)cf;
+        a = a32;
+        r = (uint32_t)g - a32 * (uint32_t)cf;
+      }
+      unrank(r, cf, m, f, fid);
+#pragma unroll
+      for (int c = 0; c < kMaxK; ++c) fid[c] += c * slack;              // < n: relative to lo
+    }
+    // ---- two rows per step, one per half ----
+    int bad_mine = 1;
+    for (int t = 0; t < steps; ++t) {
+      const int own = 2 * t + h;                                       // the lane that unranked this half's row
+      const int64_t irow = w0 + own;
+      const int ok0 = __shfl(ok, 2 * t), ok1 = __shfl(ok, 2 * t + 1);
+      const int ok_r = h ? ok1 : ok0;
+      const uint64_t a_r = (uint64_t)shfl64((int64_t)a, own);
+      int64_t fv[kMaxK];
+#pragma unroll
+      for (int c = 0; c < kMaxK; ++c) {
+        fv[c] = 0;
+        if (c < f) fv[c] = lo + (int64_t)__shfl(fid[c], own);           // f is a kernel argument: the same branch in every lane
+      }
+      int64_t v = 0;
+      if (ok_r && j < S) v = clusters[a_r * (uint64_t)S + (uint64_t)j];
+      const uint64_t zb = __ballot(v == 0);                            // lane 31 of a half never holds an id (S <= 31): ctz is defined
+      const int s0 = __builtin_ctz((uint32_t)zb | 0x80000000u), s1 = __builtin_ctz((uint32_t)(zb >> 32) | 0x80000000u);
+      const int s = h ? s1 : s0;
+      const bool mine = j < s;
+      const int64_t prev = shfl64(v, j ? lane - 1 : lane);
+      const bool desc = mine && j > 0 && v < prev;
+      bool close = mine && j > 0 && (uint64_t)v - (uint64_t)prev < gap;
+      int below = 0;
+#pragma unroll
+      for (int c = 0; c < kMaxK; ++c) {
+        if (c < f) {
+          below += fv[c] < v ? 1 : 0;
+          const uint64_t dist = v >= fv[c] ? (uint64_t)v - (uint64_t)fv[c] : (uint64_t)fv[c] - (uint64_t)v;   // exact for any int64 ids
+          close |= mine && dist < gap;
+        }
+      }
+      const uint64_t db = __ballot(desc);
+      const bool merge = (uint32_t)(db >> (32 * h)) == 0;              // the cluster's ids are non-descending
+      int64_t val = mine ? v : 0;
+      int col = (mine && merge) ? j + below : j;
+#pragma unroll
+      for (int c = 0; c < kMaxK; ++c) {
+        if (c < f) {
+          const uint64_t le = __ballot(mine && v <= fv[c]);
+          const int n_le = __popc((uint32_t)(le >> (32 * h)));
+          if (j - s == c) {
+            val = fv[c];
+            col = merge ? c + n_le : j;
+          }
+        }
+      }
+      if (!ok_r) { val = 0; col = j; }
+      const uint64_t bb = __ballot(desc || close);
+      const int bad0 = !ok0 || s0 == 0 || (uint32_t)bb != 0, bad1 = !ok1 || s1 == 0 || (uint32_t)(bb >> 32) != 0;
+      if (lane == 2 * t) bad_mine = bad0;
+      if (lane == 2 * t + 1) bad_mine = bad1;
+      if (irow < count && j < L && col < L) x[irow * L + col] = val;
+    }
+    if (i < count) flag[i] = bad_mine;
+  }
+}
+
+}  // namespace
+}  // namespace matcha
+
+extern "C" int64_t matcha_kway_complete_count(int64_t A, int32_t S, int32_t n, int32_t f, int32_t min_gap) {
+  return complete_count(A, S, n, f, min_gap, nullptr);
+}
+
+extern "C" int matcha_kway_complete_rows(const int64_t* clusters, int64_t A, int32_t S, int64_t lo, int32_t n, int32_t f, int32_t min_gap, int64_t rank0,
+                                         const int64_t* ranks, int64_t count, int32_t L, int64_t* x, int32_t* flag, matcha_stream_t stream) {
+  MATCHA_CHECK_ARG(complete_args_ok(A, S, n, f, min_gap),
+                   "matcha_kway_complete_rows: need A >= 0, 1 <= S <= %d, n >= 1, 1 <= f <= %d, min_gap >= 1 (A=%lld S=%d n=%d f=%d min_gap=%d)", kMaxWide - 1,
+                   kMaxK, (long long)A, S, n, f, min_gap);
+  MATCHA_CHECK_ARG(L >= S + f && L <= kMaxWide, "matcha_kway_complete_rows: row width L=%d must be in [S + f, %d]", L, kMaxWide);
+  MATCHA_CHECK_ARG(lo >= 0 && lo <= ((int64_t)1 << 62), "matcha_kway_complete_rows: lo out of range");
+  int64_t cf = 0;
+  const int64_t total = complete_count(A, S, n, f, min_gap, &cf);
+  MATCHA_CHECK_ARG(total >= 0, "matcha_kway_complete_rows: A C_f does not fit 63 bits (A=%lld n=%d f=%d min_gap=%d)", (long long)A, n, f, min_gap);
+  MATCHA_CHECK_ARG(count >= 0 && count <= ((int64_t)1 << 40), "matcha_kway_complete_rows: count out of range");
+  if (!ranks)
+    MATCHA_CHECK_ARG(rank0 >= 0 && rank0 <= total && count <= total - rank0,
+                     "matcha_kway_complete_rows: %lld ranks from %lld lie outside [0, %lld)", (long long)count, (long long)rank0, (long long)total);
+  if (count == 0) return MATCHA_OK;
+  MATCHA_CHECK_ARG(x && flag, "matcha_kway_complete_rows: null output");
+  MATCHA_CHECK_ARG(clusters || total == 0, "matcha_kway_complete_rows: null clusters");
+  const int32_t slack = min_gap - 1;
+  const int64_t m64 = (int64_t)n - (int64_t)(f - 1) * slack;
+  const int32_t m = m64 > 0 ? (int32_t)m64 : 0;
+  int64_t blocks = cdiv(count, kRowsPerBlock);
+  if (blocks > (1 << 20)) blocks = 1 << 20;
+  hipLaunchKernelGGL(kway_complete_rows_kernel, dim3((unsigned)blocks), dim3(kRowsPerBlock), 0, (hipStream_t)stream, clusters, S, lo, m, f, slack, min_gap,
+                     (uint64_t)cf, (uint64_t)total, rank0, ranks, count, L, x, flag);
+  MATCHA_CHECK_LAUNCH("kway_complete_rows_kernel");
+  return MATCHA_OK;
+}

@@ -14,6 +14,7 @@ CLI:  python -m matcha_amd.predict multiway -i interactions.txt -o output.txt
       python -m matcha_amd.predict pairwise --chrom 0 -o chr1_proba.npy
       python -m matcha_amd.predict kway --chrom 0 --k 3 --top 1000 [--start-bin A --end-bin B] [--exclude-known] -o top.tsv
       python -m matcha_amd.predict anchored --k 3 --top 20 --chrom 5 (--anchor-file loci.tsv | --anchor-chrom 0) -o anchored.tsv
+      python -m matcha_amd.predict complete -i clusters.txt --chrom 5 [--free 1] --top 20 [--width W] [--exclude-known] -o complete.tsv
       python -m matcha_amd.predict kmap --chrom 0 --k 3 [--start-bin A --end-bin B] [--threshold 0.5] [--exclude-known] -o map.npz
       python -m matcha_amd.predict attention -i interactions.txt -o attn.npz [--per-head]
 (all read ./config.JSON like the reference: temp_dir, resolution, chrom_list, min_distance).
@@ -22,6 +23,9 @@ CLI:  python -m matcha_amd.predict multiway -i interactions.txt -o output.txt
   with adjacent gaps > min_distance, scored on the device, the best ``--top`` written as ``chrom:start`` items and a probability.
 * ``anchored`` -- the anchored sweep of matcha_amd/sweep.py: for every anchor (a line of ``--anchor-file``, or every bin of
   ``--anchor-chrom``) the best ``--top`` candidates of size k that contain it, the other nodes taken from ``--chrom``.
+* ``complete`` -- cluster completion (matcha_amd/sweep.py): for every line of ``-i``, a cluster of 1 to 31 loci, the
+  best ``--top`` bins (or sets of ``--free`` bins) of ``--chrom`` to add to it; per kept candidate the cluster's line number, the
+  added loci and the probability.
 * ``kmap`` -- the pair map of matcha_amd/sweep.py: the probabilities of ALL candidates of size k of one chromosome (or bin window)
   projected onto pairs of bins -- per pair the summed probability, the mean, the best candidate, the number of candidates and the
   number at or above ``--threshold`` -- written as one .npz of [n, n] matrices.
@@ -332,6 +336,79 @@ def _anchored(args, config, temp_dir, model):
           % (len(anchors), out["n_candidates"], out["n_invalid"], out["n_excluded"], int(count.sum()), args.output))
 
 
+def parse_cluster_file(filepath: str, bin2node: Dict[str, int], chrom_list: Sequence[str], res: int, free: int = 1) -> Tuple[List[List[int]], List[int]]:
+    """(clusters, line numbers): one cluster per line, 1 to 31 tab-separated ``chrom:position`` loci with parse_file's coordinate
+    handling (items of unknown chromosomes are skipped, positions floored to their bin, node ids de-duplicated and sorted; an item
+    without ``:`` raises EOFError, an unknown bin KeyError).  Lines may differ in length; a line that leaves no locus is dropped.  A
+    line with more than 31 distinct bins, or with more than 32 - free, raises ValueError naming its 1-based number."""
+    most = min(_lib.MAX_LONG_L - 1, _lib.MAX_LONG_L - int(free))
+    clusters, lines = [], []
+    with open(filepath, "r") as f:
+        for lineno, line in enumerate(f, 1):
+            if not line.strip():
+                continue
+            temp = []
+            for info in line.strip().split("\t"):
+                try:
+                    chrom, bin_ = info.split(":")
+                except ValueError:
+                    raise EOFError(info)
+                if chrom not in chrom_list:
+                    continue
+                b = int(math.floor(int(bin_) / res)) * res
+                temp.append(bin2node["%s:%d" % (chrom, b)])
+            temp = sorted(set(temp))
+            if len(temp) > most:
+                raise ValueError("%s: line %d has %d distinct bins: a cluster completed by %d free bin(s) holds at most %d"
+                                 % (filepath, lineno, len(temp), int(free), most))
+            if temp:
+                clusters.append(temp)
+                lines.append(lineno)
+    return clusters, lines
+
+
+def _complete(args, config, temp_dir, model):
+    from . import sweep as SW
+    from .sampler import HyperedgeSet
+    if not 1 <= args.free <= _lib.MAX_L:
+        raise ValueError("--free must be in 1 .. %d" % _lib.MAX_L)
+    chrom_range = np.load(os.path.join(temp_dir, "chrom_range.npy"))
+    node2bin = np.load(os.path.join(temp_dir, "node2bin.npy"), allow_pickle=True).item()
+    bin2node = {v: key for key, v in node2bin.items()}
+    clusters, lines = parse_cluster_file(args.file, bin2node, config["chrom_list"], config["resolution"], args.free)      # before anything is scored
+    c_lo, c_hi = int(chrom_range[args.chrom][0]), int(chrom_range[args.chrom][1])
+    lo = c_lo + (args.start_bin if args.start_bin is not None else 0)
+    hi = c_lo + args.end_bin if args.end_bin is not None else c_hi
+    if not c_lo <= lo <= hi <= c_hi:
+        raise ValueError("the bin window [%s, %s) is not inside chromosome %d (%d bins)" % (args.start_bin, args.end_bin, args.chrom, c_hi - c_lo))
+    dev = model.layer_norm1.weight.device
+    exclude = None
+    if args.exclude_known:      # a candidate of a cluster of s loci has s + free: every size present, one set (rows of all sizes share a table)
+        known = []
+        for k in sorted({len(c) + args.free for c in clusters}):
+            path = os.path.join(temp_dir, "all_%d_counter.npy" % k)
+            if os.path.exists(path):
+                rows = np.load(path).astype(np.int64).reshape(-1, k)
+                known.append(np.pad(rows, ((0, 0), (0, _lib.MAX_LONG_L - k))))
+        if not known:
+            raise FileNotFoundError("--exclude-known: no all_<k>_counter.npy in %s for the candidate sizes of %s" % (temp_dir, args.file))
+        exclude = HyperedgeSet(torch.from_numpy(np.concatenate(known)).to(dev))
+    table = np.zeros((len(clusters), max([len(c) for c in clusters] + [1])), dtype=np.int64)
+    for a, c in enumerate(clusters):
+        table[a, :len(c)] = c
+    out = SW.completion_sweep(model, table, lo, hi, free=args.free, min_gap=int(config["min_distance"]) + 1, top=args.top,
+                              chunk_rows=args.chunk_rows, width=args.width, exclude=exclude, task_mode=args.task_mode)
+    rows, added, proba, count = out["rows"].cpu().numpy(), out["added"].cpu().numpy(), out["proba"].cpu().numpy(), out["count"].cpu().numpy()
+    with open(args.output, "w") as f:
+        for a in range(len(clusters)):
+            for ids, p in zip(added[a, :count[a]], proba[a, :count[a]]):
+                f.write("\t".join([str(lines[a])] + [node2bin[int(v)] for v in ids] + [repr(float(p))]) + "\n")
+    np.savez(os.path.splitext(args.output)[0] + ".npz", clusters=table, rows=rows, added=added, logit=out["logit"].cpu().numpy(), proba=proba,
+             rank=out["rank"].cpu().numpy(), count=count)
+    print("%d anchors, %d candidates (%d against the gap rule, %d known, skipped) -> %d in %s"
+          % (len(clusters), out["n_candidates"], out["n_invalid"], out["n_excluded"], int(count.sum()), args.output))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="inference consumers of a trained MATCHA classifier on the MI355X path")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -369,6 +446,19 @@ def main(argv=None):
     d.add_argument("--chunk-rows", type=int, default=1 << 20)
     d.add_argument("--task-mode", choices=["class", "regress"], default="class", help="the model's training objective: sigmoid or softplus outputs")
     d.add_argument("-o", "--output", type=str, default="./anchored.tsv")
+    h = sub.add_parser("complete", help="cluster completion: for every cluster of 1 .. 31 loci the best --top bins (or sets of --free bins) to add")
+    h.add_argument("-i", "--file", type=str, required=True, help="one cluster per line: 1 .. 31 tab-separated chrom:position loci; lines may differ in length")
+    h.add_argument("--chrom", type=int, required=True, help="the partner region: index into config chrom_list")
+    h.add_argument("--start-bin", type=int, default=None, help="first bin of the partner window, relative to --chrom (default 0)")
+    h.add_argument("--end-bin", type=int, default=None, help="one past the last bin of the partner window (default: the chromosome's end)")
+    h.add_argument("--free", type=int, default=1, help="how many bins to add to each cluster, 1 .. 8")
+    h.add_argument("--top", type=int, required=True, help="how many candidates to keep per cluster")
+    h.add_argument("--width", type=int, default=None, help="zero-pad rows to this width (default: longest cluster + free, at most 32)")
+    h.add_argument("--exclude-known", action="store_true", help="skip the hyperedges of temp_dir/all_<k>_counter.npy, for every candidate size k present")
+    h.add_argument("--chunk-rows", type=int, default=None, help="rows per forward (default: 2^20 up to width 8, min(2^20, 2^21 // width) beyond)")
+    h.add_argument("--task-mode", choices=["class", "regress"], default="class", help="the model's training objective: sigmoid or softplus outputs")
+    h.add_argument("-o", "--output", type=str, default="./complete.tsv")
+    h.add_argument("--config", type=str, default="./config.JSON")
     e = sub.add_parser("kmap", help="pair map: the probabilities of all candidates of size --k projected onto pairs of bins")
     e.add_argument("--chrom", type=int, required=True, help="index into config chrom_list")
     e.add_argument("--k", type=int, required=True, help="candidate size, 2 .. 8")
@@ -395,6 +485,8 @@ def main(argv=None):
         return _kway(args, config, temp_dir, model)
     if args.cmd == "anchored":
         return _anchored(args, config, temp_dir, model)
+    if args.cmd == "complete":
+        return _complete(args, config, temp_dir, model)
     if args.cmd == "kmap":
         return _kmap(args, config, temp_dir, model)
     if args.cmd == "attention":

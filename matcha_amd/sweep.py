@@ -623,3 +623,233 @@ def kway_map(model, lo: int, hi: int, k: int, min_gap: int, chunk_rows: int = 1 
     out.pop("n_rows")
     out.update(n_candidates=total, n_excluded=int(n_exc.item()), n_rejected=int(out["n_rejected"].item()))
     return out
+
+
+# ---- cluster completion: the bins that best extend clusters of 1 to 31 loci ------------------------------------------
+MAX_CLUSTER = _lib.MAX_LONG_L - 1          # a cluster leaves room for one free node in a row of 32
+
+
+def _check_complete_args(A: int, S: int, n: int, free: int, min_gap: int):
+    if not (A >= 0 and 1 <= S <= MAX_CLUSTER and n >= 1 and 1 <= free <= _lib.MAX_L and min_gap >= 1):
+        raise ValueError(f"need A >= 0, 1 <= S <= {MAX_CLUSTER}, n >= 1, 1 <= free <= {_lib.MAX_L}, min_gap >= 1 "
+                         f"(A={A} S={S} n={n} free={free} min_gap={min_gap})")
+
+
+def completion_count(A: int, S: int, n: int, free: int, min_gap: int) -> int:
+    """Number of global ranks of a cluster table [A, S]: A * C_f with C_f = C(n - (free - 1)(min_gap - 1), free), the gap-constrained
+    subsets of size ``free`` of a region of n nodes; a total >= 2^63 is refused (ValueError), not truncated."""
+    A, S, n, free, min_gap = int(A), int(S), int(n), int(free), int(min_gap)
+    _check_complete_args(A, S, n, free, min_gap)
+    total = A * _free_count(n, free, min_gap)
+    if total >= 1 << 63:
+        raise ValueError(f"{total} candidates (A={A} n={n} free={free} min_gap={min_gap}) do not fit 63 bits")
+    return total
+
+
+def completion_unrank(rank: int, cluster, lo: int, n: int, free: int, min_gap: int) -> Tuple[Tuple[int, ...], bool]:
+    """(row, valid) of one cluster's candidate of FREE rank ``rank`` (a global rank g is cluster g // C_f, free rank g % C_f), in
+    Python integers (no GPU).  ``cluster``: its ids; as in the library only the run before the first zero counts (0 to 31 ids).  The row
+    is those ids and the free part -- the gap-constrained subset of size ``free`` of [lo, lo + n) of that lexicographic rank -- sorted
+    ascending, duplicates kept.  It is valid iff the cluster has an id, its ids are non-descending and every adjacent difference of
+    the row is >= min_gap.  A cluster that descends somewhere is not merged: its ids in their order, then the free part, invalid."""
+    ids = []
+    for v in cluster:
+        if int(v) == 0:
+            break
+        ids.append(int(v))
+    lo, n, free, min_gap = int(lo), int(n), int(free), int(min_gap)
+    _check_complete_args(1, max(len(ids), 1), n, free, min_gap)
+    total = _free_count(n, free, min_gap)
+    rank = int(rank)
+    if not 0 <= rank < total:
+        raise IndexError(f"rank {rank} outside [0, {total})")
+    m = n - (free - 1) * (min_gap - 1)
+    part, q, upper = [], total - 1 - rank, m - 1                         # as anchored_unrank
+    for j in range(free, 0, -1):
+        a, b = j - 1, upper
+        while a < b:
+            mid = (a + b + 1) // 2
+            if math.comb(mid, j) <= q:
+                a = mid
+            else:
+                b = mid - 1
+        q -= math.comb(a, j)
+        part.append(lo + (m - 1 - a) + (free - j) * (min_gap - 1))
+        upper = a - 1
+    ascending = all(a <= b for a, b in zip(ids, ids[1:]))
+    row = tuple(sorted(ids + part)) if ascending else tuple(ids + part)
+    return row, bool(ids) and ascending and all(b - a >= min_gap for a, b in zip(row, row[1:]))
+
+
+def _cluster_table(clusters, device) -> Tuple[torch.Tensor, int]:
+    """(int64 [A, S] on the device, max_a s_a): every row's non-zero ids sorted ascending, zeros last, S = max(1, max_a s_a).
+    ``clusters``: a list of id lists (of any lengths), or an integer array / tensor zero-padded to a common width (1-D = single ids).
+    Host inputs are measured on the host; a device tensor costs one small read-back (its longest row), before anything is launched
+    by the library."""
+    ragged = isinstance(clusters, (list, tuple)) and any(isinstance(c, (list, tuple)) or getattr(c, "ndim", 0) >= 1 for c in clusters)
+    if isinstance(clusters, (list, tuple)) and len(clusters) == 0:
+        t = torch.zeros(0, 1, dtype=torch.long)
+    elif ragged:
+        rows = [[int(v) for v in c] for c in clusters]
+        width = max([len(r) for r in rows] + [1])
+        t = torch.zeros(len(rows), width, dtype=torch.long)
+        for a, r in enumerate(rows):
+            t[a, :len(r)] = torch.tensor(r, dtype=torch.long)
+    else:
+        t = torch.as_tensor(clusters)
+        if t.dim() == 1:
+            t = t.view(-1, 1)
+        if t.dim() != 2 or t.is_floating_point() or t.dtype == torch.bool:
+            raise ValueError("clusters must be a list of id lists or an integer [A, S] (or [A]) tensor or array")
+        t = t.to(torch.long)
+    if t.shape[1] == 0:
+        t = torch.zeros(t.shape[0], 1, dtype=torch.long, device=t.device)
+    s_max = int((t != 0).sum(dim=1).max()) if t.shape[0] else 0
+    if s_max > MAX_CLUSTER:
+        raise ValueError(f"a cluster has {s_max} ids: at most {MAX_CLUSTER} are supported")
+    t = t.to(device)
+    big = torch.iinfo(torch.long).max                                    # zeros behind every id, then back to zero
+    t = torch.where(t == 0, torch.full_like(t, big), t).sort(dim=1).values[:, :max(s_max, 1)]
+    return torch.where(t == big, torch.zeros_like(t), t).contiguous(), s_max
+
+
+def _complete_rows(table: torch.Tensor, lo: int, n: int, free: int, min_gap: int, rank0: int, count: Optional[int], ranks, width: int,
+                   out, flag_out) -> Tuple[torch.Tensor, torch.Tensor]:
+    """matcha_kway_complete_rows on a table that is already in the library's form."""
+    lib = _lib.load()
+    A, S = int(table.shape[0]), int(table.shape[1])
+    total = completion_count(A, S, n, free, min_gap)
+    if not S + free <= width <= _lib.MAX_LONG_L:
+        raise ValueError(f"width must be in [{S + free}, {_lib.MAX_LONG_L}] (the longest cluster and the free part; got {width})")
+    if ranks is not None:
+        count = int(ranks.numel())
+    else:
+        count = total - int(rank0) if count is None else int(count)
+        if rank0 < 0 or count < 0 or rank0 + count > total:
+            raise IndexError(f"ranks [{rank0}, {rank0 + count}) outside [0, {total})")
+    device = table.device
+    if out is None:
+        x = torch.empty(count, width, dtype=torch.long, device=device)
+    else:
+        if out.dtype != torch.long or not out.is_contiguous() or out.numel() < count * width or out.device != device:
+            raise ValueError("out must be a contiguous int64 tensor of at least count * width elements on the clusters' device")
+        x = out.view(-1)[:count * width].view(count, width)
+    if flag_out is None:
+        flag = torch.empty(count, dtype=torch.int32, device=device)
+    else:
+        if flag_out.dtype != torch.int32 or not flag_out.is_contiguous() or flag_out.numel() < count or flag_out.device != device:
+            raise ValueError("flag_out must be a contiguous int32 tensor of at least count elements on out's device")
+        flag = flag_out.view(-1)[:count]
+    if not x.is_cuda:
+        raise _lib.MatchaHipError("completion_rows needs a cuda device (no CPU fallback)")
+    with torch.cuda.device(device):
+        _lib.check(lib.matcha_kway_complete_rows(_lib.ptr(table), A, S, int(lo), n, free, min_gap, int(rank0), _lib.ptr(ranks), count, width,
+                                                 _lib.ptr(x), _lib.ptr(flag), _stream(device)), "matcha_kway_complete_rows")
+    return x, flag
+
+
+def completion_rows(clusters, lo: int, n: int, free: int, min_gap: int, rank0: int = 0, count: Optional[int] = None,
+                    ranks: Optional[torch.Tensor] = None, width: Optional[int] = None, device="cuda", out: Optional[torch.Tensor] = None,
+                    flag_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(x int64 [count, width], flag int32 [count]) on the device: the candidates of the global ranks rank0 .. rank0 + count - 1, or
+    of the device list ``ranks`` (a rank outside [0, A * C_f) gives an all-zero row with its flag set); flag != 0 marks an invalid
+    candidate.  ``clusters``: a list of id lists of 0 to 31 ids each, or an integer [A, S] array / tensor zero-padded (each row is
+    sorted here, zeros last).  ``width``: from (longest cluster + free), the default, up to 32.  ``out`` / ``flag_out`` reuse buffers
+    of at least count * width / count elements."""
+    if isinstance(clusters, torch.Tensor) and clusters.is_cuda and ranks is None and out is None:
+        device = clusters.device
+    if ranks is not None:
+        ranks = ranks.to(device=device, dtype=torch.long).contiguous().view(-1)
+        device = ranks.device
+    elif out is not None:
+        device = out.device
+    n, free, min_gap = int(n), int(free), int(min_gap)
+    _check_complete_args(0, 1, n, free, min_gap)
+    table, s_max = _cluster_table(clusters, device)
+    width = int(max(s_max, 1) + free if width is None else width)
+    return _complete_rows(table, lo, n, free, min_gap, rank0, count, ranks, width, out, flag_out)
+
+
+def completion_sweep(model, clusters, lo: int, hi: int, free: int = 1, min_gap: int = 1, top: int = 20, chunk_rows: Optional[int] = None,
+                     width: Optional[int] = None, exclude=None, task_mode: str = "class") -> dict:
+    """For every cluster (``clusters``: a list of id lists of 1 to 31 ids each, or a zero-padded integer [A, S] array / tensor) score
+    all its completions by a gap-constrained subset of size ``free`` (1 .. 8) of the partner region [lo, hi) and keep the ``top`` best
+    PER CLUSTER: which further bin, or set of bins, most plausibly belongs to it.  Clusters may lie inside the region, outside it or
+    across chromosomes, and differ in size.
+
+    All candidates are scored at ONE width (a logit depends on its batch's width: pads are attended): ``width``, default (longest
+    cluster + free), at most 32.  Up to 8 it is model(x)'s forward for short rows, beyond it the long forward.
+
+    Returns anchored_sweep's keys, on the model's device and best first within each cluster, with K = min(top, C_f): ``rows`` int64
+    [A, K, width], ``logit`` and ``proba`` [A, K], ``rank`` int64 [A, K] (the FREE rank; decode with completion_unrank), ``count``
+    int64 [A], and ``added`` int64 [A, K, free]: the free ids of each kept candidate.  Beyond count[a] the rank is -1 and everything
+    else 0.  The integers ``n_candidates`` = A * C_f, ``n_invalid`` (a free node on or within the gap of a cluster id, a cluster that
+    breaks the gap itself or has no id; scored, never kept) and ``n_excluded`` (valid candidates found in ``exclude``, a HyperedgeSet).
+
+    ``chunk_rows``: None = 2^20 rows up to width 8 and min(2^20, 2^21 // width) beyond (about 3.1 KB of workspace per token); an
+    explicit value the long forward cannot take is a ValueError before anything is launched.  The result does not depend on it.  The
+    loop is anchored_sweep's: eval mode, no grad, one reused row buffer and flag buffer, nothing synchronises until the end, where
+    the node-id check of the whole sweep is raised once (IndexError, also for a cluster id beyond the model's tables)."""
+    if task_mode not in ("class", "regress"):
+        raise ValueError("task_mode must be 'class' or 'regress'")
+    lo, hi, free, min_gap, top = int(lo), int(hi), int(free), int(min_gap), int(top)
+    n = hi - lo
+    if not 1 <= free <= _lib.MAX_L or min_gap < 1:
+        raise ValueError(f"need 1 <= free <= {_lib.MAX_L} and min_gap >= 1 (free={free} min_gap={min_gap})")
+    if width is not None and not free + 1 <= int(width) <= _lib.MAX_LONG_L:
+        raise ValueError(f"width must be in [longest cluster + free, {_lib.MAX_LONG_L}] (got {width})")
+    if top < 1 or (chunk_rows is not None and int(chunk_rows) < 1):
+        raise ValueError("top and chunk_rows must be >= 1")
+    act = torch.nn.functional.softplus if task_mode == "regress" else torch.sigmoid
+    model.eval()
+    dev = model.layer_norm1.weight.device
+    table, s_max = _cluster_table(clusters, dev)
+    A, S = int(table.shape[0]), int(table.shape[1])
+    width = int(max(s_max, 1) + free if width is None else width)
+    if not S + free <= width <= _lib.MAX_LONG_L:
+        raise ValueError(f"width must be in [{S + free}, {_lib.MAX_LONG_L}]: the longest cluster has {s_max} ids and free = {free} (got {width})")
+    if chunk_rows is None:
+        chunk_rows = 1 << 20 if width <= _lib.MAX_L else min(1 << 20, (1 << 21) // width)
+    else:
+        chunk_rows = int(chunk_rows)
+        if width > _lib.MAX_L:
+            rt = model._runtime()
+            if not 1 <= chunk_rows < 1 << 31 or rt.lib.matcha_workspace_bytes_long(C.byref(rt.shape), chunk_rows, width) == 0:
+                raise ValueError(f"chunk_rows = {chunk_rows} rows of {width} columns are more than the long forward takes in one call")
+    total = completion_count(A, S, n, free, min_gap) if n >= 1 else 0
+    cf = total // A if A else 0
+    K = min(top, cf)
+    if total == 0:
+        e = torch.zeros(A, K, dtype=torch.float32, device=dev)
+        return {"rows": torch.zeros(A, K, width, dtype=torch.long, device=dev), "logit": e, "proba": e.clone(),
+                "rank": torch.full((A, K), -1, dtype=torch.long, device=dev), "count": torch.zeros(A, dtype=torch.long, device=dev),
+                "added": torch.zeros(A, K, free, dtype=torch.long, device=dev), "n_candidates": 0, "n_invalid": 0, "n_excluded": 0}
+    chunk_rows = min(chunk_rows, total)
+    sel = SegTopK(A, K, cf, chunk_rows, dev)
+    buf = torch.empty(chunk_rows * width, dtype=torch.long, device=dev)
+    fbuf = torch.empty(chunk_rows, dtype=torch.int32, device=dev)
+    n_inv = torch.zeros((), dtype=torch.long, device=dev)
+    n_exc = torch.zeros((), dtype=torch.long, device=dev)
+    # Up to width 8 the large-batch route is pinned as in kway_sweep.  The long forward has one route: its kernels are chosen by the
+    # model's shape, never by the batch, and every token row is computed by itself, so a logit does not depend on chunk_rows there.
+    with torch.no_grad(), model.deferred_id_check(), _lib.option("disable_small_batch"):
+        for g0 in range(0, total, chunk_rows):
+            x, flag = _complete_rows(table, lo, n, free, min_gap, g0, min(chunk_rows, total - g0), None, width, buf, fbuf)
+            logits = model(x).reshape(-1)
+            skip = flag != 0
+            n_inv += skip.sum()
+            if exclude is not None:
+                known = exclude.contains(x)
+                n_exc += (known & ~skip).sum()
+                skip = skip | known
+            sel.update(logits, g0, skip)
+    logit, grank, count = sel.read()
+    rows, _ = _complete_rows(table, lo, n, free, min_gap, 0, None, grank.view(-1), width, None, None)
+    # the added bins: the same ranks through the s_a = 0 form of the rows kernel (a table of empty clusters: the free part alone)
+    added, _ = _complete_rows(torch.zeros(A, 1, dtype=torch.long, device=dev), lo, n, free, min_gap, 0, None, grank.view(-1), free + 1, None, None)
+    kept = grank >= 0
+    rank = torch.where(kept, grank - torch.arange(A, dtype=torch.long, device=dev).view(-1, 1) * cf, grank)
+    proba = torch.where(kept, act(logit), torch.zeros_like(logit))
+    return {"rows": rows.view(A, K, width), "logit": logit, "proba": proba, "rank": rank, "count": count,
+            "added": added.view(A, K, free + 1)[:, :, :free].contiguous(), "n_candidates": total, "n_invalid": int(n_inv.item()),
+            "n_excluded": int(n_exc.item())}
