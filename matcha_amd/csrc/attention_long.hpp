@@ -50,7 +50,7 @@ __device__ __forceinline__ void long_softmax(const f32x16& acc, int k, int n_pad
   for (int v = 0; v < 16; ++v) {
     const int j = 8 * (v >> 2) + 4 * h + (v & 3);
     const bool on = (j < k && j != r) || (j == k && n_pad > 0);
-    const float e = on ? __expf(p[v] - mx) : 0.f;      // (one v_exp, like the fused forward's softmax: the fp32 grade holds, tests/test_hip_long_rows.py)
+    const float e = on ? __expf(p[v] - mx) : 0.f;      // (one v_exp, like the fused forward's softmax: the fp32 grade holds at scores of +-60, the `sharp` cases of tests/test_hip_long_grid.py)
     p[v] = j == k ? padf * e : e;
     den += p[v];
   }

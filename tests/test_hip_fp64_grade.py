@@ -24,6 +24,7 @@ import torch
 from matcha_amd import synth, _lib
 from tests import fp64_grade as G
 from tests.helpers import oracle_state
+from tests.test_cpu_long_grid import DIM_CASES
 from tests.test_hip_model import hip_model, _trainer_grads
 
 pytestmark = pytest.mark.gpu
@@ -133,13 +134,36 @@ for _base in TABLE_BASES:
 CASES["t64_wide_below"] = replace(T64, layout="wide_adj", seed=91, rows_per_k=825, table="token", by_size=True)
 CASES["t64_wide_above"] = replace(T64, layout="wide_adj", seed=91, rows_per_k=850, table="node_r")
 
+# The embed dims check_shape_fields accepts beside 16, 32, 64, 128 and 256 (tests/test_cpu_long_grid.py::DIM_CASES), on the L <= 8 step: below 64 the
+# layer-by-layer kernels (attention's `fon` clamp at a partial last 32-feature tile, GEMMs at K = d no multiple of 16), at 192 the wide kernels (three
+# 64-feature chunks, a 3 x 3 bmm_heads grid, gemm_wide at N = 1 536, K = 192).  rows_per_k as t16 / a32 (64) and t256 (286): the smallest that reach
+# those routes.  Below 64: _LAYERWISE and nothing of _NOT_FUSED.  At 192: _WIDE without gemm_tn_wide_kernel -- its tiles are 128 x 128 and
+# gemm_tn_wide_eligible wants M and N multiples of 128, which neither 192 nor 1 536 x 192 is, so every weight gradient takes gemm_tn_kernel, and the
+# products with N = 192 take gemm_lds_kernel -- and neither enc128_* nor fused_fwd32_kernel.  What goes beyond that was read off the first MI355X run
+# and frozen: the adj front end's kernels (the small sort at 256 / 448 rows, the histogram sort at 2 002), bmm_heads_kernel and the row plan at 192.
+_C1_KS = (2, 3, 4, 5, 6, 7, 8)
+_ADJ_FRONT = frozenset({"adj_encode_fwd_kernel", "adj_tn_kernel<0>", "adj_tn_kernel<1>", "adj_tanh_gather_kernel", "adj_recon_loss_kernel"})
+for _layout, _d, _mode, _seed in DIM_CASES:
+    _ks = dict(ks=_C1_KS) if _layout == "c1" else {}
+    if _d < 64:
+        _must = _LAYERWISE | {"plan_small_kernel"}
+        _must = _must if _mode == "table" else (_must - {"embed_scatter_kernel"}) | _ADJ_FRONT | {"adj_sort_small_kernel"}
+        _sets = dict(must=_must, must_not=_NOT_FUSED | _ADJ64 | {"gemm_wide_kernel", "gemm_tn_wide_kernel"})
+    else:
+        _must = (_WIDE - {"gemm_tn_wide_kernel"}) | {"gemm_tn_kernel", "gemm_lds_kernel", "bmm_heads_kernel", "head_sum_row_kernel", "row_fill_kernel"}
+        _must = _must | {"embed_scatter_kernel"} if _mode == "table" else _must | _ADJ_FRONT | {"adj_hist_kernel", "adj_scan_kernel", "adj_scatter_kernel"}
+        _sets = dict(must=_must, must_not=frozenset({"enc128_fwd_kernel", "enc128_bwd_kernel", "fused_fwd32_kernel", "fused_fwd32h_kernel",
+                                                     "attn_fwd_kernel", "plan_small_kernel"}) | _ADJ64)
+    CASES[f"{_mode[0]}{_d}"] = Case(_layout, _d, _mode, _seed, rows_per_k=64 if _d < 64 else 286, **_ks, **_sets)
+
 # ---- dropout ON -----------------------------------------------------------------------------------------------------------------------------
 # Twins of the cases above at the model's default p (same shapes: already the smallest that reach each kernel set), the kernel sets, the table
 # route and the witness assertion unchanged.  The high-p twins take p that no float represents, the widest gap between floor(p 2^32) of the double
 # and of the float (oracle/rng.py) and (1 / (1 - p)) (1 - p) furthest from 1.
 P_DEFAULT, P_HIGH = (0.2, 0.3, 0.4), (0.6, 0.7, 0.9)
 DROP_BASES = ("t64_big", "t64_big_token", "t64_big_node_rec", "t64_det", "t64_nolif", "t64_fourprod", "t64_layerwise", "t64_edge-", "t64_edge+",
-              "t64_tiny2", "t64_k8", "t64_nattr5", "t64_wide_below", "a64_hg38", "a64_wide", "t128", "a128_wide", "t256", "t16", "a32", "r64")
+              "t64_tiny2", "t64_k8", "t64_nattr5", "t64_wide_below", "a64_hg38", "a64_wide", "t128", "a128_wide", "t256", "t16", "a32", "r64",
+              "a40", "t192")
 for _base in DROP_BASES:
     CASES[f"{_base}_drop"] = replace(CASES[_base], drop=P_DEFAULT)
 for _base in ("t64_big", "a64_hg38", "t128"):

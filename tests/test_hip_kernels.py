@@ -33,7 +33,9 @@ def _gemm(op, A, B, M, N, K, epi=None, colsum=None, gather=None, C_init=None):
 
 SHAPES = [(128, 64, 64), (1000, 64, 64), (37, 16, 16), (515, 512, 64), (515, 64, 512), (300, 128, 128), (70, 24, 20), (130, 96, 250),
           # the 128 x 128-tile kernels of gemm_wide.hip (N % 128 == 0, K % 32 == 0, K >= 64): embed_dim 128 / 256 layer shapes
-          (1000, 1024, 128), (515, 128, 1024), (257, 256, 256), (1, 128, 64), (2049, 2048, 256), (129, 256, 2048)]
+          (1000, 1024, 128), (515, 128, 1024), (257, 256, 256), (1, 128, 64), (2049, 2048, 256), (129, 256, 2048),
+          # embed_dim 40 and 192: K no multiple of 16; N = 192 x 8 = 1 536 columns (twelve 128-column tiles), K = 192
+          (300, 320, 40), (515, 1536, 192)]
 
 
 @pytest.mark.parametrize("M,N,K", SHAPES)
@@ -60,7 +62,8 @@ def test_gemm_unaligned_rows():
 
 
 @pytest.mark.parametrize("R_,M,N", [(1000, 64, 64), (5000, 512, 64), (777, 64, 512), (333, 16, 16), (4096, 64, 24), (50, 128, 128),
-                                    (5000, 1024, 128), (777, 128, 1024), (33, 256, 256), (1, 128, 128), (20000, 2048, 256)])
+                                    (5000, 1024, 128), (777, 128, 1024), (33, 256, 256), (1, 128, 128), (20000, 2048, 256),
+                                    (777, 320, 40), (777, 1536, 192)])
 def test_gemm_tn(R_, M, N):
     g = torch.Generator().manual_seed(R_ + M + N)
     dY, X = torch.randn(R_, M, generator=g), torch.randn(R_, N, generator=g)
@@ -171,7 +174,7 @@ def test_gemm_dropout_pattern_is_the_specifications_at_a_threshold_gap():
     assert (out - lin * mask).abs().max() <= 2e-5 * float((lin * mask).abs().max())
 
 
-@pytest.mark.parametrize("M,N,K", [(300, 128, 128), (1000, 1024, 128), (130, 128, 1024)])
+@pytest.mark.parametrize("M,N,K", [(300, 128, 128), (1000, 1024, 128), (130, 128, 1024), (300, 1536, 192)])
 def test_gemm_wide_tiles_equal_narrow_tiles_and_epilogues(M, N, K):
     """gemm_wide.hip against the 64-wide kernels it replaces at embed_dim >= 128 (option disable_wide_gemm) with the epilogues
     the model uses, dropout masks bit-identical (counter RNG on (row, column)); TN including the column sums."""
@@ -218,7 +221,7 @@ def _attn_ref(Q, K, V, B, L, d):
     return o, p
 
 
-@pytest.mark.parametrize("d", [16, 64, 128, 256])
+@pytest.mark.parametrize("d", [16, 64, 128, 256, 8, 24, 40, 192])
 @pytest.mark.parametrize("L", [1, 2, 3, 5, 7, 8])
 @pytest.mark.parametrize("ragged", [False, True])
 def test_attention_fwd_bwd(d, L, ragged):
@@ -228,7 +231,7 @@ def test_attention_fwd_bwd(d, L, ragged):
     _attention_case(d, L, ragged, 37)
 
 
-@pytest.mark.parametrize("d,L", [(128, 5), (256, 5), (256, 8)])
+@pytest.mark.parametrize("d,L", [(128, 5), (256, 5), (256, 8), (192, 8)])
 def test_attention_wide_many_rows(d, L):
     """attention_wide.hip (embed_dim >= 128) on >= 4 096 token rows -- many workgroups, the streamed-operand path, the pad-token
     gradient slabs reduced over many blocks -- against the same dense reference (Modules.py:449-458)."""
@@ -284,7 +287,7 @@ def _attention_case(d, L, ragged, B):
         assert (got.cpu() - ref).abs().max() <= 5e-5 * max(1.0, ref.abs().max())
 
 
-@pytest.mark.parametrize("d", [16, 64, 128, 256])
+@pytest.mark.parametrize("d", [16, 64, 128, 256, 8, 24, 40, 192])
 def test_embed_and_ln3(d):
     lib = _lib.load()
     T, N, n_attr = 1000, 300, 24

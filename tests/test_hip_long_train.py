@@ -121,17 +121,26 @@ def torch_attention_grads(Qn, Kn, Vn, dOn, row_off, L, d, shared, dtype):
 @pytest.mark.parametrize("L", [9, 32])
 @pytest.mark.parametrize("d,shared", [(16, False), (64, True), (128, True)])
 def test_attention_backward_kernel_against_torch_fp64(d, shared, L):
+    attention_backward_case(d, shared, L, [L, 2, 1, 0, 9, L - 1, 17 if L == 32 else 5], 1000 + d + L)
+
+
+def attention_backward_case(d, shared, L, ks, seed, q_scale=1.0, pad_row=False, reference=None):
+    """matcha_attn_long_bwd on hyperedges of ks real tokens against torch fp64 autograd, e <= 8 x torch fp32's own error per tensor, twice over NaN
+    and 7.0 fills with equal bits; ``q_scale`` multiplies Q (sharp scores); with ``pad_row`` the padding token's dK / dV row is held to the same
+    bound on its own, normalised by that row's fp64 maximum; ``reference`` stands in for torch_attention_grads (same signature).  Returns {tensor: e / noise} (and "dK pad" / "dV pad")."""
     lib = _lib.load()
-    ks = [L, 2, 1, 0, 9, L - 1, 17 if L == 32 else 5]
     row_off = np.concatenate([[0], np.cumsum(ks)]).astype(np.int32)
     T, B = int(row_off[-1]), len(ks)
-    rng = np.random.default_rng(1000 + d + L)
+    rng = np.random.default_rng(seed)
     kvw = d if shared else 8 * d
     Qn, dOn = (rng.standard_normal((T + 1, 8 * d)).astype(np.float32) for _ in range(2))
     Kn, Vn = (rng.standard_normal((T + 1, kvw)).astype(np.float32) for _ in range(2))
+    if q_scale != 1.0:
+        Qn = (Qn * np.float32(q_scale)).astype(np.float32)
     dOn[T] = 0.0                                             # the padding token is no query: its dO row is the masked fc1 row's gradient, zero
-    r64 = torch_attention_grads(Qn, Kn, Vn, dOn, row_off, L, d, shared, torch.float64)
-    r32 = torch_attention_grads(Qn, Kn, Vn, dOn, row_off, L, d, shared, torch.float32)
+    reference = reference or torch_attention_grads
+    r64 = reference(Qn, Kn, Vn, dOn, row_off, L, d, shared, torch.float64)
+    r32 = reference(Qn, Kn, Vn, dOn, row_off, L, d, shared, torch.float32)
     dev = lambda a: torch.from_numpy(a).cuda().contiguous()
     Q, K, V, dO, ro = dev(Qn), dev(Kn), dev(Vn), dev(dOn), dev(row_off)
     ws = torch.empty(lib.matcha_attn_long_bwd_workspace_bytes(B, d), dtype=torch.uint8, device="cuda")
@@ -148,13 +157,21 @@ def test_attention_backward_kernel_against_torch_fp64(d, shared, L):
         runs.append([t.cpu().numpy() for t in (dQ, dK, dV)])
     for a, b in zip(*runs):
         assert np.array_equal(a, b)                          # bit-identical from run to run
+    ratios = {}
     for name, got, g64, g32 in zip(("dQ", "dK", "dV"), runs[0], r64, r32):
         e, noise = G.tensor_err(got, g64), max(G.tensor_err(g32, g64), G.ULP)
-        e_pad = float(np.abs(got[T] - g64[T]).max() / np.abs(g64).max())
+        e_pad = float(np.abs(got[T] - g64[T]).max() / max(np.abs(g64).max(), 1e-300))
         print(f"d {d} L {L} {name}: e {e:.2e}, torch fp32 {noise:.2e}, ratio {e / noise:.2f}; padding row e {e_pad:.2e}")
         assert np.isfinite(got).all()
         assert e <= 8 * noise, (name, e, noise)
+        ratios[name] = e / noise
+        if pad_row and name != "dQ":
+            e_row, noise_row = G.tensor_err(got[T], g64[T]), max(G.tensor_err(g32[T], g64[T]), G.ULP)
+            print(f"d {d} L {L} {name}: padding row alone e {e_row:.2e}, torch fp32 {noise_row:.2e}, ratio {e_row / noise_row:.2f}")
+            assert e_row <= 8 * noise_row, (name, "padding row", e_row, noise_row)
+            ratios[name + " pad"] = e_row / noise_row
     assert not runs[0][0][T].any()                           # dQ of the padding token
+    return ratios
 
 
 # ---- 2. reference parity ------------------------------------------------------------------------------------------------------------------------
