@@ -733,6 +733,40 @@ int matcha_kway_complete_rows(const int64_t* clusters, int64_t A, int32_t S, int
                               int64_t rank0, const int64_t* ranks, int64_t count, int32_t L, int64_t* x, int32_t* flag,
                               matcha_stream_t stream);
 
+/* ---- cluster decomposition ----------------------------------------------------------------------------
+ * Which sub-hyperedges of clusters of up to 32 loci are real (keep), and which locus does not belong (drop): the candidates are
+ * subsets of a cluster's OWN ids.  A cluster table is int64 [A, S], 2 <= S <= 32; row a holds s_a non-zero node ids followed by
+ * zeros: the leading non-zero run is read.  A choice is an m-subset of the positions [0, S), 1 <= m <= 8, ranked lexicographically
+ * from 0 (C_m = C(S, m) <= C(32, 8) of them); the global rank is g = a C_m + r.  complement = 0 (keep, 2 <= m <= 8): the row is the
+ * ids at the chosen positions; complement = 1 (drop, 1 <= m <= 8): the ids at every other position; both in position order,
+ * zero-padded to L (keep: m <= L <= 32; drop: max(S - m, 1) <= L <= 32).  A candidate is valid iff every chosen position is < s_a,
+ * the row has at least 2 ids, the cluster's ids are non-descending and every adjacent difference of the row is >= min_gap.  A
+ * candidate with a chosen position >= s_a is an all-zero row with its flag set; every other invalid candidate keeps its row.
+ * matcha_cluster_subset_count  host only: A C(S, m), or -1 for invalid arguments or a total >= 2^63.
+ * matcha_cluster_subset_rows   matcha_kway_complete_rows' contract: clusters device int64 [A, S]; writes x, device int64 [count, L],
+ *     and flag, device int32 [count] (non-zero = invalid): row i is the candidate of global rank rank0 + i (ranks == NULL; the range
+ *     must lie inside [0, A C_m), else refused) or ranks[i] (device int64 [count]; a rank outside [0, A C_m) gives an all-zero row
+ *     with its flag set).  count = 0 launches nothing.  Every refusal is MATCHA_EINVAL with a message, before any device call;
+ *     caller-owned memory, asynchronous on the caller's stream, no allocation, no memset, no read-back.
+ * matcha_subset_support_*      per cluster and position, what a top-K cannot give: over the accepted rows whose choice contains the
+ *     position, the sum of their values in PairMap's fixed point (int64, rint(double(v) 2^32)) and their number; two int64 planes
+ *     [A, S] behind a 256-byte header {n_rows, n_rejected}.  1 <= A <= 2^40, 0 < vmax <= 2^20.  _bytes: the state's size, 0 for
+ *     invalid arguments.  _init zeroes the state (a kernel, no memset).  _update: value device float32 [n], skip device int32 [n] or
+ *     NULL; row i has the global rank g0 + i (the range must lie inside [0, A C_m)) and its choice is unranked on the device -- no row
+ *     is read; a row with skip != 0 contributes nothing, one whose value is NaN, negative or > vmax is counted in n_rejected.
+ *     Integer atomics only: the state is bit for bit independent of arrival order and of how the stream is cut.  _read: the planes
+ *     (device int64 [A, S]) and the two counters (device int64 [2]); any of the three may be NULL, not all. */
+int64_t matcha_cluster_subset_count(int64_t A, int32_t S, int32_t m, int32_t complement);
+int matcha_cluster_subset_rows(const int64_t* clusters, int64_t A, int32_t S, int32_t m, int32_t complement, int32_t min_gap,
+                               int64_t rank0, const int64_t* ranks, int64_t count, int32_t L, int64_t* x, int32_t* flag,
+                               matcha_stream_t stream);
+size_t matcha_subset_support_bytes(int64_t A, int32_t S, int32_t m, float vmax);
+int matcha_subset_support_init(void* state, size_t bytes, int64_t A, int32_t S, int32_t m, float vmax, matcha_stream_t stream);
+int matcha_subset_support_update(void* state, size_t bytes, int64_t A, int32_t S, int32_t m, float vmax, const float* value,
+                                 const int32_t* skip, int64_t n, int64_t g0, matcha_stream_t stream);
+int matcha_subset_support_read(const void* state, size_t bytes, int64_t A, int32_t S, int32_t m, float vmax, int64_t* sum_out,
+                               int64_t* count_out, int64_t* counters_out, matcha_stream_t stream);
+
 /* ---- k-way pair maps -----------------------------------------------------------------------------------
  * The values of k-way rows projected onto pairs of node ids and accumulated on the device.  A map covers the row region
  * R = [lo_r, lo_r + n_r) and the column region C = [lo_c, lo_c + n_c): R == C (symmetric) or R and C disjoint (rectangular); any

@@ -153,6 +153,12 @@ SIGNATURES = {
     "matcha_segtopk_read": (C.c_int, [_fp, _SZ, _I64, _I32, _I64, _I64, _fp, _fp, _fp, _fp]),
     "matcha_kway_complete_count": (_I64, [_I64, _I32, _I32, _I32, _I32]),
     "matcha_kway_complete_rows": (C.c_int, [_fp, _I64, _I32, _I64, _I32, _I32, _I32, _I64, _fp, _I64, _I32, _fp, _fp, _fp]),
+    "matcha_cluster_subset_count": (_I64, [_I64, _I32, _I32, _I32]),
+    "matcha_cluster_subset_rows": (C.c_int, [_fp, _I64, _I32, _I32, _I32, _I32, _I64, _fp, _I64, _I32, _fp, _fp, _fp]),
+    "matcha_subset_support_bytes": (_SZ, [_I64, _I32, _I32, _F]),
+    "matcha_subset_support_init": (C.c_int, [_fp, _SZ, _I64, _I32, _I32, _F, _fp]),
+    "matcha_subset_support_update": (C.c_int, [_fp, _SZ, _I64, _I32, _I32, _F, _fp, _fp, _I64, _I64, _fp]),
+    "matcha_subset_support_read": (C.c_int, [_fp, _SZ, _I64, _I32, _I32, _F, _fp, _fp, _fp, _fp]),
     "matcha_pairmap_bytes": (_SZ, [_I64, _I32, _I64, _I32, _I32, _F, _F]),
     "matcha_pairmap_init": (C.c_int, [_fp, _SZ, _I64, _I32, _I64, _I32, _I32, _F, _F, _fp]),
     "matcha_pairmap_update": (C.c_int, [_fp, _SZ, _I64, _I32, _I64, _I32, _I32, _F, _F, _fp, _fp, _fp, _I64, _I32, _fp]),

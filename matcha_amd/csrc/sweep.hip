@@ -904,3 +904,321 @@ extern "C" int matcha_kway_complete_rows(const int64_t* clusters, int64_t A, int
   MATCHA_CHECK_LAUNCH("kway_complete_rows_kernel");
   return MATCHA_OK;
 }
+
+// ==== cluster decomposition ==========================================================================================
+// Which sub-hyperedges of a cluster of up to 32 loci are real: the candidates are subsets of the cluster's OWN ids.  A cluster table is
+// int64 [A, S], 2 <= S <= 32; row a holds s_a non-zero ids followed by zeros, only the leading run is read.  A choice is an m-subset of
+// the positions [0, S), 1 <= m <= 8, ranked lexicographically from 0: C_m = C(S, m) <= C(32, 8) of them, so a choice's rank fits 32 bits;
+// the global rank is g = a C_m + r.  keep (complement = 0, m >= 2): the row is the ids at the chosen positions; drop (complement = 1):
+// the ids at all other positions; both in position order, zero-padded to L.  A candidate is valid iff every chosen position is < s_a,
+// the row has at least 2 ids, the cluster's own ids are non-descending and every adjacent difference of the row is >= min_gap
+// (unsigned, as in 7.10).  A chosen position >= s_a gives an all-zero row, flagged; every other invalid candidate keeps its row.
+//
+//   cluster_subset_rows_kernel    a wavefront serves 64 consecutive ranks.  Each lane divides and unranks ONE of them with the sweep's
+//                                 unrank (m = S: the positions are the "region") and folds the positions into a 32-bit mask.  Then the
+//                                 two 32-lane halves walk the 64 rows, one row each per step: the owner broadcasts its cluster index and
+//                                 mask, lane j reads cluster id j, s_a is the first zero of a ballot.  A kept id goes to the column
+//                                 popcount(kept mask below the lane); the lanes that keep nothing write the zero padding behind the row
+//                                 (there are 32 - kept of them and at most L - kept pads): one store instruction per row, its lanes
+//                                 covering one contiguous run of 8 L bytes.  The gap test compares every kept id with the previous KEPT
+//                                 id, fetched by a shuffle from the highest set bit of the mask below the lane; one ballot per row.  No
+//                                 LDS, no scratch.  Every shuffle and ballot is executed by all 64 lanes (predicated, never branched
+//                                 around; the step count is the same for the whole wavefront).
+//   subset_support_update_kernel  per cluster and position, the fixed-point sum (rint(double(v) 2^32), PairMap's) and the number of the
+//                                 accepted rows whose choice contains the position; it unranks the choice itself and never reads a row.
+//                                 A block serves runs of kSupRun consecutive ranks, hence of consecutive clusters: it accumulates into
+//                                 an LDS tile of (clusters of the run) x S cells per plane with LDS integer atomics and issues one global
+//                                 atomic per touched cell; clusters of the run beyond the tile go to global atomics directly.  Integer
+//                                 atomics only: the state does not depend on arrival order or on how the stream is cut.
+namespace matcha {
+namespace {
+
+constexpr int kSupRun = 2048;                  // consecutive ranks per block run: 8 rows per thread
+constexpr int kSupTile = 1024;                 // cells per LDS plane (2 planes x 8 KB): 32 clusters of 32 ids, 341 of 3
+constexpr size_t kSupHeader = 256;             // int64 n_rows, int64 n_rejected, padding
+
+bool subset_args_ok(int64_t A, int32_t S, int32_t m, int32_t complement) {
+  return A >= 0 && S >= 2 && S <= kMaxWide && (complement == 0 || complement == 1) && m >= (complement ? 1 : 2) && m <= kMaxK;
+}
+
+// A C(S, m), -1 for invalid arguments or a total >= 2^63; *cm_out = C(S, m)
+int64_t subset_count(int64_t A, int32_t S, int32_t m, int32_t complement, int64_t* cm_out) {
+  if (!subset_args_ok(A, S, m, complement)) return -1;
+  const int64_t cm = count_subsets(S, m);      // <= C(32, 8)
+  const unsigned __int128 total = (unsigned __int128)(uint64_t)A * (uint64_t)cm;
+  if (total >= ((unsigned __int128)1 << 63)) return -1;
+  if (cm_out) *cm_out = cm;
+  return (int64_t)total;
+}
+
+// g = a cm + r; one 64-bit division only when the operands need it
+__device__ __forceinline__ void split_rank(uint64_t g, uint64_t cm, uint64_t& a, uint64_t& r) {
+  if ((g | cm) >> 32) {
+    a = g / cm;
+    r = g - a * cm;
+  } else {
+    const uint32_t a32 = (uint32_t)g / (uint32_t)cm;
+    a = a32;
+    r = (uint32_t)g - a32 * (uint32_t)cm;
+  }
+}
+
+__global__ __launch_bounds__(kRowsPerBlock) void cluster_subset_rows_kernel(const int64_t* __restrict__ clusters, int32_t S, int32_t m, int32_t complement,
+                                                                            int32_t min_gap, uint64_t cm, uint64_t total, int64_t rank0,
+                                                                            const int64_t* __restrict__ ranks, int64_t count, int32_t L,
+                                                                            int64_t* __restrict__ x, int32_t* __restrict__ flag) {
+  const int lane = threadIdx.x & 63, h = lane >> 5, j = lane & 31;
+  const int64_t wave0 = (int64_t)(threadIdx.x >> 6) * 64;
+  const uint64_t gap = (uint64_t)min_gap;
+  const uint32_t below_me = (1u << j) - 1u;                            // j <= 31
+  for (int64_t base = (int64_t)blockIdx.x * kRowsPerBlock; base < count; base += (int64_t)gridDim.x * kRowsPerBlock) {
+    const int64_t w0 = base + wave0;                                   // the wavefront's first row; the same in all its lanes
+    const int64_t left = count - w0;
+    const int steps = left >= 64 ? 32 : left > 0 ? (int)((left + 1) >> 1) : 0;
+    // ---- one rank per lane: cluster index and the choice as a mask of positions ----
+    const int64_t i = w0 + lane;
+    const int64_t g = i < count ? (ranks ? ranks[i] : rank0 + i) : -1;
+    const int ok = g >= 0 && (uint64_t)g < total;                      // total > 0 then, so cm > 0 and m <= S
+    uint64_t a = 0;
+    uint32_t mask = 0;
+    if (ok) {
+      uint64_t r;
+      split_rank((uint64_t)g, cm, a, r);
+      int32_t y[kMaxK] = {0, 0, 0, 0, 0, 0, 0, 0};
+      unrank(r, cm, S, m, y);
+#pragma unroll
+      for (int c = 0; c < kMaxK; ++c)
+        if (c < m) mask |= 1u << (y[c] & 31);                          // y[c] < S <= 32
+    }
+    // ---- two rows per step, one per half ----
+    int bad_mine = 1;
+    for (int t = 0; t < steps; ++t) {
+      const int own = 2 * t + h;                                       // the lane that unranked this half's row
+      const int64_t irow = w0 + own;
+      const int ok0 = __shfl(ok, 2 * t), ok1 = __shfl(ok, 2 * t + 1);
+      const int ok_r = h ? ok1 : ok0;
+      const uint64_t a_r = (uint64_t)shfl64((int64_t)a, own);
+      const uint32_t mask_r = (uint32_t)__shfl((int)mask, own);
+      int64_t v = 0;
+      if (ok_r && j < S) v = clusters[a_r * (uint64_t)S + (uint64_t)j];
+      const uint64_t zb = __ballot(v == 0);
+      const uint32_t z0 = (uint32_t)zb, z1 = (uint32_t)(zb >> 32);
+      const int s0 = z0 ? __builtin_ctz(z0) : 32, s1 = z1 ? __builtin_ctz(z1) : 32;   // S = 32 and no zero: all 32 lanes hold an id
+      const int s = h ? s1 : s0;
+      const uint32_t in_cluster = (uint32_t)((1ull << s) - 1ull);
+      const bool outside = (mask_r & ~in_cluster) != 0;                // a chosen position >= s_a: an all-zero row
+      uint32_t keep = complement ? (~mask_r & in_cluster) : mask_r;
+      keep = (ok_r && !outside) ? keep : 0u;
+      const bool kept = (keep >> j) & 1u;
+      const uint32_t kb = keep & below_me;
+      const int n_below = __popc(kb), n_kept = __popc(keep);
+      // the cluster's own order: every id against its neighbour; the row's gaps: every kept id against the previous kept id
+      const int64_t prev = shfl64(v, j ? lane - 1 : lane);
+      const bool desc = j < s && j > 0 && v < prev;
+      const int64_t prev_kept = shfl64(v, kb ? (h << 5) + 31 - __builtin_clz(kb) : lane);
+      const bool close = kept && kb != 0 && (uint64_t)v - (uint64_t)prev_kept < gap;
+      const uint64_t bb = __ballot(desc || close);
+      const uint32_t out0 = (uint32_t)__shfl((int)outside, 0), out1 = (uint32_t)__shfl((int)outside, 32);
+      const int nk0 = __shfl(n_kept, 0), nk1 = __shfl(n_kept, 32);
+      const int bad0 = !ok0 || out0 || nk0 < 2 || (uint32_t)bb != 0, bad1 = !ok1 || out1 || nk1 < 2 || (uint32_t)(bb >> 32) != 0;
+      if (lane == 2 * t) bad_mine = bad0;
+      if (lane == 2 * t + 1) bad_mine = bad1;
+      const int col = kept ? n_below : n_kept + (j - n_below);         // the lanes that keep nothing write the pads behind the row
+      const int64_t val = kept ? v : 0;
+      if (irow < count && col < L) x[irow * L + col] = val;
+    }
+    if (i < count) flag[i] = bad_mine;
+  }
+}
+
+struct SupportPlan {
+  size_t off_sum, off_count, total;
+  int64_t cells;
+};
+
+bool support_args_ok(int64_t A, int32_t S, int32_t m, float vmax) {
+  return A >= 1 && A <= ((int64_t)1 << 40) && S >= 2 && S <= kMaxWide && m >= 1 && m <= kMaxK && vmax > 0.f && vmax <= 1048576.f;   // NaN fails
+}
+
+SupportPlan make_splan(int64_t A, int32_t S) {
+  SupportPlan pl{};
+  pl.cells = A * S;
+  pl.off_sum = kSupHeader;
+  pl.off_count = pl.off_sum + align_up((size_t)pl.cells * 8, 256);
+  pl.total = pl.off_count + align_up((size_t)pl.cells * 8, 256);
+  return pl;
+}
+
+__global__ __launch_bounds__(256) void subset_support_init_kernel(unsigned long long* __restrict__ p, int64_t n8) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) p[i] = 0ull;
+}
+
+// Every lane of a wavefront runs the whole body: the trip counts depend on the block's run only, the ballots read all 64 lanes.
+__global__ __launch_bounds__(256) void subset_support_update_kernel(unsigned long long* __restrict__ counters, unsigned long long* __restrict__ sum,
+                                                                    unsigned long long* __restrict__ cnt, int32_t S, int32_t m, uint64_t cm, float vmax,
+                                                                    const float* __restrict__ value, const int32_t* __restrict__ skip, int64_t n,
+                                                                    int64_t g0) {
+  __shared__ unsigned long long tsum[kSupTile], tcnt[kSupTile];
+  const int lane = threadIdx.x & (kWave - 1);
+  const uint64_t tile_clusters = (uint64_t)(kSupTile / S);              // >= 32
+  uint32_t n_rows = 0, n_rej = 0;                                       // this wavefront's totals (identical in every lane)
+  const int64_t runs = (n + kSupRun - 1) / kSupRun;
+  for (int64_t run = blockIdx.x; run < runs; run += gridDim.x) {
+    const int64_t i0 = run * kSupRun;
+    const int len = n - i0 < kSupRun ? (int)(n - i0) : kSupRun;
+    const uint64_t a_first = (uint64_t)(g0 + i0) / cm, a_last = (uint64_t)(g0 + i0 + len - 1) / cm;
+    const uint64_t span = a_last - a_first + 1 < tile_clusters ? a_last - a_first + 1 : tile_clusters;
+    const int cells = (int)span * S;                                    // <= kSupTile
+    for (int e = threadIdx.x; e < cells; e += 256) { tsum[e] = 0ull; tcnt[e] = 0ull; }
+    __syncthreads();
+    for (int off = 0; off < len; off += 256) {
+      const int at = off + (int)threadIdx.x;
+      float v = 0.f;
+      bool live = false, rejected = false;
+      if (at < len) {
+        const bool skipped = skip && skip[i0 + at] != 0;
+        v = value[i0 + at];
+        const bool okv = v >= 0.f && v <= vmax;                         // false for NaN
+        live = !skipped && okv;
+        rejected = !skipped && !okv;
+      }
+      n_rows += (uint32_t)__popcll(__ballot(live));
+      n_rej += (uint32_t)__popcll(__ballot(rejected));
+      if (live) {
+        v = v + 0.f;                                                    // -0.0 -> +0.0
+        const unsigned long long q = (unsigned long long)__double2ll_rn((double)v * 4294967296.0);
+        uint64_t a, r;
+        split_rank((uint64_t)(g0 + i0 + at), cm, a, r);
+        int32_t y[kMaxK] = {0, 0, 0, 0, 0, 0, 0, 0};
+        unrank(r, cm, S, m, y);
+        const uint64_t rel = a - a_first;
+        const bool tiled = rel < span;
+#pragma unroll
+        for (int c = 0; c < kMaxK; ++c) {
+          if (c < m) {
+            if (tiled) {
+              const int e = (int)rel * S + y[c];                        // < span S
+              atomicAdd(&tsum[e], q);
+              atomicAdd(&tcnt[e], 1ull);
+            } else {
+              const uint64_t e = a * (uint64_t)S + (uint64_t)y[c];      // a < A: the host checked g0 + n <= A cm
+              atomicAdd(sum + e, q);
+              atomicAdd(cnt + e, 1ull);
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < cells; e += 256) {
+      const unsigned long long c = tcnt[e];
+      if (c) {
+        atomicAdd(sum + a_first * (uint64_t)S + (uint64_t)e, tsum[e]);
+        atomicAdd(cnt + a_first * (uint64_t)S + (uint64_t)e, c);
+      }
+    }
+    __syncthreads();                                                    // the tile is reused by the next run
+  }
+  if (lane == 0) {
+    if (n_rows) atomicAdd(counters, (unsigned long long)n_rows);
+    if (n_rej) atomicAdd(counters + 1, (unsigned long long)n_rej);
+  }
+}
+
+__global__ __launch_bounds__(256) void subset_support_read_kernel(const unsigned long long* __restrict__ counters, const unsigned long long* __restrict__ sum,
+                                                                  const unsigned long long* __restrict__ cnt, int64_t cells, int64_t* __restrict__ sum_out,
+                                                                  int64_t* __restrict__ count_out, int64_t* __restrict__ counters_out) {
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < cells; p += (int64_t)gridDim.x * 256) {
+    if (sum_out) sum_out[p] = (int64_t)sum[p];
+    if (count_out) count_out[p] = (int64_t)cnt[p];
+  }
+  if (counters_out && blockIdx.x == 0 && threadIdx.x < 2) counters_out[threadIdx.x] = (int64_t)counters[threadIdx.x];
+}
+
+}  // namespace
+}  // namespace matcha
+
+extern "C" int64_t matcha_cluster_subset_count(int64_t A, int32_t S, int32_t m, int32_t complement) { return subset_count(A, S, m, complement, nullptr); }
+
+extern "C" int matcha_cluster_subset_rows(const int64_t* clusters, int64_t A, int32_t S, int32_t m, int32_t complement, int32_t min_gap, int64_t rank0,
+                                          const int64_t* ranks, int64_t count, int32_t L, int64_t* x, int32_t* flag, matcha_stream_t stream) {
+  MATCHA_CHECK_ARG(subset_args_ok(A, S, m, complement),
+                   "matcha_cluster_subset_rows: need A >= 0, 2 <= S <= %d, complement 0 (keep, 2 <= m <= %d) or 1 (drop, 1 <= m <= %d) "
+                   "(A=%lld S=%d m=%d complement=%d)", kMaxWide, kMaxK, kMaxK, (long long)A, S, m, complement);
+  MATCHA_CHECK_ARG(min_gap >= 1, "matcha_cluster_subset_rows: min_gap=%d must be >= 1", min_gap);
+  const int32_t l_min = complement ? (S - m > 1 ? S - m : 1) : m;
+  MATCHA_CHECK_ARG(L >= l_min && L <= kMaxWide, "matcha_cluster_subset_rows: row width L=%d must be in [%d, %d] (keep: m, drop: S - m)", L, l_min, kMaxWide);
+  int64_t cm = 0;
+  const int64_t total = subset_count(A, S, m, complement, &cm);
+  MATCHA_CHECK_ARG(total >= 0, "matcha_cluster_subset_rows: A C(S, m) does not fit 63 bits (A=%lld S=%d m=%d)", (long long)A, S, m);
+  MATCHA_CHECK_ARG(count >= 0 && count <= ((int64_t)1 << 40), "matcha_cluster_subset_rows: count out of range");
+  if (!ranks)
+    MATCHA_CHECK_ARG(rank0 >= 0 && rank0 <= total && count <= total - rank0,
+                     "matcha_cluster_subset_rows: %lld ranks from %lld lie outside [0, %lld)", (long long)count, (long long)rank0, (long long)total);
+  if (count == 0) return MATCHA_OK;
+  MATCHA_CHECK_ARG(x && flag, "matcha_cluster_subset_rows: null output");
+  MATCHA_CHECK_ARG(clusters || total == 0, "matcha_cluster_subset_rows: null clusters");
+  int64_t blocks = cdiv(count, kRowsPerBlock);
+  if (blocks > (1 << 20)) blocks = 1 << 20;
+  hipLaunchKernelGGL(cluster_subset_rows_kernel, dim3((unsigned)blocks), dim3(kRowsPerBlock), 0, (hipStream_t)stream, clusters, S, m, complement, min_gap,
+                     (uint64_t)cm, (uint64_t)total, rank0, ranks, count, L, x, flag);
+  MATCHA_CHECK_LAUNCH("cluster_subset_rows_kernel");
+  return MATCHA_OK;
+}
+
+extern "C" size_t matcha_subset_support_bytes(int64_t A, int32_t S, int32_t m, float vmax) {
+  if (!support_args_ok(A, S, m, vmax)) return 0;
+  return make_splan(A, S).total;
+}
+
+#define SUPPORT_COMMON_ARGS(fn)                                                                                                     \
+  MATCHA_CHECK_ARG(state, fn ": null state");                                                                                       \
+  MATCHA_CHECK_ARG(support_args_ok(A, S, m, vmax), fn ": need 1 <= A <= 2^40, 2 <= S <= %d, 1 <= m <= %d, 0 < vmax <= 2^20 "        \
+                                                      "(A=%lld S=%d m=%d vmax=%g)",                                                 \
+                   kMaxWide, kMaxK, (long long)A, S, m, (double)vmax);                                                              \
+  MATCHA_CHECK_ARG(((uintptr_t)state) % 8 == 0, fn ": state must be 8-byte aligned");                                               \
+  const SupportPlan pl = make_splan(A, S);                                                                                          \
+  MATCHA_CHECK_ARG(bytes >= pl.total, fn ": state too small (%zu bytes, matcha_subset_support_bytes says %zu)", bytes, pl.total)
+
+extern "C" int matcha_subset_support_init(void* state, size_t bytes, int64_t A, int32_t S, int32_t m, float vmax, matcha_stream_t stream) {
+  SUPPORT_COMMON_ARGS("matcha_subset_support_init");
+  const int64_t n8 = (int64_t)(pl.total / 8);                            // every offset is a multiple of 256
+  int64_t blocks = cdiv(n8, 256);
+  if (blocks > (1 << 14)) blocks = 1 << 14;
+  hipLaunchKernelGGL(subset_support_init_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (unsigned long long*)state, n8);
+  MATCHA_CHECK_LAUNCH("subset_support_init_kernel");
+  return MATCHA_OK;
+}
+
+extern "C" int matcha_subset_support_update(void* state, size_t bytes, int64_t A, int32_t S, int32_t m, float vmax, const float* value,
+                                            const int32_t* skip, int64_t n, int64_t g0, matcha_stream_t stream) {
+  SUPPORT_COMMON_ARGS("matcha_subset_support_update");
+  const int64_t cm = count_subsets(S, m);
+  const int64_t total = A * cm;                                          // < 2^40 * 2^24
+  MATCHA_CHECK_ARG(n >= 0 && n <= ((int64_t)1 << 40), "matcha_subset_support_update: n=%lld out of range", (long long)n);
+  MATCHA_CHECK_ARG(g0 >= 0 && g0 <= total && n <= total - g0, "matcha_subset_support_update: %lld ranks from %lld lie outside [0, %lld)", (long long)n,
+                   (long long)g0, (long long)total);
+  if (n == 0) return MATCHA_OK;
+  MATCHA_CHECK_ARG(value, "matcha_subset_support_update: null value");
+  char* w = (char*)state;
+  int64_t blocks = cdiv(n, kSupRun);
+  if (blocks > (1 << 14)) blocks = 1 << 14;
+  hipLaunchKernelGGL(subset_support_update_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (unsigned long long*)w,
+                     (unsigned long long*)(w + pl.off_sum), (unsigned long long*)(w + pl.off_count), S, m, (uint64_t)cm, vmax, value, skip, n, g0);
+  MATCHA_CHECK_LAUNCH("subset_support_update_kernel");
+  return MATCHA_OK;
+}
+
+extern "C" int matcha_subset_support_read(const void* state, size_t bytes, int64_t A, int32_t S, int32_t m, float vmax, int64_t* sum_out,
+                                          int64_t* count_out, int64_t* counters_out, matcha_stream_t stream) {
+  SUPPORT_COMMON_ARGS("matcha_subset_support_read");
+  MATCHA_CHECK_ARG(sum_out || count_out || counters_out, "matcha_subset_support_read: null output");
+  const char* w = (const char*)state;
+  int64_t blocks = cdiv(pl.cells, 256);
+  if (blocks > (1 << 14)) blocks = 1 << 14;
+  hipLaunchKernelGGL(subset_support_read_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)w,
+                     (const unsigned long long*)(w + pl.off_sum), (const unsigned long long*)(w + pl.off_count), pl.cells, sum_out, count_out,
+                     counters_out);
+  MATCHA_CHECK_LAUNCH("subset_support_read_kernel");
+  return MATCHA_OK;
+}

@@ -15,6 +15,7 @@ CLI:  python -m matcha_amd.predict multiway -i interactions.txt -o output.txt
       python -m matcha_amd.predict kway --chrom 0 --k 3 --top 1000 [--start-bin A --end-bin B] [--exclude-known] -o top.tsv
       python -m matcha_amd.predict anchored --k 3 --top 20 --chrom 5 (--anchor-file loci.tsv | --anchor-chrom 0) -o anchored.tsv
       python -m matcha_amd.predict complete -i clusters.txt --chrom 5 [--free 1] --top 20 [--width W] [--exclude-known] -o complete.tsv
+      python -m matcha_amd.predict decompose -i clusters.txt --size 3 [--drop] [--min-gap G] --top 20 [--width W] [--exclude-known] -o decompose.tsv
       python -m matcha_amd.predict kmap --chrom 0 --k 3 [--start-bin A --end-bin B] [--threshold 0.5] [--exclude-known] -o map.npz
       python -m matcha_amd.predict attention -i interactions.txt -o attn.npz [--per-head]
 (all read ./config.JSON like the reference: temp_dir, resolution, chrom_list, min_distance).
@@ -26,6 +27,11 @@ CLI:  python -m matcha_amd.predict multiway -i interactions.txt -o output.txt
 * ``complete`` -- cluster completion (matcha_amd/sweep.py): for every line of ``-i``, a cluster of 1 to 31 loci, the
   best ``--top`` bins (or sets of ``--free`` bins) of ``--chrom`` to add to it; per kept candidate the cluster's line number, the
   added loci and the probability.
+* ``decompose`` -- cluster decomposition (matcha_amd/sweep.py): for every line of ``-i``, a cluster of 2 to 32 loci,
+  the best ``--top`` sub-hyperedges of ``--size`` of its own loci, or with ``--drop`` the cluster with ``--size`` loci taken out; per
+  kept candidate the cluster's line number, the chosen (kept or dropped) loci and the probability, with ``--drop`` also its change
+  against the whole cluster.  ``<output>_support.tsv`` holds one line per cluster locus -- the mean probability and the number of the
+  candidates whose choice contains it -- and a ``.npz`` beside them every returned tensor.
 * ``kmap`` -- the pair map of matcha_amd/sweep.py: the probabilities of ALL candidates of size k of one chromosome (or bin window)
   projected onto pairs of bins -- per pair the summed probability, the mean, the best candidate, the number of candidates and the
   number at or above ``--threshold`` -- written as one .npz of [n, n] matrices.
@@ -336,12 +342,15 @@ def _anchored(args, config, temp_dir, model):
           % (len(anchors), out["n_candidates"], out["n_invalid"], out["n_excluded"], int(count.sum()), args.output))
 
 
-def parse_cluster_file(filepath: str, bin2node: Dict[str, int], chrom_list: Sequence[str], res: int, free: int = 1) -> Tuple[List[List[int]], List[int]]:
+def parse_cluster_file(filepath: str, bin2node: Dict[str, int], chrom_list: Sequence[str], res: int, free: int = 1,
+                       least: int = 1, most: Optional[int] = None) -> Tuple[List[List[int]], List[int]]:
     """(clusters, line numbers): one cluster per line, 1 to 31 tab-separated ``chrom:position`` loci with parse_file's coordinate
     handling (items of unknown chromosomes are skipped, positions floored to their bin, node ids de-duplicated and sorted; an item
     without ``:`` raises EOFError, an unknown bin KeyError).  Lines may differ in length; a line that leaves no locus is dropped.  A
-    line with more than 31 distinct bins, or with more than 32 - free, raises ValueError naming its 1-based number."""
-    most = min(_lib.MAX_LONG_L - 1, _lib.MAX_LONG_L - int(free))
+    line with more than 31 distinct bins, or with more than 32 - free, raises ValueError naming its 1-based number.  ``least`` /
+    ``most`` (``decompose``: 2 and 32) replace those bounds: a line with a locus but fewer than ``least`` distinct bins raises too."""
+    given = most is not None
+    most = min(_lib.MAX_LONG_L - 1, _lib.MAX_LONG_L - int(free)) if most is None else int(most)
     clusters, lines = [], []
     with open(filepath, "r") as f:
         for lineno, line in enumerate(f, 1):
@@ -358,6 +367,8 @@ def parse_cluster_file(filepath: str, bin2node: Dict[str, int], chrom_list: Sequ
                 b = int(math.floor(int(bin_) / res)) * res
                 temp.append(bin2node["%s:%d" % (chrom, b)])
             temp = sorted(set(temp))
+            if given and temp and not least <= len(temp) <= most:
+                raise ValueError("%s: line %d has %d distinct bins: a cluster holds %d to %d" % (filepath, lineno, len(temp), least, most))
             if len(temp) > most:
                 raise ValueError("%s: line %d has %d distinct bins: a cluster completed by %d free bin(s) holds at most %d"
                                  % (filepath, lineno, len(temp), int(free), most))
@@ -406,6 +417,52 @@ def _complete(args, config, temp_dir, model):
     np.savez(os.path.splitext(args.output)[0] + ".npz", clusters=table, rows=rows, added=added, logit=out["logit"].cpu().numpy(), proba=proba,
              rank=out["rank"].cpu().numpy(), count=count)
     print("%d anchors, %d candidates (%d against the gap rule, %d known, skipped) -> %d in %s"
+          % (len(clusters), out["n_candidates"], out["n_invalid"], out["n_excluded"], int(count.sum()), args.output))
+
+
+def _decompose(args, config, temp_dir, model):
+    from . import sweep as SW
+    from .sampler import HyperedgeSet
+    if not (1 if args.drop else 2) <= args.size <= _lib.MAX_L:
+        raise ValueError("--size must be in %d .. %d" % (1 if args.drop else 2, _lib.MAX_L))
+    node2bin = np.load(os.path.join(temp_dir, "node2bin.npy"), allow_pickle=True).item()
+    bin2node = {v: key for key, v in node2bin.items()}
+    clusters, lines = parse_cluster_file(args.file, bin2node, config["chrom_list"], config["resolution"], least=2,
+                                         most=_lib.MAX_LONG_L)                                  # before anything is scored
+    dev = model.layer_norm1.weight.device
+    exclude = None
+    if args.exclude_known:      # a candidate of a cluster of s loci has --size loci (keep) or s - size (drop): every size present, one set
+        known = []
+        for k in sorted({len(c) - args.size for c in clusters} if args.drop else {args.size}):
+            path = os.path.join(temp_dir, "all_%d_counter.npy" % k)
+            if k >= 2 and os.path.exists(path):
+                rows = np.load(path).astype(np.int64).reshape(-1, k)
+                known.append(np.pad(rows, ((0, 0), (0, _lib.MAX_LONG_L - k))))
+        if not known:
+            raise FileNotFoundError("--exclude-known: no all_<k>_counter.npy in %s for the candidate sizes of %s" % (temp_dir, args.file))
+        exclude = HyperedgeSet(torch.from_numpy(np.concatenate(known)).to(dev))
+    table = np.zeros((len(clusters), max([len(c) for c in clusters] + [2])), dtype=np.int64)
+    for a, c in enumerate(clusters):
+        table[a, :len(c)] = c
+    min_gap = int(config["min_distance"]) + 1 if args.min_gap is None else args.min_gap
+    out = SW.decomposition_sweep(model, table, args.size, mode="drop" if args.drop else "keep", min_gap=min_gap, top=args.top,
+                                 chunk_rows=args.chunk_rows, width=args.width, exclude=exclude)
+    z = {key: v.cpu().numpy() for key, v in out.items() if isinstance(v, torch.Tensor)}
+    count = z["count"]
+    with open(args.output, "w") as f:
+        for a in range(len(clusters)):
+            for ids, p in zip(z["chosen"][a, :count[a]], z["proba"][a, :count[a]]):
+                cells = [str(lines[a])] + [node2bin[int(v)] for v in ids] + [repr(float(p))]
+                if args.drop:
+                    cells.append(repr(float(p) - float(z["full_proba"][a])))
+                f.write("\t".join(cells) + "\n")
+    base = os.path.splitext(args.output)[0]
+    with open(base + "_support.tsv", "w") as f:
+        for a, c in enumerate(clusters):
+            for j, v in enumerate(c):
+                f.write("\t".join([str(lines[a]), node2bin[int(v)], repr(float(z["support_mean"][a, j])), str(int(z["support_count"][a, j]))]) + "\n")
+    np.savez(base + ".npz", clusters=table, **z)
+    print("%d clusters, %d candidates (%d against the gap rule, %d known, skipped) -> %d in %s"
           % (len(clusters), out["n_candidates"], out["n_invalid"], out["n_excluded"], int(count.sum()), args.output))
 
 
@@ -459,6 +516,17 @@ def main(argv=None):
     h.add_argument("--task-mode", choices=["class", "regress"], default="class", help="the model's training objective: sigmoid or softplus outputs")
     h.add_argument("-o", "--output", type=str, default="./complete.tsv")
     h.add_argument("--config", type=str, default="./config.JSON")
+    k = sub.add_parser("decompose", help="cluster decomposition: the best --top sub-hyperedges of --size loci of every cluster of 2 .. 32 loci, or (--drop) the cluster without them")
+    k.add_argument("-i", "--file", type=str, required=True, help="one cluster per line: 2 .. 32 tab-separated chrom:position loci; lines may differ in length")
+    k.add_argument("--size", type=int, required=True, help="how many of the cluster's loci a candidate keeps (2 .. 8) or, with --drop, leaves out (1 .. 8)")
+    k.add_argument("--drop", action="store_true", help="score the cluster with --size loci taken out, beside the whole cluster")
+    k.add_argument("--min-gap", type=int, default=None, help="smallest difference of adjacent node ids in a candidate (default: min_distance + 1)")
+    k.add_argument("--top", type=int, required=True, help="how many candidates to keep per cluster")
+    k.add_argument("--width", type=int, default=None, help="zero-pad rows to this width (default: --size, at most 8; --drop: the longest cluster, at most 32)")
+    k.add_argument("--exclude-known", action="store_true", help="skip the hyperedges of temp_dir/all_<k>_counter.npy, for every candidate size k present")
+    k.add_argument("--chunk-rows", type=int, default=None, help="rows per forward (default: 2^20 up to width 8, min(2^20, 2^21 // width) beyond)")
+    k.add_argument("-o", "--output", type=str, default="./decompose.tsv")
+    k.add_argument("--config", type=str, default="./config.JSON")
     e = sub.add_parser("kmap", help="pair map: the probabilities of all candidates of size --k projected onto pairs of bins")
     e.add_argument("--chrom", type=int, required=True, help="index into config chrom_list")
     e.add_argument("--k", type=int, required=True, help="candidate size, 2 .. 8")
@@ -487,6 +555,8 @@ def main(argv=None):
         return _anchored(args, config, temp_dir, model)
     if args.cmd == "complete":
         return _complete(args, config, temp_dir, model)
+    if args.cmd == "decompose":
+        return _decompose(args, config, temp_dir, model)
     if args.cmd == "kmap":
         return _kmap(args, config, temp_dir, model)
     if args.cmd == "attention":

@@ -12,7 +12,9 @@ rank of one is its position, from 0.  With m = n - (k - 1)(min_gap - 1), y_j = x
 preserved, onto the k-subsets of [0, m): C(m, k) candidates.
 
 ``anchored_sweep`` keeps the best K per anchor instead of one global list; ``kway_map`` / ``PairMap`` (DESIGN.md 7.5,
-csrc/pairmap.hip) project the scores of all candidates onto pairs of bins instead of keeping a list at all.
+csrc/pairmap.hip) project the scores of all candidates onto pairs of bins instead of keeping a list at all.  ``completion_sweep``
+ extends clusters of 1 to 31 loci by bins of a region; ``decomposition_sweep`` ranks the sub-hyperedges
+made of a cluster's own loci, or the cluster with some of them taken out, and sums the scores per locus (``SubsetSupport``).
 """
 from __future__ import annotations
 
@@ -681,8 +683,9 @@ def completion_unrank(rank: int, cluster, lo: int, n: int, free: int, min_gap: i
     return row, bool(ids) and ascending and all(b - a >= min_gap for a, b in zip(row, row[1:]))
 
 
-def _cluster_table(clusters, device) -> Tuple[torch.Tensor, int]:
+def _cluster_table(clusters, device, limit: Optional[int] = None) -> Tuple[torch.Tensor, int]:
     """(int64 [A, S] on the device, max_a s_a): every row's non-zero ids sorted ascending, zeros last, S = max(1, max_a s_a).
+    ``limit``: the most ids a cluster may hold, default MAX_CLUSTER (completion adds a node; decomposition, which adds none, passes 32).
     ``clusters``: a list of id lists (of any lengths), or an integer array / tensor zero-padded to a common width (1-D = single ids).
     Host inputs are measured on the host; a device tensor costs one small read-back (its longest row), before anything is launched
     by the library."""
@@ -705,8 +708,9 @@ def _cluster_table(clusters, device) -> Tuple[torch.Tensor, int]:
     if t.shape[1] == 0:
         t = torch.zeros(t.shape[0], 1, dtype=torch.long, device=t.device)
     s_max = int((t != 0).sum(dim=1).max()) if t.shape[0] else 0
-    if s_max > MAX_CLUSTER:
-        raise ValueError(f"a cluster has {s_max} ids: at most {MAX_CLUSTER} are supported")
+    limit = MAX_CLUSTER if limit is None else int(limit)
+    if s_max > limit:
+        raise ValueError(f"a cluster has {s_max} ids: at most {limit} are supported")
     t = t.to(device)
     big = torch.iinfo(torch.long).max                                    # zeros behind every id, then back to zero
     t = torch.where(t == 0, torch.full_like(t, big), t).sort(dim=1).values[:, :max(s_max, 1)]
@@ -853,3 +857,330 @@ def completion_sweep(model, clusters, lo: int, hi: int, free: int = 1, min_gap: 
     return {"rows": rows.view(A, K, width), "logit": logit, "proba": proba, "rank": rank, "count": count,
             "added": added.view(A, K, free + 1)[:, :, :free].contiguous(), "n_candidates": total, "n_invalid": int(n_inv.item()),
             "n_excluded": int(n_exc.item())}
+
+
+# ---- cluster decomposition: the sub-hyperedges of clusters of up to 32 loci ------------------------------------------
+MAX_SUBSET_CLUSTER = _lib.MAX_LONG_L       # nothing is added to a cluster here, so it may fill a row of 32
+_MODES = {"keep": 0, "drop": 1}
+
+
+def _check_subset_args(A: int, S: int, m: int, complement: int):
+    if not (A >= 0 and 2 <= S <= MAX_SUBSET_CLUSTER and complement in (0, 1) and (1 if complement else 2) <= m <= _lib.MAX_L):
+        raise ValueError(f"need A >= 0, 2 <= S <= {MAX_SUBSET_CLUSTER}, complement 0 (keep, 2 <= m <= {_lib.MAX_L}) or 1 (drop, 1 <= m <= {_lib.MAX_L}) "
+                         f"(A={A} S={S} m={m} complement={complement})")
+
+
+def subset_count(A: int, S: int, m: int, complement: int = 0) -> int:
+    """Number of global ranks of a cluster table [A, S]: A * C(S, m), the m-subsets of the S positions of every row; a total >= 2^63
+    is refused (ValueError), not truncated."""
+    A, S, m, complement = int(A), int(S), int(m), int(complement)
+    _check_subset_args(A, S, m, complement)
+    total = A * math.comb(S, m)
+    if total >= 1 << 63:
+        raise ValueError(f"{total} candidates (A={A} S={S} m={m}) do not fit 63 bits")
+    return total
+
+
+def _choice_unrank(rank: int, S: int, m: int) -> Tuple[int, ...]:
+    """The m-subset of the positions [0, S) of lexicographic rank ``rank``, as kway_unrank reads it off the combinatorial number system."""
+    pos, q, upper = [], math.comb(S, m) - 1 - rank, S - 1
+    for j in range(m, 0, -1):
+        a, b = j - 1, upper
+        while a < b:
+            mid = (a + b + 1) // 2
+            if math.comb(mid, j) <= q:
+                a = mid
+            else:
+                b = mid - 1
+        q -= math.comb(a, j)
+        pos.append(S - 1 - a)
+        upper = a - 1
+    return tuple(pos)
+
+
+def subset_unrank(rank: int, cluster, m: int, complement: int = 0, min_gap: int = 1) -> Tuple[Tuple[int, ...], bool]:
+    """(row, valid) of the candidate of CHOICE rank ``rank`` of one cluster row (a global rank g is cluster g // C(S, m), choice rank
+    g % C(S, m)), in Python integers (no GPU).  ``cluster``: a row of the table, S = its length (at least 2): its ids are the run
+    before the first zero.  The choice is the m-subset of the positions [0, S) of that lexicographic rank; the row is the ids at the
+    chosen positions (complement 0, keep) or at all others (complement 1, drop), in position order.  It is valid iff every chosen
+    position holds an id, the row has at least 2 ids, the cluster's ids are non-descending and every adjacent difference of the row
+    is >= min_gap.  A choice that reaches past the ids gives the empty row, invalid."""
+    cluster = [int(v) for v in cluster]
+    S, m, complement, min_gap, rank = max(len(cluster), 2), int(m), int(complement), int(min_gap), int(rank)
+    _check_subset_args(1, S, m, complement)
+    if min_gap < 1:
+        raise ValueError("min_gap must be >= 1")
+    total = math.comb(S, m)
+    if not 0 <= rank < total:
+        raise IndexError(f"rank {rank} outside [0, {total})")
+    ids = []
+    for v in cluster:
+        if v == 0:
+            break
+        ids.append(v)
+    pos = _choice_unrank(rank, S, m)
+    if any(p >= len(ids) for p in pos):
+        return (), False
+    chosen = set(pos)
+    row = tuple(ids[p] for p in range(len(ids)) if (p in chosen) != bool(complement))
+    ascending = all(a <= b for a, b in zip(ids, ids[1:]))
+    return row, len(row) >= 2 and ascending and all(b - a >= min_gap for a, b in zip(row, row[1:]))
+
+
+def _subset_table(clusters, device) -> Tuple[torch.Tensor, int]:
+    """_cluster_table for clusters of up to 32 ids, at least 2 columns wide."""
+    t, s_max = _cluster_table(clusters, device, limit=MAX_SUBSET_CLUSTER)
+    if t.shape[1] < 2:
+        t = torch.cat([t, torch.zeros(t.shape[0], 2 - t.shape[1], dtype=torch.long, device=t.device)], dim=1).contiguous()
+    return t, s_max
+
+
+def _subset_rows(table: torch.Tensor, m: int, complement: int, min_gap: int, rank0: int, count: Optional[int], ranks, width: int, out,
+                 flag_out) -> Tuple[torch.Tensor, torch.Tensor]:
+    """matcha_cluster_subset_rows on a table that is already in the library's form."""
+    lib = _lib.load()
+    A, S = int(table.shape[0]), int(table.shape[1])
+    total = subset_count(A, S, m, complement)
+    if min_gap < 1:
+        raise ValueError("min_gap must be >= 1")
+    least = max(S - m, 1) if complement else m
+    if not least <= width <= _lib.MAX_LONG_L:
+        raise ValueError(f"width must be in [{least}, {_lib.MAX_LONG_L}] (keep: m, drop: S - m; got {width})")
+    if ranks is not None:
+        count = int(ranks.numel())
+    else:
+        count = total - int(rank0) if count is None else int(count)
+        if rank0 < 0 or count < 0 or rank0 + count > total:
+            raise IndexError(f"ranks [{rank0}, {rank0 + count}) outside [0, {total})")
+    device = table.device
+    if out is None:
+        x = torch.empty(count, width, dtype=torch.long, device=device)
+    else:
+        if out.dtype != torch.long or not out.is_contiguous() or out.numel() < count * width or out.device != device:
+            raise ValueError("out must be a contiguous int64 tensor of at least count * width elements on the clusters' device")
+        x = out.view(-1)[:count * width].view(count, width)
+    if flag_out is None:
+        flag = torch.empty(count, dtype=torch.int32, device=device)
+    else:
+        if flag_out.dtype != torch.int32 or not flag_out.is_contiguous() or flag_out.numel() < count or flag_out.device != device:
+            raise ValueError("flag_out must be a contiguous int32 tensor of at least count elements on out's device")
+        flag = flag_out.view(-1)[:count]
+    if not x.is_cuda:
+        raise _lib.MatchaHipError("subset_rows needs a cuda device (no CPU fallback)")
+    with torch.cuda.device(device):
+        _lib.check(lib.matcha_cluster_subset_rows(_lib.ptr(table), A, S, m, complement, min_gap, int(rank0), _lib.ptr(ranks), count, width,
+                                                  _lib.ptr(x), _lib.ptr(flag), _stream(device)), "matcha_cluster_subset_rows")
+    return x, flag
+
+
+def subset_rows(clusters, m: int, complement: int = 0, min_gap: int = 1, rank0: int = 0, count: Optional[int] = None,
+                ranks: Optional[torch.Tensor] = None, width: Optional[int] = None, device="cuda", out: Optional[torch.Tensor] = None,
+                flag_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(x int64 [count, width], flag int32 [count]) on the device: the candidates of the global ranks rank0 .. rank0 + count - 1, or
+    of the device list ``ranks`` (a rank outside [0, A * C(S, m)) gives an all-zero row with its flag set); flag != 0 marks an
+    invalid candidate.  ``clusters``: a list of id lists of 0 to 32 ids each, or an integer [A, S] array / tensor zero-padded (each
+    row is sorted here, zeros last); S = the longest cluster, at least 2.  ``width``: keep, from m (the default) to 32; drop, from
+    S - m to 32, default S.  ``out`` / ``flag_out`` reuse buffers of at least count * width / count elements."""
+    if isinstance(clusters, torch.Tensor) and clusters.is_cuda and ranks is None and out is None:
+        device = clusters.device
+    if ranks is not None:
+        ranks = ranks.to(device=device, dtype=torch.long).contiguous().view(-1)
+        device = ranks.device
+    elif out is not None:
+        device = out.device
+    m, complement, min_gap = int(m), int(complement), int(min_gap)
+    _check_subset_args(0, 2, m, complement)
+    table, _ = _subset_table(clusters, device)
+    width = int((table.shape[1] if complement else m) if width is None else width)
+    return _subset_rows(table, m, complement, min_gap, rank0, count, ranks, width, out, flag_out)
+
+
+class SubsetSupport:
+    """Per-locus support on the device (csrc/sweep.hip's subset_support_update_kernel): for the ``A`` clusters of a table [A, S] and
+    choices of ``m`` positions, two int64 planes [A, S] -- over the accepted rows whose choice contains the position, the sum of their
+    values in PairMap's fixed point (32 fractional bits) and their number.  Integer atomics only: bit for bit the same whatever the
+    order of the updates and however the ranks were cut into them.  ``vmax``: the largest value accepted, 0 < vmax <= 2^20."""
+
+    def __init__(self, A: int, S: int, m: int, vmax: float = 1.0, device="cuda"):
+        lib = _lib.load()
+        self.A, self.S, self.m, self.vmax = int(A), int(S), int(m), float(vmax)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.MatchaHipError("SubsetSupport needs a cuda device (no CPU fallback)")
+        fits = 1 <= self.A <= 1 << 40 and abs(self.S) < 1 << 31 and abs(self.m) < 1 << 31
+        self._dims = (self.A, self.S, self.m, self.vmax)
+        self.bytes = int(lib.matcha_subset_support_bytes(*self._dims)) if fits else 0
+        if self.bytes == 0:
+            raise ValueError(f"SubsetSupport: need 1 <= A <= 2^40, 2 <= S <= {MAX_SUBSET_CLUSTER}, 1 <= m <= {_lib.MAX_L} and 0 < vmax <= 2^20 "
+                             f"(A={A} S={S} m={m} vmax={vmax})")
+        self.state = torch.empty(self.bytes, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(lib.matcha_subset_support_init(_lib.ptr(self.state), self.bytes, *self._dims, _stream(self.device)), "matcha_subset_support_init")
+
+    def update(self, value: torch.Tensor, g0: int, skip: Optional[torch.Tensor] = None):
+        """``value`` float32 [n] on the device, row i of global rank g0 + i (cluster (g0 + i) // C(S, m), the choice of the remainder);
+        ``skip`` int32 / bool [n], non-zero = the row contributes nothing.  A row whose value is NaN, negative or > vmax is counted as
+        rejected.  Enqueued on the current stream; nothing is read back."""
+        lib = _lib.load()
+        value = value.reshape(-1)
+        if value.dtype != torch.float32 or value.device != self.state.device:
+            raise ValueError("value must be a float32 tensor on the SubsetSupport's device")
+        value = value.contiguous()
+        if skip is not None:
+            skip = skip.reshape(-1).to(device=value.device, dtype=torch.int32).contiguous()
+            if skip.numel() != value.numel():
+                raise ValueError("skip and value differ in length")
+        with torch.cuda.device(self.device):
+            _lib.check(lib.matcha_subset_support_update(_lib.ptr(self.state), self.bytes, *self._dims, _lib.ptr(value), _lib.ptr(skip),
+                                                        value.numel(), int(g0), _stream(self.device)), "matcha_subset_support_update")
+
+    def read(self) -> dict:
+        """'sum' int64 [A, S] (fixed point, value * 2^32), 'count' int64 [A, S] and 'counters' int64 [2] = (accepted rows, rejected
+        rows), on the device and without a synchronisation."""
+        lib = _lib.load()
+        total = torch.empty(self.A, self.S, dtype=torch.long, device=self.device)
+        count = torch.empty(self.A, self.S, dtype=torch.long, device=self.device)
+        counters = torch.empty(2, dtype=torch.long, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(lib.matcha_subset_support_read(_lib.ptr(self.state), self.bytes, *self._dims, _lib.ptr(total), _lib.ptr(count),
+                                                      _lib.ptr(counters), _stream(self.device)), "matcha_subset_support_read")
+        return {"sum": total, "count": count, "counters": counters}
+
+
+def decomposition_sweep(model, clusters, m: int, mode: str = "keep", min_gap: int = 1, top: int = 20, chunk_rows: Optional[int] = None,
+                        width: Optional[int] = None, exclude=None, task_mode: str = "class", support: bool = True) -> dict:
+    """For every cluster (``clusters``: a list of id lists of up to 32 ids each, or a zero-padded integer [A, S] array / tensor) score
+    all candidates made of its OWN ids and keep the ``top`` best PER CLUSTER.  mode 'keep': the sub-hyperedges of ``m`` of its ids
+    (2 <= m <= 8) -- which triples or quadruples inside the cluster are real simultaneous contacts.  mode 'drop': the cluster with
+    ``m`` of its ids taken out (1 <= m <= 8) -- which locus does not belong -- scored beside the whole cluster.
+
+    The clusters are grouped by size and every size s is swept by itself (a table [A_s, s], C(s, m) candidates per cluster), so a
+    ragged file wastes no rank and no all-zero row is scored; results come back in the input order.  A cluster too small (keep:
+    s < m; drop: s - m < 2) never reaches the device and has count 0.  All groups are scored at ONE width (a logit depends on its
+    batch's width): keep, ``width`` from m (the default) to 8; drop, from the longest cluster (the default, at least 2) to 32.  Up
+    to 8 it is model(x)'s forward for short rows with the large-batch route pinned, beyond it the long forward.
+
+    Returns, on the model's device and best first within each cluster, with K = min(top, the largest C(s_a, m) swept): ``rows`` int64
+    [A, K, width], ``logit`` and ``proba`` [A, K], ``rank`` int64 [A, K] (the rank within C(s_a, m); decode with subset_unrank on the
+    cluster's s_a ids), ``count`` int64 [A] and ``chosen`` int64 [A, K, m]: the kept (keep) or dropped (drop) ids.  Beyond count[a]
+    the rank is -1 and everything else 0.  With ``support`` (task_mode 'class' only: the planes take the sigmoid's output):
+    ``support_sum`` float64 and ``support_count`` int64 [A, S_max] -- per locus of the cluster, the summed probability and the number
+    of the valid, non-excluded candidates whose choice contains it -- and ``support_mean`` float32, their quotient (0 where the count
+    is 0): in keep mode how credible the sub-hyperedges through the locus are, in drop mode how credible the cluster is without it.
+    In drop mode ``full_logit`` and ``full_proba`` [A]: the whole cluster at the same width (0 for a cluster not swept).  The
+    integers ``n_candidates``, ``n_invalid`` (candidates that break the gap rule; scored, never kept) and ``n_excluded`` (valid
+    candidates found in ``exclude``, a HyperedgeSet).
+
+    ``chunk_rows`` as in completion_sweep; the result does not depend on it, bit for bit.  The loop is completion_sweep's: eval mode,
+    no grad, reused buffers, nothing synchronises until the end, where the node-id check of the whole sweep is raised once."""
+    if task_mode not in ("class", "regress"):
+        raise ValueError("task_mode must be 'class' or 'regress'")
+    if mode not in _MODES:
+        raise ValueError("mode must be 'keep' or 'drop'")
+    if support and task_mode == "regress":
+        raise ValueError("the support planes take the sigmoid's output: task_mode 'regress' needs support=False")
+    complement = _MODES[mode]
+    m, min_gap, top = int(m), int(min_gap), int(top)
+    if not (1 if complement else 2) <= m <= _lib.MAX_L or min_gap < 1:
+        raise ValueError(f"need {1 if complement else 2} <= m <= {_lib.MAX_L} in mode '{mode}' and min_gap >= 1 (m={m} min_gap={min_gap})")
+    if top < 1 or (chunk_rows is not None and int(chunk_rows) < 1):
+        raise ValueError("top and chunk_rows must be >= 1")
+    act = torch.nn.functional.softplus if task_mode == "regress" else torch.sigmoid
+    model.eval()
+    dev = model.layer_norm1.weight.device
+    table, s_max = _subset_table(clusters, dev)
+    A, S_max = int(table.shape[0]), int(table.shape[1])
+    least, most = (max(s_max, 2), _lib.MAX_LONG_L) if complement else (m, _lib.MAX_L)
+    width = int(least if width is None else width)
+    if not least <= width <= most:
+        raise ValueError(f"width must be in [{least}, {most}] in mode '{mode}' (m = {m}, the longest cluster has {s_max} ids; got {width})")
+    if chunk_rows is None:
+        chunk_rows = 1 << 20 if width <= _lib.MAX_L else min(1 << 20, (1 << 21) // width)
+    else:
+        chunk_rows = int(chunk_rows)
+        if width > _lib.MAX_L:
+            rt = model._runtime()
+            if not 1 <= chunk_rows < 1 << 31 or rt.lib.matcha_workspace_bytes_long(C.byref(rt.shape), chunk_rows, width) == 0:
+                raise ValueError(f"chunk_rows = {chunk_rows} rows of {width} columns are more than the long forward takes in one call")
+    sizes = (table != 0).sum(dim=1).cpu() if A else torch.zeros(0, dtype=torch.long)      # one small read-back, before anything is launched
+    groups = []
+    for s in sorted(set(sizes.tolist())):
+        if (s - m >= 2) if complement else (s >= m):
+            idx = torch.nonzero(sizes == s).view(-1).to(dev)
+            groups.append((s, idx, math.comb(s, m)))
+    K = min(top, max([cm for _, _, cm in groups] + [0]))
+    out = {"rows": torch.zeros(A, K, width, dtype=torch.long, device=dev), "logit": torch.zeros(A, K, dtype=torch.float32, device=dev),
+           "proba": torch.zeros(A, K, dtype=torch.float32, device=dev), "rank": torch.full((A, K), -1, dtype=torch.long, device=dev),
+           "count": torch.zeros(A, dtype=torch.long, device=dev), "chosen": torch.zeros(A, K, m, dtype=torch.long, device=dev)}
+    if support:
+        out["support_sum"] = torch.zeros(A, S_max, dtype=torch.float64, device=dev)
+        out["support_count"] = torch.zeros(A, S_max, dtype=torch.long, device=dev)
+    if complement:
+        out["full_logit"] = torch.zeros(A, dtype=torch.float32, device=dev)
+    n_cand = sum(int(idx.numel()) * cm for _, idx, cm in groups)
+    if groups:
+        most_rows = min(chunk_rows, max(int(idx.numel()) * cm for _, idx, cm in groups))
+        buf = torch.empty(most_rows * width, dtype=torch.long, device=dev)
+        fbuf = torch.empty(most_rows, dtype=torch.int32, device=dev)
+    n_inv = torch.zeros((), dtype=torch.long, device=dev)
+    n_exc = torch.zeros((), dtype=torch.long, device=dev)
+    done = []
+    # One forward route, as in completion_sweep: the large-batch route pinned up to width 8, the long forward's single route beyond.
+    with torch.no_grad(), model.deferred_id_check(), _lib.option("disable_small_batch"):
+        for s, idx, cm in groups:
+            tab = table[idx, :s].contiguous()
+            A_s = int(tab.shape[0])
+            total = A_s * cm
+            chunk = min(chunk_rows, total)
+            sel = SegTopK(A_s, min(top, cm), cm, chunk, dev)
+            sup = SubsetSupport(A_s, s, m, 1.0, dev) if support else None
+            for g0 in range(0, total, chunk):
+                x, flag = _subset_rows(tab, m, complement, min_gap, g0, min(chunk, total - g0), None, width, buf, fbuf)
+                logits = model(x).reshape(-1)
+                skip = flag != 0
+                n_inv += skip.sum()
+                if exclude is not None:
+                    known = exclude.contains(x)
+                    n_exc += (known & ~skip).sum()
+                    skip = skip | known
+                sel.update(logits, g0, skip)
+                if sup is not None:
+                    sup.update(torch.sigmoid(logits), g0, skip)
+            done.append((s, idx, cm, tab, sel, sup))
+        if complement and groups:                                        # the whole clusters, all sizes in one batch: the sweep's width and route
+            swept = torch.cat([idx for _, idx, _ in groups])
+            whole = torch.zeros(int(swept.numel()), width, dtype=torch.long, device=dev)
+            whole[:, :S_max] = table[swept]                              # width >= S_max in drop mode
+            for a0 in range(0, int(swept.numel()), chunk_rows):
+                out["full_logit"][swept[a0:a0 + chunk_rows]] = model(whole[a0:a0 + chunk_rows]).reshape(-1)
+    for s, idx, cm, tab, sel, sup in done:
+        A_s, Ks = int(tab.shape[0]), min(top, cm)
+        logit, grank, count = sel.read()
+        rows, _ = _subset_rows(tab, m, complement, min_gap, 0, None, grank.view(-1), width, None, None)
+        kept = grank >= 0
+        rank = torch.where(kept, grank - torch.arange(A_s, dtype=torch.long, device=dev).view(-1, 1) * cm, grank)
+        if m == 1:                                                       # a choice of one position is its rank
+            chosen = torch.where(kept, tab.gather(1, rank.clamp(min=0)), torch.zeros_like(rank)).view(A_s, Ks, 1)
+        else:                                                            # the same ranks through the keep form of the rows kernel
+            chosen = _subset_rows(tab, m, 0, 1, 0, None, grank.view(-1), m, None, None)[0].view(A_s, Ks, m)
+        out["rows"][idx, :Ks] = rows.view(A_s, Ks, width)
+        out["logit"][idx, :Ks] = logit
+        out["proba"][idx, :Ks] = torch.where(kept, act(logit), torch.zeros_like(logit))
+        out["rank"][idx, :Ks] = rank
+        out["count"][idx] = count
+        out["chosen"][idx, :Ks] = chosen
+        if sup is not None:
+            planes = sup.read()
+            out["support_sum"][idx, :s] = planes["sum"].to(torch.float64) / 4294967296.0
+            out["support_count"][idx, :s] = planes["count"]
+    if support:
+        hit = out["support_count"] > 0
+        out["support_mean"] = torch.where(hit, out["support_sum"] / out["support_count"].clamp(min=1).to(torch.float64),
+                                          torch.zeros_like(out["support_sum"])).to(torch.float32)
+    if complement:
+        swept = torch.zeros(A, dtype=torch.bool, device=dev)
+        for _, idx, _, _, _, _ in done:
+            swept[idx] = True
+        out["full_proba"] = torch.where(swept, act(out["full_logit"]), torch.zeros_like(out["full_logit"]))
+    out.update(n_candidates=n_cand, n_invalid=int(n_inv.item()), n_excluded=int(n_exc.item()))
+    return out
