@@ -20,6 +20,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "bf16x3.hpp"
 #include "kernels.hpp"
 #include "tail_reduce.hpp"
@@ -34,6 +36,10 @@ namespace {
 constexpr int kLd = 68;              // LDS row stride (floats)
 // (kWgSlab / kVecOff -- the slab format dW'q dW'k dW'v dWfc1 | dcq dck dcv dKpad dVpad dfc1_b -- and ln_row16: fb_unfold.hpp)
 constexpr int kMaxChunks = 64;
+// buffer descriptor of the per-node adds (fused_bwdh_kernel): dword 3 of a raw gfx9 buffer of 32-bit data, and a byte offset that lies past the
+// range of every descriptor the launcher admits (< 2^31 bytes), so that the hardware drops the lane
+constexpr int kRsrcRaw32 = 0x00020000;
+constexpr uint32_t kOffPastAny = 0x80000000u;
 
 #define ZR8(p)                                                                                           \
   do {                                                                                                   \
@@ -386,14 +392,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     xn##I = *reinterpret_cast<const float4*>(g.X + (NODE ? (int64_t)kx##I : tok__) * 64 + sc4);           \
     dn##I = *reinterpret_cast<const float4*>(g.dDyn + tok__ * 64 + sc4);                                 \
   } while (0)
-#define FBH_ROWS_GLOAD(M)                                                                                \
+  // DXN (the per-node adds' walk, below): tok_pos and the key are loaded by EVERY thread (slot tid & 31, the index clamped as above) and in front
+  // of the rows -- a load under `tid < 32` behind them is one the compiler cannot count when it waits for the rows (see the walk)
+#define FBH_ROWS_GLOAD(M, DXN)                                                                           \
   do {                                                                                                   \
-    FBH_ROW_GLOAD(0, M); FBH_ROW_GLOAD(1, M);                                                            \
-    if (tid < 32) {                                                                                      \
-      const int i__ = (M).x + (tid < (M).y ? tid : ((M).y > 0 ? (M).y - 1 : 0));                         \
+    if ((DXN) || tid < 32) {                                                                             \
+      const int s__ = tid & 31;                                                                          \
+      const int i__ = (M).x + (s__ < (M).y ? s__ : ((M).y > 0 ? (M).y - 1 : 0));                         \
       tpn = g.tok_pos[i__];                                                                              \
-      if (VTAB && g.dx_node) kyn = g.xrow[i__];                                                          \
+      if ((DXN) || (VTAB && g.dx_node)) kyn = g.xrow[i__];                                               \
     }                                                                                                    \
+    FBH_ROW_GLOAD(0, M); FBH_ROW_GLOAD(1, M);                                                            \
   } while (0)
   // NODE with the r table: this head's r rows of the same two table rows, row-major like the x_hat rows (16 lanes per 256-byte row).  Issued
   // next to FBH_ROWS_GLOAD while kx0 / kx1 still hold that half tile's keys
@@ -453,7 +462,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   Frag3 Mf[2], Bf[2];
   {
     if constexpr (NODE) { FBH_KEY_GLOAD(0, mc); FBH_KEY_GLOAD(1, mc); }
-    FBH_ROWS_GLOAD(mc);
+    FBH_ROWS_GLOAD(mc, false);
     if constexpr (NODE) { if (r_tab) FBH_R_GLOAD(); FBH_KEY_GLOAD(0, mn); FBH_KEY_GLOAD(1, mn); }
     if (tile_lo < tile_hi) FBH_RIMG_GLOAD(tile_lo);
     const float* mp = g.mM + (int64_t)head * 4096 + (8 * kq) * 64 + fb + c16;
@@ -467,29 +476,40 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
   }
 
+  // ---- stage half tile M, whose rows wait in registers: the FIRST one here, every later one at the END of the iteration before it ----
+#define FBH_STAGE(M, DXN)                                                                                \
+  do {                                                                                                   \
+    const int n_real = (M).y;                                                                            \
+    FBH_ROW_STAGE(0); FBH_ROW_STAGE(1);                                                                  \
+    if (tid < 32) tinfo[tid] = tid < n_real ? ((tid - (tpn & 255)) | (tpn & ~255)) : 0;                  \
+    if (((DXN) || (VTAB && g.dx_node)) && tid < 32) keys_s[tid] = kyn;                                   \
+    if constexpr (VTAB) {                                                                                \
+      *reinterpret_cast<f32x4*>(&Fs[srow * kLd + sc4]) = yi0; *reinterpret_cast<f32x4*>(&Fs[(srow + 16) * kLd + sc4]) = yi1; \
+    }                                                                                                    \
+    if (r_tab) {                                                                                         \
+      *reinterpret_cast<f32x4*>(&Rs[srow * kLd + sc4]) = ri0; *reinterpret_cast<f32x4*>(&Rs[(srow + 16) * kLd + sc4]) = ri1; \
+    } else {                                                                                             \
+      f32x4* d__ = reinterpret_cast<f32x4*>(&Rs[(lane & 31) * kLd + 8 * wave + 4 * (lane >> 5)]);        \
+      d__[0] = ri0; d__[8] = ri1;                                                                        \
+    }                                                                                                    \
+    if (tid < 64) reinterpret_cast<f32x4*>(Ps)[tid] = pn;                                                \
+  } while (0)
+  if (tile_lo < tile_hi) FBH_STAGE(mc, false);        // (nothing has used the tiles yet: no barrier in front; xpad / ypad lie outside them)
+
+  // The walk is ROTATED: an iteration opens with the barrier behind the staging and closes with the staging of the NEXT half tile, so the
+  // staging block is entered from the loop body only.  Why: vmcnt retires in order and the compiler, when it waits for a staged load, counts the
+  // memory operations it KNOWS to be newer.  With the staging at the loop's top the prologue's path (no adds behind its loads) merged in front of
+  // the waits, and the adds -- one branch each -- were operations that "may not have been issued": the waits came out as vmcnt(8) .. vmcnt(0), which
+  // at run time meant "every float atomic of the half tile before has retired" (~1.2 us each with the chip busy) in front of a barrier, once
+  // per half tile.  DXN (per-node adds, a walk of its own so that no other d x_hat path merges in front of the staging either): the eight adds
+  // are straight-line code and NOTHING the staging consumes is issued behind them, so every wait of the staging leaves >= 8 operations in flight.
+  auto walk = [&](auto dxn_c) __attribute__((always_inline)) {
+  constexpr bool DXN = decltype(dxn_c)::value;
   for (int tile = tile_lo; tile < tile_hi; ++tile) {
-    const int4 mnn = tile + 2 < tile_hi ? meta[tile + 2] : mzero;
+    const int4 mnn = tile + 2 < tile_hi ? meta[tile + 2] : mzero;      // (far in front of the adds: consumed by the key loads behind barrier 4)
     const int t0 = mc.x, n_real = mc.y;
-    FB_T(0);
-    __syncthreads();                                  // the previous half tile's GEMMs are done with every tile
+    __syncthreads();                                  // the half tile is staged
     FB_T(7);
-    // ---- stage this half tile (its rows were fetched during the previous one's GEMMs) ----
-    {
-      FBH_ROW_STAGE(0); FBH_ROW_STAGE(1);
-      if (tid < 32) tinfo[tid] = tid < n_real ? ((tid - (tpn & 255)) | (tpn & ~255)) : 0;
-      if (VTAB && g.dx_node && tid < 32) keys_s[tid] = kyn;
-      if constexpr (VTAB) {
-        *reinterpret_cast<f32x4*>(&Fs[srow * kLd + sc4]) = yi0; *reinterpret_cast<f32x4*>(&Fs[(srow + 16) * kLd + sc4]) = yi1;
-      }
-      if (r_tab) {
-        *reinterpret_cast<f32x4*>(&Rs[srow * kLd + sc4]) = ri0; *reinterpret_cast<f32x4*>(&Rs[(srow + 16) * kLd + sc4]) = ri1;
-      } else {
-        f32x4* d__ = reinterpret_cast<f32x4*>(&Rs[(lane & 31) * kLd + 8 * wave + 4 * (lane >> 5)]);
-        d__[0] = ri0; d__[8] = ri1;
-      }
-      if (tid < 64) reinterpret_cast<f32x4*>(Ps)[tid] = pn;
-    }
-    __syncthreads();
     // per-lane indices re-derived from an opaque copy of the thread id (loop-invariant addresses are hoisted and spilled otherwise)
     int tid_ = tid;
     asm volatile("" : "+v"(tid_));
@@ -567,10 +587,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     FB_T(4);
     __syncthreads();
     FB_T(7);
-    FBH_ROWS_GLOAD(mn);                               // next half tile's rows: in flight during the GEMMs below
+    FBH_ROWS_GLOAD(mn, DXN);                          // next half tile's rows: in flight during the GEMMs below
     if constexpr (NODE) { if (r_tab) FBH_R_GLOAD(); FBH_KEY_GLOAD(0, mnn); FBH_KEY_GLOAD(1, mnn); }      // ... its r rows (r table), and the table rows of the one after
+    if constexpr (DXN) { if (tile + 1 < tile_hi) FBH_RIMG_GLOAD(tile + 1); }      // ... and its probabilities IN FRONT of the adds (four registers across the d x_hat phase)
     // ---- this head's share of d x_hat = dR B_h + Gs ----
-    if (g.dx_atomic) {
+    if (DXN || g.dx_atomic) {                         // (the launcher admits dx_node only with dx_atomic)
       // rows = tokens 4 kq + reg (+ 16), columns = features fb + c16: one atomic instruction covers 4 token rows x 64 contiguous bytes.  Float
       // atomics execute at the memory side, not in an XCD's L2 (every 64-byte segment leaves L2 as one uncached request), so the eight heads' adds do
       // NOT meet on chip: 0.47 GB of added bytes per launch at the headline, a floor of ~0.36 ms at the chip-wide ~1.3 TB/s
@@ -591,17 +612,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           dx0 = mma6(dx0, a0, Mf[s]); dx1 = mma6(dx1, a1, Mf[s]);
         }
       }
-      if (VTAB && g.dx_node) {
-        // per NODE, this head's replica: the same mask, the same four 64-byte segments per instruction, the same bytes -- the row is the token's
-        // table row instead of the token.  Wave-uniform base + a 32-bit lane offset: no address pairs held in registers
+      if constexpr (DXN) {
+        // per NODE, this head's replica: four 64-byte segments per instruction -- the row is the token's table row instead of the token.
+        // EIGHT UNCONDITIONAL instructions (the compiler counts them when the staging waits) on a BUFFER descriptor of this head's replica:
+        // a row past the tokens gets a byte offset past the descriptor's range, and the hardware DROPS an out-of-range lane of a buffer
+        // atomic -- no request leaves the CU, which is what the `if` per row did, without the branch.  (The other unconditional form, adding
+        // cond ? dx : 0.f to the last real token's row, is exact as well -- x + 0.0 = x for every x but -0.0, and a replica starts at +0.0 and
+        // is only added to -- but it was measured: 9 % more 64-byte atomic requests, which are what the kernel waits for, cost the headline
+        // step +20 us; profiles/r14_atomic_waits.md.)  buffer_atomic_add_f32 is the same memory-side add as global_atomic_add_f32.
         const int4 ka = *reinterpret_cast<const int4*>(&keys_s[4 * kq]), kb = *reinterpret_cast<const int4*>(&keys_s[16 + 4 * kq]);
         const int k0[4] = {ka.x, ka.y, ka.z, ka.w}, k1[4] = {kb.x, kb.y, kb.z, kb.w};
-        float* ah = g.dx_node + (int64_t)head * g.rn_head;
-        const uint32_t col = (uint32_t)(fb + c16);
+        const __amdgpu_buffer_rsrc_t ah = __builtin_amdgcn_make_buffer_rsrc(g.dx_node + (int64_t)head * g.rn_head, 0, (int)(g.rn_head * 4), kRsrcRaw32);
+        const uint32_t col4 = 4u * (uint32_t)(fb + c16);
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
-          if (4 * kq + reg < n_real) unsafeAtomicAdd(ah + ((uint32_t)k0[reg] * 64u + col), dx0[reg]);
-          if (16 + 4 * kq + reg < n_real) unsafeAtomicAdd(ah + ((uint32_t)k1[reg] * 64u + col), dx1[reg]);
+          __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(dx0[reg], ah, 4 * kq + reg < n_real ? (uint32_t)k0[reg] * 256u + col4 : kOffPastAny, 0, 0);
+          __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(dx1[reg], ah, 16 + 4 * kq + reg < n_real ? (uint32_t)k1[reg] * 256u + col4 : kOffPastAny, 0, 0);
         }
       } else {
       float* out = g.dxh + ((int64_t)t0 + 4 * kq) * 64 + fb + c16;
@@ -633,7 +659,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       if (16 + c16 < n_real) *reinterpret_cast<f32x4*>(out + 16 * 64) = dx1;
     }
     FB_T(5);
-    if (tile + 1 < tile_hi) FBH_RIMG_GLOAD(tile + 1);     // next half tile's r rows and probabilities: in flight during the weight-gradient GEMMs
+    if constexpr (!DXN) { if (tile + 1 < tile_hi) FBH_RIMG_GLOAD(tile + 1); }     // next half tile's r rows and probabilities: in flight during the weight-gradient GEMMs
     // ---- weight gradients: dB[a][b] += sum_t dR[t][a] x_hat[t][b];  dM[n][m] += sum_t dDyn[t][n] Z[t][m]: ONE 32-token step, column fragments ----
     {
       const int blk = ((4 * kq + ((lane & 15) >> 2)) * kPS) + 4 * (lane & 3);      // this lane's address inside a 4 x 16 transpose block
@@ -660,6 +686,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     FB_T(6);
     mc = mn; mn = mnn;
+    if (tile + 1 < tile_hi) {
+      __syncthreads();                                // this half tile's GEMMs are done with every tile
+      FB_T(7);
+      FBH_STAGE(mc, DXN);                             // the next one's rows, fetched during those GEMMs
+      FB_T(0);
+    }
+  }
+  };
+  if constexpr (VTAB) {
+    if (g.dx_node) walk(std::true_type{}); else walk(std::false_type{});
+  } else {
+    walk(std::false_type{});
   }
 
   // ---- workgroup slab ----
@@ -1000,6 +1038,7 @@ int launch_fused_bwd_merged(const matcha_tensors& p, const Ragged& rg, int64_t B
   MATCHA_CHECK_ARG(!rn || xrow, "fused backward: the r table belongs to the node route");
   MATCHA_CHECK_ARG(!vn || rn, "fused backward: the value table needs the r table");
   MATCHA_CHECK_ARG(!a.dx_node || (vn && dx_atomic && a.dx_zeroed), "fused backward: per-node d x_hat sums need the value table, the atomics and a caller that zeroed them");
+  MATCHA_CHECK_ARG(!a.dx_node || a.x.rows * 256 < ((int64_t)1 << 31), "fused backward: a head's replica of the per-node sums is addressed through a buffer descriptor of < 2^31 bytes");
   if (dx_atomic && !a.dx_zeroed) MATCHA_TRY(zero_async(dxh, (size_t)tcap * 64 * sizeof(float), st));
   int nchunks = 2 * chunks_for(rg.nhalves);                  // two four-wave workgroups per CU
   if (nchunks > kMaxChunks) nchunks = kMaxChunks;
