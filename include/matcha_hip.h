@@ -755,7 +755,15 @@ int matcha_kway_complete_rows(const int64_t* clusters, int64_t A, int32_t S, int
  *     NULL; row i has the global rank g0 + i (the range must lie inside [0, A C_m)) and its choice is unranked on the device -- no row
  *     is read; a row with skip != 0 contributes nothing, one whose value is NaN, negative or > vmax is counted in n_rejected.
  *     Integer atomics only: the state is bit for bit independent of arrival order and of how the stream is cut.  _read: the planes
- *     (device int64 [A, S]) and the two counters (device int64 [2]); any of the three may be NULL, not all. */
+ *     (device int64 [A, S]) and the two counters (device int64 [2]); any of the three may be NULL, not all.
+ * matcha_subset_pair_*         per cluster and PAIR of positions i < j: over the accepted rows whose choice contains
+ *     both, the same fixed-point sum and their number.  matcha_subset_support_*'s arguments, checks, refusals and row handling, except
+ *     2 <= m <= 8 (a choice of one position has no pair).  State: the 256-byte header {n_rows, n_rejected}, then two planes of A P
+ *     cells, P = S (S - 1) / 2, each padded to a multiple of 256 bytes: the upper triangle only, row-major; the cell of positions
+ *     i < j of cluster a is a P + i (2 S - i - 1) / 2 + (j - i - 1).  An accepted row adds rint(double(v) 2^32) and 1 to the C(m, 2)
+ *     cells of its choice.  Like the support planes, a cell holds count * v * 2^32 modulo 2^64: exact while its true sum stays below
+ *     2^31.  Integer atomics only: the state, header and padding included, is bit for bit independent of arrival order and of how the
+ *     ranks are cut into calls.  _read: the packed planes (device int64 [A, P]) and the two counters; any may be NULL, not all. */
 int64_t matcha_cluster_subset_count(int64_t A, int32_t S, int32_t m, int32_t complement);
 int matcha_cluster_subset_rows(const int64_t* clusters, int64_t A, int32_t S, int32_t m, int32_t complement, int32_t min_gap,
                                int64_t rank0, const int64_t* ranks, int64_t count, int32_t L, int64_t* x, int32_t* flag,
@@ -766,6 +774,12 @@ int matcha_subset_support_update(void* state, size_t bytes, int64_t A, int32_t S
                                  const int32_t* skip, int64_t n, int64_t g0, matcha_stream_t stream);
 int matcha_subset_support_read(const void* state, size_t bytes, int64_t A, int32_t S, int32_t m, float vmax, int64_t* sum_out,
                                int64_t* count_out, int64_t* counters_out, matcha_stream_t stream);
+size_t matcha_subset_pair_bytes(int64_t A, int32_t S, int32_t m, float vmax);
+int matcha_subset_pair_init(void* state, size_t bytes, int64_t A, int32_t S, int32_t m, float vmax, matcha_stream_t stream);
+int matcha_subset_pair_update(void* state, size_t bytes, int64_t A, int32_t S, int32_t m, float vmax, const float* value,
+                              const int32_t* skip, int64_t n, int64_t g0, matcha_stream_t stream);
+int matcha_subset_pair_read(const void* state, size_t bytes, int64_t A, int32_t S, int32_t m, float vmax, int64_t* sum_out,
+                            int64_t* count_out, int64_t* counters_out, matcha_stream_t stream);
 
 /* ---- k-way pair maps -----------------------------------------------------------------------------------
  * The values of k-way rows projected onto pairs of node ids and accumulated on the device.  A map covers the row region

@@ -159,6 +159,10 @@ SIGNATURES = {
     "matcha_subset_support_init": (C.c_int, [_fp, _SZ, _I64, _I32, _I32, _F, _fp]),
     "matcha_subset_support_update": (C.c_int, [_fp, _SZ, _I64, _I32, _I32, _F, _fp, _fp, _I64, _I64, _fp]),
     "matcha_subset_support_read": (C.c_int, [_fp, _SZ, _I64, _I32, _I32, _F, _fp, _fp, _fp, _fp]),
+    "matcha_subset_pair_bytes": (_SZ, [_I64, _I32, _I32, _F]),
+    "matcha_subset_pair_init": (C.c_int, [_fp, _SZ, _I64, _I32, _I32, _F, _fp]),
+    "matcha_subset_pair_update": (C.c_int, [_fp, _SZ, _I64, _I32, _I32, _F, _fp, _fp, _I64, _I64, _fp]),
+    "matcha_subset_pair_read": (C.c_int, [_fp, _SZ, _I64, _I32, _I32, _F, _fp, _fp, _fp, _fp]),
     "matcha_pairmap_bytes": (_SZ, [_I64, _I32, _I64, _I32, _I32, _F, _F]),
     "matcha_pairmap_init": (C.c_int, [_fp, _SZ, _I64, _I32, _I64, _I32, _I32, _F, _F, _fp]),
     "matcha_pairmap_update": (C.c_int, [_fp, _SZ, _I64, _I32, _I64, _I32, _I32, _F, _F, _fp, _fp, _fp, _I64, _I32, _fp]),

@@ -1135,6 +1135,139 @@ __global__ __launch_bounds__(256) void subset_support_read_kernel(const unsigned
   if (counters_out && blockIdx.x == 0 && threadIdx.x < 2) counters_out[threadIdx.x] = (int64_t)counters[threadIdx.x];
 }
 
+// ---- per-pair support ----
+// Per cluster and PAIR of positions i < j, the same two quantities over the accepted rows whose choice contains both: two planes of
+// A P cells, P = S (S - 1) / 2, the upper triangle packed row-major: cell a P + i (2 S - i - 1) / 2 + (j - i - 1).
+//   subset_pair_update_kernel  the support kernel's structure and row handling; an accepted row adds to the C(m, 2) <= 28 cells of its
+//                              choice.  m = 2: the choice IS one pair and its lexicographic rank is the packed index, so the row's
+//                              cell is its global rank g -- no unranking, no tile, one coalesced global atomic per plane.  m >= 3: a
+//                              block's run of kPairRun consecutive ranks accumulates into an LDS tile of kPairTile cells per plane
+//                              (uint64 sums; uint32 counts, a run adds at most kPairRun to a cell) and flushes one global atomic per
+//                              touched cell; clusters of the run beyond the tile (only where C(S, m) <= P: m >= S - 2) go to global
+//                              atomics directly.  Sizes: 2 048 cells are 16 KB + 8 KB = 24 KB of LDS per block, six blocks (24 of
+//                              32 wavefronts) per CU of 160 KB, and hold 4 clusters of 32 loci (496 cells), 56 of 9; a run of 2 048
+//                              ranks is 8 rows per thread, as in the support kernel.  Integer atomics only.
+constexpr int kPairRun = 2048;
+constexpr int kPairTile = 2048;
+
+struct PairPlan {
+  size_t off_sum, off_count, total;
+  int64_t cells;
+  int32_t P;
+};
+
+bool pair_args_ok(int64_t A, int32_t S, int32_t m, float vmax) { return support_args_ok(A, S, m, vmax) && m >= 2; }
+
+PairPlan make_pplan(int64_t A, int32_t S) {
+  PairPlan pl{};
+  pl.P = S * (S - 1) / 2;                                               // <= 496
+  pl.cells = A * pl.P;                                                  // < 2^49
+  pl.off_sum = kSupHeader;
+  pl.off_count = pl.off_sum + align_up((size_t)pl.cells * 8, 256);
+  pl.total = pl.off_count + align_up((size_t)pl.cells * 8, 256);
+  return pl;
+}
+
+__global__ __launch_bounds__(256) void subset_pair_init_kernel(unsigned long long* __restrict__ p, int64_t n8) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) p[i] = 0ull;
+}
+
+// Every lane of a wavefront runs the whole body: the trip counts depend on the block's run only (m is the launch's), the ballots read
+// all 64 lanes and every barrier is reached by all four wavefronts.
+__global__ __launch_bounds__(256) void subset_pair_update_kernel(unsigned long long* __restrict__ counters, unsigned long long* __restrict__ sum,
+                                                                 unsigned long long* __restrict__ cnt, int32_t S, int32_t P, int32_t m, uint64_t cm,
+                                                                 float vmax, const float* __restrict__ value, const int32_t* __restrict__ skip, int64_t n,
+                                                                 int64_t g0) {
+  __shared__ unsigned long long tsum[kPairTile];
+  __shared__ unsigned int tcnt[kPairTile];
+  const int lane = threadIdx.x & (kWave - 1);
+  const bool direct = m == 2;                                           // cm == P and the choice's rank is its cell
+  const uint64_t tile_clusters = (uint64_t)(kPairTile / P);             // >= 4
+  uint32_t n_rows = 0, n_rej = 0;                                       // this wavefront's totals (identical in every lane)
+  const int64_t runs = (n + kPairRun - 1) / kPairRun;
+  for (int64_t run = blockIdx.x; run < runs; run += gridDim.x) {
+    const int64_t i0 = run * kPairRun;
+    const int len = n - i0 < kPairRun ? (int)(n - i0) : kPairRun;
+    const uint64_t a_first = (uint64_t)(g0 + i0) / cm, a_last = (uint64_t)(g0 + i0 + len - 1) / cm;
+    const uint64_t span = a_last - a_first + 1 < tile_clusters ? a_last - a_first + 1 : tile_clusters;
+    const int cells = direct ? 0 : (int)span * P;                       // <= kPairTile
+    for (int e = threadIdx.x; e < cells; e += 256) { tsum[e] = 0ull; tcnt[e] = 0u; }
+    __syncthreads();
+    for (int off = 0; off < len; off += 256) {
+      const int at = off + (int)threadIdx.x;
+      float v = 0.f;
+      bool live = false, rejected = false;
+      if (at < len) {
+        const bool skipped = skip && skip[i0 + at] != 0;
+        v = value[i0 + at];
+        const bool okv = v >= 0.f && v <= vmax;                         // false for NaN
+        live = !skipped && okv;
+        rejected = !skipped && !okv;
+      }
+      n_rows += (uint32_t)__popcll(__ballot(live));
+      n_rej += (uint32_t)__popcll(__ballot(rejected));
+      if (live) {
+        v = v + 0.f;                                                    // -0.0 -> +0.0
+        const unsigned long long q = (unsigned long long)__double2ll_rn((double)v * 4294967296.0);
+        if (direct) {
+          const uint64_t e = (uint64_t)(g0 + i0 + at);                  // < A cm = A P: the host checked g0 + n <= A cm
+          atomicAdd(sum + e, q);
+          atomicAdd(cnt + e, 1ull);
+        } else {
+          uint64_t a, r;
+          split_rank((uint64_t)(g0 + i0 + at), cm, a, r);
+          int32_t y[kMaxK] = {0, 0, 0, 0, 0, 0, 0, 0};
+          unrank(r, cm, S, m, y);                                       // ascending, every y[c] < S for c < m
+          const uint64_t rel = a - a_first;
+          const bool tiled = rel < span;
+          const int tbase = tiled ? (int)rel * P : 0;
+          const uint64_t gbase = a * (uint64_t)P;                       // a < A
+#pragma unroll
+          for (int c = 0; c < kMaxK - 1; ++c) {
+            const int row = y[c] * (2 * S - y[c] - 1) / 2 - y[c] - 1;   // + j: the cell of (y[c], j), j > y[c]
+#pragma unroll
+            for (int d = c + 1; d < kMaxK; ++d) {
+              if (d < m) {
+                const int e = row + y[d];                               // in [0, P)
+                if (tiled) {
+                  atomicAdd(&tsum[tbase + e], q);                       // tbase + e < span P
+                  atomicAdd(&tcnt[tbase + e], 1u);
+                } else {
+                  atomicAdd(sum + gbase + (uint64_t)e, q);
+                  atomicAdd(cnt + gbase + (uint64_t)e, 1ull);
+                }
+              }
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < cells; e += 256) {
+      const unsigned int c = tcnt[e];
+      if (c) {
+        atomicAdd(sum + a_first * (uint64_t)P + (uint64_t)e, tsum[e]);
+        atomicAdd(cnt + a_first * (uint64_t)P + (uint64_t)e, (unsigned long long)c);
+      }
+    }
+    __syncthreads();                                                    // the tile is reused by the next run
+  }
+  if (lane == 0) {
+    if (n_rows) atomicAdd(counters, (unsigned long long)n_rows);
+    if (n_rej) atomicAdd(counters + 1, (unsigned long long)n_rej);
+  }
+}
+
+__global__ __launch_bounds__(256) void subset_pair_read_kernel(const unsigned long long* __restrict__ counters, const unsigned long long* __restrict__ sum,
+                                                               const unsigned long long* __restrict__ cnt, int64_t cells, int64_t* __restrict__ sum_out,
+                                                               int64_t* __restrict__ count_out, int64_t* __restrict__ counters_out) {
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < cells; p += (int64_t)gridDim.x * 256) {
+    if (sum_out) sum_out[p] = (int64_t)sum[p];
+    if (count_out) count_out[p] = (int64_t)cnt[p];
+  }
+  if (counters_out && blockIdx.x == 0 && threadIdx.x < 2) counters_out[threadIdx.x] = (int64_t)counters[threadIdx.x];
+}
+
 }  // namespace
 }  // namespace matcha
 
@@ -1220,5 +1353,62 @@ extern "C" int matcha_subset_support_read(const void* state, size_t bytes, int64
                      (const unsigned long long*)(w + pl.off_sum), (const unsigned long long*)(w + pl.off_count), pl.cells, sum_out, count_out,
                      counters_out);
   MATCHA_CHECK_LAUNCH("subset_support_read_kernel");
+  return MATCHA_OK;
+}
+
+extern "C" size_t matcha_subset_pair_bytes(int64_t A, int32_t S, int32_t m, float vmax) {
+  if (!pair_args_ok(A, S, m, vmax)) return 0;
+  return make_pplan(A, S).total;
+}
+
+#define PAIR_COMMON_ARGS(fn)                                                                                                        \
+  MATCHA_CHECK_ARG(state, fn ": null state");                                                                                       \
+  MATCHA_CHECK_ARG(pair_args_ok(A, S, m, vmax), fn ": need 1 <= A <= 2^40, 2 <= S <= %d, 2 <= m <= %d, 0 < vmax <= 2^20 "           \
+                                                   "(A=%lld S=%d m=%d vmax=%g)",                                                    \
+                   kMaxWide, kMaxK, (long long)A, S, m, (double)vmax);                                                              \
+  MATCHA_CHECK_ARG(((uintptr_t)state) % 8 == 0, fn ": state must be 8-byte aligned");                                               \
+  const PairPlan pl = make_pplan(A, S);                                                                                             \
+  MATCHA_CHECK_ARG(bytes >= pl.total, fn ": state too small (%zu bytes, matcha_subset_pair_bytes says %zu)", bytes, pl.total)
+
+extern "C" int matcha_subset_pair_init(void* state, size_t bytes, int64_t A, int32_t S, int32_t m, float vmax, matcha_stream_t stream) {
+  PAIR_COMMON_ARGS("matcha_subset_pair_init");
+  const int64_t n8 = (int64_t)(pl.total / 8);                            // every offset is a multiple of 256
+  int64_t blocks = cdiv(n8, 256);
+  if (blocks > (1 << 14)) blocks = 1 << 14;
+  hipLaunchKernelGGL(subset_pair_init_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (unsigned long long*)state, n8);
+  MATCHA_CHECK_LAUNCH("subset_pair_init_kernel");
+  return MATCHA_OK;
+}
+
+extern "C" int matcha_subset_pair_update(void* state, size_t bytes, int64_t A, int32_t S, int32_t m, float vmax, const float* value,
+                                         const int32_t* skip, int64_t n, int64_t g0, matcha_stream_t stream) {
+  PAIR_COMMON_ARGS("matcha_subset_pair_update");
+  const int64_t cm = count_subsets(S, m);
+  const int64_t total = A * cm;                                          // < 2^40 * 2^24
+  MATCHA_CHECK_ARG(n >= 0 && n <= ((int64_t)1 << 40), "matcha_subset_pair_update: n=%lld out of range", (long long)n);
+  MATCHA_CHECK_ARG(g0 >= 0 && g0 <= total && n <= total - g0, "matcha_subset_pair_update: %lld ranks from %lld lie outside [0, %lld)", (long long)n,
+                   (long long)g0, (long long)total);
+  if (n == 0) return MATCHA_OK;
+  MATCHA_CHECK_ARG(value, "matcha_subset_pair_update: null value");
+  char* w = (char*)state;
+  int64_t blocks = cdiv(n, kPairRun);
+  if (blocks > (1 << 14)) blocks = 1 << 14;
+  hipLaunchKernelGGL(subset_pair_update_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (unsigned long long*)w,
+                     (unsigned long long*)(w + pl.off_sum), (unsigned long long*)(w + pl.off_count), S, pl.P, m, (uint64_t)cm, vmax, value, skip, n, g0);
+  MATCHA_CHECK_LAUNCH("subset_pair_update_kernel");
+  return MATCHA_OK;
+}
+
+extern "C" int matcha_subset_pair_read(const void* state, size_t bytes, int64_t A, int32_t S, int32_t m, float vmax, int64_t* sum_out,
+                                       int64_t* count_out, int64_t* counters_out, matcha_stream_t stream) {
+  PAIR_COMMON_ARGS("matcha_subset_pair_read");
+  MATCHA_CHECK_ARG(sum_out || count_out || counters_out, "matcha_subset_pair_read: null output");
+  const char* w = (const char*)state;
+  int64_t blocks = cdiv(pl.cells, 256);
+  if (blocks > (1 << 14)) blocks = 1 << 14;
+  hipLaunchKernelGGL(subset_pair_read_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)w,
+                     (const unsigned long long*)(w + pl.off_sum), (const unsigned long long*)(w + pl.off_count), pl.cells, sum_out, count_out,
+                     counters_out);
+  MATCHA_CHECK_LAUNCH("subset_pair_read_kernel");
   return MATCHA_OK;
 }

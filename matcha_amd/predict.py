@@ -15,7 +15,7 @@ CLI:  python -m matcha_amd.predict multiway -i interactions.txt -o output.txt
       python -m matcha_amd.predict kway --chrom 0 --k 3 --top 1000 [--start-bin A --end-bin B] [--exclude-known] -o top.tsv
       python -m matcha_amd.predict anchored --k 3 --top 20 --chrom 5 (--anchor-file loci.tsv | --anchor-chrom 0) -o anchored.tsv
       python -m matcha_amd.predict complete -i clusters.txt --chrom 5 [--free 1] --top 20 [--width W] [--exclude-known] -o complete.tsv
-      python -m matcha_amd.predict decompose -i clusters.txt --size 3 [--drop] [--min-gap G] --top 20 [--width W] [--exclude-known] -o decompose.tsv
+      python -m matcha_amd.predict decompose -i clusters.txt --size 3 [--drop] [--min-gap G] --top 20 [--width W] [--exclude-known] [--pair-support] -o decompose.tsv
       python -m matcha_amd.predict kmap --chrom 0 --k 3 [--start-bin A --end-bin B] [--threshold 0.5] [--exclude-known] -o map.npz
       python -m matcha_amd.predict attention -i interactions.txt -o attn.npz [--per-head]
 (all read ./config.JSON like the reference: temp_dir, resolution, chrom_list, min_distance).
@@ -31,7 +31,9 @@ CLI:  python -m matcha_amd.predict multiway -i interactions.txt -o output.txt
   the best ``--top`` sub-hyperedges of ``--size`` of its own loci, or with ``--drop`` the cluster with ``--size`` loci taken out; per
   kept candidate the cluster's line number, the chosen (kept or dropped) loci and the probability, with ``--drop`` also its change
   against the whole cluster.  ``<output>_support.tsv`` holds one line per cluster locus -- the mean probability and the number of the
-  candidates whose choice contains it -- and a ``.npz`` beside them every returned tensor.
+  candidates whose choice contains it -- and a ``.npz`` beside them every returned tensor.  ``--pair-support`` (``--size`` >= 2) also
+  writes ``<output>_pairs.npz``: per cluster the s x s block of the mean probability and the number of the candidates whose choice
+  contains BOTH loci, in ``attention``'s ragged layout (``sizes``, ``offsets``, ``pair_mean``, ``pair_count``).
 * ``kmap`` -- the pair map of matcha_amd/sweep.py: the probabilities of ALL candidates of size k of one chromosome (or bin window)
   projected onto pairs of bins -- per pair the summed probability, the mean, the best candidate, the number of candidates and the
   number at or above ``--threshold`` -- written as one .npz of [n, n] matrices.
@@ -425,6 +427,8 @@ def _decompose(args, config, temp_dir, model):
     from .sampler import HyperedgeSet
     if not (1 if args.drop else 2) <= args.size <= _lib.MAX_L:
         raise ValueError("--size must be in %d .. %d" % (1 if args.drop else 2, _lib.MAX_L))
+    if args.pair_support and args.size < 2:
+        raise ValueError("--pair-support needs --size >= 2: a choice of one locus has no pair")
     node2bin = np.load(os.path.join(temp_dir, "node2bin.npy"), allow_pickle=True).item()
     bin2node = {v: key for key, v in node2bin.items()}
     clusters, lines = parse_cluster_file(args.file, bin2node, config["chrom_list"], config["resolution"], least=2,
@@ -446,8 +450,8 @@ def _decompose(args, config, temp_dir, model):
         table[a, :len(c)] = c
     min_gap = int(config["min_distance"]) + 1 if args.min_gap is None else args.min_gap
     out = SW.decomposition_sweep(model, table, args.size, mode="drop" if args.drop else "keep", min_gap=min_gap, top=args.top,
-                                 chunk_rows=args.chunk_rows, width=args.width, exclude=exclude)
-    z = {key: v.cpu().numpy() for key, v in out.items() if isinstance(v, torch.Tensor)}
+                                 chunk_rows=args.chunk_rows, width=args.width, exclude=exclude, pair_support=args.pair_support)
+    z = {key: v.cpu().numpy() for key, v in out.items() if isinstance(v, torch.Tensor) and not key.startswith("pair_")}
     count = z["count"]
     with open(args.output, "w") as f:
         for a in range(len(clusters)):
@@ -462,6 +466,11 @@ def _decompose(args, config, temp_dir, model):
             for j, v in enumerate(c):
                 f.write("\t".join([str(lines[a]), node2bin[int(v)], repr(float(z["support_mean"][a, j])), str(int(z["support_count"][a, j]))]) + "\n")
     np.savez(base + ".npz", clusters=table, **z)
+    if args.pair_support:       # attention_maps' layout: cluster a is the row-major s_a x s_a block at offsets[a], loci in the order of _support.tsv
+        sizes = np.asarray([len(c) for c in clusters], dtype=np.int64)
+        mean, cnt = out["pair_mean"].cpu().numpy(), out["pair_count"].cpu().numpy()
+        flat = lambda t, dtype: np.concatenate([t[a, :s, :s].reshape(-1) for a, s in enumerate(sizes)] + [np.zeros(0, dtype=dtype)]).astype(dtype)
+        np.savez(base + "_pairs.npz", sizes=sizes, offsets=block_offsets(sizes), pair_mean=flat(mean, np.float32), pair_count=flat(cnt, np.int64))
     print("%d clusters, %d candidates (%d against the gap rule, %d known, skipped) -> %d in %s"
           % (len(clusters), out["n_candidates"], out["n_invalid"], out["n_excluded"], int(count.sum()), args.output))
 
@@ -525,6 +534,7 @@ def main(argv=None):
     k.add_argument("--width", type=int, default=None, help="zero-pad rows to this width (default: --size, at most 8; --drop: the longest cluster, at most 32)")
     k.add_argument("--exclude-known", action="store_true", help="skip the hyperedges of temp_dir/all_<k>_counter.npy, for every candidate size k present")
     k.add_argument("--chunk-rows", type=int, default=None, help="rows per forward (default: 2^20 up to width 8, min(2^20, 2^21 // width) beyond)")
+    k.add_argument("--pair-support", action="store_true", help="also write <output>_pairs.npz: per cluster the s x s mean probability and number of the candidates that contain both loci (--size >= 2)")
     k.add_argument("-o", "--output", type=str, default="./decompose.tsv")
     k.add_argument("--config", type=str, default="./config.JSON")
     e = sub.add_parser("kmap", help="pair map: the probabilities of all candidates of size --k projected onto pairs of bins")

@@ -19,6 +19,7 @@ made of a cluster's own loci, or the cluster with some of them taken out, and su
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 from typing import Optional, Tuple
 
@@ -1047,8 +1048,81 @@ class SubsetSupport:
         return {"sum": total, "count": count, "counters": counters}
 
 
+class SubsetPairSupport:
+    """Per-pair support on the device (csrc/sweep.hip's subset_pair_update_kernel), SubsetSupport's twin: for the ``A``
+    clusters of a table [A, S] and choices of ``m`` positions, 2 <= m <= 8, two int64 planes [A, P], P = S (S - 1) / 2 -- per pair of
+    positions i < j, over the accepted rows whose choice contains both, the sum of their values in the same fixed point and their
+    number.  Only the upper triangle is kept, row-major: pair (i, j) is column i (2 S - i - 1) / 2 + (j - i - 1), the order of
+    ``pair_index``.  Integer atomics only: bit for bit the same whatever the order of the updates and however the ranks were cut."""
+
+    def __init__(self, A: int, S: int, m: int, vmax: float = 1.0, device="cuda"):
+        lib = _lib.load()
+        self.A, self.S, self.m, self.vmax = int(A), int(S), int(m), float(vmax)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.MatchaHipError("SubsetPairSupport needs a cuda device (no CPU fallback)")
+        fits = 1 <= self.A <= 1 << 40 and abs(self.S) < 1 << 31 and abs(self.m) < 1 << 31
+        self._dims = (self.A, self.S, self.m, self.vmax)
+        self.bytes = int(lib.matcha_subset_pair_bytes(*self._dims)) if fits else 0
+        if self.bytes == 0:
+            raise ValueError(f"SubsetPairSupport: need 1 <= A <= 2^40, 2 <= S <= {MAX_SUBSET_CLUSTER}, 2 <= m <= {_lib.MAX_L} and 0 < vmax <= 2^20 "
+                             f"(A={A} S={S} m={m} vmax={vmax})")
+        self.P = self.S * (self.S - 1) // 2
+        self.state = torch.empty(self.bytes, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(lib.matcha_subset_pair_init(_lib.ptr(self.state), self.bytes, *self._dims, _stream(self.device)), "matcha_subset_pair_init")
+
+    @staticmethod
+    def pair_index(S: int, device=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(i, j) int64 [P] each: the positions of the packed columns, torch.triu_indices(S, S, 1) in row-major order."""
+        S = int(S)
+        i, j = torch.triu_indices(S, S, 1)
+        assert torch.equal(i * (2 * S - i - 1) // 2 + (j - i - 1), torch.arange(S * (S - 1) // 2))     # the kernel's cell formula
+        return i.to(device), j.to(device)
+
+    def update(self, value: torch.Tensor, g0: int, skip: Optional[torch.Tensor] = None):
+        """SubsetSupport.update's contract: ``value`` float32 [n] on the device, row i of global rank g0 + i; ``skip`` int32 / bool [n],
+        non-zero = the row contributes nothing; a row whose value is NaN, negative or > vmax is counted as rejected.  Enqueued on the
+        current stream; nothing is read back."""
+        lib = _lib.load()
+        value = value.reshape(-1)
+        if value.dtype != torch.float32 or value.device != self.state.device:
+            raise ValueError("value must be a float32 tensor on the SubsetPairSupport's device")
+        value = value.contiguous()
+        if skip is not None:
+            skip = skip.reshape(-1).to(device=value.device, dtype=torch.int32).contiguous()
+            if skip.numel() != value.numel():
+                raise ValueError("skip and value differ in length")
+        with torch.cuda.device(self.device):
+            _lib.check(lib.matcha_subset_pair_update(_lib.ptr(self.state), self.bytes, *self._dims, _lib.ptr(value), _lib.ptr(skip),
+                                                     value.numel(), int(g0), _stream(self.device)), "matcha_subset_pair_update")
+
+    def read(self) -> dict:
+        """'sum' int64 [A, P] (fixed point, value * 2^32), 'count' int64 [A, P] and 'counters' int64 [2] = (accepted rows, rejected
+        rows), on the device and without a synchronisation."""
+        lib = _lib.load()
+        total = torch.empty(self.A, self.P, dtype=torch.long, device=self.device)
+        count = torch.empty(self.A, self.P, dtype=torch.long, device=self.device)
+        counters = torch.empty(2, dtype=torch.long, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(lib.matcha_subset_pair_read(_lib.ptr(self.state), self.bytes, *self._dims, _lib.ptr(total), _lib.ptr(count),
+                                                   _lib.ptr(counters), _stream(self.device)), "matcha_subset_pair_read")
+        return {"sum": total, "count": count, "counters": counters}
+
+
+@functools.lru_cache(maxsize=None)
+def _pair_square_map(S: int) -> torch.Tensor:
+    """int64 [S * S] on the host: for every cell of the row-major S x S square the column of the packed upper triangle that holds its
+    pair, P = S (S - 1) / 2 (a zero column appended to the plane) on the diagonal."""
+    pi, pj = SubsetPairSupport.pair_index(S)
+    square = torch.full((S, S), S * (S - 1) // 2, dtype=torch.long)
+    square[pi, pj] = square[pj, pi] = torch.arange(pi.numel())
+    return square.view(-1)
+
+
 def decomposition_sweep(model, clusters, m: int, mode: str = "keep", min_gap: int = 1, top: int = 20, chunk_rows: Optional[int] = None,
-                        width: Optional[int] = None, exclude=None, task_mode: str = "class", support: bool = True) -> dict:
+                        width: Optional[int] = None, exclude=None, task_mode: str = "class", support: bool = True,
+                        pair_support: bool = False) -> dict:
     """For every cluster (``clusters``: a list of id lists of up to 32 ids each, or a zero-padded integer [A, S] array / tensor) score
     all candidates made of its OWN ids and keep the ``top`` best PER CLUSTER.  mode 'keep': the sub-hyperedges of ``m`` of its ids
     (2 <= m <= 8) -- which triples or quadruples inside the cluster are real simultaneous contacts.  mode 'drop': the cluster with
@@ -1067,6 +1141,13 @@ def decomposition_sweep(model, clusters, m: int, mode: str = "keep", min_gap: in
     ``support_sum`` float64 and ``support_count`` int64 [A, S_max] -- per locus of the cluster, the summed probability and the number
     of the valid, non-excluded candidates whose choice contains it -- and ``support_mean`` float32, their quotient (0 where the count
     is 0): in keep mode how credible the sub-hyperedges through the locus are, in drop mode how credible the cluster is without it.
+    With ``pair_support`` (task_mode 'class' and m >= 2 only): ``pair_sum`` float64 and ``pair_count`` int64
+    [A, S_max, S_max] -- per PAIR of loci (i, j) of the cluster, the summed probability and the number of the valid, non-excluded
+    candidates whose choice contains both -- and ``pair_mean`` float32, their quotient (0 where the count is 0).  In keep mode cell
+    (i, j) is the mean probability of the sub-hyperedges of m loci that contain both locus i and locus j; in drop mode the mean
+    probability of the cluster with both (and m - 2 others) taken out.  All three are symmetric with a zero diagonal, zero at
+    positions >= s_a and in a cluster not swept; cell for cell the layout of the attention map of the same cluster.  They are dense:
+    together 20 * A * S_max^2 bytes.
     In drop mode ``full_logit`` and ``full_proba`` [A]: the whole cluster at the same width (0 for a cluster not swept).  The
     integers ``n_candidates``, ``n_invalid`` (candidates that break the gap rule; scored, never kept) and ``n_excluded`` (valid
     candidates found in ``exclude``, a HyperedgeSet).
@@ -1081,6 +1162,9 @@ def decomposition_sweep(model, clusters, m: int, mode: str = "keep", min_gap: in
         raise ValueError("the support planes take the sigmoid's output: task_mode 'regress' needs support=False")
     complement = _MODES[mode]
     m, min_gap, top = int(m), int(min_gap), int(top)
+    if pair_support and (task_mode != "class" or m < 2):
+        raise ValueError("the pair planes take the sigmoid's output and a choice of at least two positions: pair_support needs "
+                         f"task_mode 'class' and m >= 2 (task_mode='{task_mode}' m={m})")
     if not (1 if complement else 2) <= m <= _lib.MAX_L or min_gap < 1:
         raise ValueError(f"need {1 if complement else 2} <= m <= {_lib.MAX_L} in mode '{mode}' and min_gap >= 1 (m={m} min_gap={min_gap})")
     if top < 1 or (chunk_rows is not None and int(chunk_rows) < 1):
@@ -1108,6 +1192,10 @@ def decomposition_sweep(model, clusters, m: int, mode: str = "keep", min_gap: in
         if (s - m >= 2) if complement else (s >= m):
             idx = torch.nonzero(sizes == s).view(-1).to(dev)
             groups.append((s, idx, math.comb(s, m)))
+    pair_map = {}                                                        # per size: square cell -> packed column; one copy, before anything is launched
+    if pair_support and groups:
+        maps = [_pair_square_map(s) for s, _, _ in groups]
+        pair_map = dict(zip([s for s, _, _ in groups], torch.cat(maps).to(dev).split([int(t.numel()) for t in maps])))
     K = min(top, max([cm for _, _, cm in groups] + [0]))
     out = {"rows": torch.zeros(A, K, width, dtype=torch.long, device=dev), "logit": torch.zeros(A, K, dtype=torch.float32, device=dev),
            "proba": torch.zeros(A, K, dtype=torch.float32, device=dev), "rank": torch.full((A, K), -1, dtype=torch.long, device=dev),
@@ -1115,6 +1203,9 @@ def decomposition_sweep(model, clusters, m: int, mode: str = "keep", min_gap: in
     if support:
         out["support_sum"] = torch.zeros(A, S_max, dtype=torch.float64, device=dev)
         out["support_count"] = torch.zeros(A, S_max, dtype=torch.long, device=dev)
+    if pair_support:
+        out["pair_sum"] = torch.zeros(A, S_max, S_max, dtype=torch.long, device=dev)        # fixed point until the end
+        out["pair_count"] = torch.zeros(A, S_max, S_max, dtype=torch.long, device=dev)
     if complement:
         out["full_logit"] = torch.zeros(A, dtype=torch.float32, device=dev)
     n_cand = sum(int(idx.numel()) * cm for _, idx, cm in groups)
@@ -1134,6 +1225,7 @@ def decomposition_sweep(model, clusters, m: int, mode: str = "keep", min_gap: in
             chunk = min(chunk_rows, total)
             sel = SegTopK(A_s, min(top, cm), cm, chunk, dev)
             sup = SubsetSupport(A_s, s, m, 1.0, dev) if support else None
+            psup = SubsetPairSupport(A_s, s, m, 1.0, dev) if pair_support else None
             for g0 in range(0, total, chunk):
                 x, flag = _subset_rows(tab, m, complement, min_gap, g0, min(chunk, total - g0), None, width, buf, fbuf)
                 logits = model(x).reshape(-1)
@@ -1144,16 +1236,20 @@ def decomposition_sweep(model, clusters, m: int, mode: str = "keep", min_gap: in
                     n_exc += (known & ~skip).sum()
                     skip = skip | known
                 sel.update(logits, g0, skip)
-                if sup is not None:
-                    sup.update(torch.sigmoid(logits), g0, skip)
-            done.append((s, idx, cm, tab, sel, sup))
+                if sup is not None or psup is not None:
+                    proba = torch.sigmoid(logits)
+                    if sup is not None:
+                        sup.update(proba, g0, skip)
+                    if psup is not None:
+                        psup.update(proba, g0, skip)
+            done.append((s, idx, cm, tab, sel, sup, psup))
         if complement and groups:                                        # the whole clusters, all sizes in one batch: the sweep's width and route
             swept = torch.cat([idx for _, idx, _ in groups])
             whole = torch.zeros(int(swept.numel()), width, dtype=torch.long, device=dev)
             whole[:, :S_max] = table[swept]                              # width >= S_max in drop mode
             for a0 in range(0, int(swept.numel()), chunk_rows):
                 out["full_logit"][swept[a0:a0 + chunk_rows]] = model(whole[a0:a0 + chunk_rows]).reshape(-1)
-    for s, idx, cm, tab, sel, sup in done:
+    for s, idx, cm, tab, sel, sup, psup in done:
         A_s, Ks = int(tab.shape[0]), min(top, cm)
         logit, grank, count = sel.read()
         rows, _ = _subset_rows(tab, m, complement, min_gap, 0, None, grank.view(-1), width, None, None)
@@ -1173,13 +1269,23 @@ def decomposition_sweep(model, clusters, m: int, mode: str = "keep", min_gap: in
             planes = sup.read()
             out["support_sum"][idx, :s] = planes["sum"].to(torch.float64) / 4294967296.0
             out["support_count"][idx, :s] = planes["count"]
+        if psup is not None:                                             # the packed upper triangles into both halves of the squares
+            planes = psup.read()
+            for key, packed in (("pair_sum", planes["sum"]), ("pair_count", planes["count"])):
+                square = torch.nn.functional.pad(packed, (0, 1)).index_select(1, pair_map[s])
+                out[key][idx, :s, :s] = square.view(A_s, s, s)
+    if pair_support:
+        out["pair_sum"] = out["pair_sum"].to(torch.float64) / 4294967296.0
+        hit = out["pair_count"] > 0
+        out["pair_mean"] = torch.where(hit, out["pair_sum"] / out["pair_count"].clamp(min=1).to(torch.float64),
+                                       torch.zeros_like(out["pair_sum"])).to(torch.float32)
     if support:
         hit = out["support_count"] > 0
         out["support_mean"] = torch.where(hit, out["support_sum"] / out["support_count"].clamp(min=1).to(torch.float64),
                                           torch.zeros_like(out["support_sum"])).to(torch.float32)
     if complement:
         swept = torch.zeros(A, dtype=torch.bool, device=dev)
-        for _, idx, _, _, _, _ in done:
+        for _, idx, _, _, _, _, _ in done:
             swept[idx] = True
         out["full_proba"] = torch.where(swept, act(out["full_logit"]), torch.zeros_like(out["full_logit"]))
     out.update(n_candidates=n_cand, n_invalid=int(n_inv.item()), n_excluded=int(n_exc.item()))

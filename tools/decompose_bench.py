@@ -1,7 +1,7 @@
 """Cost of cluster decomposition (matcha_amd/sweep.py::decomposition_sweep, cluster_subset_rows_kernel and subset_support_update_kernel;
 DESIGN.md 7.11) beside the eval forward on the same rows.
 
-  python tools/decompose_bench.py [--reps 10] [--cases abc]
+  python tools/decompose_bench.py [--reps 10] [--cases abc] [--pairs]
 
 d = 64 table model, hg38 at 1 Mb, eval mode under no_grad, timed with device events after a warm-up (median of --reps), one process per
 case, as tools/complete_bench.py.  Cluster ids are drawn from the whole genome, min_gap 1, top 20:
@@ -12,7 +12,9 @@ case, as tools/complete_bench.py.  Cluster ids are drawn from the whole genome, 
 
 and per case, in the same run: the sweep; the yardstick, model(x) alone over the same candidate rows, generated beforehand, in the
 sweep's groups and chunks and on its route; the rows kernel alone over all ranks in the same chunks; the support kernel alone over the
-same chunks with values and skip flags made beforehand."""
+same chunks with values and skip flags made beforehand.  --pairs appends, from the same run: the pair kernel
+(subset_pair_update_kernel) alone over the same chunks, values and flags; the sweep with pair_support=True; their ratios to model(x), to
+the unchanged support kernel and to the sweep without.  Case (b) drops one locus, which has no pair: its pair columns read n/a."""
 import argparse
 import math
 import sys
@@ -35,13 +37,14 @@ def clusters_of(rng, N, A, sizes):
     return t
 
 
-def bench(reps, which):
+def bench(reps, which, pairs=False):
     clf, _, num = model()
     N = int(np.sum(num))
     rng = np.random.default_rng(2028)
     print("| case | rows | groups | chunk | sweep | model(x) on the same rows | rows kernel alone | support kernel alone | sweep / model(x) | rows kernel / model(x) | "
-          "support kernel / model(x) |")
-    print("|---|---|---|---|---|---|---|---|---|---|---|")
+          "support kernel / model(x) |" + (" pair kernel alone | sweep with pairs | pair kernel / model(x) | pair kernel / support kernel | "
+                                           "sweep with pairs / sweep |" if pairs else ""))
+    print("|---|---|---|---|---|---|---|---|---|---|---|" + ("---|---|---|---|---|" if pairs else ""))
     for name in which:
         A, sizes, m, mode, width = CASES[name]
         comp = int(mode == "drop")
@@ -75,6 +78,18 @@ def bench(reps, which):
                     sup.update(v[g0:g0 + chunk], g0, flag[g0:g0 + chunk])
 
         t_sup = timed(support_only, reps)
+        t_pair = t_both = None
+        if pairs and m >= 2:
+            psups = [SW.SubsetPairSupport(tab.shape[0], tab.shape[1], m, device="cuda") for tab, _, _ in groups]
+
+            def pairs_only():
+                for (tab, cm, chunk), (_, flag), v, sup in zip(groups, xs, vals, psups):
+                    for g0 in range(0, tab.shape[0] * cm, chunk):
+                        sup.update(v[g0:g0 + chunk], g0, flag[g0:g0 + chunk])
+
+            t_pair = timed(pairs_only, reps)
+            del psups
+            t_both = timed(lambda: SW.decomposition_sweep(clf, table, m, mode=mode, min_gap=1, top=20, width=width, pair_support=True), reps)
 
         def forward_only():
             for (tab, cm, chunk), (x, _) in zip(groups, xs):
@@ -86,12 +101,15 @@ def bench(reps, which):
         del xs, vals, sups, buf, fbuf
         torch.cuda.empty_cache()
         print(f"| ({name}) {A} clusters of {sizes[0]}..{sizes[1]}, {mode} m = {m}, width {width} | {total} | {len(groups)} | {most} | {t_sweep:.2f} ms | "
-              f"{t_fwd:.2f} ms | {t_rows:.3f} ms | {t_sup:.3f} ms | {t_sweep / t_fwd:.3f} | {t_rows / t_fwd:.4f} | {t_sup / t_fwd:.4f} |", flush=True)
+              f"{t_fwd:.2f} ms | {t_rows:.3f} ms | {t_sup:.3f} ms | {t_sweep / t_fwd:.3f} | {t_rows / t_fwd:.4f} | {t_sup / t_fwd:.4f} |"
+              + ((f" {t_pair:.3f} ms | {t_both:.2f} ms | {t_pair / t_fwd:.4f} | {t_pair / t_sup:.2f} | {t_both / t_sweep:.3f} |" if t_pair is not None
+                  else " n/a | n/a | n/a | n/a | n/a |") if pairs else ""), flush=True)
 
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--cases", type=str, default="abc")
+    ap.add_argument("--pairs", action="store_true", help="also time the pair kernel alone and the sweep with pair_support=True")
     a = ap.parse_args()
-    bench(a.reps, [c for c in a.cases if c in CASES])
+    bench(a.reps, [c for c in a.cases if c in CASES], a.pairs)
