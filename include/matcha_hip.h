@@ -733,6 +733,27 @@ int matcha_kway_complete_rows(const int64_t* clusters, int64_t A, int32_t S, int
                               int64_t rank0, const int64_t* ranks, int64_t count, int32_t L, int64_t* x, int32_t* flag,
                               matcha_stream_t stream);
 
+/* ---- cluster growth -------------------------------------------------------------------------------------
+ * A beam search that grows hubs of up to 32 loci from seed clusters, one bin of the region [lo, lo + n) per step.  The beam table is
+ * int64 [A, B, S]: A seeds, B slots per seed (1 <= B <= 64), each slot a cluster row of matcha_kway_complete_rows (1 <= S <= 31, the
+ * leading non-zero run; an all-zero slot is empty).  Entry e = a B + j; the candidate of (e, r) is that of cluster e with f = 1 and
+ * free id lo + r, its global rank g = e n + r, 0 <= g < A B n < 2^63: rows, validity and flag bit 1 come from
+ * matcha_kway_complete_rows(beam, A B, S, lo, n, 1, min_gap, ...).  Candidate (a, j, r) is a TWIN iff a lower slot j' < j of the same
+ * seed is strictly ascending, non-empty, holds as many ids as slot j (strictly ascending too) and slot_j' \ slot_j is {lo + r} or
+ * empty (identical slots: every candidate of slot j is a twin).  Of all candidates of a seed that give the same sorted row exactly
+ * one is not a twin: the one of the lowest slot.  Selection: matcha_segtopk_* with seg_len = B n.
+ * matcha_grow_twins       beam device int64 [A, B, S]; writes twin, device int64 [A B, B]: column j' < j of row e = a B + j holds
+ *     the one id of slot_j' \ slot_j, -1 for identical slots, 0 for no relation; columns j' >= j are 0.  A = 0 launches nothing.
+ * matcha_grow_twin_flags  ORs 2 into flag[i] (device int32 [count], as matcha_kway_complete_rows wrote it) when the candidate of
+ *     global rank rank0 + i is a twin: lo + r stands in its entry's twin row, or a -1 does.  The range must lie inside [0, A B n),
+ *     else refused; count = 0 or A = 0 launches nothing.
+ * Both: every refusal (B outside [1, 64], S outside [1, 31], n < 1, A < 0, lo < 0, A B n >= 2^63, a null pointer) is MATCHA_EINVAL
+ * with a message, before any device call; caller-owned memory, asynchronous on the caller's stream, no allocation, no memset, no
+ * read-back. */
+int matcha_grow_twins(const int64_t* beam, int64_t A, int32_t B, int32_t S, int64_t* twin, matcha_stream_t stream);
+int matcha_grow_twin_flags(const int64_t* twin, int64_t A, int32_t B, int64_t lo, int32_t n, int64_t rank0, int64_t count, int32_t* flag,
+                           matcha_stream_t stream);
+
 /* ---- cluster decomposition ----------------------------------------------------------------------------
  * Which sub-hyperedges of clusters of up to 32 loci are real (keep), and which locus does not belong (drop): the candidates are
  * subsets of a cluster's OWN ids.  A cluster table is int64 [A, S], 2 <= S <= 32; row a holds s_a non-zero node ids followed by

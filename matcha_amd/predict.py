@@ -16,6 +16,7 @@ CLI:  python -m matcha_amd.predict multiway -i interactions.txt -o output.txt
       python -m matcha_amd.predict anchored --k 3 --top 20 --chrom 5 (--anchor-file loci.tsv | --anchor-chrom 0) -o anchored.tsv
       python -m matcha_amd.predict complete -i clusters.txt --chrom 5 [--free 1] --top 20 [--width W] [--exclude-known] -o complete.tsv
       python -m matcha_amd.predict decompose -i clusters.txt --size 3 [--drop] [--min-gap G] --top 20 [--width W] [--exclude-known] [--pair-support] -o decompose.tsv
+      python -m matcha_amd.predict grow -i seeds.txt --chrom 5 [--start-bin A --end-bin B] --max-size 10 [--beam 8] [--min-gap G] [--width W] [--exclude-known] -o grow.tsv
       python -m matcha_amd.predict kmap --chrom 0 --k 3 [--start-bin A --end-bin B] [--threshold 0.5] [--exclude-known] -o map.npz
       python -m matcha_amd.predict attention -i interactions.txt -o attn.npz [--per-head]
 (all read ./config.JSON like the reference: temp_dir, resolution, chrom_list, min_distance).
@@ -34,6 +35,10 @@ CLI:  python -m matcha_amd.predict multiway -i interactions.txt -o output.txt
   candidates whose choice contains it -- and a ``.npz`` beside them every returned tensor.  ``--pair-support`` (``--size`` >= 2) also
   writes ``<output>_pairs.npz``: per cluster the s x s block of the mean probability and the number of the candidates whose choice
   contains BOTH loci, in ``attention``'s ragged layout (``sizes``, ``offsets``, ``pair_mean``, ``pair_count``).
+* ``grow`` -- cluster growth (matcha_amd/sweep.py): for every line of ``-i``, a seed of 1 to 31 loci, a beam search of
+  the most plausible hubs of up to ``--max-size`` loci that contain it, one bin of ``--chrom`` added per step and ``--beam`` hubs kept
+  per seed and size; per kept hub the seed's line number, the size, the loci and the probability, grouped by seed and size, best
+  first, and a ``.npz`` beside it with every returned tensor.
 * ``kmap`` -- the pair map of matcha_amd/sweep.py: the probabilities of ALL candidates of size k of one chromosome (or bin window)
   projected onto pairs of bins -- per pair the summed probability, the mean, the best candidate, the number of candidates and the
   number at or above ``--threshold`` -- written as one .npz of [n, n] matrices.
@@ -422,6 +427,51 @@ def _complete(args, config, temp_dir, model):
           % (len(clusters), out["n_candidates"], out["n_invalid"], out["n_excluded"], int(count.sum()), args.output))
 
 
+def _grow(args, config, temp_dir, model):
+    from . import sweep as SW
+    from .sampler import HyperedgeSet
+    if not 2 <= args.max_size <= _lib.MAX_LONG_L:
+        raise ValueError("--max-size must be in 2 .. %d" % _lib.MAX_LONG_L)
+    if not 1 <= args.beam <= SW.MAX_BEAM:
+        raise ValueError("--beam must be in 1 .. %d" % SW.MAX_BEAM)
+    chrom_range = np.load(os.path.join(temp_dir, "chrom_range.npy"))
+    node2bin = np.load(os.path.join(temp_dir, "node2bin.npy"), allow_pickle=True).item()
+    bin2node = {v: key for key, v in node2bin.items()}
+    seeds, lines = parse_cluster_file(args.file, bin2node, config["chrom_list"], config["resolution"])      # before anything is scored
+    c_lo, c_hi = int(chrom_range[args.chrom][0]), int(chrom_range[args.chrom][1])
+    lo = c_lo + (args.start_bin if args.start_bin is not None else 0)
+    hi = c_lo + args.end_bin if args.end_bin is not None else c_hi
+    if not c_lo <= lo <= hi <= c_hi:
+        raise ValueError("the bin window [%s, %s) is not inside chromosome %d (%d bins)" % (args.start_bin, args.end_bin, args.chrom, c_hi - c_lo))
+    dev = model.layer_norm1.weight.device
+    exclude = None
+    if args.exclude_known:      # a seed of s loci passes through every size s + 1 .. max_size: every size present, one set
+        known = []
+        for k in sorted({k for c in seeds for k in range(len(c) + 1, args.max_size + 1)}):
+            path = os.path.join(temp_dir, "all_%d_counter.npy" % k)
+            if os.path.exists(path):
+                rows = np.load(path).astype(np.int64).reshape(-1, k)
+                known.append(np.pad(rows, ((0, 0), (0, _lib.MAX_LONG_L - k))))
+        if not known:
+            raise FileNotFoundError("--exclude-known: no all_<k>_counter.npy in %s for the hub sizes of %s" % (temp_dir, args.file))
+        exclude = HyperedgeSet(torch.from_numpy(np.concatenate(known)).to(dev))
+    table = np.zeros((len(seeds), max([len(c) for c in seeds] + [1])), dtype=np.int64)
+    for a, c in enumerate(seeds):
+        table[a, :len(c)] = c
+    min_gap = int(config["min_distance"]) + 1 if args.min_gap is None else args.min_gap
+    out = SW.growth_sweep(model, table, lo, hi, args.max_size, beam=args.beam, min_gap=min_gap, width=args.width, exclude=exclude,
+                          chunk_rows=args.chunk_rows, task_mode=args.task_mode)
+    z = {key: out[key].cpu().numpy() for key in ("rows", "logit", "proba", "parent", "added", "count", "size", "path")}
+    with open(args.output, "w") as f:
+        for a in range(len(seeds)):
+            for t in range(z["count"].shape[1]):
+                for ids, p in zip(z["rows"][a, t, :z["count"][a, t]], z["proba"][a, t, :z["count"][a, t]]):
+                    f.write("\t".join([str(lines[a]), str(int(z["size"][a, t]))] + [node2bin[int(v)] for v in ids if v] + [repr(float(p))]) + "\n")
+    np.savez(os.path.splitext(args.output)[0] + ".npz", seeds=table, **z)
+    print("%d seeds, %d steps, %d candidates (%d against the gap rule, %d twins, %d known, skipped) -> %d in %s"
+          % (len(seeds), out["steps"], out["n_candidates"], out["n_invalid"], out["n_twins"], out["n_excluded"], int(z["count"].sum()), args.output))
+
+
 def _decompose(args, config, temp_dir, model):
     from . import sweep as SW
     from .sampler import HyperedgeSet
@@ -525,6 +575,20 @@ def main(argv=None):
     h.add_argument("--task-mode", choices=["class", "regress"], default="class", help="the model's training objective: sigmoid or softplus outputs")
     h.add_argument("-o", "--output", type=str, default="./complete.tsv")
     h.add_argument("--config", type=str, default="./config.JSON")
+    m = sub.add_parser("grow", help="cluster growth: beam-search the most plausible hubs of up to --max-size loci that contain each seed of 1 .. 31 loci")
+    m.add_argument("-i", "--file", type=str, required=True, help="one seed per line: 1 .. 31 tab-separated chrom:position loci; lines may differ in length")
+    m.add_argument("--chrom", type=int, required=True, help="the region the added bins come from: index into config chrom_list")
+    m.add_argument("--start-bin", type=int, default=None, help="first bin of the window, relative to --chrom (default 0)")
+    m.add_argument("--end-bin", type=int, default=None, help="one past the last bin of the window (default: the chromosome's end)")
+    m.add_argument("--max-size", type=int, required=True, help="grow every seed up to this many loci, 2 .. 32")
+    m.add_argument("--beam", type=int, default=8, help="hubs kept per seed and size, 1 .. 64")
+    m.add_argument("--min-gap", type=int, default=None, help="smallest difference of adjacent node ids in a hub (default: min_distance + 1)")
+    m.add_argument("--width", type=int, default=None, help="zero-pad rows to this width (default: --max-size, at most 32): every step is scored at one width")
+    m.add_argument("--exclude-known", action="store_true", help="skip the hyperedges of temp_dir/all_<k>_counter.npy, for every hub size k present")
+    m.add_argument("--chunk-rows", type=int, default=None, help="rows per forward (default: 2^20 up to width 8, min(2^20, 2^21 // width) beyond)")
+    m.add_argument("--task-mode", choices=["class", "regress"], default="class", help="the model's training objective: sigmoid or softplus outputs")
+    m.add_argument("-o", "--output", type=str, default="./grow.tsv")
+    m.add_argument("--config", type=str, default="./config.JSON")
     k = sub.add_parser("decompose", help="cluster decomposition: the best --top sub-hyperedges of --size loci of every cluster of 2 .. 32 loci, or (--drop) the cluster without them")
     k.add_argument("-i", "--file", type=str, required=True, help="one cluster per line: 2 .. 32 tab-separated chrom:position loci; lines may differ in length")
     k.add_argument("--size", type=int, required=True, help="how many of the cluster's loci a candidate keeps (2 .. 8) or, with --drop, leaves out (1 .. 8)")
@@ -565,6 +629,8 @@ def main(argv=None):
         return _anchored(args, config, temp_dir, model)
     if args.cmd == "complete":
         return _complete(args, config, temp_dir, model)
+    if args.cmd == "grow":
+        return _grow(args, config, temp_dir, model)
     if args.cmd == "decompose":
         return _decompose(args, config, temp_dir, model)
     if args.cmd == "kmap":

@@ -15,6 +15,7 @@ preserved, onto the k-subsets of [0, m): C(m, k) candidates.
 csrc/pairmap.hip) project the scores of all candidates onto pairs of bins instead of keeping a list at all.  ``completion_sweep``
  extends clusters of 1 to 31 loci by bins of a region; ``decomposition_sweep`` ranks the sub-hyperedges
 made of a cluster's own loci, or the cluster with some of them taken out, and sums the scores per locus (``SubsetSupport``).
+``growth_sweep`` (csrc/grow.hip) beam-searches hubs of up to 32 loci from seed clusters, one bin per step (``grow_step``).
 """
 from __future__ import annotations
 
@@ -1289,4 +1290,261 @@ def decomposition_sweep(model, clusters, m: int, mode: str = "keep", min_gap: in
             swept[idx] = True
         out["full_proba"] = torch.where(swept, act(out["full_logit"]), torch.zeros_like(out["full_logit"]))
     out.update(n_candidates=n_cand, n_invalid=int(n_inv.item()), n_excluded=int(n_exc.item()))
+    return out
+
+
+# ---- cluster growth: beam-search hubs of up to 32 loci from seed clusters ------------------------------------------------
+MAX_BEAM = 64                              # slots per seed: one lane per column of a twin row (csrc/grow.hip)
+
+
+def _check_grow_args(B: int, S: int):
+    if not (1 <= B <= MAX_BEAM and 1 <= S <= MAX_CLUSTER):
+        raise ValueError(f"need 1 <= B <= {MAX_BEAM} slots per seed and 1 <= S <= {MAX_CLUSTER} ids per slot (B={B} S={S})")
+
+
+def grow_twins(beam: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int64 [A * B, B] on the device, matcha_grow_twins on a beam table int64 [A, B, S] as it stands (nothing is sorted here): column
+    j' < j of row a * B + j holds the one id of slot_j' \\ slot_j when the two slots of seed a are strictly ascending, non-empty and of
+    one size, -1 when they are identical, 0 for no relation; columns j' >= j are 0.  ``out`` reuses a buffer of at least A * B * B
+    elements."""
+    lib = _lib.load()
+    if beam.dim() != 3 or beam.dtype != torch.long:
+        raise ValueError("beam must be an int64 [A, B, S] tensor")
+    A, B, S = (int(v) for v in beam.shape)
+    _check_grow_args(B, S)
+    if not beam.is_cuda:
+        raise _lib.MatchaHipError("grow_twins needs a cuda device (no CPU fallback)")
+    beam = beam.contiguous()
+    if out is None:
+        twin = torch.empty(A * B, B, dtype=torch.long, device=beam.device)
+    else:
+        if out.dtype != torch.long or not out.is_contiguous() or out.numel() < A * B * B or out.device != beam.device:
+            raise ValueError("out must be a contiguous int64 tensor of at least A * B * B elements on the beam's device")
+        twin = out.view(-1)[:A * B * B].view(A * B, B)
+    with torch.cuda.device(beam.device):
+        _lib.check(lib.matcha_grow_twins(_lib.ptr(beam), A, B, S, _lib.ptr(twin), _stream(beam.device)), "matcha_grow_twins")
+    return twin
+
+
+def grow_twin_flags(twin: torch.Tensor, lo: int, n: int, flag: torch.Tensor, rank0: int = 0, count: Optional[int] = None) -> torch.Tensor:
+    """ORs 2 into flag[i] (int32, as the rows kernel of cluster completion wrote it) when the candidate of global rank rank0 + i --
+    entry g // n, free id lo + g % n -- is a twin by ``twin`` (grow_twins' table, int64 [A * B, B]).  ``count``: default everything
+    from rank0; ``flag`` may be longer than count, what lies behind is untouched.  Returns flag."""
+    lib = _lib.load()
+    if twin.dim() != 2 or twin.dtype != torch.long or not twin.is_contiguous():
+        raise ValueError("twin must be a contiguous int64 [A * B, B] tensor")
+    B = int(twin.shape[1])
+    _check_grow_args(B, 1)
+    if int(twin.shape[0]) % B:
+        raise ValueError("twin must have A * B rows of B columns")
+    A, lo, n, rank0 = int(twin.shape[0]) // B, int(lo), int(n), int(rank0)
+    if n < 1:
+        raise ValueError(f"need n >= 1 (n={n})")
+    total = A * B * n
+    if total >= 1 << 63:
+        raise ValueError(f"{total} candidates (A={A} B={B} n={n}) do not fit 63 bits")
+    count = total - rank0 if count is None else int(count)
+    if rank0 < 0 or count < 0 or rank0 + count > total:
+        raise IndexError(f"ranks [{rank0}, {rank0 + count}) outside [0, {total})")
+    if flag.dtype != torch.int32 or not flag.is_contiguous() or flag.numel() < count or flag.device != twin.device:
+        raise ValueError("flag must be a contiguous int32 tensor of at least count elements on twin's device")
+    if not twin.is_cuda:
+        raise _lib.MatchaHipError("grow_twin_flags needs a cuda device (no CPU fallback)")
+    with torch.cuda.device(twin.device):
+        _lib.check(lib.matcha_grow_twin_flags(_lib.ptr(twin), A, B, lo, n, rank0, count, _lib.ptr(flag), _stream(twin.device)),
+                   "matcha_grow_twin_flags")
+    return flag
+
+
+def _grow_chunk_rows(model, chunk_rows: Optional[int], width: int) -> int:
+    """completion_sweep's defaults and refusal."""
+    if chunk_rows is None:
+        return 1 << 20 if width <= _lib.MAX_L else min(1 << 20, (1 << 21) // width)
+    chunk_rows = int(chunk_rows)
+    if chunk_rows < 1:
+        raise ValueError("chunk_rows must be >= 1")
+    if width > _lib.MAX_L:
+        rt = model._runtime()
+        if not chunk_rows < 1 << 31 or rt.lib.matcha_workspace_bytes_long(C.byref(rt.shape), chunk_rows, width) == 0:
+            raise ValueError(f"chunk_rows = {chunk_rows} rows of {width} columns are more than the long forward takes in one call")
+    return chunk_rows
+
+
+def _grow_step(model, beam: torch.Tensor, lo: int, n: int, K: int, min_gap: int, width: int, exclude, chunk_rows: int, act,
+               counters: torch.Tensor) -> dict:
+    """One step on a beam int64 [A, B, S] on the model's device, A >= 1 and n >= 1: twin table, candidates chunk by chunk, one
+    SegTopK per seed, the advance.  Nothing is read back; ``counters`` (device int64 [3]: invalid, twins, excluded) is added to.  The
+    caller holds eval mode, no_grad, the deferred id check and the pinned route."""
+    A, B, S = (int(v) for v in beam.shape)
+    dev = beam.device
+    table = beam.view(A * B, S)
+    total = A * B * n
+    chunk_rows = min(chunk_rows, total)
+    twin = grow_twins(beam)
+    sel = SegTopK(A, K, B * n, chunk_rows, dev)
+    buf = torch.empty(chunk_rows * width, dtype=torch.long, device=dev)
+    fbuf = torch.empty(chunk_rows, dtype=torch.int32, device=dev)
+    for g0 in range(0, total, chunk_rows):
+        cnt = min(chunk_rows, total - g0)
+        x, flag = _complete_rows(table, lo, n, 1, min_gap, g0, cnt, None, width, buf, fbuf)
+        grow_twin_flags(twin, lo, n, flag, g0, cnt)
+        logits = model(x).reshape(-1)
+        skip = flag != 0
+        counters[0] += ((flag & 1) != 0).sum()
+        counters[1] += (flag == 2).sum()                                 # valid candidates that are twins
+        if exclude is not None:
+            known = exclude.contains(x)
+            counters[2] += (known & ~skip).sum()
+            skip = skip | known
+        sel.update(logits, g0, skip)
+    logit, grank, count = sel.read()
+    rows, _ = _complete_rows(table, lo, n, 1, min_gap, 0, None, grank.view(-1), width, None, None)      # rank -1: an all-zero row
+    rows = rows.view(A, K, width)
+    kept = grank >= 0
+    zero = torch.zeros_like(grank)
+    rank = torch.where(kept, grank - torch.arange(A, dtype=torch.long, device=dev).view(-1, 1) * (B * n), grank)
+    return {"rows": rows, "logit": logit, "proba": torch.where(kept, act(logit), torch.zeros_like(logit)), "rank": rank,
+            "parent": torch.where(kept, torch.div(rank, n, rounding_mode="floor"), zero), "added": torch.where(kept, lo + rank % n, zero),
+            "count": count, "beam": rows[:, :, :S + 1].contiguous()}
+
+
+def _empty_step(A: int, K: int, S: int, width: int, dev) -> dict:
+    e = torch.zeros(A, K, dtype=torch.float32, device=dev)
+    z = torch.zeros(A, K, dtype=torch.long, device=dev)
+    return {"rows": torch.zeros(A, K, width, dtype=torch.long, device=dev), "logit": e, "proba": e.clone(),
+            "rank": torch.full((A, K), -1, dtype=torch.long, device=dev), "parent": z, "added": z.clone(),
+            "count": torch.zeros(A, dtype=torch.long, device=dev), "beam": torch.zeros(A, K, S + 1, dtype=torch.long, device=dev)}
+
+
+def grow_step(model, beam, lo: int, hi: int, beam_out: Optional[int] = None, min_gap: int = 1, width: Optional[int] = None, exclude=None,
+              chunk_rows: Optional[int] = None, task_mode: str = "class") -> dict:
+    """One step of cluster growth.  ``beam`` int64 [A, B, S]: A seeds, B slots (1 .. 64) per seed, every slot a cluster of up to S ids
+    (1 .. 31) ascending with zeros behind them, an all-zero slot empty; it is used as it stands.  Every slot is extended by every bin
+    of [lo, hi) (cluster completion with free = 1; the candidate of slot j and bin lo + r has the seed's rank j n + r), candidates that
+    a LOWER slot of the seed reaches too are flagged as twins, and per seed the K = min(beam_out, B n) best candidates that are valid,
+    not twins and not in ``exclude`` are kept (``beam_out``: default B).
+
+    All candidates are scored at ONE width, default S + 1, at most 32: up to 8 model(x)'s forward for short rows with the large-batch
+    route pinned, beyond it the long forward.  Returns, on the model's device and best first within a seed, ``rows`` int64
+    [A, K, width], ``logit``, ``proba``, ``rank`` (within the seed), ``parent`` (the slot extended) and ``added`` (the bin) [A, K],
+    ``count`` int64 [A] and ``beam`` int64 [A, K, S + 1], the table of the next step; beyond count[a] the rank is -1 and everything
+    else 0.  The integers ``n_candidates`` = A B n, ``n_invalid`` (completion_sweep's), ``n_twins`` (valid candidates flagged as
+    twins) and ``n_excluded``.  ``chunk_rows`` and the loop are completion_sweep's; the result does not depend on the cut."""
+    if task_mode not in ("class", "regress"):
+        raise ValueError("task_mode must be 'class' or 'regress'")
+    lo, hi, min_gap = int(lo), int(hi), int(min_gap)
+    n = hi - lo
+    beam = torch.as_tensor(beam)
+    if beam.dim() != 3 or beam.is_floating_point() or beam.dtype == torch.bool:
+        raise ValueError("beam must be an integer [A, B, S] tensor or array")
+    A, B, S = (int(v) for v in beam.shape)
+    _check_grow_args(B, S)
+    beam_out = B if beam_out is None else int(beam_out)
+    if not 1 <= beam_out <= MAX_BEAM or min_gap < 1:
+        raise ValueError(f"need 1 <= beam_out <= {MAX_BEAM} and min_gap >= 1 (beam_out={beam_out} min_gap={min_gap})")
+    width = int(S + 1 if width is None else width)
+    if not S + 1 <= width <= _lib.MAX_LONG_L:
+        raise ValueError(f"width must be in [{S + 1}, {_lib.MAX_LONG_L}]: a slot holds up to {S} ids and a bin is added (got {width})")
+    chunk_rows = _grow_chunk_rows(model, chunk_rows, width)
+    act = torch.nn.functional.softplus if task_mode == "regress" else torch.sigmoid
+    model.eval()
+    dev = model.layer_norm1.weight.device
+    K = min(beam_out, B * max(n, 0))
+    if A == 0 or n < 1:
+        out = _empty_step(A, K, S, width, dev)
+        out.update(n_candidates=0, n_invalid=0, n_twins=0, n_excluded=0)
+        return out
+    beam = beam.to(device=dev, dtype=torch.long).contiguous()
+    counters = torch.zeros(3, dtype=torch.long, device=dev)
+    with torch.no_grad(), model.deferred_id_check(), _lib.option("disable_small_batch"):
+        out = _grow_step(model, beam, lo, n, K, min_gap, width, exclude, chunk_rows, act, counters)
+    c = counters.tolist()
+    out.update(n_candidates=A * B * n, n_invalid=c[0], n_twins=c[1], n_excluded=c[2])
+    return out
+
+
+def growth_sweep(model, seeds, lo: int, hi: int, max_size: int, beam: int = 8, min_gap: int = 1, width: Optional[int] = None, exclude=None,
+                 chunk_rows: Optional[int] = None, task_mode: str = "class") -> dict:
+    """Beam-search the most plausible hubs of up to ``max_size`` loci (2 .. 32) that contain a seed: every seed (``seeds`` in
+    completion_sweep's ``clusters`` form, 1 to 31 ids each, of any sizes) is grown by one bin of [lo, hi) per step, ``beam`` (1 .. 64)
+    hubs kept per seed and size (grow_step).  Step t runs on the seeds with s_a + t < max_size, the first with one slot per seed.
+
+    Every step is scored at ONE width, default ``max_size``, at most 32 (a logit depends on its batch's width).  With T = max_size -
+    (the fewest ids of a seed that has any) and B = beam it returns, on the model's device, level t of seed a holding its hubs of
+    s_a + t + 1 loci best first: ``rows`` int64 [A, T, B, width], ``logit``, ``proba``, ``parent`` (the slot of level t - 1 a hub
+    extends), ``added`` (the bin it adds) [A, T, B]; ``count`` and ``size`` int64 [A, T] (size = s_a + t + 1 where the level exists,
+    else 0); ``path`` int64 [A, B, T]: for each hub of a seed's LAST level the bins added, in the order of addition, zeros behind;
+    the integers ``n_candidates``, ``n_invalid``, ``n_twins``, ``n_excluded`` (summed over the steps) and ``steps``.  A seed with
+    s_a >= max_size, or without an id, has no levels.  Slots beyond count are 0.
+
+    Seed sizes are read on the host (a device tensor costs one small read-back before anything is launched); the counters stay on the
+    device, nothing synchronises between steps, and the node-id check of the whole growth is raised once at the end (IndexError)."""
+    if task_mode not in ("class", "regress"):
+        raise ValueError("task_mode must be 'class' or 'regress'")
+    lo, hi, max_size, B, min_gap = int(lo), int(hi), int(max_size), int(beam), int(min_gap)
+    n = hi - lo
+    if not 2 <= max_size <= _lib.MAX_LONG_L:
+        raise ValueError(f"max_size must be in [2, {_lib.MAX_LONG_L}] (got {max_size})")
+    if not 1 <= B <= MAX_BEAM or min_gap < 1:
+        raise ValueError(f"need 1 <= beam <= {MAX_BEAM} and min_gap >= 1 (beam={B} min_gap={min_gap})")
+    width = int(max_size if width is None else width)
+    if not max_size <= width <= _lib.MAX_LONG_L:
+        raise ValueError(f"width must be in [max_size, {_lib.MAX_LONG_L}] (got {width} for max_size = {max_size})")
+    chunk_rows = _grow_chunk_rows(model, chunk_rows, width)
+    act = torch.nn.functional.softplus if task_mode == "regress" else torch.sigmoid
+    model.eval()
+    dev = model.layer_norm1.weight.device
+    if isinstance(seeds, torch.Tensor) and seeds.is_cuda:
+        seeds = seeds.cpu()                                              # the one read-back: sizes are host knowledge from here on
+    table, _ = _cluster_table(seeds, "cpu")
+    sizes = (table != 0).sum(dim=1)
+    A = int(table.shape[0])
+    grows = (sizes >= 1) & (sizes < max_size)
+    T = max_size - int(sizes[sizes >= 1].min()) if bool((sizes >= 1).any()) else 0
+    T = max(T, 0)
+    zf = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
+    zl = lambda *shape: torch.zeros(*shape, dtype=torch.long, device=dev)
+    out = {"rows": zl(A, T, B, width), "logit": zf(A, T, B), "proba": zf(A, T, B), "parent": zl(A, T, B), "added": zl(A, T, B),
+           "count": zl(A, T), "size": zl(A, T), "path": zl(A, B, T)}
+    steps = torch.where(grows, max_size - sizes, torch.zeros_like(sizes))                # levels per seed, on the host
+    n_cand, n_steps = 0, 0
+    counters = torch.zeros(3, dtype=torch.long, device=dev)
+    if n >= 1 and T > 0:
+        t_idx = torch.arange(T).view(1, -1)
+        out["size"] = torch.where(t_idx < steps.view(-1, 1), sizes.view(-1, 1) + t_idx + 1, torch.zeros(A, T, dtype=torch.long)).to(dev)
+        with torch.no_grad(), model.deferred_id_check(), _lib.option("disable_small_batch"):
+            active = torch.nonzero(steps > 0).view(-1)                   # host indices of the seeds of step 0
+            cur = table[active].to(dev).view(-1, 1, int(table.shape[1]))
+            for t in range(T):
+                if t:
+                    keep = torch.nonzero(steps[active] > t).view(-1)     # a seed that has reached max_size leaves
+                    if keep.numel() == 0:
+                        break
+                    if keep.numel() < active.numel():
+                        cur = cur[keep.to(dev)]
+                        active = active[keep]
+                S_t = min(int(sizes[active].max()) + t, int(cur.shape[2]))
+                cur = cur[:, :, :S_t].contiguous()                       # the longest slot of this step
+                A_t, B_t = int(cur.shape[0]), int(cur.shape[1])
+                K = min(B, B_t * n)
+                res = _grow_step(model, cur, lo, n, K, min_gap, width, exclude, chunk_rows, act, counters)
+                idx = active.to(dev)
+                for key in ("rows", "logit", "proba", "parent", "added"):
+                    out[key][idx, t, :K] = res[key]
+                out["count"][idx, t] = res["count"]
+                cur = res["beam"]
+                n_cand += A_t * B_t * n
+                n_steps += 1
+        # the bins of every hub of a seed's last level, gathered back through parent
+        last = (steps - 1).to(dev)                                       # -1: no level
+        slot = torch.arange(B, device=dev).view(1, -1).expand(A, B).contiguous()
+        for t in range(T - 1, -1, -1):
+            on = (last >= t).view(-1, 1)
+            out["path"][:, :, t] = torch.where(on, out["added"][:, t].gather(1, slot), out["path"][:, :, t])
+            slot = torch.where(on, out["parent"][:, t].gather(1, slot), slot)
+        final = out["count"].gather(1, last.clamp(min=0).view(-1, 1)) if T else zl(A, 1)
+        live = (torch.arange(B, device=dev).view(1, -1) < final) & (last >= 0).view(-1, 1)
+        out["path"] = torch.where(live.view(A, B, 1), out["path"], torch.zeros_like(out["path"]))
+    c = counters.tolist()
+    out.update(n_candidates=n_cand, n_invalid=c[0], n_twins=c[1], n_excluded=c[2], steps=n_steps)
     return out
