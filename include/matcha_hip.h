@@ -733,6 +733,28 @@ int matcha_kway_complete_rows(const int64_t* clusters, int64_t A, int32_t S, int
                               int64_t rank0, const int64_t* ranks, int64_t count, int32_t L, int64_t* x, int32_t* flag,
                               matcha_stream_t stream);
 
+/* ---- multi-region sweep --------------------------------------------------------------------------------
+ * Candidates whose bins are drawn from several regions.  A sweep is P parts, 1 <= P <= 8, given as three HOST arrays of P elements
+ * that are read before the call returns: part p is the region [lo[p], lo[p] + n[p]) of node ids and m[p] >= 1 bins drawn from it;
+ * k = sum m[p], 2 <= k <= 8.  The regions are ascending and pairwise disjoint (lo[0] >= 0, lo[p] + n[p] <= lo[p + 1]).  A candidate
+ * is the concatenation, part by part, of one candidate of every part under the rule above (C_p = C(n_p - (m_p - 1)(min_gap - 1),
+ * m_p) of them, ranked r_p lexicographically from 0); the global rank is the mixed radix g = ((r_0 C_1 + r_1) C_2 + ...) C_{P-1} +
+ * r_{P-1}, 0 <= g < T = prod C_p < 2^63.  Every row is ascending as it stands and rank order is the lexicographic order of the rows;
+ * with P = 1 the rows are matcha_kway_rows'.  A candidate is invalid iff for some p the first id of part p + 1 minus the last id of
+ * part p is below min_gap (two regions closer than min_gap); it keeps its rank and its row, a flag marks it.
+ * matcha_kway_region_count  host only: T, or -1 for invalid arguments or T >= 2^63.
+ * matcha_kway_region_rows   matcha_kway_anchor_rows' contract: writes x, device int64 [count, L] with k <= L <= 8 (columns k .. L - 1
+ *     zero), and flag, device int32 [count] (non-zero = invalid): row i is the candidate of global rank rank0 + i (ranks == NULL; the
+ *     range must lie inside [0, T), else refused) or ranks[i] (device int64 [count]; a rank outside [0, T) gives an all-zero row with
+ *     its flag set).  At most one division per part and row.  count = 0 launches nothing.  Every refusal (P outside [1, 8], an m[p] or
+ *     n[p] < 1, k outside [2, 8], min_gap < 1, regions not ascending and disjoint, a lo out of range, T >= 2^63, a range outside
+ *     [0, T), count out of range, a null pointer) is MATCHA_EINVAL with a message, before any device call; caller-owned memory,
+ *     asynchronous on the caller's stream, no allocation, no memset, no read-back.  Selection: matcha_topk_*, or matcha_segtopk_* with
+ *     seg_len = T / C_0 for the best K per candidate of the leading part. */
+int64_t matcha_kway_region_count(int32_t P, const int64_t* lo, const int32_t* n, const int32_t* m, int32_t min_gap);
+int matcha_kway_region_rows(int32_t P, const int64_t* lo, const int32_t* n, const int32_t* m, int32_t min_gap, int64_t rank0,
+                            const int64_t* ranks, int64_t count, int32_t L, int64_t* x, int32_t* flag, matcha_stream_t stream);
+
 /* ---- cluster growth -------------------------------------------------------------------------------------
  * A beam search that grows hubs of up to 32 loci from seed clusters, one bin of the region [lo, lo + n) per step.  The beam table is
  * int64 [A, B, S]: A seeds, B slots per seed (1 <= B <= 64), each slot a cluster row of matcha_kway_complete_rows (1 <= S <= 31, the

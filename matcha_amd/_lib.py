@@ -153,6 +153,8 @@ SIGNATURES = {
     "matcha_segtopk_read": (C.c_int, [_fp, _SZ, _I64, _I32, _I64, _I64, _fp, _fp, _fp, _fp]),
     "matcha_kway_complete_count": (_I64, [_I64, _I32, _I32, _I32, _I32]),
     "matcha_kway_complete_rows": (C.c_int, [_fp, _I64, _I32, _I64, _I32, _I32, _I32, _I64, _fp, _I64, _I32, _fp, _fp, _fp]),
+    "matcha_kway_region_count": (_I64, [_I32, _fp, _fp, _fp, _I32]),
+    "matcha_kway_region_rows": (C.c_int, [_I32, _fp, _fp, _fp, _I32, _I64, _fp, _I64, _I32, _fp, _fp, _fp]),
     "matcha_grow_twins": (C.c_int, [_fp, _I64, _I32, _I32, _fp, _fp]),
     "matcha_grow_twin_flags": (C.c_int, [_fp, _I64, _I32, _I64, _I32, _I64, _I64, _fp, _fp]),
     "matcha_cluster_subset_count": (_I64, [_I64, _I32, _I32, _I32]),

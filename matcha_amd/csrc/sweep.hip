@@ -1412,3 +1412,173 @@ extern "C" int matcha_subset_pair_read(const void* state, size_t bytes, int64_t 
   MATCHA_CHECK_LAUNCH("subset_pair_read_kernel");
   return MATCHA_OK;
 }
+
+// ==== multi-region sweep ===============================================================================================
+// Candidates whose bins come from several regions: P parts, 1 <= P <= 8; part p is a region [lo_p, lo_p + n_p) and a number m_p >= 1 of
+// bins drawn from it, k = sum m_p in [2, 8].  The regions are ascending and disjoint, so the concatenation, part by part, of one 7.3
+// candidate of every part is an ascending row as it stands.  Part p has C_p = C(n_p - (m_p - 1)(min_gap - 1), m_p) candidates, ranked r_p
+// as kway_rows_kernel ranks them; the global rank is the mixed radix g = ((r_0 C_1 + r_1) C_2 + ...) C_{P-1} + r_{P-1}, 0 <= g < T = prod
+// C_p < 2^63: rank order is the lexicographic order of the rows.  The gap rule holds inside every part by construction; across a part
+// boundary (two regions closer than min_gap) it may fail, and such a candidate keeps its rank and its row with its flag set.
+//
+//   kway_region_rows_kernel   one thread per row.  The rank is decoded from the last part backwards, one division per part (none for
+//                             part 0), 32-bit when the rest of the rank and the radix both fit.  A part of one bin is lo_p + r_p; any
+//                             other goes through unrank.  A part's ids go straight into the row's slice of the LDS tile at the part's
+//                             column offset (an LDS address, not an index into a register array); the boundary test uses the part's
+//                             last id and the next part's first id while both are in registers.  The loop over parts is unrolled to 8
+//                             and predicated on p < P; the parts travel by value in one kernel argument, indexed statically.  The tile
+//                             leaves as the coalesced copy of the other rows kernels.  No atomics, no scratch.
+namespace matcha {
+namespace {
+
+constexpr int kMaxParts = 8;
+
+struct RegionParts {
+  int64_t lo[kMaxParts];      // first node id of the region
+  uint64_t C[kMaxParts];      // candidates of the part (the radix)
+  int32_t M[kMaxParts];       // n_p - (m_p - 1)(min_gap - 1), clamped at 0: the part's candidates are the m_p-subsets of [0, M_p)
+  int32_t m[kMaxParts];       // bins drawn from the part
+  int32_t P;
+};
+
+// T, -1 for invalid arguments or T >= 2^63; *k_out = sum m_p, parts filled when given
+int64_t region_count(int32_t P, const int64_t* lo, const int32_t* n, const int32_t* m, int32_t min_gap, RegionParts* parts, int32_t* k_out) {
+  if (P < 1 || P > kMaxParts || !lo || !n || !m || min_gap < 1) return -1;
+  int64_t k = 0;
+  for (int p = 0; p < P; ++p) {
+    if (m[p] < 1 || n[p] < 1 || lo[p] < 0 || lo[p] > ((int64_t)1 << 62)) return -1;
+    if (p > 0 && lo[p - 1] + (int64_t)n[p - 1] > lo[p]) return -1;
+    k += m[p];
+  }
+  if (k < 2 || k > kMaxK) return -1;
+  unsigned __int128 total = 1;
+  bool empty = false;
+  for (int p = 0; p < P; ++p) {
+    const int64_t M = (int64_t)n[p] - (int64_t)(m[p] - 1) * (min_gap - 1);
+    const int64_t c = count_subsets(M, m[p]);
+    if (c < 0) return -1;
+    empty |= c == 0;
+    if (!empty) {
+      total *= (unsigned __int128)(uint64_t)c;
+      if (total >= ((unsigned __int128)1 << 63)) return -1;
+    }
+    if (parts) {
+      parts->lo[p] = lo[p];
+      parts->C[p] = (uint64_t)c;
+      parts->M[p] = M > 0 ? (int32_t)M : 0;
+      parts->m[p] = m[p];
+    }
+  }
+  if (k_out) *k_out = (int32_t)k;
+  return empty ? 0 : (int64_t)total;
+}
+
+__global__ __launch_bounds__(kRowsPerBlock) void kway_region_rows_kernel(RegionParts parts, int32_t k, int32_t slack, int32_t min_gap, uint64_t total,
+                                                                         int64_t rank0, const int64_t* __restrict__ ranks, int64_t count, int32_t L,
+                                                                         int64_t* __restrict__ x, int32_t* __restrict__ flag) {
+  __shared__ int64_t tile[kRowsPerBlock * kMaxK];
+  for (int64_t base = (int64_t)blockIdx.x * kRowsPerBlock; base < count; base += (int64_t)gridDim.x * kRowsPerBlock) {
+    const int64_t i = base + threadIdx.x;
+    if (i < count) {
+      const int64_t g = ranks ? ranks[i] : rank0 + i;
+      const bool ok = g >= 0 && (uint64_t)g < total;                   // total > 0 then, so every C_p > 0
+      int64_t* __restrict__ row = tile + threadIdx.x * L;
+#pragma unroll
+      for (int c = 0; c < kMaxK; ++c)
+        if (c < L && (!ok || c >= k)) row[c] = 0;
+      bool bad = !ok;
+      if (ok) {
+        uint64_t rest = (uint64_t)g;
+        int col = k;                                                   // one past the part's last column
+        int64_t next_first = 0;                                        // first id of part p + 1
+#pragma unroll
+        for (int p = kMaxParts - 1; p >= 0; --p) {
+          if (p < parts.P) {
+            const uint64_t cp = parts.C[p];
+            const int mp = parts.m[p];
+            uint64_t r;
+            if (p == 0) {
+              r = rest;                                                // rest < C_0: nothing left to divide
+            } else if ((rest | cp) >> 32) {                            // the part's one 64-bit division
+              const uint64_t q = rest / cp;
+              r = rest - q * cp;
+              rest = q;
+            } else {
+              const uint32_t q32 = (uint32_t)rest / (uint32_t)cp;
+              r = (uint32_t)rest - q32 * (uint32_t)cp;
+              rest = q32;
+            }
+            col -= mp;
+            int64_t first, last;
+            if (mp == 1) {
+              first = last = parts.lo[p] + (int64_t)r;
+              row[col] = first;
+            } else {
+              int32_t y[kMaxK] = {0, 0, 0, 0, 0, 0, 0, 0};
+              unrank(r, cp, parts.M[p], mp, y);
+              first = last = parts.lo[p] + (int64_t)y[0];
+#pragma unroll
+              for (int c = 0; c < kMaxK; ++c) {
+                if (c < mp) {
+                  const int64_t v = parts.lo[p] + (int64_t)y[c] + (int64_t)c * slack;
+                  row[col + c] = v;
+                  last = v;
+                }
+              }
+            }
+            if (p + 1 < parts.P) bad |= next_first - last < (int64_t)min_gap;      // regions ascend: the difference is positive
+            next_first = first;
+          }
+        }
+      }
+      flag[i] = bad ? 1 : 0;
+    }
+    __syncthreads();
+    const int64_t rows = count - base < kRowsPerBlock ? count - base : kRowsPerBlock;
+    const int elems = (int)rows * L;
+    for (int e = threadIdx.x; e < elems; e += kRowsPerBlock) x[base * L + e] = tile[e];
+    __syncthreads();                                                   // the tile is reused by the next run of rows
+  }
+}
+
+}  // namespace
+}  // namespace matcha
+
+extern "C" int64_t matcha_kway_region_count(int32_t P, const int64_t* lo, const int32_t* n, const int32_t* m, int32_t min_gap) {
+  return region_count(P, lo, n, m, min_gap, nullptr, nullptr);
+}
+
+extern "C" int matcha_kway_region_rows(int32_t P, const int64_t* lo, const int32_t* n, const int32_t* m, int32_t min_gap, int64_t rank0,
+                                       const int64_t* ranks, int64_t count, int32_t L, int64_t* x, int32_t* flag, matcha_stream_t stream) {
+  MATCHA_CHECK_ARG(P >= 1 && P <= kMaxParts, "matcha_kway_region_rows: need 1 <= P <= %d parts (P=%d)", kMaxParts, P);
+  MATCHA_CHECK_ARG(lo && n && m, "matcha_kway_region_rows: null part arrays");
+  MATCHA_CHECK_ARG(min_gap >= 1, "matcha_kway_region_rows: need min_gap >= 1 (min_gap=%d)", min_gap);
+  int64_t k = 0;
+  for (int p = 0; p < P; ++p) {
+    MATCHA_CHECK_ARG(m[p] >= 1 && n[p] >= 1, "matcha_kway_region_rows: part %d needs n >= 1 bins and m >= 1 drawn (n=%d m=%d)", p, n[p], m[p]);
+    MATCHA_CHECK_ARG(lo[p] >= 0 && lo[p] <= ((int64_t)1 << 62), "matcha_kway_region_rows: lo of part %d out of range", p);
+    MATCHA_CHECK_ARG(p == 0 || lo[p - 1] + (int64_t)n[p - 1] <= lo[p],
+                     "matcha_kway_region_rows: the regions must be ascending and disjoint (part %d begins at %lld, part %d ends at %lld)", p,
+                     (long long)lo[p], p - 1, (long long)(lo[p - 1] + (int64_t)n[p - 1]));
+    k += m[p];
+  }
+  MATCHA_CHECK_ARG(k >= 2 && k <= kMaxK, "matcha_kway_region_rows: need 2 <= k <= %d bins per candidate (k=%lld)", kMaxK, (long long)k);
+  MATCHA_CHECK_ARG(L >= k && L <= kMaxK, "matcha_kway_region_rows: row width L=%d must be in [k, %d]", L, kMaxK);
+  RegionParts parts = {};
+  parts.P = P;
+  const int64_t total = region_count(P, lo, n, m, min_gap, &parts, nullptr);
+  MATCHA_CHECK_ARG(total >= 0, "matcha_kway_region_rows: the product of the parts' counts does not fit 63 bits (P=%d k=%lld min_gap=%d)", P, (long long)k,
+                   min_gap);
+  MATCHA_CHECK_ARG(count >= 0 && count <= ((int64_t)1 << 40), "matcha_kway_region_rows: count out of range");
+  if (!ranks)
+    MATCHA_CHECK_ARG(rank0 >= 0 && rank0 <= total && count <= total - rank0,
+                     "matcha_kway_region_rows: %lld ranks from %lld lie outside [0, %lld)", (long long)count, (long long)rank0, (long long)total);
+  if (count == 0) return MATCHA_OK;
+  MATCHA_CHECK_ARG(x && flag, "matcha_kway_region_rows: null output");
+  int64_t blocks = cdiv(count, kRowsPerBlock);
+  if (blocks > (1 << 20)) blocks = 1 << 20;
+  hipLaunchKernelGGL(kway_region_rows_kernel, dim3((unsigned)blocks), dim3(kRowsPerBlock), 0, (hipStream_t)stream, parts, (int32_t)k, min_gap - 1, min_gap,
+                     (uint64_t)total, rank0, ranks, count, L, x, flag);
+  MATCHA_CHECK_LAUNCH("kway_region_rows_kernel");
+  return MATCHA_OK;
+}

@@ -17,6 +17,7 @@ CLI:  python -m matcha_amd.predict multiway -i interactions.txt -o output.txt
       python -m matcha_amd.predict complete -i clusters.txt --chrom 5 [--free 1] --top 20 [--width W] [--exclude-known] -o complete.tsv
       python -m matcha_amd.predict decompose -i clusters.txt --size 3 [--drop] [--min-gap G] --top 20 [--width W] [--exclude-known] [--pair-support] -o decompose.tsv
       python -m matcha_amd.predict grow -i seeds.txt --chrom 5 [--start-bin A --end-bin B] --max-size 10 [--beam 8] [--min-gap G] [--width W] [--exclude-known] -o grow.tsv
+      python -m matcha_amd.predict regions --part 0:1 --part 5:1 --part 10:1:20-60 --top 1000 [--per-leading] [--map R C] [--exclude-known] -o regions.tsv
       python -m matcha_amd.predict kmap --chrom 0 --k 3 [--start-bin A --end-bin B] [--threshold 0.5] [--exclude-known] -o map.npz
       python -m matcha_amd.predict attention -i interactions.txt -o attn.npz [--per-head]
 (all read ./config.JSON like the reference: temp_dir, resolution, chrom_list, min_distance).
@@ -39,6 +40,11 @@ CLI:  python -m matcha_amd.predict multiway -i interactions.txt -o output.txt
   the most plausible hubs of up to ``--max-size`` loci that contain it, one bin of ``--chrom`` added per step and ``--beam`` hubs kept
   per seed and size; per kept hub the seed's line number, the size, the loci and the probability, grouped by seed and size, best
   first, and a ``.npz`` beside it with every returned tensor.
+* ``regions`` -- the multi-region sweep (matcha_amd/sweep.py): candidates with ``COUNT`` bins drawn from each ``--part
+  CHROM:COUNT[:START-END]`` (a chromosome, or a window of its bins; parts in ascending genome order), e.g. every triple with one bin on
+  each of three chromosomes; the best ``--top`` written like ``kway``'s, with ``--per-leading`` the best ``--top`` per candidate of the
+  first part, grouped like ``anchored``'s; ``--map R C`` writes the pair map between parts R and C (R = C: within one part) to the
+  ``.npz`` instead of a list.
 * ``kmap`` -- the pair map of matcha_amd/sweep.py: the probabilities of ALL candidates of size k of one chromosome (or bin window)
   projected onto pairs of bins -- per pair the summed probability, the mean, the best candidate, the number of candidates and the
   number at or above ``--threshold`` -- written as one .npz of [n, n] matrices.
@@ -280,6 +286,98 @@ def _kmap(args, config, temp_dir, model):
              n=np.int64(hi - lo), k=np.int64(args.k), min_gap=np.int64(min_gap), threshold=np.float32(args.threshold))
     print("%d candidates (%d known, skipped; %d rejected) -> %d x %d map in %s"
           % (out["n_candidates"], out["n_excluded"], out["n_rejected"], hi - lo, hi - lo, args.output))
+
+
+def parse_parts(specs: Sequence[str], chrom_range, chrom_list: Sequence[str]) -> List[Tuple[int, int, int]]:
+    """[(lo, hi, m)] in node ids from ``--part CHROM:COUNT[:START-END]`` arguments: CHROM an index into chrom_list or one of its names,
+    COUNT >= 1 bins drawn from the part, START-END a window of bins relative to the chromosome (default: all of it).  The parts must
+    come in ascending genome order without overlap; every error is a ValueError that names the offending argument."""
+    if not specs:
+        raise ValueError("regions needs at least one --part CHROM:COUNT[:START-END]")
+    names = list(chrom_list)
+    parts = []
+    for spec in specs:
+        what = "--part %s" % spec
+        items = spec.split(":")
+        if len(items) not in (2, 3):
+            raise ValueError("%s: expected CHROM:COUNT or CHROM:COUNT:START-END" % what)
+        if items[0] in names:
+            chrom = names.index(items[0])
+        else:
+            try:
+                chrom = int(items[0])
+            except ValueError:
+                raise ValueError("%s: %r is neither a name nor an index of chrom_list" % (what, items[0]))
+        if not 0 <= chrom < len(chrom_range):
+            raise ValueError("%s: chromosome index %d outside [0, %d)" % (what, chrom, len(chrom_range)))
+        try:
+            m = int(items[1])
+        except ValueError:
+            raise ValueError("%s: COUNT %r is not an integer" % (what, items[1]))
+        if m < 1:
+            raise ValueError("%s: COUNT must be >= 1" % what)
+        c_lo, c_hi = int(chrom_range[chrom][0]), int(chrom_range[chrom][1])
+        lo, hi = c_lo, c_hi
+        if len(items) == 3:
+            try:
+                start, end = (int(v) for v in items[2].split("-"))
+            except ValueError:
+                raise ValueError("%s: the window %r is not START-END" % (what, items[2]))
+            lo, hi = c_lo + start, c_lo + end
+            if not c_lo <= lo < hi <= c_hi:
+                raise ValueError("%s: the bin window [%d, %d) is empty or not inside the chromosome (%d bins)" % (what, start, end, c_hi - c_lo))
+        if parts and lo < parts[-1][1]:
+            raise ValueError("%s: parts must be given in ascending genome order without overlap (it begins at node %d, the part before "
+                             "ends at %d)" % (what, lo, parts[-1][1]))
+        parts.append((lo, hi, m))
+    return parts
+
+
+def _regions(args, config, temp_dir, model):
+    from . import sweep as SW
+    from .sampler import HyperedgeSet
+    chrom_range = np.load(os.path.join(temp_dir, "chrom_range.npy"))
+    node2bin = np.load(os.path.join(temp_dir, "node2bin.npy"), allow_pickle=True).item()
+    parts = parse_parts(args.part, chrom_range, config["chrom_list"])
+    k = sum(m for _, _, m in parts)
+    min_gap = args.min_gap if args.min_gap is not None else int(config["min_distance"]) + 1
+    dev = model.layer_norm1.weight.device
+    exclude = None
+    if args.exclude_known:
+        known = np.load(os.path.join(temp_dir, "all_%d_counter.npy" % k)).astype(np.int64).reshape(-1, k)
+        exclude = HyperedgeSet(torch.from_numpy(known).to(dev))
+    npz = os.path.splitext(args.output)[0] + ".npz"
+    if args.map is not None:
+        r, c = args.map
+        out = SW.region_map(model, parts, min_gap, r, c, chunk_rows=args.chunk_rows, width=args.width, exclude=exclude, task_mode=args.task_mode,
+                            threshold=args.threshold, value_max=args.value_max)
+        np.savez(npz, **{name: out[name].cpu().numpy() for name in ("sum", "mean", "max", "count", "count_ge")},
+                 parts=np.asarray(parts, dtype=np.int64), rows_part=np.int64(r), cols_part=np.int64(c), min_gap=np.int64(min_gap),
+                 threshold=np.float32(args.threshold))
+        print("%d candidates (%d against the gap rule, %d known, skipped; %d rejected) -> %d x %d map in %s"
+              % (out["n_candidates"], out["n_invalid"], out["n_excluded"], out["n_rejected"], parts[r][1] - parts[r][0], parts[c][1] - parts[c][0], npz))
+        return
+    if args.top is None:
+        raise ValueError("regions needs --top (or --map R C)")
+    out = SW.region_sweep(model, parts, min_gap, args.top, chunk_rows=args.chunk_rows, width=args.width, exclude=exclude,
+                          task_mode=args.task_mode, per_leading=args.per_leading)
+    rows, proba = out["rows"].cpu().numpy(), out["proba"].cpu().numpy()
+    extra = {}
+    with open(args.output, "w") as f:
+        if args.per_leading:
+            count = out["count"].cpu().numpy()
+            extra = dict(count=count, leading=out["leading"].cpu().numpy())
+            kept = int(count.sum())
+            for a in range(len(count)):                                  # grouped by the leading candidate, best first
+                for r, p in zip(rows[a, :count[a]], proba[a, :count[a]]):
+                    f.write("\t".join([node2bin[int(v)] for v in r[:k]] + [repr(float(p))]) + "\n")
+        else:
+            kept = len(rows)
+            for r, p in zip(rows, proba):
+                f.write("\t".join([node2bin[int(v)] for v in r[:k]] + [repr(float(p))]) + "\n")
+    np.savez(npz, rows=rows, logit=out["logit"].cpu().numpy(), proba=proba, rank=out["rank"].cpu().numpy(), **extra)
+    print("%d candidates (%d against the gap rule, %d known, skipped) -> %d in %s"
+          % (out["n_candidates"], out["n_invalid"], out["n_excluded"], kept, args.output))
 
 
 def parse_anchor_file(filepath: str, bin2node: Dict[str, int], chrom_list: Sequence[str], res: int) -> np.ndarray:
@@ -601,6 +699,23 @@ def main(argv=None):
     k.add_argument("--pair-support", action="store_true", help="also write <output>_pairs.npz: per cluster the s x s mean probability and number of the candidates that contain both loci (--size >= 2)")
     k.add_argument("-o", "--output", type=str, default="./decompose.tsv")
     k.add_argument("--config", type=str, default="./config.JSON")
+    r = sub.add_parser("regions", help="multi-region sweep: the best --top candidates with bins drawn from several chromosomes or bin windows")
+    r.add_argument("--part", action="append", default=[], metavar="CHROM:COUNT[:START-END]",
+                   help="repeatable, 1 .. 8 times in ascending genome order: COUNT bins drawn from chromosome CHROM (index into config chrom_list, "
+                        "or its name), or from its bins START .. END - 1")
+    r.add_argument("--top", type=int, default=None, help="how many candidates to keep (with --per-leading: per candidate of the first part)")
+    r.add_argument("--min-gap", type=int, default=None, help="smallest difference of adjacent node ids in a candidate (default: min_distance + 1)")
+    r.add_argument("--per-leading", action="store_true", help="keep the best --top for every candidate of the first part (needs two parts or more)")
+    r.add_argument("--map", type=int, nargs=2, default=None, metavar=("R", "C"),
+                   help="write the pair map between the bins of parts R and C (R = C: within one part) to the .npz instead of a list")
+    r.add_argument("--threshold", type=float, default=0.5, help="--map: count_ge counts the candidates of a pair with a value >= this")
+    r.add_argument("--value-max", type=float, default=None, help="--map with task-mode regress: the largest value a candidate may contribute (<= 2^20)")
+    r.add_argument("--exclude-known", action="store_true", help="skip the hyperedges of temp_dir/all_<k>_counter.npy")
+    r.add_argument("--width", type=int, default=None, help="zero-pad rows to this width (default k): a logit depends on its batch's width")
+    r.add_argument("--chunk-rows", type=int, default=1 << 20)
+    r.add_argument("--task-mode", choices=["class", "regress"], default="class", help="the model's training objective: sigmoid or softplus outputs")
+    r.add_argument("-o", "--output", type=str, default="./regions.tsv")
+    r.add_argument("--config", type=str, default="./config.JSON")
     e = sub.add_parser("kmap", help="pair map: the probabilities of all candidates of size --k projected onto pairs of bins")
     e.add_argument("--chrom", type=int, required=True, help="index into config chrom_list")
     e.add_argument("--k", type=int, required=True, help="candidate size, 2 .. 8")
@@ -633,6 +748,8 @@ def main(argv=None):
         return _grow(args, config, temp_dir, model)
     if args.cmd == "decompose":
         return _decompose(args, config, temp_dir, model)
+    if args.cmd == "regions":
+        return _regions(args, config, temp_dir, model)
     if args.cmd == "kmap":
         return _kmap(args, config, temp_dir, model)
     if args.cmd == "attention":

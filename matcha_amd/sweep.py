@@ -16,6 +16,10 @@ csrc/pairmap.hip) project the scores of all candidates onto pairs of bins instea
  extends clusters of 1 to 31 loci by bins of a region; ``decomposition_sweep`` ranks the sub-hyperedges
 made of a cluster's own loci, or the cluster with some of them taken out, and sums the scores per locus (``SubsetSupport``).
 ``growth_sweep`` (csrc/grow.hip) beam-searches hubs of up to 32 loci from seed clusters, one bin per step (``grow_step``).
+``region_sweep`` / ``region_map`` draw a candidate's bins from up to 8 ascending, disjoint regions -- one bin on chr1, one on
+chr6, two on chr11: each part contributes one candidate of its own region, the global rank is the mixed radix of the parts' ranks
+(``region_count``, ``region_unrank``, ``region_rows``), and the result is the best K overall, the best K per candidate of the leading part, or
+the pair map between two parts.
 """
 from __future__ import annotations
 
@@ -1547,4 +1551,295 @@ def growth_sweep(model, seeds, lo: int, hi: int, max_size: int, beam: int = 8, m
         out["path"] = torch.where(live.view(A, B, 1), out["path"], torch.zeros_like(out["path"]))
     c = counters.tolist()
     out.update(n_candidates=n_cand, n_invalid=c[0], n_twins=c[1], n_excluded=c[2], steps=n_steps)
+    return out
+
+
+# ---- multi-region sweep: candidates with bins drawn from several regions ------------------------------------------
+MAX_PARTS = 8
+
+
+def _subset_unrank(rank: int, lo: int, n: int, f: int, min_gap: int) -> Tuple[int, ...]:
+    """The gap-constrained subset of size f >= 1 of [lo, lo + n) of lexicographic rank ``rank`` (kway_unrank's decoding, f = 1 allowed)."""
+    m = n - (f - 1) * (min_gap - 1)
+    total = math.comb(m, f) if m >= f else 0
+    row, q, upper = [], total - 1 - rank, m - 1
+    for j in range(f, 0, -1):
+        a, b = j - 1, upper
+        while a < b:
+            mid = (a + b + 1) // 2
+            if math.comb(mid, j) <= q:
+                a = mid
+            else:
+                b = mid - 1
+        q -= math.comb(a, j)
+        row.append(lo + (m - 1 - a) + (f - j) * (min_gap - 1))
+        upper = a - 1
+    return tuple(row)
+
+
+def _region_parts(parts, min_gap: int):
+    """(lo [P], n [P], m [P], C [P], k) of a validated part list; every refusal is a ValueError."""
+    try:
+        parts = [(int(lo), int(hi), int(m)) for lo, hi, m in parts]
+    except (TypeError, ValueError):
+        raise ValueError("parts must be a sequence of (lo, hi, m)")
+    min_gap = int(min_gap)
+    if not 1 <= len(parts) <= MAX_PARTS:
+        raise ValueError(f"need 1 to {MAX_PARTS} parts (got {len(parts)})")
+    if min_gap < 1:
+        raise ValueError(f"need min_gap >= 1 (min_gap={min_gap})")
+    for p, (lo, hi, m) in enumerate(parts):
+        if m < 1 or hi - lo < 1 or hi - lo >= 1 << 31:
+            raise ValueError(f"part {p}: need a region of 1 <= hi - lo < 2^31 bins and m >= 1 bins drawn from it (lo={lo} hi={hi} m={m})")
+        if not 0 <= lo <= 1 << 62:
+            raise ValueError(f"part {p}: lo out of range (lo={lo})")
+        if p and parts[p - 1][1] > lo:
+            raise ValueError(f"the regions must be ascending and disjoint: part {p} begins at {lo}, part {p - 1} ends at {parts[p - 1][1]}")
+    k = sum(m for _, _, m in parts)
+    if not 2 <= k <= _lib.MAX_L:
+        raise ValueError(f"need 2 <= k <= {_lib.MAX_L} bins per candidate (k={k})")
+    counts = [_free_count(hi - lo, m, min_gap) for lo, hi, m in parts]
+    return [lo for lo, _, _ in parts], [hi - lo for lo, hi, _ in parts], [m for _, _, m in parts], counts, k
+
+
+def region_count(parts, min_gap: int) -> int:
+    """Number of candidates of a multi-region sweep: T = prod C_p with C_p = C(n_p - (m_p - 1)(min_gap - 1), m_p).  ``parts`` is a
+    sequence of (lo, hi, m), 1 to 8 of them: m >= 1 bins drawn from the region [lo, hi) of node ids; the regions ascending and pairwise
+    disjoint, 2 <= sum m <= 8.  A total >= 2^63 is refused (ValueError), not truncated."""
+    _, _, _, counts, _ = _region_parts(parts, min_gap)
+    total = math.prod(counts)
+    if total >= 1 << 63:
+        raise ValueError(f"{total} candidates (parts={list(parts)} min_gap={min_gap}) do not fit 63 bits")
+    return total
+
+
+def region_unrank(rank: int, parts, min_gap: int) -> Tuple[Tuple[int, ...], bool]:
+    """(row, valid) of the candidate of global rank ``rank``, in Python integers (no GPU): how a rank is decoded, and the checker of the
+    kernel.  The rank is the mixed radix ((r_0 C_1 + r_1) C_2 + ...) C_{P-1} + r_{P-1} of the parts' own lexicographic ranks; the row is
+    the parts' candidates one behind the other, ascending as it stands.  It is valid iff every adjacent difference is >= min_gap, which
+    can only fail between the last bin of one part and the first of the next."""
+    los, ns, ms, counts, _ = _region_parts(parts, min_gap)
+    total = region_count(parts, min_gap)
+    rank, min_gap = int(rank), int(min_gap)
+    if not 0 <= rank < total:
+        raise IndexError(f"rank {rank} outside [0, {total})")
+    pieces = []
+    for p in range(len(los) - 1, -1, -1):
+        rank, r = divmod(rank, counts[p])
+        pieces.append(_subset_unrank(r, los[p], ns[p], ms[p], min_gap))
+    row = tuple(v for piece in reversed(pieces) for v in piece)
+    return row, all(b - a >= min_gap for a, b in zip(row, row[1:]))
+
+
+def _part_arrays(los, ns, ms):
+    P = len(los)
+    return (C.c_int64 * P)(*los), (C.c_int32 * P)(*ns), (C.c_int32 * P)(*ms)
+
+
+def region_rows(parts, min_gap: int, rank0: int = 0, count: Optional[int] = None, ranks: Optional[torch.Tensor] = None,
+                width: Optional[int] = None, device="cuda", out: Optional[torch.Tensor] = None,
+                flag_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(x int64 [count, width], flag int32 [count]) on the device: the candidates of the global ranks rank0 .. rank0 + count - 1, or of
+    the device list ``ranks`` (a rank outside [0, T) gives an all-zero row with its flag set); flag != 0 marks an invalid candidate
+    (region_unrank's rule).  Columns k .. width - 1 are zero (k <= width <= 8).  ``out`` / ``flag_out`` reuse buffers of at least
+    count * width / count elements."""
+    lib = _lib.load()
+    los, ns, ms, _, k = _region_parts(parts, min_gap)
+    total = region_count(parts, min_gap)
+    min_gap = int(min_gap)
+    width = int(k if width is None else width)
+    if not k <= width <= _lib.MAX_L:
+        raise ValueError(f"width must be in [k, {_lib.MAX_L}]")
+    if ranks is not None:
+        ranks = ranks.to(device=device, dtype=torch.long).contiguous().view(-1)
+        count, device = int(ranks.numel()), ranks.device
+    else:
+        if out is not None:
+            device = out.device
+        rank0 = int(rank0)
+        count = total - rank0 if count is None else int(count)
+        if rank0 < 0 or count < 0 or rank0 + count > total:
+            raise IndexError(f"ranks [{rank0}, {rank0 + count}) outside [0, {total})")
+    if out is None:
+        x = torch.empty(count, width, dtype=torch.long, device=device)
+    else:
+        if out.dtype != torch.long or not out.is_contiguous() or out.numel() < count * width:
+            raise ValueError("out must be a contiguous int64 tensor of at least count * width elements")
+        x = out.view(-1)[:count * width].view(count, width)
+    if flag_out is None:
+        flag = torch.empty(count, dtype=torch.int32, device=x.device)
+    else:
+        if flag_out.dtype != torch.int32 or not flag_out.is_contiguous() or flag_out.numel() < count or flag_out.device != x.device:
+            raise ValueError("flag_out must be a contiguous int32 tensor of at least count elements on out's device")
+        flag = flag_out.view(-1)[:count]
+    if not x.is_cuda:
+        raise _lib.MatchaHipError("region_rows needs a cuda device (no CPU fallback)")
+    arrays = _part_arrays(los, ns, ms)                                   # host arrays, alive until the call returns: it reads them before
+    lo_a, n_a, m_a = (C.cast(a, C.c_void_p) for a in arrays)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.matcha_kway_region_rows(len(los), lo_a, n_a, m_a, min_gap, int(rank0), _lib.ptr(ranks), count, width, _lib.ptr(x),
+                                               _lib.ptr(flag), _stream(x.device)), "matcha_kway_region_rows")
+    return x, flag
+
+
+def region_sweep(model, parts, min_gap: int, top: int, chunk_rows: int = 1 << 20, width: Optional[int] = None, exclude=None,
+                 task_mode: str = "class", per_leading: bool = False) -> dict:
+    """Score every candidate of a multi-region sweep (``parts``: (lo, hi, m) per region, see region_count) and keep the ``top`` best.
+
+    Returns ``rows`` int64 [K', width], ``logit`` and ``proba`` [K'], ``rank`` int64 [K'] (the global rank; decode one with
+    region_unrank), on the model's device and best first, and the integers ``n_candidates`` = T, ``n_invalid`` (candidates that break
+    the gap rule across a part boundary; they are scored but never kept) and ``n_excluded`` (valid candidates found in ``exclude``).
+
+    ``per_leading=True`` (needs two parts or more) keeps the best ``top`` PER CANDIDATE OF THE LEADING PART instead: with A = C_0 and
+    K = min(top, T / C_0) it returns ``rows`` [A, K, width], ``logit``, ``proba`` and ``rank`` [A, K], ``count`` int64 [A] and
+    ``leading`` int64 [A, m_0], the leading part's candidates in rank order; beyond count[a] the rank is -1 and rows, logit and proba
+    are 0.  With m_0 = 1 that is, for every bin of the first region, its best hubs with partners in all the others.  An empty sweep
+    (T = 0) returns A = 0.
+
+    The loop is kway_sweep's: eval mode, no grad, the large-batch route pinned, one reused row buffer and one reused flag buffer,
+    nothing synchronises until the end, where the node-id check of the whole sweep is raised once (IndexError)."""
+    if task_mode not in ("class", "regress"):
+        raise ValueError("task_mode must be 'class' or 'regress'")
+    los, ns, ms, counts, k = _region_parts(parts, min_gap)
+    parts = [(lo, lo + n, m) for lo, n, m in zip(los, ns, ms)]
+    min_gap, top, chunk_rows = int(min_gap), int(top), int(chunk_rows)
+    width = int(k if width is None else width)
+    if not k <= width <= _lib.MAX_L:
+        raise ValueError(f"width must be in [k, {_lib.MAX_L}]")
+    if top < 1 or chunk_rows < 1:
+        raise ValueError("top and chunk_rows must be >= 1")
+    if per_leading and len(parts) < 2:
+        raise ValueError("per_leading needs at least two parts")
+    total = region_count(parts, min_gap)
+    act = torch.nn.functional.softplus if task_mode == "regress" else torch.sigmoid
+    model.eval()
+    dev = model.layer_norm1.weight.device
+    if total == 0:
+        e = torch.empty(0, dtype=torch.float32, device=dev)
+        out = {"rows": torch.empty(0, width, dtype=torch.long, device=dev), "logit": e, "proba": e.clone(),
+               "rank": torch.empty(0, dtype=torch.long, device=dev), "n_candidates": 0, "n_invalid": 0, "n_excluded": 0}
+        if per_leading:
+            out.update(rows=out["rows"].view(0, 0, width), logit=e.view(0, 0), proba=e.clone().view(0, 0), rank=out["rank"].view(0, 0),
+                       count=torch.empty(0, dtype=torch.long, device=dev), leading=torch.empty(0, ms[0], dtype=torch.long, device=dev))
+        return out
+    chunk_rows = min(chunk_rows, total)
+    if per_leading:
+        A, seg_len = counts[0], total // counts[0]
+        K = min(top, seg_len)
+        sel = SegTopK(A, K, seg_len, chunk_rows, dev)
+    else:
+        sel = TopK(min(top, total), chunk_rows, dev)
+    buf = torch.empty(chunk_rows * width, dtype=torch.long, device=dev)
+    fbuf = torch.empty(chunk_rows, dtype=torch.int32, device=dev)
+    n_inv = torch.zeros((), dtype=torch.long, device=dev)
+    n_exc = torch.zeros((), dtype=torch.long, device=dev)
+    with torch.no_grad(), model.deferred_id_check(), _lib.option("disable_small_batch"):      # as kway_sweep: one forward route
+        for g0 in range(0, total, chunk_rows):
+            x, flag = region_rows(parts, min_gap, rank0=g0, count=min(chunk_rows, total - g0), width=width, out=buf, flag_out=fbuf)
+            logits = model(x).reshape(-1)
+            skip = flag != 0
+            n_inv += skip.sum()
+            if exclude is not None:
+                known = exclude.contains(x)
+                n_exc += (known & ~skip).sum()
+                skip = skip | known
+            sel.update(logits, g0, skip)
+    if not per_leading:
+        logit, rank = sel.result()
+        rows, _ = region_rows(parts, min_gap, ranks=rank, width=width, device=dev)
+        return {"rows": rows, "logit": logit, "proba": act(logit), "rank": rank, "n_candidates": total, "n_invalid": int(n_inv.item()),
+                "n_excluded": int(n_exc.item())}
+    logit, rank, count = sel.read()
+    rows, _ = region_rows(parts, min_gap, ranks=rank, width=width, device=dev)
+    if ms[0] == 1:
+        leading = torch.arange(los[0], los[0] + ns[0], dtype=torch.long, device=dev).view(-1, 1)
+    else:                                                                # the first candidate of every segment begins with it
+        first = torch.arange(A, dtype=torch.long, device=dev) * seg_len
+        leading = region_rows(parts, min_gap, ranks=first, device=dev)[0][:, :ms[0]].contiguous()
+    proba = torch.where(rank >= 0, act(logit), torch.zeros_like(logit))
+    return {"rows": rows.view(A, K, width), "logit": logit, "proba": proba, "rank": rank, "count": count, "leading": leading,
+            "n_candidates": total, "n_invalid": int(n_inv.item()), "n_excluded": int(n_exc.item())}
+
+
+def region_map_bound(parts, min_gap: int, rows_part: int, cols_part: int) -> int:
+    """An upper bound, certainly not too small, on the candidates of a multi-region sweep that pass through one cell of region_map's
+    pair map: rectangular (rows_part != cols_part), prod_{p not in {r, c}} C_p * C(n_r - 1, m_r - 1) * C(n_c - 1, m_c - 1) -- one bin of
+    each of the two parts is fixed, the others are counted without the gap rule; symmetric, prod_{p != r} C_p * C(n_r - 2, m_r - 2)."""
+    _, ns, ms, counts, _ = _region_parts(parts, min_gap)
+    r, c = int(rows_part), int(cols_part)
+    others = math.prod(cp for p, cp in enumerate(counts) if p not in (r, c))
+    if r != c:
+        return others * math.comb(ns[r] - 1, ms[r] - 1) * math.comb(ns[c] - 1, ms[c] - 1)
+    return others * math.comb(ns[r] - 2, ms[r] - 2)
+
+
+def region_map(model, parts, min_gap: int, rows_part: int, cols_part: int, chunk_rows: Optional[int] = 1 << 20, width: Optional[int] = None,
+               exclude=None, task_mode: str = "class", threshold: float = 0.5, planes="all", value_max: Optional[float] = None) -> dict:
+    """Score every candidate of a multi-region sweep (region_sweep's candidates, in its order, through its loop) and project the
+    probabilities onto pairs of bins, as kway_map does.  ``rows_part`` != ``cols_part`` (indices into ``parts``) gives the rectangular
+    map [n_r, n_c] between the bins of two parts -- with parts on two chromosomes, the inter-chromosomal pair map; ``rows_part`` ==
+    ``cols_part`` (a part with m >= 2) gives the symmetric map over that part's region (mirrored, zero diagonal).  Invalid candidates and
+    the members of ``exclude`` contribute nothing.  Values, ``value_max``, ``threshold`` and ``planes`` as in kway_map; a sweep whose
+    bound per cell (region_map_bound) times the largest value reaches 2^31 is refused before anything is launched.  The planes do not
+    depend on ``chunk_rows`` (None: one chunk), bit for bit.
+
+    Returns the planes (device tensors) and the integers ``n_candidates``, ``n_invalid``, ``n_excluded`` and ``n_rejected``."""
+    if task_mode not in ("class", "regress"):
+        raise ValueError("task_mode must be 'class' or 'regress'")
+    los, ns, ms, counts, k = _region_parts(parts, min_gap)
+    parts = [(lo, lo + n, m) for lo, n, m in zip(los, ns, ms)]
+    min_gap = int(min_gap)
+    width = int(k if width is None else width)
+    if not k <= width <= _lib.MAX_L:
+        raise ValueError(f"width must be in [k, {_lib.MAX_L}]")
+    total = region_count(parts, min_gap)
+    chunk_rows = max(total, 1) if chunk_rows is None else int(chunk_rows)
+    if chunk_rows < 1:
+        raise ValueError("chunk_rows must be >= 1")
+    r, c = int(rows_part), int(cols_part)
+    if not (0 <= r < len(parts) and 0 <= c < len(parts)):
+        raise ValueError(f"rows_part and cols_part must be indices into the {len(parts)} parts")
+    if r == c and ms[r] < 2:
+        raise ValueError(f"a symmetric map over part {r} needs at least two bins drawn from it (m={ms[r]})")
+    if task_mode == "regress":
+        if value_max is None:
+            raise ValueError("task_mode 'regress' needs value_max: the largest value a candidate may contribute")
+        vmax, act = float(value_max), torch.nn.functional.softplus
+    else:
+        vmax, act = 1.0, torch.sigmoid
+    if not 0.0 < vmax <= float(1 << 20):
+        raise ValueError("value_max must be in (0, 2^20]")
+    mask = _plane_mask(planes)
+    bound = region_map_bound(parts, min_gap, r, c)
+    if bound * vmax >= float(1 << 31):
+        raise ValueError(f"a cell may receive {bound} candidates of value <= {vmax}: the sum's capacity of 2^31 per cell is not enough "
+                         "(sweep smaller regions)")
+    model.eval()
+    dev = model.layer_norm1.weight.device
+    if total == 0:
+        out = _empty_map(ns[r], ns[c], mask, dev)
+        if r != c and "max" in out:
+            out["max"].fill_(float("-inf"))                              # a rectangular map has no diagonal
+        out.update(n_candidates=0, n_invalid=0, n_excluded=0, n_rejected=0)
+        return out
+    chunk_rows = min(chunk_rows, total, (1 << 31) - 1)
+    pm = PairMap((los[r], ns[r]), (los[c], ns[c]), mask, vmax=vmax, threshold=threshold, device=dev)
+    buf = torch.empty(chunk_rows * width, dtype=torch.long, device=dev)
+    fbuf = torch.empty(chunk_rows, dtype=torch.int32, device=dev)
+    n_inv = torch.zeros((), dtype=torch.long, device=dev)
+    n_exc = torch.zeros((), dtype=torch.long, device=dev)
+    with torch.no_grad(), model.deferred_id_check(), _lib.option("disable_small_batch"):      # as kway_sweep: one forward route
+        for g0 in range(0, total, chunk_rows):
+            x, flag = region_rows(parts, min_gap, rank0=g0, count=min(chunk_rows, total - g0), width=width, out=buf, flag_out=fbuf)
+            value = act(model(x).reshape(-1))
+            skip = flag != 0
+            n_inv += skip.sum()
+            if exclude is not None:
+                known = exclude.contains(x)
+                n_exc += (known & ~skip).sum()
+                skip = skip | known
+            pm.update(x, value, skip)
+    out = pm.result()
+    out.pop("n_rows")
+    out.update(n_candidates=total, n_invalid=int(n_inv.item()), n_excluded=int(n_exc.item()), n_rejected=int(out["n_rejected"].item()))
     return out
