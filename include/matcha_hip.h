@@ -297,6 +297,22 @@ int matcha_get_embedding_long(const matcha_shape* shp, const matcha_tensors* par
                               const matcha_step_opts* opts, const int64_t* x, int64_t B, int32_t L, float* dynamic,
                               float* static_, float* attn, float* losses, void* ws, size_t ws_bytes, matcha_stream_t stream);
 
+/* Per-locus scores: which locus of a hyperedge does the model support least?  The reference's logit is the masked mean of a per-position
+ * score, pff_classifier((layer_norm1(dynamic) - layer_norm2(static))^2) of shape [B, L, 1] (Modules.py:290-311); this entry keeps it.
+ * matcha_forward_long's chain up to pff_n1's convolutions, on its workspace (matcha_workspace_bytes_long), with its bounds, option rules and
+ * refusals (2 <= L <= 32, training 0, forward_only 1, no random_chrom_dev, opts->status honoured); then head_scores_kernel, which is
+ * head_fwd_kernel with the per-token value kept:
+ *   scores float [B,L]       the score of the locus in slot l of x[b] (a zero inside a row stays where it stands), exactly 0.0f at padding slots;
+ *   logits float [B]         optional (may be NULL): sum of the row's scores / (k + 1e-15) -- the bits matcha_forward_long writes for the same (x, L);
+ *   lowest, order            0 <= lowest <= 32; order int64 [B, lowest], NULL iff lowest == 0: order[b][j] = the slot of the j-th lowest score among
+ *                            the row's k real loci -- ascending by value, ties to the lower slot, a NaN behind every number --, -1 for j >= k;
+ *   losses float [3]         as matcha_forward_long, may be NULL.
+ * The kernel writes every element of scores, logits and order itself: the buffers need no memset and nothing runs behind it.
+ * A workspace below the query's size is MATCHA_ENOMEM, every other refusal MATCHA_EINVAL, all before any device call.  Not differentiable. */
+int matcha_locus_scores(const matcha_shape* shp, const matcha_tensors* params, const matcha_frozen* frozen,
+                        const matcha_step_opts* opts, const int64_t* x, int64_t B, int32_t L, float* scores, float* logits,
+                        int32_t lowest, int64_t* order, float* losses, void* ws, size_t ws_bytes, matcha_stream_t stream);
+
 /* Long rows, training: matcha_forward_long_train is the chain of matcha_forward_long with every activation the backward needs kept in a
  * buffer of its own (x0, X, the LayerNorm statistics, qin / kin / vin, Q or r, O or Z -- not written over Q --, Y, H1, H2, the logits);
  * matcha_backward_long is the layer-by-layer chain of matcha_backward on that layout, with the attention backward of
@@ -463,6 +479,26 @@ int matcha_neg_sample_long(const void* set, const int64_t* set_edges, int64_t n_
                            const int64_t* pos, int64_t P, int32_t L, int32_t neg_num, int32_t min_dis,
                            const int32_t* node2chrom, int32_t n_nodes, const int32_t* chrom_range, int32_t n_chrom,
                            const uint64_t* seed, int64_t* neg, int32_t* status, matcha_stream_t stream);
+
+/* Planted outliers (the reference's generate_outlier_part, History_version/Code/utils.py:184-233): `draws` copies of every positive
+ * (int64 [P,L] zero-padded ascending, 1 <= L <= 32) with ONE locus replaced by a foreign bin of the same chromosome.  Local row i is global
+ * row n = n0 + i, a copy of positive i / draws (n0 >= 0; a caller that cuts its positives into chunks passes n0 = draws * (positives in front
+ * of the chunk), so that n / draws is the positive and n % draws the copy, and gets the rows of one call).  k = the positive's non-zero prefix.  Counter RNG of oracle/rng.py,
+ * stream 18, hi counter n:
+ *   position   p = (n % draws) % k with `cycle`, else (rand(key, n, 0xFFFF0000) * k) >> 32;
+ *   trial t    (0 .. 255) bin j = start + ((rand(key, n, t) * (end - start)) >> 32) in the chromosome of the positive's locus p; cand = the
+ *              positive without locus p plus j, ascending.  Refused: j is a locus of the positive; an adjacent gap of cand <= min_dis;
+ *              (pair set given) a pair (min(j, v), max(j, v)), v another locus of cand, is in the pair set; (set given) cand is in the set.
+ *   out        int64 [P*draws, L] = cand zero-padded; planted int32 [P*draws] = the index of j in cand.
+ * No plant -- 256 trials exhausted, k < 2, a locus outside [1, n_nodes], locus p without a chromosome: the row is a copy of the positive and
+ * planted = -1.  status (optional device int32[4]): [0] |= MATCHA_STATUS_BAD_CHROM for the last two, [1] += rows whose trials were exhausted.
+ * Both sets are tables of matcha_hashset_build(_long) over their edge lists; n_*_edges == 0 switches that refusal off (buffers may be NULL).
+ * Every argument check of matcha_neg_sample_long; P*draws and n0 + P*draws below 2^31.  outlier_plant_kernel: 32 lanes per row. */
+int matcha_outlier_plant(const void* set, const int64_t* set_edges, int64_t n_set_edges, int32_t L_set,
+                         const void* pair_set, const int64_t* pair_edges, int64_t n_pair_edges, int32_t L_pair,
+                         const int64_t* pos, int64_t P, int32_t L, int32_t draws, int32_t cycle, int32_t min_dis,
+                         const int32_t* node2chrom, int32_t n_nodes, const int32_t* chrom_range, int32_t n_chrom,
+                         const uint64_t* seed, int64_t n0, int64_t* out, int32_t* planted, int32_t* status, matcha_stream_t stream);
 
 /* The bookkeeping of one step of the reference's epoch loop (main.py:155-188) on the device, so that an epoch can replay one captured
  * step (matcha_amd/train.py).  `it` is a device int64 step counter.

@@ -15,6 +15,7 @@ HIP path unchanged: the runtime state is rebuilt lazily from the module tree.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import math
 import os
@@ -32,6 +33,9 @@ __all__ = ["Classifier", "MultipleEmbedding", "Wrap_Embedding", "SparseEmbedding
            "FeedForward", "DataGenerator", "get_non_pad_mask", "get_attn_key_pad_mask"]
 
 _PUBLIC_MODULE = "Modules"   # pickles refer to `Modules.<Class>` exactly like the reference's (main.py:322)
+
+# what Classifier.locus_scores returns: logits [B,1], scores [B,L], order [B,lowest] int64 or None
+LocusScores = collections.namedtuple("LocusScores", ["logits", "scores", "order"])
 
 
 def _default_device() -> torch.device:
@@ -739,6 +743,8 @@ class Classifier(nn.Module):
 
     # ---- the reference's call surface -----------------------------------------------------------------
     def forward(self, x, mask=None, get_outlier=None, return_recon=False):
+        """Logits [B, 1] of the hyperedges x [B, L] (reference Modules.py:278-311).  ``mask`` and ``get_outlier`` are accepted and ignored,
+        as the reference ignores them; what ``get_outlier`` was for -- the least supported loci of a hyperedge -- is ``locus_scores``."""
         rt = self._runtime()
         x = torch.as_tensor(x).to(device=rt.device, dtype=torch.long)
         if x.dim() != 2:
@@ -783,6 +789,46 @@ class Classifier(nn.Module):
             rt.check_status("Classifier.forward")
         logits = logits.view(B, 1)
         return (logits, losses[1:2]) if return_recon else logits
+
+    def locus_scores(self, x, lowest: int = 0):
+        """Which locus of a hyperedge does the model support least?  ``LocusScores(logits [B,1], scores [B,L], order)``: ``scores[b, l]`` is
+        the reference's per-position output ``pff_classifier((layer_norm1(dynamic) - layer_norm2(static))**2)`` (Modules.py:290-311) of the
+        locus in slot l of ``x[b]``, exactly 0 at padding slots, and ``logits[b] = scores[b].sum() / (k + 1e-15)`` -- the bits ``model(x)``
+        returns on the long-row chain.  ``order`` (``lowest`` > 0, at most 32; otherwise None) is int64 [B, lowest]: the slots of the row's
+        ``lowest`` least supported loci, ascending by score, ties to the lower slot, -1 behind the row's k real loci.
+
+        Every width 2 .. 32, one forward (the layer-by-layer long-row chain at every width and embed_dim, then head_scores_kernel).  Scores
+        depend on the batch width L as the logits do: the reference's softmax runs over the padding key slots too (SURVEY.md headline fact
+        7), so score a cluster at the width it will be compared at.  Eval mode only, not differentiable; ``check_ids`` /
+        ``deferred_id_check`` and the one ``np.random.choice`` per call in adj mode as in ``forward``."""
+        rt = self._runtime()
+        x = torch.as_tensor(x).to(device=rt.device, dtype=torch.long)
+        if x.dim() != 2:
+            raise ValueError("x must be [B, L] node ids (0 = padding)")
+        x = x.contiguous()
+        B, L = x.shape
+        if L < 2 or L > _lib.MAX_LONG_L:
+            raise ValueError(f"locus_scores takes hyperedges of 2 .. {_lib.MAX_LONG_L} columns (x has {L})")
+        lowest = int(lowest)
+        if lowest < 0 or lowest > _lib.MAX_LONG_L:
+            raise ValueError(f"lowest={lowest} outside 0 .. {_lib.MAX_LONG_L}")
+        if self.training:
+            raise NotImplementedError("locus_scores is inference-only (the scores of a dropout forward are not kept): call model.eval() first")
+        opts, _ = self._opts(rt, False)              # one np.random.choice in adj mode; training = 0, no seed
+        opts.forward_only = 1
+        opts.status = rt.status.data_ptr()
+        ws = rt.workspace(B, L, long_rows=True)
+        scores = torch.empty(B, L, dtype=torch.float32, device=rt.device)
+        logits = torch.empty(B, dtype=torch.float32, device=rt.device)
+        order = torch.empty(B, lowest, dtype=torch.long, device=rt.device) if lowest else None
+        losses = torch.zeros(3, dtype=torch.float32, device=rt.device)
+        _lib.check(rt.lib.matcha_locus_scores(C.byref(rt.shape), C.byref(rt.params), C.byref(rt.frozen), C.byref(opts), _lib.ptr(x), B, L,
+                                              _lib.ptr(scores), _lib.ptr(logits), lowest, _lib.ptr(order), _lib.ptr(losses), _lib.ptr(ws),
+                                              ws.numel(), rt.stream()),
+                   "matcha_locus_scores")
+        if self.check_ids and not torch.cuda.is_current_stream_capturing():
+            rt.check_status("Classifier.locus_scores")
+        return LocusScores(logits.view(B, 1), scores, order)
 
     def get_node_embeddings(self, x, return_recon=False):
         """Rows of the node-embedding front end, [B, L, d] (reference Modules.py:252-259).  Inference surface

@@ -120,6 +120,10 @@ SIGNATURES = {
     "matcha_hashset_build_long": (C.c_int, [_fp, _SZ, _fp, _I64, _I32, _fp]),
     "matcha_hashset_contains_long": (C.c_int, [_fp, _fp, _I32, _fp, _I64, _I32, _fp, _fp]),
     "matcha_neg_sample_long": (C.c_int, [_fp, _fp, _I64, _I32, _fp, _I64, _I32, _I32, _I32, _fp, _I32, _fp, _I32, _fp, _fp, _fp, _fp]),
+    "matcha_outlier_plant": (C.c_int, [_fp, _fp, _I64, _I32, _fp, _fp, _I64, _I32, _fp, _I64, _I32, _I32, _I32, _I32, _fp, _I32, _fp, _I32,
+                                       _fp, _I64, _fp, _fp, _fp, _fp]),
+    "matcha_locus_scores": (C.c_int, [C.POINTER(Shape), C.POINTER(Tensors), C.POINTER(Frozen), C.POINTER(StepOpts), _fp, _I64, _I32,
+                                      _fp, _fp, _I32, _fp, _fp, _fp, _SZ, _fp]),
     "matcha_gemm_tn_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
     "matcha_gemm": (C.c_int, [_I32, _fp, _fp, _fp, _I64, _I64, _I64, C.POINTER(GemmEpilogue), _fp, _fp, _fp, _SZ, _fp]),
     "matcha_embed_fwd": (C.c_int, [_fp, _I64, _I32, _fp, _fp, _fp, _I32, _fp, _fp, _fp, _fp]),

@@ -95,7 +95,7 @@ __host__ __device__ __forceinline__ uint32_t dropout_threshold(float p) {
   double t = (double)p * 4294967296.0;
   return t >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)t;
 }
-constexpr uint32_t kStreamDropAdj = 1, kStreamDropFc1 = 2, kStreamDropPff = 3, kStreamNeg = 16;
+constexpr uint32_t kStreamDropAdj = 1, kStreamDropFc1 = 2, kStreamDropPff = 3, kStreamNeg = 16, kStreamOutlier = 18;
 
 // ---- wave-level reductions over groups of 2^k adjacent lanes -----------------------------------
 template <int WIDTH>

@@ -172,6 +172,39 @@ extern "C" int matcha_get_embedding_long(const matcha_shape* shp, const matcha_t
   return launch_expand_embedding(x, B, L, s.d, w.rg.row_off, w.H2, w.X, params->pff_ln_g, params->pff_ln_b, dynamic, static_, st);
 }
 
+// Per-locus scores: matcha_forward_long's chain up to pff_n1's convolutions (same checks, same workspace), then the head that keeps the
+// per-token value (locus.hip: head_scores_kernel writes scores, logits and order completely).
+extern "C" int matcha_locus_scores(const matcha_shape* shp, const matcha_tensors* params, const matcha_frozen* frozen, const matcha_step_opts* opts,
+                                   const int64_t* x, int64_t B, int32_t L, float* scores, float* logits, int32_t lowest, int64_t* order,
+                                   float* losses, void* ws, size_t ws_bytes, matcha_stream_t stream) {
+  static const char fn[] = "matcha_locus_scores";
+  MATCHA_TRY(check_shape_long(shp, B, L, fn));
+  MATCHA_CHECK_ARG(params && frozen && opts && x && ws && scores, "%s: null pointer (only logits, order and losses are optional)", fn);
+  MATCHA_CHECK_ARG(lowest >= 0 && lowest <= MATCHA_MAX_LONG_L, "%s: lowest=%d outside 0..%d", fn, lowest, MATCHA_MAX_LONG_L);
+  MATCHA_CHECK_ARG((lowest == 0) == (order == nullptr), "%s: order must be null when lowest == 0 and only then (lowest=%d)", fn, lowest);
+  MATCHA_CHECK_ARG(opts->training == 0 && opts->forward_only == 1,
+                   "matcha_locus_scores: inference-only (opts->training must be 0 and opts->forward_only 1; got %d, %d)",
+                   (int)opts->training, (int)opts->forward_only);
+  MATCHA_CHECK_ARG(!opts->random_chrom_dev, "matcha_locus_scores: opts->random_chrom_dev needs the fused adj front end; pass opts->random_chrom");
+  const matcha_shape& s = *shp;
+  MATCHA_TRY(check_forward_long(s, *params, *frozen, *opts, ws, fn));
+  const bool merged = long_merged(s);
+  LongWs w;
+  const size_t need = carve_long(s, B, L, (char*)ws, w, merged);
+  if (ws_bytes < need) { set_error("matcha_locus_scores: workspace %zu < %zu bytes", ws_bytes, need); return MATCHA_ENOMEM; }
+  hipStream_t st = (hipStream_t)stream;
+  const ChainCall chain{s, *params, *frozen, *opts, B, L, st, {merged, true, false}, fn};
+
+  forget_forward(ws);
+  MATCHA_TRY(launch_long_plan(x, B, L, s.n_nodes, opts->status, w.rg, w.mask, st));
+  MATCHA_TRY(chain_front_fwd(chain, w, losses ? losses + 1 : nullptr, true));
+  MATCHA_TRY(chain_attn_fwd(chain, w));
+  MATCHA_TRY(chain_tail_fwd(chain, w, nullptr, nullptr, nullptr, nullptr, MATCHA_OBJECTIVE_BCE, true));
+  const matcha_tensors& p = *params;
+  const HeadParams hp = {p.pff_ln_g, p.pff_ln_b, p.ln1_g, p.ln1_b, p.ln2_g, p.ln2_b, p.cls_w, p.cls_b};
+  return launch_head_scores(w.rg.row_off, w.rg.tok_slot, w.H2, w.X, B, L, s.d, hp, scores, logits, lowest, order, st);
+}
+
 extern "C" size_t matcha_workspace_bytes_long_train(const matcha_shape* shp, int64_t B, int32_t L) {
   if (check_shape_long(shp, B, L, "matcha_workspace_bytes_long_train") != MATCHA_OK) return 0;
   LongWs w;

@@ -140,6 +140,10 @@ int launch_head_bwd(const int32_t* row_off, const float* H2, const float* X, int
                     const float* y, const float* w, const float* logits, const float* dlogits, float alpha, float* dH2,
                     float* dXs, float* slab, const HeadParams& ghp, hipStream_t st, int objective = MATCHA_OBJECTIVE_BCE,
                     const int32_t* xrow = nullptr);      // xrow != null: X is a per-node table and token t reads row xrow[t] (node route)
+// locus.hip: head_fwd_kernel's arithmetic with the per-token score kept -- scores [B,L] at the tokens' slots (0.0f elsewhere), logits [B] (optional,
+// the bits of launch_head_fwd), order [B,lowest] (lowest > 0: the slots of the row's `lowest` least scores, -1 behind its k real loci)
+int launch_head_scores(const int32_t* row_off, const int32_t* tok_slot, const float* H2, const float* X, int64_t B, int L, int d,
+                       const HeadParams& hp, float* scores, float* logits, int lowest, int64_t* order, hipStream_t st);
 size_t colsum_slab_bytes(int64_t n, int nv, int d);
 int launch_loss_reduce(const float* row_loss, int64_t B, float* bce_out, hipStream_t st, bool zero_recon = false,     // zero_recon: losses[1..2] = 0 too
                        float* zero_buf = nullptr, size_t zero_bytes = 0);                                               // a buffer zeroed by extra blocks of the launch

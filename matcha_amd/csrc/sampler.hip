@@ -378,6 +378,101 @@ __global__ __launch_bounds__(256) void neg_sample_long_kernel(const int32_t* __r
   if (valid && lane < L) neg[n * L + lane] = result;                       // one coalesced store
 }
 
+// ---- planted outliers (matcha_outlier_plant; the reference's generate_outlier_part, History_version/Code/utils.py:184-233) -------------
+// Is the pair (lo, hi), 1 <= lo < hi, a row of the pair set?  row_hash / set_contains above for a row of two nodes, on two registers: one lane,
+// one probe chain (the reference's dict_pair lookup).
+__device__ __forceinline__ bool pair_contains(const int32_t* __restrict__ set, const int64_t* __restrict__ edges, int L_set, int64_t lo, int64_t hi) {
+  const int64_t cap = reinterpret_cast<const int64_t*>(set)[0];
+  const unsigned long long* slots = reinterpret_cast<const unsigned long long*>(set + kSetHeader);
+  uint64_t h = 0x9E3779B97F4A7C15ull;
+  h ^= (uint64_t)lo + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2); h *= 0xBF58476D1CE4E5B9ull; h ^= h >> 31;
+  h ^= (uint64_t)hi + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2); h *= 0xBF58476D1CE4E5B9ull; h ^= h >> 31;
+  const uint32_t tag = row_tag(h);
+  uint64_t p = h & (uint64_t)(cap - 1);
+  for (int64_t probe = 0; probe < cap; ++probe) {
+    const unsigned long long w = slots[p];
+    const int32_t idx = (int32_t)(uint32_t)(w & 0xFFFFFFFFull);
+    if (idx < 0) return false;
+    if ((uint32_t)(w >> 32) == tag) {
+      const int64_t* row = edges + (int64_t)idx * L_set;
+      if (row[0] == lo && row[1] == hi && (L_set == 2 || row[2] == 0)) return true;
+    }
+    p = (p + 1) & (uint64_t)(cap - 1);
+  }
+  return false;
+}
+
+// One group of 32 lanes per output row, lane i = position i, like neg_sample_long_kernel and under its rule for cross-lane operations: every
+// shuffle and ballot is executed by all 64 lanes, a group with nothing left to do is predicated off (`active`, `ok`).  Local row i is global
+// row n = n0 + i, a copy of positive i / draws (copy n % draws of it where n0 is a multiple of draws).  The plant rule is stated in include/matcha_hip.h.
+constexpr int kPlantTrials = 256;
+__global__ __launch_bounds__(256) void outlier_plant_kernel(const int32_t* __restrict__ set, const int64_t* __restrict__ set_edges, int64_t n_set,
+                                                            int L_set, const int32_t* __restrict__ pair_set, const int64_t* __restrict__ pair_edges,
+                                                            int64_t n_pair, int L_pair, const int64_t* __restrict__ pos, int64_t P, int L, int draws,
+                                                            int cycle, int min_dis, const int32_t* __restrict__ node2chrom, int n_nodes,
+                                                            const int32_t* __restrict__ chrom_range, int n_chrom, const uint64_t* __restrict__ seed,
+                                                            int64_t n0, int64_t* __restrict__ out, int32_t* __restrict__ planted,
+                                                            int32_t* __restrict__ status) {
+  const int lane = (int)threadIdx.x & (kGroup - 1), half = ((int)threadIdx.x / kGroup) & 1;
+  const int64_t i = (int64_t)blockIdx.x * (256 / kGroup) + (int64_t)(threadIdx.x / kGroup);
+  const bool valid = i < P * draws;               // group-uniform; a group behind the end takes part in the exchanges and stores nothing
+  const int64_t n = n0 + i;
+  const int64_t orig = (valid && lane < L) ? pos[(i / draws) * L + lane] : 0;          // one coalesced row read
+  const int k = first_bit(group_ballot(lane >= L || orig == 0, half));                 // the non-zero prefix (32: no zero in the row)
+  const bool in = lane < k && orig >= 1 && orig <= n_nodes;
+  const bool bad_id = group_ballot(lane < k && !in, half) != 0;
+  const int c = node2chrom[in ? orig : 0];
+  const int cidx = (in && c >= 0 && c < n_chrom) ? c : -1;
+  const int2 crange = reinterpret_cast<const int2*>(chrom_range)[cidx >= 0 ? cidx : 0];
+  const uint32_t key = rng_key(*seed, kStreamOutlier);
+  int p = 0;
+  if (k >= 2) p = cycle ? (int)((n % draws) % k) : (int)(((uint64_t)rng_u32(key, (uint32_t)n, 0xFFFF0000u) * (uint64_t)k) >> 32);
+  // the chromosome of the locus that leaves, from its lane
+  const int pc = __shfl(cidx, p, kGroup);
+  const int64_t cstart = __shfl(crange.x, p, kGroup), clen = (int64_t)__shfl(crange.y, p, kGroup) - cstart;
+  const bool no_chrom = k >= 2 && (pc < 0 || clen <= 0);
+  if (valid && lane == 0 && (bad_id || no_chrom) && status) atomicOr(status, MATCHA_STATUS_BAD_CHROM);
+  constexpr int64_t kBig = 0x7FFFFFFFFFFFFFFFll;                           // unused lanes sort behind every node id
+  int64_t result = orig;
+  int plant = -1;
+  bool active = valid && k >= 2 && !bad_id && !no_chrom;
+  for (int trial = 0; trial < kPlantTrials; ++trial) {
+    if (!__any(active)) break;
+    const uint32_t r = rng_u32(key, (uint32_t)n, (uint32_t)trial);
+    const int64_t j = cstart + (int64_t)(((uint64_t)r * (uint64_t)(active ? clen : 0)) >> 32);
+    const bool dup = group_ballot(lane < k && orig == j, half) != 0;       // j is a locus of the positive (the one it replaces included)
+    const int rank = __popc(group_ballot(lane < k && lane != p && orig < j, half));      // where j stands in cand
+    int64_t cand = lane < k ? (lane == p ? j : orig) : kBig;
+    // bitonic sort over the group's 32 lanes, ascending (neg_sample_long_kernel)
+#pragma unroll
+    for (int sz = 2; sz <= kGroup; sz <<= 1) {
+#pragma unroll
+      for (int st = sz >> 1; st > 0; st >>= 1) {
+        const int64_t other = (int64_t)__shfl_xor((long long)cand, st, kGroup);
+        const bool take_min = ((lane & sz) == 0) == ((lane & st) == 0);
+        const int64_t lo = cand < other ? cand : other, hi = cand < other ? other : cand;
+        cand = take_min ? lo : hi;
+      }
+    }
+    const int64_t gap = cand - (int64_t)__shfl_up((long long)cand, 1, kGroup);
+    const bool bad = lane >= 1 && lane < k && (gap == 0 || gap <= min_dis);
+    bool ok = active && !dup && group_ballot(bad, half) == 0;
+    cand = lane < k ? cand : 0;
+    if (n_pair > 0) {                                                      // kernel-uniform: no known pair through the planted bin
+      bool hit = false;
+      if (ok && lane < k && cand != j) hit = pair_contains(pair_set, pair_edges, L_pair, cand < j ? cand : j, cand < j ? j : cand);
+      ok = ok && group_ballot(hit, half) == 0;
+    }
+    bool known = false;
+    if (n_set > 0) known = group_contains(set, set_edges, L_set, cand, L, lane, half, ok);
+    if (ok && !known) { result = cand; plant = rank; active = false; }
+  }
+  // trials exhausted: the row is returned equal to its positive, planted = -1, and counted once
+  if (active && lane == 0 && status) atomicAdd(status + 1, 1);
+  if (valid && lane < L) out[i * L + lane] = result;                       // one coalesced store
+  if (valid && lane == 0) planted[i] = plant;
+}
+
 }  // namespace matcha
 
 using namespace matcha;
@@ -477,5 +572,32 @@ extern "C" int matcha_neg_sample_long(const void* set, const int64_t* set_edges,
                      (const int32_t*)set, set_edges, n_set_edges, L_set, pos, P, L, neg_num, min_dis, node2chrom, n_nodes,
                      chrom_range, n_chrom, seed, neg, status);
   MATCHA_CHECK_LAUNCH("neg_sample_long_kernel");
+  return MATCHA_OK;
+}
+
+extern "C" int matcha_outlier_plant(const void* set, const int64_t* set_edges, int64_t n_set_edges, int32_t L_set,
+                                    const void* pair_set, const int64_t* pair_edges, int64_t n_pair_edges, int32_t L_pair,
+                                    const int64_t* pos, int64_t P, int32_t L, int32_t draws, int32_t cycle, int32_t min_dis,
+                                    const int32_t* node2chrom, int32_t n_nodes, const int32_t* chrom_range, int32_t n_chrom,
+                                    const uint64_t* seed, int64_t n0, int64_t* out, int32_t* planted, int32_t* status, matcha_stream_t stream) {
+  MATCHA_CHECK_ARG(pos && out && planted && node2chrom && chrom_range && seed, "matcha_outlier_plant: null pointer");
+  MATCHA_CHECK_ARG(((uintptr_t)chrom_range) % 8 == 0, "matcha_outlier_plant: chrom_range must be 8-byte aligned (the kernel reads [lo, hi] pairs as one int2)");
+  MATCHA_CHECK_ARG(n_nodes >= 1 && n_chrom >= 1, "matcha_outlier_plant: n_nodes=%d n_chrom=%d", n_nodes, n_chrom);
+  MATCHA_CHECK_ARG(n_set_edges == 0 || (set && set_edges), "matcha_outlier_plant: non-empty set without buffers");
+  MATCHA_CHECK_ARG(n_pair_edges == 0 || (pair_set && pair_edges), "matcha_outlier_plant: non-empty pair set without buffers");
+  MATCHA_CHECK_ARG(L >= 1 && L <= MATCHA_MAX_LONG_L && draws >= 1, "matcha_outlier_plant: L=%d draws=%d", L, draws);
+  MATCHA_CHECK_ARG(L_set >= 1 && L_set <= MATCHA_MAX_LONG_L, "matcha_outlier_plant: L_set=%d", L_set);
+  MATCHA_CHECK_ARG(n_set_edges >= 0 && n_set_edges < (1ll << 31), "matcha_outlier_plant: n_set_edges=%lld", (long long)n_set_edges);
+  MATCHA_CHECK_ARG(n_pair_edges >= 0 && n_pair_edges < (1ll << 31), "matcha_outlier_plant: n_pair_edges=%lld", (long long)n_pair_edges);
+  MATCHA_CHECK_ARG(n_pair_edges == 0 || (L_pair >= 2 && L_pair <= MATCHA_MAX_LONG_L), "matcha_outlier_plant: L_pair=%d (a pair set holds rows of two nodes)", L_pair);
+  MATCHA_CHECK_ARG(n0 >= 0, "matcha_outlier_plant: n0=%lld must not be negative", (long long)n0);
+  if (P <= 0) return MATCHA_OK;
+  // the row's global index is the random stream's 32-bit hi counter, and a block owns eight rows
+  MATCHA_CHECK_ARG(P <= ((1ll << 31) - 1) / draws, "matcha_outlier_plant: P=%lld x draws=%d rows", (long long)P, draws);
+  MATCHA_CHECK_ARG(n0 <= (1ll << 31) - 1 - P * draws, "matcha_outlier_plant: n0=%lld + P*draws=%lld rows reach 2^31", (long long)n0, (long long)(P * draws));
+  hipLaunchKernelGGL(outlier_plant_kernel, dim3((unsigned)cdiv(P * draws, 256 / kGroup)), dim3(256), 0, (hipStream_t)stream,
+                     (const int32_t*)set, set_edges, n_set_edges, L_set, (const int32_t*)pair_set, pair_edges, n_pair_edges, L_pair, pos, P, L,
+                     draws, cycle != 0 ? 1 : 0, min_dis, node2chrom, n_nodes, chrom_range, n_chrom, seed, n0, out, planted, status);
+  MATCHA_CHECK_LAUNCH("outlier_plant_kernel");
   return MATCHA_OK;
 }

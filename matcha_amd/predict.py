@@ -20,6 +20,7 @@ CLI:  python -m matcha_amd.predict multiway -i interactions.txt -o output.txt
       python -m matcha_amd.predict regions --part 0:1 --part 5:1 --part 10:1:20-60 --top 1000 [--per-leading] [--map R C] [--exclude-known] -o regions.tsv
       python -m matcha_amd.predict kmap --chrom 0 --k 3 [--start-bin A --end-bin B] [--threshold 0.5] [--exclude-known] -o map.npz
       python -m matcha_amd.predict attention -i interactions.txt -o attn.npz [--per-head]
+      python -m matcha_amd.predict outliers -i interactions.txt -o outliers.tsv [--lowest 3] [--scores scores.npz]
 (all read ./config.JSON like the reference: temp_dir, resolution, chrom_list, min_distance).
 
 * ``kway`` -- the de novo sweep of matcha_amd/sweep.py: every candidate of size k in one chromosome (or a window of its bins)
@@ -50,6 +51,9 @@ CLI:  python -m matcha_amd.predict multiway -i interactions.txt -o output.txt
   number at or above ``--threshold`` -- written as one .npz of [n, n] matrices.
 * ``attention`` -- ``attention_maps``: the lines of ``multiway``'s input (2 to 32 loci each), scored in the same chunks, and per line the
   k x k block of attention probabilities among its loci (``Classifier.get_embedding``), mean over the heads, as one .npz.
+* ``outliers`` -- ``locus_scores``: the lines of ``multiway``'s input, scored in the same chunks; per line the
+  probability, the size and the ``--lowest`` least supported loci as ``chrom:start`` with their scores (``Classifier.locus_scores``),
+  ``--scores`` every locus's score as one .npz, ragged by line.
 """
 from __future__ import annotations
 
@@ -163,6 +167,61 @@ def attention_maps(model, samples, batch_size: int = CHUNK_ROWS, per_head: bool 
     if per_head:
         out["attn_heads"] = cat(heads, np.float32)
     return out
+
+
+def locus_scores(model, samples, batch_size: int = CHUNK_ROWS, lowest: int = 3) -> Dict[str, np.ndarray]:
+    """Which locus of each hyperedge the model supports least: ``Classifier.locus_scores`` on a list / array of hyperedges of 2 .. 32 nodes
+    in ``predict``'s chunks -- file order, ``batch_size`` rows, each chunk zero-padded to ITS longest row -- so ``logit`` is ``predict``'s
+    column row for row (the same bits where the chunk is wider than 8 and ``model(x)`` runs the same chain; to fp32 rounding where
+    ``model(x)`` takes its short-row kernels).  Returns numpy arrays, ragged by hyperedge like ``attention_maps``'s:
+
+      logit   float32 [n]      sizes  int64 [n]  k_i      offsets  int64 [n + 1]  row i's scores are scores[offsets[i]:offsets[i + 1]]
+      scores  float32          the k_i per-locus scores of row i, in the row's node order
+      lowest  int64 [n, lowest]  positions (0 .. k_i - 1) of the row's least supported loci, ascending by score; -1 behind the k_i-th
+
+    A row of more than 32 nodes raises ValueError naming it, before anything is scored."""
+    U.check_row_sizes(samples, _lib.MAX_LONG_L)
+    lowest = int(lowest)
+    logit, sizes, scores, low = [], [], [], []
+    if len(samples):
+        model.eval()
+        dev = model.layer_norm1.weight.device
+        with torch.no_grad():
+            for j in range(0, len(samples), batch_size):
+                x = U.pad_rows(samples[j:j + batch_size]).to(dev)
+                if x.shape[1] < 2:
+                    x = torch.nn.functional.pad(x, (0, 2 - x.shape[1]))
+                res = model.locus_scores(x, lowest=lowest)
+                real = x != 0
+                logit.append(res.logits.view(-1).cpu().numpy())
+                sizes.append(real.sum(1).cpu().numpy().astype(np.int64))
+                scores.append(res.scores[real].cpu().numpy())
+                if lowest:
+                    # slot -> position among the row's real loci (the same thing for the zero-padded rows of pad_rows; kept general)
+                    rank = torch.cumsum(real.long(), 1) - 1
+                    o = res.order
+                    low.append(torch.where(o >= 0, rank.gather(1, o.clamp(min=0)), o).cpu().numpy())
+    cat = lambda parts, dt: np.concatenate(parts) if parts else np.zeros(0, dtype=dt)
+    out = {"logit": cat(logit, np.float32), "sizes": cat(sizes, np.int64), "scores": cat(scores, np.float32)}
+    out["offsets"] = np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum(out["sizes"])])
+    out["lowest"] = np.concatenate(low) if low else np.zeros((0, lowest), dtype=np.int64)
+    return out
+
+
+def _outliers(args, config, temp_dir, model):
+    bin2node = np.load(os.path.join(temp_dir, "bin2node.npy"), allow_pickle=True).item()
+    node2bin = np.load(os.path.join(temp_dir, "node2bin.npy"), allow_pickle=True).item()
+    samples = parse_file(args.file, bin2node, config["chrom_list"], config["resolution"], max_size=_lib.MAX_LONG_L)
+    out = locus_scores(model, samples, lowest=args.lowest)
+    proba = torch.sigmoid(torch.from_numpy(out["logit"])).numpy()
+    with open(args.output, "w") as f:
+        for i, row in enumerate(samples):
+            sc = out["scores"][out["offsets"][i]:out["offsets"][i + 1]]
+            items = ["%s\t%r" % (node2bin[int(row[p])], float(sc[p])) for p in out["lowest"][i] if p >= 0]
+            f.write("\t".join(["%.18e" % proba[i], str(len(row))] + items) + "\n")
+    if args.scores:
+        np.savez(args.scores, sizes=out["sizes"], offsets=out["offsets"], scores=out["scores"])
+    print("%d interactions -> %s" % (len(samples), args.output))
 
 
 def generate_pair_wise(chrom_range, chrom_id: int, min_dis: int, device=None) -> torch.Tensor:
@@ -733,6 +792,12 @@ def main(argv=None):
     g.add_argument("-o", "--output", type=str, default="./attn.npz")
     g.add_argument("--per-head", action="store_true", help="also write the eight heads' blocks (attn_heads)")
     g.add_argument("--config", type=str, default="./config.JSON")
+    n = sub.add_parser("outliers", help="outlier identification: per interaction of a text file, its probability and its least supported loci")
+    n.add_argument("-i", "--file", type=str, required=True)
+    n.add_argument("-o", "--output", type=str, default="./outliers.tsv")
+    n.add_argument("--lowest", type=int, default=3, help="loci to list per interaction, least supported first (0 .. 32)")
+    n.add_argument("--scores", type=str, default=None, help="also write every locus's score to this .npz (sizes, offsets, scores)")
+    n.add_argument("--config", type=str, default="./config.JSON")
     d.add_argument("--config", type=str, default="./config.JSON")
     for q in (a, b, c, e):
         q.add_argument("--config", type=str, default="./config.JSON")
@@ -752,6 +817,8 @@ def main(argv=None):
         return _regions(args, config, temp_dir, model)
     if args.cmd == "kmap":
         return _kmap(args, config, temp_dir, model)
+    if args.cmd == "outliers":
+        return _outliers(args, config, temp_dir, model)
     if args.cmd == "attention":
         bin2node = np.load(os.path.join(temp_dir, "bin2node.npy"), allow_pickle=True).item()
         samples = parse_file(args.file, bin2node, config["chrom_list"], config["resolution"], max_size=_lib.MAX_LONG_L)
