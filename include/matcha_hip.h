@@ -902,6 +902,50 @@ int matcha_pairmap_update(void* state, size_t bytes, int64_t lo_r, int32_t n_r, 
 int matcha_pairmap_read(const void* state, size_t bytes, int64_t lo_r, int32_t n_r, int64_t lo_c, int32_t n_c, int32_t planes,
                         float vmax, float threshold, int32_t plane, void* out, int64_t* counters_out, matcha_stream_t stream);
 
+/* ---- distance-matched expectation of k-way sweeps (csrc/expected.hip) ----
+ * A candidate of size k is a strictly ascending k-tuple of positive node ids, zero-padded to the row width L (2 <= k <= L <= 8).  Its gaps
+ * g_j = x[j+1] - x[j] fall into classes: class(g) = the number of edges <= g, `edges` a strictly ascending host array of 0 .. 15 positive
+ * int64 (copied into the kernel arguments: the library keeps nothing between calls), G = n_edges + 1 classes.  The stratum is
+ * s = ((c_0 G + c_1) G + ...) + c_{k-2} in [0, G^(k-1)), G^(k-1) <= 2^20; gap tuples stay ordered.  A row whose leading non-zero run is not
+ * exactly k ids, is not strictly ascending, starts below 1 or holds a non-zero id behind a zero has stratum -1.
+ * Statistics (a bit mask of planes, int64 [G^(k-1)] each; only the planes asked for take memory): an accepted row -- skip[i] == 0, stratum
+ * >= 0, 0 <= v <= vmax (-0.0 counts as 0; everything else that is not skipped is counted in n_rejected) -- adds
+ *   MATCHA_GAP_COUNT  1,      MATCHA_GAP_SUM  rint((double)v 2^shift),      MATCHA_GAP_SUMSQ  rint((double)v (double)v 2^shift)
+ * to its stratum with integer adds, so every plane is bitwise independent of the order of the rows and of how the stream is cut.
+ * MATCHA_GAP_DIRECT in the mask of an update (ignored elsewhere) turns the block-level accumulation in LDS off: an A/B switch, same planes.
+ * State blob (caller-owned, 8-byte aligned, exactly matcha_gap_stats_bytes bytes): a 256-byte header {int64 n_rows, int64 n_rejected, zero
+ * padding}, then the planes present in the order COUNT, SUM, SUMSQ, each padded to a multiple of 256 bytes.  All calls are asynchronous on
+ * the caller's stream; nothing is allocated or read back.
+ * matcha_gap_strata_count  host only: G^(k-1), or -1 for k outside [2, 8], n_edges outside [0, 15] or more than 2^20 strata.
+ * matcha_gap_strata_ids    stratum_out device int32 [n].
+ * matcha_gap_stats_bytes   host only; 0 for invalid arguments.
+ * matcha_gap_stats_init    zeroes the state (a kernel, no memset).
+ * matcha_gap_stats_update  x device int64 [n, L], value device float32 [n], skip device int32 [n] or null; n = 0 launches nothing.  16 <= shift
+ *     <= 32, 0 < vmax <= 2^20, and with SUMSQ vmax^2 2^shift <= 2^62 (one row's term must fit).
+ * matcha_gap_stats_read    the raw planes to device int64 [G^(k-1)] arrays (null = not wanted; a non-null output needs its plane in the mask),
+ *     counters_out optional device int64 [2] = {n_rows, n_rejected}.
+ * matcha_gap_enrich        out[i] = (score[i] - offset[s]) * scale[s], two separately rounded float32 operations (no FMA), NaN for stratum -1;
+ *     offset, scale device float32 [G^(k-1)]; stratum_out optional device int32 [n].  With score, offset, scale and out all null only the
+ *     strata are written.
+ * All refuse with MATCHA_EINVAL, before any device call: k outside [2, 8], L < k or L > 8, more than 15 edges, edges not positive and strictly
+ * ascending, more than 2^20 strata, an empty or unknown plane mask, shift or vmax out of range, a `bytes` that differs from the sizing call,
+ * null pointers, n < 0. */
+#define MATCHA_GAP_COUNT 1
+#define MATCHA_GAP_SUM 2
+#define MATCHA_GAP_SUMSQ 4
+#define MATCHA_GAP_DIRECT 8
+int64_t matcha_gap_strata_count(int32_t k, int32_t n_edges);
+int matcha_gap_strata_ids(int32_t k, const int64_t* edges, int32_t n_edges, const int64_t* x, int64_t n, int32_t L, int32_t* stratum_out,
+                          matcha_stream_t stream);
+size_t matcha_gap_stats_bytes(int32_t k, int32_t n_edges, int32_t planes);
+int matcha_gap_stats_init(void* state, size_t bytes, int32_t k, int32_t n_edges, int32_t planes, matcha_stream_t stream);
+int matcha_gap_stats_update(void* state, size_t bytes, int32_t k, const int64_t* edges, int32_t n_edges, int32_t planes, int32_t shift, float vmax,
+                            const int64_t* x, int32_t L, const float* value, const int32_t* skip, int64_t n, matcha_stream_t stream);
+int matcha_gap_stats_read(const void* state, size_t bytes, int32_t k, int32_t n_edges, int32_t planes, int64_t* count_out, int64_t* sum_out,
+                          int64_t* sumsq_out, int64_t* counters_out, matcha_stream_t stream);
+int matcha_gap_enrich(int32_t k, const int64_t* edges, int32_t n_edges, const int64_t* x, int64_t n, int32_t L, const float* score,
+                      const float* offset, const float* scale, int32_t* stratum_out, float* out, matcha_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -175,7 +175,19 @@ SIGNATURES = {
     "matcha_pairmap_init": (C.c_int, [_fp, _SZ, _I64, _I32, _I64, _I32, _I32, _F, _F, _fp]),
     "matcha_pairmap_update": (C.c_int, [_fp, _SZ, _I64, _I32, _I64, _I32, _I32, _F, _F, _fp, _fp, _fp, _I64, _I32, _fp]),
     "matcha_pairmap_read": (C.c_int, [_fp, _SZ, _I64, _I32, _I64, _I32, _I32, _F, _F, _I32, _fp, _fp, _fp]),
+    "matcha_gap_strata_count": (_I64, [_I32, _I32]),
+    "matcha_gap_strata_ids": (C.c_int, [_I32, _fp, _I32, _fp, _I64, _I32, _fp, _fp]),
+    "matcha_gap_stats_bytes": (_SZ, [_I32, _I32, _I32]),
+    "matcha_gap_stats_init": (C.c_int, [_fp, _SZ, _I32, _I32, _I32, _fp]),
+    "matcha_gap_stats_update": (C.c_int, [_fp, _SZ, _I32, _fp, _I32, _I32, _I32, _F, _fp, _I32, _fp, _fp, _I64, _fp]),
+    "matcha_gap_stats_read": (C.c_int, [_fp, _SZ, _I32, _I32, _I32, _fp, _fp, _fp, _fp, _fp]),
+    "matcha_gap_enrich": (C.c_int, [_I32, _fp, _I32, _fp, _I64, _I32, _fp, _fp, _fp, _fp, _fp, _fp]),
 }
+
+GAP_COUNT, GAP_SUM, GAP_SUMSQ, GAP_DIRECT = 1, 2, 4, 8      # MATCHA_GAP_* of include/matcha_hip.h
+GAP_PLANES = {"count": GAP_COUNT, "sum": GAP_SUM, "sumsq": GAP_SUMSQ}
+GAP_ALL = 7
+GAP_MAX_EDGES, GAP_MAX_STRATA = 15, 1 << 20
 
 PAIRMAP_SUM, PAIRMAP_COUNT, PAIRMAP_COUNT_GE, PAIRMAP_MAX = 1, 2, 4, 8      # MATCHA_PAIRMAP_* of include/matcha_hip.h
 PAIRMAP_PLANES = {"sum": PAIRMAP_SUM, "count": PAIRMAP_COUNT, "count_ge": PAIRMAP_COUNT_GE, "max": PAIRMAP_MAX}

@@ -314,7 +314,10 @@ def _kway(args, config, temp_dir, model):
     if args.exclude_known:
         known = np.load(os.path.join(temp_dir, "all_%d_counter.npy" % args.k)).astype(np.int64).reshape(-1, args.k)
         exclude = HyperedgeSet(torch.from_numpy(known).to(dev))
-    out = SW.kway_sweep(model, lo, hi, args.k, int(config["min_distance"]) + 1, args.top, chunk_rows=args.chunk_rows, width=args.width,
+    min_gap = int(config["min_distance"]) + 1
+    if args.enrich is not None:
+        return _kway_enriched(args, model, chrom_range, node2bin, lo, hi, min_gap, exclude)
+    out = SW.kway_sweep(model, lo, hi, args.k, min_gap, args.top, chunk_rows=args.chunk_rows, width=args.width,
                         exclude=exclude, task_mode=args.task_mode)
     rows, proba = out["rows"].cpu().numpy(), out["proba"].cpu().numpy()
     with open(args.output, "w") as f:
@@ -322,6 +325,61 @@ def _kway(args, config, temp_dir, model):
             f.write("\t".join([node2bin[int(v)] for v in r[:args.k]] + [repr(float(p))]) + "\n")
     np.savez(os.path.splitext(args.output)[0] + ".npz", rows=rows, logit=out["logit"].cpu().numpy(), proba=proba, rank=out["rank"].cpu().numpy())
     print("%d candidates (%d known, skipped) -> %d in %s" % (out["n_candidates"], out["n_excluded"], len(rows), args.output))
+
+
+def parse_gap_edges(text: Optional[str]) -> Optional[Tuple[int, ...]]:
+    """--gap-edges: a comma-separated, strictly ascending list of positive gaps ('' = no edges, one stratum); None = the default."""
+    if text is None:
+        return None
+    try:
+        edges = tuple(int(t) for t in text.split(",") if t.strip() != "")
+    except ValueError:
+        raise ValueError("--gap-edges must be a comma-separated list of integers (got %r)" % text)
+    if any(e < 1 for e in edges) or any(b <= a for a, b in zip(edges, edges[1:])):
+        raise ValueError("--gap-edges must be positive and strictly ascending (got %r)" % text)
+    return edges
+
+
+def _cli_expected(args, model, chrom_range, lo, hi, min_gap):
+    """The expectation a --enrich run applies: --load-expected's file, or the expectation of every chromosome (--expected-chroms all), or
+    None -- the sweep's own region, which kway_enriched_sweep computes itself (and whose logits it then keeps)."""
+    from . import expected as EX
+    if args.load_expected is not None:
+        ex = EX.GapExpected.load(args.load_expected)
+        if ex.k != args.k or ex.task_mode != args.task_mode:
+            raise ValueError("%s holds the expectation of k=%d, task mode %s" % (args.load_expected, ex.k, ex.task_mode))
+        return ex
+    if args.expected_chroms == "all":
+        regions = [(int(a), int(b)) for a, b in np.asarray(chrom_range)[:, :2]]
+        return EX.kway_expected(model, regions, args.k, min_gap, edges=parse_gap_edges(args.gap_edges), width=args.width, chunk_rows=args.chunk_rows,
+                                task_mode=args.task_mode, vmax=args.value_max)
+    return None
+
+
+def gap_ranges(decoded) -> str:
+    """A stratum's gap ranges for the TSV: '1', '2-3', '8+' per gap, comma-separated."""
+    return ",".join("%d+" % a if b is None else ("%d" % a if a == b else "%d-%d" % (a, b)) for a, b in decoded)
+
+
+def _kway_enriched(args, model, chrom_range, node2bin, lo, hi, min_gap, exclude):
+    from . import expected as EX
+    ex = _cli_expected(args, model, chrom_range, lo, hi, min_gap)
+    out = EX.kway_enriched_sweep(model, lo, hi, args.k, min_gap, args.top, expected=ex, mode=args.enrich, min_count=args.min_count,
+                                 edges=parse_gap_edges(args.gap_edges), width=args.width, exclude=exclude, chunk_rows=args.chunk_rows,
+                                 task_mode=args.task_mode, vmax=args.value_max)
+    ex = out["expected_table"]
+    if args.save_expected is not None:
+        ex.save(args.save_expected)
+    rows, proba, enrich = out["rows"].cpu().numpy(), out["proba"].cpu().numpy(), out["enrich"].cpu().numpy()
+    stratum, mean = out["stratum"].cpu().numpy(), out["expected"].cpu().numpy()
+    with open(args.output, "w") as f:
+        for r, p, e, s, m in zip(rows, proba, enrich, stratum, mean):
+            f.write("\t".join([node2bin[int(v)] for v in r[:args.k]] + [repr(float(p)), repr(float(e)), repr(float(m)), gap_ranges(ex.strata.decode(int(s)))])
+                    + "\n")
+    np.savez(os.path.splitext(args.output)[0] + ".npz", rows=rows, logit=out["logit"].cpu().numpy(), proba=proba, rank=out["rank"].cpu().numpy(),
+             enrich=enrich, stratum=stratum, expected=mean, gap_edges=np.asarray(ex.edges, dtype=np.int64))
+    print("%d candidates (%d known, skipped; %d in undersampled strata) -> %d by %s enrichment in %s"
+          % (out["n_candidates"], out["n_excluded"], out["n_undersampled"], len(rows), args.enrich, args.output))
 
 
 def _kmap(args, config, temp_dir, model):
@@ -339,10 +397,22 @@ def _kmap(args, config, temp_dir, model):
         known = np.load(os.path.join(temp_dir, "all_%d_counter.npy" % args.k)).astype(np.int64).reshape(-1, args.k)
         exclude = HyperedgeSet(torch.from_numpy(known).to(dev))
     min_gap = int(config["min_distance"]) + 1
+    extra = {}
+    if args.enrich is not None:                                          # the observed-over-expected map
+        from . import expected as EX
+        ex = _cli_expected(args, model, chrom_range, lo, hi, min_gap)
+        if ex is None:
+            ex = EX.kway_expected(model, [(lo, hi)], args.k, min_gap, edges=parse_gap_edges(args.gap_edges), width=args.width,
+                                  chunk_rows=args.chunk_rows, task_mode=args.task_mode, vmax=args.value_max)
+        if args.save_expected is not None:
+            ex.save(args.save_expected)
+        extra = dict(expected=ex, mode=args.enrich, min_count=args.min_count)
     out = SW.kway_map(model, lo, hi, args.k, min_gap, chunk_rows=args.chunk_rows, width=args.width, exclude=exclude, task_mode=args.task_mode,
-                      threshold=args.threshold, value_max=args.value_max)
+                      threshold=args.threshold, value_max=None if args.enrich is not None else args.value_max, **extra)      # a ratio's cap is kway_map's default, 1024
+    if args.enrich is not None:
+        extra = dict(gap_edges=np.asarray(ex.edges, dtype=np.int64), expected_mean=ex.mean, expected_count=ex.count, min_count=np.int64(args.min_count))
     np.savez(args.output, **{name: out[name].cpu().numpy() for name in ("sum", "mean", "max", "count", "count_ge")}, lo=np.int64(lo),
-             n=np.int64(hi - lo), k=np.int64(args.k), min_gap=np.int64(min_gap), threshold=np.float32(args.threshold))
+             n=np.int64(hi - lo), k=np.int64(args.k), min_gap=np.int64(min_gap), threshold=np.float32(args.threshold), **extra)
     print("%d candidates (%d known, skipped; %d rejected) -> %d x %d map in %s"
           % (out["n_candidates"], out["n_excluded"], out["n_rejected"], hi - lo, hi - lo, args.output))
 
@@ -703,6 +773,9 @@ def main(argv=None):
     c.add_argument("--chunk-rows", type=int, default=1 << 20)
     c.add_argument("--task-mode", choices=["class", "regress"], default="class", help="the model's training objective: sigmoid or softplus outputs")
     c.add_argument("-o", "--output", type=str, default="./kway.tsv")
+    c.add_argument("--enrich", choices=["logodds", "ratio", "z"], default=None,
+                   help="rank by enrichment over the distance-matched expectation instead of by probability; adds the columns enrich, expected and gap ranges")
+    c.add_argument("--value-max", type=float, default=None, help="--enrich with task-mode regress: the largest value the expectation accepts (<= 2^20)")
     d = sub.add_parser("anchored", help="anchored sweep: for every anchor the best --top candidates of size --k that contain it")
     d.add_argument("--chrom", type=int, required=True, help="the partner region: index into config chrom_list")
     d.add_argument("--k", type=int, required=True, help="candidate size, 2 .. 8 (anchor loci included)")
@@ -785,8 +858,16 @@ def main(argv=None):
     e.add_argument("--width", type=int, default=None, help="zero-pad rows to this width (default k): a logit depends on its batch's width")
     e.add_argument("--chunk-rows", type=int, default=1 << 20)
     e.add_argument("--task-mode", choices=["class", "regress"], default="class", help="the model's training objective: sigmoid or softplus outputs")
-    e.add_argument("--value-max", type=float, default=None, help="task-mode regress: the largest value a candidate may contribute (<= 2^20)")
+    e.add_argument("--value-max", type=float, default=None, help="task-mode regress: the largest value a candidate may contribute (<= 2^20); with --enrich: the largest the expectation accepts (a ratio's cap is 1024)")
     e.add_argument("-o", "--output", type=str, default="./kmap.npz")
+    e.add_argument("--enrich", choices=["ratio"], default=None, help="the observed-over-expected map: every candidate's value divided by the mean of its gap stratum")
+    for q in (c, e):
+        q.add_argument("--gap-edges", type=str, default=None, help="--enrich: the gap classes' edges, comma-separated and ascending (default: powers of two)")
+        q.add_argument("--min-count", type=int, default=30, help="--enrich: strata with fewer candidates have no expectation; their candidates drop out")
+        q.add_argument("--expected-chroms", choices=["all", "same"], default="same",
+                       help="--enrich: take the expectation over every chromosome (the Hi-C convention) or over the swept window only")
+        q.add_argument("--save-expected", type=str, default=None, help="--enrich: write the expectation to this .npz")
+        q.add_argument("--load-expected", type=str, default=None, help="--enrich: apply the expectation of this .npz instead of computing one")
     g = sub.add_parser("attention", help="attention maps: per interaction of a text file, the head-mean attention among its loci")
     g.add_argument("-i", "--file", type=str, required=True)
     g.add_argument("-o", "--output", type=str, default="./attn.npz")

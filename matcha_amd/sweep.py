@@ -558,7 +558,8 @@ def _empty_map(n_r: int, n_c: int, mask: int, dev) -> dict:
 
 def kway_map(model, lo: int, hi: int, k: int, min_gap: int, chunk_rows: int = 1 << 20, width: Optional[int] = None, exclude=None,
              task_mode: str = "class", threshold: float = 0.5, planes="all", value_max: Optional[float] = None,
-             row_window: Optional[Tuple[int, int]] = None, col_window: Optional[Tuple[int, int]] = None) -> dict:
+             row_window: Optional[Tuple[int, int]] = None, col_window: Optional[Tuple[int, int]] = None, expected=None, mode: str = "ratio",
+             min_count: int = 30) -> dict:
     """Score every candidate of size k in the region [lo, hi) (kway_sweep's candidates, in its order, through its loop) and project
     the probabilities onto pairs of bins: for every pair, the summed probability of the candidates that contain it ('sum', float64),
     their number ('count'), how many reach ``threshold`` ('count_ge'), the best of them ('max', -inf where there is none) and
@@ -572,10 +573,22 @@ def kway_map(model, lo: int, hi: int, k: int, min_gap: int, chunk_rows: int = 1 
     2^31 is refused before anything is launched.  ``exclude``, ``width`` and ``chunk_rows`` as in kway_sweep; the planes do not depend
     on ``chunk_rows``, bit for bit.
 
+    ``expected`` (a GapExpected of matcha_amd/expected.py) gives the observed-over-expected map: a candidate's value is
+    its activated value divided by the mean of its gap stratum (``mode`` 'ratio', the only one a map of non-negative values takes;
+    ``min_count`` as in GapExpected.table), ``value_max`` defaults to 1024, and candidates of undersampled strata (their ratio is NaN)
+    land in ``n_rejected`` with the ratios above ``value_max``.  Without ``expected`` nothing changes, bit for bit.
+
     Returns the planes (device tensors) and the integers ``n_candidates``, ``n_excluded`` and ``n_rejected``.  Nothing synchronises
     until the end, where the node-id check of the whole sweep is raised once (IndexError)."""
     if task_mode not in ("class", "regress"):
         raise ValueError("task_mode must be 'class' or 'regress'")
+    if expected is not None:
+        if mode != "ratio":
+            raise ValueError("kway_map accumulates non-negative values: with expected only mode 'ratio' is supported")
+        if expected.k != int(k):
+            raise ValueError(f"the expected table is for k={expected.k}, the map for k={k}")
+        if value_max is None:
+            value_max = 1024.0
     lo, hi, k, min_gap, chunk_rows = int(lo), int(hi), int(k), int(min_gap), int(chunk_rows)
     n = hi - lo
     width = int(k if width is None else width)
@@ -588,7 +601,7 @@ def kway_map(model, lo: int, hi: int, k: int, min_gap: int, chunk_rows: int = 1 
             raise ValueError("task_mode 'regress' needs value_max: the largest value a candidate may contribute")
         vmax, act = float(value_max), torch.nn.functional.softplus
     else:
-        vmax, act = 1.0, torch.sigmoid
+        vmax, act = (1.0 if expected is None else float(value_max)), torch.sigmoid
     if not 0.0 < vmax <= float(1 << 20):
         raise ValueError("value_max must be in (0, 2^20]")
     mask = _plane_mask(planes)
@@ -618,10 +631,14 @@ def kway_map(model, lo: int, hi: int, k: int, min_gap: int, chunk_rows: int = 1 
     pm = PairMap(rows, cols, mask, vmax=vmax, threshold=threshold, device=dev)
     buf = torch.empty(chunk_rows * width, dtype=torch.long, device=dev)
     n_exc = torch.zeros((), dtype=torch.long, device=dev)
+    if expected is not None:
+        offset, scale = expected.table(mode, min_count, device=dev)
     with torch.no_grad(), model.deferred_id_check(), _lib.option("disable_small_batch"):      # as kway_sweep: one forward route
         for r0 in range(0, total, chunk_rows):
             x = kway_rows(lo, n, k, min_gap, rank0=r0, count=min(chunk_rows, total - r0), width=width, out=buf)
             value = act(model(x).reshape(-1))
+            if expected is not None:
+                value = expected.strata.enrich(x, value, offset, scale)
             skip = None
             if exclude is not None:
                 skip = exclude.contains(x)
