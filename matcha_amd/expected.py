@@ -166,14 +166,9 @@ class GapStats:
         is counted as rejected.  Enqueued on the current stream; nothing is read back."""
         lib = _lib.load()
         x = self.strata._rows(x)
-        value = value.reshape(-1)
-        if x.device != self.state.device or value.dtype != torch.float32 or value.device != x.device or value.numel() != x.shape[0]:
+        value, skip = SW._scores_and_skip(value, skip, self.state.device, "GapStats")
+        if x.device != self.state.device or value.numel() != x.shape[0]:
             raise ValueError("x and value must be an int64 [n, L] and a float32 [n] tensor on the GapStats' device")
-        value = value.contiguous()
-        if skip is not None:
-            skip = skip.reshape(-1).to(device=value.device, dtype=torch.int32).contiguous()
-            if skip.numel() != value.numel():
-                raise ValueError("skip and value differ in length")
         st = self.strata
         with torch.cuda.device(self.device):
             _lib.check(lib.matcha_gap_stats_update(_lib.ptr(self.state), self.bytes, st.k, st.edges_ptr, len(st.edges), self._update_mask, self.shift,
@@ -289,40 +284,24 @@ class GapExpected:
         return torch.from_numpy(offset).to(device), torch.from_numpy(scale).to(device)
 
 
-def _activation(task_mode: str):
-    if task_mode not in ("class", "regress"):
-        raise ValueError("task_mode must be 'class' or 'regress'")
-    return torch.nn.functional.softplus if task_mode == "regress" else torch.sigmoid
-
-
 def _expected_pass(model, strata, regions, k, min_gap, width, chunk_rows, act, vmax, shift, keep=None) -> GapStats:
-    """kway_sweep's loop with GapStats.update in place of TopK.update, over every region into one table.  ``keep``: a float32 buffer
-    that receives the logits of the (single) region in rank order."""
+    """The loop of matcha_amd/sweep.py with kway_rows and GapStats.update, over every region into one table and through one row
+    buffer.  ``keep``: a float32 buffer that receives the logits of the (single) region in rank order."""
     dev = model.layer_norm1.weight.device
     stats = GapStats(strata, "all", vmax=vmax, shift=shift, device=dev)
     totals = [SW.kway_count(hi - lo, k, min_gap) if hi - lo >= 1 else 0 for lo, hi in regions]
     most = min(chunk_rows, max(totals + [0]))
     if most == 0:
         return stats
-    buf = torch.empty(most * width, dtype=torch.long, device=dev)
-    with torch.no_grad(), model.deferred_id_check(), _lib.option("disable_small_batch"):      # as kway_sweep: one forward route
+    buffers = SW._buffers(most, width, dev, flags=False)
+    with SW._pinned(model):
         for (lo, hi), total in zip(regions, totals):
-            for r0 in range(0, total, most):
-                x = SW.kway_rows(lo, hi - lo, k, min_gap, rank0=r0, count=min(most, total - r0), width=width, out=buf)
-                logits = model(x).reshape(-1)
+            rows = lambda r0, count, buf, _: SW.kway_rows(lo, hi - lo, k, min_gap, rank0=r0, count=count, width=width, out=buf)
+            for r0, x, logits, _, _ in SW._chunks(model, total, most, buffers, rows, None, {}):
                 if keep is not None:
                     keep[r0:r0 + logits.numel()] = logits
                 stats.update(x, act(logits))
     return stats
-
-
-def _check_sweep_args(k, width, chunk_rows):
-    width = int(k if width is None else width)
-    if not k <= width <= _lib.MAX_L:
-        raise ValueError(f"width must be in [k, {_lib.MAX_L}]")
-    if chunk_rows < 1:
-        raise ValueError("chunk_rows must be >= 1")
-    return width
 
 
 def kway_expected(model, regions, k: int, min_gap: int, edges: Optional[Sequence[int]] = None, width: Optional[int] = None,
@@ -331,12 +310,12 @@ def kway_expected(model, regions, k: int, min_gap: int, edges: Optional[Sequence
     score in each region is scored, and count, mean and variance of its value -- sigmoid(logit), or softplus(logit) for task_mode
     'regress', where ``vmax`` is required -- are accumulated per stratum of its gaps, all regions into ONE table: the stratum depends
     on gaps only, so a genome-wide expectation is the Hi-C convention.  Known hyperedges are part of the background and are included.
-    ``edges``: default_gap_edges of the longest region.  The loop is kway_sweep's (eval mode, no grad, the large-batch route pinned,
-    one reused rows buffer, nothing synchronises per chunk); the table does not depend on ``chunk_rows``, bit for bit."""
-    act = _activation(task_mode)
+    ``edges``: default_gap_edges of the longest region.  Eval mode and the loop of matcha_amd/sweep.py (no grad, the large-batch route
+    pinned, one reused rows buffer, nothing synchronises per chunk); the table does not depend on ``chunk_rows``, bit for bit."""
+    act = SW._activation(task_mode)
     k, min_gap, chunk_rows = int(k), int(min_gap), int(chunk_rows)
     regions = [(int(lo), int(hi)) for lo, hi in regions]
-    width = _check_sweep_args(k, width, chunk_rows)
+    width = SW._check_sweep_args(k, width, chunk_rows)
     if task_mode == "regress" and vmax is None:
         raise ValueError("task_mode 'regress' needs vmax: the largest value a candidate may contribute")
     vmax = 1.0 if vmax is None else float(vmax)
@@ -376,16 +355,14 @@ def kway_enriched_sweep(model, lo: int, hi: int, k: int, min_gap: int, top: int,
     Returns kway_sweep's dictionary (rows, logit, proba, rank, best ENRICHMENT first, n_candidates, n_excluded) plus ``enrich`` [K'],
     ``stratum`` int32 [K'], ``expected`` [K'] (the stratum's mean, float64), ``n_undersampled`` and ``expected_table`` (the
     GapExpected)."""
-    act = _activation(task_mode)
+    act = SW._activation(task_mode)
     if mode not in MODES:
         raise ValueError(f"mode must be one of {MODES}")
     if mode == "logodds" and task_mode == "regress":
         raise ValueError("mode 'logodds' needs probabilities: task_mode 'regress' takes 'ratio' or 'z'")
     lo, hi, k, min_gap, top, chunk_rows = int(lo), int(hi), int(k), int(min_gap), int(top), int(chunk_rows)
     n = hi - lo
-    width = _check_sweep_args(k, width, chunk_rows)
-    if top < 1:
-        raise ValueError("top must be >= 1")
+    width = SW._check_sweep_args(k, width, chunk_rows, top)
     model.eval()
     dev = model.layer_norm1.weight.device
     total = SW.kway_count(n, k, min_gap) if n >= 1 else 0
@@ -412,20 +389,18 @@ def kway_enriched_sweep(model, lo: int, hi: int, k: int, min_gap: int, top: int,
     under = torch.isnan(offset)
     chunk_rows = min(chunk_rows, total)
     sel = SW.TopK(min(top, total), chunk_rows, dev)
-    buf = torch.empty(chunk_rows * width, dtype=torch.long, device=dev)
-    n_exc = torch.zeros((), dtype=torch.long, device=dev)
-    n_under = torch.zeros((), dtype=torch.long, device=dev)
-    with torch.no_grad(), model.deferred_id_check(), _lib.option("disable_small_batch"):      # as kway_sweep: one forward route
-        for r0 in range(0, total, chunk_rows):
-            x = SW.kway_rows(lo, n, k, min_gap, rank0=r0, count=min(chunk_rows, total - r0), width=width, out=buf)
-            logits = cache[r0:r0 + x.shape[0]] if cache is not None else model(x).reshape(-1)
-            score = logits if mode == "logodds" else act(logits)
-            enr, s = strata.enrich(x, score, offset, scale, want_strata=True)
-            n_under += under[s.long()].sum()                             # a sweep's rows all have a stratum
-            skip = None
-            if exclude is not None:
-                skip = exclude.contains(x)
-                n_exc += skip.sum()
+    tally = SW._tally(dev, "n_excluded", "n_undersampled")
+    rows = lambda r0, count, buf, _: SW.kway_rows(lo, n, k, min_gap, rank0=r0, count=count, width=width, out=buf)
+
+    def enrichment(r0, x):                                               # what TopK ranks: from the cached logits, or the model's
+        logits = cache[r0:r0 + x.shape[0]] if cache is not None else model(x).reshape(-1)
+        enr, s = strata.enrich(x, logits if mode == "logodds" else act(logits), offset, scale, want_strata=True)
+        tally["n_undersampled"] += under[s.long()].sum()                 # a sweep's rows all have a stratum
+        return enr
+
+    with SW._pinned(model):                                              # held across the winners' forward below: the same route
+        for r0, _, enr, skip, _ in SW._chunks(model, total, chunk_rows, SW._buffers(chunk_rows, width, dev, flags=False), rows, exclude,
+                                              tally, enrichment):
             sel.update(enr, r0, skip)
         enrich, rank = sel.result()
         if rank.numel():
@@ -439,5 +414,5 @@ def kway_enriched_sweep(model, lo: int, hi: int, k: int, min_gap: int, top: int,
             logit = model(rows).reshape(-1) if rows.shape[0] else e
     stratum = strata.ids(rows) if rows.shape[0] else torch.empty(0, dtype=torch.int32, device=dev)
     mean = torch.from_numpy(expected.mean).to(dev)[stratum.long()]
-    return {"rows": rows, "logit": logit, "proba": act(logit), "rank": rank, "n_candidates": total, "n_excluded": int(n_exc.item()),
-            "enrich": enrich, "stratum": stratum, "expected": mean, "n_undersampled": int(n_under.item()), "expected_table": expected}
+    return {"rows": rows, "logit": logit, "proba": act(logit), "rank": rank, "n_candidates": total, **SW._counted(tally),
+            "enrich": enrich, "stratum": stratum, "expected": mean, "expected_table": expected}

@@ -20,9 +20,19 @@ made of a cluster's own loci, or the cluster with some of them taken out, and su
 chr6, two on chr11: each part contributes one candidate of its own region, the global rank is the mixed radix of the parts' ranks
 (``region_count``, ``region_unrank``, ``region_rows``), and the result is the best K overall, the best K per candidate of the leading part, or
 the pair map between two parts.
+
+The loop.  Every driver here and in matcha_amd/expected.py walks its candidates through ``_chunks`` under ``_pinned``.  ``_pinned(model)`` holds
+no_grad, the model's deferred node-id check (raised once, when the block ends: IndexError) and the large-batch forward route, so a logit does
+not depend on the cut.  ``_chunks`` cuts ``total`` ranks into chunks of min(chunk_rows, total); per chunk it has ``rows(g0, count, buf, fbuf)``
+fill the reused buffers (x, or x and a flag per row), scores x with model(x) (or ``forward(g0, x)``), and settles ``skip``: flag != 0, or a
+member of ``exclude``; None when the source has no flags and there is no ``exclude``, so the sink gets a null pointer.  ``n_invalid`` counts
+the flagged rows and ``n_excluded`` the members of ``exclude`` that are not flagged, as device scalars in ``tally``.  It yields (g0, x, logits,
+skip, flag) to the driver, whose body holds only its own sinks.  Nothing is copied to the host and nothing synchronises per chunk; an empty
+sweep returns before anything is allocated or launched.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import functools
 import math
@@ -49,17 +59,20 @@ def kway_count(n: int, k: int, min_gap: int) -> int:
     return total
 
 
-def kway_unrank(rank: int, lo: int, n: int, k: int, min_gap: int) -> Tuple[int, ...]:
-    """The candidate of one rank, in Python integers (no GPU): how a rank is decoded, and the checker of the kernel."""
-    total = kway_count(n, k, min_gap)
-    rank = int(rank)
-    if not 0 <= rank < total:
-        raise IndexError(f"rank {rank} outside [0, {total})")
-    m = n - (k - 1) * (min_gap - 1)
+def _free_count(n: int, f: int, min_gap: int) -> int:
+    """C_f: the gap-constrained subsets of size f >= 1 of a region of n nodes (f = 1: n)."""
+    m = n - (f - 1) * (min_gap - 1)
+    return math.comb(m, f) if m >= f else 0
+
+
+def _subset_unrank(rank: int, lo: int, n: int, f: int, min_gap: int) -> Tuple[int, ...]:
+    """The gap-constrained subset of size f >= 1 of [lo, lo + n) of lexicographic rank ``rank``, 0 <= rank < C_f, in Python integers:
+    the one decoder behind every *_unrank here."""
+    m = n - (f - 1) * (min_gap - 1)
     # the lexicographic rank of y is total - 1 - (colexicographic rank of the mirrored set z_j = m - 1 - y_j): read z off the
     # combinatorial number system of q, largest element first
-    row, q, upper = [], total - 1 - rank, m - 1
-    for j in range(k, 0, -1):
+    row, q, upper = [], _free_count(n, f, min_gap) - 1 - rank, m - 1
+    for j in range(f, 0, -1):
         a, b = j - 1, upper                            # the largest c in [j - 1, upper] with C(c, j) <= q
         while a < b:
             mid = (a + b + 1) // 2
@@ -68,13 +81,183 @@ def kway_unrank(rank: int, lo: int, n: int, k: int, min_gap: int) -> Tuple[int, 
             else:
                 b = mid - 1
         q -= math.comb(a, j)
-        row.append(int(lo) + (m - 1 - a) + (k - j) * (min_gap - 1))
+        row.append(lo + (m - 1 - a) + (f - j) * (min_gap - 1))
         upper = a - 1
     return tuple(row)
 
 
+def _checked_rank(rank: int, total: int) -> int:
+    rank = int(rank)
+    if not 0 <= rank < total:
+        raise IndexError(f"rank {rank} outside [0, {total})")
+    return rank
+
+
+def kway_unrank(rank: int, lo: int, n: int, k: int, min_gap: int) -> Tuple[int, ...]:
+    """The candidate of one rank, in Python integers (no GPU): how a rank is decoded, and the checker of the kernel."""
+    rank = _checked_rank(rank, kway_count(n, k, min_gap))
+    return _subset_unrank(rank, int(lo), int(n), int(k), int(min_gap))
+
+
 def _stream(dev):
     return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _activation(task_mode: str):
+    """What turns a logit into the value reported: sigmoid, softplus for task_mode 'regress' (as in pairwise_probabilities)."""
+    if task_mode not in ("class", "regress"):
+        raise ValueError("task_mode must be 'class' or 'regress'")
+    return torch.nn.functional.softplus if task_mode == "regress" else torch.sigmoid
+
+
+def _check_width(k: int, width: Optional[int]) -> int:
+    width = int(k if width is None else width)
+    if not k <= width <= _lib.MAX_L:
+        raise ValueError(f"width must be in [k, {_lib.MAX_L}]")
+    return width
+
+
+def _check_sweep_args(k: int, width: Optional[int], chunk_rows: int, top: int = 1) -> int:
+    """The width of a sweep of rows of up to 8 columns (default k), once ``top`` and ``chunk_rows`` are known to be usable."""
+    width = _check_width(k, width)
+    if top < 1 or chunk_rows < 1:
+        raise ValueError("top and chunk_rows must be >= 1")
+    return width
+
+
+def _rank_range(total: int, rank0: int, count: Optional[int], ranks: Optional[torch.Tensor]) -> int:
+    """How many rows a rows call makes: the length of the list ``ranks`` (``rank0`` is not looked at), or ``count`` (default: everything
+    from ``rank0`` on); a range that leaves [0, total) is an IndexError."""
+    if ranks is not None:
+        return int(ranks.numel())
+    rank0 = int(rank0)
+    count = total - rank0 if count is None else int(count)
+    if rank0 < 0 or count < 0 or rank0 + count > total:
+        raise IndexError(f"ranks [{rank0}, {rank0 + count}) outside [0, {total})")
+    return count
+
+
+def _row_buffers(count: int, width: int, device, out: Optional[torch.Tensor], flag_out: Optional[torch.Tensor], who: str, flags: bool = True):
+    """(x int64 [count, width], flag int32 [count]) on ``device``: fresh, or the leading elements of ``out`` / ``flag_out`` once they are
+    seen to be contiguous, of the right type, large enough and on that device.  ``flags=False``: no flag, (x, None)."""
+    if out is None:
+        x = torch.empty(count, width, dtype=torch.long, device=device)
+    else:
+        if out.dtype != torch.long or not out.is_contiguous() or out.numel() < count * width or out.device != device:
+            raise ValueError(f"{who}: out must be a contiguous int64 tensor of at least count * width elements on the rows' device")
+        x = out.view(-1)[:count * width].view(count, width)
+    if not flags:
+        return x, None
+    if flag_out is None:
+        flag = torch.empty(count, dtype=torch.int32, device=device)
+    else:
+        if flag_out.dtype != torch.int32 or not flag_out.is_contiguous() or flag_out.numel() < count or flag_out.device != x.device:
+            raise ValueError(f"{who}: flag_out must be a contiguous int32 tensor of at least count elements on out's device")
+        flag = flag_out.view(-1)[:count]
+    return x, flag
+
+
+def _scores_and_skip(scores: torch.Tensor, skip: Optional[torch.Tensor], device, who: str):
+    """What every sink's ``update`` takes: (float32 [n] contiguous on ``device``, int32 [n] or None)."""
+    scores = scores.reshape(-1)
+    if scores.dtype != torch.float32 or scores.device != device:
+        raise ValueError(f"scores (values) must be a float32 tensor on the {who}'s device")
+    scores = scores.contiguous()
+    if skip is not None:
+        skip = skip.reshape(-1).to(device=device, dtype=torch.int32).contiguous()
+        if skip.numel() != scores.numel():
+            raise ValueError("skip and scores (values) differ in length")
+    return scores, skip
+
+
+# ---- the loop (see the module's docstring) -------------------------------------------------------------------------------------------
+@contextlib.contextmanager
+def _pinned(model):
+    """no_grad, the node-id check of everything inside raised once at the end (IndexError), and ONE forward route.
+
+    The library picks its forward kernels by batch size (csrc/fused_fwd32.hip: up to two half tiles per compute unit go to the
+    small-batch kernels), and the two routes round differently (a few ulp of the logit).  A sweep pins the large-batch route, so a
+    candidate's logit does not depend on chunk_rows, on the size of the region or on the last chunk being short.  Beyond 8 columns
+    the long forward has one route: its kernels are chosen by the model's shape, never by the batch, and every token row is computed
+    by itself, so a logit does not depend on chunk_rows there either."""
+    with torch.no_grad(), model.deferred_id_check(), _lib.option("disable_small_batch"):
+        yield
+
+
+def _buffers(most_rows: int, width: int, device, flags: bool = True):
+    """The loop's reused (row buffer, flag buffer or None) for chunks of up to ``most_rows`` rows."""
+    return (torch.empty(most_rows * width, dtype=torch.long, device=device),
+            torch.empty(most_rows, dtype=torch.int32, device=device) if flags else None)
+
+
+def _tally(device, *names) -> dict:
+    """Zeroed device scalars, the loop's counters ('n_invalid', 'n_excluded'); ``_counted`` reads them back."""
+    return {name: torch.zeros((), dtype=torch.long, device=device) for name in names}
+
+
+def _counted(tally: dict) -> dict:
+    return {name: int(t.item()) for name, t in tally.items()}
+
+
+def _chunks(model, total: int, chunk_rows: int, buffers, rows, exclude, tally: dict, forward=None):
+    """Walk the ranks [0, total) in chunks of min(chunk_rows, total) and yield (g0, x, logits, skip, flag) per chunk.
+
+    ``rows(g0, count, buf, fbuf)`` makes the candidates of the ranks g0 .. g0 + count - 1 in ``buffers`` = (buf, fbuf) (``_buffers``; they
+    may serve several walks) and returns x, or (x, flag) with flag != 0 for an invalid candidate; ``flag`` is yielded as None for a source
+    without flags.  ``logits`` = model(x).reshape(-1), or ``forward(g0, x)`` where something else stands in for it (a cache of logits, a
+    map's values).  ``skip``: flagged or in ``exclude`` (an object with ``contains(x)``); None without flags and without ``exclude``.
+    ``tally['n_invalid']`` (where present) counts the flagged rows, ``tally['n_excluded']`` the members of ``exclude`` not flagged."""
+    chunk = min(chunk_rows, total)
+    buf, fbuf = buffers
+    n_inv = tally.get("n_invalid")
+    for g0 in range(0, total, chunk):
+        made = rows(g0, min(chunk, total - g0), buf, fbuf)
+        x, flag = made if isinstance(made, tuple) else (made, None)
+        logits = model(x).reshape(-1) if forward is None else forward(g0, x)
+        skip = None
+        if flag is not None:
+            skip = flag != 0
+            if n_inv is not None:
+                n_inv += skip.sum()
+        if exclude is not None:
+            known = exclude.contains(x)
+            if skip is None:
+                tally["n_excluded"] += known.sum()
+                skip = known
+            else:
+                tally["n_excluded"] += (known & ~skip).sum()
+                skip = skip | known
+        yield g0, x, logits, skip, flag
+
+
+def _long_chunk_rows(model, chunk_rows: Optional[int], width: int) -> int:
+    """The chunk of a sweep whose rows may be long.  None: 2^20 rows up to width 8 and min(2^20, 2^21 // width) beyond (about 3.1 KB of
+    workspace per token); an explicit value the long forward cannot take is a ValueError before anything is launched."""
+    if chunk_rows is None:
+        return 1 << 20 if width <= _lib.MAX_L else min(1 << 20, (1 << 21) // width)
+    chunk_rows = int(chunk_rows)
+    if chunk_rows < 1:
+        raise ValueError("chunk_rows must be >= 1")
+    if width > _lib.MAX_L:
+        rt = model._runtime()
+        if not chunk_rows < 1 << 31 or rt.lib.matcha_workspace_bytes_long(C.byref(rt.shape), chunk_rows, width) == 0:
+            raise ValueError(f"chunk_rows = {chunk_rows} rows of {width} columns are more than the long forward takes in one call")
+    return chunk_rows
+
+
+def _per_segment(grank: torch.Tensor, logit: torch.Tensor, seg_len: int, act):
+    """(rank within its segment, proba) [A, K] of a SegTopK's read: segment a holds the global ranks from a * seg_len on; where nothing
+    was kept the rank stays -1 and proba is 0."""
+    kept = grank >= 0
+    first = torch.arange(grank.shape[0], dtype=torch.long, device=grank.device).view(-1, 1) * seg_len
+    return torch.where(kept, grank - first, grank), torch.where(kept, act(logit), torch.zeros_like(logit))
+
+
+def _empty_segments(A: int, K: int, width: int, dev) -> dict:
+    """The per-segment keys with nothing kept: rank -1, everything else 0."""
+    e = torch.zeros(A, K, dtype=torch.float32, device=dev)
+    return {"rows": torch.zeros(A, K, width, dtype=torch.long, device=dev), "logit": e, "proba": e.clone(),
+            "rank": torch.full((A, K), -1, dtype=torch.long, device=dev), "count": torch.zeros(A, dtype=torch.long, device=dev)}
 
 
 def kway_rows(lo: int, n: int, k: int, min_gap: int, rank0: int = 0, count: Optional[int] = None, ranks: Optional[torch.Tensor] = None,
@@ -84,22 +267,12 @@ def kway_rows(lo: int, n: int, k: int, min_gap: int, rank0: int = 0, count: Opti
     count * width elements."""
     lib = _lib.load()
     total = kway_count(n, k, min_gap)
-    width = int(k if width is None else width)
-    if not k <= width <= _lib.MAX_L:
-        raise ValueError(f"width must be in [k, {_lib.MAX_L}]")
+    width = _check_width(k, width)
     if ranks is not None:
         ranks = ranks.to(device=device, dtype=torch.long).contiguous().view(-1)
-        count, device = int(ranks.numel()), ranks.device
-    else:
-        count = total - int(rank0) if count is None else int(count)
-        if rank0 < 0 or count < 0 or rank0 + count > total:
-            raise IndexError(f"ranks [{rank0}, {rank0 + count}) outside [0, {total})")
-    if out is None:
-        x = torch.empty(count, width, dtype=torch.long, device=device)
-    else:
-        if out.dtype != torch.long or not out.is_contiguous() or out.numel() < count * width:
-            raise ValueError("out must be a contiguous int64 tensor of at least count * width elements")
-        x = out.view(-1)[:count * width].view(count, width)
+        device = ranks.device
+    count = _rank_range(total, rank0, count, ranks)
+    x, _ = _row_buffers(count, width, device if out is None else out.device, out, None, "kway_rows", flags=False)
     if not x.is_cuda:
         raise _lib.MatchaHipError("kway_rows needs a cuda device (no CPU fallback)")
     with torch.cuda.device(x.device):
@@ -130,14 +303,7 @@ class TopK:
         """``scores`` float32 [n] on the device (n <= max_chunk), row i of rank rank0 + i; ``skip`` int32 / bool [n], non-zero = never
         keep.  Enqueued on the current stream; nothing is read back."""
         lib = _lib.load()
-        scores = scores.reshape(-1)
-        if scores.dtype != torch.float32 or scores.device != self.state.device:
-            raise ValueError("scores must be a float32 tensor on the TopK's device")
-        scores = scores.contiguous()
-        if skip is not None:
-            skip = skip.reshape(-1).to(device=scores.device, dtype=torch.int32).contiguous()
-            if skip.numel() != scores.numel():
-                raise ValueError("skip and scores differ in length")
+        scores, skip = _scores_and_skip(scores, skip, self.state.device, "TopK")
         with torch.cuda.device(self.device):
             _lib.check(lib.matcha_topk_update(_lib.ptr(self.state), self.bytes, self.K, self.max_chunk, _lib.ptr(scores), _lib.ptr(skip),
                                               scores.numel(), int(rank0), _stream(self.device)), "matcha_topk_update")
@@ -171,19 +337,13 @@ def kway_sweep(model, lo: int, hi: int, k: int, min_gap: int, top: int, chunk_ro
     pads are attended, so ask for the width the other predictions used (k and width stay at most 8 here: the long forward of model(x), 9 .. 32 columns, has no sweep).  ``exclude``: a HyperedgeSet of known hyperedges; its
     members are skipped and counted, which is what makes the result de novo.
 
-    Eval mode, no grad; per chunk: rows into one reused buffer, model(x), TopK.update -- nothing is copied to the host and nothing
-    synchronises until the end, where the node-id check of the whole sweep is raised once (IndexError for a region beyond the
-    model's tables) and the winners' rows are made from their ranks."""
-    if task_mode not in ("class", "regress"):
-        raise ValueError("task_mode must be 'class' or 'regress'")
+    Eval mode and the loop (see the module's docstring) with kway_rows and TopK.update: nothing synchronises until the end, where the
+    node-id check of the whole sweep is raised once (IndexError for a region beyond the model's tables) and the winners' rows are made
+    from their ranks."""
+    act = _activation(task_mode)
     lo, hi, k, min_gap, top, chunk_rows = int(lo), int(hi), int(k), int(min_gap), int(top), int(chunk_rows)
     n = hi - lo
-    width = int(k if width is None else width)
-    if not k <= width <= _lib.MAX_L:
-        raise ValueError(f"width must be in [k, {_lib.MAX_L}]")
-    if top < 1 or chunk_rows < 1:
-        raise ValueError("top and chunk_rows must be >= 1")
-    act = torch.nn.functional.softplus if task_mode == "regress" else torch.sigmoid
+    width = _check_sweep_args(k, width, chunk_rows, top)
     model.eval()
     dev = model.layer_norm1.weight.device
     total = kway_count(n, k, min_gap) if n >= 1 else 0
@@ -193,35 +353,20 @@ def kway_sweep(model, lo: int, hi: int, k: int, min_gap: int, top: int, chunk_ro
                 "rank": torch.empty(0, dtype=torch.long, device=dev), "n_candidates": 0, "n_excluded": 0}
     chunk_rows = min(chunk_rows, total)
     sel = TopK(min(top, total), chunk_rows, dev)
-    buf = torch.empty(chunk_rows * width, dtype=torch.long, device=dev)
-    n_exc = torch.zeros((), dtype=torch.long, device=dev)
-    # The library picks its forward kernels by batch size (csrc/fused_fwd32.hip: up to two half tiles per compute unit go to the
-    # small-batch kernels), and the two routes round differently (a few ulp of the logit).  The sweep pins the large-batch route, so
-    # a candidate's logit does not depend on chunk_rows, on the size of the region or on the last chunk being short.
-    with torch.no_grad(), model.deferred_id_check(), _lib.option("disable_small_batch"):
-        for r0 in range(0, total, chunk_rows):
-            x = kway_rows(lo, n, k, min_gap, rank0=r0, count=min(chunk_rows, total - r0), width=width, out=buf)
-            logits = model(x).reshape(-1)
-            skip = None
-            if exclude is not None:
-                skip = exclude.contains(x)
-                n_exc += skip.sum()
+    tally = _tally(dev, "n_excluded")
+    rows = lambda r0, count, buf, _: kway_rows(lo, n, k, min_gap, rank0=r0, count=count, width=width, out=buf)
+    with _pinned(model):
+        for r0, _, logits, skip, _ in _chunks(model, total, chunk_rows, _buffers(chunk_rows, width, dev, flags=False), rows, exclude, tally):
             sel.update(logits, r0, skip)
     logit, rank = sel.result()
     rows = kway_rows(lo, n, k, min_gap, ranks=rank, width=width, device=dev)
-    return {"rows": rows, "logit": logit, "proba": act(logit), "rank": rank, "n_candidates": total, "n_excluded": int(n_exc.item())}
+    return {"rows": rows, "logit": logit, "proba": act(logit), "rank": rank, "n_candidates": total, **_counted(tally)}
 
 
 # ---- anchored sweep: the best K completions of every anchor -------------------------------------------------------
 def _check_anchor_args(A: int, s: int, n: int, k: int, min_gap: int):
     if not (A >= 0 and n >= 1 and 2 <= k <= _lib.MAX_L and 1 <= s <= k - 1 and min_gap >= 1):
         raise ValueError(f"need A >= 0, n >= 1, 2 <= k <= {_lib.MAX_L}, 1 <= s <= k - 1, min_gap >= 1 (A={A} s={s} n={n} k={k} min_gap={min_gap})")
-
-
-def _free_count(n: int, f: int, min_gap: int) -> int:
-    """C_f: the gap-constrained subsets of size f >= 1 of a region of n nodes (f = 1: n)."""
-    m = n - (f - 1) * (min_gap - 1)
-    return math.comb(m, f) if m >= f else 0
 
 
 def anchored_count(A: int, s: int, n: int, k: int, min_gap: int) -> int:
@@ -243,25 +388,8 @@ def anchored_unrank(rank: int, anchor_row, lo: int, n: int, k: int, min_gap: int
     anchor_row = [int(v) for v in anchor_row]
     s, lo, n, k, min_gap = len(anchor_row), int(lo), int(n), int(k), int(min_gap)
     _check_anchor_args(1, s, n, k, min_gap)
-    f = k - s
-    total = _free_count(n, f, min_gap)
-    rank = int(rank)
-    if not 0 <= rank < total:
-        raise IndexError(f"rank {rank} outside [0, {total})")
-    m = n - (f - 1) * (min_gap - 1)
-    free, q, upper = [], total - 1 - rank, m - 1                         # as kway_unrank, which refuses a single free node
-    for j in range(f, 0, -1):
-        a, b = j - 1, upper
-        while a < b:
-            mid = (a + b + 1) // 2
-            if math.comb(mid, j) <= q:
-                a = mid
-            else:
-                b = mid - 1
-        q -= math.comb(a, j)
-        free.append(lo + (m - 1 - a) + (f - j) * (min_gap - 1))
-        upper = a - 1
-    row = tuple(sorted(anchor_row + free))
+    rank = _checked_rank(rank, _free_count(n, k - s, min_gap))
+    row = tuple(sorted(anchor_row + list(_subset_unrank(rank, lo, n, k - s, min_gap))))
     return row, all(b - a >= min_gap for a, b in zip(row, row[1:]))
 
 
@@ -293,27 +421,9 @@ def anchored_rows(anchors, lo: int, n: int, k: int, min_gap: int, rank0: int = 0
     anchors = _anchor_table(anchors, device)
     A, s = int(anchors.shape[0]), int(anchors.shape[1])
     total = anchored_count(A, s, n, k, min_gap)
-    width = int(k if width is None else width)
-    if not k <= width <= _lib.MAX_L:
-        raise ValueError(f"width must be in [k, {_lib.MAX_L}]")
-    if ranks is not None:
-        count = int(ranks.numel())
-    else:
-        count = total - int(rank0) if count is None else int(count)
-        if rank0 < 0 or count < 0 or rank0 + count > total:
-            raise IndexError(f"ranks [{rank0}, {rank0 + count}) outside [0, {total})")
-    if out is None:
-        x = torch.empty(count, width, dtype=torch.long, device=device)
-    else:
-        if out.dtype != torch.long or not out.is_contiguous() or out.numel() < count * width:
-            raise ValueError("out must be a contiguous int64 tensor of at least count * width elements")
-        x = out.view(-1)[:count * width].view(count, width)
-    if flag_out is None:
-        flag = torch.empty(count, dtype=torch.int32, device=device)
-    else:
-        if flag_out.dtype != torch.int32 or not flag_out.is_contiguous() or flag_out.numel() < count or flag_out.device != x.device:
-            raise ValueError("flag_out must be a contiguous int32 tensor of at least count elements on out's device")
-        flag = flag_out.view(-1)[:count]
+    width = _check_width(k, width)
+    count = _rank_range(total, rank0, count, ranks)
+    x, flag = _row_buffers(count, width, anchors.device, out, flag_out, "anchored_rows")
     if not x.is_cuda:
         raise _lib.MatchaHipError("anchored_rows needs a cuda device (no CPU fallback)")
     with torch.cuda.device(x.device):
@@ -348,14 +458,7 @@ class SegTopK:
         """``scores`` float32 [n] on the device (n <= max_chunk), row i of global rank g0 + i (segment (g0 + i) // seg_len);
         ``skip`` int32 / bool [n], non-zero = never keep.  Enqueued on the current stream; nothing is read back."""
         lib = _lib.load()
-        scores = scores.reshape(-1)
-        if scores.dtype != torch.float32 or scores.device != self.state.device:
-            raise ValueError("scores must be a float32 tensor on the SegTopK's device")
-        scores = scores.contiguous()
-        if skip is not None:
-            skip = skip.reshape(-1).to(device=scores.device, dtype=torch.int32).contiguous()
-            if skip.numel() != scores.numel():
-                raise ValueError("skip and scores differ in length")
+        scores, skip = _scores_and_skip(scores, skip, self.state.device, "SegTopK")
         with torch.cuda.device(self.device):
             _lib.check(lib.matcha_segtopk_update(_lib.ptr(self.state), self.bytes, *self._dims, self.first_segment, _lib.ptr(scores),
                                                  _lib.ptr(skip), scores.numel(), int(g0), _stream(self.device)), "matcha_segtopk_update")
@@ -385,18 +488,12 @@ def anchored_sweep(model, anchors, lo: int, hi: int, k: int, min_gap: int, top: 
     ``n_invalid`` (candidates that break the rule: a free node on or too near an anchor, or an anchor row that breaks it itself;
     they are scored but never kept) and ``n_excluded`` (valid candidates found in ``exclude``).
 
-    The loop is kway_sweep's: eval mode, no grad, the large-batch route pinned, one reused row buffer, nothing synchronises until
-    the end, where the node-id check of the whole sweep is raised once (IndexError, also for an anchor beyond the model's tables)."""
-    if task_mode not in ("class", "regress"):
-        raise ValueError("task_mode must be 'class' or 'regress'")
+    Eval mode and the loop (see the module's docstring) with anchored_rows and SegTopK.update: nothing synchronises until the end,
+    where the node-id check of the whole sweep is raised once (IndexError, also for an anchor beyond the model's tables)."""
+    act = _activation(task_mode)
     lo, hi, k, min_gap, top, chunk_rows = int(lo), int(hi), int(k), int(min_gap), int(top), int(chunk_rows)
     n = hi - lo
-    width = int(k if width is None else width)
-    if not k <= width <= _lib.MAX_L:
-        raise ValueError(f"width must be in [k, {_lib.MAX_L}]")
-    if top < 1 or chunk_rows < 1:
-        raise ValueError("top and chunk_rows must be >= 1")
-    act = torch.nn.functional.softplus if task_mode == "regress" else torch.sigmoid
+    width = _check_sweep_args(k, width, chunk_rows, top)
     model.eval()
     dev = model.layer_norm1.weight.device
     anchors = _anchor_table(anchors, dev)
@@ -405,34 +502,19 @@ def anchored_sweep(model, anchors, lo: int, hi: int, k: int, min_gap: int, top: 
     cf = total // A if A else 0
     K = min(top, cf)
     if total == 0:
-        e = torch.zeros(A, K, dtype=torch.float32, device=dev)
-        return {"rows": torch.zeros(A, K, width, dtype=torch.long, device=dev), "logit": e, "proba": e.clone(),
-                "rank": torch.full((A, K), -1, dtype=torch.long, device=dev), "count": torch.zeros(A, dtype=torch.long, device=dev),
-                "n_candidates": 0, "n_invalid": 0, "n_excluded": 0}
+        return {**_empty_segments(A, K, width, dev), "n_candidates": 0, "n_invalid": 0, "n_excluded": 0}
     chunk_rows = min(chunk_rows, total)
     sel = SegTopK(A, K, cf, chunk_rows, dev)
-    buf = torch.empty(chunk_rows * width, dtype=torch.long, device=dev)
-    fbuf = torch.empty(chunk_rows, dtype=torch.int32, device=dev)
-    n_inv = torch.zeros((), dtype=torch.long, device=dev)
-    n_exc = torch.zeros((), dtype=torch.long, device=dev)
-    with torch.no_grad(), model.deferred_id_check(), _lib.option("disable_small_batch"):
-        for g0 in range(0, total, chunk_rows):
-            x, flag = anchored_rows(anchors, lo, n, k, min_gap, rank0=g0, count=min(chunk_rows, total - g0), width=width, out=buf, flag_out=fbuf)
-            logits = model(x).reshape(-1)
-            skip = flag != 0
-            n_inv += skip.sum()
-            if exclude is not None:
-                known = exclude.contains(x)
-                n_exc += (known & ~skip).sum()
-                skip = skip | known
+    tally = _tally(dev, "n_invalid", "n_excluded")
+    rows = lambda g0, count, buf, fbuf: anchored_rows(anchors, lo, n, k, min_gap, rank0=g0, count=count, width=width, out=buf, flag_out=fbuf)
+    with _pinned(model):
+        for g0, _, logits, skip, _ in _chunks(model, total, chunk_rows, _buffers(chunk_rows, width, dev), rows, exclude, tally):
             sel.update(logits, g0, skip)
     logit, grank, count = sel.read()
     rows, _ = anchored_rows(anchors, lo, n, k, min_gap, ranks=grank, width=width, device=dev)
-    kept = grank >= 0
-    rank = torch.where(kept, grank - torch.arange(A, dtype=torch.long, device=dev).view(-1, 1) * cf, grank)
-    proba = torch.where(kept, act(logit), torch.zeros_like(logit))
+    rank, proba = _per_segment(grank, logit, cf, act)
     return {"rows": rows.view(A, K, width), "logit": logit, "proba": proba, "rank": rank, "count": count, "n_candidates": total,
-            "n_invalid": int(n_inv.item()), "n_excluded": int(n_exc.item())}
+            **_counted(tally)}
 
 
 # ---- pair maps: a sweep's scores projected onto pairs of bins ------------------------------------------------------
@@ -492,14 +574,10 @@ class PairMap:
         lib = _lib.load()
         if x.dim() != 2 or x.dtype != torch.long or x.device != self.state.device:
             raise ValueError("x must be an int64 [n, L] tensor on the PairMap's device")
-        value = value.reshape(-1)
-        if value.dtype != torch.float32 or value.device != self.state.device or value.numel() != x.shape[0]:
-            raise ValueError("value must be a float32 [n] tensor on the PairMap's device")
-        x, value = x.contiguous(), value.contiguous()
-        if skip is not None:
-            skip = skip.reshape(-1).to(device=value.device, dtype=torch.int32).contiguous()
-            if skip.numel() != value.numel():
-                raise ValueError("skip and value differ in length")
+        value, skip = _scores_and_skip(value, skip, self.state.device, "PairMap")
+        if value.numel() != x.shape[0]:
+            raise ValueError("value must hold one float32 per row of x")
+        x = x.contiguous()
         with torch.cuda.device(self.device):
             _lib.check(lib.matcha_pairmap_update(_lib.ptr(self.state), self.bytes, *self._dims, _lib.ptr(x), _lib.ptr(value), _lib.ptr(skip),
                                                  int(x.shape[0]), int(x.shape[1]), _stream(self.device)), "matcha_pairmap_update")
@@ -560,7 +638,7 @@ def kway_map(model, lo: int, hi: int, k: int, min_gap: int, chunk_rows: int = 1 
              task_mode: str = "class", threshold: float = 0.5, planes="all", value_max: Optional[float] = None,
              row_window: Optional[Tuple[int, int]] = None, col_window: Optional[Tuple[int, int]] = None, expected=None, mode: str = "ratio",
              min_count: int = 30) -> dict:
-    """Score every candidate of size k in the region [lo, hi) (kway_sweep's candidates, in its order, through its loop) and project
+    """Score every candidate of size k in the region [lo, hi) (kway_sweep's candidates, in its order, through the same loop) and project
     the probabilities onto pairs of bins: for every pair, the summed probability of the candidates that contain it ('sum', float64),
     their number ('count'), how many reach ``threshold`` ('count_ge'), the best of them ('max', -inf where there is none) and
     'mean' = sum / count -- the multi-way counterpart of the pairwise probability matrix.
@@ -580,8 +658,7 @@ def kway_map(model, lo: int, hi: int, k: int, min_gap: int, chunk_rows: int = 1 
 
     Returns the planes (device tensors) and the integers ``n_candidates``, ``n_excluded`` and ``n_rejected``.  Nothing synchronises
     until the end, where the node-id check of the whole sweep is raised once (IndexError)."""
-    if task_mode not in ("class", "regress"):
-        raise ValueError("task_mode must be 'class' or 'regress'")
+    act = _activation(task_mode)
     if expected is not None:
         if mode != "ratio":
             raise ValueError("kway_map accumulates non-negative values: with expected only mode 'ratio' is supported")
@@ -591,17 +668,13 @@ def kway_map(model, lo: int, hi: int, k: int, min_gap: int, chunk_rows: int = 1 
             value_max = 1024.0
     lo, hi, k, min_gap, chunk_rows = int(lo), int(hi), int(k), int(min_gap), int(chunk_rows)
     n = hi - lo
-    width = int(k if width is None else width)
-    if not k <= width <= _lib.MAX_L:
-        raise ValueError(f"width must be in [k, {_lib.MAX_L}]")
-    if chunk_rows < 1:
-        raise ValueError("chunk_rows must be >= 1")
+    width = _check_sweep_args(k, width, chunk_rows)
     if task_mode == "regress":
         if value_max is None:
             raise ValueError("task_mode 'regress' needs value_max: the largest value a candidate may contribute")
-        vmax, act = float(value_max), torch.nn.functional.softplus
+        vmax = float(value_max)
     else:
-        vmax, act = (1.0 if expected is None else float(value_max)), torch.sigmoid
+        vmax = 1.0 if expected is None else float(value_max)
     if not 0.0 < vmax <= float(1 << 20):
         raise ValueError("value_max must be in (0, 2^20]")
     mask = _plane_mask(planes)
@@ -629,24 +702,18 @@ def kway_map(model, lo: int, hi: int, k: int, min_gap: int, chunk_rows: int = 1 
         return out
     chunk_rows = min(chunk_rows, total)
     pm = PairMap(rows, cols, mask, vmax=vmax, threshold=threshold, device=dev)
-    buf = torch.empty(chunk_rows * width, dtype=torch.long, device=dev)
-    n_exc = torch.zeros((), dtype=torch.long, device=dev)
+    tally = _tally(dev, "n_excluded")
+    rows = lambda r0, count, buf, _: kway_rows(lo, n, k, min_gap, rank0=r0, count=count, width=width, out=buf)
+    value = lambda r0, x: act(model(x).reshape(-1))                      # a map takes values, not logits
     if expected is not None:
         offset, scale = expected.table(mode, min_count, device=dev)
-    with torch.no_grad(), model.deferred_id_check(), _lib.option("disable_small_batch"):      # as kway_sweep: one forward route
-        for r0 in range(0, total, chunk_rows):
-            x = kway_rows(lo, n, k, min_gap, rank0=r0, count=min(chunk_rows, total - r0), width=width, out=buf)
-            value = act(model(x).reshape(-1))
-            if expected is not None:
-                value = expected.strata.enrich(x, value, offset, scale)
-            skip = None
-            if exclude is not None:
-                skip = exclude.contains(x)
-                n_exc += skip.sum()
-            pm.update(x, value, skip)
+        value = lambda r0, x: expected.strata.enrich(x, act(model(x).reshape(-1)), offset, scale)
+    with _pinned(model):
+        for _, x, v, skip, _ in _chunks(model, total, chunk_rows, _buffers(chunk_rows, width, dev, flags=False), rows, exclude, tally, value):
+            pm.update(x, v, skip)
     out = pm.result()
     out.pop("n_rows")
-    out.update(n_candidates=total, n_excluded=int(n_exc.item()), n_rejected=int(out["n_rejected"].item()))
+    out.update(n_candidates=total, **_counted(tally), n_rejected=int(out["n_rejected"].item()))
     return out
 
 
@@ -684,23 +751,7 @@ def completion_unrank(rank: int, cluster, lo: int, n: int, free: int, min_gap: i
         ids.append(int(v))
     lo, n, free, min_gap = int(lo), int(n), int(free), int(min_gap)
     _check_complete_args(1, max(len(ids), 1), n, free, min_gap)
-    total = _free_count(n, free, min_gap)
-    rank = int(rank)
-    if not 0 <= rank < total:
-        raise IndexError(f"rank {rank} outside [0, {total})")
-    m = n - (free - 1) * (min_gap - 1)
-    part, q, upper = [], total - 1 - rank, m - 1                         # as anchored_unrank
-    for j in range(free, 0, -1):
-        a, b = j - 1, upper
-        while a < b:
-            mid = (a + b + 1) // 2
-            if math.comb(mid, j) <= q:
-                a = mid
-            else:
-                b = mid - 1
-        q -= math.comb(a, j)
-        part.append(lo + (m - 1 - a) + (free - j) * (min_gap - 1))
-        upper = a - 1
+    part = list(_subset_unrank(_checked_rank(rank, _free_count(n, free, min_gap)), lo, n, free, min_gap))
     ascending = all(a <= b for a, b in zip(ids, ids[1:]))
     row = tuple(sorted(ids + part)) if ascending else tuple(ids + part)
     return row, bool(ids) and ascending and all(b - a >= min_gap for a, b in zip(row, row[1:]))
@@ -748,25 +799,9 @@ def _complete_rows(table: torch.Tensor, lo: int, n: int, free: int, min_gap: int
     total = completion_count(A, S, n, free, min_gap)
     if not S + free <= width <= _lib.MAX_LONG_L:
         raise ValueError(f"width must be in [{S + free}, {_lib.MAX_LONG_L}] (the longest cluster and the free part; got {width})")
-    if ranks is not None:
-        count = int(ranks.numel())
-    else:
-        count = total - int(rank0) if count is None else int(count)
-        if rank0 < 0 or count < 0 or rank0 + count > total:
-            raise IndexError(f"ranks [{rank0}, {rank0 + count}) outside [0, {total})")
+    count = _rank_range(total, rank0, count, ranks)
     device = table.device
-    if out is None:
-        x = torch.empty(count, width, dtype=torch.long, device=device)
-    else:
-        if out.dtype != torch.long or not out.is_contiguous() or out.numel() < count * width or out.device != device:
-            raise ValueError("out must be a contiguous int64 tensor of at least count * width elements on the clusters' device")
-        x = out.view(-1)[:count * width].view(count, width)
-    if flag_out is None:
-        flag = torch.empty(count, dtype=torch.int32, device=device)
-    else:
-        if flag_out.dtype != torch.int32 or not flag_out.is_contiguous() or flag_out.numel() < count or flag_out.device != device:
-            raise ValueError("flag_out must be a contiguous int32 tensor of at least count elements on out's device")
-        flag = flag_out.view(-1)[:count]
+    x, flag = _row_buffers(count, width, device, out, flag_out, "completion_rows")
     if not x.is_cuda:
         raise _lib.MatchaHipError("completion_rows needs a cuda device (no CPU fallback)")
     with torch.cuda.device(device):
@@ -814,11 +849,10 @@ def completion_sweep(model, clusters, lo: int, hi: int, free: int = 1, min_gap: 
     breaks the gap itself or has no id; scored, never kept) and ``n_excluded`` (valid candidates found in ``exclude``, a HyperedgeSet).
 
     ``chunk_rows``: None = 2^20 rows up to width 8 and min(2^20, 2^21 // width) beyond (about 3.1 KB of workspace per token); an
-    explicit value the long forward cannot take is a ValueError before anything is launched.  The result does not depend on it.  The
-    loop is anchored_sweep's: eval mode, no grad, one reused row buffer and flag buffer, nothing synchronises until the end, where
-    the node-id check of the whole sweep is raised once (IndexError, also for a cluster id beyond the model's tables)."""
-    if task_mode not in ("class", "regress"):
-        raise ValueError("task_mode must be 'class' or 'regress'")
+    explicit value the long forward cannot take is a ValueError before anything is launched.  The result does not depend on it.
+    Eval mode and the loop (see the module's docstring) with the completion rows and SegTopK.update: nothing synchronises until the
+    end, where the node-id check of the whole sweep is raised once (IndexError, also for a cluster id beyond the model's tables)."""
+    act = _activation(task_mode)
     lo, hi, free, min_gap, top = int(lo), int(hi), int(free), int(min_gap), int(top)
     n = hi - lo
     if not 1 <= free <= _lib.MAX_L or min_gap < 1:
@@ -827,7 +861,6 @@ def completion_sweep(model, clusters, lo: int, hi: int, free: int = 1, min_gap: 
         raise ValueError(f"width must be in [longest cluster + free, {_lib.MAX_LONG_L}] (got {width})")
     if top < 1 or (chunk_rows is not None and int(chunk_rows) < 1):
         raise ValueError("top and chunk_rows must be >= 1")
-    act = torch.nn.functional.softplus if task_mode == "regress" else torch.sigmoid
     model.eval()
     dev = model.layer_norm1.weight.device
     table, s_max = _cluster_table(clusters, dev)
@@ -835,51 +868,27 @@ def completion_sweep(model, clusters, lo: int, hi: int, free: int = 1, min_gap: 
     width = int(max(s_max, 1) + free if width is None else width)
     if not S + free <= width <= _lib.MAX_LONG_L:
         raise ValueError(f"width must be in [{S + free}, {_lib.MAX_LONG_L}]: the longest cluster has {s_max} ids and free = {free} (got {width})")
-    if chunk_rows is None:
-        chunk_rows = 1 << 20 if width <= _lib.MAX_L else min(1 << 20, (1 << 21) // width)
-    else:
-        chunk_rows = int(chunk_rows)
-        if width > _lib.MAX_L:
-            rt = model._runtime()
-            if not 1 <= chunk_rows < 1 << 31 or rt.lib.matcha_workspace_bytes_long(C.byref(rt.shape), chunk_rows, width) == 0:
-                raise ValueError(f"chunk_rows = {chunk_rows} rows of {width} columns are more than the long forward takes in one call")
+    chunk_rows = _long_chunk_rows(model, chunk_rows, width)
     total = completion_count(A, S, n, free, min_gap) if n >= 1 else 0
     cf = total // A if A else 0
     K = min(top, cf)
     if total == 0:
-        e = torch.zeros(A, K, dtype=torch.float32, device=dev)
-        return {"rows": torch.zeros(A, K, width, dtype=torch.long, device=dev), "logit": e, "proba": e.clone(),
-                "rank": torch.full((A, K), -1, dtype=torch.long, device=dev), "count": torch.zeros(A, dtype=torch.long, device=dev),
-                "added": torch.zeros(A, K, free, dtype=torch.long, device=dev), "n_candidates": 0, "n_invalid": 0, "n_excluded": 0}
+        return {**_empty_segments(A, K, width, dev), "added": torch.zeros(A, K, free, dtype=torch.long, device=dev), "n_candidates": 0,
+                "n_invalid": 0, "n_excluded": 0}
     chunk_rows = min(chunk_rows, total)
     sel = SegTopK(A, K, cf, chunk_rows, dev)
-    buf = torch.empty(chunk_rows * width, dtype=torch.long, device=dev)
-    fbuf = torch.empty(chunk_rows, dtype=torch.int32, device=dev)
-    n_inv = torch.zeros((), dtype=torch.long, device=dev)
-    n_exc = torch.zeros((), dtype=torch.long, device=dev)
-    # Up to width 8 the large-batch route is pinned as in kway_sweep.  The long forward has one route: its kernels are chosen by the
-    # model's shape, never by the batch, and every token row is computed by itself, so a logit does not depend on chunk_rows there.
-    with torch.no_grad(), model.deferred_id_check(), _lib.option("disable_small_batch"):
-        for g0 in range(0, total, chunk_rows):
-            x, flag = _complete_rows(table, lo, n, free, min_gap, g0, min(chunk_rows, total - g0), None, width, buf, fbuf)
-            logits = model(x).reshape(-1)
-            skip = flag != 0
-            n_inv += skip.sum()
-            if exclude is not None:
-                known = exclude.contains(x)
-                n_exc += (known & ~skip).sum()
-                skip = skip | known
+    tally = _tally(dev, "n_invalid", "n_excluded")
+    rows = lambda g0, count, buf, fbuf: _complete_rows(table, lo, n, free, min_gap, g0, count, None, width, buf, fbuf)
+    with _pinned(model):
+        for g0, _, logits, skip, _ in _chunks(model, total, chunk_rows, _buffers(chunk_rows, width, dev), rows, exclude, tally):
             sel.update(logits, g0, skip)
     logit, grank, count = sel.read()
     rows, _ = _complete_rows(table, lo, n, free, min_gap, 0, None, grank.view(-1), width, None, None)
     # the added bins: the same ranks through the s_a = 0 form of the rows kernel (a table of empty clusters: the free part alone)
     added, _ = _complete_rows(torch.zeros(A, 1, dtype=torch.long, device=dev), lo, n, free, min_gap, 0, None, grank.view(-1), free + 1, None, None)
-    kept = grank >= 0
-    rank = torch.where(kept, grank - torch.arange(A, dtype=torch.long, device=dev).view(-1, 1) * cf, grank)
-    proba = torch.where(kept, act(logit), torch.zeros_like(logit))
+    rank, proba = _per_segment(grank, logit, cf, act)
     return {"rows": rows.view(A, K, width), "logit": logit, "proba": proba, "rank": rank, "count": count,
-            "added": added.view(A, K, free + 1)[:, :, :free].contiguous(), "n_candidates": total, "n_invalid": int(n_inv.item()),
-            "n_excluded": int(n_exc.item())}
+            "added": added.view(A, K, free + 1)[:, :, :free].contiguous(), "n_candidates": total, **_counted(tally)}
 
 
 # ---- cluster decomposition: the sub-hyperedges of clusters of up to 32 loci ------------------------------------------
@@ -905,20 +914,8 @@ def subset_count(A: int, S: int, m: int, complement: int = 0) -> int:
 
 
 def _choice_unrank(rank: int, S: int, m: int) -> Tuple[int, ...]:
-    """The m-subset of the positions [0, S) of lexicographic rank ``rank``, as kway_unrank reads it off the combinatorial number system."""
-    pos, q, upper = [], math.comb(S, m) - 1 - rank, S - 1
-    for j in range(m, 0, -1):
-        a, b = j - 1, upper
-        while a < b:
-            mid = (a + b + 1) // 2
-            if math.comb(mid, j) <= q:
-                a = mid
-            else:
-                b = mid - 1
-        q -= math.comb(a, j)
-        pos.append(S - 1 - a)
-        upper = a - 1
-    return tuple(pos)
+    """The m-subset of the positions [0, S) of lexicographic rank ``rank``."""
+    return _subset_unrank(rank, 0, S, m, 1)
 
 
 def subset_unrank(rank: int, cluster, m: int, complement: int = 0, min_gap: int = 1) -> Tuple[Tuple[int, ...], bool]:
@@ -933,9 +930,7 @@ def subset_unrank(rank: int, cluster, m: int, complement: int = 0, min_gap: int 
     _check_subset_args(1, S, m, complement)
     if min_gap < 1:
         raise ValueError("min_gap must be >= 1")
-    total = math.comb(S, m)
-    if not 0 <= rank < total:
-        raise IndexError(f"rank {rank} outside [0, {total})")
+    rank = _checked_rank(rank, math.comb(S, m))
     ids = []
     for v in cluster:
         if v == 0:
@@ -969,25 +964,9 @@ def _subset_rows(table: torch.Tensor, m: int, complement: int, min_gap: int, ran
     least = max(S - m, 1) if complement else m
     if not least <= width <= _lib.MAX_LONG_L:
         raise ValueError(f"width must be in [{least}, {_lib.MAX_LONG_L}] (keep: m, drop: S - m; got {width})")
-    if ranks is not None:
-        count = int(ranks.numel())
-    else:
-        count = total - int(rank0) if count is None else int(count)
-        if rank0 < 0 or count < 0 or rank0 + count > total:
-            raise IndexError(f"ranks [{rank0}, {rank0 + count}) outside [0, {total})")
+    count = _rank_range(total, rank0, count, ranks)
     device = table.device
-    if out is None:
-        x = torch.empty(count, width, dtype=torch.long, device=device)
-    else:
-        if out.dtype != torch.long or not out.is_contiguous() or out.numel() < count * width or out.device != device:
-            raise ValueError("out must be a contiguous int64 tensor of at least count * width elements on the clusters' device")
-        x = out.view(-1)[:count * width].view(count, width)
-    if flag_out is None:
-        flag = torch.empty(count, dtype=torch.int32, device=device)
-    else:
-        if flag_out.dtype != torch.int32 or not flag_out.is_contiguous() or flag_out.numel() < count or flag_out.device != device:
-            raise ValueError("flag_out must be a contiguous int32 tensor of at least count elements on out's device")
-        flag = flag_out.view(-1)[:count]
+    x, flag = _row_buffers(count, width, device, out, flag_out, "subset_rows")
     if not x.is_cuda:
         raise _lib.MatchaHipError("subset_rows needs a cuda device (no CPU fallback)")
     with torch.cuda.device(device):
@@ -1045,14 +1024,7 @@ class SubsetSupport:
         ``skip`` int32 / bool [n], non-zero = the row contributes nothing.  A row whose value is NaN, negative or > vmax is counted as
         rejected.  Enqueued on the current stream; nothing is read back."""
         lib = _lib.load()
-        value = value.reshape(-1)
-        if value.dtype != torch.float32 or value.device != self.state.device:
-            raise ValueError("value must be a float32 tensor on the SubsetSupport's device")
-        value = value.contiguous()
-        if skip is not None:
-            skip = skip.reshape(-1).to(device=value.device, dtype=torch.int32).contiguous()
-            if skip.numel() != value.numel():
-                raise ValueError("skip and value differ in length")
+        value, skip = _scores_and_skip(value, skip, self.state.device, "SubsetSupport")
         with torch.cuda.device(self.device):
             _lib.check(lib.matcha_subset_support_update(_lib.ptr(self.state), self.bytes, *self._dims, _lib.ptr(value), _lib.ptr(skip),
                                                         value.numel(), int(g0), _stream(self.device)), "matcha_subset_support_update")
@@ -1107,14 +1079,7 @@ class SubsetPairSupport:
         non-zero = the row contributes nothing; a row whose value is NaN, negative or > vmax is counted as rejected.  Enqueued on the
         current stream; nothing is read back."""
         lib = _lib.load()
-        value = value.reshape(-1)
-        if value.dtype != torch.float32 or value.device != self.state.device:
-            raise ValueError("value must be a float32 tensor on the SubsetPairSupport's device")
-        value = value.contiguous()
-        if skip is not None:
-            skip = skip.reshape(-1).to(device=value.device, dtype=torch.int32).contiguous()
-            if skip.numel() != value.numel():
-                raise ValueError("skip and value differ in length")
+        value, skip = _scores_and_skip(value, skip, self.state.device, "SubsetPairSupport")
         with torch.cuda.device(self.device):
             _lib.check(lib.matcha_subset_pair_update(_lib.ptr(self.state), self.bytes, *self._dims, _lib.ptr(value), _lib.ptr(skip),
                                                      value.numel(), int(g0), _stream(self.device)), "matcha_subset_pair_update")
@@ -1174,10 +1139,10 @@ def decomposition_sweep(model, clusters, m: int, mode: str = "keep", min_gap: in
     integers ``n_candidates``, ``n_invalid`` (candidates that break the gap rule; scored, never kept) and ``n_excluded`` (valid
     candidates found in ``exclude``, a HyperedgeSet).
 
-    ``chunk_rows`` as in completion_sweep; the result does not depend on it, bit for bit.  The loop is completion_sweep's: eval mode,
-    no grad, reused buffers, nothing synchronises until the end, where the node-id check of the whole sweep is raised once."""
-    if task_mode not in ("class", "regress"):
-        raise ValueError("task_mode must be 'class' or 'regress'")
+    ``chunk_rows`` as in completion_sweep; the result does not depend on it, bit for bit.  Eval mode and the loop (see the module's
+    docstring), once per size with buffers sized for the largest, into SegTopK and the support planes: nothing synchronises until
+    the end, where the node-id check of the whole sweep is raised once."""
+    act = _activation(task_mode)
     if mode not in _MODES:
         raise ValueError("mode must be 'keep' or 'drop'")
     if support and task_mode == "regress":
@@ -1191,7 +1156,6 @@ def decomposition_sweep(model, clusters, m: int, mode: str = "keep", min_gap: in
         raise ValueError(f"need {1 if complement else 2} <= m <= {_lib.MAX_L} in mode '{mode}' and min_gap >= 1 (m={m} min_gap={min_gap})")
     if top < 1 or (chunk_rows is not None and int(chunk_rows) < 1):
         raise ValueError("top and chunk_rows must be >= 1")
-    act = torch.nn.functional.softplus if task_mode == "regress" else torch.sigmoid
     model.eval()
     dev = model.layer_norm1.weight.device
     table, s_max = _subset_table(clusters, dev)
@@ -1200,14 +1164,7 @@ def decomposition_sweep(model, clusters, m: int, mode: str = "keep", min_gap: in
     width = int(least if width is None else width)
     if not least <= width <= most:
         raise ValueError(f"width must be in [{least}, {most}] in mode '{mode}' (m = {m}, the longest cluster has {s_max} ids; got {width})")
-    if chunk_rows is None:
-        chunk_rows = 1 << 20 if width <= _lib.MAX_L else min(1 << 20, (1 << 21) // width)
-    else:
-        chunk_rows = int(chunk_rows)
-        if width > _lib.MAX_L:
-            rt = model._runtime()
-            if not 1 <= chunk_rows < 1 << 31 or rt.lib.matcha_workspace_bytes_long(C.byref(rt.shape), chunk_rows, width) == 0:
-                raise ValueError(f"chunk_rows = {chunk_rows} rows of {width} columns are more than the long forward takes in one call")
+    chunk_rows = _long_chunk_rows(model, chunk_rows, width)
     sizes = (table != 0).sum(dim=1).cpu() if A else torch.zeros(0, dtype=torch.long)      # one small read-back, before anything is launched
     groups = []
     for s in sorted(set(sizes.tolist())):
@@ -1219,9 +1176,7 @@ def decomposition_sweep(model, clusters, m: int, mode: str = "keep", min_gap: in
         maps = [_pair_square_map(s) for s, _, _ in groups]
         pair_map = dict(zip([s for s, _, _ in groups], torch.cat(maps).to(dev).split([int(t.numel()) for t in maps])))
     K = min(top, max([cm for _, _, cm in groups] + [0]))
-    out = {"rows": torch.zeros(A, K, width, dtype=torch.long, device=dev), "logit": torch.zeros(A, K, dtype=torch.float32, device=dev),
-           "proba": torch.zeros(A, K, dtype=torch.float32, device=dev), "rank": torch.full((A, K), -1, dtype=torch.long, device=dev),
-           "count": torch.zeros(A, dtype=torch.long, device=dev), "chosen": torch.zeros(A, K, m, dtype=torch.long, device=dev)}
+    out = {**_empty_segments(A, K, width, dev), "chosen": torch.zeros(A, K, m, dtype=torch.long, device=dev)}
     if support:
         out["support_sum"] = torch.zeros(A, S_max, dtype=torch.float64, device=dev)
         out["support_count"] = torch.zeros(A, S_max, dtype=torch.long, device=dev)
@@ -1232,31 +1187,19 @@ def decomposition_sweep(model, clusters, m: int, mode: str = "keep", min_gap: in
         out["full_logit"] = torch.zeros(A, dtype=torch.float32, device=dev)
     n_cand = sum(int(idx.numel()) * cm for _, idx, cm in groups)
     if groups:
-        most_rows = min(chunk_rows, max(int(idx.numel()) * cm for _, idx, cm in groups))
-        buf = torch.empty(most_rows * width, dtype=torch.long, device=dev)
-        fbuf = torch.empty(most_rows, dtype=torch.int32, device=dev)
-    n_inv = torch.zeros((), dtype=torch.long, device=dev)
-    n_exc = torch.zeros((), dtype=torch.long, device=dev)
+        buffers = _buffers(min(chunk_rows, max(int(idx.numel()) * cm for _, idx, cm in groups)), width, dev)
+    tally = _tally(dev, "n_invalid", "n_excluded")
     done = []
-    # One forward route, as in completion_sweep: the large-batch route pinned up to width 8, the long forward's single route beyond.
-    with torch.no_grad(), model.deferred_id_check(), _lib.option("disable_small_batch"):
+    with _pinned(model):
         for s, idx, cm in groups:
             tab = table[idx, :s].contiguous()
             A_s = int(tab.shape[0])
             total = A_s * cm
-            chunk = min(chunk_rows, total)
-            sel = SegTopK(A_s, min(top, cm), cm, chunk, dev)
+            sel = SegTopK(A_s, min(top, cm), cm, min(chunk_rows, total), dev)
             sup = SubsetSupport(A_s, s, m, 1.0, dev) if support else None
             psup = SubsetPairSupport(A_s, s, m, 1.0, dev) if pair_support else None
-            for g0 in range(0, total, chunk):
-                x, flag = _subset_rows(tab, m, complement, min_gap, g0, min(chunk, total - g0), None, width, buf, fbuf)
-                logits = model(x).reshape(-1)
-                skip = flag != 0
-                n_inv += skip.sum()
-                if exclude is not None:
-                    known = exclude.contains(x)
-                    n_exc += (known & ~skip).sum()
-                    skip = skip | known
+            rows = lambda g0, count, buf, fbuf: _subset_rows(tab, m, complement, min_gap, g0, count, None, width, buf, fbuf)
+            for g0, _, logits, skip, _ in _chunks(model, total, chunk_rows, buffers, rows, exclude, tally):
                 sel.update(logits, g0, skip)
                 if sup is not None or psup is not None:
                     proba = torch.sigmoid(logits)
@@ -1275,15 +1218,14 @@ def decomposition_sweep(model, clusters, m: int, mode: str = "keep", min_gap: in
         A_s, Ks = int(tab.shape[0]), min(top, cm)
         logit, grank, count = sel.read()
         rows, _ = _subset_rows(tab, m, complement, min_gap, 0, None, grank.view(-1), width, None, None)
-        kept = grank >= 0
-        rank = torch.where(kept, grank - torch.arange(A_s, dtype=torch.long, device=dev).view(-1, 1) * cm, grank)
+        rank, proba = _per_segment(grank, logit, cm, act)
         if m == 1:                                                       # a choice of one position is its rank
-            chosen = torch.where(kept, tab.gather(1, rank.clamp(min=0)), torch.zeros_like(rank)).view(A_s, Ks, 1)
+            chosen = torch.where(rank >= 0, tab.gather(1, rank.clamp(min=0)), torch.zeros_like(rank)).view(A_s, Ks, 1)
         else:                                                            # the same ranks through the keep form of the rows kernel
             chosen = _subset_rows(tab, m, 0, 1, 0, None, grank.view(-1), m, None, None)[0].view(A_s, Ks, m)
         out["rows"][idx, :Ks] = rows.view(A_s, Ks, width)
         out["logit"][idx, :Ks] = logit
-        out["proba"][idx, :Ks] = torch.where(kept, act(logit), torch.zeros_like(logit))
+        out["proba"][idx, :Ks] = proba
         out["rank"][idx, :Ks] = rank
         out["count"][idx] = count
         out["chosen"][idx, :Ks] = chosen
@@ -1310,7 +1252,7 @@ def decomposition_sweep(model, clusters, m: int, mode: str = "keep", min_gap: in
         for _, idx, _, _, _, _, _ in done:
             swept[idx] = True
         out["full_proba"] = torch.where(swept, act(out["full_logit"]), torch.zeros_like(out["full_logit"]))
-    out.update(n_candidates=n_cand, n_invalid=int(n_inv.item()), n_excluded=int(n_exc.item()))
+    out.update(n_candidates=n_cand, **_counted(tally))
     return out
 
 
@@ -1336,12 +1278,7 @@ def grow_twins(beam: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.
     if not beam.is_cuda:
         raise _lib.MatchaHipError("grow_twins needs a cuda device (no CPU fallback)")
     beam = beam.contiguous()
-    if out is None:
-        twin = torch.empty(A * B, B, dtype=torch.long, device=beam.device)
-    else:
-        if out.dtype != torch.long or not out.is_contiguous() or out.numel() < A * B * B or out.device != beam.device:
-            raise ValueError("out must be a contiguous int64 tensor of at least A * B * B elements on the beam's device")
-        twin = out.view(-1)[:A * B * B].view(A * B, B)
+    twin, _ = _row_buffers(A * B, B, beam.device, out, None, "grow_twins", flags=False)
     with torch.cuda.device(beam.device):
         _lib.check(lib.matcha_grow_twins(_lib.ptr(beam), A, B, S, _lib.ptr(twin), _stream(beam.device)), "matcha_grow_twins")
     return twin
@@ -1364,9 +1301,7 @@ def grow_twin_flags(twin: torch.Tensor, lo: int, n: int, flag: torch.Tensor, ran
     total = A * B * n
     if total >= 1 << 63:
         raise ValueError(f"{total} candidates (A={A} B={B} n={n}) do not fit 63 bits")
-    count = total - rank0 if count is None else int(count)
-    if rank0 < 0 or count < 0 or rank0 + count > total:
-        raise IndexError(f"ranks [{rank0}, {rank0 + count}) outside [0, {total})")
+    count = _rank_range(total, rank0, count, None)
     if flag.dtype != torch.int32 or not flag.is_contiguous() or flag.numel() < count or flag.device != twin.device:
         raise ValueError("flag must be a contiguous int32 tensor of at least count elements on twin's device")
     if not twin.is_cuda:
@@ -1377,25 +1312,11 @@ def grow_twin_flags(twin: torch.Tensor, lo: int, n: int, flag: torch.Tensor, ran
     return flag
 
 
-def _grow_chunk_rows(model, chunk_rows: Optional[int], width: int) -> int:
-    """completion_sweep's defaults and refusal."""
-    if chunk_rows is None:
-        return 1 << 20 if width <= _lib.MAX_L else min(1 << 20, (1 << 21) // width)
-    chunk_rows = int(chunk_rows)
-    if chunk_rows < 1:
-        raise ValueError("chunk_rows must be >= 1")
-    if width > _lib.MAX_L:
-        rt = model._runtime()
-        if not chunk_rows < 1 << 31 or rt.lib.matcha_workspace_bytes_long(C.byref(rt.shape), chunk_rows, width) == 0:
-            raise ValueError(f"chunk_rows = {chunk_rows} rows of {width} columns are more than the long forward takes in one call")
-    return chunk_rows
-
-
 def _grow_step(model, beam: torch.Tensor, lo: int, n: int, K: int, min_gap: int, width: int, exclude, chunk_rows: int, act,
                counters: torch.Tensor) -> dict:
-    """One step on a beam int64 [A, B, S] on the model's device, A >= 1 and n >= 1: twin table, candidates chunk by chunk, one
-    SegTopK per seed, the advance.  Nothing is read back; ``counters`` (device int64 [3]: invalid, twins, excluded) is added to.  The
-    caller holds eval mode, no_grad, the deferred id check and the pinned route."""
+    """One step on a beam int64 [A, B, S] on the model's device, A >= 1 and n >= 1: twin table, the loop over the completion rows with
+    the twins flagged, one SegTopK per seed, the advance.  Nothing is read back; ``counters`` (device int64 [3]: invalid, twins,
+    excluded) is added to.  The caller holds eval mode and ``_pinned``."""
     A, B, S = (int(v) for v in beam.shape)
     dev = beam.device
     table = beam.view(A * B, S)
@@ -1403,38 +1324,29 @@ def _grow_step(model, beam: torch.Tensor, lo: int, n: int, K: int, min_gap: int,
     chunk_rows = min(chunk_rows, total)
     twin = grow_twins(beam)
     sel = SegTopK(A, K, B * n, chunk_rows, dev)
-    buf = torch.empty(chunk_rows * width, dtype=torch.long, device=dev)
-    fbuf = torch.empty(chunk_rows, dtype=torch.int32, device=dev)
-    for g0 in range(0, total, chunk_rows):
-        cnt = min(chunk_rows, total - g0)
-        x, flag = _complete_rows(table, lo, n, 1, min_gap, g0, cnt, None, width, buf, fbuf)
-        grow_twin_flags(twin, lo, n, flag, g0, cnt)
-        logits = model(x).reshape(-1)
-        skip = flag != 0
+
+    def rows(g0, count, buf, fbuf):
+        x, flag = _complete_rows(table, lo, n, 1, min_gap, g0, count, None, width, buf, fbuf)
+        return x, grow_twin_flags(twin, lo, n, flag, g0, count)
+
+    tally = {"n_excluded": counters[2]}                                  # invalid rows and twins are told apart here, from the flag
+    for g0, _, logits, skip, flag in _chunks(model, total, chunk_rows, _buffers(chunk_rows, width, dev), rows, exclude, tally):
         counters[0] += ((flag & 1) != 0).sum()
         counters[1] += (flag == 2).sum()                                 # valid candidates that are twins
-        if exclude is not None:
-            known = exclude.contains(x)
-            counters[2] += (known & ~skip).sum()
-            skip = skip | known
         sel.update(logits, g0, skip)
     logit, grank, count = sel.read()
     rows, _ = _complete_rows(table, lo, n, 1, min_gap, 0, None, grank.view(-1), width, None, None)      # rank -1: an all-zero row
     rows = rows.view(A, K, width)
-    kept = grank >= 0
-    zero = torch.zeros_like(grank)
-    rank = torch.where(kept, grank - torch.arange(A, dtype=torch.long, device=dev).view(-1, 1) * (B * n), grank)
-    return {"rows": rows, "logit": logit, "proba": torch.where(kept, act(logit), torch.zeros_like(logit)), "rank": rank,
+    rank, proba = _per_segment(grank, logit, B * n, act)
+    kept, zero = rank >= 0, torch.zeros_like(rank)
+    return {"rows": rows, "logit": logit, "proba": proba, "rank": rank,
             "parent": torch.where(kept, torch.div(rank, n, rounding_mode="floor"), zero), "added": torch.where(kept, lo + rank % n, zero),
             "count": count, "beam": rows[:, :, :S + 1].contiguous()}
 
 
 def _empty_step(A: int, K: int, S: int, width: int, dev) -> dict:
-    e = torch.zeros(A, K, dtype=torch.float32, device=dev)
     z = torch.zeros(A, K, dtype=torch.long, device=dev)
-    return {"rows": torch.zeros(A, K, width, dtype=torch.long, device=dev), "logit": e, "proba": e.clone(),
-            "rank": torch.full((A, K), -1, dtype=torch.long, device=dev), "parent": z, "added": z.clone(),
-            "count": torch.zeros(A, dtype=torch.long, device=dev), "beam": torch.zeros(A, K, S + 1, dtype=torch.long, device=dev)}
+    return {**_empty_segments(A, K, width, dev), "parent": z, "added": z.clone(), "beam": torch.zeros(A, K, S + 1, dtype=torch.long, device=dev)}
 
 
 def grow_step(model, beam, lo: int, hi: int, beam_out: Optional[int] = None, min_gap: int = 1, width: Optional[int] = None, exclude=None,
@@ -1450,9 +1362,9 @@ def grow_step(model, beam, lo: int, hi: int, beam_out: Optional[int] = None, min
     [A, K, width], ``logit``, ``proba``, ``rank`` (within the seed), ``parent`` (the slot extended) and ``added`` (the bin) [A, K],
     ``count`` int64 [A] and ``beam`` int64 [A, K, S + 1], the table of the next step; beyond count[a] the rank is -1 and everything
     else 0.  The integers ``n_candidates`` = A B n, ``n_invalid`` (completion_sweep's), ``n_twins`` (valid candidates flagged as
-    twins) and ``n_excluded``.  ``chunk_rows`` and the loop are completion_sweep's; the result does not depend on the cut."""
-    if task_mode not in ("class", "regress"):
-        raise ValueError("task_mode must be 'class' or 'regress'")
+    twins) and ``n_excluded``.  ``chunk_rows`` as in completion_sweep, and the loop of the module's docstring; the result does not depend
+    on the cut."""
+    act = _activation(task_mode)
     lo, hi, min_gap = int(lo), int(hi), int(min_gap)
     n = hi - lo
     beam = torch.as_tensor(beam)
@@ -1466,8 +1378,7 @@ def grow_step(model, beam, lo: int, hi: int, beam_out: Optional[int] = None, min
     width = int(S + 1 if width is None else width)
     if not S + 1 <= width <= _lib.MAX_LONG_L:
         raise ValueError(f"width must be in [{S + 1}, {_lib.MAX_LONG_L}]: a slot holds up to {S} ids and a bin is added (got {width})")
-    chunk_rows = _grow_chunk_rows(model, chunk_rows, width)
-    act = torch.nn.functional.softplus if task_mode == "regress" else torch.sigmoid
+    chunk_rows = _long_chunk_rows(model, chunk_rows, width)
     model.eval()
     dev = model.layer_norm1.weight.device
     K = min(beam_out, B * max(n, 0))
@@ -1477,7 +1388,7 @@ def grow_step(model, beam, lo: int, hi: int, beam_out: Optional[int] = None, min
         return out
     beam = beam.to(device=dev, dtype=torch.long).contiguous()
     counters = torch.zeros(3, dtype=torch.long, device=dev)
-    with torch.no_grad(), model.deferred_id_check(), _lib.option("disable_small_batch"):
+    with _pinned(model):
         out = _grow_step(model, beam, lo, n, K, min_gap, width, exclude, chunk_rows, act, counters)
     c = counters.tolist()
     out.update(n_candidates=A * B * n, n_invalid=c[0], n_twins=c[1], n_excluded=c[2])
@@ -1499,9 +1410,9 @@ def growth_sweep(model, seeds, lo: int, hi: int, max_size: int, beam: int = 8, m
     s_a >= max_size, or without an id, has no levels.  Slots beyond count are 0.
 
     Seed sizes are read on the host (a device tensor costs one small read-back before anything is launched); the counters stay on the
-    device, nothing synchronises between steps, and the node-id check of the whole growth is raised once at the end (IndexError)."""
-    if task_mode not in ("class", "regress"):
-        raise ValueError("task_mode must be 'class' or 'regress'")
+    device, nothing synchronises between steps, and the node-id check of the whole growth is raised once at the end (IndexError):
+    ``_pinned`` is held across all steps."""
+    act = _activation(task_mode)
     lo, hi, max_size, B, min_gap = int(lo), int(hi), int(max_size), int(beam), int(min_gap)
     n = hi - lo
     if not 2 <= max_size <= _lib.MAX_LONG_L:
@@ -1511,8 +1422,7 @@ def growth_sweep(model, seeds, lo: int, hi: int, max_size: int, beam: int = 8, m
     width = int(max_size if width is None else width)
     if not max_size <= width <= _lib.MAX_LONG_L:
         raise ValueError(f"width must be in [max_size, {_lib.MAX_LONG_L}] (got {width} for max_size = {max_size})")
-    chunk_rows = _grow_chunk_rows(model, chunk_rows, width)
-    act = torch.nn.functional.softplus if task_mode == "regress" else torch.sigmoid
+    chunk_rows = _long_chunk_rows(model, chunk_rows, width)
     model.eval()
     dev = model.layer_norm1.weight.device
     if isinstance(seeds, torch.Tensor) and seeds.is_cuda:
@@ -1533,7 +1443,7 @@ def growth_sweep(model, seeds, lo: int, hi: int, max_size: int, beam: int = 8, m
     if n >= 1 and T > 0:
         t_idx = torch.arange(T).view(1, -1)
         out["size"] = torch.where(t_idx < steps.view(-1, 1), sizes.view(-1, 1) + t_idx + 1, torch.zeros(A, T, dtype=torch.long)).to(dev)
-        with torch.no_grad(), model.deferred_id_check(), _lib.option("disable_small_batch"):
+        with _pinned(model):
             active = torch.nonzero(steps > 0).view(-1)                   # host indices of the seeds of step 0
             cur = table[active].to(dev).view(-1, 1, int(table.shape[1]))
             for t in range(T):
@@ -1573,25 +1483,6 @@ def growth_sweep(model, seeds, lo: int, hi: int, max_size: int, beam: int = 8, m
 
 # ---- multi-region sweep: candidates with bins drawn from several regions ------------------------------------------
 MAX_PARTS = 8
-
-
-def _subset_unrank(rank: int, lo: int, n: int, f: int, min_gap: int) -> Tuple[int, ...]:
-    """The gap-constrained subset of size f >= 1 of [lo, lo + n) of lexicographic rank ``rank`` (kway_unrank's decoding, f = 1 allowed)."""
-    m = n - (f - 1) * (min_gap - 1)
-    total = math.comb(m, f) if m >= f else 0
-    row, q, upper = [], total - 1 - rank, m - 1
-    for j in range(f, 0, -1):
-        a, b = j - 1, upper
-        while a < b:
-            mid = (a + b + 1) // 2
-            if math.comb(mid, j) <= q:
-                a = mid
-            else:
-                b = mid - 1
-        q -= math.comb(a, j)
-        row.append(lo + (m - 1 - a) + (f - j) * (min_gap - 1))
-        upper = a - 1
-    return tuple(row)
 
 
 def _region_parts(parts, min_gap: int):
@@ -1636,10 +1527,7 @@ def region_unrank(rank: int, parts, min_gap: int) -> Tuple[Tuple[int, ...], bool
     the parts' candidates one behind the other, ascending as it stands.  It is valid iff every adjacent difference is >= min_gap, which
     can only fail between the last bin of one part and the first of the next."""
     los, ns, ms, counts, _ = _region_parts(parts, min_gap)
-    total = region_count(parts, min_gap)
-    rank, min_gap = int(rank), int(min_gap)
-    if not 0 <= rank < total:
-        raise IndexError(f"rank {rank} outside [0, {total})")
+    rank, min_gap = _checked_rank(rank, region_count(parts, min_gap)), int(min_gap)
     pieces = []
     for p in range(len(los) - 1, -1, -1):
         rank, r = divmod(rank, counts[p])
@@ -1664,31 +1552,12 @@ def region_rows(parts, min_gap: int, rank0: int = 0, count: Optional[int] = None
     los, ns, ms, _, k = _region_parts(parts, min_gap)
     total = region_count(parts, min_gap)
     min_gap = int(min_gap)
-    width = int(k if width is None else width)
-    if not k <= width <= _lib.MAX_L:
-        raise ValueError(f"width must be in [k, {_lib.MAX_L}]")
+    width = _check_width(k, width)
     if ranks is not None:
         ranks = ranks.to(device=device, dtype=torch.long).contiguous().view(-1)
-        count, device = int(ranks.numel()), ranks.device
-    else:
-        if out is not None:
-            device = out.device
-        rank0 = int(rank0)
-        count = total - rank0 if count is None else int(count)
-        if rank0 < 0 or count < 0 or rank0 + count > total:
-            raise IndexError(f"ranks [{rank0}, {rank0 + count}) outside [0, {total})")
-    if out is None:
-        x = torch.empty(count, width, dtype=torch.long, device=device)
-    else:
-        if out.dtype != torch.long or not out.is_contiguous() or out.numel() < count * width:
-            raise ValueError("out must be a contiguous int64 tensor of at least count * width elements")
-        x = out.view(-1)[:count * width].view(count, width)
-    if flag_out is None:
-        flag = torch.empty(count, dtype=torch.int32, device=x.device)
-    else:
-        if flag_out.dtype != torch.int32 or not flag_out.is_contiguous() or flag_out.numel() < count or flag_out.device != x.device:
-            raise ValueError("flag_out must be a contiguous int32 tensor of at least count elements on out's device")
-        flag = flag_out.view(-1)[:count]
+        device = ranks.device
+    count = _rank_range(total, rank0, count, ranks)
+    x, flag = _row_buffers(count, width, device if out is None else out.device, out, flag_out, "region_rows")
     if not x.is_cuda:
         raise _lib.MatchaHipError("region_rows needs a cuda device (no CPU fallback)")
     arrays = _part_arrays(los, ns, ms)                                   # host arrays, alive until the call returns: it reads them before
@@ -1713,22 +1582,16 @@ def region_sweep(model, parts, min_gap: int, top: int, chunk_rows: int = 1 << 20
     are 0.  With m_0 = 1 that is, for every bin of the first region, its best hubs with partners in all the others.  An empty sweep
     (T = 0) returns A = 0.
 
-    The loop is kway_sweep's: eval mode, no grad, the large-batch route pinned, one reused row buffer and one reused flag buffer,
-    nothing synchronises until the end, where the node-id check of the whole sweep is raised once (IndexError)."""
-    if task_mode not in ("class", "regress"):
-        raise ValueError("task_mode must be 'class' or 'regress'")
+    Eval mode and the loop (see the module's docstring) with region_rows and TopK.update or SegTopK.update: nothing synchronises until
+    the end, where the node-id check of the whole sweep is raised once (IndexError)."""
+    act = _activation(task_mode)
     los, ns, ms, counts, k = _region_parts(parts, min_gap)
     parts = [(lo, lo + n, m) for lo, n, m in zip(los, ns, ms)]
     min_gap, top, chunk_rows = int(min_gap), int(top), int(chunk_rows)
-    width = int(k if width is None else width)
-    if not k <= width <= _lib.MAX_L:
-        raise ValueError(f"width must be in [k, {_lib.MAX_L}]")
-    if top < 1 or chunk_rows < 1:
-        raise ValueError("top and chunk_rows must be >= 1")
+    width = _check_sweep_args(k, width, chunk_rows, top)
     if per_leading and len(parts) < 2:
         raise ValueError("per_leading needs at least two parts")
     total = region_count(parts, min_gap)
-    act = torch.nn.functional.softplus if task_mode == "regress" else torch.sigmoid
     model.eval()
     dev = model.layer_norm1.weight.device
     if total == 0:
@@ -1746,26 +1609,15 @@ def region_sweep(model, parts, min_gap: int, top: int, chunk_rows: int = 1 << 20
         sel = SegTopK(A, K, seg_len, chunk_rows, dev)
     else:
         sel = TopK(min(top, total), chunk_rows, dev)
-    buf = torch.empty(chunk_rows * width, dtype=torch.long, device=dev)
-    fbuf = torch.empty(chunk_rows, dtype=torch.int32, device=dev)
-    n_inv = torch.zeros((), dtype=torch.long, device=dev)
-    n_exc = torch.zeros((), dtype=torch.long, device=dev)
-    with torch.no_grad(), model.deferred_id_check(), _lib.option("disable_small_batch"):      # as kway_sweep: one forward route
-        for g0 in range(0, total, chunk_rows):
-            x, flag = region_rows(parts, min_gap, rank0=g0, count=min(chunk_rows, total - g0), width=width, out=buf, flag_out=fbuf)
-            logits = model(x).reshape(-1)
-            skip = flag != 0
-            n_inv += skip.sum()
-            if exclude is not None:
-                known = exclude.contains(x)
-                n_exc += (known & ~skip).sum()
-                skip = skip | known
+    tally = _tally(dev, "n_invalid", "n_excluded")
+    rows = lambda g0, count, buf, fbuf: region_rows(parts, min_gap, rank0=g0, count=count, width=width, out=buf, flag_out=fbuf)
+    with _pinned(model):
+        for g0, _, logits, skip, _ in _chunks(model, total, chunk_rows, _buffers(chunk_rows, width, dev), rows, exclude, tally):
             sel.update(logits, g0, skip)
     if not per_leading:
         logit, rank = sel.result()
         rows, _ = region_rows(parts, min_gap, ranks=rank, width=width, device=dev)
-        return {"rows": rows, "logit": logit, "proba": act(logit), "rank": rank, "n_candidates": total, "n_invalid": int(n_inv.item()),
-                "n_excluded": int(n_exc.item())}
+        return {"rows": rows, "logit": logit, "proba": act(logit), "rank": rank, "n_candidates": total, **_counted(tally)}
     logit, rank, count = sel.read()
     rows, _ = region_rows(parts, min_gap, ranks=rank, width=width, device=dev)
     if ms[0] == 1:
@@ -1775,7 +1627,7 @@ def region_sweep(model, parts, min_gap: int, top: int, chunk_rows: int = 1 << 20
         leading = region_rows(parts, min_gap, ranks=first, device=dev)[0][:, :ms[0]].contiguous()
     proba = torch.where(rank >= 0, act(logit), torch.zeros_like(logit))
     return {"rows": rows.view(A, K, width), "logit": logit, "proba": proba, "rank": rank, "count": count, "leading": leading,
-            "n_candidates": total, "n_invalid": int(n_inv.item()), "n_excluded": int(n_exc.item())}
+            "n_candidates": total, **_counted(tally)}
 
 
 def region_map_bound(parts, min_gap: int, rows_part: int, cols_part: int) -> int:
@@ -1792,7 +1644,7 @@ def region_map_bound(parts, min_gap: int, rows_part: int, cols_part: int) -> int
 
 def region_map(model, parts, min_gap: int, rows_part: int, cols_part: int, chunk_rows: Optional[int] = 1 << 20, width: Optional[int] = None,
                exclude=None, task_mode: str = "class", threshold: float = 0.5, planes="all", value_max: Optional[float] = None) -> dict:
-    """Score every candidate of a multi-region sweep (region_sweep's candidates, in its order, through its loop) and project the
+    """Score every candidate of a multi-region sweep (region_sweep's candidates, in its order, through the same loop) and project the
     probabilities onto pairs of bins, as kway_map does.  ``rows_part`` != ``cols_part`` (indices into ``parts``) gives the rectangular
     map [n_r, n_c] between the bins of two parts -- with parts on two chromosomes, the inter-chromosomal pair map; ``rows_part`` ==
     ``cols_part`` (a part with m >= 2) gives the symmetric map over that part's region (mirrored, zero diagonal).  Invalid candidates and
@@ -1801,14 +1653,11 @@ def region_map(model, parts, min_gap: int, rows_part: int, cols_part: int, chunk
     depend on ``chunk_rows`` (None: one chunk), bit for bit.
 
     Returns the planes (device tensors) and the integers ``n_candidates``, ``n_invalid``, ``n_excluded`` and ``n_rejected``."""
-    if task_mode not in ("class", "regress"):
-        raise ValueError("task_mode must be 'class' or 'regress'")
+    act = _activation(task_mode)
     los, ns, ms, counts, k = _region_parts(parts, min_gap)
     parts = [(lo, lo + n, m) for lo, n, m in zip(los, ns, ms)]
     min_gap = int(min_gap)
-    width = int(k if width is None else width)
-    if not k <= width <= _lib.MAX_L:
-        raise ValueError(f"width must be in [k, {_lib.MAX_L}]")
+    width = _check_width(k, width)
     total = region_count(parts, min_gap)
     chunk_rows = max(total, 1) if chunk_rows is None else int(chunk_rows)
     if chunk_rows < 1:
@@ -1821,9 +1670,9 @@ def region_map(model, parts, min_gap: int, rows_part: int, cols_part: int, chunk
     if task_mode == "regress":
         if value_max is None:
             raise ValueError("task_mode 'regress' needs value_max: the largest value a candidate may contribute")
-        vmax, act = float(value_max), torch.nn.functional.softplus
+        vmax = float(value_max)
     else:
-        vmax, act = 1.0, torch.sigmoid
+        vmax = 1.0
     if not 0.0 < vmax <= float(1 << 20):
         raise ValueError("value_max must be in (0, 2^20]")
     mask = _plane_mask(planes)
@@ -1841,22 +1690,13 @@ def region_map(model, parts, min_gap: int, rows_part: int, cols_part: int, chunk
         return out
     chunk_rows = min(chunk_rows, total, (1 << 31) - 1)
     pm = PairMap((los[r], ns[r]), (los[c], ns[c]), mask, vmax=vmax, threshold=threshold, device=dev)
-    buf = torch.empty(chunk_rows * width, dtype=torch.long, device=dev)
-    fbuf = torch.empty(chunk_rows, dtype=torch.int32, device=dev)
-    n_inv = torch.zeros((), dtype=torch.long, device=dev)
-    n_exc = torch.zeros((), dtype=torch.long, device=dev)
-    with torch.no_grad(), model.deferred_id_check(), _lib.option("disable_small_batch"):      # as kway_sweep: one forward route
-        for g0 in range(0, total, chunk_rows):
-            x, flag = region_rows(parts, min_gap, rank0=g0, count=min(chunk_rows, total - g0), width=width, out=buf, flag_out=fbuf)
-            value = act(model(x).reshape(-1))
-            skip = flag != 0
-            n_inv += skip.sum()
-            if exclude is not None:
-                known = exclude.contains(x)
-                n_exc += (known & ~skip).sum()
-                skip = skip | known
-            pm.update(x, value, skip)
+    tally = _tally(dev, "n_invalid", "n_excluded")
+    rows = lambda g0, count, buf, fbuf: region_rows(parts, min_gap, rank0=g0, count=count, width=width, out=buf, flag_out=fbuf)
+    value = lambda g0, x: act(model(x).reshape(-1))                      # a map takes values, not logits
+    with _pinned(model):
+        for _, x, v, skip, _ in _chunks(model, total, chunk_rows, _buffers(chunk_rows, width, dev), rows, exclude, tally, value):
+            pm.update(x, v, skip)
     out = pm.result()
     out.pop("n_rows")
-    out.update(n_candidates=total, n_invalid=int(n_inv.item()), n_excluded=int(n_exc.item()), n_rejected=int(out["n_rejected"].item()))
+    out.update(n_candidates=total, **_counted(tally), n_rejected=int(out["n_rejected"].item()))
     return out
