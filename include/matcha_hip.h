@@ -554,7 +554,9 @@ typedef struct matcha_gemm_epilogue {
 } matcha_gemm_epilogue;
 
 /* f32 MFMA GEMM. For TN, `ws` must hold matcha_gemm_tn_workspace_bytes(M,N,R) bytes; `colsum` (may be
- * NULL) additionally receives sum_r A[r,m] (bias gradient), accumulated like C. */
+ * NULL) additionally receives sum_r A[r,m] (bias gradient), accumulated like C.
+ * The contraction length (K; R for TN) must be >= 1 and M, N >= 0: anything else is MATCHA_EINVAL before any launch
+ * (an empty sum has no defined epilogue here).  M == 0 or N == 0 is a no-op that returns MATCHA_OK. */
 size_t matcha_gemm_tn_workspace_bytes(int64_t M, int64_t N, int64_t R);
 int matcha_gemm(int32_t op, const float* A, const float* B, float* C, int64_t M, int64_t N, int64_t K,
                 const matcha_gemm_epilogue* epi, float* colsum, const int64_t* b_row_gather,

@@ -392,6 +392,10 @@ extern "C" int matcha_gemm(int32_t op, const float* A, const float* B, float* C,
                            const matcha_gemm_epilogue* epi, float* colsum, const int64_t* b_row_gather,
                            void* ws, size_t ws_bytes, matcha_stream_t stream) {
   MATCHA_CHECK_ARG(A && B && C, "matcha_gemm: null operand");
+  // an empty contraction has no defined result here (the staged kernel would run zero steps and leave C unwritten, the direct one would
+  // write epilogue(0)): refused, like negative extents, before any launch.  M == 0 or N == 0 stays a no-op.
+  MATCHA_CHECK_ARG(M >= 0 && N >= 0, "matcha_gemm: negative extent M=%lld N=%lld", (long long)M, (long long)N);
+  MATCHA_CHECK_ARG(K >= 1, "matcha_gemm: contraction length %lld < 1", (long long)K);
   hipStream_t st = (hipStream_t)stream;
   if (op == MATCHA_GEMM_TN) {
     const bool acc = epi && (epi->flags & MATCHA_EPI_ACCUM);

@@ -169,6 +169,18 @@ static void check_entry_point_errors() {
   CHECK(matcha_ragged_plan(x, 8, 3, 100, nullptr, ws, 64, &view, nullptr) == MATCHA_ENOMEM);
   CHECK(matcha_ragged_plan(x, 8, 9, 100, nullptr, ws, need, &view, nullptr) == MATCHA_EINVAL);
   CHECK(matcha_gemm(7, logits, logits, logits, 8, 8, 8, nullptr, nullptr, nullptr, nullptr, 0, nullptr) != MATCHA_OK);
+  // an empty or negative contraction and negative extents are refused before any launch, for every op; M == 0 or N == 0 is a no-op
+  for (int op = MATCHA_GEMM_NT; op <= MATCHA_GEMM_TN; ++op) {
+    CHECK(matcha_gemm(op, logits, logits, logits, 8, 8, 0, nullptr, nullptr, nullptr, ws, need, nullptr) == MATCHA_EINVAL);
+    CHECK(strstr(matcha_last_error(), "contraction") != nullptr);
+    CHECK(matcha_gemm(op, logits, logits, logits, 8, 8, -3, nullptr, nullptr, nullptr, ws, need, nullptr) == MATCHA_EINVAL);
+    CHECK(matcha_gemm(op, logits, logits, logits, -1, 8, 8, nullptr, nullptr, nullptr, ws, need, nullptr) == MATCHA_EINVAL);
+    CHECK(matcha_gemm(op, logits, logits, logits, 8, -1, 8, nullptr, nullptr, nullptr, ws, need, nullptr) == MATCHA_EINVAL);
+    CHECK(matcha_gemm(op, logits, logits, logits, 0, 8, 8, nullptr, nullptr, nullptr, ws, need, nullptr) == MATCHA_OK);
+    CHECK(matcha_gemm(op, logits, logits, logits, 8, 0, 8, nullptr, nullptr, nullptr, ws, need, nullptr) == MATCHA_OK);
+    CHECK(matcha_gemm(op, logits, logits, logits, 0, 0, 0, nullptr, nullptr, nullptr, ws, need, nullptr) == MATCHA_EINVAL);
+  }
+  CHECK(matcha_gemm(MATCHA_GEMM_NT, nullptr, logits, logits, 8, 8, 8, nullptr, nullptr, nullptr, nullptr, 0, nullptr) == MATCHA_EINVAL);
   CHECK(matcha_embed_fwd(nullptr, 8, 64, nullptr, nullptr, nullptr, 24, nullptr, nullptr, nullptr, nullptr) == MATCHA_EINVAL);
   CHECK(matcha_quantile_uniform(nullptr, 10, 1000, nullptr, nullptr, nullptr, 0, nullptr) != MATCHA_OK);
   CHECK(matcha_zscore_rows(nullptr, 4, 4, nullptr) != MATCHA_OK);
