@@ -500,6 +500,39 @@ int matcha_outlier_plant(const void* set, const int64_t* set_edges, int64_t n_se
                          const int32_t* node2chrom, int32_t n_nodes, const int32_t* chrom_range, int32_t n_chrom,
                          const uint64_t* seed, int64_t n0, int64_t* out, int32_t* planted, int32_t* status, matcha_stream_t stream);
 
+/* Biased second-order random walks over the hypergraph (the reference's History_version/Code/random_walk_hyper.py): walks
+ * w0 <= w < w1, walk w starting at nodes[w % n_start], out int32 [(w1 - w0), walk_length] (row w - w0), node ids 0 .. n_nodes.
+ * Tables (matcha_amd/walk.py builds them): inc_ptr int64 [n_nodes + 2], and per incidence (edge e of node v, c another node of e) the
+ * neighbour inc_nb and inc_cum, the inclusive prefix WITHIN the node of the integer weight max(1, rint(2^40 deg(c)^-1/2 / |e|)); the
+ * pair and the triple set are tables of matcha_hashset_build over all 2- and 3-subsets of the hyperedges (n_*_edges == 0: no such
+ * subset, buffers may be NULL); thresholds is a HOST int64[3] for the classes back (1/p), pair (1) and far (1/q): floor(2^32 alpha /
+ * alpha_max), 2^32 = accepts always.  Counter RNG of oracle/rng.py, stream 19, hi = w, lo = step << 18 | trial << 2 | draw.  Step s >= 1
+ * from dst (previous node src):
+ *   proposal   c = inc_nb[first i with inc_cum[i] > mulhi64(rand64(draws 0, 1), the node's total)];  step 1 takes it;
+ *   class      back if c == src or {src, dst, c} is in the triple set, else pair if {src, c} is in the pair set, else far;
+ *   accepted   when rand(draw 2) < thresholds[class]; otherwise the next trial, at most max_trials (1 .. 65536): then the last
+ *              proposal stands and status[1] += 1 (status: optional device int32[4]).
+ * A node without incidences repeats itself.  A start outside 0 .. n_nodes gives an all-zero row and status[0] |= MATCHA_STATUS_BAD_ID.
+ * walk_length 1 .. 16384, 0 <= w0, w1 < 2^31.  hyper_walk_kernel: one lane per walk. */
+int matcha_hyper_walk(const int64_t* inc_ptr, const int32_t* inc_nb, const uint64_t* inc_cum, int32_t n_nodes,
+                      const void* pair_set, const int64_t* pair_edges, int64_t n_pair_edges, int32_t L_pair,
+                      const void* triple_set, const int64_t* triple_edges, int64_t n_triple_edges, int32_t L_triple,
+                      const int64_t* thresholds, const int32_t* nodes, int64_t n_start, int64_t w0, int64_t w1,
+                      int32_t walk_length, int32_t max_trials, const uint64_t* seed, int32_t* out, int32_t* status,
+                      matcha_stream_t stream);
+
+/* One pass of skip-gram with negative sampling (word2vec) over walks w0 <= w < w1 of walks int32 [n_walks, walk_length] (ids 1 .. n_nodes):
+ * syn0 / syn1 float [n_nodes + 1, d], d = 64, 128 or 256, updated in place with float atomics -- NOT bitwise reproducible from run to run.
+ * noise_cum uint64 [n_nodes + 1]: the inclusive prefix of the nodes' integer noise weights, entry 0 (no node) = 0.  The global position of
+ * (w, i) is g = g_base + w walk_length + i (g_base = epoch * n_walks * walk_length) of g_total <= 2^32 positions in all; the rule per
+ * position is stated at the top of csrc/sgns.hip (stream 20, hi = g).  window 1 .. 1024, negative 0 .. 32, lr0 >= lr1 >= 0.  An id outside
+ * 1 .. n_nodes trains nothing and sets status[0] |= MATCHA_STATUS_BAD_ID (status: optional device int32[4]).  sgns_kernel: one wavefront
+ * per position. */
+int matcha_sgns_epoch(const int32_t* walks, int64_t n_walks, int32_t walk_length, int64_t w0, int64_t w1, int32_t n_nodes,
+                      int32_t d, float* syn0, float* syn1, const uint64_t* noise_cum, int32_t window, int32_t negative,
+                      double lr0, double lr1, int64_t g_base, int64_t g_total, const uint64_t* seed, int32_t* status,
+                      matcha_stream_t stream);
+
 /* The bookkeeping of one step of the reference's epoch loop (main.py:155-188) on the device, so that an epoch can replay one captured
  * step (matcha_amd/train.py).  `it` is a device int64 step counter.
  * matcha_step_select (main.py:160-161, Modules.py:192): x[0:P] = pos[it*P .. it*P+P) (rows of the epoch's shuffled positives,

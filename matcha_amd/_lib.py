@@ -122,6 +122,9 @@ SIGNATURES = {
     "matcha_neg_sample_long": (C.c_int, [_fp, _fp, _I64, _I32, _fp, _I64, _I32, _I32, _I32, _fp, _I32, _fp, _I32, _fp, _fp, _fp, _fp]),
     "matcha_outlier_plant": (C.c_int, [_fp, _fp, _I64, _I32, _fp, _fp, _I64, _I32, _fp, _I64, _I32, _I32, _I32, _I32, _fp, _I32, _fp, _I32,
                                        _fp, _I64, _fp, _fp, _fp, _fp]),
+    "matcha_hyper_walk": (C.c_int, [_fp, _fp, _fp, _I32, _fp, _fp, _I64, _I32, _fp, _fp, _I64, _I32, C.POINTER(C.c_int64), _fp, _I64, _I64, _I64,
+                                    _I32, _I32, _fp, _fp, _fp, _fp]),
+    "matcha_sgns_epoch": (C.c_int, [_fp, _I64, _I32, _I64, _I64, _I32, _I32, _fp, _fp, _fp, _I32, _I32, _D, _D, _I64, _I64, _fp, _fp, _fp]),
     "matcha_locus_scores": (C.c_int, [C.POINTER(Shape), C.POINTER(Tensors), C.POINTER(Frozen), C.POINTER(StepOpts), _fp, _I64, _I32,
                                       _fp, _fp, _I32, _fp, _fp, _fp, _SZ, _fp]),
     "matcha_gemm_tn_workspace_bytes": (_SZ, [_I64, _I64, _I64]),

@@ -95,7 +95,24 @@ __host__ __device__ __forceinline__ uint32_t dropout_threshold(float p) {
   double t = (double)p * 4294967296.0;
   return t >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)t;
 }
-constexpr uint32_t kStreamDropAdj = 1, kStreamDropFc1 = 2, kStreamDropPff = 3, kStreamNeg = 16, kStreamOutlier = 18;
+constexpr uint32_t kStreamDropAdj = 1, kStreamDropFc1 = 2, kStreamDropPff = 3, kStreamNeg = 16, kStreamOutlier = 18,
+                   kStreamWalk = 19, kStreamSgns = 20;
+
+// ---- inverse CDF over an integer cumulative table (walk.hip, sgns.hip) -------------------------
+// cum[0 .. n) is an inclusive prefix sum of positive integer weights, total = cum[n - 1].  The draw is r = floor(u * total / 2^64) for a
+// 64-bit uniform u, the answer the first i with cum[i] > r: index i is drawn with probability (cum[i] - cum[i - 1]) / total up to 2^-64.
+__device__ __forceinline__ uint64_t rng_u64(uint32_t key, uint32_t hi, uint32_t lo) {
+  return ((uint64_t)rng_u32(key, hi, lo) << 32) | (uint64_t)rng_u32(key, hi, lo + 1u);
+}
+__device__ __forceinline__ int64_t cum_draw(const uint64_t* __restrict__ cum, int64_t n, uint64_t u) {
+  const uint64_t r = __umul64hi(u, cum[n - 1]);
+  int64_t lo = 0, hi = n - 1;                          // the answer lies in [lo, hi]: cum[n - 1] = total > r
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (cum[mid] > r) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
 
 // ---- wave-level reductions over groups of 2^k adjacent lanes -----------------------------------
 template <int WIDTH>

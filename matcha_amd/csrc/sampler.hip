@@ -12,21 +12,12 @@
 //         replacement : rand(key, n, 8*trial + position)     -> start + floor(u * (end - start))    (:405-407)
 //                       (rows of more than 8 columns, neg_sample_long_kernel: 32*trial + position)
 #include "kernels.hpp"
+#include "set_probe.hpp"
 
 namespace matcha {
 
-// Set layout (round 6): 64 int32 header words (words 0..1 = capacity, a power of two), then `capacity` slots of 8 bytes: {int32 index of the
-// stored hyperedge in the edge list (-1 = empty), uint32 tag = upper 32 bits of the row's hash}.  A probe reads a WINDOW of eight consecutive
-// slots in one round trip (linear probing: the probe chain of a row lies inside its window with probability 1 - load^8) and compares tags;
-// only a tag match costs a second trip (the stored row itself: exactness does not rest on the tag).  Rounds 1-5 kept bare indices and loaded a
-// stored row per occupied slot: slot -> row -> next slot -> row ..., two dependent trips per probe, and the slowest lane of a wavefront paid
-// a chain of ~5 probes -- the negative sampler was a chain of 10+ global round trips (18.8 us for 288 negatives).
-constexpr int kSetHeader = 64;         // int32 words reserved in front of the slots (word 0..1 = capacity)
-constexpr int kSetWindow = 8;          // slots per probe window
+// The set's layout and its one-lane probes for rows of two and three nodes: set_probe.hpp.
 constexpr int kMaxTrials = 1 << 16;
-struct SetSlot { int32_t idx; uint32_t tag; };
-static_assert(sizeof(SetSlot) == 8, "a slot is one 8-byte word (inserted with a 64-bit compare-and-swap)");
-__device__ __forceinline__ uint32_t row_tag(uint64_t h) { return (uint32_t)(h >> 32); }
 
 __device__ __forceinline__ uint64_t row_hash(const int64_t* __restrict__ row, int L) {
   uint64_t h = 0x9E3779B97F4A7C15ull;
@@ -379,29 +370,7 @@ __global__ __launch_bounds__(256) void neg_sample_long_kernel(const int32_t* __r
 }
 
 // ---- planted outliers (matcha_outlier_plant; the reference's generate_outlier_part, History_version/Code/utils.py:184-233) -------------
-// Is the pair (lo, hi), 1 <= lo < hi, a row of the pair set?  row_hash / set_contains above for a row of two nodes, on two registers: one lane,
-// one probe chain (the reference's dict_pair lookup).
-__device__ __forceinline__ bool pair_contains(const int32_t* __restrict__ set, const int64_t* __restrict__ edges, int L_set, int64_t lo, int64_t hi) {
-  const int64_t cap = reinterpret_cast<const int64_t*>(set)[0];
-  const unsigned long long* slots = reinterpret_cast<const unsigned long long*>(set + kSetHeader);
-  uint64_t h = 0x9E3779B97F4A7C15ull;
-  h ^= (uint64_t)lo + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2); h *= 0xBF58476D1CE4E5B9ull; h ^= h >> 31;
-  h ^= (uint64_t)hi + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2); h *= 0xBF58476D1CE4E5B9ull; h ^= h >> 31;
-  const uint32_t tag = row_tag(h);
-  uint64_t p = h & (uint64_t)(cap - 1);
-  for (int64_t probe = 0; probe < cap; ++probe) {
-    const unsigned long long w = slots[p];
-    const int32_t idx = (int32_t)(uint32_t)(w & 0xFFFFFFFFull);
-    if (idx < 0) return false;
-    if ((uint32_t)(w >> 32) == tag) {
-      const int64_t* row = edges + (int64_t)idx * L_set;
-      if (row[0] == lo && row[1] == hi && (L_set == 2 || row[2] == 0)) return true;
-    }
-    p = (p + 1) & (uint64_t)(cap - 1);
-  }
-  return false;
-}
-
+// (the pair-set probe, pair_contains: set_probe.hpp)
 // One group of 32 lanes per output row, lane i = position i, like neg_sample_long_kernel and under its rule for cross-lane operations: every
 // shuffle and ballot is executed by all 64 lanes, a group with nothing left to do is predicated off (`active`, `ok`).  Local row i is global
 // row n = n0 + i, a copy of positive i / draws (copy n % draws of it where n0 is a multiple of draws).  The plant rule is stated in include/matcha_hip.h.

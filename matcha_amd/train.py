@@ -635,9 +635,49 @@ def init_distributed(backend: Optional[str] = None) -> Tuple[int, int, str]:
     return torch.distributed.get_rank(), world, f"cuda:{local}"
 
 
+def _table_init(table_init: str, data: np.ndarray, N: int, d: int, device: str, rank: int, world: int, walk_opts: dict) -> torch.Tensor:
+    """float32 [N + 1, d] for Wrap_Embedding.weight: StandardScaler over the N node rows, row 0 zero (main_SPRITE.py:753-765).  The walk's
+    seed, unless ``walk_opts`` names one, is drawn from numpy's global generator -- on every rank, so the rank-shared stream stays shared.
+    Under data parallel rank 0 computes; it broadcasts whether it succeeded before it broadcasts the table, so a failure raises on every
+    rank instead of leaving the others waiting."""
+    from . import walk as W
+    opts = dict(walk_opts)
+    opts.setdefault("seed", int(np.random.randint(1 << 31)))
+    table = torch.zeros(N + 1, d, dtype=torch.float32, device=device)
+    error = None
+    if rank == 0:
+        try:
+            if table_init == "walk":
+                table = W.walk_embeddings(torch.from_numpy(np.ascontiguousarray(data).astype(np.int64)).to(device), N, d, **opts)
+            else:
+                A = torch.from_numpy(np.load(table_init).astype(np.float32)).to(device)
+                if tuple(A.shape) != (N, d):
+                    raise ValueError("%s holds %s, the table needs [%d, %d]" % (table_init, tuple(A.shape), N, d))
+                table[1:] = W.standard_scale(A)
+        except Exception as e:                       # noqa: BLE001  (re-raised below, on every rank)
+            if world == 1:
+                raise
+            error = e
+    if world > 1:
+        ok = torch.tensor([0 if error is not None else 1], dtype=torch.int64, device=device)
+        torch.distributed.broadcast(ok, 0)
+        if int(ok.item()) == 0:
+            raise RuntimeError("table_init=%r failed on rank 0%s" % (table_init, ": %r" % (error,) if error is not None else ""))
+        torch.distributed.broadcast(table.contiguous(), 0)
+    return table
+
+
 def run(config: dict, front_end: str = "adj", epochs1: int = 3, epochs2: int = 30, batches_per_epoch: int = 1000, device: str = "cuda",
-        emb_path: Optional[str] = "../embeddings.npy", log=print, deterministic: bool = False, task_mode: str = "class") -> Classifier:
-    """The script body of main.py:516-685 (on every rank of a data-parallel launch, see the module docstring)."""
+        emb_path: Optional[str] = "../embeddings.npy", log=print, deterministic: bool = False, task_mode: str = "class",
+        table_init: str = "random", walk_opts: Optional[dict] = None) -> Classifier:
+    """The script body of main.py:516-685 (on every rank of a data-parallel launch, see the module docstring).
+
+    ``table_init`` (table front end): "random" -- nn.Embedding's normal draw; "walk" -- the reference's ``--feature walk`` set-up
+    (History_version/Code/main_SPRITE.py:637-765): hypergraph walks over the positives + skip-gram, standard-scaled
+    (matcha_amd.walk.walk_embeddings with ``walk_opts``; rank 0 computes, the others receive); or the path of a .npy of unscaled vectors
+    [N, d] (what ``python -m matcha_amd.walk -o`` writes), scaled the same way."""
+    if table_init != "random" and front_end != "table":
+        raise ValueError("table_init=%r needs the table front end" % (table_init,))
     rank, world = _dist()
     if world > 1:
         # numpy's global generator drives the split, the epoch shuffles and random_chrom: one seed for all ranks
@@ -673,6 +713,8 @@ def run(config: dict, front_end: str = "adj", epochs1: int = 3, epochs2: int = 3
         ne = MultipleEmbedding(feats, d, False, torch.as_tensor(np.cumsum(num)), chrom_range, inter)   # main.py:609-613
     else:
         ne = Wrap_Embedding(N + 1, d, padding_idx=0)
+        if table_init != "random":
+            ne.weight = torch.nn.Parameter(_table_init(table_init, data, N, d, device, rank, world, walk_opts or {}))   # main_SPRITE.py:765
     model = Classifier(n_head=8, d_model=d, d_k=d, d_v=d, node_embedding=ne, diag_mask=True, bottle_neck=d, attribute_dict=attr).to(device)
     save_embeddings(model, N, emb_path if rank == 0 else None)                     # main.py:625 (every rank: keeps the numpy stream shared)
 
@@ -703,10 +745,22 @@ def main(argv=None):
     ap.add_argument("--deterministic", action="store_true", help="table front end: sorted embedding backward (bitwise reproducible table)")
     ap.add_argument("--task-mode", choices=["class", "regress"], default="class",
                     help="main.py:532: 'class' = weighted BCE on pos / neg labels; 'regress' = learn each k-mer's weight (softplus MSE)")
+    ap.add_argument("--table-init", default="random",
+                    help="table front end: 'random' (nn.Embedding's normal draw), 'walk' (hypergraph walks + skip-gram over the positives, "
+                         "standard-scaled: the reference's --feature walk; its skip-gram pass uses float atomics and is not bitwise "
+                         "reproducible from run to run) or a .npy of unscaled vectors [N, d] written by python -m matcha_amd.walk")
+    ap.add_argument("--walk-length", type=int, default=80)
+    ap.add_argument("--num-walks", type=int, default=40)
+    ap.add_argument("--window", type=int, default=10)
+    ap.add_argument("--p", type=float, default=2.0)
+    ap.add_argument("--q", type=float, default=0.25)
+    ap.add_argument("--walk-seed", type=int, default=None, help="seed of the walks and the skip-gram pass (default: drawn from numpy's generator)")
     a = ap.parse_args(argv)
     rank, world, device = init_distributed()
     run(U.get_config(a.config), a.front_end, a.epochs1, a.epochs2, a.batches_per_epoch, device=device, deterministic=a.deterministic,
-        task_mode=a.task_mode)
+        task_mode=a.task_mode, table_init=a.table_init,
+        walk_opts=dict(walk_length=a.walk_length, num_walks=a.num_walks, window=a.window, p=a.p, q=a.q,
+                       **({} if a.walk_seed is None else {"seed": a.walk_seed})))
     if world > 1:
         torch.distributed.destroy_process_group()
 
