@@ -83,6 +83,13 @@ int matcha_profile_read(double* total_ms, int64_t* launches, double* work);
 int matcha_launch_log(int32_t on);
 int matcha_launch_log_read(char* out, size_t cap);
 
+/* Route record: which kernel route did the last forward that a backward may follow take on workspace `ws`?  Writes one "field value\n"
+ * line per field of the record the backward replays (0 / 1; `fwd_values`: where the embed_dim-64 large-batch forward took the heads'
+ * value rows y_h = M_h x_hat from -- 1 a product per token inside the kernel, 2 a product per token on the node route with the r rows
+ * gathered, 3 gathered from the per-node value table, 0 another kernel ran the forward).  MATCHA_EINVAL when no forward is on record
+ * (none ran, it kept nothing, or a backward consumed it), MATCHA_ENOMEM if `cap` is too small.  Host state only: no launch, no sync. */
+int matcha_route_read(const void* ws, char* out, size_t cap);
+
 /* A/B switches for tests and profiling.  Each option is read from the environment variable MATCHA_<NAME> (upper case) ONCE,
  * when the library is loaded, and can be changed afterwards only through matcha_set_option -- no entry point reads the
  * environment per call.  NINE switches: "disable_fused" (1 = layer-by-layer kernels at every embed_dim, also instead of the fused

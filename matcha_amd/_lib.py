@@ -75,6 +75,7 @@ SIGNATURES = {
     "matcha_profile_read": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "matcha_launch_log": (C.c_int, [_I32]),
     "matcha_launch_log_read": (C.c_int, [C.c_char_p, _SZ]),
+    "matcha_route_read": (C.c_int, [_fp, C.c_char_p, _SZ]),
     "matcha_workspace_bytes": (_SZ, [C.POINTER(Shape), _I64, _I32]),
     "matcha_workspace_bytes_forward": (_SZ, [C.POINTER(Shape), _I64, _I32]),
     "matcha_forward": (C.c_int, [C.POINTER(Shape), C.POINTER(Tensors), C.POINTER(Frozen), C.POINTER(StepOpts), _fp, _I64,
@@ -282,6 +283,13 @@ class launch_log:
         for line in buf.value.decode().splitlines():
             name, n = line.rsplit(" ", 1)
             self.counts[name] = int(n)
+
+
+def route_record(ws) -> dict:
+    """{field: int} of the kernel route the last training forward on workspace tensor ``ws`` recorded (matcha_route_read)."""
+    buf = C.create_string_buffer(1 << 10)
+    check(load().matcha_route_read(ptr(ws), buf, len(buf)), "matcha_route_read")
+    return {name: int(v) for name, v in (line.rsplit(" ", 1) for line in buf.value.decode().splitlines())}
 
 
 def raise_on_status(status_host, what: str):

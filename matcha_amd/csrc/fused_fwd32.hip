@@ -1,6 +1,6 @@
 // Wave-independent fused forward for embed_dim 64, merged heads.  The mathematics of Modules.py:519-572,
-// :353-376, :290-311 and main.py:56 with the per-head products merged (r = B_h x_hat + b_h, s_ij = r_i . x_hat_j, z_i = sum_j p_ij x_hat_j,
-// dyn += M_h z_i), decomposed as
+// :353-376, :290-311 and main.py:56 with the per-head products merged (r = B_h x_hat + b_h, s_ij = r_i . x_hat_j, y_j = M_h x_hat_j,
+// dyn_i += sum_j p_ij y_j -- the association of M_h (sum_j p_ij x_hat_j) that needs no product behind the attention), decomposed as
 //
 //   ONE WAVEFRONT = ONE WORKGROUP = one HALF TILE: <= 31 real tokens of whole hyperedges + the shared padding token as local row n
 //   (ragged.hip: half_meta).  Nothing is shared between wavefronts, so there is no workgroup barrier anywhere (the four-wave tile kernel
@@ -9,8 +9,8 @@
 //   Layout "FL": lane (r, h) owns token row r and the 32 features  f(e) = 32 wc + 8 g + 4 h + j,  e = 16 wc + 4 g + j  -- exactly what
 //   the 32x32x2 MFMA leaves in a lane when a projection is computed as the TRANSPOSED product  D[feature][token] = W . x^T, and exactly
 //   what the next product needs as its token-side operand.  r, z, dyn, Y, H1, H2 and their gradients therefore never leave the
-//   registers; only the x_hat rows (keys = values of every head, read by the other tokens of a hyperedge) and the weight-gradient
-//   operands pass through the wave's two private LDS tiles (2 x 8.5 KB: eight wavefronts per CU, two per SIMD, limited by the 256
+//   registers; only the x_hat rows (the keys of every head), one head's value rows y = M_h x_hat at a time (both read by the other tokens of a
+//   hyperedge) and the weight-gradient operands pass through the wave's two private LDS tiles (2 x 8.5 KB: eight wavefronts per CU, two per SIMD, limited by the 256
 //   registers).
 //
 //   Weights are STREAMED FROM L2 in fragment-major order (prep_heads_kernel rewrites them once per step: one coalesced 1 KB load per
@@ -18,7 +18,8 @@
 //   matrix pipe's rate for that pattern with two decoupled waves per SIMD, without any LDS staging.
 //
 //   Attention: two lanes per query token (32 features each), every token of the half tile at once; the dot products' cross-lane part
-//   is ONE v_permlane32_swap instead of three DPP steps; cut into pieces that ride between the MFMAs of the next head's r product.
+//   is ONE v_permlane32_swap instead of three DPP steps; cut into pieces that ride between the MFMAs of the next head's r and y products
+//   (on the node route those rows are gathered per node instead, and with both tables the head loop runs no product at all).
 //
 //   A training forward leaves, per (half tile, head), the r rows as the lane's accumulator registers + the probabilities [32][8]
 //   (kImgRecH floats): fused_bwdh_kernel walks the same half tiles and reloads them thread for thread.
@@ -269,6 +270,7 @@ __device__ __forceinline__ FL fl_zero() {
 //            diagonal is REPLACED, Modules.py:443-445)           ->  r_i = B_h x_i + b_h,   s_ij = r_i . x_j
 //   output   sum_j p_ij v_j = W'v (sum_j p_ij x_j) + cv  (the probabilities, padding slots included, sum to 1)
 //            dyn += Wfc1_h O_i                                   ->  z_i = sum_j p_ij x_j,  dyn += M_h z_i,   M_h = Wfc1_h W'v_h
+//            (fused_fwd32h_kernel computes it so; fused_fwd32_kernel as dyn += sum_j p_ij (M_h x_j): the rows M_h x_j depend on (token, head) alone)
 // (x = the LayerNorm-normalised row, the same for every head: it is the key AND the value of every head, written to LDS once per tile.)
 // The constants Wfc1_h cv_h join the fc1 bias.  prep_heads_kernel builds B_h, b_h, M_h and that bias once per step.
 // ---- the per-step weight forms (prep_heads.hpp): stand-alone launch for the paths whose front end is not front_fwd_kernel ----------------
@@ -294,11 +296,13 @@ struct Fwd32Args {
   float* qkv;         // training: the record per (half tile, head) -- this wavefront's own r rows + probabilities, kImgRecH floats (fused_bwdh_kernel)
   float* tail_dh2;    // single-wave kernel, training: [T][64] dH2 rows -- the tail's backward stops behind its LayerNorms, tail_bwd64_kernel does the convolutions
   const float* rn;    // node route, single-wave kernel: the heads' r rows per NODE, [8][rn_rows][64] (node_r_kernel) -- gathered by xrow instead of computed per token
+  const float* vn;    // ... and their value rows y = M_h x_hat, same shape (node_r_kernel's V role; non-null exactly where the route wrote VN): gathered the same way
   int rn_rows;
   float* dxs_node;    // node route, single-wave kernel, training: [rn_rows][64] per-NODE sums of the dXs rows (zeroed by the caller) -- added here by xrow, no row per token
 };
 
-// Merged per-head matrices (two products per head: r = B_h x + b_h, dyn += M_h z).
+// Merged per-head matrices in the y-tile form (4.2): per head r = B_h x_hat + b_h and y = M_h x_hat -- products of the token alone, computed
+// under the attention pieces or gathered per node --, scores r_i . x_hat_j, dyn_i += sum_j p_ij y_j.  No product waits for the attention.
 template <int ML>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void fused_fwd32_kernel(Fwd32Args g) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -322,15 +326,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
   const float inv_temp = 0.125f;
   const bool real = r < n;
 
-  // ---- weight stream: prime the window with the first chunk of R_0; the f32 bias table -> TV (free until the tail) ----
+  // ---- weight stream: every path of the head loop primes the window at the first matrix it consumes, where it first needs it (primed here, the six
+  // fragments lived across the x_hat prologue and went to scratch).  The f32 bias table stays in L2 during the head loop -- TV holds the heads' value
+  // tiles there --; the two rows the tail reads are staged into TV behind the loop ----
   const u32x4* wp;
   u32x4 W_[F32_WIN];
-  W32_PRIME_AT(g.rn ? 2 : 0);          // (r table: the stream starts at M_0)
-  {
-    const f32x4* bsrc = reinterpret_cast<const f32x4*>(g.wfrag + (kNMat + 1) * kFragU4);
-    for (int i4 = lane; i4 < kNBias * 16; i4 += 64) reinterpret_cast<f32x4*>(TV)[i4] = bsrc[i4];
-  }
+  const float* const btab = reinterpret_cast<const float*>(g.wfrag + (kNMat + 1) * kFragU4);
 #define F32_BIAS(ROW) fl_vec(TV + (ROW) * 64 + 4 * h)
+#define F32_BIAS_L2(ROW) fl_vec(btab + (ROW) * 64 + 4 * h)
 
   // ---- x_hat in layout FL straight from global memory ----
   int64_t xoff = F32_ROW();
@@ -440,20 +443,30 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 
   FF_T(0);
   fl_store(krow, xh);
-  FL dyn;
-  if (!g.rn) {
-  // x_hat as three bf16 planes: the token-side operand of all eight r products (x_hat in f32 is dead until the tail, which reads its row back)
-  B3 xs[4];
-  FL_SPLIT(xs[0], xh, 0); FL_SPLIT(xs[1], xh, 1); FL_SPLIT(xs[2], xh, 2); FL_SPLIT(xs[3], xh, 3);
-  F32_WAVE_SYNC();                                    // x_hat rows and the bias table visible (one wavefront = the whole workgroup)
-  dyn = F32_BIAS(kBiasDyn);                           // the merged fc1 bias enters once
-  {
-    // ======================= merged heads: two products per head, keys = values = the x_hat rows (written to TK once) =======================
-    // pieces of head hd (five per step of the NEXT head's r product): score half-dots, softmax, probabilities out, z half-rows
-    FL q = F32_BIAS(kBiasR), o;                       // q: the r rows of the current head; o: z = P x_hat
-    W32_CHAIN_XS(q, xs, true);                        // r_0 = B_0 x_hat + b_0
-    F32_IMG_STORE(q, 0, 0);
-    FF_T(1);
+  // ======================= merged heads: keys = the x_hat rows (TK, written once), values = the rows y_h = M_h x_hat of the SAME tokens (TV, one tile per
+  // head): dyn += sum_j p_ij y_hj + n_pad p_i,pad y_h,pad, real keys in order, then the padding term, heads in order ("y tile").  y_h is a
+  // function of (token, head) -- on the node route of (node, head) -- and not of the attention, so its product rides under the attention pieces or is not
+  // run at all.  Three sources of a head's tile behind wave-uniform branches; every one leaves the bits of node_r_kernel's V role (the same text: FL_SPLIT,
+  // the WB_MMA sequence into a zero accumulator), so the value pieces -- the same text as well -- give the same dyn on every path.
+  // pieces of head hd: score half-dots, softmax, probabilities out (F32_SC_PIECE), then the value half-rows
+#define F32_Y_PIECE(S)                                                                                   \
+  do {                                                                                                   \
+    constexpr int j__ = (S) >> 1, hf__ = (S) & 1;                                                        \
+    if constexpr (j__ <= ML) {                                                                           \
+      const float* rp__ = TV + ro[j__] + 32 * hf__;                                                      \
+      const float w__ = j__ < ML ? p[j__] : padf * p[ML];                                                \
+      const f2 w2__ = {w__, w__};                                                                        \
+      f32x16& oo__ = hf__ ? dyn.hi : dyn.lo;                                                             \
+      _Pragma("unroll") for (int g__ = 0; g__ < 4; ++g__) {                                              \
+        const f32x4 a__ = *reinterpret_cast<const f32x4*>(rp__ + 8 * g__);                               \
+        const f2 u0__ = __builtin_elementwise_fma(w2__, (f2){a__.x, a__.y}, (f2){oo__[4 * g__], oo__[4 * g__ + 1]});     \
+        const f2 u1__ = __builtin_elementwise_fma(w2__, (f2){a__.z, a__.w}, (f2){oo__[4 * g__ + 2], oo__[4 * g__ + 3]}); \
+        oo__[4 * g__] = u0__.x; oo__[4 * g__ + 1] = u0__.y; oo__[4 * g__ + 2] = u1__.x; oo__[4 * g__ + 3] = u1__.y;      \
+      }                                                                                                  \
+      asm volatile("" : "+v"(oo__));                                                                     \
+    }                                                                                                    \
+  } while (0)
+  // the small-batch kernel below keeps z = P x_hat and dyn += M_hd z (one head per wavefront: its product cannot leave the attention's shadow)
 #define F32_Z_PIECE(S)                                                                                   \
   do {                                                                                                   \
     constexpr int j__ = (S) >> 1, hf__ = (S) & 1;                                                        \
@@ -471,63 +484,134 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
       asm volatile("" : "+v"(oo__));                                                                     \
     }                                                                                                    \
   } while (0)
-    // piece index Q: [0, 2 (ML + 1) + 2): the score pieces of F32_SC_PIECE (dots, softmax, probabilities out), then the z half-rows
+#define F32_V_PIECE(S) F32_Y_PIECE(S)
+  // piece index Q: [0, F32_NSC): the score pieces of F32_SC_PIECE (dots, softmax, probabilities out), then the value half-rows
+#define F32_NSC (2 * (ML + 1) + 2)
 #define F32_MG_PIECE(Q)                                                                                  \
   do {                                                                                                   \
     if constexpr ((F32_ABL & 1) != 0) { } else                                                           \
-    if constexpr ((Q) < 2 * (ML + 1) + 2) F32_SC_PIECE(Q); else F32_Z_PIECE((Q) - (2 * (ML + 1) + 2));   \
+    if constexpr ((Q) < F32_NSC) F32_SC_PIECE(Q); else F32_V_PIECE((Q) - F32_NSC);                       \
   } while (0)
-    // ML = 8: 4 ML + 6 = 38 pieces over the eight steps of a product, five per step
+  // ML = 8: 4 ML + 6 = 38 pieces over the eight steps of a product, five per step -- or, with two products per head, the 2 ML + 4 = 20 score pieces over
+  // the r product and the 2 ML + 2 = 18 value pieces over the y product, three per step
 #define F32_MG_ONLY(S) do { F32_MG_PIECE(5 * (S)); F32_MG_PIECE(5 * (S) + 1); F32_MG_PIECE(5 * (S) + 2); F32_MG_PIECE(5 * (S) + 3); F32_MG_PIECE(5 * (S) + 4); } while (0)
-#define F32_MG_STEP(S) do { WB_MMA(acc, xs[(S) >> 1], S); F32_MG_ONLY(S); WB_REFILL(S, true); } while (0)
-    int hd = 0;
-    for (; hd + 1 < MATCHA_N_HEAD; ++hd) {
-      o = fl_zero();
-      {
-        FL acc = F32_BIAS(kBiasR + hd + 1);           // r_{hd+1} = B_{hd+1} x_hat + b_{hd+1}
-        F32_STAGE8(F32_MG_STEP);
-        q = acc;
-        F32_IMG_STORE(q, hd + 1, 0);
-      }
-      FF_T(2);
-      W32_CHAIN(dyn, o, true);                        // dyn += M_hd z
-      FF_T(5);
+  // (the scheduling barrier between the third and the fourth piece keeps at most three pieces' LDS rows in flight: with five the allocator spilled x_hat planes)
+#define F32_MG_STEP(S)                                                                                   \
+  do {                                                                                                   \
+    WB_MMA(acc, xs[(S) >> 1], S);                                                                        \
+    F32_MG_PIECE(5 * (S)); F32_MG_PIECE(5 * (S) + 1); F32_MG_PIECE(5 * (S) + 2);                         \
+    __builtin_amdgcn_sched_barrier(0);                                                                   \
+    F32_MG_PIECE(5 * (S) + 3); F32_MG_PIECE(5 * (S) + 4);                                                \
+    WB_REFILL(S, true);                                                                                  \
+  } while (0)
+#define F32_XS_STEP(S) do { WB_MMA(acc, xs[(S) >> 1], S); WB_REFILL(S, true); } while (0)
+  // (score pieces ONLY under the r product: an index past them is no piece here -- the value pieces wait for the y product)
+#define F32_SC_ONLY(Q) do { if constexpr ((Q) < F32_NSC) F32_MG_PIECE(Q); } while (0)
+#define F32_R_STEP(S) do { WB_MMA(racc, xs[(S) >> 1], S); F32_SC_ONLY(3 * (S)); F32_SC_ONLY(3 * (S) + 1); F32_SC_ONLY(3 * (S) + 2); WB_REFILL(S, true); } while (0)
+#define F32_Y_STEP(S)                                                                                    \
+  do {                                                                                                   \
+    WB_MMA(acc, xs[(S) >> 1], S);                                                                        \
+    F32_MG_PIECE(F32_NSC + 3 * (S)); F32_MG_PIECE(F32_NSC + 3 * (S) + 1); F32_MG_PIECE(F32_NSC + 3 * (S) + 2);                                          \
+    WB_REFILL(S, true);                                                                                  \
+  } while (0)
+  // the eight steps of a product whose window runs on into matrix NEXT of the stream: the last two steps' refills are the first two steps' fragments
+  // of NEXT (the stream's order is R_0 | R_{h+1} M_h | M_7 | the convolutions; the order of use here is another)
+  // (MID4, MID6: statements in front of steps 4 and 6 -- behind the head's score pieces and behind its last piece, where a row can be fetched into
+  // registers that have just died without raising the peak)
+#define F32_STAGE8_TO(MAC, NEXT, MID4, MID6) do { MAC(0); MAC(1); MAC(2); MAC(3); MID4; MAC(4); MAC(5); wp = g.wfrag + (NEXT) * kFragU4; MID6; MAC(6); MAC(7); } while (0)
+  // this lane's row of the next head's value tile -> TV, between the value pieces of two heads (one wavefront is the workgroup)
+#define F32_Y_TILE(V) do { F32_WAVE_SYNC(); fl_store(vrow, V); F32_WAVE_SYNC(); } while (0)
+  FL dyn, q;
+  if (g.vn) {
+    // ---- node route with the r AND the value table (node_r_kernel's two roles): both rows are GATHERED (bit for bit what the products below leave: an
+    // MFMA output column depends on the same column of the token-side operand alone).  No x_hat planes, no weight window, no MFMA in the head loop;
+    // the next head's rows are in flight during this head's pieces
+    F32_WAVE_SYNC();                                  // x_hat rows visible (one wavefront = the whole workgroup)
+    dyn = F32_BIAS_L2(kBiasDyn);                      // the merged fc1 bias enters once
+    const int roff = g.xrow[F32_TOK()] * 64 + 4 * h;
+    const float *rnh = g.rn, *vnh = g.vn;
+    q = fl_load(rnh + roff);
+    {
+      const FL y0 = fl_load(vnh + roff);
+      fl_store(vrow, y0);
     }
-    o = fl_zero();
-    F32_STAGE8(F32_MG_ONLY);
-    FF_T(2);
-    W32_CHAIN(dyn, o, true);
-    FF_T(5);
-  }
-  } else {
-    // ======================= node route with the r table (node_r_kernel): r = B_h x_hat + b_h depends on (node, head) only, so the row is GATHERED
-    // (bit for bit what the product above leaves in `q`: an MFMA output column depends on the same column of the token-side operand alone).  No
-    // x_hat planes, no R_h fragments, no r rows in the record; the next head's row is in flight during this head's attention pieces, in the
-    // registers the r product's accumulator has above; the stream is re-primed from M_h to M_{h+1} (R_{h+2} sits between them)
     F32_WAVE_SYNC();
-    dyn = F32_BIAS(kBiasDyn);
-    int roff = g.xrow[F32_TOK()] * 64 + 4 * h;
-    const float* rnh = g.rn;
-    FL q = fl_load(rnh + roff), o;
     FF_T(1);
-    int hd = 0;
-    for (; hd + 1 < MATCHA_N_HEAD; ++hd) {
-      o = fl_zero();
-      rnh += (int64_t)g.rn_rows * 64;
-      const FL acc = fl_load(rnh + roff);             // r_{hd+1}
+    for (int hd = 0; hd + 1 < MATCHA_N_HEAD; ++hd) {
+      rnh += (int64_t)g.rn_rows * 64; vnh += (int64_t)g.rn_rows * 64;
+      const FL racc = fl_load(rnh + roff), acc = fl_load(vnh + roff);      // r_{hd+1}, y_{hd+1}
       F32_STAGE8(F32_MG_ONLY);
+      F32_Y_TILE(acc);
+      q = racc;
       FF_T(2);
-      W32_CHAIN(dyn, o, false);                       // dyn += M_hd z
-      W32_PRIME_AT(hd + 1 < MATCHA_N_HEAD - 1 ? 2 * hd + 4 : 15);      // M_{hd+1}
-      q = acc;
-      FF_T(5);
     }
-    o = fl_zero();
+    W32_PRIME_AT(16);                                 // conv0: in flight during the last head's pieces
+  } else {
+    // x_hat as three bf16 planes: the token-side operand of every product of the head loop (x_hat in f32 is dead until the tail, which reads its row back)
+    B3 xs[4];
+    FL_SPLIT(xs[0], xh, 0); FL_SPLIT(xs[1], xh, 1); FL_SPLIT(xs[2], xh, 2); FL_SPLIT(xs[3], xh, 3);
+    F32_WAVE_SYNC();
+    if (g.rn) {
+      // ---- node route with the r table alone (inference; disable_node_v): r rows gathered, y_{hd+1} = M_{hd+1} x_hat hosts ALL pieces of head hd
+      const int roff = g.xrow[F32_TOK()] * 64 + 4 * h;
+      const float* rnh = g.rn;
+      W32_PRIME_AT(2);                                // the stream starts at M_0
+      q = fl_load(rnh + roff);
+      {
+        FL acc = fl_zero();
+        F32_STAGE8_TO(F32_XS_STEP, 4, , );            // y_0 = M_0 x_hat; M_1 follows
+        fl_store(vrow, acc);
+      }
+      F32_WAVE_SYNC();
+      dyn = F32_BIAS_L2(kBiasDyn);                    // (fetched behind the prologue's products: first read by head 0's value pieces)
+      FF_T(1);
+      for (int hd = 0; hd + 1 < MATCHA_N_HEAD; ++hd) {
+        rnh += (int64_t)g.rn_rows * 64;
+        FL acc = fl_zero();
+        // y_{hd+1}; then M_{hd+2} (M_7 at 15), conv0 (16) behind the last.  r_{hd+1} is fetched once the score pieces of head hd (the first four steps) are done with r_hd
+        F32_STAGE8_TO(F32_MG_STEP, hd < 5 ? 2 * hd + 6 : 10 + hd, q = fl_load(rnh + roff), );
+        F32_Y_TILE(acc);
+        FF_T(2);
+      }
+    } else {
+      // ---- per-token route: r_{hd+1} = B_{hd+1} x_hat + b_{hd+1} hosts the score pieces of head hd, y_{hd+1} its value pieces.  Order of use
+      // R_0 M_0 | R_{hd+1} M_{hd+1} | conv0, i.e. matrices 0 2 | 1 4 | 3 6 | ... | 11 14 | 13 15 | 16 of the stream
+      W32_PRIME_AT(0);
+      q = F32_BIAS_L2(kBiasR);
+      {
+        FL& acc = q;
+        F32_STAGE8_TO(F32_XS_STEP, 2, , );            // r_0 = B_0 x_hat + b_0
+      }
+      F32_IMG_STORE(q, 0, 0);
+      {
+        FL acc = fl_zero();
+        F32_STAGE8_TO(F32_XS_STEP, 1, , );            // y_0
+        fl_store(vrow, acc);
+      }
+      F32_WAVE_SYNC();
+      dyn = F32_BIAS_L2(kBiasDyn);
+      FL racc = F32_BIAS_L2(kBiasR + 1);
+      FF_T(1);
+      for (int hd = 0; hd + 1 < MATCHA_N_HEAD; ++hd) {
+        F32_STAGE8_TO(F32_R_STEP, hd < 6 ? 2 * hd + 4 : 15, , );             // r_{hd+1}; then M_{hd+1}
+        F32_IMG_STORE(racc, hd + 1, 0);
+        q = racc;                                     // (the score pieces of head hd are done)
+        FL acc = fl_zero();
+        // y_{hd+1}; then R_{hd+2}, conv0 behind the last.  b_{hd+2} is fetched behind the last value piece (behind the last head: the row of the fc1 bias, unused)
+        F32_STAGE8_TO(F32_Y_STEP, hd < 6 ? 2 * hd + 3 : 16, , racc = F32_BIAS_L2(kBiasR + hd + 2));
+        F32_Y_TILE(acc);
+        FF_T(2);
+      }
+    }
+  }
+  {
+    constexpr int hd = MATCHA_N_HEAD - 1;             // the last head's pieces stand alone on every path
     F32_STAGE8(F32_MG_ONLY);
-    FF_T(2);
-    W32_CHAIN(dyn, o, true);                          // ... M_7; conv0 follows it in the stream
     FF_T(5);
   }
+  // the tail's two bias rows (conv0, conv1) -> their place in TV; its parameter vectors land in front of them
+  F32_WAVE_SYNC();                                    // the last head's value reads of TV are done
+  if (lane < 32) reinterpret_cast<f32x4*>(TV + kBiasConv0 * 64)[lane] = reinterpret_cast<const f32x4*>(btab + kBiasConv0 * 64)[lane];
   // =========================== tail: pff_n1, LayerNorms, classifier (all in registers) ===========================
   if (F32_ABL & 8) { if (dyn.lo[0] == 12345.f) g.logits[0] = dyn.hi[3]; return; }
   // Y and H1 are parked in the workspace's Y / H1 rows (every lane stores: the rows past the tokens are copies of the padding token's row,
@@ -592,6 +676,8 @@ __global__ __launch_bounds__(512) void fused_fwd32h_kernel(Fwd32Args g) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
 #undef FF_T
 #define FF_T(i) do { } while (0)
+#undef F32_V_PIECE
+#define F32_V_PIECE(S) F32_Z_PIECE(S)
   float* TK = lds;                       // the x_hat rows (keys = values of every head); tail: product tiles
   float* TV = lds + kHT;                 // tail: parameter vectors, H1, dZ1
   float* outs = lds + 2 * kHT;
@@ -799,7 +885,8 @@ int launch_fused_fwd32(const matcha_tensors& p, const Ragged& rg, int64_t B, int
   Fwd32Args g;
   g.xrow = a.x.xrow;
   MATCHA_CHECK_ARG(!a.x.rn || a.x.xrow, "fused forward: the r table belongs to the node route");
-  g.rn = a.x.rn; g.rn_rows = (int)a.x.rows;
+  MATCHA_CHECK_ARG(!a.x.vn || a.x.rn, "fused forward: the value table needs the r table");
+  g.rn = a.x.rn; g.vn = a.x.vn; g.rn_rows = (int)a.x.rows;
   g.tail_dh2 = nullptr; g.dxs_node = nullptr;
   g.X = a.x.X; g.row_off = rg.row_off; g.tok_slot = rg.tok_slot; g.count = rg.count; g.half_meta = rg.half_meta; g.tok_pos = rg.tok_pos;
   g.L = L;

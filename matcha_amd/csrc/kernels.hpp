@@ -174,7 +174,8 @@ struct NodeOperands {
   const int32_t* xrow;   // on the route: token t reads row xrow[t] of the tables (the plan's sanitised id, Ragged::tok_key); null off it
   float* xhat;           // ... the table's normalised rows, staged as they are by the backward kernel (null in a forward-only layout)
   float* rn;             // ... the heads' r rows per node [8][rows][64] (launch_node_r): gathered, not computed per token; null: per token, rows in the record
-  float* vn;             // ... with rn: their value rows y = M_h x_hat, same shape -- the backward's VTAB instance, no dZ product; null: dZ / Z per token
+  float* vn;             // ... with rn: their value rows y = M_h x_hat, same shape -- gathered by the forward's value pieces (no product in its head loop) and by the
+                         // backward's VTAB instance (no dZ product); null: the forward forms y per token, the backward dZ / Z per token
   int64_t rows;          // n_nodes + 1
 };
 struct FusedFwdLaunch {
@@ -193,7 +194,7 @@ struct FusedFwdLaunch {
 };
 int launch_fused_fwd32(const matcha_tensors& p, const Ragged& rg, int64_t B, int L, const FusedFwdLaunch& a, hipStream_t st);
 // the r rows of every (head, node): rows of the per-node table XN -> RN[8][rows][64]; needs this step's fragment stream (launch_prep_heads / the front end's launch)
-// vn != null: the same launch also writes the value rows y = M_h x_hat (no bias) -> VN[8][rows][64] for the backward's VTAB instance
+// vn != null: the same launch also writes the value rows y = M_h x_hat (no bias) -> VN[8][rows][64] for the forward's value pieces and the backward's VTAB instance
 size_t node_r_floats(int64_t rows);
 // compact != null: the plan's deferred compaction pass rides in the launch as a block role (or, beyond the role's reach, is launched in front of it)
 int launch_node_r(const float* XN, const float* frag, int64_t rows, float* rn, hipStream_t st, float* vn = nullptr, const CompactArgs* compact = nullptr);

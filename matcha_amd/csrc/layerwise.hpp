@@ -98,6 +98,9 @@ void nan_check(const char* name, const float* p, const int32_t* rows_dev, int64_
 // The kernel route of one step: every decision of the forward that a later line of it, or the backward on the same workspace, depends on.
 // decide_route (model.hip, behind the workspace layout it reads) fills it ONCE per short forward; matcha_forward_long_train notes one with
 // long_rows set and its head formulation in merged_layerwise.
+// StepRoute::fwd_values: per token inside the kernel (a second product per head) | per token from the node's x_hat with the r rows gathered (the route
+// without the value table: inference, disable_node_v) | gathered from the value table VN next to the r rows (no product in the head loop)
+constexpr int kValuesToken = 1, kValuesNodeProduct = 2, kValuesTable = 3;
 struct StepRoute {
   bool compact;                  // workspace layout of a forward that will not be differentiated (carve)
   bool half_plan;                // the ragged plan stops at the half tiles (level 1: no 64-row tile list, no token -> tile map)
@@ -108,7 +111,8 @@ struct StepRoute {
   bool lif;                      // the tail's backward ran inside the forward kernel: Y / H1 / H2 hold parked rows, ddyn0 and dXs are final
   bool split_tail, dx_zeroed;    // ... up to its LayerNorms, the convolutions' as tail_bwd64_kernel;  the forward zeroed the d x_hat rows the backward's heads add into
   bool node;                     // table front end per NODE: X lives in the per-node table, rows by tok_key
-  bool node_r, node_v;           // ... the heads' r rows gathered from the per-node table (none in the record);  ... and the value table VN left for the backward
+  bool node_r, node_v;           // ... the heads' r rows gathered from the per-node table (none in the record);  ... and the value table VN, gathered by the forward and left for the backward
+  int fwd_values;                // where fused_fwd32_kernel took the heads' value rows y_h = M_h x_hat from (kValues*; 0: another kernel ran the forward)
   bool node_dx;                  // ... d x_hat and dXs added per NODE by their producers (AH in dO, AS in GN): node_scatter_kernel is the per-node finisher
   bool paired;                   // fused route: independent small launches share a launch -- the chain rule's blocks un-fold their own rows; with node_dx
                                  // the node route the final vectors ride in node_scatter_kernel and the plan's tile lists in the table launches.  Off: the launches of the step one by one

@@ -281,6 +281,7 @@ static StepRoute decide_route(const matcha_shape& s, const matcha_step_opts& o, 
   r.node = r.front && node_front_shape(s, B, L) && !r.small && atomics && !options().disable_node_front;
   r.node_r = r.node && !options().disable_node_r;      // ... with the heads' r rows once per node
   r.node_v = r.node_r && !o.forward_only && w.VN && node_v_shape(s, B, L) && !options().disable_node_v;      // ... and, for the backward alone, their value rows
+  r.fwd_values = (r.fused && !r.small) ? (r.node_v ? kValuesTable : r.node_r ? kValuesNodeProduct : kValuesToken) : 0;      // (node_operands hands VN to the forward exactly then)
   r.lif = r.fused && o.loss_in_forward && !o.forward_only && has_target(objective, y, w_bce);
   // large batches: the tail's backward inside the forward kernel stops behind its LayerNorms; pff_n1's two convolutions (dZ1, d dyn, the
   // weight gradients) are a kernel of their own right behind it (tail_bwd.hip).  Development switch fused_dbg bit 0: all of it in-kernel.
@@ -345,6 +346,23 @@ extern "C" int matcha_launch_log_read(char* out, size_t cap) {
     if (k < 0 || (size_t)k >= cap - n) { set_error("matcha_launch_log_read: buffer too small"); return MATCHA_ENOMEM; }
     n += (size_t)k;
   }
+  return MATCHA_OK;
+}
+
+extern "C" int matcha_route_read(const void* ws, char* out, size_t cap) {
+  MATCHA_CHECK_ARG(ws && out && cap > 0, "matcha_route_read: null pointer");
+  StepRoute r;
+  MATCHA_CHECK_ARG(recorded_route(ws, r), "matcha_route_read: no forward on record for this workspace");
+  // every field of StepRoute, in the struct's order: a structured binding names ALL members of an aggregate, so a field added to (or taken out of) the
+  // struct stops this function from compiling until the list and the format below follow
+  const auto& [compact, half_plan, fused, merged_layerwise, enc128, front, adj_fused, small, lif, split_tail, dx_zeroed, node, node_r, node_v, fwd_values, node_dx,
+               paired, long_rows] = r;
+  const int k = snprintf(out, cap,
+                         "compact %d\nhalf_plan %d\nfused %d\nmerged_layerwise %d\nenc128 %d\nfront %d\nadj_fused %d\nsmall %d\nlif %d\nsplit_tail %d\ndx_zeroed %d\n"
+                         "node %d\nnode_r %d\nnode_v %d\nfwd_values %d\nnode_dx %d\npaired %d\nlong_rows %d\n",
+                         compact, half_plan, fused, merged_layerwise, enc128, front, adj_fused, small, lif, split_tail, dx_zeroed, node, node_r, node_v, fwd_values,
+                         node_dx, paired, long_rows);
+  if (k < 0 || (size_t)k >= cap) { set_error("matcha_route_read: buffer too small"); return MATCHA_ENOMEM; }
   return MATCHA_OK;
 }
 
