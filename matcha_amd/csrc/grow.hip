@@ -2,7 +2,7 @@
 // A beam search that grows hubs of up to 32 loci from seed clusters, one bin of a region per step.  The beam table is int64 [A, B, S]:
 // A seeds, B slots per seed (1 <= B <= 64), every slot a cluster row of 7.10 (1 <= S <= 31; the leading non-zero run is the slot, an
 // all-zero slot is empty).  Entry e = a B + j; the candidate of (e, r) is 7.10's candidate of cluster e with one free id lo + r, its
-// global rank g = e n + r.  The rows, their validity and flag bit 1 are csrc/sweep.hip's kway_complete_rows_kernel, unchanged.  What is
+// global rank g = e n + r.  The rows, their validity and flag bit 1 are csrc/sweep_rows.hip's kway_complete_rows_kernel, unchanged.  What is
 // new is the duplicate rule: the same sorted row is reached from several slots of a seed ({a, b} + c and {a, c} + b).
 //
 // Twins.  Candidate (a, j, r) is a twin iff a LOWER slot j' < j of the same seed is strictly ascending, non-empty, holds as many ids as
@@ -23,7 +23,7 @@
 //   grow_twin_flags_kernel  one thread per rank of [rank0, rank0 + count): ORs 2 into flag[i] when lo + r stands in columns [0, j) of
 //                           its entry's twin row, or a -1 does.  Consecutive ranks share the entry: the row is a broadcast read.
 // No LDS, no scratch, plain C++ and vector stores.
-#include "common.hpp"
+#include "sweep_rank.hpp"
 
 namespace matcha {
 namespace {
@@ -31,11 +31,6 @@ namespace {
 constexpr int kGrowBlock = 256;                // 4 wavefronts: 4 entries per block (twins), 256 ranks per block (flags)
 constexpr int kMaxBeam = 64;                   // slots per seed: one lane per column of a twin row
 constexpr int kMaxSlot = MATCHA_MAX_LONG_L - 1;
-
-__device__ __forceinline__ int64_t grow_shfl64(int64_t v, int src) {
-  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src), hi = (uint32_t)__shfl((int)((uint64_t)v >> 32), src);
-  return (int64_t)(((uint64_t)hi << 32) | lo);
-}
 
 __global__ __launch_bounds__(kGrowBlock) void grow_twins_kernel(const int64_t* __restrict__ beam, int64_t entries, int32_t B, int32_t S,
                                                                 int64_t* __restrict__ twin) {
@@ -50,7 +45,7 @@ __global__ __launch_bounds__(kGrowBlock) void grow_twins_kernel(const int64_t* _
     if (live && lane < S) v = beam[e * S + lane];
     const uint64_t zv = __ballot(v == 0);                                // lanes >= S hold 0 and S <= 31: bit 31 at the latest is set
     const int s = __builtin_ctzll(zv);
-    const int64_t v_prev = grow_shfl64(v, lane ? lane - 1 : 0), v_next = grow_shfl64(v, lane < 63 ? lane + 1 : 63);
+    const int64_t v_prev = shfl64(v, lane ? lane - 1 : 0), v_next = shfl64(v, lane < 63 ? lane + 1 : 63);
     const bool v_ok = s >= 1 && __ballot(lane >= 1 && lane < s && v <= v_prev) == 0;      // non-empty and strictly ascending
     int64_t mine = 0;                                                    // lane c: column c of the twin row
     for (int jp = 0; jp < j; ++jp) {
@@ -58,14 +53,14 @@ __global__ __launch_bounds__(kGrowBlock) void grow_twins_kernel(const int64_t* _
       if (lane < S) u = beam[(seed0 + jp) * S + lane];
       const uint64_t zu = __ballot(u == 0);
       const int su = __builtin_ctzll(zu);
-      const int64_t u_prev = grow_shfl64(u, lane ? lane - 1 : 0);
+      const int64_t u_prev = shfl64(u, lane ? lane - 1 : 0);
       const bool u_ok = su >= 1 && __ballot(lane >= 1 && lane < su && u <= u_prev) == 0;
       const bool pair = v_ok && u_ok && su == s;
       const uint64_t d = __ballot(lane < s && u != v);
       const int p = __builtin_ctzll(d | (1ull << 63)), q = 63 - __builtin_clzll(d | 1ull);      // defined for d = 0 too (not used then)
       const uint64_t up = __ballot(lane > p && lane <= q && u != v_prev);                        // u is v shifted up on (p, q]?
       const uint64_t down = __ballot(lane >= p && lane < q && u != v_next);                      // ... or shifted down on [p, q)?
-      const int64_t x_up = grow_shfl64(u, p), x_down = grow_shfl64(u, q);
+      const int64_t x_up = shfl64(u, p), x_down = shfl64(u, q);
       int64_t t = 0;
       if (pair) t = d == 0 ? -1 : up == 0 ? x_up : down == 0 ? x_down : 0;
       if (lane == jp) mine = t;
@@ -77,16 +72,8 @@ __global__ __launch_bounds__(kGrowBlock) void grow_twins_kernel(const int64_t* _
 __global__ __launch_bounds__(kGrowBlock) void grow_twin_flags_kernel(const int64_t* __restrict__ twin, int32_t B, int64_t lo, uint64_t n, int64_t rank0,
                                                                      int64_t count, int32_t* __restrict__ flag) {
   for (int64_t i = (int64_t)blockIdx.x * kGrowBlock + threadIdx.x; i < count; i += (int64_t)gridDim.x * kGrowBlock) {
-    const uint64_t g = (uint64_t)(rank0 + i);
     uint64_t e, r;
-    if ((g | n) >> 32) {
-      e = g / n;
-      r = g - e * n;
-    } else {
-      const uint32_t e32 = (uint32_t)g / (uint32_t)n;
-      e = e32;
-      r = (uint32_t)g - e32 * (uint32_t)n;
-    }
+    split_rank((uint64_t)(rank0 + i), n, e, r);
     const int j = (int)(e % (uint64_t)B);
     const int64_t id = lo + (int64_t)r;
     const int64_t* __restrict__ row = twin + e * (uint64_t)B;
@@ -133,15 +120,11 @@ extern "C" int matcha_grow_twin_flags(const int64_t* twin, int64_t A, int32_t B,
   MATCHA_CHECK_ARG(lo >= 0 && lo <= ((int64_t)1 << 62), "matcha_grow_twin_flags: lo out of range");
   const int64_t total = grow_total(A, B, n);
   MATCHA_CHECK_ARG(total >= 0, "matcha_grow_twin_flags: A B n does not fit 63 bits (A=%lld B=%d n=%d)", (long long)A, B, n);
-  MATCHA_CHECK_ARG(count >= 0 && count <= ((int64_t)1 << 40), "matcha_grow_twin_flags: count out of range");
-  MATCHA_CHECK_ARG(rank0 >= 0 && rank0 <= total && count <= total - rank0, "matcha_grow_twin_flags: %lld ranks from %lld lie outside [0, %lld)",
-                   (long long)count, (long long)rank0, (long long)total);
+  MATCHA_ROWS_RANGE("matcha_grow_twin_flags", false, kGrowBlock);
   if (count == 0 || A == 0) return MATCHA_OK;
   MATCHA_CHECK_ARG(twin, "matcha_grow_twin_flags: null twin table");
   MATCHA_CHECK_ARG(flag, "matcha_grow_twin_flags: null flag");
-  int64_t blocks = cdiv(count, kGrowBlock);
-  if (blocks > (1 << 20)) blocks = 1 << 20;
-  hipLaunchKernelGGL(grow_twin_flags_kernel, dim3((unsigned)blocks), dim3(kGrowBlock), 0, (hipStream_t)stream, twin, B, lo, (uint64_t)n, rank0, count, flag);
+  hipLaunchKernelGGL(grow_twin_flags_kernel, dim3(blocks), dim3(kGrowBlock), 0, (hipStream_t)stream, twin, B, lo, (uint64_t)n, rank0, count, flag);
   MATCHA_CHECK_LAUNCH("grow_twin_flags_kernel");
   return MATCHA_OK;
 }

@@ -1,4 +1,4 @@
-"""Cluster completion restated in plain Python with itertools: the twin of csrc/sweep.hip's kway_complete_rows_kernel and
+"""Cluster completion restated in plain Python with itertools: the twin of csrc/sweep_rows.hip's kway_complete_rows_kernel and
 of matcha_amd/sweep.py's completion_unrank.  No GPU, no torch; tests/test_cpu_complete.py and tests/test_hip_complete.py both check against it.
 
 The rule.  A cluster row holds s non-zero ids followed by zeros: the run before the first zero is the cluster.  The free parts are the

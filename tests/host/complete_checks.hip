@@ -1,4 +1,4 @@
-// Cluster completion's host side (csrc/sweep.hip: matcha_kway_complete_count and the argument checks of matcha_kway_complete_rows, DESIGN.md
+// Cluster completion's host side (csrc/sweep_rows.hip: matcha_kway_complete_count and the argument checks of matcha_kway_complete_rows, DESIGN.md
 // 7.10) under AddressSanitizer + UndefinedBehaviorSanitizer on the host, next to tests/host/route_pairs.hip: the same host-only objects,
 // model.hip included as source for the library's error and option plumbing, a driver of its own.  No kernel runs: every call to the rows
 // entry point below is refused, or is a no-op, before any device call, on pointers that are never dereferenced.

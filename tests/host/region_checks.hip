@@ -1,4 +1,4 @@
-// The multi-region sweep's host side (csrc/sweep.hip: matcha_kway_region_count and the argument checks of matcha_kway_region_rows,
+// The multi-region sweep's host side (csrc/sweep_rows.hip: matcha_kway_region_count and the argument checks of matcha_kway_region_rows,
 // DESIGN.md 7.14) under AddressSanitizer + UndefinedBehaviorSanitizer on the host, next to tests/host/grow_checks.hip: the same
 // host-only objects, model.hip included as source for the library's error and option plumbing, a driver of its own.  The three part
 // arrays are host memory of exactly P elements, so a read past them is an ASan report; no kernel runs: every rows call below is refused,

@@ -1,4 +1,4 @@
-// Cluster decomposition's host side (csrc/sweep.hip: matcha_cluster_subset_count, the argument checks of matcha_cluster_subset_rows and of
+// Cluster decomposition's host side (csrc/sweep_rows.hip and csrc/sweep_support.hip: matcha_cluster_subset_count, the argument checks of matcha_cluster_subset_rows and of
 // matcha_subset_support_*) under AddressSanitizer + UndefinedBehaviorSanitizer on the host, next to
 // tests/host/complete_checks.hip: the same host-only objects, model.hip included as source for the library's error and option plumbing, a
 // driver of its own.  No kernel runs: every call below is refused, or is a no-op, before any device call, on pointers that are never

@@ -1,4 +1,4 @@
-"""The per-pair support planes restated in numpy: the twin of csrc/sweep.hip's subset_pair_update_kernel.  No GPU, no
+"""The per-pair support planes restated in numpy: the twin of csrc/sweep_support.hip's subset_pair_update_kernel.  No GPU, no
 torch; tests/test_cpu_pair_support.py and tests/test_hip_pair_support.py both check against it.
 
 The rule.  Row i of an update has the global rank g0 + i, hence cluster a = g // C(S, m) and the choice of rank g % C(S, m)

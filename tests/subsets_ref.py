@@ -1,4 +1,4 @@
-"""Cluster decomposition restated in plain Python with itertools: the twin of csrc/sweep.hip's two decomposition kernels and of
+"""Cluster decomposition restated in plain Python with itertools: the twin of the two decomposition kernels of csrc/sweep_rows.hip and csrc/sweep_support.hip and of
 matcha_amd/sweep.py's subset_unrank.  No GPU, no torch; tests/test_cpu_subsets.py and tests/test_hip_subsets.py both check against it.
 
 The rule.  A cluster table is [A, S], 2 <= S <= 32; row a holds s_a non-zero ids followed by zeros: the run before the first zero is

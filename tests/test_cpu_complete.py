@@ -1,4 +1,4 @@
-"""Cluster completion without a GPU (matcha_amd/sweep.py, csrc/sweep.hip's host side): the two entry points and their
+"""Cluster completion without a GPU (matcha_amd/sweep.py, csrc/sweep_rows.hip's host side): the two entry points and their
 refusals before any device call, counts and unranking against the itertools twin (tests/complete_ref.py) and against the anchored
 sweep's unranking, the g15 fixture's consistency, the fp32 oracle on its rows, and the CLI's line check."""
 import ctypes as C

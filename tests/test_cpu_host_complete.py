@@ -1,4 +1,4 @@
-"""Cluster completion's host side (csrc/sweep.hip: matcha_kway_complete_count, the argument checks of matcha_kway_complete_rows) under
+"""Cluster completion's host side (csrc/sweep_rows.hip: matcha_kway_complete_count, the argument checks of matcha_kway_complete_rows) under
 AddressSanitizer + UndefinedBehaviorSanitizer on the host: tests/host/complete_checks.hip, a stand-alone driver on the host-only objects of
 tests/test_cpu_host_sanitizers.py -- the count against a 128-bit restatement over a grid that includes every integer extreme, every
 refusal with its message, the no-op forms.  No kernel is launched."""

@@ -1,4 +1,4 @@
-"""The anchored k-way sweep without a GPU (matcha_amd/sweep.py, csrc/sweep.hip's host side): the anchored candidate
+"""The anchored k-way sweep without a GPU (matcha_amd/sweep.py, the host side of csrc/sweep_rows.hip and csrc/sweep_select.hip): the anchored candidate
 rule and its ranking against itertools, argument errors refused before any device call, and that the g11 fixture separates every
 anchor's top rows by far more than the tolerance its GPU test allows."""
 import ctypes as C

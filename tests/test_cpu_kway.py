@@ -1,4 +1,4 @@
-"""The de novo k-way sweep without a GPU (matcha_amd/sweep.py, csrc/sweep.hip's host side): the candidate rule and its ranking
+"""The de novo k-way sweep without a GPU (matcha_amd/sweep.py, the host side of csrc/sweep_rows.hip and csrc/sweep_select.hip): the candidate rule and its ranking
 against itertools, the host-only count against math.comb, argument errors refused before any device call, and the fixture's own
 consistency (tests/golden/make_golden_kway.py)."""
 import ctypes as C

@@ -1,4 +1,4 @@
-"""Per-pair support without a GPU (matcha_amd/sweep.py's SubsetPairSupport, csrc/sweep.hip's host side): the four entry
+"""Per-pair support without a GPU (matcha_amd/sweep.py's SubsetPairSupport, csrc/sweep_support.hip's host side): the four entry
 points and their refusals before any device call, the numpy twin (tests/pair_support_ref.py) against the per-locus twin in exact integers
 and against a brute-force float64 sum on the g16 fixture's reference logits, and decomposition_sweep's argument refusals."""
 import ctypes as C

@@ -1,4 +1,4 @@
-"""The multi-region sweep without a GPU (matcha_amd/sweep.py, csrc/sweep.hip's host side): the two entry points and their
+"""The multi-region sweep without a GPU (matcha_amd/sweep.py, csrc/sweep_rows.hip's host side): the two entry points and their
 refusals before any device call, region_count / region_unrank against itertools, the g18 fixture's consistency, the wrappers' and the
 CLI parser's checks, and the host side alone under ASan + UBSan."""
 import ctypes as C

@@ -1,4 +1,4 @@
-"""Cluster decomposition without a GPU (matcha_amd/sweep.py, csrc/sweep.hip's host side): the new entry points and their
+"""Cluster decomposition without a GPU (matcha_amd/sweep.py, the host side of csrc/sweep_rows.hip and csrc/sweep_support.hip): the new entry points and their
 refusals before any device call, counts and unranking against the itertools twin (tests/subsets_ref.py), the g16 fixture's consistency,
 the fp32 oracle on its rows, the CLI's line check, and the host side alone under ASan + UBSan as a stand-alone program."""
 import ctypes as C

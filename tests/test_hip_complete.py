@@ -1,4 +1,4 @@
-"""Cluster completion on the MI355X (csrc/sweep.hip's kway_complete_rows_kernel, matcha_amd/sweep.py): candidate rows and
+"""Cluster completion on the MI355X (csrc/sweep_rows.hip's kway_complete_rows_kernel, matcha_amd/sweep.py): candidate rows and
 flags bit for bit against the itertools twin (tests/complete_ref.py) and against the anchored kernel; the sweep against the reference's
 own logits per cluster (g15), independent of how it is cut; exclusion, errors and empty cases; the untouched sweeps; the CLI."""
 import json

@@ -1,4 +1,4 @@
-"""The anchored k-way sweep on the MI355X (csrc/sweep.hip, matcha_amd/sweep.py): anchored candidate rows and their
+"""The anchored k-way sweep on the MI355X (csrc/sweep_rows.hip, csrc/sweep_select.hip, matcha_amd/sweep.py): anchored candidate rows and their
 flags bit for bit against itertools and, beyond 2^40, against anchored_unrank; the segmented selection bit for bit against numpy's
 lexsort however the stream is cut; the sweep against the reference's own logits per anchor (g11) and against one batch per anchor
 of the d = 64 model with partners on another chromosome; the CLI."""

@@ -1,4 +1,4 @@
-"""The de novo k-way sweep on the MI355X (csrc/sweep.hip, matcha_amd/sweep.py): candidate rows bit for bit against itertools and,
+"""The de novo k-way sweep on the MI355X (csrc/sweep_rows.hip, csrc/sweep_select.hip, matcha_amd/sweep.py): candidate rows bit for bit against itertools and,
 beyond 2^32, against kway_unrank; the streaming selection bit for bit against numpy's lexsort however the stream is cut; the sweep
 against the reference's own logits (g11) and against one big batch of the d = 64 model; the CLI."""
 import itertools

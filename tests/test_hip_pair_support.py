@@ -1,4 +1,4 @@
-"""Per-pair support on the MI355X (csrc/sweep.hip's subset_pair_update_kernel, matcha_amd/sweep.py's SubsetPairSupport and
+"""Per-pair support on the MI355X (csrc/sweep_support.hip's subset_pair_update_kernel, matcha_amd/sweep.py's SubsetPairSupport and
 decomposition_sweep(pair_support=True)): the packed planes bit for bit against the numpy twin (tests/pair_support_ref.py),
 whatever the cut and the order, and in exact identities against the per-locus planes filled on the device from the same stream; the sweep's
 pair matrices against the reference's own logits (g16); the untouched defaults; the CLI."""

@@ -1,4 +1,4 @@
-"""The multi-region sweep on the MI355X (csrc/sweep.hip, matcha_amd/sweep.py): candidate rows and their flags bit for
+"""The multi-region sweep on the MI355X (csrc/sweep_rows.hip, matcha_amd/sweep.py): candidate rows and their flags bit for
 bit against region_unrank and itertools and, beyond 2^61, against Python integers; region_sweep against the reference's own logits
 (g18), per leading candidate against the anchored sweep, and against one batch of the d = 64 model with parts on three chromosomes;
 region_map against the numpy twin of the pair map; the CLI."""

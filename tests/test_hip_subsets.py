@@ -1,4 +1,4 @@
-"""Cluster decomposition on the MI355X (csrc/sweep.hip's cluster_subset_rows_kernel and subset_support_update_kernel, matcha_amd/sweep.py,
+"""Cluster decomposition on the MI355X (csrc/sweep_rows.hip's cluster_subset_rows_kernel and csrc/sweep_support.hip's subset_support_update_kernel, matcha_amd/sweep.py,
 DESIGN.md 7.11): candidate rows and flags bit for bit against the itertools twin (tests/subsets_ref.py); the support planes bit for bit
 against its integer restatement, whatever the cut and the order; the sweep against the reference's own logits per cluster (g16),
 independent of how it is cut and of how the clusters are grouped; exclusion, errors and empty cases; the untouched sweeps; the CLI."""

@@ -1,4 +1,4 @@
-"""Cost of the multi-region sweep (matcha_amd/sweep.py::region_sweep / region_map, csrc/sweep.hip::kway_region_rows_kernel)
+"""Cost of the multi-region sweep (matcha_amd/sweep.py::region_sweep / region_map, csrc/sweep_rows.hip::kway_region_rows_kernel)
 beside the eval forward on the same rows, and of its rows kernel beside kway_rows_kernel.
 
   python tools/region_bench.py [--reps 10] [--cases ab]

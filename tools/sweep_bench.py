@@ -1,4 +1,4 @@
-"""Cost of the de novo k-way sweep (csrc/sweep.hip, matcha_amd/sweep.py) beside the forward it feeds.
+"""Cost of the de novo k-way sweep (csrc/sweep_rows.hip, csrc/sweep_select.hip, matcha_amd/sweep.py) beside the forward it feeds.
 
   python tools/sweep_bench.py [--top 10000] [--chunk-rows 1048576] [--sweep-only] [--stats kernel_stats.csv]
   python tools/sweep_bench.py --anchored [--chunk-rows 1048576] [--sweep-only]
@@ -10,7 +10,7 @@ its first 2^26 ranks, timed end to end with device events after a warm-up (candi
 stand next to the forward of the same chunk in the same run.  By bytes kway_rows writes 8 k bytes per row and the update reads 4
 (the radix sort of the chunk's 32-bit keys and indices is on top: four passes over 8 bytes per row, read and written).
 --sweep-only runs the k = 4 sweep alone (the run to put under rocprofv3 --kernel-trace --stats); --stats reads that run's
-kernel_stats.csv and prints the share of kway_rows_kernel, of the selection (topk_* and the radix sort) and of everything else (the
+kernel_stats.csv and prints the share of kway_rows_kernel, of the selection (select_*, *topk_keys and the radix sort) and of everything else (the
 forward).
 --anchored: the anchored sweep at k = 3 with every bin of chr1 an anchor and chr1 as partner region (250 x 31 125
 global ranks), top 100 per anchor, beside the plain k = 3 kway_sweep (top 100) in the same run, rows/s by device events after a
@@ -150,15 +150,15 @@ def bench_map(top, chunk_rows, sweep_only):
 def stats(path):
     import csv
     rows = list(csv.DictReader(open(path)))
-    groups = {"kway_rows_kernel": 0.0, "selection (topk_* + radix sort)": 0.0, "pair map (pairmap_*)": 0.0, "everything else (the forward)": 0.0}
+    groups = {"kway_rows_kernel": 0.0, "selection (select_* + radix sort)": 0.0, "pair map (pairmap_*)": 0.0, "everything else (the forward)": 0.0}
     for r in rows:
         name, ns = r["Name"], float(r["TotalDurationNs"])
         if "kway_rows_kernel" in name or "kway_anchor_rows_kernel" in name:
             groups["kway_rows_kernel"] += ns
         elif "pairmap_" in name:
             groups["pair map (pairmap_*)"] += ns
-        elif "topk_" in name or "rocprim" in name.lower() or "radix" in name.lower():
-            groups["selection (topk_* + radix sort)"] += ns
+        elif "select_" in name or "topk_" in name or "rocprim" in name.lower() or "radix" in name.lower():
+            groups["selection (select_* + radix sort)"] += ns
         else:
             groups["everything else (the forward)"] += ns
     total = sum(groups.values())
