@@ -118,6 +118,20 @@ struct StepRoute {
                                  // the node route the final vectors ride in node_scatter_kernel and the plan's tile lists in the table launches.  Off: the launches of the step one by one
   bool long_rows;                // the forward was matcha_forward_long_train: the long rows' training layout, consumed by matcha_backward_long alone
 };
+// Every member of a route (const or not) handed to f(name, member), in the struct's order: the ONE list of the fields besides the struct itself --
+// matcha_route_read prints from it and the host checks compare, count and set fields through it.  A structured binding names ALL members of an
+// aggregate, so a field added to (or taken out of) the struct stops this function from compiling until the list follows.
+template <class Route, class F>
+inline void for_each_route_field(Route& r, F&& f) {
+  auto& [compact, half_plan, fused, merged_layerwise, enc128, front, adj_fused, small, lif, split_tail, dx_zeroed, node, node_r, node_v, fwd_values, node_dx,
+         paired, long_rows] = r;
+#define MATCHA_ROUTE_FIELD(x) f(#x, x)
+  MATCHA_ROUTE_FIELD(compact); MATCHA_ROUTE_FIELD(half_plan); MATCHA_ROUTE_FIELD(fused); MATCHA_ROUTE_FIELD(merged_layerwise); MATCHA_ROUTE_FIELD(enc128);
+  MATCHA_ROUTE_FIELD(front); MATCHA_ROUTE_FIELD(adj_fused); MATCHA_ROUTE_FIELD(small); MATCHA_ROUTE_FIELD(lif); MATCHA_ROUTE_FIELD(split_tail);
+  MATCHA_ROUTE_FIELD(dx_zeroed); MATCHA_ROUTE_FIELD(node); MATCHA_ROUTE_FIELD(node_r); MATCHA_ROUTE_FIELD(node_v); MATCHA_ROUTE_FIELD(fwd_values);
+  MATCHA_ROUTE_FIELD(node_dx); MATCHA_ROUTE_FIELD(paired); MATCHA_ROUTE_FIELD(long_rows);
+#undef MATCHA_ROUTE_FIELD
+}
 // Which route the forward that last ran on a workspace took.  The backward keys off THIS record and reads no option: the two calls are
 // separate on the autograd path and the switches are process-wide, so a flip between them would otherwise make the backward consume records
 // nobody wrote.  Host-side record per workspace pointer (the decision picks a kernel, so it cannot live in device memory without a

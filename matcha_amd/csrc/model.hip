@@ -353,16 +353,17 @@ extern "C" int matcha_route_read(const void* ws, char* out, size_t cap) {
   MATCHA_CHECK_ARG(ws && out && cap > 0, "matcha_route_read: null pointer");
   StepRoute r;
   MATCHA_CHECK_ARG(recorded_route(ws, r), "matcha_route_read: no forward on record for this workspace");
-  // every field of StepRoute, in the struct's order: a structured binding names ALL members of an aggregate, so a field added to (or taken out of) the
-  // struct stops this function from compiling until the list and the format below follow
-  const auto& [compact, half_plan, fused, merged_layerwise, enc128, front, adj_fused, small, lif, split_tail, dx_zeroed, node, node_r, node_v, fwd_values, node_dx,
-               paired, long_rows] = r;
-  const int k = snprintf(out, cap,
-                         "compact %d\nhalf_plan %d\nfused %d\nmerged_layerwise %d\nenc128 %d\nfront %d\nadj_fused %d\nsmall %d\nlif %d\nsplit_tail %d\ndx_zeroed %d\n"
-                         "node %d\nnode_r %d\nnode_v %d\nfwd_values %d\nnode_dx %d\npaired %d\nlong_rows %d\n",
-                         compact, half_plan, fused, merged_layerwise, enc128, front, adj_fused, small, lif, split_tail, dx_zeroed, node, node_r, node_v, fwd_values,
-                         node_dx, paired, long_rows);
-  if (k < 0 || (size_t)k >= cap) { set_error("matcha_route_read: buffer too small"); return MATCHA_ENOMEM; }
+  // "name value\n" for every field of StepRoute, in the struct's order (for_each_route_field, layerwise.hpp)
+  size_t n = 0;
+  bool fits = true;
+  out[0] = 0;
+  for_each_route_field(r, [&](const char* name, const auto& v) {
+    if (!fits) return;
+    const int k = snprintf(out + n, cap - n, "%s %d\n", name, (int)v);
+    if (k < 0 || (size_t)k >= cap - n) fits = false;
+    else n += (size_t)k;
+  });
+  if (!fits) { set_error("matcha_route_read: buffer too small"); return MATCHA_ENOMEM; }
   return MATCHA_OK;
 }
 

@@ -2,18 +2,7 @@
 // 7.10) under AddressSanitizer + UndefinedBehaviorSanitizer on the host, next to tests/host/route_pairs.hip: the same host-only objects,
 // model.hip included as source for the library's error and option plumbing, a driver of its own.  No kernel runs: every call to the rows
 // entry point below is refused, or is a no-op, before any device call, on pointers that are never dereferenced.
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "../../matcha_amd/csrc/model.hip"
-
-static int g_fail = 0, g_checks = 0;
-#define CHECK(cond)                                                              \
-  do {                                                                           \
-    ++g_checks;                                                                  \
-    if (!(cond)) { ++g_fail; fprintf(stderr, "CHECK FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); } \
-  } while (0)
+#include "host_driver.hpp"
 
 // C(m, f) in 128 bits, -1 from 2^63 on: the definition, multiplied out
 static __int128 choose(int64_t m, int f) {
@@ -52,7 +41,6 @@ int main() {
   int32_t hflag[8] = {0};
   int64_t* const p = host;
   int32_t* const q = hflag;
-  auto refused = [&](int rc, const char* word) { return rc == MATCHA_EINVAL && strstr(matcha_last_error(), word) != nullptr; };
   // clusters, A, S, lo, n, f, min_gap, rank0, ranks, count, L, x, flag
   CHECK(refused(matcha_kway_complete_rows(p, 4, 9, 1, 16, 1, 1, 0, nullptr, 4, 10, nullptr, q, nullptr), "null output"));
   CHECK(refused(matcha_kway_complete_rows(p, 4, 9, 1, 16, 1, 1, 0, nullptr, 4, 10, p, nullptr, nullptr), "null output"));
@@ -81,7 +69,5 @@ int main() {
   CHECK(matcha_kway_complete_rows(nullptr, 0, 9, 1, 16, 1, 1, 0, nullptr, 0, 10, nullptr, nullptr, nullptr) == MATCHA_OK);
   CHECK(matcha_kway_complete_rows(p, 4, 9, 1, 16, 1, 1, 0, p, 0, 10, nullptr, nullptr, nullptr) == MATCHA_OK);
 
-  printf("%d checks, %d failed\n", g_checks, g_fail);
-  if (g_fail == 0) printf("ALL CLUSTER COMPLETION HOST CHECKS PASSED\n");
-  return g_fail ? 1 : 0;
+  return finish("CLUSTER COMPLETION HOST CHECKS");
 }

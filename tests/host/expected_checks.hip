@@ -3,20 +3,9 @@
 // tests/host/region_checks.hip: the same host-only objects, model.hip included as source for the library's error and option plumbing, a
 // driver of its own.  The edge arrays are host memory of exactly n_edges elements, so a read past them is an ASan report; no kernel runs:
 // every launching call below is refused, or is a no-op, before any device call, and state / x / value are never dereferenced.
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
 #include <vector>
 
-#include "../../matcha_amd/csrc/model.hip"
-
-static int g_fail = 0, g_checks = 0;
-#define CHECK(cond)                                                              \
-  do {                                                                           \
-    ++g_checks;                                                                  \
-    if (!(cond)) { ++g_fail; fprintf(stderr, "CHECK FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); } \
-  } while (0)
+#include "host_driver.hpp"
 
 static int64_t ipow(int64_t b, int e) {
   int64_t r = 1;
@@ -30,11 +19,6 @@ int main() {
   int64_t rows[8] = {0};
   float vals[8] = {0};
   int32_t ids[8] = {0};
-  auto refused = [&](int rc, const char* word) {
-    const bool hit = rc == MATCHA_EINVAL && strstr(matcha_last_error(), word) != nullptr;
-    if (!hit) fprintf(stderr, "  rc=%d error=\"%s\" (wanted \"%s\")\n", rc, matcha_last_error(), word);
-    return hit;
-  };
   const std::vector<int64_t> e3{2, 4, 8};
   std::vector<int64_t> e15;
   for (int j = 0; j < 15; ++j) e15.push_back(2 + 3 * j);
@@ -177,7 +161,5 @@ int main() {
   CHECK(matcha_gap_strata_ids(3, e3.data(), 3, nullptr, 0, 3, ids, nullptr) == MATCHA_OK);
   CHECK(matcha_gap_strata_ids(2, nullptr, 0, nullptr, 0, 2, ids, nullptr) == MATCHA_OK);
 
-  printf("%d checks, %d failed\n", g_checks, g_fail);
-  if (g_fail == 0) printf("ALL EXPECTATION HOST CHECKS PASSED\n");
-  return g_fail ? 1 : 0;
+  return finish("EXPECTATION HOST CHECKS");
 }

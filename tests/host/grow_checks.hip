@@ -2,25 +2,13 @@
 // AddressSanitizer + UndefinedBehaviorSanitizer on the host, next to tests/host/complete_checks.hip: the same host-only objects, model.hip
 // included as source for the library's error and option plumbing, a driver of its own.  No kernel runs: every call below is refused, or is
 // a no-op, before any device call, on pointers that are never dereferenced.
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "../../matcha_amd/csrc/model.hip"
-
-static int g_fail = 0, g_checks = 0;
-#define CHECK(cond)                                                              \
-  do {                                                                           \
-    ++g_checks;                                                                  \
-    if (!(cond)) { ++g_fail; fprintf(stderr, "CHECK FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); } \
-  } while (0)
+#include "host_driver.hpp"
 
 int main() {
   int64_t host[8] = {0};
   int32_t hflag[8] = {0};
   int64_t* const p = host;
   int32_t* const q = hflag;
-  auto refused = [&](int rc, const char* word) { return rc == MATCHA_EINVAL && strstr(matcha_last_error(), word) != nullptr; };
   // beam, A, B, S, twin
   CHECK(refused(matcha_grow_twins(p, 4, 0, 9, p, nullptr), "B="));
   CHECK(refused(matcha_grow_twins(p, 4, 65, 9, p, nullptr), "B="));
@@ -58,7 +46,5 @@ int main() {
   CHECK(matcha_grow_twin_flags(nullptr, 0, 8, 1, 16, 0, 0, nullptr, nullptr) == MATCHA_OK);
   CHECK(matcha_grow_twin_flags(p, ((int64_t)1 << 40) - 1, 64, 1, 1 << 17, 0, 0, nullptr, nullptr) == MATCHA_OK);  // just below 2^63
 
-  printf("%d checks, %d failed\n", g_checks, g_fail);
-  if (g_fail == 0) printf("ALL CLUSTER GROWTH HOST CHECKS PASSED\n");
-  return g_fail ? 1 : 0;
+  return finish("CLUSTER GROWTH HOST CHECKS");
 }

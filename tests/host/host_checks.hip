@@ -1,7 +1,7 @@
 // Host-side checks of libmatcha_hip's NON-KERNEL logic under AddressSanitizer + UndefinedBehaviorSanitizer (SURVEY.md §5
 // "sanitizers"; GPU ASan is not available on the MI355X pool, so this is where sanitizers run): every source file of the
 // library is compiled for the host only (hipcc --offload-host-only -fsanitize=address,undefined), this driver is linked
-// against those objects and executed by tests/test_cpu_host_sanitizers.py in the CPU container.  No kernel runs here -- launches
+// against those objects and executed by tests/test_cpu_host_checks.py in the CPU container.  No kernel runs here -- launches
 // fail with "no device" and the entry points must turn that into MATCHA_EHIP; what IS exercised, instrumented:
 //   * argument validation and error reporting of every extern "C" entry point (null pointers, bad shapes, misaligned or
 //     too-small workspaces);
@@ -10,36 +10,18 @@
 //     the first and last byte of every region into an exactly-sized heap buffer (ASan traps an overrun);
 //   * the option table (matcha_set_option / environment parsing);
 //   * the step's kernel route (decide_route: implications over a sweep of shapes, options and switches, the sizes the history fixed) and the
-//     per-workspace record of it;
+//     per-workspace record of it, as the library keeps it and as matcha_route_read prints it;
 //   * the C restatement of the ragged plan (oracle/c/ragged_plan.c), fuzzed with its invariants.
-// model.hip is included as source so that its static functions (carve, check_shape) are reachable.
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
+// host_driver.hpp holds what the drivers of this directory share.
 #include <random>
-#include <vector>
 
-#include "../../matcha_amd/csrc/model.hip"
+#include "host_driver.hpp"
 
 extern "C" int64_t matcha_oracle_ragged_halves(const int32_t* row_off, int64_t B, const int32_t* tile_meta, int64_t n_tiles, int32_t* half_meta,
                                                int64_t halves_cap, int32_t* tok_tile);
 extern "C" int64_t matcha_oracle_ragged_plan(const int64_t* x, int64_t B, int32_t L, int64_t n_nodes, int32_t* row_off, int32_t* tok_slot,
                                              int64_t* tok_id, int32_t* tok_key, int32_t* tok_pos, int32_t* count, int32_t* tile_meta,
                                              int64_t tiles_cap, int32_t* status);
-
-static int g_fail = 0, g_checks = 0;
-#define CHECK(cond)                                                              \
-  do {                                                                           \
-    ++g_checks;                                                                  \
-    if (!(cond)) { ++g_fail; fprintf(stderr, "CHECK FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); } \
-  } while (0)
-
-static matcha_shape shape(int d, int n_attr, int n_nodes, int n_chrom, int mode, int max_bins) {
-  matcha_shape s;
-  s.d = d; s.n_attr = n_attr; s.n_nodes = n_nodes; s.n_chrom = n_chrom; s.mode = mode; s.max_bins = max_bins;
-  return s;
-}
 
 static void touch(char* base, size_t total, const void* p, const void* next) {
   // first and last byte of the region [p, next): ASan traps if either lies outside the heap block
@@ -210,38 +192,16 @@ static void check_options() {
 }
 
 // ---- the step's kernel route (model.hip: StepRoute, decide_route, the per-workspace record): decided without a device, so checked here ----
-static bool same_route(const StepRoute& a, const StepRoute& b) {
-  return a.compact == b.compact && a.half_plan == b.half_plan && a.fused == b.fused && a.merged_layerwise == b.merged_layerwise && a.enc128 == b.enc128 &&
-         a.front == b.front && a.adj_fused == b.adj_fused && a.small == b.small && a.lif == b.lif && a.split_tail == b.split_tail &&
-         a.dx_zeroed == b.dx_zeroed && a.node == b.node && a.node_r == b.node_r && a.node_v == b.node_v && a.long_rows == b.long_rows;
-}
-static StepRoute route_of(const matcha_shape& s, const matcha_step_opts& o, int64_t B, int L, bool targets, bool force_layerwise = false) {
-  Workspace w;
-  char* const base = reinterpret_cast<char*>((uintptr_t)1 << 20);      // the layout only: nothing is dereferenced
-  carve(s, B, L, base, w, compact_forward(s, o, force_layerwise));
-  matcha_frozen f;
-  memset(&f, 0, sizeof(f));
-  f.feat_row_pad = 64;                                                 // what the fused adj kernels take
-  static const float t[1] = {0.f};
-  return decide_route(s, o, B, L, w, f, targets ? t : nullptr, targets ? t : nullptr, MATCHA_OBJECTIVE_BCE, force_layerwise, true);
-}
-static matcha_step_opts train_opts() {
-  matcha_step_opts o;
-  memset(&o, 0, sizeof(o));
-  o.training = 1; o.loss_in_forward = 1;
-  return o;
-}
-
 static void check_routes() {
   const int dbg = matcha_get_option("fused_dbg");
   matcha_set_option("fused_dbg", 0);                  // (bit 0 keeps the whole tail in the forward kernel: no split tail to check)
   CHECK(device_cu_count() == 256 || matcha_device_count() > 0);      // without a device the small-batch bound is 512 half tiles
   // implications, over shapes x front ends x per-call options x every switch
-  const char* switches[] = {"", "disable_fused", "disable_fused", "disable_merged", "disable_small_batch", "disable_wide_gemm", "disable_node_front", "disable_node_r", "disable_node_v"};
-  const int values[] = {0, 1, 2, 1, 1, 1, 1, 1, 1};
-  int seen[14] = {0};
-  for (int sw = 0; sw < 9; ++sw) {
-    if (sw) CHECK(matcha_set_option(switches[sw], values[sw]) == MATCHA_OK);
+  const Fields names = route_field_names();
+  const int n_fields = (int)names.size();
+  std::vector<int> seen(n_fields, 0);
+  for (int sw = 0; sw < kNumRouteSwitches; ++sw) {
+    set_route_switch(sw, true);
     for (int d : {16, 64, 128, 256})
       for (int mode = 0; mode < 2; ++mode)
         for (int64_t B : {2ll, 1024ll, 8192ll, 65536ll})
@@ -265,12 +225,14 @@ static void check_routes() {
             CHECK(!r.compact || (r.fused && o.forward_only));
             CHECK(!o.forward_only || (!r.node_v && !r.lif));
             CHECK(!force || (!r.fused && !r.enc128 && !r.node && !r.compact));
-            const bool f[14] = {r.compact, r.half_plan, r.fused, r.merged_layerwise, r.enc128, r.front, r.adj_fused, r.small, r.lif, r.split_tail, r.dx_zeroed, r.node, r.node_r, r.node_v};
-            if (!sw) for (int i = 0; i < 14; ++i) seen[i] += f[i];
+            CHECK(!r.long_rows);                        // decide_route never sets it: the long training forward notes its own record
+            int i = 0;
+            if (!sw) for_each_route_field(r, [&](const char*, const auto& v) { seen[i++] += v != 0; });
           }
-    if (sw) matcha_set_option(switches[sw], 0);
+    set_route_switch(sw, false);
   }
-  for (int i = 0; i < 14; ++i) CHECK(seen[i] > 0);      // the default sweep reaches every field: none of the implications is vacuous
+  // the default sweep reaches every field decide_route can set -- all but long_rows: none of the implications is vacuous
+  for (int i = 0; i < n_fields; ++i) CHECK((seen[i] > 0) == (names[i] != "long_rows"));
 
   // the table front end at hg38 1 Mb (3 068 nodes), k <= 5, a training step with targets: the node route from 8 192 rows, its value table at 65 536
   const matcha_shape t64 = shape(64, 24, 3068, 0, 0, 0);
@@ -282,18 +244,25 @@ static void check_routes() {
   }
   const StepRoute small = route_of(t64, o, 1024, 5, true);
   CHECK(small.fused && small.front && small.small && !small.node && !small.node_r && !small.node_v && small.lif && !small.split_tail && small.dx_zeroed);
-  // each switch of the node route takes out its own field and the fields that depend on it, nothing else
+  // each switch of the node route takes out its own field and the fields that depend on it, nothing else.  From decide_route: node_r needs node and
+  // node_v needs node_r; fwd_values names the table only with node_v and the per-node product only with node_r; node_dx needs node_v.  Every other
+  // field reads none of these
   const StepRoute base = route_of(t64, o, 65536, 5, true);
+  CHECK(base.fwd_values == kValuesTable && base.node_dx && base.paired);
   const char* node_sw[] = {"disable_node_v", "disable_node_r", "disable_node_front"};
+  const Fields node_diff[] = {{"node_v", "fwd_values", "node_dx"}, {"node_r", "node_v", "fwd_values", "node_dx"}, {"node", "node_r", "node_v", "fwd_values", "node_dx"}};
   for (int i = 0; i < 3; ++i) {
     matcha_set_option(node_sw[i], 1);
     const StepRoute r = route_of(t64, o, 65536, 5, true);
     matcha_set_option(node_sw[i], 0);
-    StepRoute want = base;
-    want.node_v = false;
-    if (i >= 1) want.node_r = false;
-    if (i >= 2) want.node = false;
-    CHECK(same_route(r, want));
+    CHECK(route_diff(base, r) == node_diff[i]);
+    CHECK(r.fwd_values == (i == 0 ? kValuesNodeProduct : kValuesToken));
+  }
+  for (const char* sw : {"disable_node_dx", "disable_launch_pairs"}) {      // the two switches without dependants: their own field alone
+    matcha_set_option(sw, 1);
+    const StepRoute r = route_of(t64, o, 65536, 5, true);
+    matcha_set_option(sw, 0);
+    CHECK(route_diff(base, r) == Fields{!strcmp(sw, "disable_node_dx") ? "node_dx" : "paired"});
   }
   {
     matcha_set_option("disable_small_batch", 1);
@@ -301,36 +270,87 @@ static void check_routes() {
     matcha_set_option("disable_small_batch", 0);
     CHECK(!r.small && r.split_tail && r.dx_zeroed && !r.node);            // 5 121 token rows: below the node route's size rule
   }
-  CHECK(same_route(base, route_of(t64, o, 65536, 5, true)));             // every switch restored
+  CHECK(route_diff(base, route_of(t64, o, 65536, 5, true)).empty());     // every switch restored
 
   // the record: field for field, dropped by forget_forward, the 4 096 most recent workspaces kept
   g_fwd_state.clear();
-  auto pattern = [&](int i) {
-    StepRoute r = base;
-    r.compact = i & 1; r.half_plan = i & 2; r.fused = i & 4; r.merged_layerwise = i & 8; r.enc128 = i & 16; r.front = i & 32; r.adj_fused = i & 64;
-    r.small = i & 128; r.lif = i & 256; r.split_tail = i & 512; r.dx_zeroed = i & 1024; r.node = i & 2048; r.node_r = i & 4096; r.node_v = i % 3 == 0;
-    r.long_rows = i & 8192;
+  const StepRoute zero = {};
+  auto pattern = [&](int i) {      // every field from the bits of a hash of i: a flag from bit j, a number (fwd_values) as 1..3 where its bit is set
+    StepRoute r = zero;
+    const uint32_t h = (uint32_t)i * 2654435761u;
+    for (int j = 0; j < n_fields; ++j) set_route_field(r, j, ((h >> j) & 1) ? 1 + (int)((h >> 28) % 3) : 0);
     return r;
   };
   auto ws_ptr = [](int i) { return reinterpret_cast<const void*>((uintptr_t)(i + 1) << 12); };
   StepRoute got;
   CHECK(!recorded_route(ws_ptr(0), got));
-  CHECK(!base.long_rows);                             // decide_route never sets it: the long training forward notes its own record
-  for (int i = 0; i < 14; ++i) {                     // one field set at a time (bit 13: long_rows)
-    note_forward(ws_ptr(0), pattern(1 << i));
-    CHECK(recorded_route(ws_ptr(0), got) && same_route(got, pattern(1 << i)) && g_fwd_state.size() == 1);
-  }
+  for (int j = 0; j < n_fields; ++j)                  // one field set at a time, a number at each of its values (1..3: kValuesToken .. kValuesTable)
+    for (int v = 1; v <= 3; ++v) {
+      StepRoute one = zero;
+      set_route_field(one, j, v);
+      CHECK(route_diff(one, zero) == Fields{names[j]});
+      note_forward(ws_ptr(0), one);
+      CHECK(recorded_route(ws_ptr(0), got) && route_diff(got, one).empty() && g_fwd_state.size() == 1);
+    }
   forget_forward(ws_ptr(0));
   CHECK(!recorded_route(ws_ptr(0), got) && g_fwd_state.empty());
-  for (int i = 0; i < 4097; ++i) note_forward(ws_ptr(i), pattern(i));
+  std::vector<int> ones(n_fields, 0);
+  for (int i = 0; i < 4097; ++i) {
+    const StepRoute r = pattern(i);
+    note_forward(ws_ptr(i), r);
+    int j = 0;
+    for_each_route_field(r, [&](const char*, const auto& v) { ones[j++] += v != 0; });
+  }
+  for (int j = 0; j < n_fields; ++j) CHECK(ones[j] > 1024 && ones[j] < 3072);      // the pattern sets and clears every field, about half the time each
   CHECK(g_fwd_state.size() == 4096 && !recorded_route(ws_ptr(0), got));
   int kept = 0;
-  for (int i = 1; i < 4097; ++i) kept += recorded_route(ws_ptr(i), got) && same_route(got, pattern(i));
+  for (int i = 1; i < 4097; ++i) kept += recorded_route(ws_ptr(i), got) && route_diff(got, pattern(i)).empty();
   CHECK(kept == 4096);
+  CHECK(!route_diff(pattern(1), pattern(7)).empty());
   note_forward(ws_ptr(1), pattern(7));               // a pointer already on record is refreshed, nothing evicted
-  CHECK(g_fwd_state.size() == 4096 && recorded_route(ws_ptr(2), got) && recorded_route(ws_ptr(1), got) && same_route(got, pattern(7)));
+  CHECK(g_fwd_state.size() == 4096 && recorded_route(ws_ptr(2), got) && recorded_route(ws_ptr(1), got) && route_diff(got, pattern(7)).empty());
   g_fwd_state.clear();
   matcha_set_option("fused_dbg", dbg);
+}
+
+// matcha_route_read: the record as text, the only reader of it outside the library (matcha_amd/_lib.py: route_record).  The text below is the
+// entry's output format, written out: "name value\n" per field in the struct's order, here with every value 0.
+static void check_route_read() {
+  static const char kZeroText[] =
+      "compact 0\nhalf_plan 0\nfused 0\nmerged_layerwise 0\nenc128 0\nfront 0\nadj_fused 0\nsmall 0\nlif 0\nsplit_tail 0\ndx_zeroed 0\n"
+      "node 0\nnode_r 0\nnode_v 0\nfwd_values 0\nnode_dx 0\npaired 0\nlong_rows 0\n";
+  const size_t len = strlen(kZeroText);
+  const void* const ws = reinterpret_cast<const void*>((uintptr_t)1 << 12);
+  const StepRoute zero = {};
+  std::vector<char> buf(len + 1);                     // exactly what the text takes: ASan traps a write past it
+  g_fwd_state.clear();
+  note_forward(ws, zero);
+  CHECK(matcha_route_read(ws, buf.data(), buf.size()) == MATCHA_OK && !strcmp(buf.data(), kZeroText));
+  // each field set alone -- fwd_values at each of its three constants -- changes the digit of its own line and nothing else
+  int j = 0;
+  for (const char* line = kZeroText; *line; line = strchr(line, '\n') + 1, ++j) {
+    const bool number = !strncmp(line, "fwd_values ", 11);
+    for (int v : {kValuesToken, kValuesNodeProduct, kValuesTable}) {
+      if (!number && v != 1) continue;
+      std::string want(kZeroText);
+      want[(size_t)(strchr(line, '\n') - kZeroText) - 1] = (char)('0' + v);
+      StepRoute one = zero;
+      set_route_field(one, j, v);
+      note_forward(ws, one);
+      CHECK(matcha_route_read(ws, buf.data(), buf.size()) == MATCHA_OK && want == buf.data());
+    }
+  }
+  CHECK(j == (int)route_field_names().size());
+  // one byte short: MATCHA_ENOMEM with a message, nothing written past the buffer
+  std::vector<char> tight(len);
+  CHECK(matcha_route_read(ws, tight.data(), tight.size()) == MATCHA_ENOMEM && strstr(matcha_last_error(), "buffer too small") != nullptr);
+  // refused: null pointers, an empty buffer, a workspace with no forward on record
+  CHECK(refused(matcha_route_read(nullptr, buf.data(), buf.size()), "matcha_route_read: null pointer"));
+  CHECK(refused(matcha_route_read(ws, nullptr, buf.size()), "matcha_route_read: null pointer"));
+  CHECK(refused(matcha_route_read(ws, buf.data(), 0), "matcha_route_read: null pointer"));
+  forget_forward(ws);
+  CHECK(refused(matcha_route_read(ws, buf.data(), buf.size()), "matcha_route_read: no forward on record for this workspace"));
+  CHECK(g_fwd_state.empty());
 }
 
 static void fuzz_plan_oracle() {
@@ -394,8 +414,8 @@ int main() {
   check_sizes_and_validation();
   check_entry_point_errors();
   check_routes();
+  check_route_read();
   fuzz_plan_oracle();
-  if (g_fail) { fprintf(stderr, "%d of %d host checks FAILED\n", g_fail, g_checks); return 1; }
-  printf("ALL HOST CHECKS PASSED (%d checks, device_count=%d)\n", g_checks, matcha_device_count());
-  return 0;
+  printf("device_count=%d\n", matcha_device_count());
+  return finish("HOST CHECKS");
 }

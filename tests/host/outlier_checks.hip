@@ -2,20 +2,7 @@
 // 7.15) under AddressSanitizer + UndefinedBehaviorSanitizer on the host, next to tests/host/complete_checks.hip: the same host-only objects,
 // model.hip included as source for the library's error and option plumbing, a driver of its own.  No kernel runs: every call below is
 // refused, or is a no-op, before any device call, on pointers that are never dereferenced.
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "../../matcha_amd/csrc/model.hip"
-
-static int g_fail = 0, g_checks = 0;
-#define CHECK(cond)                                                              \
-  do {                                                                           \
-    ++g_checks;                                                                  \
-    if (!(cond)) { ++g_fail; fprintf(stderr, "CHECK FAILED %s:%d: %s (last error: %s)\n", __FILE__, __LINE__, #cond, matcha_last_error()); } \
-  } while (0)
-
-static bool refused(int rc, const char* word) { return rc == MATCHA_EINVAL && strstr(matcha_last_error(), word) != nullptr; }
+#include "host_driver.hpp"
 
 static void locus_scores_checks() {
   matcha_shape s;
@@ -152,7 +139,5 @@ static void outlier_plant_checks() {
 int main() {
   locus_scores_checks();
   outlier_plant_checks();
-  printf("%d checks, %d failed\n", g_checks, g_fail);
-  if (g_fail == 0) printf("ALL OUTLIER HOST CHECKS PASSED\n");
-  return g_fail ? 1 : 0;
+  return finish("OUTLIER HOST CHECKS");
 }

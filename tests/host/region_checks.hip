@@ -3,20 +3,9 @@
 // host-only objects, model.hip included as source for the library's error and option plumbing, a driver of its own.  The three part
 // arrays are host memory of exactly P elements, so a read past them is an ASan report; no kernel runs: every rows call below is refused,
 // or is a no-op, before any device call, and x / flag / ranks are never dereferenced.
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
 #include <vector>
 
-#include "../../matcha_amd/csrc/model.hip"
-
-static int g_fail = 0, g_checks = 0;
-#define CHECK(cond)                                                              \
-  do {                                                                           \
-    ++g_checks;                                                                  \
-    if (!(cond)) { ++g_fail; fprintf(stderr, "CHECK FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); } \
-  } while (0)
+#include "host_driver.hpp"
 
 struct Parts {
   std::vector<int64_t> lo;
@@ -35,7 +24,6 @@ int main() {
   int32_t hflag[8] = {0};
   int64_t* const p = host;
   int32_t* const q = hflag;
-  auto refused = [&](int rc, const char* word) { return rc == MATCHA_EINVAL && strstr(matcha_last_error(), word) != nullptr; };
   const Parts two({1, 33}, {16, 16}, {1, 2});                            // 16 C(16, 2) = 1920
   const Parts touch({17, 23}, {6, 10}, {2, 2});                          // gap 3: C(4, 2) C(8, 2) = 168
   const Parts eight({1, 201, 401, 601, 801, 1001, 1201, 1401}, {200, 200, 200, 200, 200, 200, 200, 200}, {1, 1, 1, 1, 1, 1, 1, 1});
@@ -117,7 +105,5 @@ int main() {
   CHECK(rows(eight, 1, 2560000000000000000ll, nullptr, 0, 8, nullptr, nullptr) == MATCHA_OK);
   CHECK(rows(one8, 5, 0, nullptr, 0, 8, nullptr, nullptr) == MATCHA_OK);
 
-  printf("%d checks, %d failed\n", g_checks, g_fail);
-  if (g_fail == 0) printf("ALL MULTI-REGION HOST CHECKS PASSED\n");
-  return g_fail ? 1 : 0;
+  return finish("MULTI-REGION HOST CHECKS");
 }

@@ -4,48 +4,14 @@
 // every switch: the field is the fused route's and nothing else's; its switch takes out this field and no other; no other switch touches it
 // beyond what it does to `fused`; the record hands it to the backward; the plan's deferral (what the forward leaves to the table launches)
 // exists exactly where the five-launch plan runs at level 1.
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "../../matcha_amd/csrc/model.hip"
-
-static int g_fail = 0, g_checks = 0;
-#define CHECK(cond)                                                              \
-  do {                                                                           \
-    ++g_checks;                                                                  \
-    if (!(cond)) { ++g_fail; fprintf(stderr, "CHECK FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); } \
-  } while (0)
-
-static matcha_shape shape(int d, int n_attr, int n_nodes, int n_chrom, int mode, int max_bins) {
-  matcha_shape s;
-  s.d = d; s.n_attr = n_attr; s.n_nodes = n_nodes; s.n_chrom = n_chrom; s.mode = mode; s.max_bins = max_bins;
-  return s;
-}
-static StepRoute route_of(const matcha_shape& s, const matcha_step_opts& o, int64_t B, int L, bool targets, bool force_layerwise, bool want_losses) {
-  Workspace w;
-  char* const base = reinterpret_cast<char*>((uintptr_t)1 << 20);      // the layout only: nothing is dereferenced
-  carve(s, B, L, base, w, compact_forward(s, o, force_layerwise));
-  matcha_frozen f;
-  memset(&f, 0, sizeof(f));
-  f.feat_row_pad = 64;
-  static const float t[1] = {0.f};
-  return decide_route(s, o, B, L, w, f, targets ? t : nullptr, targets ? t : nullptr, MATCHA_OBJECTIVE_BCE, force_layerwise, want_losses);
-}
-static bool same_but_paired(const StepRoute& a, const StepRoute& b) {
-  return a.compact == b.compact && a.half_plan == b.half_plan && a.fused == b.fused && a.merged_layerwise == b.merged_layerwise && a.enc128 == b.enc128 &&
-         a.front == b.front && a.adj_fused == b.adj_fused && a.small == b.small && a.lif == b.lif && a.split_tail == b.split_tail &&
-         a.dx_zeroed == b.dx_zeroed && a.node == b.node && a.node_r == b.node_r && a.node_v == b.node_v && a.node_dx == b.node_dx;
-}
+#include "host_driver.hpp"
 
 int main() {
   matcha_set_option("fused_dbg", 0);
-  const char* switches[] = {"", "disable_fused", "disable_fused", "disable_merged", "disable_small_batch", "disable_wide_gemm", "disable_node_front", "disable_node_r", "disable_node_v", "disable_node_dx", "disable_launch_pairs"};
-  const int values[] = {0, 1, 2, 1, 1, 1, 1, 1, 1, 1, 1};
-  const int kPairs = 10;
+  const int kPairs = route_switch("disable_launch_pairs"), kLayerwise = route_switch("disable_fused", 1), kUnmerged = route_switch("disable_merged");
   int seen = 0, seen_node_dx = 0;
-  for (int sw = 0; sw < 11; ++sw) {
-    if (sw) CHECK(matcha_set_option(switches[sw], values[sw]) == MATCHA_OK);
+  for (int sw = 0; sw < kNumRouteSwitches; ++sw) {
+    set_route_switch(sw, true);
     for (int d : {16, 64, 128})
       for (int mode = 0; mode < 2; ++mode)
         for (int n_nodes : {150, 3067})
@@ -53,9 +19,7 @@ int main() {
             for (int L : {5, 8})
               for (int bits = 0; bits < 128; ++bits) {
                 const matcha_shape s = mode ? shape(d, 24, n_nodes, 23, 1, 250) : shape(d, 24, n_nodes, 0, 0, 0);
-                matcha_step_opts o;
-                memset(&o, 0, sizeof(o));
-                o.training = 1;
+                matcha_step_opts o = train_opts();
                 o.forward_only = bits & 1; o.deterministic = (bits >> 1) & 1; o.loss_in_forward = (bits >> 2) & 1; o.sparse_table_grad = (bits >> 5) & 1;
                 const bool targets = (bits >> 3) & 1, force = (bits >> 4) & 1, want_losses = (bits >> 6) & 1;
                 const StepRoute r = route_of(s, o, B, L, targets, force, want_losses);
@@ -63,49 +27,47 @@ int main() {
                 // the switch is off -- whatever the front end, the batch size and the per-call options are
                 CHECK(r.paired == (r.fused && sw != kPairs));
                 if (r.paired) {
-                  CHECK(d == 64 && !force && sw != 1 && sw != 3);
+                  CHECK(d == 64 && !force && sw != kLayerwise && sw != kUnmerged);
                   ++seen;
                   seen_node_dx += r.node_dx;
                 }
-                if (sw == kPairs) {      // the switch takes out this field and no other
+                if (sw == kPairs) {      // the switch takes out this field and no other: decide_route reads it for `paired` alone, and no field reads `paired`
                   matcha_set_option("disable_launch_pairs", 0);
                   const StepRoute on = route_of(s, o, B, L, targets, force, want_losses);
                   matcha_set_option("disable_launch_pairs", 1);
-                  CHECK(!r.paired && same_but_paired(r, on) && on.paired == on.fused);
+                  CHECK(!r.paired && on.paired == on.fused && route_diff(r, on) == (on.paired ? Fields{"paired"} : Fields{}));
                 }
               }
-    if (sw) matcha_set_option(switches[sw], 0);
+    set_route_switch(sw, false);
   }
   CHECK(seen > 0 && seen_node_dx > 0);
   // the headline and the tests' shapes: a training step with targets
-  matcha_step_opts o;
-  memset(&o, 0, sizeof(o));
-  o.training = 1; o.loss_in_forward = 1;
+  const matcha_step_opts o = train_opts();
   {
-    const StepRoute h = route_of(shape(64, 24, 3067, 0, 0, 0), o, 65536, 5, true, false, true);
+    const StepRoute h = route_of(shape(64, 24, 3067, 0, 0, 0), o, 65536, 5, true);
     CHECK(h.paired && h.node && h.node_r && h.node_v && h.node_dx && h.half_plan);
-    const StepRoute c = route_of(shape(64, 24, 150, 0, 0, 0), o, 3072, 5, true, false, true);
+    const StepRoute c = route_of(shape(64, 24, 150, 0, 0, 0), o, 3072, 5, true);
     CHECK(c.paired && c.node_dx);
-    const StepRoute c8 = route_of(shape(64, 24, 150, 0, 0, 0), o, 1536, 8, true, false, true);
+    const StepRoute c8 = route_of(shape(64, 24, 150, 0, 0, 0), o, 1536, 8, true);
     CHECK(c8.paired && c8.node_dx);
-    const StepRoute sm = route_of(shape(64, 24, 150, 0, 0, 0), o, 384, 5, true, false, true);
+    const StepRoute sm = route_of(shape(64, 24, 150, 0, 0, 0), o, 384, 5, true);
     CHECK(sm.paired && sm.small && !sm.node);
-    const StepRoute adj = route_of(shape(64, 24, 3067, 23, 1, 250), o, 65536, 5, true, false, true);
+    const StepRoute adj = route_of(shape(64, 24, 3067, 23, 1, 250), o, 65536, 5, true);
     CHECK(adj.paired && !adj.node);
     matcha_step_opts fo = o;
     fo.training = 0; fo.forward_only = 1; fo.loss_in_forward = 0;
     const StepRoute inf = route_of(shape(64, 24, 150, 0, 0, 0), fo, 3072, 5, false, false, false);
     CHECK(inf.paired && inf.node && inf.node_r && !inf.node_v && inf.compact);
-    CHECK(!route_of(shape(128, 24, 3067, 0, 0, 0), o, 8192, 5, true, false, true).paired);
+    CHECK(!route_of(shape(128, 24, 3067, 0, 0, 0), o, 8192, 5, true).paired);
   }
   // the record hands the field to the backward as it is
   const void* ws = reinterpret_cast<const void*>((uintptr_t)1 << 12);
-  StepRoute r = route_of(shape(64, 24, 150, 0, 0, 0), o, 3072, 5, true, false, true), got;
+  StepRoute r = route_of(shape(64, 24, 150, 0, 0, 0), o, 3072, 5, true), got;
   for (int v = 0; v < 2; ++v) {
     r.paired = v;
     note_forward(ws, r);
     matcha_set_option("disable_launch_pairs", 1 - v);      // the option table at the time of the backward is not what decides
-    CHECK(recorded_route(ws, got) && got.paired == (bool)v && same_but_paired(got, r));
+    CHECK(recorded_route(ws, got) && got.paired == (bool)v && route_diff(got, r).empty());
     matcha_set_option("disable_launch_pairs", 0);
   }
   forget_forward(ws);
@@ -125,7 +87,5 @@ int main() {
   // the option table knows the switch by name
   CHECK(matcha_get_option("disable_launch_pairs") == 0 && matcha_set_option("disable_launch_pairs", 1) == MATCHA_OK && matcha_get_option("disable_launch_pairs") == 1);
   matcha_set_option("disable_launch_pairs", 0);
-  printf("%d checks, %d failed\n", g_checks, g_fail);
-  if (g_fail == 0) printf("ALL LAUNCH PAIR ROUTE CHECKS PASSED\n");
-  return g_fail ? 1 : 0;
+  return finish("LAUNCH PAIR ROUTE CHECKS");
 }

@@ -3,18 +3,7 @@
 // tests/host/complete_checks.hip: the same host-only objects, model.hip included as source for the library's error and option plumbing, a
 // driver of its own.  No kernel runs: every call below is refused, or is a no-op, before any device call, on pointers that are never
 // dereferenced.
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "../../matcha_amd/csrc/model.hip"
-
-static int g_fail = 0, g_checks = 0;
-#define CHECK(cond)                                                              \
-  do {                                                                           \
-    ++g_checks;                                                                  \
-    if (!(cond)) { ++g_fail; fprintf(stderr, "CHECK FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); } \
-  } while (0)
+#include "host_driver.hpp"
 
 // C(S, m) in 128 bits: the definition, multiplied out
 static __int128 choose(int64_t S, int m) {
@@ -50,7 +39,6 @@ int main() {
   float hval[8] = {0};
   int64_t* const p = host;
   int32_t* const q = hflag;
-  auto refused = [&](int rc, const char* word) { return rc == MATCHA_EINVAL && strstr(matcha_last_error(), word) != nullptr; };
   // clusters, A, S, m, complement, min_gap, rank0, ranks, count, L, x, flag
   CHECK(refused(matcha_cluster_subset_rows(p, 4, 9, 3, 0, 1, 0, nullptr, 4, 3, nullptr, q, nullptr), "null output"));
   CHECK(refused(matcha_cluster_subset_rows(p, 4, 9, 3, 0, 1, 0, nullptr, 4, 3, p, nullptr, nullptr), "null output"));
@@ -110,7 +98,5 @@ int main() {
   CHECK(refused(matcha_subset_support_read(p, need - 1, 4, 9, 3, 1.f, p, p, p, nullptr), "too small"));
   CHECK(refused(matcha_subset_support_read(p, need, 4, 9, 3, 1.f, nullptr, nullptr, nullptr, nullptr), "null output"));
 
-  printf("%d checks, %d failed\n", g_checks, g_fail);
-  if (g_fail == 0) printf("ALL CLUSTER DECOMPOSITION HOST CHECKS PASSED\n");
-  return g_fail ? 1 : 0;
+  return finish("CLUSTER DECOMPOSITION HOST CHECKS");
 }

@@ -1,9 +1,8 @@
 """Cluster growth without a GPU (matcha_amd/sweep.py, csrc/grow.hip's host side): the two entry points and their refusals
 before any device call, the twin rule's "exactly one non-twin per distinct row" on random beams (tests/grow_ref.py), the g17 fixture's
-consistency, the fp32 oracle on its rows, the wrappers' and the CLI's checks, and the host side alone under ASan + UBSan."""
+consistency, the fp32 oracle on its rows, and the wrappers' and the CLI's checks.  (The host side alone under ASan + UBSan: tests/test_cpu_host_checks.py.)"""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -237,18 +236,3 @@ def test_cli_line_check(tmp_path):
     ap_error = pytest.raises(SystemExit)
     with ap_error:
         PR.main(["grow", "-i", path, "--chrom", "0"])                    # --max-size is required
-
-
-def test_growth_host_side_under_asan_ubsan():
-    csrc = os.path.join(ROOT, "matcha_amd", "csrc")
-    build = subprocess.run(["make", "-C", csrc, "-j", str(min(8, os.cpu_count() or 1)), "host-asan-grow"], capture_output=True, text=True)
-    assert build.returncode == 0, build.stdout[-3000:] + build.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    for k in list(env):
-        if k.startswith("MATCHA_DISABLE") or k == "MATCHA_FUSED_DBG":
-            env.pop(k)
-    run = subprocess.run([os.path.join(ROOT, "build", "host_asan", "grow_checks")], capture_output=True, text=True, env=env, timeout=600)
-    out = run.stdout + run.stderr
-    assert run.returncode == 0, out[-4000:]
-    assert "ALL CLUSTER GROWTH HOST CHECKS PASSED" in out
-    assert "AddressSanitizer" not in out and "runtime error" not in out, out[-4000:]

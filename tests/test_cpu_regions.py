@@ -1,11 +1,10 @@
 """The multi-region sweep without a GPU (matcha_amd/sweep.py, csrc/sweep_rows.hip's host side): the two entry points and their
 refusals before any device call, region_count / region_unrank against itertools, the g18 fixture's consistency, the wrappers' and the
-CLI parser's checks, and the host side alone under ASan + UBSan."""
+CLI parser's checks.  (The host side alone under ASan + UBSan: tests/test_cpu_host_checks.py.)"""
 import ctypes as C
 import itertools
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -270,18 +269,3 @@ def test_region_cli_part_parser():
         with pytest.raises(ValueError) as e:
             PR.parse_parts(specs, TINY, names)
         assert word in str(e.value), (specs, str(e.value))
-
-
-def test_region_host_side_under_asan_ubsan():
-    csrc = os.path.join(ROOT, "matcha_amd", "csrc")
-    build = subprocess.run(["make", "-C", csrc, "-j", str(min(8, os.cpu_count() or 1)), "host-asan-regions"], capture_output=True, text=True)
-    assert build.returncode == 0, build.stdout[-3000:] + build.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    for k in list(env):
-        if k.startswith("MATCHA_DISABLE") or k == "MATCHA_FUSED_DBG":
-            env.pop(k)
-    run = subprocess.run([os.path.join(ROOT, "build", "host_asan", "region_checks")], capture_output=True, text=True, env=env, timeout=600)
-    out = run.stdout + run.stderr
-    assert run.returncode == 0, out[-4000:]
-    assert "ALL MULTI-REGION HOST CHECKS PASSED" in out
-    assert "AddressSanitizer" not in out and "runtime error" not in out, out[-4000:]

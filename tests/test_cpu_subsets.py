@@ -1,10 +1,9 @@
 """Cluster decomposition without a GPU (matcha_amd/sweep.py, the host side of csrc/sweep_rows.hip and csrc/sweep_support.hip): the new entry points and their
 refusals before any device call, counts and unranking against the itertools twin (tests/subsets_ref.py), the g16 fixture's consistency,
-the fp32 oracle on its rows, the CLI's line check, and the host side alone under ASan + UBSan as a stand-alone program."""
+the fp32 oracle on its rows, and the CLI's line check.  (The host side alone under ASan + UBSan: tests/test_cpu_host_checks.py.)"""
 import ctypes as C
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -280,21 +279,3 @@ def test_cli_line_check(tmp_path):
     _write_lines(path, [[5], list(range(32))])
     with pytest.raises(ValueError, match=r"line 2 has 32 distinct bins"):
         PR.parse_cluster_file(path, bin2node, ["chr1"], 100)
-
-
-def test_decomposition_host_side_under_asan_ubsan():
-    """tests/host/subsets_checks.hip: a stand-alone driver with its own main on the host-only objects of tests/test_cpu_host_sanitizers.py --
-    the count against a 128-bit restatement over a grid that includes every integer extreme, every refusal with its message, the no-op
-    forms.  Nothing is loaded into Python, no kernel is launched."""
-    csrc = os.path.join(ROOT, "matcha_amd", "csrc")
-    build = subprocess.run(["make", "-C", csrc, "-j", str(min(8, os.cpu_count() or 1)), "host-asan-subsets"], capture_output=True, text=True)
-    assert build.returncode == 0, build.stdout[-3000:] + build.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    for k in list(env):
-        if k.startswith("MATCHA_DISABLE") or k == "MATCHA_FUSED_DBG":
-            env.pop(k)
-    run = subprocess.run([os.path.join(ROOT, "build", "host_asan", "subsets_checks")], capture_output=True, text=True, env=env, timeout=600)
-    out = run.stdout + run.stderr
-    assert run.returncode == 0, out[-4000:]
-    assert "ALL CLUSTER DECOMPOSITION HOST CHECKS PASSED" in out
-    assert "AddressSanitizer" not in out and "runtime error" not in out, out[-4000:]
