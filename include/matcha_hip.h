@@ -697,6 +697,39 @@ int matcha_corrcoef_block(const float* adj, int64_t ld, int32_t n, float* out, v
                           matcha_stream_t stream);
 int matcha_zscore_rows(float* matrix, int64_t rows, int64_t cols, matcha_stream_t stream);
 
+/* ---- contact matrices from the clusters (Code/process.py:90-105 edgelist2adj; History_version/Code/main_drop.py:543-563 get_adjacency;
+ * DESIGN.md 7.18; csrc/cluster_adj.hip) --------------------------------------------------------------------------------------------
+ * Clusters as CSR: ids device int32 [I], node ids 1 .. n_nodes strictly ascending inside a cluster; offsets int64 [M + 1] with
+ * offsets[M] = I; a cluster holds 2 .. 65535 nodes (clusters of 0 or 1 nodes have no pairs and are passed over).
+ * matcha_cluster_pairs_count   host only: the sum over the clusters of s (s - 1) / 2 from a HOST copy of offsets; -1 when a cluster has more
+ *     than 65535 nodes (or a negative length), the sum leaves int63, or an argument is invalid.
+ * matcha_cluster_adj_update    q device int64 [M]: the clusters' weights in fixed point, rint(w 2^32); pair_ptr device int64 [M + 1]: pair_ptr[0]
+ *     = 0, pair_ptr[c + 1] = pair_ptr[c] + s_c (s_c - 1) / 2 (made on the host).  Every pair i < j of every cluster adds q[c] to
+ *     acc[(id_i - 1) n_nodes + (id_j - 1)] with one 64-bit integer atomic: acc, device int64 [n_nodes, n_nodes], is caller-owned, zeroed by the
+ *     caller before the first call and carried from call to call; only its upper triangle is written.  The result does not depend on the order
+ *     of the adds, of the clusters or on how the clusters are cut into calls.  The caller keeps the sum of |q| below 2^62 (a cell receives at
+ *     most one add per cluster).  A cluster whose ids are not strictly ascending or leave 1 .. n_nodes, or whose offsets disagree with
+ *     pair_ptr, adds nothing and sets status[0] |= MATCHA_STATUS_BAD_ID (status: optional device int32[4]).  M = 0 launches nothing.
+ *     cluster_pairs_update_kernel: 2048 blocks, every wavefront one contiguous run of global pair ranks.
+ * matcha_cluster_adj_finish    acc -> float64 matrices, value double(acc) 2^-32 in the cell and in its mirror, diagonal 0: with inter_or_null the
+ *     cell goes to intra when node2chrom[id_i] == node2chrom[id_j] (device int32 [n_nodes + 1], entry 0 unused) and to inter otherwise, the
+ *     other matrix's cell is written 0; without it everything goes to intra (edgelist2adj's matrix; node2chrom may be NULL).  Overwrites every
+ *     element of its outputs; acc is left as it is.  cluster_adj_finish_kernel.
+ * matcha_block_colmax_normalise   get_adjacency(norm=True): for every range k, rows [ranges[2 k], ranges[2 k + 1]) (device int64 [n_ranges, 2],
+ *     0-based, clipped to [0, n_nodes); the ranges must not overlap) and every column: A[rows, col] /= max(A[rows, col]) + 1e-10, float64, in
+ *     place on A [n_nodes, n_nodes].  ws (matcha_block_colmax_workspace_bytes, 8-byte aligned) keeps the maxima as float64 [n_ranges, n_nodes].
+ *     n_ranges = 0 launches nothing.  block_colmax_normalise_kernel.
+ * Every refusal (a null pointer, n_nodes < 1, M or n_ranges out of range, a workspace that is too small) is MATCHA_EINVAL with a message,
+ * before any device call. */
+int64_t matcha_cluster_pairs_count(const int64_t* offsets_host, int64_t M);
+int matcha_cluster_adj_update(const int32_t* ids, const int64_t* offsets, const int64_t* q, const int64_t* pair_ptr, int64_t M,
+                              int32_t n_nodes, int64_t* acc, int32_t* status, matcha_stream_t stream);
+int matcha_cluster_adj_finish(const int64_t* acc, const int32_t* node2chrom, int32_t n_nodes, double* intra, double* inter_or_null,
+                              matcha_stream_t stream);
+size_t matcha_block_colmax_workspace_bytes(int32_t n_nodes, int32_t n_ranges);
+int matcha_block_colmax_normalise(double* A, int32_t n_nodes, const int64_t* ranges, int32_t n_ranges, void* ws, size_t ws_bytes,
+                                  matcha_stream_t stream);
+
 /* ---- denoised contact maps (Code/denoise_contact.py:147-207) ----------------------------------------------------------
  * One chromosome [lo, hi) of chrom_range, n = hi - lo bins, pairs (i, j) with i + min_dis <= j in generate_pair_wise order: row
  * r = i - lo holds max(0, n - min_dis - r) pairs, stored contiguously.  Bit for bit with the reference's numpy for the same inputs.

@@ -144,6 +144,11 @@ SIGNATURES = {
     "matcha_corrcoef_workspace_bytes": (_SZ, [_I32]),
     "matcha_corrcoef_block": (C.c_int, [_fp, _I64, _I32, _fp, _fp, _SZ, _fp]),
     "matcha_zscore_rows": (C.c_int, [_fp, _I64, _I64, _fp]),
+    "matcha_cluster_pairs_count": (_I64, [_fp, _I64]),
+    "matcha_cluster_adj_update": (C.c_int, [_fp, _fp, _fp, _fp, _I64, _I32, _fp, _fp, _fp]),
+    "matcha_cluster_adj_finish": (C.c_int, [_fp, _fp, _I32, _fp, _fp, _fp]),
+    "matcha_block_colmax_workspace_bytes": (_SZ, [_I32, _I32]),
+    "matcha_block_colmax_normalise": (C.c_int, [_fp, _I32, _fp, _I32, _fp, _SZ, _fp]),
     "matcha_denoise_workspace_bytes": (_SZ, [_I32]),
     "matcha_denoise_intra": (C.c_int, [_fp, _I64, _I32, _I32, _fp, _I64, _fp, _fp, _fp, _fp, _fp, _SZ, _fp]),
     "matcha_denoise_pixels": (C.c_int, [_fp, _I32, _I32, _fp, _fp]),

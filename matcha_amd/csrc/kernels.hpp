@@ -297,4 +297,7 @@ size_t attn_long_bwd_slab_bytes(int64_t B, int d);
 int launch_attn_long_bwd(const float* Q, const float* K, const float* V, const float* dO, const int32_t* row_off, int64_t B, int L, int d,
                          int64_t kv_ld, int kv_head, float* dQ, float* dK, float* dV, float* slab, hipStream_t st);
 
+// cluster_adj.hip: contact matrices from the clusters (matcha_cluster_adj_update / _finish, matcha_block_colmax_normalise).  Its entries are
+// its only launchers; what other code may share is the pair unrank of cluster_unrank.hpp (tri_unrank, kMaxClusterNodes).
+
 }  // namespace matcha

@@ -6,9 +6,14 @@ file -> ``edge_list.npy``, cooler pixels -> ``intra_adj.npy`` / ``inter_adj.npy`
   parse_clusters    process.py:42-87    SPRITE-style cluster file (id <tab> chr:pos <tab> ...) -> sorted unique node lists
   cool_index2node   process.py:121-137  cooler bin table -> node id per cooler bin (0 = not in chrom_list)
   pixels_to_adj     process.py:144-176  pixels -> intra / inter adjacency, accumulated on the device (csrc/features.hip)
+  edgelist2adj      process.py:90-105   edge_list.npy -> edge_list_adj.npy, every cluster projected onto its pairs
+  ClusterAdj / clusters_to_adj          the same projection as a stream: clusters -> intra / inter adjacency (or one matrix, with the
+                                        History version's per-hyperedge weights and block-maximum normalisation, main_drop.py:543-563),
+                                        accumulated on the device in int64 fixed point (csrc/cluster_adj.hip)
 
 Reading the .mcool container itself (h5py) is out of scope: ``pixels_to_adj`` takes the arrays ``f['pixels']['bin1_id']``,
-``['bin2_id']`` and ``['balanced']`` / ``['count']`` hold, in chunks of any size.
+``['bin2_id']`` and ``['balanced']`` / ``['count']`` hold, in chunks of any size.  ``main(["--adj-from", "clusters"])`` needs no container:
+the adjacency comes from the cluster file.
 """
 from __future__ import annotations
 
@@ -141,6 +146,208 @@ def pixels_to_adj(bin1, bin2, count, index2node, node2chrom, n_nodes: int, out: 
     return intra, inter
 
 
+# ---- contact matrices from the clusters ---------------------------------------------------------------------------------
+MAX_ADJ_CLUSTER = 65535          # csrc/cluster_unrank.hpp kMaxClusterNodes: every local pair rank stays below 2^31
+_Q_ONE = 1 << 32                 # the fixed point: q = rint(w 2^32)
+_Q_SUM_LIMIT = 1 << 62           # bound on the running sum of |q|: a cell receives at most one add per cluster
+
+
+def _clusters_csr(clusters):
+    """(ids int32 [I], offsets int64 [M + 1]) from a list of id lists or from an (ids, offsets) TUPLE of two arrays / tensors."""
+    if isinstance(clusters, tuple) and len(clusters) == 2 and all(isinstance(t, (np.ndarray, torch.Tensor)) for t in clusters):
+        clusters = tuple(t.cpu().numpy() if isinstance(t, torch.Tensor) else t for t in clusters)
+        ids = np.ascontiguousarray(np.asarray(clusters[0]), dtype=np.int32)
+        offsets = np.ascontiguousarray(np.asarray(clusters[1]), dtype=np.int64)
+        if offsets.ndim != 1 or len(offsets) < 1 or offsets[0] != 0 or (np.diff(offsets) < 0).any() or offsets[-1] != ids.size or ids.ndim != 1:
+            raise ValueError("(ids, offsets): offsets must start at 0, not decrease and end at len(ids)")
+        return ids, offsets
+    lens = np.fromiter((len(c) for c in clusters), dtype=np.int64, count=len(clusters))
+    offsets = np.zeros(len(clusters) + 1, dtype=np.int64)
+    np.cumsum(lens, out=offsets[1:])
+    ids = np.concatenate([np.asarray(c, dtype=np.int32).reshape(-1) for c in clusters]) if int(offsets[-1]) else np.zeros(0, dtype=np.int32)
+    return np.ascontiguousarray(ids, dtype=np.int32), offsets
+
+
+def cluster_weights_q(lens: np.ndarray, weight) -> np.ndarray:
+    """The clusters' fixed-point weights q = rint(w 2^32) as int64, computed in float64: ``"one"`` (edgelist2adj), ``"two_over_n"`` (2 / n for
+    a cluster of n nodes) or one float per cluster (get_adjacency's ``weight``).  Weights must be finite and below 2^30 in magnitude."""
+    lens = np.asarray(lens, dtype=np.int64)
+    if isinstance(weight, str):
+        if weight == "one":
+            w = np.ones(len(lens), dtype=np.float64)
+        elif weight == "two_over_n":
+            w = 2.0 / np.maximum(lens, 1).astype(np.float64)
+        else:
+            raise ValueError("weight must be 'one', 'two_over_n' or an array, not %r" % (weight,))
+    else:
+        w = np.asarray(weight, dtype=np.float64).reshape(-1)
+        if len(w) != len(lens):
+            raise ValueError("%d weights for %d clusters" % (len(w), len(lens)))
+    if not np.isfinite(w).all():
+        raise ValueError("cluster weights must be finite")
+    if len(w) and np.abs(w).max() >= float(1 << 30):
+        raise ValueError("cluster weights must be below 2^30 in magnitude")
+    return np.rint(w * float(_Q_ONE)).astype(np.int64)
+
+
+class ClusterAdj:
+    """Clusters -> contact matrices, accumulated on the device (csrc/cluster_adj.hip).  Every cluster adds its weight to every pair of its
+    nodes, as the reference's ``edgelist2adj`` (process.py:90-105) and the History version's ``get_adjacency`` (main_drop.py:543-563) do; the
+    sums are int64 in 2^-32 fixed point, so the matrices do not depend on the order of the clusters or on how they are cut into ``update``
+    calls.  ``node2chrom``: the dict of ``build_node_dict`` or an int array [n_nodes + 1] (entry 0 unused); it may be None when only
+    ``finish(split=False)`` is wanted.  There is no CPU path."""
+
+    def __init__(self, n_nodes: int, node2chrom=None, device="cuda"):
+        n_nodes = int(n_nodes)
+        if n_nodes < 1:
+            raise ValueError("n_nodes must be >= 1")
+        self.n_nodes = n_nodes
+        self.device = torch.device(device)
+        if node2chrom is None:
+            self._n2c_host = None
+        else:
+            n2c = node2chrom_array(node2chrom, n_nodes) if isinstance(node2chrom, dict) else np.asarray(node2chrom, dtype=np.int32)
+            if len(n2c) < n_nodes + 1:
+                raise ValueError("node2chrom must cover node ids 0 .. n_nodes")
+            self._n2c_host = np.ascontiguousarray(n2c[:n_nodes + 1], dtype=np.int32)
+        self.q_abs_sum = 0               # the running sum of |q| over every accepted update, a Python int
+        self.n_pairs = 0
+        self._acc = self._status = self._n2c = None
+
+    def _state(self):
+        if self._acc is None:
+            if self.device.type != "cuda" or not torch.cuda.is_available():
+                raise _lib.MatchaHipError("ClusterAdj needs a cuda device (no CPU fallback)")
+            _lib.load()
+            self._acc = torch.zeros((self.n_nodes, self.n_nodes), dtype=torch.int64, device=self.device)
+            self._status = torch.zeros(4, dtype=torch.int32, device=self.device)
+            self._n2c = None if self._n2c_host is None else torch.from_numpy(self._n2c_host).to(self.device)
+        return self._acc
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def update(self, clusters, weight="one"):
+        """Add ``clusters`` (a list of ascending id lists, or an ``(ids, offsets)`` pair) with ``weight`` = "one" | "two_over_n" | one float per
+        cluster.  Refused with ValueError before anything runs: a non-finite weight, a cluster of more than 65535 nodes, and an update that
+        would take the running sum of |q| to 2^62.  Ids that are not strictly ascending or leave 1 .. n_nodes are found on the device: such a
+        cluster adds nothing and ``status()[0]`` gets STATUS_BAD_ID."""
+        lib = _lib.load()
+        ids, offsets = _clusters_csr(clusters)
+        M = len(offsets) - 1
+        lens = np.diff(offsets)
+        q = cluster_weights_q(lens, weight)
+        total = lib.matcha_cluster_pairs_count(offsets.ctypes.data_as(C.c_void_p), M)
+        if total < 0:
+            raise ValueError("a cluster has more than %d nodes (or the pair count leaves int63)" % MAX_ADJ_CLUSTER)
+        q_sum = int(np.abs(q).astype(object).sum()) if M else 0
+        if self.q_abs_sum + q_sum >= _Q_SUM_LIMIT:
+            raise ValueError("the clusters' weights sum to %.6g or more: the fixed-point sums are bounded by 2^30"
+                             % ((self.q_abs_sum + q_sum) / float(_Q_ONE)))
+        acc = self._state()
+        if M == 0 or total == 0:
+            return self
+        pair_ptr = np.zeros(M + 1, dtype=np.int64)
+        np.cumsum(lens * (lens - 1) // 2, out=pair_ptr[1:])
+        dev = self.device
+        ids_d, off_d = torch.from_numpy(ids).to(dev), torch.from_numpy(offsets).to(dev)
+        q_d, ptr_d = torch.from_numpy(q).to(dev), torch.from_numpy(pair_ptr).to(dev)
+        _lib.check(lib.matcha_cluster_adj_update(_lib.ptr(ids_d), _lib.ptr(off_d), _lib.ptr(q_d), _lib.ptr(ptr_d), M, self.n_nodes, _lib.ptr(acc),
+                                                 _lib.ptr(self._status), self._stream()), "matcha_cluster_adj_update")
+        self.q_abs_sum += q_sum
+        self.n_pairs += int(total)
+        return self
+
+    def finish(self, split: bool = True):
+        """(intra, inter) float64 [n_nodes, n_nodes] on the device, or with ``split=False`` the one matrix of ``edgelist2adj``.  Symmetric,
+        zero diagonal; the accumulator is kept, so more updates may follow."""
+        lib = _lib.load()
+        acc = self._state()
+        N = self.n_nodes
+        intra = torch.empty((N, N), dtype=torch.float64, device=self.device)
+        if split:
+            if self._n2c is None:
+                raise ValueError("finish(split=True) needs node2chrom")
+            inter = torch.empty((N, N), dtype=torch.float64, device=self.device)
+            _lib.check(lib.matcha_cluster_adj_finish(_lib.ptr(acc), _lib.ptr(self._n2c), N, _lib.ptr(intra), _lib.ptr(inter), self._stream()),
+                       "matcha_cluster_adj_finish")
+            return intra, inter
+        _lib.check(lib.matcha_cluster_adj_finish(_lib.ptr(acc), None, N, _lib.ptr(intra), None, self._stream()), "matcha_cluster_adj_finish")
+        return intra
+
+    def status(self) -> List[int]:
+        """The device status words as a list of 4 ints ([0] & STATUS_BAD_ID: a cluster was rejected)."""
+        self._state()
+        return [int(v) for v in self._status.cpu().tolist()]
+
+
+def block_colmax_normalise_(A: torch.Tensor, ranges) -> torch.Tensor:
+    """In place on the float64 device matrix A [N, N]: for every 0-based row block [lo, hi) of ``ranges`` [C, 2] and every column,
+    A[lo:hi, col] /= A[lo:hi, col].max() + 1e-10 (main_drop.py:552-561)."""
+    lib = _lib.load()
+    if A.dim() != 2 or A.shape[0] != A.shape[1] or A.dtype != torch.float64 or not A.is_contiguous() or A.device.type != "cuda":
+        raise _lib.MatchaHipError("block_colmax_normalise_ needs a contiguous square float64 matrix on a cuda device (no CPU fallback)")
+    N = int(A.shape[0])
+    r = np.ascontiguousarray(np.asarray(ranges, dtype=np.int64).reshape(-1, 2))
+    if len(r) and ((r[:, 0] < 0).any() or (r[:, 1] > N).any() or (r[:, 0] > r[:, 1]).any()):
+        raise ValueError("row blocks must satisfy 0 <= lo <= hi <= %d" % N)
+    order = np.argsort(r[:, 0], kind="stable")
+    if len(r) > 1 and (r[order][1:, 0] < r[order][:-1, 1]).any():
+        raise ValueError("row blocks must not overlap")
+    if len(r) == 0:
+        return A
+    r_d = torch.from_numpy(r).to(A.device)
+    ws_bytes = lib.matcha_block_colmax_workspace_bytes(N, len(r))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=A.device)
+    st = C.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
+    _lib.check(lib.matcha_block_colmax_normalise(_lib.ptr(A), N, _lib.ptr(r_d), len(r), _lib.ptr(ws), ws_bytes, st), "matcha_block_colmax_normalise")
+    return A
+
+
+def clusters_to_adj(clusters, node2chrom, n_nodes: int, weight="one", normalise: Optional[str] = None, chrom_range=None, split: bool = True,
+                    device="cuda"):
+    """One shot: ``ClusterAdj(n_nodes, node2chrom).update(clusters, weight).finish()`` -> (intra, inter) float64 on the device, or with
+    ``split=False`` the one matrix.
+
+    ``normalise="block_max"`` is the History version's ``get_adjacency(norm=True)``: every block of rows of ``chrom_range`` (int [C, 2],
+    1-based node ids, ``[start, end)``, as ``build_node_dict`` writes it) is divided per column by its maximum + 1e-10.  It is applied to the
+    single unsplit matrix, and the split (if asked for) is taken from the normalised matrix.
+
+    Against the reference: ``edgelist2adj`` is ``weight="one", split=False`` on the same 1-based ids (its matrix row is id - 1, as here).
+    ``get_adjacency(data, weight, norm)`` works on 0-based ids ``datum`` and on ``num`` (``nums_type``), the node count per type: pass the
+    clusters as ``datum + 1``, ``weight`` as its per-hyperedge array, and ``chrom_range = [[1 + sum(num[:t]), 1 + sum(num[:t + 1])] for t]``;
+    its result is this function's ``split=False`` matrix cast to float32 (it returns a float32 csr_matrix).  Integer weights are exact, so
+    both are reproduced bit for bit; other weights are rounded once to 2^-32 and then summed exactly."""
+    if normalise not in (None, "block_max"):
+        raise ValueError("normalise must be None or 'block_max', not %r" % (normalise,))
+    if normalise == "block_max" and chrom_range is None:
+        raise ValueError("normalise='block_max' needs chrom_range")
+    ca = ClusterAdj(n_nodes, node2chrom, device=device)
+    ca.update(clusters, weight)
+    if normalise is None:
+        return ca.finish(split=split)
+    A = ca.finish(split=False)
+    block_colmax_normalise_(A, np.asarray(chrom_range, dtype=np.int64).reshape(-1, 2) - 1)
+    if not split:
+        return A
+    if ca._n2c is None:
+        raise ValueError("the split needs node2chrom")
+    n2c = ca._n2c[1:].to(torch.int64)
+    same = n2c[:, None] == n2c[None, :]
+    zero = torch.zeros((), dtype=A.dtype, device=A.device)
+    return torch.where(same, A, zero), torch.where(same, zero, A)
+
+
+def edgelist2adj(temp_dir: str, device="cuda") -> np.ndarray:
+    """process.py:90-105: ``edge_list.npy`` + ``chrom_range.npy`` -> ``edge_list_adj.npy``, float64 [N, N] with N = max(chrom_range) - 1."""
+    edge_list = np.load(os.path.join(temp_dir, "edge_list.npy"), allow_pickle=True)
+    chrom_range = np.load(os.path.join(temp_dir, "chrom_range.npy"), allow_pickle=True)
+    N = int(np.max(chrom_range)) - 1
+    adj = clusters_to_adj([list(e) for e in edge_list], None, N, weight="one", split=False, device=device).cpu().numpy()
+    np.save(os.path.join(temp_dir, "edge_list_adj.npy"), adj)
+    return adj
+
+
 def save_adj(temp_dir: str, intra: torch.Tensor, inter: torch.Tensor):
     """process.py:175-176."""
     np.save(os.path.join(temp_dir, "intra_adj.npy"), intra.cpu().numpy())
@@ -148,12 +355,17 @@ def save_adj(temp_dir: str, intra: torch.Tensor, inter: torch.Tensor):
 
 
 def main(argv=None):
-    """The script body of process.py:229-242: node dictionaries, edge_list.npy and -- when h5py is importable, it is not part
-    of this image -- the adjacency matrices from ``mcool_path``, streamed through the device 16 M pixels at a time."""
+    """The script body of process.py:229-242: node dictionaries, edge_list.npy and the adjacency matrices -- with ``--adj-from mcool`` (the
+    default) from ``mcool_path`` when h5py is importable (it is not part of this image), streamed through the device 16 M pixels at a time;
+    with ``--adj-from clusters`` from the cluster file itself (ClusterAdj), which needs no h5py."""
     import argparse
     import json
     ap = argparse.ArgumentParser(description="process.py on the MI355X path")
     ap.add_argument("--config", default="./config.JSON")
+    ap.add_argument("--adj-from", choices=["mcool", "clusters"], default="mcool", help="where intra_adj.npy / inter_adj.npy come from")
+    ap.add_argument("--adj-weight", choices=["one", "two_over_n"], default="one", help="--adj-from clusters: a cluster's weight per pair")
+    ap.add_argument("--adj-max-cluster-size", type=int, default=None,
+                    help="--adj-from clusters: largest cluster that enters the contact matrix (default: the config's max_cluster_size)")
     args = ap.parse_args(argv)
     with open(args.config) as f:
         config = json.load(f)
@@ -161,15 +373,32 @@ def main(argv=None):
     bin2node, _, node2chrom, chrom_range = build_node_dict(config["chrom_size"], chrom_list, res, temp_dir)
     clusters = parse_clusters(config["cluster_path"], bin2node, chrom_list, res, config["max_cluster_size"], temp_dir)
     print("%d nodes, %d clusters" % (int(chrom_range.max()) - 1, len(clusters)))
+    N = int(chrom_range.max()) - 1
+    if args.adj_from == "clusters":
+        bound = config["max_cluster_size"] if args.adj_max_cluster_size is None else args.adj_max_cluster_size
+        if bound > MAX_ADJ_CLUSTER:
+            raise SystemExit("--adj-max-cluster-size is at most %d" % MAX_ADJ_CLUSTER)
+        adj_clusters = clusters if bound == config["max_cluster_size"] else parse_clusters(config["cluster_path"], bin2node, chrom_list, res, bound)
+        ca = ClusterAdj(N, node2chrom)
+        step = 1 << 20                                                          # clusters per update
+        for s in range(0, len(adj_clusters), step):
+            ca.update(adj_clusters[s:s + step], args.adj_weight)
+        intra, inter = ca.finish()
+        if ca.status()[0] & _lib.STATUS_BAD_ID:
+            raise IndexError("a cluster with ids that are not ascending or outside 1 .. %d was left out" % N)
+        print("%d clusters, %d pairs -> intra_adj.npy / inter_adj.npy" % (len(adj_clusters), ca.n_pairs))
+        save_adj(temp_dir, intra, inter)
+        return
     try:
         import h5py
     except ImportError:
-        raise SystemExit("h5py is not installed: load the cooler's bins / pixels yourself and call process.pixels_to_adj")
+        raise SystemExit("h5py is not installed: load the cooler's bins / pixels yourself and call process.pixels_to_adj, or build the "
+                         "adjacency from the cluster file with --adj-from clusters")
     f = h5py.File(config["mcool_path"], "r")["resolutions"][str(res)]
     i2n = cool_index2node(np.array(f["bins"]["chrom"]), np.array(f["bins"]["start"]), np.array(f["chroms"]["name"]).astype("str"),
                           chrom_list, bin2node)
     weights = f["pixels"]["balanced"] if "balanced" in f["pixels"].keys() else f["pixels"]["count"]       # process.py:147-150
-    N, out, step = int(chrom_range.max()) - 1, None, 1 << 24
+    out, step = None, 1 << 24
     for s in range(0, len(weights), step):
         out = pixels_to_adj(f["pixels"]["bin1_id"][s:s + step], f["pixels"]["bin2_id"][s:s + step], weights[s:s + step], i2n, node2chrom, N, out=out)
     save_adj(temp_dir, *out)
