@@ -730,6 +730,47 @@ size_t matcha_block_colmax_workspace_bytes(int32_t n_nodes, int32_t n_ranges);
 int matcha_block_colmax_normalise(double* A, int32_t n_nodes, const int64_t* ranges, int32_t n_ranges, void* ws, size_t ws_bytes,
                                   matcha_stream_t stream);
 
+/* ---- the cluster file's text -> clusters in CSR form (Code/process.py:42-87 parse_file; csrc/cluster_text.hip) -----------
+ * One chunk of WHOLE lines of a SPRITE-style cluster file (id <tab> chr:pos <tab> ...), as bytes on the device, becomes the CSR that
+ * matcha_kmer_generate and matcha_cluster_adj_update take: ids device int32, offsets device int64.  Integer work: for every text it accepts
+ * the result is the reference's parse_file bit for bit.
+ *   lines      every '\r' and every '\n' ends a line; a last line without a terminator counts
+ *   strip      leading / trailing bytes 0x09-0x0d, 0x1c-0x1f, 0x20 are removed, the rest is split on '\t', the first field (the id) is dropped
+ *   pre-filter a line of fewer than 2 or more than 50 max_cluster_size items is skipped unparsed: nothing on it is an error
+ *   items      exactly one ':' (else _ESPLIT); an item whose name is not in the table is dropped before its position is read; node id =
+ *              first_node + floor(position / res); a bin >= n_bins is _EBIN
+ *   cluster    ids de-duplicated and ascending; kept when 2 <= ids <= max_cluster_size; kept clusters stay in file order
+ * NARROWER than Python's int(): a position is 1 .. 18 ASCII digits.  "+5", " 5", "2_500", "-5", "x" and the empty string are _EGRAMMAR (the
+ * host parser takes the first three and answers KeyError to the fourth); 19 or more digits are _EBIN; a byte >= 0x80 anywhere in the text,
+ * skipped lines included, is _ENONASCII (Python's strip would also strip some non-ASCII blanks).
+ * The chromosome table (HOST arrays, checked and copied by the call): names char [n_chrom][MATCHA_CLUSTER_TEXT_NAME_MAX], each 1 .. 32 bytes
+ * above 0x20 and below 0x80 without ':', zero-padded, no two alike, compared exactly ("chr1", "chr10" and "chr1_random" are three names);
+ * at most MATCHA_CLUSTER_TEXT_CHROM_MAX = 256 of them; first_node / n_bins int32 [n_chrom] with 1 <= first_node and first_node + n_bins - 1 <=
+ * n_nodes and n_bins * res <= 2^53 (build_node_dict: n_bins = ceil(size / res) + 1).
+ * matcha_cluster_text_count   counts device int64 [2] <- {lines, tabs} of text (device uint8 [n], 16-byte aligned, n < 2^31); lines = terminators
+ *     + 1.  The caller reads them (one host sync per chunk) and sizes the workspace and the outputs from them.
+ * matcha_cluster_text_parse   n_lines / n_tabs as counted (the kernels check them against the text: a mismatch writes nothing and sets _ECOUNT);
+ *     ids [ids_cap >= n_tabs], offsets [offsets_cap >= n_lines + 1]; n_clusters, n_ids device int64 [1]; offsets[0 .. n_clusters] and
+ *     ids[0 .. n_ids) are written.  status device int32 [8], OVERWRITTEN: [0] the MATCHA_CLUSTER_TEXT_E* bits, [1] / [2] / [3] the least byte
+ *     offset of an item that is _ESPLIT / _EBIN / _EGRAMMAR, [4] the least offset of a byte >= 0x80 (INT32_MAX where there is none).  With an
+ *     error bit set the CSR is not to be used.  ws: matcha_cluster_text_workspace_bytes(n, n_lines, n_tabs) bytes, 256-byte aligned.
+ * Every refusal (a size out of range, a null or misaligned pointer, a bad table, a workspace that is too small) is MATCHA_EINVAL with a
+ * message, before any device call. */
+#define MATCHA_CLUSTER_TEXT_NAME_MAX 32
+#define MATCHA_CLUSTER_TEXT_CHROM_MAX 256
+#define MATCHA_CLUSTER_TEXT_ESPLIT 1    /* an item without exactly one ':' (the host parser's EOFError) */
+#define MATCHA_CLUSTER_TEXT_EBIN 2      /* a bin past its chromosome's last (KeyError) */
+#define MATCHA_CLUSTER_TEXT_EGRAMMAR 4  /* a position that is not 1 .. 18 ASCII digits (ValueError) */
+#define MATCHA_CLUSTER_TEXT_ENONASCII 8 /* a byte >= 0x80 (ValueError) */
+#define MATCHA_CLUSTER_TEXT_ECOUNT 16   /* n_lines / n_tabs are not the text's counts */
+size_t matcha_cluster_text_count_workspace_bytes(int64_t n);
+int matcha_cluster_text_count(const uint8_t* text, int64_t n, int64_t* counts, void* ws, size_t ws_bytes, matcha_stream_t stream);
+size_t matcha_cluster_text_workspace_bytes(int64_t n, int64_t n_lines, int64_t n_tabs);
+int matcha_cluster_text_parse(const uint8_t* text, int64_t n, int64_t n_lines, int64_t n_tabs, const char* names, const int32_t* first_node,
+                              const int32_t* n_bins, int32_t n_chrom, int64_t res, int64_t max_cluster_size, int32_t n_nodes, int32_t* ids,
+                              int64_t ids_cap, int64_t* offsets, int64_t offsets_cap, int64_t* n_clusters, int64_t* n_ids, int32_t* status,
+                              void* ws, size_t ws_bytes, matcha_stream_t stream);
+
 /* ---- denoised contact maps (Code/denoise_contact.py:147-207) ----------------------------------------------------------
  * One chromosome [lo, hi) of chrom_range, n = hi - lo bins, pairs (i, j) with i + min_dis <= j in generate_pair_wise order: row
  * r = i - lo holds max(0, n - min_dis - r) pairs, stored contiguously.  Bit for bit with the reference's numpy for the same inputs.

@@ -149,6 +149,11 @@ SIGNATURES = {
     "matcha_cluster_adj_finish": (C.c_int, [_fp, _fp, _I32, _fp, _fp, _fp]),
     "matcha_block_colmax_workspace_bytes": (_SZ, [_I32, _I32]),
     "matcha_block_colmax_normalise": (C.c_int, [_fp, _I32, _fp, _I32, _fp, _SZ, _fp]),
+    "matcha_cluster_text_count_workspace_bytes": (_SZ, [_I64]),
+    "matcha_cluster_text_count": (C.c_int, [_fp, _I64, _fp, _fp, _SZ, _fp]),
+    "matcha_cluster_text_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
+    "matcha_cluster_text_parse": (C.c_int, [_fp, _I64, _I64, _I64, _fp, _fp, _fp, _I32, _I64, _I64, _I32, _fp, _I64, _fp, _I64, _fp, _fp, _fp,
+                                            _fp, _SZ, _fp]),
     "matcha_denoise_workspace_bytes": (_SZ, [_I32]),
     "matcha_denoise_intra": (C.c_int, [_fp, _I64, _I32, _I32, _fp, _I64, _fp, _fp, _fp, _fp, _fp, _SZ, _fp]),
     "matcha_denoise_pixels": (C.c_int, [_fp, _I32, _I32, _fp, _fp]),
@@ -247,6 +252,8 @@ def ptr(t):
 
 
 STATUS_BAD_ID, STATUS_BAD_CHROM = 1, 2      # bits of status[0] (include/matcha_hip.h)
+CLUSTER_TEXT_NAME_MAX, CLUSTER_TEXT_CHROM_MAX = 32, 256      # MATCHA_CLUSTER_TEXT_* of include/matcha_hip.h
+CLUSTER_TEXT_ESPLIT, CLUSTER_TEXT_EBIN, CLUSTER_TEXT_EGRAMMAR, CLUSTER_TEXT_ENONASCII, CLUSTER_TEXT_ECOUNT = 1, 2, 4, 8, 16
 
 
 def set_option(name: str, value: int = 1) -> int:

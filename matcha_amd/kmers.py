@@ -33,20 +33,30 @@ def _csr(clusters: Sequence[Sequence[int]]):
 def generate_kmers(clusters: Sequence[Sequence[int]], size: int, min_dis: int, max_size: int, min_freq_cutoff: int, n_nodes: int = 0,
                    device="cuda", max_combos_per_launch: int = 0) -> Tuple[np.ndarray, np.ndarray]:
     """(kmers int64 [M, size], freq int64 [M]) for one k-mer size (generate_kmers.py:8-69, :86-96).  ``clusters``: sorted
-    unique node-id lists (process.py:66-77).  Launches are split so that each counts fewer than 2^32 candidate subsets AND
+    unique node-id lists (process.py:66-77), or the ``(ids, offsets)`` pair of ``process.parse_clusters_device`` with its ids on the
+    device: they are used where they are, only the offsets come to the host.  Launches are split so that each counts fewer than 2^32 candidate subsets AND
     fits half of the free device memory (``max_combos_per_launch`` lowers the bound further: tests); partial results of
     different launches are merged on the device (a k-mer may occur in several launches)."""
     if max_size > MAX_CLUSTER_LEN:
         raise _lib.MatchaHipError(f"max_cluster_size {max_size} exceeds the device kernel's limit {MAX_CLUSTER_LEN}")
     lib = _lib.load()
-    ids, offsets, lens = _csr(clusters)
-    if n_nodes <= 0:
-        n_nodes = int(ids.max()) if len(ids) else 1
+    dev = torch.device(device)
+    ids_d = None
+    if isinstance(clusters, tuple) and len(clusters) == 2 and isinstance(clusters[0], torch.Tensor) and clusters[0].device.type == "cuda":
+        from .process import device_csr                                 # (ids, offsets) of parse_clusters_device: ids are used where they are,
+        ids_d, offsets = device_csr(clusters, dev)                      # offsets come to the host for the launch splitting below
+        lens = np.diff(offsets)
+        if n_nodes <= 0:
+            n_nodes = int(ids_d.max()) if ids_d.numel() else 1
+    else:
+        ids, offsets, lens = _csr(clusters)
+        if n_nodes <= 0:
+            n_nodes = int(ids.max()) if len(ids) else 1
     per = np.array([math.comb(int(n), size) if size <= n <= max_size else 0 for n in lens], dtype=np.int64)     # :88
     if per.sum() == 0:
         return np.zeros((0, size), dtype=np.int64), np.zeros((0,), dtype=np.int64)
-    dev = torch.device(device)
-    ids_d = torch.from_numpy(ids).to(dev)
+    if ids_d is None:
+        ids_d = torch.from_numpy(ids).to(dev)
     off_d = torch.from_numpy(offsets).to(dev)
     parts = []
     start = 0
@@ -110,13 +120,19 @@ def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(description="k-mer generation (generate_kmers.py) on the MI355X path")
     ap.add_argument("--config", default="./config.JSON")
+    ap.add_argument("--clusters", choices=["npy", "csr"], default="npy",
+                    help="csr: read temp_dir/edge_list_csr.npz (process --parse device) instead of edge_list.npy")
     args = ap.parse_args(argv)
     with open(args.config) as f:
         config = json.load(f)
     temp_dir = config["temp_dir"]
     chrom_range = np.load(os.path.join(temp_dir, "chrom_range.npy"))
     n_nodes = int(np.max(chrom_range))                                  # node ids are 1 .. max(chrom_range) - 1 (generate_kmers.py:80)
-    data = np.load(os.path.join(temp_dir, "edge_list.npy"), allow_pickle=True)
+    if args.clusters == "csr":
+        with np.load(os.path.join(temp_dir, "edge_list_csr.npz")) as z:
+            data = (torch.from_numpy(z["ids"].astype(np.int32)).to("cuda"), z["offsets"].astype(np.int64))
+    else:
+        data = np.load(os.path.join(temp_dir, "edge_list.npy"), allow_pickle=True)
     for size in config["k-mer_size"]:
         rows, freq = generate_kmers(data, size, config["min_distance"], config["max_cluster_size"], config["min_freq_cutoff"], n_nodes)
         if len(rows) > 0:                                               # the reference only writes non-empty results (:133-139)

@@ -4,6 +4,8 @@ file -> ``edge_list.npy``, cooler pixels -> ``intra_adj.npy`` / ``inter_adj.npy`
   build_node_dict   process.py:10-39    chrom sizes -> bin2node / node2bin / node2chrom / chrom_range (node ids from 1;
                                         ceil(size / res) + 1 bins per chromosome, as the reference's ``range(max_bin + 1)``)
   parse_clusters    process.py:42-87    SPRITE-style cluster file (id <tab> chr:pos <tab> ...) -> sorted unique node lists
+  parse_clusters_device                 the same file -> the same clusters as (ids, offsets) device tensors, parsed on the device
+                                        (csrc/cluster_text.hip); ``main(["--parse", "device"])``
   cool_index2node   process.py:121-137  cooler bin table -> node id per cooler bin (0 = not in chrom_list)
   pixels_to_adj     process.py:144-176  pixels -> intra / inter adjacency, accumulated on the device (csrc/features.hip)
   edgelist2adj      process.py:90-105   edge_list.npy -> edge_list_adj.npy, every cluster projected onto its pairs
@@ -18,6 +20,7 @@ the adjacency comes from the cluster file.
 from __future__ import annotations
 
 import ctypes as C
+import io
 import math
 import os
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -96,6 +99,182 @@ def parse_clusters(cluster_path: str, bin2node: Dict[str, int], chrom_list: Sequ
             arr[i] = c
         np.save(os.path.join(temp_dir, "edge_list.npy"), arr, allow_pickle=True)
     return final
+
+
+# ---- the cluster file parsed on the device ------------------------------------------------------------------------------
+CLUSTER_NAME_MAX = _lib.CLUSTER_TEXT_NAME_MAX          # bytes per chromosome name in the device table
+CLUSTER_CHROM_MAX = _lib.CLUSTER_TEXT_CHROM_MAX        # names the table holds
+_STRIP_BYTES = bytes(range(0x09, 0x0e)) + bytes(range(0x1c, 0x21))      # what str.strip() removes from ASCII text
+
+
+def cluster_chrom_table(chrom_list: Sequence[str], chrom_range, res: int):
+    """The device parser's chromosome table from ``chrom_list`` and ``chrom_range`` (int [C, 2], ``[start, end)`` node ids as
+    ``build_node_dict`` writes them): (names uint8 [C, 32] zero-padded, first_node int32 [C], n_bins int32 [C], n_nodes).  ValueError for
+    what the table cannot hold: a duplicate, empty or non-ASCII name, a name with a blank, a control byte or a colon, a name longer than
+    32 bytes, more than 256 names, a resolution outside 1 .. 2^31 - 1, a chromosome of more than 2^53 / res bins."""
+    names = list(chrom_list)
+    cr = np.asarray(chrom_range, dtype=np.int64).reshape(-1, 2)
+    if len(cr) != len(names):
+        raise ValueError("%d chromosome names for %d rows of chrom_range" % (len(names), len(cr)))
+    if not 1 <= len(names) <= CLUSTER_CHROM_MAX:
+        raise ValueError("the device parser's table holds 1 .. %d chromosome names, not %d" % (CLUSTER_CHROM_MAX, len(names)))
+    if isinstance(res, bool) or int(res) != res or not 1 <= int(res) < (1 << 31):
+        raise ValueError("res must be an integer in 1 .. 2^31 - 1, not %r" % (res,))
+    res = int(res)
+    table = np.zeros((len(names), CLUSTER_NAME_MAX), dtype=np.uint8)
+    seen = set()
+    for c, name in enumerate(names):
+        if not isinstance(name, str):
+            raise ValueError("chromosome name %r is not a string" % (name,))
+        try:
+            raw = name.encode("ascii")
+        except UnicodeEncodeError:
+            raise ValueError("chromosome name %r is not ASCII" % (name,))
+        if not raw:
+            raise ValueError("chromosome name %d is empty" % c)
+        if any(b <= 0x20 or b == 0x3a for b in raw):
+            raise ValueError("chromosome name %r holds a blank, a tab, a control byte or a colon" % (name,))
+        if len(raw) > CLUSTER_NAME_MAX:
+            raise ValueError("chromosome name %r is longer than %d bytes" % (name, CLUSTER_NAME_MAX))
+        if raw in seen:
+            raise ValueError("chromosome name %r is listed twice" % (name,))
+        seen.add(raw)
+        table[c, :len(raw)] = np.frombuffer(raw, dtype=np.uint8)
+    first, bins = cr[:, 0], cr[:, 1] - cr[:, 0]
+    n_nodes = int(cr.max()) - 1
+    if (first < 1).any() or (bins < 1).any() or n_nodes >= (1 << 31) - 1:
+        raise ValueError("chrom_range rows must be [start, end) with 1 <= start < end < 2^31")
+    if (bins > (1 << 53) // res).any():
+        raise ValueError("a chromosome has more than 2^53 / res bins: its positions leave float64's integers")
+    return table, np.ascontiguousarray(first, dtype=np.int32), np.ascontiguousarray(bins, dtype=np.int32), n_nodes
+
+
+def _text_chunks(src, chunk_bytes: int):
+    """Cut a cluster file (a path, or bytes) into runs of whole lines of at most ``chunk_bytes`` bytes: yields (file offset, buffer, length);
+    ``buffer[:length]`` ends behind a ``\\r`` or ``\\n`` (found with ``rfind``) except at the end of the file, and is valid until the next
+    chunk is asked for.  A line longer than ``chunk_bytes`` raises ValueError naming the byte offset it starts at."""
+    chunk_bytes = int(chunk_bytes)
+    if not 1 <= chunk_bytes < (1 << 31):
+        raise ValueError("chunk_bytes must be in 1 .. 2^31 - 1, not %d" % chunk_bytes)
+    if isinstance(src, (bytes, bytearray, memoryview)):
+        f, total = io.BytesIO(src), len(src)
+    else:
+        f = open(os.fspath(src), "rb")
+        total = os.fstat(f.fileno()).st_size
+    with f:
+        buf = bytearray(max(1, min(chunk_bytes, total)))
+        view = memoryview(buf)
+        base = have = 0                                                       # the file offset of buf[0]; bytes in buf
+        while True:
+            while have < len(buf):
+                got = f.readinto(view[have:])
+                if not got:
+                    break
+                have += got
+            if have < len(buf):                                               # the end of the file: what is left is the last chunk
+                if have:
+                    yield base, buf, have
+                return
+            cut = max(buf.rfind(b"\n", 0, have), buf.rfind(b"\r", 0, have)) + 1
+            if cut == 0:
+                if f.read(1):
+                    raise ValueError("the line at byte offset %d is longer than chunk_bytes = %d" % (base, chunk_bytes))
+                yield base, buf, have                                         # the file ends with the buffer
+                return
+            yield base, buf, cut
+            buf[:have - cut] = buf[cut:have]
+            base, have = base + cut, have - cut
+
+
+def _raise_cluster_text_error(st, base: int, buf, length: int):
+    """The device status of one chunk as the exception the host parser raises for the FIRST offending item of the file."""
+    if st[0] & _lib.CLUSTER_TEXT_ECOUNT:
+        raise _lib.MatchaHipError("parse_clusters_device: the chunk's line and tab counts changed between the count and the parse")
+    found = [(st[word], rank) for rank, (bit, word) in enumerate(((_lib.CLUSTER_TEXT_ESPLIT, 1), (_lib.CLUSTER_TEXT_EBIN, 2),
+                                                                  (_lib.CLUSTER_TEXT_EGRAMMAR, 3), (_lib.CLUSTER_TEXT_ENONASCII, 4))) if st[0] & bit]
+    off, rank = min(found)
+    if rank == 3:
+        raise ValueError("byte offset %d: byte 0x%02x is not ASCII (the device parser takes ASCII text only)" % (base + off, buf[off]))
+    end = off
+    while end < length and buf[end] not in b"\t\r\n":
+        end += 1
+    item = bytes(buf[off:end]).rstrip(_STRIP_BYTES).decode("ascii", "backslashreplace")
+    where = "byte offset %d: item %r" % (base + off, item)
+    if rank == 0:
+        raise EOFError(where + " is not chrom:position")
+    if rank == 1:
+        raise KeyError(where + " lies past the last bin of its chromosome")
+    raise ValueError(where + ": the position must be 1 to 18 ASCII digits")
+
+
+def parse_clusters_device(cluster_path_or_bytes, chrom_list: Sequence[str], chrom_range, res: int, max_cluster_size: int,
+                          chunk_bytes: int = 1 << 28, device="cuda") -> Tuple[torch.Tensor, torch.Tensor]:
+    """``parse_clusters`` on the device (csrc/cluster_text.hip): the cluster file (a path, or its bytes) -> the clusters in CSR
+    form, (ids int32 [I], offsets int64 [M + 1]) device tensors, which ``ClusterAdj.update`` and ``kmers.generate_kmers`` take as they are.
+    For every text it accepts, the CSR equals ``parse_clusters``'s lists bit for bit; an empty file, or one without a kept cluster, gives
+    ids [0] and offsets [0].  The host reads the file in chunks of whole lines of at most ``chunk_bytes`` bytes.
+
+    Errors keep the host parser's classes and name the byte offset and the text of the first offending item: EOFError for an item that is
+    not ``chrom:position``, KeyError for a bin past its chromosome, ValueError for a position that is no number.  The grammar is narrower
+    than ``int()``'s: a position is 1 to 18 ASCII digits (``+5``, `` 5``, ``2_500`` and ``-5`` are ValueError, 19 or more digits KeyError), and
+    a byte >= 0x80 anywhere in the file is ValueError.  ``cluster_chrom_table`` lists what the chromosome table refuses.  There is no CPU
+    path: without a GPU this raises MatchaHipError."""
+    names, first, bins, n_nodes = cluster_chrom_table(chrom_list, chrom_range, res)
+    max_cluster_size = int(max_cluster_size)
+    if not 1 <= max_cluster_size <= (1 << 24):
+        raise ValueError("max_cluster_size must be in 1 .. 2^24, not %d" % max_cluster_size)
+    chunks = _text_chunks(cluster_path_or_bytes, chunk_bytes)
+    chunk = next(chunks, None)                                                # a first line that is too long is refused here
+    dev = torch.device(device)
+    if dev.type != "cuda" or not torch.cuda.is_available():
+        raise _lib.MatchaHipError("parse_clusters_device needs a cuda device (no CPU fallback)")
+    lib = _lib.load()
+    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    i32, i64, u8 = (dict(dtype=t, device=dev) for t in (torch.int32, torch.int64, torch.uint8))
+    count_ws = torch.empty(lib.matcha_cluster_text_count_workspace_bytes(0), **u8)
+    counts, n_out, status = torch.empty(2, **i64), torch.empty(2, **i64), torch.empty(8, **i32)
+    ids_parts, off_parts, n_ids = [], [torch.zeros(1, **i64)], 0
+    while chunk is not None:
+        base, buf, length = chunk
+        text = torch.frombuffer(buf, dtype=torch.uint8, count=length).to(dev)      # a copy from pageable memory: done when it returns
+        _lib.check(lib.matcha_cluster_text_count(_lib.ptr(text), length, _lib.ptr(counts), _lib.ptr(count_ws), count_ws.numel(), st),
+                   "matcha_cluster_text_count")
+        n_lines, n_tabs = (int(v) for v in counts.tolist())                   # the chunk's one sizing sync
+        ws_bytes = lib.matcha_cluster_text_workspace_bytes(length, n_lines, n_tabs)
+        if ws_bytes == 0:
+            raise _lib.MatchaHipError("matcha_cluster_text_workspace_bytes(%d, %d, %d) = 0" % (length, n_lines, n_tabs))
+        ws = torch.empty(ws_bytes, **u8)
+        ids, offsets = torch.empty(max(n_tabs, 1), **i32), torch.empty(n_lines + 1, **i64)
+        _lib.check(lib.matcha_cluster_text_parse(_lib.ptr(text), length, n_lines, n_tabs, names.ctypes.data_as(C.c_void_p),
+                                                 first.ctypes.data_as(C.c_void_p), bins.ctypes.data_as(C.c_void_p), len(first), int(res),
+                                                 max_cluster_size, n_nodes, _lib.ptr(ids), ids.numel(), _lib.ptr(offsets), offsets.numel(),
+                                                 _lib.ptr(n_out), C.c_void_p(n_out.data_ptr() + 8), _lib.ptr(status), _lib.ptr(ws), ws_bytes, st),
+                   "matcha_cluster_text_parse")
+        st_host = [int(v) for v in status.tolist()]
+        if st_host[0]:
+            _raise_cluster_text_error(st_host, base, buf, length)
+        m, i = (int(v) for v in n_out.tolist())
+        if m:
+            ids_parts.append(ids[:i].clone())                                 # compact copies; the chunk's buffers are freed
+            off_parts.append(offsets[1:m + 1] + n_ids)
+            n_ids += i
+        del ws, ids, offsets, text
+        chunk = next(chunks, None)
+    return (torch.cat(ids_parts) if ids_parts else torch.zeros(0, **i32)), torch.cat(off_parts)
+
+
+def _is_device_csr(clusters) -> bool:
+    return isinstance(clusters, tuple) and len(clusters) == 2 and isinstance(clusters[0], torch.Tensor) and clusters[0].device.type == "cuda"
+
+
+def device_csr(clusters, device):
+    """An (ids, offsets) pair whose ids are a device tensor -> (ids int32 on ``device``, never moved to the host; offsets int64 numpy, 8
+    bytes per cluster, for what the callers compute on the host), checked like ``_clusters_csr`` checks a host pair."""
+    ids, offsets = clusters
+    offsets = np.ascontiguousarray(offsets.cpu().numpy() if isinstance(offsets, torch.Tensor) else np.asarray(offsets), dtype=np.int64)
+    if offsets.ndim != 1 or len(offsets) < 1 or offsets[0] != 0 or (np.diff(offsets) < 0).any() or offsets[-1] != ids.numel() or ids.dim() != 1:
+        raise ValueError("(ids, offsets): offsets must start at 0, not decrease and end at len(ids)")
+    return ids.to(device=device, dtype=torch.int32).contiguous(), offsets
 
 
 def cool_index2node(bins_chrom: np.ndarray, bins_start: np.ndarray, chrom_names: Sequence[str], chrom_list: Sequence[str],
@@ -229,11 +408,16 @@ class ClusterAdj:
 
     def update(self, clusters, weight="one"):
         """Add ``clusters`` (a list of ascending id lists, or an ``(ids, offsets)`` pair) with ``weight`` = "one" | "two_over_n" | one float per
-        cluster.  Refused with ValueError before anything runs: a non-finite weight, a cluster of more than 65535 nodes, and an update that
+        cluster.  A pair whose ids are a device tensor (``parse_clusters_device``) is used where it is: only its offsets are copied to the
+        host.  Refused with ValueError before anything runs: a non-finite weight, a cluster of more than 65535 nodes, and an update that
         would take the running sum of |q| to 2^62.  Ids that are not strictly ascending or leave 1 .. n_nodes are found on the device: such a
         cluster adds nothing and ``status()[0]`` gets STATUS_BAD_ID."""
         lib = _lib.load()
-        ids, offsets = _clusters_csr(clusters)
+        ids_d = None
+        if _is_device_csr(clusters):                                          # ids stay where they are; offsets (8 bytes per cluster) come to the host
+            ids_d, offsets = device_csr(clusters, self.device)
+        else:
+            ids, offsets = _clusters_csr(clusters)
         M = len(offsets) - 1
         lens = np.diff(offsets)
         q = cluster_weights_q(lens, weight)
@@ -250,7 +434,9 @@ class ClusterAdj:
         pair_ptr = np.zeros(M + 1, dtype=np.int64)
         np.cumsum(lens * (lens - 1) // 2, out=pair_ptr[1:])
         dev = self.device
-        ids_d, off_d = torch.from_numpy(ids).to(dev), torch.from_numpy(offsets).to(dev)
+        if ids_d is None:
+            ids_d = torch.from_numpy(ids).to(dev)
+        off_d = torch.from_numpy(offsets).to(dev)
         q_d, ptr_d = torch.from_numpy(q).to(dev), torch.from_numpy(pair_ptr).to(dev)
         _lib.check(lib.matcha_cluster_adj_update(_lib.ptr(ids_d), _lib.ptr(off_d), _lib.ptr(q_d), _lib.ptr(ptr_d), M, self.n_nodes, _lib.ptr(acc),
                                                  _lib.ptr(self._status), self._stream()), "matcha_cluster_adj_update")
@@ -354,6 +540,21 @@ def save_adj(temp_dir: str, intra: torch.Tensor, inter: torch.Tensor):
     np.save(os.path.join(temp_dir, "inter_adj.npy"), inter.cpu().numpy())
 
 
+def save_clusters_csr(temp_dir: str, clusters, edge_list_npy: bool = True):
+    """``temp_dir/edge_list_csr.npz`` (``ids`` int32, ``offsets`` int64) from an (ids, offsets) pair, which ``kmers.main --clusters csr`` reads;
+    with ``edge_list_npy`` also the reference's ``edge_list.npy``, the object array of id lists its other tools load."""
+    ids, offsets = (t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t) for t in clusters)
+    ids, offsets = np.ascontiguousarray(ids, dtype=np.int32), np.ascontiguousarray(offsets, dtype=np.int64)
+    os.makedirs(temp_dir, exist_ok=True)
+    np.savez(os.path.join(temp_dir, "edge_list_csr.npz"), ids=ids, offsets=offsets)
+    if edge_list_npy:
+        arr = np.empty(len(offsets) - 1, dtype=object)
+        flat = ids.tolist()
+        for i in range(len(arr)):
+            arr[i] = flat[offsets[i]:offsets[i + 1]]
+        np.save(os.path.join(temp_dir, "edge_list.npy"), arr, allow_pickle=True)
+
+
 def main(argv=None):
     """The script body of process.py:229-242: node dictionaries, edge_list.npy and the adjacency matrices -- with ``--adj-from mcool`` (the
     default) from ``mcool_path`` when h5py is importable (it is not part of this image), streamed through the device 16 M pixels at a time;
@@ -366,27 +567,48 @@ def main(argv=None):
     ap.add_argument("--adj-weight", choices=["one", "two_over_n"], default="one", help="--adj-from clusters: a cluster's weight per pair")
     ap.add_argument("--adj-max-cluster-size", type=int, default=None,
                     help="--adj-from clusters: largest cluster that enters the contact matrix (default: the config's max_cluster_size)")
+    ap.add_argument("--parse", choices=["host", "device"], default="host",
+                    help="device: the cluster file is parsed on the GPU (parse_clusters_device) and temp_dir/edge_list_csr.npz is written")
+    ap.add_argument("--no-edge-list-npy", action="store_true",
+                    help="--parse device: do not write edge_list.npy as well (building its object array costs what the device parse saves)")
     args = ap.parse_args(argv)
     with open(args.config) as f:
         config = json.load(f)
     res, chrom_list, temp_dir = config["resolution"], config["chrom_list"], config["temp_dir"]
     bin2node, _, node2chrom, chrom_range = build_node_dict(config["chrom_size"], chrom_list, res, temp_dir)
-    clusters = parse_clusters(config["cluster_path"], bin2node, chrom_list, res, config["max_cluster_size"], temp_dir)
-    print("%d nodes, %d clusters" % (int(chrom_range.max()) - 1, len(clusters)))
+    device_parse = args.parse == "device"
+    if device_parse:
+        clusters = parse_clusters_device(config["cluster_path"], chrom_list, chrom_range, res, config["max_cluster_size"])
+        save_clusters_csr(temp_dir, clusters, edge_list_npy=not args.no_edge_list_npy)
+        n_clusters = len(clusters[1]) - 1
+    else:
+        clusters = parse_clusters(config["cluster_path"], bin2node, chrom_list, res, config["max_cluster_size"], temp_dir)
+        n_clusters = len(clusters)
+    print("%d nodes, %d clusters" % (int(chrom_range.max()) - 1, n_clusters))
     N = int(chrom_range.max()) - 1
     if args.adj_from == "clusters":
         bound = config["max_cluster_size"] if args.adj_max_cluster_size is None else args.adj_max_cluster_size
         if bound > MAX_ADJ_CLUSTER:
             raise SystemExit("--adj-max-cluster-size is at most %d" % MAX_ADJ_CLUSTER)
-        adj_clusters = clusters if bound == config["max_cluster_size"] else parse_clusters(config["cluster_path"], bin2node, chrom_list, res, bound)
         ca = ClusterAdj(N, node2chrom)
         step = 1 << 20                                                          # clusters per update
-        for s in range(0, len(adj_clusters), step):
-            ca.update(adj_clusters[s:s + step], args.adj_weight)
+        if device_parse:
+            adj_clusters = clusters if bound == config["max_cluster_size"] else parse_clusters_device(config["cluster_path"], chrom_list, chrom_range,
+                                                                                                      res, bound)
+            ids_d, off = adj_clusters[0], adj_clusters[1].cpu().numpy()
+            n_adj = len(off) - 1
+            for s in range(0, n_adj, step):                                     # slices of the device CSR: the ids stay on the device
+                o = off[s:s + step + 1]
+                ca.update((ids_d[int(o[0]):int(o[-1])], o - o[0]), args.adj_weight)
+        else:
+            adj_clusters = clusters if bound == config["max_cluster_size"] else parse_clusters(config["cluster_path"], bin2node, chrom_list, res, bound)
+            n_adj = len(adj_clusters)
+            for s in range(0, n_adj, step):
+                ca.update(adj_clusters[s:s + step], args.adj_weight)
         intra, inter = ca.finish()
         if ca.status()[0] & _lib.STATUS_BAD_ID:
             raise IndexError("a cluster with ids that are not ascending or outside 1 .. %d was left out" % N)
-        print("%d clusters, %d pairs -> intra_adj.npy / inter_adj.npy" % (len(adj_clusters), ca.n_pairs))
+        print("%d clusters, %d pairs -> intra_adj.npy / inter_adj.npy" % (n_adj, ca.n_pairs))
         save_adj(temp_dir, intra, inter)
         return
     try:
