@@ -112,7 +112,11 @@ int matcha_route_read(const void* ws, char* out, size_t cap);
  * fbm_chain_kernel un-fold their own rows -- no fb_unfold_kernel --, and on the node route fb_unfold2's vectors ride in node_scatter_kernel, the
  * plan's tile_pack pass in the table front end's forward and its tile_compact pass in node_r_kernel -- four launches fewer per node-route step,
  * one fewer elsewhere; every role runs the text of the stand-alone kernel, so the plan and every output are the same bits either way;
- * matcha_backward follows what the forward recorded); development: "debug_nan", "fused_dbg" (bit 0: the backward of
+ * matcha_backward follows what the forward recorded), "disable_row_pack" (the fused embed_dim 64 step's ragged plan in batch order; without it
+ * the plan's rows are a permutation of the batch's, ordered by size class so that the half tiles fill to 31 tokens -- the loss-in-forward training
+ * step and the forward-only call, where the five-launch plan runs (more than 1 024 rows or eight planning superblocks) AND the order's arrays fit
+ * the plan regions it borrows: L >= 3 and at least five planning superblocks, i.e. B L >= 8 064 token slots (L = 5: from 1 613 rows); logits and losses are the same bits either way, gradients the same sums in another order;
+ * matcha_ragged_plan itself never reorders); development: "debug_nan", "fused_dbg" (bit 0: the backward of
  * pff_n1's convolutions inside the forward kernel at every batch size, instead of tail_bwd64_kernel for large batches).  (Whether the tail's backward runs inside the forward
  * kernel is a per-call choice: matcha_step_opts.loss_in_forward.)  Returns MATCHA_EINVAL for an unknown name;
  * matcha_get_option returns -1 for one.

@@ -283,6 +283,7 @@ struct Fwd32Args {
   const float* X;
   const int32_t* xrow;             // null: token t reads X + 64 t; node route: X is the per-node table and t reads row xrow[t] (the plan's tok_key: 0 = padding)
   const int32_t* row_off; const int32_t* tok_slot; const int32_t* count; const int32_t* half_meta; const int32_t* tok_pos;
+  const int32_t* row_src;          // null: plan row = batch row; packed plan: the batch row of plan row b' (logits, row_loss live in batch order; y, w come in plan order)
   int L;
   const u32x4* wfrag;              // the bf16 x 3 fragment stream + the f32 bias table behind it (prep_heads_kernel)
   HeadParams hp;
@@ -889,6 +890,7 @@ int launch_fused_fwd32(const matcha_tensors& p, const Ragged& rg, int64_t B, int
   g.rn = a.x.rn; g.vn = a.x.vn; g.rn_rows = (int)a.x.rows;
   g.tail_dh2 = nullptr; g.dxs_node = nullptr;
   g.X = a.x.X; g.row_off = rg.row_off; g.tok_slot = rg.tok_slot; g.count = rg.count; g.half_meta = rg.half_meta; g.tok_pos = rg.tok_pos;
+  g.row_src = a.row_src;
   g.L = L;
   g.wfrag = reinterpret_cast<const u32x4*>(a.frag);
   g.hp = HeadParams{p.pff_ln_g, p.pff_ln_b, p.ln1_g, p.ln1_b, p.ln2_g, p.ln2_b, p.cls_w, p.cls_b};

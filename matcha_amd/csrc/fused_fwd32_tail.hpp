@@ -118,12 +118,13 @@
   F32_TAIL_SYNC();
   // ---- per-hyperedge masked mean -> logit (+ BCE term, + its gradient): lane e takes hyperedge b0 + e (+ 64, ... only with many all-padding rows) ----
   for (int e = lane; e < n_h; e += 64) {
-    const int64_t b = b0 + e;
-    const int lo_g = g.row_off[b];
-    const int lo = lo_g - t0, kk = g.row_off[b + 1] - lo_g;
+    const int64_t bp = b0 + e;                        // the plan's row; b: the batch's (packed plan: another order, ragged.hip)
+    const int lo_g = g.row_off[bp];
+    const int lo = lo_g - t0, kk = g.row_off[bp + 1] - lo_g;
+    const int64_t b = g.row_src ? g.row_src[bp] : bp;
     float yb = 0.f, wb = 0.f;
     const bool mse = g.objective == MATCHA_OBJECTIVE_SOFTPLUS_MSE;      // wave-uniform (a launch parameter)
-    if (g.row_loss) { yb = g.y[b]; wb = mse ? 0.f : g.w[b]; }
+    if (g.row_loss) { yb = g.y[bp]; wb = mse ? 0.f : g.w[bp]; }      // (y, w: in the plan's order)
     float tot = 0.f;
     for (int i = 0; i < kk; ++i) tot += outs[lo + i];
     const float z = tot / ((float)kk + 1e-15f);

@@ -52,7 +52,16 @@ struct Ragged {
   int32_t* sb_htiles;  // planning scratch of the half tiles
   int32_t* sb_hcnt;
   int nhalves, sb_hcap;
+  // packed row order (ragged.hip; null: the plan cannot take it).  No bytes of their own: ragged_carve places them in the regions of the 64-row
+  // tile list and the token -> tile map, which a plan of level <= 1 -- the only kind that packs -- does not build
+  int32_t* row_src;    // [B] batch row of plan row b' (written by a packed plan only: the plan's rows are then a permutation of the batch's)
+  int32_t* cls_hist;   // [nblk][16] planning scratch: rows per size class and counting block, then their exclusive bases
+  int32_t* sched;      // the schedule (ragged_pack_sched_bytes)
+  float *y_plan, *w_plan;   // [B] the step's targets and weights in plan order (written by a packed plan that is handed y / w)
 };
+size_t ragged_pack_sched_bytes();
+size_t ragged_pack_hist_bytes(int64_t B);
+bool ragged_plan_packs(int64_t B, const Ragged& r);      // would launch_ragged_plan take `packed` for this batch (the five-launch plan with the arrays above)
 size_t ragged_bytes(int64_t B, int L);
 int ragged_tiles_cap(int64_t B, int L);
 int ragged_halves_cap(int64_t B, int L);
@@ -60,7 +69,9 @@ void ragged_carve(int64_t B, int L, char* base, Ragged& r);
 struct PlanDeferred; struct TilePackArgs; struct CompactArgs;      // ragged_roles.hpp
 int launch_ragged_plan(const int64_t* x, int64_t B, int L, int64_t n_nodes, int32_t* status, const Ragged& r, hipStream_t st, int level = 2,
                        int64_t* node_ids = nullptr, int32_t* node_cnt = nullptr, float* node_zero = nullptr,
-                       PlanDeferred* defer = nullptr);      // != null: the two tile-list passes may be left to the caller (ragged.hip)
+                       PlanDeferred* defer = nullptr,       // != null: the two tile-list passes may be left to the caller (ragged.hip)
+                       bool packed = false,                 // rows ordered by size class, r.row_src written (only where ragged_plan_packs)
+                       const float* y = nullptr, const float* w = nullptr);      // ... and the rows' targets / weights (null: none) copied to r.y_plan / r.w_plan
 // (node_ids != null: the plan also writes the id list 0..n_nodes and its length {n_nodes + 1, n_nodes}; node_zero != null: and zeroes [n_nodes + 1][64] floats)
 
 struct HeadParams {
@@ -119,6 +130,7 @@ struct Options {
   int disable_node_v;        // node route with the r table: the backward forms dZ / Z per token (the per-node value table y = M_h x_hat and the kernel instance on it off)
   int disable_node_dx;       // node route with the value table: d x_hat / dXs per TOKEN and node_scatter_kernel's walk over the tokens (their per-node sums at the producers off)
   int disable_launch_pairs;  // every small launch of the step on its own (StepRoute::paired off: the launches of the step as they were before the pairs)
+  int disable_row_pack;      // the fused d = 64 step's plan in batch order (the packed row order of ragged.hip off: ~5 % more half tiles at mixed k)
   int debug_nan, fused_dbg;  // development
 };
 Options& options();
@@ -190,6 +202,7 @@ struct FusedFwdLaunch {
   float *ddyn0, *dXs, *tslab; float alpha;   // ddyn0 != null: the tail's backward runs in the kernel (needs targets)
   float* rimg;           // r rows + probabilities per (half tile, head) for the fused backward (null: a forward only)
   float* tail_dh2;       // large batches only: the convolutions' backward is left to launch_tail_bwd64
+  const int32_t* row_src = nullptr;   // the plan's rows are in the packed order (ragged.hip): hyperedge b' of the plan writes logits, row_loss at row_src[b'] (y, w: the caller hands the plan-order copies)
   float* dxs_node = nullptr;   // node route, single-wave kernel with the tail's backward: dXs rows are ADDED per node into [x.rows][64] (zeroed by the caller) instead of stored per token
 };
 int launch_fused_fwd32(const matcha_tensors& p, const Ragged& rg, int64_t B, int L, const FusedFwdLaunch& a, hipStream_t st);

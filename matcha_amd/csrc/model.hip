@@ -127,12 +127,14 @@ struct Workspace : TokenChain {
 //                            fbm_chain_kernel's blocks un-fold their own rows -- no fb_unfold_kernel --; on the node route fb_unfold2's vectors ride in
 //                            node_scatter_kernel and the plan's tile_pack / tile_compact passes in the table front end's forward / node_r_kernel;
 //                            every output is the same bits either way)
+//   disable_row_pack         the fused d = 64 step's plan in batch order (without the switch: rows ordered by size class so that the half tiles fill to 31
+//                            tokens, ragged.hip; logits and losses are the same bits either way, token-contracted sums add in another order)
 //   disable_wide_gemm        embed_dim >= 128: the 64-wide GEMM / attention kernels (gemm_lds.hip, gemm_f32.hip, attention.hip; four-product
 //                            heads) instead of gemm_wide.hip / attention_wide.hip
 struct OptionName { const char* name; int Options::*field; };
 static const OptionName kOptionNames[] = {
     {"disable_fused", &Options::disable_fused}, {"disable_merged", &Options::disable_merged}, {"disable_small_batch", &Options::disable_small_batch},
-    {"disable_wide_gemm", &Options::disable_wide_gemm}, {"disable_node_front", &Options::disable_node_front}, {"disable_node_r", &Options::disable_node_r}, {"disable_node_v", &Options::disable_node_v}, {"disable_node_dx", &Options::disable_node_dx}, {"disable_launch_pairs", &Options::disable_launch_pairs}, {"debug_nan", &Options::debug_nan}, {"fused_dbg", &Options::fused_dbg}};
+    {"disable_wide_gemm", &Options::disable_wide_gemm}, {"disable_node_front", &Options::disable_node_front}, {"disable_node_r", &Options::disable_node_r}, {"disable_node_v", &Options::disable_node_v}, {"disable_node_dx", &Options::disable_node_dx}, {"disable_launch_pairs", &Options::disable_launch_pairs}, {"disable_row_pack", &Options::disable_row_pack}, {"debug_nan", &Options::debug_nan}, {"fused_dbg", &Options::fused_dbg}};
 Options& options() {
   static Options o = [] {
     Options v;
@@ -295,6 +297,15 @@ static StepRoute decide_route(const matcha_shape& s, const matcha_step_opts& o, 
   r.long_rows = false;      // (matcha_forward_long_train notes its own record)
   return r;
 }
+// Does this forward's plan take the packed row order (ragged.hip)?  Only where every consumer of the plan sees tokens and half tiles, or rows through
+// row_src: the fused d = 64 kernels with the loss inside the forward (the training step, every front end, `deterministic` too) and the forward that
+// keeps nothing (inference logits).  NOT: the layer-by-layer path and enc128 (head_fwd / head_bwd / the attention kernels index rows by plan row;
+// embeddings and attention maps go back to the caller in batch order), a fused forward differentiated by an explicit dlogits (head_bwd reads
+// dlogits[b] by plan row), the row-sparse table gradient (its (id, row) list is handed to the caller), and the one-launch plan of small batches.
+// The backward needs no record of it: none of its kernels indexes a hyperedge -- they walk the tokens and half tiles the plan left in the workspace.
+static bool row_pack_route(const StepRoute& r, const matcha_step_opts& o, int64_t B, const Workspace& w) {
+  return r.fused && (r.lif || o.forward_only) && !o.sparse_table_grad && !options().disable_row_pack && ragged_plan_packs(B, w.rg);
+}
 // what the encoder kernels and head_bwd read for X on this route (kernels.hpp): the per-node tables by tok_key, or X per token
 static NodeOperands node_operands(const StepRoute& r, const matcha_shape& s, const Workspace& w) {
   const int64_t rows = (int64_t)s.n_nodes + 1;
@@ -426,9 +437,10 @@ static int forward_impl(const matcha_shape* shp, const matcha_tensors* params, c
   const bool tgt = has_target(objective, y, w_bce);
   PlanDeferred deferred;
   deferred.pending = false;
+  const bool row_pack = row_pack_route(route, *opts, B, w);
   MATCHA_TRY(launch_ragged_plan(x, B, L, s.n_nodes, opts->status, w.rg, st, route.half_plan ? 1 : 0, route.node ? w.node_ids : nullptr, route.node ? w.node_cnt : nullptr,
                                 (route.node && keep) ? w.GN : nullptr,        // ... which also writes the node route's id list and zeroes its accumulator
-                                (route.paired && route.node) ? &deferred : nullptr));
+                                (route.paired && route.node) ? &deferred : nullptr, row_pack, y, w_bce));
   // (paired, node route: the plan's two tile-list passes -- batch only -- ride in the table launches below -- parameters only; the plan stops behind
   // row_fill_kernel, which those launches need for their id list anyway.  deferred.pending: the five-launch plan ran and left them)
   // front end: node rows (K1) + attribute path (K6) + add (Modules.py:263-269)
@@ -479,6 +491,8 @@ static int forward_impl(const matcha_shape* shp, const matcha_tensors* params, c
     a.seed = opts->seed; a.p_fc1 = train ? opts->p_drop_fc1 : 0.f; a.p_pff = train ? opts->p_drop_pff : 0.f; a.alpha = opts->alpha;
     a.ddyn0 = route.lif ? w.ddyn0 : nullptr; a.dXs = w.dXs; a.tslab = w.tslab; a.tail_dh2 = route.split_tail ? w.dH2 : nullptr;
     a.dxs_node = route.node_dx ? w.GN : nullptr;      // (zeroed by the plan's launch above)
+    a.row_src = row_pack ? w.rg.row_src : nullptr;
+    if (row_pack) { a.y = y ? w.rg.y_plan : nullptr; a.w = w_bce ? w.rg.w_plan : nullptr; }      // (the plan's launch copied them in its order)
     MATCHA_CHECK_ARG(!route.node_dx || nx.rows <= Tn, "matcha_forward: the heads' per-node d x_hat rows do not fit dO");
     MATCHA_TRY(launch_fused_fwd32(p, w.rg, B, L, a, st));
     if (route.split_tail)
@@ -548,7 +562,7 @@ extern "C" int matcha_debug_layout(const matcha_shape* shp, int64_t B, int32_t L
       {"dXs", w.dXs}, {"dZ1", w.dZ1}, {"ddyn0", w.ddyn0}, {"dZ0", w.dZ0}, {"dX0", w.dX0}, {"slab", w.slab}, {"gemm_ws", w.gemm_ws}, {"adj_ws", w.adj_ws},
       {"folded", w.folded}, {"frag", w.frag}, {"merged", w.merged}, {"lwB", w.lwB}, {"lwM", w.lwM}, {"lwdB", w.lwdB}, {"lwdM", w.lwdM}, {"enc", w.enc}, {"fb_ws", w.fb_ws},
       {"tpart", w.tpart}, {"tslab", w.tslab}, {"tslab2", w.tslab2}, {"qkv_records", w.qkv}, {"front_ws", w.front_ws}, {"tg_ws", w.tg_ws}, {"XN", w.XN}, {"x0N", w.x0N}, {"xhN", w.xhN}, {"GN", w.GN},
-      {"node_ids", w.node_ids}, {"node_cnt", w.node_cnt}, {"RN", w.RN}, {"VN", w.VN}};
+      {"node_ids", w.node_ids}, {"node_cnt", w.node_cnt}, {"RN", w.RN}, {"VN", w.VN}, {"row_src", w.rg.row_src}, {"pack_sched", w.rg.sched}};
   size_t n = 0;
   for (const auto& e : f) {
     if (!e.p) continue;

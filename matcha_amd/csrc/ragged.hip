@@ -21,6 +21,9 @@
 //                   32 rows: one wavefront of the wave-independent fused forward, fused_fwd32.hip); count[3] = number of half tiles
 //   tok_tile [T+1]  compact token -> (tile << 6) | row inside that tile: where the forward's wavefront stores the token's Q / K / V
 //                   rows for the backward kernel, whose 64-row tiles cut the stream at other places than the half tiles
+//   row_src [B]     packed plans only (launch_ragged_plan's `packed`, the fused d = 64 step): the plan's rows are a permutation of the batch's, ordered
+//                   by size class so that the half tiles fill to 31 tokens; row_src[b'] = batch row of plan row b'.  Every array above is then in
+//                   plan order (tok_slot still names the ORIGINAL slot).  matcha_ragged_plan never packs
 #include "kernels.hpp"
 #include "ragged_roles.hpp"
 
@@ -47,23 +50,136 @@ __device__ __forceinline__ int block_exclusive_scan_256(int v, int* lds4, int* t
   return base + incl - v;
 }
 
-__global__ __launch_bounds__(256) void row_count_kernel(const int64_t* __restrict__ x, int64_t B, int L, int32_t* __restrict__ blk_sum) {
+// ---- the packed row order ("Packed row order"): rows by size class, so that the greedy packer's half tiles fill to 31 tokens ------------------------
+// A row's class is its number of real tokens k = 0 .. MATCHA_MAX_L.  row_count_kernel leaves the classes' counts per block (cls_hist [nblk][16]),
+// row_scan_kernel turns them into per-class bases and lets one wavefront derive the SCHEDULE from the class totals: phases (recipe a_k = rows of
+// class k per half tile with sum k a_k <= 31, m tiles), a phase ending when a class cannot fill another tile; the last phase takes what is left,
+// class by class.  Inside a tile the classes stand in ascending order.  Row r of class k (r in batch order) then has its plan row and first token
+// in closed form (row_fill_kernel).  tests/row_pack_ref.py is the twin of all of it, integer for integer.
+constexpr int kPackCls = MATCHA_MAX_L + 1;
+constexpr int kPackPhases = 12;
+constexpr int kPackTailTok = 64 * kHalfTok;        // at most this many tokens left (or 1 / 32 of the batch's): the remaining rows in class order (the greedy packer's loss there: a few tiles)
+constexpr int kPackStride = 56;                    // ints per phase: m, rows, toks, row_base, tok_base, pred_k, last_k, -, then five arrays of kPackCls
+constexpr int kPackHead = 16;                      // sched[0] = number of phases; the phases start here
+constexpr int kPhA = 8, kPhRowIn = kPhA + kPackCls, kPhTokIn = kPhRowIn + kPackCls, kPhBase = kPhTokIn + kPackCls, kPhPrevK = kPhBase + kPackCls;
+static_assert(kPhPrevK + kPackCls <= kPackStride && kPackCls <= 16 && kRpt == 1, "schedule layout");
+size_t ragged_pack_sched_bytes() { return (size_t)(kPackHead + kPackPhases * kPackStride) * 4; }
+size_t ragged_pack_hist_bytes(int64_t B) { return (size_t)cdiv(B, kRowsPerBlock) * 16 * 4; }
+
+__global__ __launch_bounds__(256) void row_count_kernel(const int64_t* __restrict__ x, int64_t B, int L, int32_t* __restrict__ blk_sum,
+                                                        int32_t* __restrict__ cls_hist) {
   __shared__ int lds4[4];
+  __shared__ int hist[16];
   const int64_t b0 = (int64_t)blockIdx.x * kRowsPerBlock + threadIdx.x * kRpt;
   int cnt = 0;
   for (int i = 0; i < kRpt; ++i)
     if (b0 + i < B)
       for (int l = 0; l < L; ++l) cnt += x[(b0 + i) * L + l] != 0 ? 1 : 0;
+  if (cls_hist && threadIdx.x < 16) hist[threadIdx.x] = 0;
   int total;
-  (void)block_exclusive_scan_256(cnt, lds4, &total);
+  (void)block_exclusive_scan_256(cnt, lds4, &total);     // (its barrier orders the zeros above against the adds below)
   if (threadIdx.x == 0) blk_sum[blockIdx.x] = total;
+  if (cls_hist) {
+    const int cls = b0 < B ? cnt : -1;
+#pragma unroll
+    for (int c = 0; c < kPackCls; ++c) {
+      const uint64_t m = __ballot(cls == c);
+      if ((threadIdx.x & 63) == 0 && m) atomicAdd(&hist[c], __popcll(m));
+    }
+    __syncthreads();
+    if (threadIdx.x < 16) cls_hist[(int64_t)blockIdx.x * 16 + threadIdx.x] = hist[threadIdx.x];
+  }
+}
+
+// one wavefront, lane c = class c: the schedule from the class totals (tests/row_pack_ref.py: schedule, _recipe)
+__device__ __forceinline__ int pack_lane_sum(int v) {      // over the kPackCls class lanes, uniform result
+  int s = 0;
+#pragma unroll
+  for (int c = 0; c < kPackCls; ++c) s += __builtin_amdgcn_readlane(v, c);
+  return s;
+}
+__device__ __forceinline__ void pack_schedule(const int* __restrict__ ntot, int32_t* __restrict__ sched, int lane) {
+  const int c = lane;
+  int rem = c < kPackCls ? ntot[c] : 0;
+  int row_base = 0, tok_base = 0, cls_base = 0, pred_k = 0, np = 0;
+  const int tail_tok = max(kPackTailTok, pack_lane_sum(c * rem) >> 5);      // the last 1 / 32 of the tokens (at least 64 tiles' worth): in class order
+  while (pack_lane_sum(rem) > 0) {
+    const int T = pack_lane_sum(c * rem);
+    const bool last = np == kPackPhases - 1 || T <= tail_tok;
+    int a = rem, m = 1;
+    if (!last) {
+      // the classes' shares of the remaining tokens, rounded down ...
+      int s = 0;
+      while ((T >> s) >= (1 << 26)) ++s;
+      const int rs = rem >> s;
+      const int Ts = pack_lane_sum(c * rs);
+      a = 0;                                             // (class 0 and the idle lanes take no share: their product below could overflow, and Ts may be 0)
+      if (c >= 1 && c < kPackCls && Ts > 0) a = min(rem, (int)(((uint32_t)kHalfTok * (uint32_t)rs) / (uint32_t)Ts));
+      const int left = kHalfTok - pack_lane_sum(c * a);
+      // ... and the slots left filled exactly: a bounded knapsack over what remains, classes 8 .. 1 (reach: bit w = w tokens can be added)
+      const int spare = rem - a;
+      uint32_t reach = 1u, before[kPackCls];
+#pragma unroll
+      for (int cc = MATCHA_MAX_L; cc >= 1; --cc) {
+        before[cc] = reach;
+        const int avail = min(__builtin_amdgcn_readlane(spare, cc), left / cc);
+        for (int j = 0; j < avail; ++j) reach |= reach << cc;
+        reach &= 0xffffffffu >> (31 - left);
+      }
+      int w = 31 - __clz((int)reach);
+#pragma unroll
+      for (int cc = 1; cc <= MATCHA_MAX_L; ++cc) {
+        int j = 0;
+        while (j * cc < w && !((before[cc] >> (w - j * cc)) & 1u)) ++j;
+        if (c == cc) a += j;
+        w -= j * cc;
+      }
+      // tiles until a class cannot fill another one; the all-padding rows spread over them
+      int q = (c >= 1 && c < kPackCls && a > 0) ? (int)((uint32_t)rem / (uint32_t)a) : 0x7fffffff;
+      m = q;
+#pragma unroll
+      for (int cc = 1; cc < kPackCls; ++cc) m = min(m, __builtin_amdgcn_readlane(q, cc));
+      if (c == 0) a = (int)((uint32_t)rem / (uint32_t)m);
+    }
+    int row_in = 0, tok_in = 0, prev_k = -1, last_k = -1, rows = 0, toks = 0;
+#pragma unroll
+    for (int cc = 0; cc < kPackCls; ++cc) {
+      const int ac = __builtin_amdgcn_readlane(a, cc);
+      if (c == cc) { row_in = rows; tok_in = toks; prev_k = last_k; }
+      rows += ac;
+      toks += cc * ac;
+      if (ac > 0) last_k = cc;
+    }
+    int32_t* ph = sched + kPackHead + np * kPackStride;
+    if (c == 0) { ph[0] = m; ph[1] = rows; ph[2] = toks; ph[3] = row_base; ph[4] = tok_base; ph[5] = pred_k; ph[6] = last_k; }
+    if (c < kPackCls) { ph[kPhA + c] = a; ph[kPhRowIn + c] = row_in; ph[kPhTokIn + c] = tok_in; ph[kPhBase + c] = cls_base; ph[kPhPrevK + c] = prev_k; }
+    rem -= m * a;
+    cls_base += m * a;
+    row_base += m * rows;
+    tok_base += m * toks;
+    pred_k = last_k;
+    ++np;
+    if (last) break;
+  }
+  if (lane == 0) sched[0] = np;
 }
 
 // exclusive scan of the block sums in place; count = {Tr + 1, Tr}
 __global__ __launch_bounds__(1024) void row_scan_kernel(int32_t* __restrict__ blk_sum, int nblk, int32_t* __restrict__ count,
-                                                        int32_t* __restrict__ sb_first, int nsb, int32_t n_rows) {
+                                                        int32_t* __restrict__ sb_first, int nsb, int32_t n_rows,
+                                                        int32_t* __restrict__ cls_hist, int32_t* __restrict__ sched) {
   __shared__ int part[1024];
   for (int i = threadIdx.x; i <= nsb; i += 1024) sb_first[i] = n_rows;       // superblocks in which no hyperedge starts: empty range
+  // packed order: wavefront c < kPackCls scans class c's per-block counts (64 lanes, nblk / 64 blocks each).  Their loads go first, the totals
+  // reach LDS in front of the barrier below, and the LAST wavefront derives the schedule behind it while the others write their bases
+  __shared__ int ntot[16];
+  const int hch = (nblk + 63) / 64;
+  const int hlane = threadIdx.x & 63, hcls = threadIdx.x >> 6;
+  const int h0 = hlane * hch < nblk ? hlane * hch : nblk, h1 = h0 + hch < nblk ? h0 + hch : nblk;
+  const bool hist_wave = cls_hist && hcls < kPackCls;
+  int hloc = 0;
+  if (hist_wave)
+    for (int b = h0; b < h1; ++b) hloc += cls_hist[(int64_t)b * 16 + hcls];
   const int chunk = (nblk + 1023) / 1024;
   const int b0 = threadIdx.x * chunk, b1 = (b0 + chunk < nblk) ? b0 + chunk : nblk;
   int local = 0;
@@ -79,7 +195,17 @@ __global__ __launch_bounds__(1024) void row_scan_kernel(int32_t* __restrict__ bl
     if (lane >= o) incl += u;
   }
   if (lane == 63) wtot[wave] = incl;
+  int hinc = hloc;
+  if (hist_wave) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int u = __shfl_up(hinc, o, 64);
+      if (lane >= o) hinc += u;
+    }
+    if (lane == 63) ntot[wave] = hinc;
+  }
   __syncthreads();
+  if (cls_hist && wave == 15) pack_schedule(ntot, sched, lane);
   int wbase = 0, total = 0;
 #pragma unroll
   for (int w2 = 0; w2 < 16; ++w2) { const int v = wtot[w2]; if (w2 < wave) wbase += v; total += v; }
@@ -90,15 +216,26 @@ __global__ __launch_bounds__(1024) void row_scan_kernel(int32_t* __restrict__ bl
   }
   int run = part[threadIdx.x];
   for (int b = b0; b < b1; ++b) { const int v = blk_sum[b]; blk_sum[b] = run; run += v; }
+  if (hist_wave) {                                       // the class's exclusive bases per counting block, in place
+    int at = hinc - hloc;
+    for (int b = h0; b < h1; ++b) { const int v = cls_hist[(int64_t)b * 16 + hcls]; cls_hist[(int64_t)b * 16 + hcls] = at; at += v; }
+  }
 }
 
+// PACK: the rows go to the plan rows and token positions of the schedule (row_src[plan row] = batch row; tok_slot keeps the ORIGINAL slot, which
+// keys the dropout counters); otherwise plan row = batch row, bit for bit the plan of every earlier version
+template <bool PACK>
 __global__ __launch_bounds__(256) void row_fill_kernel(const int64_t* __restrict__ x, int64_t B, int L, const int32_t* __restrict__ blk_base,
                                                        const int32_t* __restrict__ count, int32_t* __restrict__ row_off,
                                                        int32_t* __restrict__ tok_slot, int64_t* __restrict__ tok_id,
                                                        int32_t* __restrict__ tok_pos, int32_t* __restrict__ sb_first, int super_tok,
                                                        int32_t* __restrict__ tok_key, int64_t n_nodes, int32_t* __restrict__ status,
-                                                       int64_t* __restrict__ node_ids, int32_t* __restrict__ node_cnt, float* __restrict__ node_zero) {
+                                                       int64_t* __restrict__ node_ids, int32_t* __restrict__ node_cnt, float* __restrict__ node_zero,
+                                                       const int32_t* __restrict__ cls_base, const int32_t* __restrict__ sched, int32_t* __restrict__ row_src,
+                                                       const float* __restrict__ y_in, const float* __restrict__ w_in, float* __restrict__ y_plan, float* __restrict__ w_plan) {
   __shared__ int lds4[4];
+  __shared__ int sch[PACK ? kPackHead + kPackPhases * kPackStride : 1];
+  __shared__ int wcls[4][16];
   const int64_t b0 = (int64_t)blockIdx.x * kRowsPerBlock + threadIdx.x * kRpt;
   // this thread's rows (and the row in front of them) in registers: ONE round of loads, all in flight together, on clamped
   // addresses with the masks applied to the values (the first version read x three times behind dependent waits)
@@ -109,7 +246,14 @@ __global__ __launch_bounds__(256) void row_fill_kernel(const int64_t* __restrict
 #pragma unroll
     for (int l = 0; l < MATCHA_MAX_L; ++l) v[i][l] = x[bc * L + (l < L ? l : L - 1)];
   }
-  {
+  float yv = 0.f, wv = 0.f;
+  if (PACK) {
+    // the whole schedule table into LDS (phases past the count hold whatever the workspace held: never read), no dependent read of its length
+    for (int i = threadIdx.x; i < kPackHead + kPackPhases * kPackStride; i += 256) sch[i] = sched[i];
+    const int64_t bc = b0 < B ? b0 : B - 1;
+    if (y_in) yv = y_in[bc];
+    if (w_in) wv = w_in[bc];
+  } else {
     const int64_t bp = b0 > 0 ? (b0 - 1 < B ? b0 - 1 : B - 1) : 0;
 #pragma unroll
     for (int l = 0; l < MATCHA_MAX_L; ++l) vp[l] = x[bp * L + (l < L ? l : L - 1)];
@@ -127,17 +271,53 @@ __global__ __launch_bounds__(256) void row_fill_kernel(const int64_t* __restrict
     cnt += k;
   }
   int kprev = 0;
+  if (!PACK) {
 #pragma unroll
-  for (int l = 0; l < MATCHA_MAX_L; ++l) kprev += (b0 > 0 && l < L && vp[l] != 0) ? 1 : 0;
-  int pos = blk_base[blockIdx.x] + block_exclusive_scan_256(cnt, lds4, nullptr);
+    for (int l = 0; l < MATCHA_MAX_L; ++l) kprev += (b0 > 0 && l < L && vp[l] != 0) ? 1 : 0;
+  }
+  int pos = 0;
+  int64_t bdst = b0;                                     // plan row of this thread's row
+  if (PACK) {
+    // rank of the row inside its class: the block's base + the rows of the class in front of it in the block (ballots, the waves' counts through LDS)
+    const int cls = b0 < B ? kk[0] : -1, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int rk = 0;
+#pragma unroll
+    for (int c = 0; c < kPackCls; ++c) {
+      const uint64_t m = __ballot(cls == c);
+      if (cls == c) rk = __popcll(m & ((1ull << lane) - 1ull));
+      if (lane == 0) wcls[wave][c] = __popcll(m);
+    }
+    __syncthreads();                                     // wcls and the schedule in LDS
+    if (cls >= 0) {
+      for (int w = 0; w < wave; ++w) rk += wcls[w][cls];
+      const int r = cls_base[(int64_t)blockIdx.x * 16 + cls] + rk;
+      int p = 0;                                         // the last phase whose class base is <= r holds the row
+      for (int q = 1; q < sch[0]; ++q)
+        if (sch[kPackHead + q * kPackStride + kPhBase + cls] <= r) p = q;
+      const int* ph = sch + kPackHead + p * kPackStride;
+      const int a = ph[kPhA + cls], q = r - ph[kPhBase + cls];
+      const int t = (int)((uint32_t)q / (uint32_t)a), j = q - t * a;
+      bdst = ph[3] + t * ph[1] + ph[kPhRowIn + cls] + j;
+      pos = ph[4] + t * ph[2] + ph[kPhTokIn + cls] + j * cls;
+      // the plan row in front: the slot before this one in the recipe, the last slot of the tile before, or of the phase before
+      kprev = j > 0 ? cls : ph[kPhPrevK + cls] >= 0 ? ph[kPhPrevK + cls] : t > 0 ? ph[6] : ph[5];
+    }
+  } else {
+    pos = blk_base[blockIdx.x] + block_exclusive_scan_256(cnt, lds4, nullptr);
+  }
 #pragma unroll
   for (int i = 0; i < kRpt; ++i) {
     const int64_t b = b0 + i;
     if (b < B) {
-      row_off[b] = pos;
+      row_off[bdst] = pos;
+      if (PACK) {                                        // the batch row of the plan row, and the row's targets in plan order (the forward's tail reads them by plan row)
+        row_src[bdst] = (int32_t)b;
+        if (y_in) y_plan[bdst] = yv;
+        if (w_in) w_plan[bdst] = wv;
+      }
       const int k = kk[i];
       // first hyperedge of a planning superblock: its first token lies in another window of super_tok tokens than its predecessor's
-      if (b == 0 || pos / super_tok != (pos - kprev) / super_tok) sb_first[pos / super_tok] = (int32_t)b;
+      if (bdst == 0 || pos / super_tok != (pos - kprev) / super_tok) sb_first[pos / super_tok] = (int32_t)bdst;
       kprev = k;
       int nth = 0;
 #pragma unroll
@@ -431,6 +611,17 @@ void ragged_carve(int64_t B, int L, char* base, Ragged& r) {
   r.sb_htiles = (int32_t*)take((size_t)r.nsb * r.sb_hcap * 16);
   r.sb_hcnt = (int32_t*)take((size_t)r.nsb * 4);
   r.tok_tile = (int32_t*)take((size_t)(T + 1) * 4);
+  // The packed row order's arrays take no bytes of their own (the plan's and the workspace's sizes are what they were): a plan that stops at the
+  // half tiles (level <= 1, the only kind that packs) builds neither the 64-row tile list nor the token -> tile map, and the arrays live in those
+  // three regions.  Where they do not fit (L <= 2, or fewer than five planning superblocks) the pointers stay null and the plan does not pack.
+  r.row_src = nullptr; r.cls_hist = nullptr; r.sched = nullptr; r.y_plan = nullptr; r.w_plan = nullptr;
+  if ((size_t)3 * B <= (size_t)T + 1 && ragged_pack_hist_bytes(B) <= (size_t)(r.ntiles + 2) * 16 && ragged_pack_sched_bytes() <= (size_t)r.nsb * r.sb_cap * 16) {
+    r.row_src = r.tok_tile;
+    r.y_plan = reinterpret_cast<float*>(r.tok_tile + B);
+    r.w_plan = reinterpret_cast<float*>(r.tok_tile + 2 * B);
+    r.cls_hist = r.tile_meta;
+    r.sched = r.sb_tiles;
+  }
 }
 
 // the two tile-list passes as launches of their own (the plan below; a host kernel that cannot take the role)
@@ -449,9 +640,21 @@ int launch_tile_compact(const CompactArgs& a, hipStream_t st) {
 // tokens only (no fused kernel will read a tile list)
 // defer != null: with the five-launch plan at level 1 the two tile-list passes are NOT launched -- their argument blocks are left in *defer
 // (pending = true) for the caller, who runs them as roles of later launches or through launch_tile_pack / launch_tile_compact, in that order
+// packed: the rows in the packed order (above) -- the caller asks only where ragged_plan_packs says the plan takes it, and hands r.row_src to its consumers
+bool ragged_plan_packs(int64_t B, const Ragged& r) {
+  return r.row_src && r.cls_hist && r.sched && r.y_plan && r.w_plan && !(B <= kSmallRows && r.nsb <= kSmallSb && !options().disable_small_batch);
+}
 int launch_ragged_plan(const int64_t* x, int64_t B, int L, int64_t n_nodes, int32_t* status, const Ragged& r, hipStream_t st, int level,
-                       int64_t* node_ids, int32_t* node_cnt, float* node_zero, PlanDeferred* defer) {
+                       int64_t* node_ids, int32_t* node_cnt, float* node_zero, PlanDeferred* defer, bool packed, const float* y, const float* w) {
   if (defer) defer->pending = false;
+  MATCHA_CHECK_ARG(!packed || (ragged_plan_packs(B, r) && level <= 1), "launch_ragged_plan: the packed order needs the five-launch plan at level <= 1");
+  // The packed order needs no larger lists.  halves_cap and super_hcap rest on ONE invariant of tile_pack_wave, which holds for any row order: a
+  // half tile closes only when the next row (<= L tokens) does not fit, so every tile but a superblock's last holds > kHalfTok - L tokens, and a
+  // superblock is still the rows whose first token lies in a window of kSuperTok tokens.  What the host can check is that `r` was carved with
+  // exactly those caps for this batch (tests/test_cpu_row_pack.py holds the twin's lists to the same two bounds)
+  static_assert(kHalfTok == 31 && MATCHA_MAX_L < kHalfTok, "halves_cap / super_hcap: a row always fits an empty half tile");
+  MATCHA_CHECK_ARG(!packed || (r.nsb == super_blocks(B * L) && r.sb_hcap == super_hcap(L) && r.nhalves == halves_cap(B * L, L)),
+                   "launch_ragged_plan: the plan was not carved for B=%lld L=%d", (long long)B, L);
   if (B <= kSmallRows && r.nsb <= kSmallSb && !options().disable_small_batch) {
     PlanSmallArgs a;
     a.x = x; a.B = B; a.L = L; a.n_nodes = n_nodes; a.status = status;
@@ -465,12 +668,17 @@ int launch_ragged_plan(const int64_t* x, int64_t B, int L, int64_t n_nodes, int3
     MATCHA_CHECK_LAUNCH("plan_small_kernel");
     return MATCHA_OK;
   }
-  hipLaunchKernelGGL(row_count_kernel, dim3(r.nblk), dim3(256), 0, st, x, B, L, r.blk_sum);
+  hipLaunchKernelGGL(row_count_kernel, dim3(r.nblk), dim3(256), 0, st, x, B, L, r.blk_sum, packed ? r.cls_hist : nullptr);
   MATCHA_CHECK_LAUNCH("row_count_kernel");
-  hipLaunchKernelGGL(row_scan_kernel, dim3(1), dim3(1024), 0, st, r.blk_sum, r.nblk, r.count, r.sb_first, r.nsb, (int32_t)B);
+  hipLaunchKernelGGL(row_scan_kernel, dim3(1), dim3(1024), 0, st, r.blk_sum, r.nblk, r.count, r.sb_first, r.nsb, (int32_t)B, packed ? r.cls_hist : nullptr,
+                     packed ? r.sched : nullptr);
   MATCHA_CHECK_LAUNCH("row_scan_kernel");
-  hipLaunchKernelGGL(row_fill_kernel, dim3(r.nblk), dim3(256), 0, st, x, B, L, r.blk_sum, r.count, r.row_off, r.tok_slot, r.tok_id, r.tok_pos, r.sb_first, kSuperTok,
-                     r.tok_key, n_nodes, status, node_ids, node_cnt, node_zero);
+  if (packed)
+    hipLaunchKernelGGL(row_fill_kernel<true>, dim3(r.nblk), dim3(256), 0, st, x, B, L, r.blk_sum, r.count, r.row_off, r.tok_slot, r.tok_id, r.tok_pos, r.sb_first, kSuperTok,
+                       r.tok_key, n_nodes, status, node_ids, node_cnt, node_zero, r.cls_hist, r.sched, r.row_src, y, w, r.y_plan, r.w_plan);
+  else
+    hipLaunchKernelGGL(row_fill_kernel<false>, dim3(r.nblk), dim3(256), 0, st, x, B, L, r.blk_sum, r.count, r.row_off, r.tok_slot, r.tok_id, r.tok_pos, r.sb_first, kSuperTok,
+                       r.tok_key, n_nodes, status, node_ids, node_cnt, node_zero, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
   MATCHA_CHECK_LAUNCH("row_fill_kernel");
   if (level <= 0) return MATCHA_OK;
   const int first = level >= 2 ? 0 : 1;                // list 0: 64-row tiles, list 1: half tiles
