@@ -8,7 +8,8 @@ import pytest
 import torch
 
 from matcha_amd import _lib, walk as Wk
-from tests import walk_ref as WR
+from tests import sgns_cases as SC, walk_ref as WR
+from tests.fp64_grade import K, tensor_err
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -185,3 +186,149 @@ def test_sgns_twin_learns_and_orders_agree():
     for _ in range(3):
         a64 = WR.sgns(walks, a64[0], a64[1], noise.numpy(), **kw)
     assert WR.sgns_loss(a64[0], a64[1], pairs, neg) < WR.sgns_loss(syn0.numpy(), syn1.numpy(), pairs, neg) - 0.05
+
+
+# ---- the skip-gram cases of tests/sgns_cases.py: what the device comparisons of tests/test_hip_walk.py rest on, from the twin alone ----------
+def _unchanged(c, p, table, rows):
+    """Rows ``rows`` of table 0 (syn0) / 1 (syn1) are bit for bit the initial ones after pass p, in all three twins."""
+    first = (c.syn0, c.syn1)[table]
+    return all(np.array_equal(c.twins[k][p][table][rows], first[rows].astype(k[0])) for k in SC.DTYPES)
+
+
+@pytest.mark.parametrize("d", SC.WIDTHS)
+@pytest.mark.parametrize("name", ["A1", "A2"])
+def test_dead_flanks_add_exact_zeros_in_every_twin(name, d):
+    c = SC.case(name, d)
+    x, ctr, y = (c.walks[:, i] for i in range(3))
+    ids = set(c.walks.ravel().tolist())
+    before = (c.syn0, c.syn1)
+    for p, pairs in enumerate(c.trained):
+        assert len(pairs) == 32 and [r[1:3] for r in pairs[:4]] == [(0, 1), (1, 0), (1, 2), (2, 1)]     # two contexts for every middle
+        mid = [r for r in pairs if r[1] == 1]
+        if name == "A1":                                         # one launch: no two middles may meet in a row
+            drawn = sum((r[6] for r in mid), [])
+            assert len(drawn) == 80 and len(set(drawn)) == 80 and not set(drawn) & ids
+        else:                                                    # a launch per walk: a middle's own live draws are distinct rows
+            own = other = 0
+            for w in range(8):
+                drawn = sum((r[6] for r in mid if r[0] == w), [])
+                live = [t for t in drawn if t != ctr[w]]
+                assert len(drawn) == 10 and len(set(live)) == len(live) and not set(live) & (set(x.tolist()) | set(y.tolist()))
+                own += len(drawn) - len(live)
+                other += len(set(live) & set(ctr.tolist()))
+            print(f"{name} d={d}: {own} draws of the own centre, {other} of another walk's")
+            assert own >= 2 and other >= 8
+        # the flanks' margins hold on the tables the pass starts from and on those it leaves
+        after = c.twins[SC.DTYPES[0]][p]
+        for s0, s1 in (before, after):
+            pos, neg = SC.flank_margins(c.walks, s0, s1, pairs)
+            assert pos >= 40 and neg <= -100, (name, d, p, pos, neg)
+        before = after
+        assert _unchanged(c, p, 1, x) and _unchanged(c, p, 1, y) and _unchanged(c, p, 0, ctr)
+        assert _unchanged(c, p, 0, 0) and _unchanged(c, p, 1, 0)
+    # the middles did train: their centres' rows and every live draw moved in syn1, their contexts' rows in syn0
+    s0, s1 = c.twins[SC.DTYPES[1]][0]
+    moved0, moved1 = (np.flatnonzero((a != b).any(1)) for a, b in ((s0, c.syn0), (s1, c.syn1)))
+    assert sorted(moved0.tolist()) == sorted(x.tolist() + y.tolist())
+    live = {t for r in c.trained[0] if r[1] == 1 for t in r[6] if t != r[3]}
+    assert sorted(moved1.tolist()) == sorted(live | set(ctr.tolist())) and (name != "A1" or len(moved1) == 88)
+
+
+def test_wide_window_draws_from_the_slots_beside_the_window():
+    c = SC.case("B", 64)
+    pairs = c.trained[0]
+    drawn = sum((r[6] for r in pairs), [])
+    assert len(pairs) == 16 and len(drawn) == 80 and len(set(drawn)) == 80 and not set(drawn) & set(c.walks.ravel().tolist())
+    assert {r[5] for r in pairs} == {1, 2, 3, 4, 5}                                # every reduced window; the context is in reach of each
+    assert {r[2] - (r[1] - 5) for r in pairs} == {4, 6}                            # jj = window - 1, window + 1
+    _, slots = WR.draws(8, 2, 0, c.noise, 5, 5, c.kw["seed"])
+    assert all(slots[w * 2 + i, 1 + j - i].tolist() != ids for w, i, j, _, _, _, ids in pairs)   # window 1's slots (0, 2) hold other draws
+
+
+def test_clipped_pairs_train_by_the_window_draw_alone():
+    c = SC.case("C", 64)
+    W, Lw = c.walks.shape
+    valid = (c.walks >= 1) & (c.walks <= SC.N)
+    assert W >= 16 and Lw == 6 and (valid.sum(1) == 2).all() and len(set(c.walks[valid].tolist())) == 2 * W
+    assert {0, SC.N + 1} <= set(c.walks[~valid].tolist())
+    places = {(int(np.flatnonzero(v)[0]), int(np.diff(np.flatnonzero(v))[0])) for v in valid}
+    assert places == {(p, dist) for dist in (1, 2, 3) for p in (0, 5 - dist)} | {(2, 1), (1, 2), (1, 3)}     # start, mid-walk, end per dist
+    pairs = c.trained[0]
+    drawn = sum((r[6] for r in pairs), [])
+    assert len(set(drawn)) == len(drawn) == 5 * len(pairs) and not set(drawn) & set(c.walks[valid].tolist())
+    b_all, _ = WR.draws(W, Lw, 0, c.noise, 3, 5, c.kw["seed"])
+    took = {(w, i) for w, i, *_ in pairs}
+    idle = far = 0
+    for w in range(W):
+        p, q = np.flatnonzero(valid[w])
+        for i in (p, q):
+            assert ((w, i) in took) == (b_all[w * Lw + i] >= q - p)                # a position trains its partner iff b >= dist
+            idle += (w, i) not in took
+            far += (w, i) in took and q - p >= 2
+    print(f"C: {len(pairs)} positions train ({far} at distance 2 or 3), {idle} have their partner out of reach")
+    assert idle >= 2 and far >= 2 and idle + len(pairs) == 2 * W
+    # the twin met bad ids, as centres and as contexts, and left every row but the pairs' and their draws' alone
+    bad = []
+    got = WR.sgns(c.walks, c.syn0, c.syn1, c.noise, n_nodes=SC.N, bad=bad, **c.kw)
+    assert all(np.array_equal(a, b) for a, b in zip(got, c.twins[SC.DTYPES[0]][0]))
+    assert any(i == j for _, i, j in bad) and any(i != j for _, i, j in bad)
+    rows0, rows1 = ({r[k] for r in pairs} for k in (4, 3))
+    for k in SC.DTYPES[1:]:
+        s0, s1 = c.twins[k][0]
+        assert set(np.flatnonzero((s0 != c.syn0).any(1)).tolist()) == rows0
+        assert set(np.flatnonzero((s1 != c.syn1).any(1)).tolist()) == rows1 | set(drawn)
+
+
+def _position_loop(c, mutant=None):
+    """A float64 copy of the skip-gram position (the rule at the top of csrc/sgns.hip) over the case's passes, exact or with one branch
+    broken -- the mutants the cases are there to catch: ``nocarry`` (a later context reads the centre's row as it was before the first),
+    ``noreset`` (neu runs on from context to context), ``noskip`` (a draw of the centre itself is trained), ``jj_from_b`` (the negatives'
+    slot counted from the reduced window)."""
+    W, Lw = c.walks.shape
+    kw = c.kw
+    s0, s1 = c.syn0.astype(np.float64), c.syn1.astype(np.float64)
+    for ep in c.epochs_run:
+        g_base, g_total = ep * W * Lw, kw["epochs"] * W * Lw
+        b_all, neg_all = WR.draws(W, Lw, g_base, c.noise, kw["window"], kw["negative"], kw["seed"])
+        for w in range(W):
+            for i in range(Lw):
+                centre, g = int(c.walks[w, i]), g_base + w * Lw + i
+                if c.n_nodes is not None and not 1 <= centre <= c.n_nodes:
+                    continue
+                lr = float(np.float32(max(kw["lr1"], kw["lr0"] - (kw["lr0"] - kw["lr1"]) * float(g) / float(g_total))))
+                b = int(b_all[g - g_base])
+                u0 = s1[centre].copy()
+                u, neu = u0.copy(), np.zeros_like(u0)
+                for j in range(max(0, i - b), min(Lw - 1, i + b) + 1):
+                    ctx = int(c.walks[w, j])
+                    if j == i or (c.n_nodes is not None and not 1 <= ctx <= c.n_nodes):
+                        continue
+                    v = s0[ctx].copy()
+                    seen = u0 if mutant == "nocarry" else u
+                    gt = (1.0 - 1.0 / (1.0 + np.exp(-(v @ seen)))) * lr
+                    neu = gt * seen + (neu if mutant == "noreset" else 0.0)
+                    u = u + gt * v
+                    for t_id in neg_all[g - g_base, j - (i - (b if mutant == "jj_from_b" else kw["window"]))].tolist():
+                        if t_id == centre and mutant != "noskip":
+                            continue
+                        t = s1[t_id].copy()
+                        gt = (0.0 - 1.0 / (1.0 + np.exp(-(v @ t)))) * lr
+                        neu = neu + gt * t
+                        s1[t_id] = t + gt * v
+                    s0[ctx] = s0[ctx] + neu
+                s1[centre] = s1[centre] + (u - u0)
+    return s0, s1
+
+
+@pytest.mark.parametrize("mutant,name", [(None, "A1"), (None, "A2"), (None, "B"), (None, "C"), ("nocarry", "A1"), ("noreset", "A1"),
+                                         ("noskip", "A2"), ("jj_from_b", "B"), ("jj_from_b", "C")])
+def test_the_cases_tell_a_broken_position_from_the_twin(mutant, name):
+    """The grade of tests/test_hip_walk.py (e <= K max(e(R32 seq), e(R32 tree), 2^-23) against the float64 twin) passes the exact position
+    loop and misses each mutant by a factor of 10 at least on some table of the case meant for it: a condition on the inputs."""
+    c = SC.case(name, 64)
+    ratios = [tensor_err(g[:, c.cols], r[:, c.cols]) / n for g, r, n in zip(_position_loop(c, mutant), c.twins[SC.DTYPES[0]][-1], SC.noise_floor(c))]
+    print(f"{name} {mutant}: e / noise syn0 {ratios[0]:.3g}, syn1 {ratios[1]:.3g}")
+    if mutant is None:
+        assert max(ratios) < K
+    else:
+        assert max(ratios) >= 10 * K

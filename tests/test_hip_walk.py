@@ -1,8 +1,9 @@
 """The hypergraph walk and the skip-gram pass on the device: hyper_walk_kernel bit for bit against the numpy twin
 (tests/walk_ref.py; what the twin samples is held to the reference in tests/test_cpu_walk.py); sgns_kernel against the sequential twin where
 no two positions meet in a row, at fp32 grade (the form of tests/fp64_grade.py: e <= 8 max(e(R32 seq), e(R32 tree), 2^-23) against the
-float64 twin), and on a planted graph by what it learns; the chain walk_embeddings -> train.run(table_init="walk") and the CLI's two files.
-GPU only (-m gpu)."""
+float64 twin) -- one context per position on walks of length 2, and on the inputs of tests/sgns_cases.py several contexts, a window above
+1, draws of the centre, bad ids in reach and one walk per launch -- and on a planted graph by what it learns; the chain
+walk_embeddings -> train.run(table_init="walk") and the CLI's two files.  GPU only (-m gpu)."""
 import os
 
 import numpy as np
@@ -10,7 +11,7 @@ import pytest
 import torch
 
 from matcha_amd import _lib, walk as Wk
-from tests import walk_ref as WR
+from tests import sgns_cases as SC, walk_ref as WR
 from tests.fp64_grade import K, ULP, tensor_err
 
 pytestmark = pytest.mark.gpu
@@ -137,12 +138,18 @@ def _tables(d, seed=0):
     return (rng.uniform(-0.5, 0.5, size=(RF_N + 1, d)).astype(np.float32), rng.uniform(-0.5, 0.5, size=(RF_N + 1, d)).astype(np.float32))
 
 
-def _grade(label, got, r64, r32a, r32b):
+def _grade(label, got, r64, r32a, r32b, cols=None):
+    """``cols`` (a mask): the error and max|r| over those columns only.  Returns the worst e / noise."""
+    worst = 0.0
     for name, g, a, b, c in zip(("syn0", "syn1"), got, r64, r32a, r32b):
+        if cols is not None:
+            g, a, b, c = (t[:, cols] for t in (g, a, b, c))
         noise = max(tensor_err(b, a), tensor_err(c, a), ULP)
         err = tensor_err(g, a)
         print(f"{label} {name}: e {err:.2e}, noise {noise:.2e}, ratio {err / noise:.2f}")
         assert err <= K * noise, (label, name, err, noise)
+        worst = max(worst, err / noise)
+    return worst
 
 
 @pytest.mark.parametrize("d", [64, 128, 256])
@@ -202,6 +209,78 @@ def test_sgns_edge_forms(race_free):
     bad = torch.tensor([[3, RF_N + 1], [0, 4]], dtype=torch.int32).cuda()
     st = Wk.sgns_epoch(bad, g0, g1, nt, window=1, negative=0, seed=2)
     assert int(st[0]) & _lib.STATUS_BAD_ID and np.array_equal(g0.cpu().numpy(), s0) and np.array_equal(g1.cpu().numpy(), s1)
+
+
+def _run_case(c, chunk_walks):
+    """The case's passes on the device, on copies of its tables: per pass (syn0, syn1, the status words, the launches of sgns_kernel)."""
+    wt, nt = torch.from_numpy(c.walks.copy()).cuda(), torch.from_numpy(c.noise.copy()).cuda()
+    g0, g1 = torch.from_numpy(c.syn0.copy()).cuda(), torch.from_numpy(c.syn1.copy()).cuda()
+    out = []
+    for ep in c.epochs_run:
+        with _lib.launch_log() as log:
+            st = Wk.sgns_epoch(wt, g0, g1, nt, epoch=ep, chunk_walks=chunk_walks, **c.kw)
+            torch.cuda.synchronize()
+        out.append((g0.cpu().numpy(), g1.cpu().numpy(), st.tolist(), log.counts.get("sgns_kernel")))
+    return out
+
+
+def _check_case(c, passes):
+    """Every pass at fp32 grade against the case's twins over its columns; the rows both float32 twins leave as they were (every column
+    of them) are bit for bit as they were on the device."""
+    worst = 0.0
+    for p, (g0, g1, _, _) in enumerate(passes):
+        r64, r32a, r32b = (c.twins[k][p] for k in SC.DTYPES)
+        worst = max(worst, _grade(f"{c.name} d={c.d} pass {c.epochs_run[p]}", (g0, g1), r64, r32a, r32b, c.cols))
+        for got, first, a, b in zip((g0, g1), (c.syn0, c.syn1), r32a, r32b):
+            still = ~((a != first).any(1) | (b != first).any(1))
+            assert still[0] and still.sum() >= SC.N - 200
+            assert np.array_equal(got[still].view(np.uint32), first[still].view(np.uint32)), (c.name, c.d, p)
+            assert ((got != first).any(1) == ~still).all()       # and every row the twins move moved
+    print(f"{c.name} d={c.d}: worst e / noise {worst:.2f}")
+
+
+@pytest.mark.parametrize("d", SC.WIDTHS)
+def test_sgns_two_contexts_per_position_match_the_twin(d):
+    """A1 (tests/sgns_cases.py): walks [x, c, y] whose flanks add exact zeros, all 24 positions in ONE launch, two passes: the carry of
+    u from the first context to the second and the restart of neu, against the sequential twin."""
+    c = SC.case("A1", d)
+    passes = _run_case(c, chunk_walks=8)
+    assert all(st == [0, 0, 0, 0] and launches == 1 for _, _, st, launches in passes)
+    _check_case(c, passes)
+
+
+@pytest.mark.parametrize("d", SC.WIDTHS)
+def test_sgns_skips_its_own_centre_and_numbers_positions_across_launches(d):
+    """A2: the same walks one per launch with the centres in the noise table, pass 1 of 4: a draw of the position's own centre is skipped,
+    another walk's centre is a live row of an earlier or later launch, and g (the learning rate, the random stream) counts from the
+    epoch's base plus the walk's offset in every launch."""
+    c = SC.case("A2", d)
+    passes = _run_case(c, chunk_walks=1)
+    assert all(st == [0, 0, 0, 0] and launches == len(c.walks) == 8 for _, _, st, launches in passes)
+    _check_case(c, passes)
+
+
+@pytest.mark.parametrize("d", SC.WIDTHS)
+def test_sgns_wide_window_draws_the_twins_negatives(d):
+    """B: window 5 over walks of length 2 -- the negatives' slot jj = j - (i - window) -- in one launch, and bit for bit the same in
+    launches of 3 walks (no two positions share a row, so chunking may not change a bit)."""
+    c = SC.case("B", d)
+    passes = _run_case(c, chunk_walks=8)
+    assert all(st == [0, 0, 0, 0] and launches == 1 for _, _, st, launches in passes)
+    _check_case(c, passes)
+    (h0, h1, st, launches), = _run_case(c, chunk_walks=3)
+    assert st == [0, 0, 0, 0] and launches == 3
+    assert np.array_equal(h0.view(np.uint32), passes[0][0].view(np.uint32)) and np.array_equal(h1.view(np.uint32), passes[0][1].view(np.uint32))
+
+
+@pytest.mark.parametrize("d", SC.WIDTHS)
+def test_sgns_window_draw_clipping_and_bad_ids_among_the_contexts(d):
+    """C: two valid ids per walk of 6 at distance 1 .. 3, at the walk's start, middle and end, among slots holding 0 and N + 1, window 3:
+    a position trains its partner iff its drawn b reaches it, skips the bad slots in reach, and the call is flagged with nothing else."""
+    c = SC.case("C", d)
+    passes = _run_case(c, chunk_walks=len(c.walks))
+    assert all(st == [_lib.STATUS_BAD_ID, 0, 0, 0] and launches == 1 for _, _, st, launches in passes)
+    _check_case(c, passes)
 
 
 @pytest.fixture(scope="module")

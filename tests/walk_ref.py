@@ -136,11 +136,13 @@ def draws(W, Lw, g_base, noise_cum, window, negative, seed):
     return b, ids
 
 
+@np.errstate(over="ignore")                             # exp(-f) of a dot product below -88 is +inf in float32, as expf's is: sigmoid 0
 def sgns(walks_arr, syn0, syn1, noise_cum, window=10, negative=5, lr0=0.025, lr1=1e-4, epoch=0, epochs=1, seed=0, dtype=np.float64,
-         order="seq", drawn=None):
+         order="seq", drawn=None, n_nodes=None, bad=None):
     """One pass over ``walks_arr`` [W, Lw] in sequence, on copies: returns (syn0, syn1) in ``dtype``.  ``drawn`` (a list) collects every
     negative id drawn.  (float64 takes a context's targets in one matrix product where its negatives are distinct: the same arithmetic,
-    a target's update touches only its own row.)"""
+    a target's update touches only its own row.)  ``n_nodes``: the kernel's rule for ids outside 1 .. n_nodes -- such a centre trains
+    nothing, such a context is skipped, and ``bad`` (a list) collects the (w, i, j) at which one was met (j = i for a centre)."""
     walks_arr = np.asarray(walks_arr)
     W, Lw = walks_arr.shape
     s0, s1 = np.array(syn0, dtype=dtype), np.array(syn1, dtype=dtype)
@@ -150,6 +152,10 @@ def sgns(walks_arr, syn0, syn1, noise_cum, window=10, negative=5, lr0=0.025, lr1
     for w in range(W):
         for i in range(Lw):
             center = int(walks_arr[w, i])
+            if n_nodes is not None and not 1 <= center <= n_nodes:
+                if bad is not None:
+                    bad.append((w, i, i))
+                continue
             g = g_base + w * Lw + i
             lr = dtype(np.float32(max(lr1, lr0 - (lr0 - lr1) * float(g) / float(g_total))))
             u = s1[center].copy()
@@ -159,6 +165,10 @@ def sgns(walks_arr, syn0, syn1, noise_cum, window=10, negative=5, lr0=0.025, lr1
                 if j == i:
                     continue
                 ctx = int(walks_arr[w, j])
+                if n_nodes is not None and not 1 <= ctx <= n_nodes:
+                    if bad is not None:
+                        bad.append((w, i, j))
+                    continue
                 v = s0[ctx].copy()
                 f = _dot(v, u, dtype, order)
                 gt = dtype((one - one / (one + np.exp(-dtype(f)))) * lr)
